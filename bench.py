@@ -171,6 +171,25 @@ def emit(out):
     sys.stdout.flush()
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """Write each array as d/<name>.npy in float64.  When the data exceed DUMP_MAX_BYTES in all (less 1 MB for the
+    headers), every array is cut to the same share of its elements, a sample drawn with a fixed seed (flattened,
+    positions sorted), so that two builds given the same arguments are compared element for element."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    budget = (DUMP_MAX_BYTES - (1 << 20)) // 8
+    total = sum(a.size for a in arrays.values())
+    for k, a in arrays.items():
+        if total > budget:
+            keep = max(1, a.size * budget // total)
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def makespan_fields(names, rec):
     """Scaling ceiling visible from one GPU: with the LPs spread over 8 GPUs the wall cannot go below the slowest single LP
     (seconds as measured here, under this run's contention)."""
@@ -490,6 +509,7 @@ def run_netlib(names, probs, flops, dev, dist=None, red_dev="cuda", store=None, 
 def netlib_main(args):
     """Batched-LP mode (BASELINE.json configs[3]): the Netlib fixtures sharded over the ranks (self-scheduled from a
     shared counter, or a static LPT partition), a single RCCL all-gather of the statistics records at the end."""
+    import numpy as np
     import torch
     from interiorpointmethod_amd import batch
 
@@ -509,6 +529,9 @@ def netlib_main(args):
     rec, elapsed = run_netlib(names, probs, flops, dev, dist=dist, red_dev=red_dev, store=store, workers=args.workers,
                               schedule=args.schedule, start=args.start, regularize=args.regularize, general=general)
     if rank == 0:
+        if args.dump_outputs:
+            by_lp = rec[np.argsort(rec[:, 0])]
+            dump_outputs(args.dump_outputs, {"status": by_lp[:, 1], "iterations": by_lp[:, 2], "objective": by_lp[:, 3]})
         summ = batch.summarize(rec)
         sched = "one rank" if dist is None else ("self-scheduled from a shared counter (TCPStore)"
                                                  if (args.schedule == "dynamic" and store is not None) else "static LPT partition")
@@ -562,7 +585,13 @@ def main():
                     help="netlib: start point; reference = x=s=y=1 (sparse_interior.py:193-200, parity mode), mehrotra = "
                          "Mehrotra's least-squares start (optional mode, not the reference's algorithm)")
     ap.add_argument("--regularize", type=float, default=0.0, help="netlib: Tikhonov shift (0 = reference-faithful)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float64, at most 64 MB in all): dense = the iterate x, y, s and the step's statistics; "
+                         "netlib = status, iterations and objective of every LP in suite order")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.workload == "netlib":
         return netlib_main(args)
 
@@ -585,7 +614,7 @@ def main():
 
     def run(steps, profile=0):
         sv.set_profiling(profile)
-        done, total_ms = 0, 0.0
+        done, total_ms, st = 0, 0.0, None
         form_ms = factor_ms = tri_ms = other_ms = 0.0
         while done < steps:
             k = min(RESET_EVERY, steps - done)
@@ -615,6 +644,11 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # read back before the untimed passes below reset the iterate; solve_ms is a timing, not a result
+        x, y, s = sv.get_state()
+        dump_outputs(args.dump_outputs, dict({"x": x, "y": y, "s": s},
+                                             **{k: v for k, v in st.items() if k != "solve_ms"}))
 
     # phase breakdown from a separate, untimed pass (nine event records per step cost ~1 %)
     _, phases_all, _ = run(min(args.steps, RESET_EVERY), profile=2)

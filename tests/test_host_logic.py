@@ -227,3 +227,26 @@ def test_lockstep_rule_is_the_same_on_every_rank():
     assert not batch.lockstep_wanted(many, world=2, workers=8, mode="auto")       # half of them per rank
     assert not batch.lockstep_wanted(many, world=1, workers=1, mode="auto")       # nothing to overlap
     assert batch.lockstep_wanted(few, world=1, workers=8, mode=True) and not batch.lockstep_wanted(many, world=1, workers=8, mode=False)
+
+
+def test_bench_dump_outputs_float64_capped_and_seeded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array lands as DIR/<name>.npy in float64; over the size cap each is cut to the
+    same seeded sample of its elements, so two runs (two builds) write the same positions."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    x = np.arange(10, dtype=np.float32).reshape(-1, 1)
+    bench.dump_outputs(str(tmp_path / "small"), {"x": x, "iterations": 7})
+    got = np.load(tmp_path / "small" / "x.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, x.astype(np.float64))
+    assert np.load(tmp_path / "small" / "iterations.npy") == 7.0
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", (1 << 20) + 8 * 1000)       # room for 1000 values besides the headers
+    big = {"a": np.arange(3000.0), "b": -np.arange(1000.0)}
+    for d in ("r1", "r2"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    a1, b1 = np.load(tmp_path / "r1" / "a.npy"), np.load(tmp_path / "r1" / "b.npy")
+    assert a1.size + b1.size <= 1000 and a1.size == 750 and b1.size == 250
+    assert np.all(np.diff(a1) > 0) and np.all(np.isin(a1, big["a"]))          # positions sorted, values taken as they are
+    assert np.array_equal(a1, np.load(tmp_path / "r2" / "a.npy")) and np.array_equal(b1, np.load(tmp_path / "r2" / "b.npy"))
