@@ -39,7 +39,8 @@ enum {
     IPM_ERR_NO_DEVICE = -3,
     IPM_ERR_WORKSPACE = -4,    /* caller workspace too small / misaligned */
     IPM_ERR_STATE = -5,        /* call order violated (e.g. solve before set_A) */
-    IPM_ERR_INVALID_INPUT = -6 /* non-finite entries in A, b or c (8 Netlib files) */
+    IPM_ERR_INVALID_INPUT = -6, /* non-finite entries in A, b or c (8 Netlib files) */
+    IPM_ERR_SINGULAR = -7      /* ipm_lu_solve / ipm_lu_factor: an exactly zero pivot (info > 0) */
 };
 
 /* solver status written to ipm_stats.status (reference semantics in comments) */
@@ -255,6 +256,20 @@ int ipm_get_factor_info(ipm_handle* h, int64_t out[8]);
  * z may alias rhs.  pivots_fixed may be NULL. */
 int ipm_solve_linear(ipm_handle* h, const double* B, int64_t ldb, const double* rhs, double* z,
                      int32_t* pivots_fixed);
+/* The GENERAL-matrix seam (ipm_solve_linear above stays the SPD one): solve A X = B for any square n x n A by LU with partial
+ * pivoting on the device (csrc/getrf_f64.h; LAPACK gesv, what the reference's np.linalg.solve does, main.py:178).  This is how the
+ * reference's unreduced KKT system [[0, A^T, I], [A, 0, 0], [S, 0, X]] (main.py:13-21, zero diagonal block) is solved.  No handle:
+ * the call allocates its own device memory and stream on `device` and frees both before it returns.  A (lda >= n), B and X
+ * (nrhs columns, ldb / ldx >= nrhs) are row-major HOST arrays; X may alias B.  *info: 0, or j + 1 for the first exactly zero pivot
+ * U[j][j] (then IPM_ERR_SINGULAR and X is not written).  NaN / Inf in A or B: IPM_ERR_INVALID_INPUT; bad sizes or leading
+ * dimensions: IPM_ERR_INVALID_ARG; device memory not available: IPM_ERR_WORKSPACE.  Bitwise repeatable. */
+int ipm_lu_solve(int device, int64_t n, const double* A, int64_t lda, int64_t nrhs, const double* B, int64_t ldb,
+                 double* X, int64_t ldx, int64_t* info);
+/* The factorization alone: P A = L U with the packed factors (unit L below the diagonal, U on and above it) written to host LU
+ * (ldlu >= n) and the interchanges to ipiv (0-based: row i was swapped with row ipiv[i], in order; scipy.linalg.lu_factor's
+ * convention).  info and errors as ipm_lu_solve; with IPM_ERR_SINGULAR the factors are still written. */
+int ipm_lu_factor(int device, int64_t n, const double* A, int64_t lda, double* LU, int64_t ldlu, int32_t* ipiv,
+                  int64_t* info);
 /* Solve (A diag(d) A^T) z = rhs with the handle's own A: forms the normal matrix on the device (d on the host,
  * length n; NULL = all ones), factors it with the guarded blocked Cholesky (reuse_factor != 0: the factor of the
  * previous ipm_normal_solve / direction call is kept) and back-substitutes.  rhs, z: host, length m; z may alias

@@ -18,7 +18,7 @@ EXPORTS = [
     "ipm_abi_version", "ipm_device_count", "ipm_default_options", "ipm_workspace_bytes", "ipm_workspace_bytes_csc", "ipm_workspace_bytes_opts",
     "ipm_create", "ipm_destroy", "ipm_last_error", "ipm_set_A_dense", "ipm_set_A_csc",
     "ipm_set_bc", "ipm_set_state", "ipm_get_state", "ipm_init_state", "ipm_newton_direction",
-    "ipm_iterate", "ipm_solve", "ipm_solve_batch", "ipm_batch_create", "ipm_batch_destroy", "ipm_batch_last_error", "ipm_batch_add", "ipm_batch_step", "ipm_batch_stats", "ipm_get_history", "ipm_get_schedule", "ipm_order_rows", "ipm_get_factor_info", "ipm_solve_linear", "ipm_normal_solve", "ipm_form_normal_matrix", "ipm_get_factor",
+    "ipm_iterate", "ipm_solve", "ipm_solve_batch", "ipm_batch_create", "ipm_batch_destroy", "ipm_batch_last_error", "ipm_batch_add", "ipm_batch_step", "ipm_batch_stats", "ipm_get_history", "ipm_get_schedule", "ipm_order_rows", "ipm_get_factor_info", "ipm_solve_linear", "ipm_lu_solve", "ipm_lu_factor", "ipm_normal_solve", "ipm_form_normal_matrix", "ipm_get_factor",
     "ipm_set_profiling", "ipm_get_phase_ms", "ipm_debug_get_stamps", "ipm_debug_ff_schedule", "ipm_debug_ff_trace", "ipm_debug_get_block_inverse", "ipm_debug_ls_merge",
 ]
 
@@ -33,6 +33,7 @@ ERR_WORKSPACE = -4
 ABI_VERSION = 4
 HISTORY_CAPACITY = 1024         # IPM_HISTORY_CAPACITY
 ERR_INVALID_INPUT = -6
+ERR_SINGULAR = -7               # include/ipm_hip.h: IPM_ERR_SINGULAR (ipm_lu_solve / ipm_lu_factor, info > 0)
 
 
 class IpmLibraryError(RuntimeError):
@@ -135,6 +136,8 @@ def load():
     lib.ipm_order_rows.argtypes = [i64, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), pd]
     lib.ipm_get_factor_info.argtypes = [vp, C.POINTER(i64)]
     lib.ipm_solve_linear.argtypes = [vp, pd, i64, pd, pd, C.POINTER(i32)]
+    lib.ipm_lu_solve.argtypes = [C.c_int, i64, pd, i64, i64, pd, i64, pd, i64, C.POINTER(i64)]
+    lib.ipm_lu_factor.argtypes = [C.c_int, i64, pd, i64, pd, i64, C.POINTER(i32), C.POINTER(i64)]
     lib.ipm_normal_solve.argtypes = [vp, pd, pd, pd, C.c_int, C.POINTER(i32)]
     lib.ipm_form_normal_matrix.argtypes = [vp, pd, pd, i64]
     lib.ipm_get_factor.argtypes = [vp, pd, i64]
