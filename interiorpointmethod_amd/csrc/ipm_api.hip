@@ -2895,11 +2895,19 @@ static int lu_nb() {
 
 template <int NB>
 static int lu_factor_device(LuRun& R, double* a, int64_t np, int n, LuState* st, int* ipiv, double* ut) {
-    static std::atomic<bool> attr_set[MAX_DEVICES];
-    if (!attr_set[R.device].exchange(true)) {
-        LU_TRY(hipFuncSetAttribute((const void*)lu_trsm_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, NB * NB * 8));
-        LU_TRY(hipFuncSetAttribute((const void*)lu_trsv_step_kernel<NB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (NB * NB + NB * LU_RC) * 8));
-        LU_TRY(hipFuncSetAttribute((const void*)lu_trsv_step_kernel<NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (NB * NB + NB * LU_RC) * 8));
+    // The dynamic-LDS limits of this width's kernels, once per device.  Under the mutex, so no thread launches them before the
+    // thread that sets the attributes has finished (an exchange-first flag let a second thread through early); a failed
+    // attempt leaves the flag clear for the next call.
+    static std::mutex attr_mu;
+    static bool attr_set[MAX_DEVICES];
+    {
+        std::lock_guard<std::mutex> lk(attr_mu);
+        if (!attr_set[R.device]) {
+            LU_TRY(hipFuncSetAttribute((const void*)lu_trsm_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, NB * NB * 8));
+            LU_TRY(hipFuncSetAttribute((const void*)lu_trsv_step_kernel<NB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (NB * NB + NB * LU_RC) * 8));
+            LU_TRY(hipFuncSetAttribute((const void*)lu_trsv_step_kernel<NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (NB * NB + NB * LU_RC) * 8));
+            attr_set[R.device] = true;
+        }
     }
     const int npi = (int)np;
     for (int k = 0; k < npi; k += NB) {
