@@ -398,6 +398,7 @@ __device__ __forceinline__ void ff_chain_role(const FFChain& c, double* lds) {
         a.trace = c.trace ? c.trace + 12 * (size_t)k : nullptr;
         const int real = c.m - k * NB;                       // 16-wide panels that hold rows of the LP (potrf_panels of the host)
         a.nt = (c.shift_rel != 0.0 || real >= NB) ? NB / 16 : (real + 15) / 16 < 1 ? 1 : (real + 15) / 16;
+        a.rows = real;
         potrf_diag_body<false>(a, W, dinv_s);
         __syncthreads();
     }

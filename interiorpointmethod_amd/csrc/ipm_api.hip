@@ -1406,6 +1406,7 @@ static int enqueue_factor(ipm_handle* h, bool use_env = false, int mid_step = -1
         pd.wait_on = nullptr; pd.wait_count = 0; pd.signal = nullptr; pd.timeout = nullptr; pd.dbg = nullptr; pd.dbg_tag = 0;
         pd.trace = nullptr;
         pd.nt = potrf_panels(h, k);
+        pd.rows = (int)(h->m - (int64_t)k * NB);
         if (h->stamp_buf && k == 0) {
             pd.stamps = h->stamp_buf;
             if (getenv("IPM_POTRF_SKIP")) pd.dbg_tag = (unsigned)atoi(getenv("IPM_POTRF_SKIP"));
@@ -1736,6 +1737,7 @@ static int enqueue_form_factor(ipm_handle* h, hipEvent_t* ev, int mid_step, int 
         pd.wait_on = dready + k; pd.wait_count = 10; pd.signal = potrfdone + k; pd.timeout = timeout; pd.dbg = dbg; pd.dbg_tag = (unsigned)k;
         pd.trace = ctrace ? ctrace + 12 * (size_t)k : nullptr;
         pd.nt = potrf_panels(h, k);
+        pd.rows = (int)(h->m - (int64_t)k * NB);
         hipLaunchKernelGGL(potrf_diag_kernel<false>, dim3(1), dim3(PD_THREADS), 0, sm, pd);
         ++h->n_counter_steps;
         if (k == ginv_step) {

@@ -53,6 +53,7 @@ struct PotrfDiag {
     unsigned* dbg; unsigned dbg_tag;   // diagnostic (may be null): see GemmNT::dbg; kind 7
     int nt;                            // 16-wide panels to factor (1 .. 8): the rows from 16 nt on are PADDING rows (unit diagonal, nothing else):
                                        // L and inv(L) are the identity there, exactly what factoring them gives, without the pivots
+    int rows;                          // rows of the block that are rows of the matrix (m - 128 k, may exceed NB): the guard skips the rest
     long long* trace;                  // diagnostic (may be null): wall_clock64 at {start, inputs ready, done}
 };
 
@@ -113,7 +114,9 @@ __device__ __forceinline__ double row_bcast(double v, int k) {
 // About 25 instructions per pivot instead of ~65 for the one-lane-per-row / v_readlane form.
 // `pre` (optional): the tile already sits in registers in exactly this layout -- the MFMA accumulator of the update that
 // produced it (register a of lane l is row (l>>4)+4a, column l&15) -- and the LDS round trip is skipped.
-__device__ __forceinline__ int factor_tile(double* W, int c0, int lane, double thresh, double big, double* dinv_s,
+// lim: rows of the block that are rows of the matrix; a pivot at or beyond it is a PADDING row (unit diagonal) and is never
+// guarded -- once max diag(B) passes 1/eps the threshold passes 1, and those pivots were guarded and counted.
+__device__ __forceinline__ int factor_tile(double* W, int c0, int lane, double thresh, double big, int lim, double* dinv_s,
                                            const f64x4* pre = nullptr) {
     const int q = lane >> 4, c = lane & 15;
     double t[4];
@@ -129,7 +132,7 @@ __device__ __forceinline__ int factor_tile(double* W, int c0, int lane, double t
     for (int j = 0; j < 16; ++j) {
         const int ja = j >> 2, jq = j & 3;
         double p = readlane_f64(t[ja], 16 * jq + j);         // wave-uniform pivot
-        if (!(p > thresh)) { p = big; ++nfix; if (lane == 16 * jq + j) t[ja] = big; }
+        if (!(p > thresh) && c0 + j < lim) { p = big; ++nfix; if (lane == 16 * jq + j) t[ja] = big; }
         double rownext = 0.0, mnext = 0.0;
         if (j + 1 < 16) {
             const int na = (j + 1) >> 2, nq = (j + 1) & 3;
@@ -327,14 +330,14 @@ struct NoEarlyWork {
 
 // tile0_done: the caller has factored tile (0,0) itself (factor_tile with `pre`) and every wave has passed a barrier since.
 template <bool STAMP, typename Early = NoEarlyWork>
-__device__ __forceinline__ int potrf_lds(double* W, double* dinv_s, int nt, double thresh, double big, long long* stamps,
+__device__ __forceinline__ int potrf_lds(double* W, double* dinv_s, int nt, double thresh, double big, int lim, long long* stamps,
                                          Early early = Early(), bool tile0_done = false) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fk = lane >> 4;
     int nfix = 0;
     if (!tile0_done) {
-        if (wave == 0) nfix += factor_tile(W, 0, lane, thresh, big, dinv_s);
+        if (wave == 0) nfix += factor_tile(W, 0, lane, thresh, big, lim, dinv_s);
         IPM_STAMP(2);
         __syncthreads();
     }
@@ -365,7 +368,7 @@ __device__ __forceinline__ int potrf_lds(double* W, double* dinv_s, int nt, doub
         IPM_STAMP(5 + jb * 4);
         if (wave == 0 && nrt > 0) {
             const f64x4 nxt = update_tile_regs(W, c0, c0 + 16, c0 + 16, fr, fk);     // stays in registers
-            nfix += factor_tile(W, c0 + 16, lane, thresh, big, dinv_s, &nxt);
+            nfix += factor_tile(W, c0 + 16, lane, thresh, big, lim, dinv_s, &nxt);
         } else {
             // items: update tiles 1..ntile-1 of panel jb, then tiles 0..jb-2 of inverse row jb-1.
             // Wave 7 only inverts tile jb (about as long as wave 0's factorization) while a pivot tile is
@@ -486,7 +489,7 @@ __device__ __forceinline__ void potrf_diag_body(const PotrfDiag& a, double* W, d
 #pragma unroll
                 for (int q = 0; q < 4; ++q) if ((lane >> 4) + 4 * q == (lane & 15)) t0[q] += a.shift_rel * (*a.maxdiag);
             }
-            nfix = factor_tile(W, 0, lane, thresh, a.big, dinv_s, &t0);
+            nfix = factor_tile(W, 0, lane, thresh, a.big, a.rows, dinv_s, &t0);
         }
 #pragma unroll
         for (int u = 0; u < 14; ++u) {
@@ -631,7 +634,7 @@ __device__ __forceinline__ void potrf_diag_body(const PotrfDiag& a, double* W, d
         }
     };
     const Hooks hooks{a, W, nt, lane, STAMP ? a.dbg_tag : 0u};      // (skip: timing experiments of the diagnostic build)
-    nfix += potrf_lds<STAMP>(W, dinv_s, nt, thresh, a.big, stamps, hooks, /*tile0_done=*/true);
+    nfix += potrf_lds<STAMP>(W, dinv_s, nt, thresh, a.big, a.rows, stamps, hooks, /*tile0_done=*/true);
     hooks.end(wave);
     IPM_STAMP(40);
     if (lane == 0 && wave == 0 && nfix) atomicAdd(a.fixed, nfix);

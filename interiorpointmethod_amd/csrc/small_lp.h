@@ -211,7 +211,7 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) {
         }
         if (a.shift_rel != 0.0 && tid < mt) W[tid * WLD + tid] += a.shift_rel * mx[0];
         __syncthreads();
-        const int nfix = potrf_lds<false>(W, dinv_s, nt, a.eps * mx[0], a.big, nullptr);
+        const int nfix = potrf_lds<false>(W, dinv_s, nt, a.eps * mx[0], a.big, m, nullptr);
         if (tid == 0) {
             sc->maxdiag = mx[0];
             const int fx = sc->fixed + nfix;
