@@ -131,9 +131,9 @@ struct ipm_handle {
     // IPM_FF_MAX_NBLK / IPM_FUSED_FACTOR=force|0 override.
     int ff_min_nblk = 16, ff_max_nblk = 72;
     bool ff_forced = false;
-    int ff_chain_mode = 1;                // FFModel::chain_mode (IPM_FF_CHAIN_MODE): 1 = the pivot chain as roles of the ONE persistent launch (default), 0 = three launches per step on a second stream beside 7/8 of the CUs
+    int ff_chain_mode = 1;                // FFModel::chain_mode: 1 = the pivot chain as roles of the ONE persistent launch; 0 (three launches per step on a second stream beside 7/8 of the CUs) is refused by ipm_create
     int ff_q = 4;                         // formation chunks per tile (IPM_FF_Q)
-    int ff_workers = 0;                   // WORKER workgroups of the persistent launch (IPM_FF_WORKERS; default: 7/8 of the CUs, see ff_build)
+    int ff_workers = 0;                   // WORKER workgroups of the persistent launch (set by ff_build from the CU count, no switch)
     int* d_ff_tile_items = nullptr;       // [tile_items | tile_q]
     int ff_qmax = 16;                     // slab capacity per tile (the first block rows are formed in more, shorter chunks)
     bool ff_built = false, ff_last = false;
@@ -539,7 +539,16 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     CREATE_TRY(hipEventCreateWithFlags(&h->ev_last, hipEventDisableTiming));
     if (const char* e = getenv("IPM_FUSED_FACTOR")) { if (!strcmp(e, "force")) { h->ff_enabled = 1; h->ff_min_nblk = 3; h->ff_forced = true; } else h->ff_enabled = atoi(e); }
     if (const char* e = getenv("IPM_FF_MAX_NBLK")) h->ff_max_nblk = atoi(e);
-    if (const char* e = getenv("IPM_FF_CHAIN_MODE")) h->ff_chain_mode = atoi(e) != 0;
+    if (const char* e = getenv("IPM_FF_CHAIN_MODE")) {
+        // chain_mode 0 (round 3: the chain as three launches per step beside 224 workers) is refused: beside the current kernels its
+        // fused launch hit a recovered hand-off time-out in a plain test sequence at 16 blocks.  The host list generator
+        // still models it (ipm_debug_ff_schedule, tools/ff_tune.py).
+        if (atoi(e) == 0) {
+            int rc_ = fail(nullptr, IPM_ERR_INVALID_ARG, "IPM_FF_CHAIN_MODE=0 is not supported (the fused launch runs chain mode 1 only)");
+            ipm_destroy(h);
+            return rc_;
+        }
+    }
     if (const char* e = getenv("IPM_FF_Q")) h->ff_q = std::max(1, std::min(16, atoi(e)));
     CREATE_TRY(hipEventCreateWithFlags(&h->ev_ffjoin, hipEventDisableTiming));
     h->ev_diag.assign(h->nblk, nullptr); h->ev_crit.assign(h->nblk, nullptr); h->ev_bulk.assign(h->nblk, nullptr);
@@ -2141,13 +2150,14 @@ static int read_scalars(ipm_handle* h, bool* timed_out = nullptr) {
             for (int k = 0; k < nb; ++k) fprintf(stderr, " %u", dr[k]);
             fprintf(stderr, "\n  lfinal:");
             for (int k = 0; k < nb; ++k) fprintf(stderr, " %u", lf[k]);
-            fprintf(stderr, "\n  incomplete tiles (i,c: fcount tprog/expected):");
+            fprintf(stderr, "\n  incomplete tiles (i,c: fcount/expected tprog/expected):");
             int shown = 0;
             for (int i = 0; i < nb; ++i)
                 for (int c = 0; c <= i; ++c) {
                     const size_t t = (size_t)ff_tile(i, c);
-                    if ((fc[t] != (unsigned)h->ff_q || tp[t] != (unsigned)h->ff_sched.tile_items[t]) && shown++ < 24)
-                        fprintf(stderr, " (%d,%d: %u %u/%d)", i, c, fc[t], tp[t], h->ff_sched.tile_items[t]);
+                    // (a tile's chunk count is its own: IPM_FF_Q_LAST forms the last block rows in other counts than ff_q)
+                    if ((fc[t] != (unsigned)h->ff_sched.tile_q[t] || tp[t] != (unsigned)h->ff_sched.tile_items[t]) && shown++ < 24)
+                        fprintf(stderr, " (%d,%d: %u/%d %u/%d)", i, c, fc[t], h->ff_sched.tile_q[t], tp[t], h->ff_sched.tile_items[t]);
                 }
             fprintf(stderr, "\n");
         }

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from ff_cases import KNOBS, MODELS, pair_chunks
 from interiorpointmethod_amd import _lib
 
 F, T, D = 0, 1, 2
@@ -39,8 +40,8 @@ def tid(i, c):
     return i * (i + 1) // 2 + c
 
 
-def replay(nblk, q, items, tile_items):
-    """Replay the list in order; returns the number of chain steps completed at the end."""
+def replay(nblk, q, items, tile_items, q_last=0):
+    """Replay the list in order; returns the number of chain steps completed at the end.  q_last: IPM_FF_Q_LAST in effect."""
     ntile = nblk * (nblk + 1) // 2
     fcount = np.zeros(ntile, int)
     base = np.zeros(ntile, int)
@@ -83,7 +84,7 @@ def replay(nblk, q, items, tile_items):
             for ii in (i, i + 1):
                 if c <= ii < nblk:
                     qtile[tid(ii, c)] = max(qtile[tid(ii, c)], qq + 1)
-    assert qtile.min() >= 1 and np.all(qtile[tid(nblk - 1, 0):] == min(q, 512)) or nblk <= 8
+    assert qtile.min() >= 1 and np.all(qtile[tid(nblk - 1, 0):] == min(q_last or q, 512)) or nblk <= 8
     for n, (typ, i, c, qq, j0, j1, flags, seq, s0, s1) in enumerate(items):
         if typ == D:                         # max diag(B) of row block i: the items the chain-in-kernel launch starts with
             assert n < nblk and i == n
@@ -147,3 +148,90 @@ def test_work_list_is_deterministic_and_its_simulated_time_beats_the_serial_path
     assert sa[0] < 4100.0, sa
     n_t = int((a[:, 0] == T).sum())
     assert n_t < 6000          # batching keeps the read-modify-write passes per tile small (pure right-looking: 5456 + 528)
+
+
+# -------------------------------------------------------------------------------- every generator setting yields a valid list
+# Each knob alone, chain mode 0 (modelled by the host generator for tools/ff_tune.py only; ipm_create refuses it) and the
+# duration-model perturbations that the GPU order-invariance test runs, from 16 blocks (the default rule's lower end) to
+# FF_MAX_NBLK = 96 (tile indices and column ranges of a work item are unsigned char fields, the largest values only occur there).  251 workers = chain mode 1 on 256 CUs (256 - 1 - FF_CRIT_WGS).
+SETTINGS = KNOBS + [("IPM_FF_CHAIN_MODE", "0")] + [("IPM_FF_MODEL", m) for m in MODELS]
+
+
+def _check_cuts(nblk, q, items, stagger=0.3, q_last=0):
+    """The F items carry exactly the K-chunk cuts of the generator's formula (restated in ff_cases.pair_chunks)."""
+    want = pair_chunks(nblk, q, NSTAGES, stagger=stagger, q_last=q_last)
+    got = {}
+    for (typ, i, c, qq, _j0, _j1, _fl, _sq, s0, s1) in items:
+        if typ == F:
+            got.setdefault((int(i), int(c)), {})[int(qq)] = (int(s0), int(s1))
+    assert sorted(got) == sorted(want)
+    for key, cuts in want.items():
+        assert [got[key][k] for k in range(len(cuts))] == cuts, key
+
+
+@pytest.mark.parametrize("nblk", [16, 33, 72, 96])
+@pytest.mark.parametrize("var,val", SETTINGS, ids=[f"{k[7:]}={v}" for k, v in SETTINGS])
+def test_every_generator_setting_gives_a_complete_list_in_dependency_order(built_lib, monkeypatch, var, val, nblk):
+    monkeypatch.setenv(var, val)
+    q, workers = 4, 251
+    items, tile_items, sim = schedule(nblk, q, workers)
+    q_last = int(val) if var == "IPM_FF_Q_LAST" else 0
+    assert replay(nblk, q, items, tile_items, q_last=q_last) == nblk
+    assert sim[0] > 0 and sim[1] > 0
+    _check_cuts(nblk, q, items, stagger=float(val) if var == "IPM_FF_STAGGER" else 0.3, q_last=q_last)
+    assert bool((items[:, 0] == D).any()) == (var != "IPM_FF_CHAIN_MODE")          # FF_D items head the chain-mode-1 list only
+    t = items[items[:, 0] == T]
+    if var == "IPM_FF_BATCH":                                                        # the bulk items really are that wide
+        assert (t[:, 5] - t[:, 4]).max() == int(val)
+    if var == "IPM_FF_TAIL":                                                         # the last `tail` columns one item each
+        i, c = nblk - 1, nblk - 3
+        cols = [(j0, j1) for (_ty, ii, cc, _q, j0, j1, *_r) in t if ii == i and cc == c]
+        assert cols[-int(val):] == [(j, j + 1) for j in range(c - int(val), c)], cols
+
+
+def _producers(items, nblk):
+    """For every T item (list position): the positions of the list items it waits for -- the formation chunks of its tile (when it
+    adds the base), the tile's previous T item, and the items that finalise the L tiles (i, j), (c, j) it applies.  (A sub-diagonal
+    tile (k+1, k) is finalised by the chain after the tile's last T item: that item stands in for it.)"""
+    last_t, fpos = {}, {}
+    for n, (typ, i, c, *_r) in enumerate(items):
+        if typ == F:
+            for ii in (i, i + 1):
+                if c <= ii < nblk:
+                    fpos.setdefault((ii, c), []).append(n)
+        elif typ == T:
+            last_t[(i, c)] = n
+    prev, out = {}, {}
+    for n, (typ, i, c, _q, j0, j1, flags, _seq, *_r) in enumerate(items):
+        if typ != T:
+            continue
+        p = list(fpos[(i, c)]) if flags & ADD_BASE else []
+        if (i, c) in prev:
+            p.append(prev[(i, c)])
+        for j in range(j0, j1):
+            p += [last_t[(i, j)], last_t[(c, j)]]
+        prev[(i, c)] = n
+        out[n] = p
+    return out
+
+
+@pytest.mark.parametrize("nblk", [16, 32, 33])
+def test_model_perturbations_reorder_the_list_without_changing_any_item(built_lib, monkeypatch, nblk):
+    """What the GPU order-invariance test relies on: under each IPM_FF_MODEL perturbation the list for the handle's own
+    (nblk, Q = 4, 251 workers, 512 stages = n of 8192) has a different ORDER but the same multiset of items -- type, tile, chunk,
+    stage cuts, column range, flags, sequence number -- so every tile's arithmetic is unchanged and the results must be bitwise
+    equal.  And EVERY perturbation, at every one of these block counts, puts some update item right behind (within two positions
+    of) the last item it waits for, so that on the device each GPU shape really races a hand-off between neighbouring workers
+    (3 to 8 such items per list today)."""
+    base, tb, _ = schedule(nblk, 4, 251)
+    key = lambda a: sorted(map(tuple, a.tolist()))                                 # noqa: E731
+    for m in MODELS:
+        monkeypatch.setenv("IPM_FF_MODEL", m)
+        items, ti, _ = schedule(nblk, 4, 251)
+        assert items.shape == base.shape and np.array_equal(ti, tb), m
+        assert not np.array_equal(items, base), (m, "the perturbation does not reorder the list")
+        assert key(items) == key(base), (m, "the perturbation changes an item")
+        assert replay(nblk, 4, items, ti) == nblk
+        gaps = [n - max(p) for n, p in _producers(items, nblk).items() if p]
+        assert min(gaps) >= 1
+        assert sum(1 for g in gaps if g <= 2) > 0, (m, nblk, "no update item right behind its producer")
