@@ -100,7 +100,10 @@ typedef struct ipm_options {
                                 1e-12 makes the rank-deficient QAP family converge) */
 } ipm_options;
 
-/* per-solve statistics; norms use the reference's scaling (main.py:170-171) */
+/* per-solve statistics; norms use the reference's scaling (main.py:170-171).  With upper bounds set (ipm_set_bounds) the
+ * fields describe the bounded system: rp_norm = ||(A x - b, x_U + w - u_U)||_2, rd_norm = ||A^T y + s - z - c||_2,
+ * gap = x^T s + w^T z, mu = gap / (n + |U|), b_norm = ||(b, u_U)||_2 -- the norms the stop test of the folded problem
+ * (one row x_j + t_j = u_j per bound) sees. */
 typedef struct ipm_stats {
     int32_t status;          /* IPM_STATUS_* */
     int32_t iterations;      /* k: completed predictor-corrector steps */
@@ -173,13 +176,27 @@ int ipm_set_bc(ipm_handle* h, const double* b, const double* c);        /* host,
 /* ---- iterate (x, y, s) ------------------------------------------------------------- */
 int ipm_set_state(ipm_handle* h, const double* x, const double* y, const double* s);  /* host */
 int ipm_get_state(ipm_handle* h, double* x, double* y, double* s);                    /* host */
-/* x = s = 1, y = y0: sparse_interior.py:193-200 (y0=1) / main.py:287-302 (y0=0) */
+/* x = s = 1, y = y0: sparse_interior.py:193-200 (y0=1) / main.py:287-302 (y0=0); with bounds set also w = z = 1 on U */
 int ipm_init_state(ipm_handle* h, double y0);
+
+/* ---- native upper bounds 0 <= x <= u ------------------------------------------------- */
+/* u: host array of length n, +inf where x_j has no upper bound; u == NULL (or all +inf) removes the bounds, and the
+ * handle then runs exactly the unbounded code.  NaN or negative entries: IPM_ERR_INVALID_INPUT.  The bounded set U
+ * gets an upper slack w (x + w = u) and its dual z inside the Newton system: the normal matrix keeps order m
+ * (DESIGN.md 4-B).  Sets w = z = 1 on U.  The bound vectors are allocated by the library on first use and freed by
+ * ipm_destroy; the workspace size does not change.  Invalidates a pending predictor.  A handle with bounds cannot
+ * join the lockstep batch (ipm_batch_add / ipm_solve_batch: IPM_ERR_INVALID_ARG). */
+int ipm_set_bounds(ipm_handle* h, const double* u);
+/* (w, z): host arrays of length n; entries outside U are ignored on set and read back as 0.  IPM_ERR_STATE without bounds. */
+int ipm_set_bound_state(ipm_handle* h, const double* w, const double* z);
+int ipm_get_bound_state(ipm_handle* h, double* w, double* z);
 
 /* ---- direction seam (main.py:197 / :247) ------------------------------------------- */
 /* corrector == 0: predictor direction at the current state (forms and factors A D^2 A^T).
  * corrector == 1: corrector direction; requires a preceding predictor call at the same
- * state (reuses its factor and affine direction).  Outputs are host arrays (may be NULL). */
+ * state (reuses its factor and affine direction).  Outputs are host arrays (may be NULL).
+ * With bounds set these are the bounded (dx, dy, ds); dw = -(x + w - u) - dx and dz = -(r4 + z dw) / w on U follow
+ * from them (r4 = w z for the predictor, w z + dw_aff dz_aff - sigma mu for the corrector). */
 int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, double* dy, double* ds,
                          ipm_stats* stats);
 

@@ -37,6 +37,7 @@
 #include <atomic>
 #include <mutex>
 #include <chrono>
+#include <limits>
 #include <utility>
 
 using namespace ipm;
@@ -165,6 +166,10 @@ struct ipm_handle {
     Scalars* sc = nullptr;
     IterRec* hist = nullptr;              // [HIST_CAP] per-iteration records (ring)
     double* snap = nullptr;               // roll-back copy of (x, y, s) + Scalars (poll time-out / auto-regularize restart)
+    // native upper bounds (ipm_set_bounds): own allocation of BND_VECS n-vectors, made on first use
+    bool bnd = false;                     // a finite bound is set: the bounded kernel instantiations run
+    int bnd_nU = 0;                       // |U|
+    double* bnd_mem = nullptr;            // u | w | z | dwa | dza | dw | dz | qz | roll-back w | roll-back z
     int* fixed = nullptr;
     Scalars* h_sc = nullptr;          // pinned host mirror
     bool haveA = false, haveBC = false, haveState = false, predictor_valid = false;
@@ -600,7 +605,7 @@ extern "C" int ipm_destroy(ipm_handle* h) {
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->h_sc) { std::lock_guard<std::mutex> lock(g_hsc_mutex); g_hsc_pool.push_back(h->h_sc); h->h_sc = nullptr; }
-    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
+    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
         dev_free(h->device, h->stream, p);
     ff_release(h);
     free_sparse_factor(h);
@@ -1117,13 +1122,25 @@ extern "C" int ipm_set_A_csc(ipm_handle* h, const int32_t* colptr, const int32_t
     return IPM_OK;
 }
 
+// native upper bounds: views into the BND_VECS n-vectors of ipm_set_bounds
+static const int BND_VECS = 10;
+static BndArgs bnd_args(ipm_handle* h) {
+    const size_t np = (size_t)h->np;
+    double* p = h->bnd_mem;
+    BndArgs b;
+    b.u = p; b.w = p + np; b.z = p + 2 * np; b.dwa = p + 3 * np; b.dza = p + 4 * np; b.dw = p + 5 * np; b.dz = p + 6 * np;
+    b.qz = p + 7 * np; b.nU = h->bnd_nU;
+    return b;
+}
+
 extern "C" int ipm_set_bc(ipm_handle* h, const double* b, const double* c) {
     if (!h || !b || !c) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_bc: bad arguments");
     if (!all_finite(b, 1, h->m, h->m) || !all_finite(c, 1, h->n, h->n)) return fail(h, IPM_ERR_INVALID_INPUT, "b or c has non-finite entries");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipMemcpyAsync(h->b, b, sizeof(double) * h->m, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->c, c, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(norm2_kernel, dim3(1), dim3(VBLK), 0, h->stream, h->b, (int)h->m, &h->sc->b_norm);
+    if (h->bnd) hipLaunchKernelGGL(bnd_norm2_kernel, dim3(1), dim3(VBLK), 0, h->stream, h->b, (int)h->m, bnd_args(h).u, (int)h->n, &h->sc->b_norm);
+    else hipLaunchKernelGGL(norm2_kernel, dim3(1), dim3(VBLK), 0, h->stream, h->b, (int)h->m, &h->sc->b_norm);
     hipLaunchKernelGGL(norm2_kernel, dim3(1), dim3(VBLK), 0, h->stream, h->c, (int)h->n, &h->sc->c_norm);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1152,11 +1169,79 @@ extern "C" int ipm_get_state(ipm_handle* h, double* x, double* y, double* s) {
     return IPM_OK;
 }
 
+// Native upper bounds x_j <= u_j.  The bound vectors are the library's own allocation, made on first use and
+// kept (a later ipm_set_bounds(h, NULL) only switches the bounded kernels off); the workspace is not involved.
+extern "C" int ipm_set_bounds(ipm_handle* h, const double* u) {
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_bounds: NULL handle");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int nU = 0;
+    if (u) {
+        for (int64_t j = 0; j < h->n; ++j) {
+            const double v = u[j];
+            if (!(v >= 0.0)) return fail(h, IPM_ERR_INVALID_INPUT, "ipm_set_bounds: u[%lld] = %g (bounds must be >= 0, +inf for none)", (long long)j, v);
+            if (v < std::numeric_limits<double>::infinity()) ++nU;
+        }
+    }
+    h->predictor_valid = false;
+    if (nU == 0) {                                             // NULL or all +inf: the unbounded code, exactly
+        h->bnd = false; h->bnd_nU = 0;
+        if (h->haveBC) hipLaunchKernelGGL(norm2_kernel, dim3(1), dim3(VBLK), 0, h->stream, h->b, (int)h->m, &h->sc->b_norm);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return IPM_OK;
+    }
+    const size_t np = (size_t)h->np;
+    if (!h->bnd_mem) {
+        if (dev_malloc(h->device, h->stream, (void**)&h->bnd_mem, sizeof(double) * BND_VECS * np) != hipSuccess)
+            return fail(h, IPM_ERR_HIP, "ipm_set_bounds: %d x %lld doubles could not be allocated", BND_VECS, (long long)np);
+        HIP_TRY(h, hipMemsetAsync(h->bnd_mem, 0, sizeof(double) * BND_VECS * np, h->stream));
+    }
+    std::vector<double> uu(np, std::numeric_limits<double>::infinity());     // padding columns: unbounded
+    std::copy(u, u + h->n, uu.begin());
+    HIP_TRY(h, hipMemcpyAsync(h->bnd_mem, uu.data(), sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
+    h->bnd = true; h->bnd_nU = nU;
+    const BndArgs bd = bnd_args(h);
+    hipLaunchKernelGGL(bnd_fill_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, h->stream, bd.u, bd.w, bd.z, (int)np, 1.0, 0);
+    if (h->haveBC) hipLaunchKernelGGL(bnd_norm2_kernel, dim3(1), dim3(VBLK), 0, h->stream, h->b, (int)h->m, bd.u, (int)h->n, &h->sc->b_norm);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return IPM_OK;
+}
+
+extern "C" int ipm_set_bound_state(ipm_handle* h, const double* w, const double* z) {
+    if (!h || !w || !z) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_bound_state: bad arguments");
+    if (!h->bnd) return fail(h, IPM_ERR_STATE, "ipm_set_bound_state: no finite bound is set (ipm_set_bounds)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const BndArgs bd = bnd_args(h);
+    HIP_TRY(h, hipMemcpyAsync(bd.w, w, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(bd.z, z, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(bnd_fill_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, bd.u, bd.w, bd.z, (int)h->n, 0.0, 1);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->predictor_valid = false; h->fresh_state = true;
+    return IPM_OK;
+}
+
+extern "C" int ipm_get_bound_state(ipm_handle* h, double* w, double* z) {
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_bound_state: NULL handle");
+    if (!h->bnd) return fail(h, IPM_ERR_STATE, "ipm_get_bound_state: no finite bound is set (ipm_set_bounds)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const BndArgs bd = bnd_args(h);
+    if (w) HIP_TRY(h, hipMemcpyAsync(w, bd.w, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+    if (z) HIP_TRY(h, hipMemcpyAsync(z, bd.z, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return IPM_OK;
+}
+
 static int enqueue_init_state(ipm_handle* h, double y0) {
     int gn = (int)((h->n + 255) / 256), gm = (int)((h->m + 255) / 256);
     hipLaunchKernelGGL(fill_kernel, dim3(gn), dim3(256), 0, h->stream, h->x, (int)h->n, 1.0);
     hipLaunchKernelGGL(fill_kernel, dim3(gn), dim3(256), 0, h->stream, h->s, (int)h->n, 1.0);
     hipLaunchKernelGGL(fill_kernel, dim3(gm), dim3(256), 0, h->stream, h->y, (int)h->m, y0);
+    if (h->bnd) {                                                   // w = z = 1 on U (0 outside)
+        const BndArgs bd = bnd_args(h);
+        hipLaunchKernelGGL(bnd_fill_kernel, dim3(gn), dim3(256), 0, h->stream, bd.u, bd.w, bd.z, (int)h->n, 1.0, 0);
+    }
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
@@ -1223,8 +1308,13 @@ static int enqueue_residuals(ipm_handle* h, hipStream_t st = nullptr) {
     VecArgs a = vec_args(h);
     launch_gemv_n(h, h->x, 1.0, -1.0, h->b, h->rb, st);             // r_b = A x - b
     launch_gemv_t(h, h->y, st);                                     // A^T y (partials)
-    if (!ls_push(h, LS_PREPARE, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(prepare_kernel, dim3(h->vblk), dim3(VBLK), 0, st, a);
-    if (!ls_push(h, LS_STOP_TEST, 1u, LsVecA{a, 0})) hipLaunchKernelGGL(stop_test_kernel, dim3(1), dim3(64), 0, st, a);
+    if (h->bnd) {                                                   // (a bounded handle is never recorded: ls_eligible)
+        hipLaunchKernelGGL(prepare_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, st, a, bnd_args(h));
+        hipLaunchKernelGGL(stop_test_bounded_kernel, dim3(1), dim3(64), 0, st, a, bnd_args(h));
+    } else {
+        if (!ls_push(h, LS_PREPARE, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(prepare_kernel, dim3(h->vblk), dim3(VBLK), 0, st, a);
+        if (!ls_push(h, LS_STOP_TEST, 1u, LsVecA{a, 0})) hipLaunchKernelGGL(stop_test_kernel, dim3(1), dim3(64), 0, st, a);
+    }
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
@@ -2000,29 +2090,37 @@ static int enqueue_predictor(ipm_handle* h, hipEvent_t* ev, bool have_rhs = fals
     if (rc) return rc;
     if (ev) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
     launch_gemv_t(h, h->dya);
-    if (!ls_push(h, LS_DIRECTION, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(direction_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, 0);
+    if (h->bnd) hipLaunchKernelGGL(direction_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, 0, bnd_args(h));
+    else if (!ls_push(h, LS_DIRECTION, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(direction_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, 0);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
 
 static int enqueue_corrector(ipm_handle* h, hipEvent_t* ev) {
     VecArgs a = vec_args(h);
-    if (!ls_push(h, LS_MU_AFF, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(mu_aff_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);
-    if (!ls_push(h, LS_CORR_RHS, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(corrector_rhs_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);
+    if (h->bnd) {
+        hipLaunchKernelGGL(mu_aff_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, bnd_args(h));
+        hipLaunchKernelGGL(corrector_rhs_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, bnd_args(h));
+    } else {
+        if (!ls_push(h, LS_MU_AFF, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(mu_aff_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);
+        if (!ls_push(h, LS_CORR_RHS, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(corrector_rhs_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);
+    }
     launch_gemv_n(h, h->v, -1.0, -1.0, h->rb, h->t1);
     if (ev) HIP_TRY(h, hipEventRecord(ev[0], h->stream));
     int rc = enqueue_potrs(h, h->t1, h->dy);
     if (rc) return rc;
     if (ev) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
     launch_gemv_t(h, h->dy);
-    if (!ls_push(h, LS_DIRECTION, (unsigned)h->vblk, LsVecA{a, 1})) hipLaunchKernelGGL(direction_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, 1);
+    if (h->bnd) hipLaunchKernelGGL(direction_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, 1, bnd_args(h));
+    else if (!ls_push(h, LS_DIRECTION, (unsigned)h->vblk, LsVecA{a, 1})) hipLaunchKernelGGL(direction_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, 1);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
 
 static int enqueue_update(ipm_handle* h) {
     VecArgs a = vec_args(h);
-    if (!ls_push(h, LS_UPDATE, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(update_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);
+    if (h->bnd) hipLaunchKernelGGL(update_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, bnd_args(h));
+    else if (!ls_push(h, LS_UPDATE, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(update_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
@@ -2038,7 +2136,8 @@ static int enqueue_iteration(ipm_handle* h, hipEvent_t* ev) {
         // d = x/s -> formation -> factorization, with the residuals, the stop test and the predictor rhs on the residual
         // stream under the chain-bound tail of the factorization
         VecArgs a = vec_args(h);
-        hipLaunchKernelGGL(scaling_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);
+        if (h->bnd) hipLaunchKernelGGL(scaling_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, bnd_args(h));
+        else hipLaunchKernelGGL(scaling_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);
         const bool fused = ff_use(h);                        // evaluated ONCE per iteration (the live-handle count can change under it)
         if (ev && !fused) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
         // the stop test of THIS iterate runs on the residual stream while the factorization is in flight: formation and
@@ -2194,11 +2293,23 @@ __global__ __launch_bounds__(256) void snapshot_kernel(double* x, double* y, dou
         if (gid == 0) *ssc = *sc;
     }
 }
+__global__ __launch_bounds__(256) void snapshot_bounds_kernel(double* w, double* z, double* sw, double* sz, int np, int restore) {
+    const int gid = blockIdx.x * 256 + threadIdx.x, gsz = gridDim.x * 256;
+    for (int j = gid; j < np; j += gsz) {
+        if (restore) { w[j] = sw[j]; z[j] = sz[j]; }
+        else { sw[j] = w[j]; sz[j] = z[j]; }
+    }
+}
 static int enqueue_snapshot(ipm_handle* h, int restore, hipStream_t st = nullptr) {
     const int64_t mx = h->np > h->mp ? h->np : h->mp;
     const unsigned grid = (unsigned)std::min<int64_t>((mx + 255) / 256, 256);
     hipLaunchKernelGGL(snapshot_kernel, dim3(grid), dim3(256), 0, st ? st : h->stream, h->x, h->y, h->s, h->sc, h->snap, (int)h->np,
                        (int)h->mp, restore);
+    if (h->bnd) {                                              // (w, z) <-> their roll-back copies behind the bound vectors
+        const BndArgs b = bnd_args(h);
+        double* sw = h->bnd_mem + 8 * (size_t)h->np;
+        hipLaunchKernelGGL(snapshot_bounds_kernel, dim3(grid), dim3(256), 0, st ? st : h->stream, b.w, b.z, sw, sw + h->np, (int)h->np, restore);
+    }
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
@@ -2237,7 +2348,8 @@ extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, do
             if ((rc = enqueue_group_inverses(h))) return rc;
             if ((rc = enqueue_predictor(h, nullptr))) return rc;
             VecArgs a = vec_args(h);
-            hipLaunchKernelGGL(mu_aff_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);   // alpha_aff for stats
+            if (h->bnd) hipLaunchKernelGGL(mu_aff_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, bnd_args(h));
+            else hipLaunchKernelGGL(mu_aff_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);   // alpha_aff for stats
             bool tmo = false;
             if ((rc = read_scalars(h, &tmo))) return rc;
             if (!tmo) break;
@@ -2293,7 +2405,8 @@ static int enqueue_small(ipm_handle* h, int max_steps, int auto_reg) {
     a.sc = h->sc; a.hist = h->hist;
     a.eps = h->opt.pivot_guard_eps; a.big = h->opt.pivot_guard_big; a.shift_rel = h->shift_rel;
     a.max_steps = max_steps; a.auto_reg = auto_reg;
-    hipLaunchKernelGGL(small_lp_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a);
+    if (h->bnd) hipLaunchKernelGGL(small_lp_bounded_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a, bnd_args(h));
+    else hipLaunchKernelGGL(small_lp_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
@@ -2453,7 +2566,7 @@ static void ls_gemm_hook(void* ctx, int bm, int bn, int bk, int wm, int wn, cons
     ls_push(h, type, (unsigned)grid, g);
 }
 static bool ls_eligible(const ipm_handle* h) {
-    return h->lockstep && h->sparse && !h->small && !h->spf && h->lookahead == 0 && h->stream2 == nullptr && h->B && h->invD &&
+    return h->lockstep && !h->bnd && h->sparse && !h->small && !h->spf && h->lookahead == 0 && h->stream2 == nullptr && h->B && h->invD &&
            h->haveA && h->haveBC && h->haveState;
 }
 // the launch sequence of ONE iteration of the handle, recorded (nothing is launched)
@@ -2589,6 +2702,7 @@ extern "C" const char* ipm_batch_last_error(const ipm_batch* b) { return b ? b->
 extern "C" int ipm_batch_add(ipm_batch* b, ipm_handle* h, double tol_p, double tol_d, double tol_gap, int32_t max_iter, int32_t* index) {
     if (!b || !h || max_iter < 0) return bfail(b, IPM_ERR_INVALID_ARG, "ipm_batch_add: bad arguments");
     if (h->device != b->device) return bfail(b, IPM_ERR_INVALID_ARG, "ipm_batch_add: the handle lives on device %d, the batch on %d", h->device, b->device);
+    if (h->bnd) return bfail(b, IPM_ERR_INVALID_ARG, "ipm_batch_add: a handle with upper bounds (ipm_set_bounds) has no lockstep twin");
     if (!ls_eligible(h)) return bfail(b, IPM_ERR_STATE, "ipm_batch_add: not a lockstep handle (IPM_FLAG_LOCKSTEP, sparse A, more than 128 rows, dense-tile factor, A / b / c / state set)");
     B_TRY(b, hipSetDevice(b->device));
     if (h->stream != b->S) B_TRY(b, hipStreamSynchronize(h->stream));      // everything the handle did on its own stream is complete
@@ -2715,6 +2829,8 @@ extern "C" int ipm_batch_stats(ipm_batch* b, int32_t index, ipm_stats* stats) {
 extern "C" int ipm_solve_batch(ipm_handle** hs, int32_t n, double tol_p, double tol_d, double tol_gap, int32_t max_iter, ipm_stats* stats) {
     if (!hs || n <= 0 || max_iter < 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_batch: bad arguments");
     for (int i = 0; i < n; ++i) if (!hs[i]) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_batch: NULL handle");
+    for (int i = 0; i < n; ++i)
+        if (hs[i]->bnd) return fail(hs[i], IPM_ERR_INVALID_ARG, "ipm_solve_batch: handle %d has upper bounds (ipm_set_bounds): no lockstep twin", i);
     ipm_batch* b = nullptr;
     int rc = ipm_batch_create(hs[0]->device, nullptr, &b);
     if (rc) return rc;

@@ -68,7 +68,10 @@ __device__ __forceinline__ void block_reduce512(double (&v)[NV], double* red) {
     }
 }
 
-__global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) {
+// Bounded = true: native upper bounds (vector_ops.h BndArgs) -- the same loop with the w / z terms folded into
+// the same reductions (r_u^2 into ||r_b||^2, w.z into x.s, the w / z ratios into the step minima); no extra LDS.
+template <bool Bounded>
+__device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd) {
     __shared__ __attribute__((aligned(16))) double W[NB * WLD];
     __shared__ double dinv_s[NB];
     __shared__ double ys[NB], rbs[NB], t1s[NB], zs[NB], dys[NB];
@@ -103,15 +106,36 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) {
         return rb2;
     };
     // r_c, d, q, v and the partial sums of ||r_c||^2, x.s, c.x
+    double ru2 = 0.0;                                   // bounded: this thread's share of ||r_u||^2 (residual_cols)
+    double *DWp = nullptr, *DZp = nullptr;              // bounded: where direction() puts (dw, dz)
     auto residual_cols = [&](double& rc2, double& xs, double& cx) {
         for (int j = tid; j < n; j += PD_THREADS) {
             const int pb = a.A.colptr[j], pe = a.A.colptr[j + 1];
             double w = 0.0;
             for (int p = pb; p < pe; ++p) w += a.A.cval[p] * ys[a.A.rowind[p]];
             const double xj = a.x[j], sj = a.s[j], cj = a.c[j];
-            const double rcj = w + sj - cj, dj = xj / sj, r3 = xj * sj;
-            a.rc[j] = rcj; a.d[j] = dj; a.q[j] = r3 / xj; a.v[j] = dj * (rcj - r3 / xj);
-            rc2 += rcj * rcj; xs += r3; cx += cj * xj;
+            if constexpr (Bounded) {
+                // one straight-line update of the four sums for both kinds of column (with a `continue` per kind the
+                // accumulators were left in scratch memory)
+                const double uj = bd.u[j];
+                double rcj = w + sj - cj, dj = xj / sj, vj, r4 = 0.0, ru_j2 = 0.0;
+                const double r3 = xj * sj, qj = r3 / xj;
+                if (bnd_in(uj)) {
+                    const double wj = bd.w[j], zj = bd.z[j];
+                    const double ruj = xj + wj - uj;
+                    rcj = w + sj - zj - cj; dj = bnd_theta(xj, sj, wj, zj); r4 = wj * zj; ru_j2 = ruj * ruj;
+                    bd.qz[j] = r4 / wj;
+                    vj = dj * (rcj - qj + (r4 - zj * ruj) / wj);
+                } else {
+                    vj = dj * (rcj - qj);
+                }
+                a.rc[j] = rcj; a.d[j] = dj; a.q[j] = qj; a.v[j] = vj;
+                rc2 += rcj * rcj; xs += r3; xs += r4; cx += cj * xj; ru2 += ru_j2;
+            } else {
+                const double rcj = w + sj - cj, dj = xj / sj, r3 = xj * sj;
+                a.rc[j] = rcj; a.d[j] = dj; a.q[j] = r3 / xj; a.v[j] = dj * (rcj - r3 / xj);
+                rc2 += rcj * rcj; xs += r3; cx += cj * xj;
+            }
         }
     };
     // stop test of check_optimality (main.py:162-173): thread 0, result in `go`
@@ -120,8 +144,9 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) {
             const double rb = sqrt(rb2), rcn = sqrt(rc2);
             sc->rb_norm = rb; sc->rc_norm = rcn; sc->gap = gap; sc->obj = obj;
             if (fabs(obj) < 1.7e308) sc->obj_last_finite = obj;
-            sc->mu = gap / (double)n;
-            sh[0] = gap / (double)n;
+            const double nmu = Bounded ? (double)(n + bd.nU) : (double)n;
+            sc->mu = gap / nmu;
+            sh[0] = gap / nmu;
             int cont_loop = 1;
             if (!sc->force) {
                 const bool cont = (sc->e1 * (1.0 + sc->b_norm) < rb) || (sc->e2 * (1.0 + sc->c_norm) < rcn) || (sc->e3 < gap);
@@ -176,6 +201,18 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) {
             DX[j] = dxj; DS[j] = dsj;
             if (dxj < 0.0) minp = fmin(minp, -xj / dxj);
             if (dsj < 0.0) mind = fmin(mind, -sj / dsj);
+            if constexpr (Bounded) {
+                const double uj = bd.u[j];
+                double dwj = 0.0, dzj = 0.0;
+                if (bnd_in(uj)) {
+                    const double wj = bd.w[j], zj = bd.z[j];
+                    dwj = -(xj + wj - uj) - dxj;
+                    dzj = (-zj * dwj) / wj - bd.qz[j];
+                    if (dwj < 0.0) minp = fmin(minp, -wj / dwj);
+                    if (dzj < 0.0) mind = fmin(mind, -zj / dzj);
+                }
+                DWp[j] = dwj; DZp[j] = dzj;
+            }
         }
     };
 
@@ -184,7 +221,9 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) {
         // ---------------------------------------------------------------- residuals + stop test
         double r4[4] = {0.0, 0.0, 0.0, 0.0};               // ||r_b||^2, ||r_c||^2, x.s, c.x
         r4[0] = residual_rows();
+        if constexpr (Bounded) ru2 = 0.0;
         residual_cols(r4[1], r4[2], r4[3]);
+        if constexpr (Bounded) r4[0] += ru2;
         block_reduce512<4, false>(r4, red);
         stop_test(r4[0], r4[1], r4[2], r4[3]);
         __syncthreads();
@@ -231,13 +270,17 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) {
         // ---------------------------------------------------------------- predictor
         solve_normal();
         double mn[2] = {1.0, 1.0};
+        if constexpr (Bounded) { DWp = bd.dwa; DZp = bd.dza; }
         direction(a.dxa, a.dsa, mn[0], mn[1]);
         block_reduce512<2, true>(mn, red);
         const double aap = mn[0], aad = mn[1];
         double ma[1] = {0.0};
-        for (int j = tid; j < n; j += PD_THREADS) ma[0] += (a.x[j] + aap * a.dxa[j]) * (a.s[j] + aad * a.dsa[j]);
+        for (int j = tid; j < n; j += PD_THREADS) {
+            ma[0] += (a.x[j] + aap * a.dxa[j]) * (a.s[j] + aad * a.dsa[j]);
+            if constexpr (Bounded) ma[0] += (bd.w[j] + aap * bd.dwa[j]) * (bd.z[j] + aad * bd.dza[j]);      // 0 outside U
+        }
         block_reduce512<1, false>(ma, red);
-        const double mu_aff = ma[0] / (double)n;
+        const double mu_aff = ma[0] / (Bounded ? (double)(n + bd.nU) : (double)n);
         const double rr = mu_aff / mu;
         const double sigma = rr * rr * rr;
         const double sm = sigma * mu;
@@ -246,11 +289,22 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) {
             const double xj = a.x[j];
             const double qj = (xj * a.s[j] + a.dxa[j] * a.dsa[j] - sm) / xj;
             a.q[j] = qj;
+            if constexpr (Bounded) {
+                const double uj = bd.u[j];
+                if (bnd_in(uj)) {
+                    const double wj = bd.w[j], zj = bd.z[j];
+                    const double r4c = wj * zj + bd.dwa[j] * bd.dza[j] - sm;
+                    bd.qz[j] = r4c / wj;
+                    a.v[j] = a.d[j] * (a.rc[j] - qj + (r4c - zj * (xj + wj - uj)) / wj);
+                    continue;
+                }
+            }
             a.v[j] = a.d[j] * (a.rc[j] - qj);
         }
         __syncthreads();
         solve_normal();
         double mc[2] = {1.0, 1.0};
+        if constexpr (Bounded) { DWp = bd.dw; DZp = bd.dz; }
         direction(a.dx, a.ds, mc[0], mc[1]);
         block_reduce512<2, true>(mc, red);
         // ---------------------------------------------------------------- damped step (main.py:604-626, 694-696)
@@ -259,6 +313,10 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) {
         for (int j = tid; j < n; j += PD_THREADS) {
             a.x[j] += ap * a.dx[j];
             a.s[j] += ad * a.ds[j];
+            if constexpr (Bounded) {
+                bd.w[j] += ap * bd.dw[j];
+                bd.z[j] += ad * bd.dz[j];
+            }
         }
         if (tid < m) ys[tid] += ad * dys[tid];
         if (tid == 0) {
@@ -275,5 +333,8 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) {
     }
     if (tid < m) a.y[tid] = ys[tid];
 }
+
+__global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) { small_lp_body<false>(a, BndArgs{}); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_bounded_kernel(SmallLP a, BndArgs bd) { small_lp_body<true>(a, bd); }
 
 }  // namespace ipm

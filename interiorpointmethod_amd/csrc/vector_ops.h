@@ -149,6 +149,18 @@ struct VecArgs {
     IterRec* hist;                 // [HIST_CAP] ring of per-iteration records
 };
 
+// Native upper bounds 0 <= x <= u: the bounded instantiations (Bounded = true) of the kernels below take
+// these.  Every array is an n-vector; outside the bounded set U, u = +inf and w = z = dw = dz = 0, so the streams stay
+// coalesced and no index gather is needed.  qz = r_4 / w of the current direction (the z-analogue of VecArgs::q).
+struct BndArgs {
+    const double* u;
+    double *w, *z, *dwa, *dza, *dw, *dz, *qz;
+    int nU;                        // |U|: mu = (x.s + w.z) / (n + |U|)
+};
+__device__ __forceinline__ bool bnd_in(double u) { return u < 1.7976931348623157e308; }     // finite bound (u is never NaN)
+// theta_j = 1 / (s/x + z/w) on U: the diagonal of D^2 (scaling_kernel and prepare_kernel write it concurrently: one expression)
+__device__ __forceinline__ double bnd_theta(double x, double s, double w, double z) { return 1.0 / (s / x + z / w); }
+
 // sum over the row chunks of the GEMV-T partials, in chunk order (fixed order: bitwise reproducible).  Eight loads are in
 // flight at a time: a plain loop waits for every load before it issues the next one (32 chunks = 32 L2 latencies, 13 us of
 // direction_kernel's 13 us at n = 8192).
@@ -167,12 +179,36 @@ __device__ __forceinline__ double col_sum(const double* atp, int rc_chunks, int 
 }
 
 // r_c = A^T y + s - c ; d = x/s ; predictor v = d*(r_c - r3/x) ; partial ||r_c||^2, x.s, c.x, ||r_b||^2
-__device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_) {
+// Bounded, on U: r_c -= z ; r_u = x + w - u ; d = theta ; v = theta (r_c - r3/x + (r4 - z r_u)/w) with r4 = w z ;
+// r_u^2 joins ||r_b||^2 and w z joins x.s
+template <bool Bounded = false>
+__device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     __shared__ double red[VBLK];
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     double rc2 = 0.0, xs = 0.0, cx = 0.0, rb2 = 0.0;
     for (int j = gid; j < a.n; j += gsz) {
         double xj = a.x[j], sj = a.s[j];
+        if constexpr (Bounded) {
+            const double uj = bd.u[j];
+            if (bnd_in(uj)) {
+                const double wj = bd.w[j], zj = bd.z[j];
+                const double rcj = col_sum(a.atp, a.rc_chunks, a.np, j) + sj - zj - a.c[j];
+                const double ruj = xj + wj - uj;
+                const double dj = bnd_theta(xj, sj, wj, zj);
+                const double r3 = xj * sj, r4 = wj * zj;
+                a.rc[j] = rcj;
+                a.d[j] = dj;
+                a.q[j] = r3 / xj;
+                bd.qz[j] = r4 / wj;
+                a.v[j] = dj * (rcj - r3 / xj + (r4 - zj * ruj) / wj);
+                rc2 += rcj * rcj;
+                xs += r3;
+                xs += r4;
+                cx += a.c[j] * xj;
+                rb2 += ruj * ruj;
+                continue;
+            }
+        }
         double rcj = col_sum(a.atp, a.rc_chunks, a.np, j) + sj - a.c[j];
         double dj = xj / sj;
         double r3 = xj * sj;
@@ -194,18 +230,29 @@ __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx
     }
 }
 __global__ __launch_bounds__(VBLK) void prepare_kernel(VecArgs a) { prepare_kernel_body(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(VBLK) void prepare_bounded_kernel(VecArgs a, BndArgs bd) { prepare_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 
 // d = x / s only (main.py:223): what the formation of A D^2 A^T needs; the full prepare_kernel follows on the residual
-// stream while the factorization runs (ipm_api.hip, enqueue_iteration)
-__global__ __launch_bounds__(VBLK) void scaling_kernel(VecArgs a) {
+// stream while the factorization runs (ipm_api.hip, enqueue_iteration).  Bounded: d = theta on U.
+template <bool Bounded = false>
+__device__ __forceinline__ void scaling_kernel_body(VecArgs a, BndArgs bd = BndArgs{}) {
     if (blockIdx.x == 0 && threadIdx.x == 0) a.sc->done_f = a.sc->done;      // latch for this iteration's factorization
     if (a.sc->done) return;
     const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
-    for (int j = gid; j < a.n; j += gsz) a.d[j] = a.x[j] / a.s[j];
+    for (int j = gid; j < a.n; j += gsz) {
+        if constexpr (Bounded) {
+            if (bnd_in(bd.u[j])) { a.d[j] = bnd_theta(a.x[j], a.s[j], bd.w[j], bd.z[j]); continue; }
+        }
+        a.d[j] = a.x[j] / a.s[j];
+    }
 }
+__global__ __launch_bounds__(VBLK) void scaling_kernel(VecArgs a) { scaling_kernel_body(a); }
+__global__ __launch_bounds__(VBLK) void scaling_bounded_kernel(VecArgs a, BndArgs bd) { scaling_kernel_body<true>(a, bd); }
 
 // stop test of check_optimality (main.py:162-173) -- one thread.
-__device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_) {
+// Bounded: ||r_b||^2 carries r_u^2 and the gap w.z (prepare_kernel), b_norm is ||(b, u_U)|| (ipm_set_bounds), mu divides by n + |U|.
+template <bool Bounded = false>
+__device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     if (threadIdx.x != 0 || bx_ != 0) return;
     Scalars* sc = a.sc;
     if (sc->done) return;
@@ -216,7 +263,8 @@ __device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned 
     const double obj = sum_partials(a.part, P_CX, a.nblk);
     sc->obj = obj;
     if (fabs(obj) < 1.7e308) sc->obj_last_finite = obj;          // false for NaN and Inf
-    sc->mu = gap / (double)a.n;
+    if constexpr (Bounded) sc->mu = gap / (double)(a.n + bd.nU);
+    else sc->mu = gap / (double)a.n;
     bool cont = (sc->e1 * (1.0 + sc->b_norm) < rb) || (sc->e2 * (1.0 + sc->c_norm) < rc) || (sc->e3 < gap);
     if (sc->force) return;
     if (!cont) {
@@ -230,10 +278,13 @@ __device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned 
     }
 }
 __global__ void stop_test_kernel(VecArgs a) { stop_test_kernel_body(a, blockIdx.x, gridDim.x); }
+__global__ void stop_test_bounded_kernel(VecArgs a, BndArgs bd) { stop_test_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 
 // direction recovery + ratio test.  corr == 0: (dxa, dsa) from dya with q = r3/x;
-// corr == 1: (dx, ds) from dy with the corrector q.
-__device__ __forceinline__ void direction_kernel_body(VecArgs a, int corr, const unsigned bx_, const unsigned gx_) {
+// corr == 1: (dx, ds) from dy with the corrector q.  Bounded, on U: dw = -r_u - dx, dz = -(r4 + z dw)/w (qz = r4/w), and the
+// ratio tests also run over w (primal) and z (dual); dw = dz = 0 outside U.
+template <bool Bounded = false>
+__device__ __forceinline__ void direction_kernel_body(VecArgs a, int corr, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     if (a.sc->done) return;
     __shared__ double red[VBLK];
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
@@ -248,6 +299,19 @@ __device__ __forceinline__ void direction_kernel_body(VecArgs a, int corr, const
         DX[j] = dxj; DS[j] = dsj;
         if (dxj < 0.0) mp_ = fmin(mp_, -xj / dxj);
         if (dsj < 0.0) md_ = fmin(md_, -sj / dsj);
+        if constexpr (Bounded) {
+            const double uj = bd.u[j];
+            double dwj = 0.0, dzj = 0.0;
+            if (bnd_in(uj)) {
+                const double wj = bd.w[j], zj = bd.z[j];
+                dwj = -(xj + wj - uj) - dxj;
+                dzj = (-zj * dwj) / wj - bd.qz[j];
+                if (dwj < 0.0) mp_ = fmin(mp_, -wj / dwj);
+                if (dzj < 0.0) md_ = fmin(md_, -zj / dzj);
+            }
+            (corr ? bd.dw : bd.dwa)[j] = dwj;
+            (corr ? bd.dz : bd.dza)[j] = dzj;
+        }
     }
     mp_ = block_min(mp_, red); md_ = block_min(md_, red);
     if (threadIdx.x == 0) {
@@ -256,16 +320,21 @@ __device__ __forceinline__ void direction_kernel_body(VecArgs a, int corr, const
     }
 }
 __global__ __launch_bounds__(VBLK) void direction_kernel(VecArgs a, int corr) { direction_kernel_body(a, corr, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(VBLK) void direction_bounded_kernel(VecArgs a, int corr, BndArgs bd) { direction_kernel_body<true>(a, corr, blockIdx.x, gridDim.x, bd); }
 
-// partial sums of (x + a_p dxa).(s + a_d dsa)      main.py:579-584, 598
-__device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_) {
+// partial sums of (x + a_p dxa).(s + a_d dsa)      main.py:579-584, 598   (Bounded: + (w + a_p dwa).(z + a_d dza))
+template <bool Bounded = false>
+__device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     if (a.sc->done) return;
     __shared__ double red[VBLK];
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     const double ap = min_partials(a.part, P_MINP_AFF, a.nblk);
     const double ad = min_partials(a.part, P_MIND_AFF, a.nblk);
     double acc = 0.0;
-    for (int j = gid; j < a.n; j += gsz) acc += (a.x[j] + ap * a.dxa[j]) * (a.s[j] + ad * a.dsa[j]);
+    for (int j = gid; j < a.n; j += gsz) {
+        acc += (a.x[j] + ap * a.dxa[j]) * (a.s[j] + ad * a.dsa[j]);
+        if constexpr (Bounded) acc += (bd.w[j] + ap * bd.dwa[j]) * (bd.z[j] + ad * bd.dza[j]);      // 0 outside U
+    }
     acc = block_sum(acc, red);
     if (threadIdx.x == 0) {
         a.part[P_MUAFF * MAXPART + bx_] = acc;
@@ -273,13 +342,16 @@ __device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_
     }
 }
 __global__ __launch_bounds__(VBLK) void mu_aff_kernel(VecArgs a) { mu_aff_kernel_body(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(VBLK) void mu_aff_bounded_kernel(VecArgs a, BndArgs bd) { mu_aff_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 
 // corrector: r3c = x s + dxa dsa - sigma mu ; q = r3c/x ; v = d (r_c - q)     main.py:150-152
-__device__ __forceinline__ void corrector_rhs_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_) {
+// Bounded, on U: r4c = w z + dwa dza - sigma mu ; qz = r4c/w ; v = theta (r_c - q + (r4c - z r_u)/w) ; mu_aff over n + |U|
+template <bool Bounded = false>
+__device__ __forceinline__ void corrector_rhs_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     if (a.sc->done) return;
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     const double mu = a.sc->mu;
-    const double mu_aff = sum_partials(a.part, P_MUAFF, a.nblk) / (double)a.n;
+    const double mu_aff = sum_partials(a.part, P_MUAFF, a.nblk) / (Bounded ? (double)(a.n + bd.nU) : (double)a.n);
     const double r = mu_aff / mu;
     const double sigma = r * r * r;
     const double sm = sigma * mu;
@@ -288,14 +360,26 @@ __device__ __forceinline__ void corrector_rhs_kernel_body(VecArgs a, const unsig
         double r3c = xj * a.s[j] + a.dxa[j] * a.dsa[j] - sm;
         double qj = r3c / xj;
         a.q[j] = qj;
+        if constexpr (Bounded) {
+            const double uj = bd.u[j];
+            if (bnd_in(uj)) {
+                const double wj = bd.w[j], zj = bd.z[j];
+                const double r4c = wj * zj + bd.dwa[j] * bd.dza[j] - sm;
+                bd.qz[j] = r4c / wj;
+                a.v[j] = a.d[j] * (a.rc[j] - qj + (r4c - zj * (xj + wj - uj)) / wj);
+                continue;
+            }
+        }
         a.v[j] = a.d[j] * (a.rc[j] - qj);
     }
     if (gid == 0) { a.sc->mu_aff = mu_aff; a.sc->sigma = sigma; }
 }
 __global__ __launch_bounds__(VBLK) void corrector_rhs_kernel(VecArgs a) { corrector_rhs_kernel_body(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(VBLK) void corrector_rhs_bounded_kernel(VecArgs a, BndArgs bd) { corrector_rhs_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 
-// x += a_p dx ; y += a_d dy ; s += a_d ds ; k += 1          main.py:604-626, 694-696
-__device__ __forceinline__ void update_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_) {
+// x += a_p dx ; y += a_d dy ; s += a_d ds ; k += 1          main.py:604-626, 694-696   (Bounded: w += a_p dw ; z += a_d dz)
+template <bool Bounded = false>
+__device__ __forceinline__ void update_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     if (a.sc->done) return;
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     const double eta = a.sc->eta;
@@ -304,6 +388,10 @@ __device__ __forceinline__ void update_kernel_body(VecArgs a, const unsigned bx_
     for (int j = gid; j < a.n; j += gsz) {
         a.x[j] += ap * a.dx[j];
         a.s[j] += ad * a.ds[j];
+        if constexpr (Bounded) {
+            bd.w[j] += ap * bd.dw[j];
+            bd.z[j] += ad * bd.dz[j];
+        }
     }
     for (int i = gid; i < a.m; i += gsz) a.y[i] += ad * a.dy[i];
     if (gid == 0) {
@@ -318,6 +406,7 @@ __device__ __forceinline__ void update_kernel_body(VecArgs a, const unsigned bx_
     }
 }
 __global__ __launch_bounds__(VBLK) void update_kernel(VecArgs a) { update_kernel_body(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(VBLK) void update_bounded_kernel(VecArgs a, BndArgs bd) { update_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 
 // out[i] = value for i < n (fill)
 __global__ void fill_kernel(double* out, int n, double value) {
@@ -332,6 +421,24 @@ __global__ __launch_bounds__(VBLK) void norm2_kernel(const double* v, int n, dou
     for (int i = threadIdx.x; i < n; i += VBLK) acc += v[i] * v[i];
     acc = block_sum(acc, red);
     if (threadIdx.x == 0) *out = sqrt(acc);
+}
+
+// ||(b, u_U)||_2 -> *out (single block): b_norm of the bounded stop test
+__global__ __launch_bounds__(VBLK) void bnd_norm2_kernel(const double* b, int m, const double* u, int n, double* out) {
+    __shared__ double red[VBLK];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < m; i += VBLK) acc += b[i] * b[i];
+    for (int j = threadIdx.x; j < n; j += VBLK) { const double uj = u[j]; if (bnd_in(uj)) acc += uj * uj; }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) *out = sqrt(acc);
+}
+
+// w = z = value on U, 0 outside (mask_only: keep w, z on U and zero them outside)
+__global__ void bnd_fill_kernel(const double* u, double* w, double* z, int n, double value, int mask_only) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    if (!bnd_in(u[j])) { w[j] = 0.0; z[j] = 0.0; }
+    else if (!mask_only) { w[j] = value; z[j] = value; }
 }
 
 }  // namespace ipm

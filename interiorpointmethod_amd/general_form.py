@@ -7,6 +7,7 @@ Same names and argument meaning as the reference (payakorn/InteriorPointMethod):
     get_Abc(c, Aeq, beq, Aineq, bineq, lb, ub, options)   -> (A, b, c, bound)        main.py:818-965
     add_bound_into_matrix(A, b, c, bound)                 -> (A, b, c, (None, None), constant)   main.py:968-1060
     new_interior_sparse(c, Aeq, beq, Aineq, bineq, lb, ub, tol)  -> objective        main.py:1081-1245
+    native_form(c, Aeq, beq, Aineq, bineq, lb, ub)        -> NativeForm   (bounds="native": 0 <= x <= u in the Newton system)
     create_problem_from_mps_matlab(name)                  -> (c, Aineq, bineq, Aeq, beq, lb, ub)  sparse_interior.py:290-314
 
 The conversion is host-side data plumbing (scipy.sparse / numpy); the solve is libipm_hip's loop with the
@@ -134,13 +135,71 @@ def standard_form(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=Non
     return A, _vec(b), _vec(cs), offset
 
 
+class NativeForm:
+    """What new_interior_sparse(bounds="native") solves: min c^T x' s.t. A x' = b, 0 <= x' <= u, with
+    original objective = c^T x' + offset.  A is get_Abc's matrix (inequality slacks appended) without the columns of the
+    fixed variables (lb == ub), b is shifted by the finite lower bounds (x = x' + lb), u = ub - lb (+inf where there is no
+    upper bound, and for the slack columns).  keep: get_Abc columns that remain; fixed: those removed; lb0: lower bounds
+    of every get_Abc column; n: number of original variables."""
+    __slots__ = ("A", "b", "c", "u", "offset", "keep", "fixed", "lb0", "n")
+
+    def x_original(self, xn):
+        """x' of the native problem -> x of the original variables (length n)."""
+        x = self.lb0.copy()
+        x[self.keep] += np.asarray(xn, dtype=np.float64).reshape(-1)
+        return x[:self.n]
+
+
+def native_form(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None):
+    """General form -> NativeForm (host only).  ValueError for ub < lb or a -inf lower bound (free variables are not
+    supported)."""
+    c0 = _vec(c)
+    n = c0.shape[0]
+    lb = np.zeros((n, 1)) if lb is None else _vec(lb, "lb", n)
+    ub = np.full((n, 1), np.inf) if ub is None else _vec(ub, "ub", n)
+    if np.isnan(lb).any() or np.isnan(ub).any():
+        raise ValueError("lb / ub have NaN entries")
+    if (ub < lb).any():
+        raise ValueError("ub < lb for %d variables (infeasible bounds)" % int((ub < lb).sum()))
+    if not np.all(lb > -np.inf):
+        raise ValueError("there are -inf in lower bound (free variables are not supported)")
+    A0, b0, cs, _ = get_Abc(c0, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=None, ub=None)
+    A0 = sparse.csc_matrix(A0, dtype=np.float64)
+    N = A0.shape[1]
+    lb0 = np.zeros(N); lb0[:n] = lb.ravel()
+    u0 = np.full(N, np.inf); u0[:n] = (ub - lb).ravel()
+    cs = np.asarray(cs, dtype=np.float64).ravel()
+    b = np.asarray(b0, dtype=np.float64).ravel() - np.asarray(A0 @ lb0).ravel()
+    fixed = np.nonzero(u0 == 0.0)[0]
+    keep = np.nonzero(u0 != 0.0)[0]
+    F = NativeForm()
+    F.A = sparse.csc_matrix(A0[:, keep])
+    F.b, F.c, F.u = b.reshape(-1, 1), cs[keep].reshape(-1, 1), u0[keep]
+    F.offset = float(cs @ lb0)
+    F.keep, F.fixed, F.lb0, F.n = keep, fixed, lb0, n
+    return F
+
+
 def new_interior_sparse(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None, tol=1e-20, device=0,
-                        return_info=False, start="reference"):
+                        return_info=False, start="reference", bounds="fold"):
     """Drop-in for main.py:1081-1245: convert to standard form, run the predictor-corrector loop on the GPU
-    (e1 = e2 = tol, e3 = 1e-6, at most 999 iterations, x = y = s = 1), return the objective."""
-    A, b, cs, offset = standard_form(c, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=lb, ub=ub)
-    _, _, _, info = _solver.solve_with_info(A, b, cs, tol=tol, tol_gap=1e-6, max_iter=999, y0=1.0, device=device,
-                                            start=start)            # start="mehrotra": optional, not the reference's
+    (e1 = e2 = tol, e3 = 1e-6, at most 999 iterations, x = y = s = 1), return the objective.
+    bounds="fold" (default, the reference's way): every finite upper bound becomes a row and a slack column of A.
+    bounds="native": native_form() -- the bounds stay in the Newton system (ipm_set_bounds), fixed variables are removed
+    on the host; info["bounded"] = |U|, info["fixed_removed"], info["x"] = the original variables."""
+    if bounds not in ("fold", "native"):
+        raise ValueError('bounds must be "fold" or "native"')
+    if bounds == "native":
+        F = native_form(c, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=lb, ub=ub)
+        x, _, _, info = _solver.solve_with_info(F.A, F.b, F.c, tol=tol, tol_gap=1e-6, max_iter=999, y0=1.0, device=device,
+                                                start=start, ub=F.u)
+        info["fixed_removed"] = int(F.fixed.size)
+        info["x"] = F.x_original(x)
+        offset = F.offset
+    else:
+        A, b, cs, offset = standard_form(c, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=lb, ub=ub)
+        _, _, _, info = _solver.solve_with_info(A, b, cs, tol=tol, tol_gap=1e-6, max_iter=999, y0=1.0, device=device,
+                                                start=start)            # start="mehrotra": optional, not the reference's
     obj = info["objective"]
     if info["status"] == 3:                      # NaN iterate: the reference returns the last finite objective it saw
         obj = info["objective_last_finite"]      # (main.py:1227-1233)

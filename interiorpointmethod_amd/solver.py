@@ -181,11 +181,26 @@ class Prepared:
     IpmSolver(..., prepared=P) takes it.  (Computing it AHEAD of the solves on helper threads in the batched mode was tried and
     is slower -- 14.55 -> 13.2 LPs/s on the 73-LP suite: the helpers' SciPy sections hold the interpreter lock the eight
     worker threads need between their library calls.)"""
-    __slots__ = ("host", "A", "b", "c", "m", "n", "factor", "order_info", "perm")
+    __slots__ = ("host", "A", "b", "c", "m", "n", "factor", "order_info", "perm", "ub")
 
 
-def prepare(A, b, c, dense=False, reorder="auto", factor=None):
-    """Host-only part of IpmSolver.__init__ (no device is touched) -> Prepared."""
+def _upper_bounds(ub, n):
+    """Host check of native upper bounds -> float64 (n,) with +inf where x_j is unbounded, or None when no entry is finite
+    (the unbounded code runs exactly then).  ValueError for a wrong length, NaN or a negative entry."""
+    if ub is None:
+        return None
+    u = np.ascontiguousarray(np.asarray(ub, dtype=np.float64).reshape(-1))
+    if u.shape[0] != n:
+        raise ValueError("ub has length %d, expected %d" % (u.shape[0], n))
+    if np.isnan(u).any():
+        raise ValueError("ub has NaN entries")
+    if (u < 0).any():
+        raise ValueError("ub has negative entries (0 <= x <= ub; shift lower bounds first)")
+    return u if np.isfinite(u).any() else None
+
+
+def prepare(A, b, c, dense=False, reorder="auto", factor=None, ub=None):
+    """Host-only part of IpmSolver.__init__ (no device is touched) -> Prepared.  ub: native upper bounds (see IpmSolver)."""
     P = Prepared()
     P.perm = None
     if _sp is not None and _sp.issparse(A):
@@ -203,6 +218,7 @@ def prepare(A, b, c, dense=False, reorder="auto", factor=None):
     P.m, P.n = int(m), int(n)
     b = _col(b, P.m, "b")
     c = _col(c, P.n, "c")
+    P.ub = _upper_bounds(ub, P.n)
     P.host = (A, b, c)
     # factor: "dense" = blocked dense-tile Cholesky (tile envelope, RCM row order), "sparse" = multifrontal sparse
     # Cholesky (minimum-degree row order), "auto" (default; environment IPM_FACTOR overrides) = whichever the model
@@ -239,12 +255,16 @@ class IpmSolver:
 
     def __init__(self, A, b, c, device=0, eta=0.91, pivot_guard_eps=1e-30, pivot_guard_big=1e64,
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
-                 auto_regularize=True, factor=None, prepared=None, lockstep=False):
+                 auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None):
+        """ub: native upper bounds 0 <= x <= ub (length n, +inf = none), checked on the host before any device
+        is touched.  The normal matrix keeps order m; a bounded solver cannot join the lockstep batch."""
+        if prepared is None:
+            prepared = prepare(A, b, c, dense=dense, reorder=reorder, factor=factor, ub=ub)
+        elif ub is not None:
+            raise ValueError("pass ub to prepare() when a Prepared is given")
         lib = _lib.load()
         self._lib = lib
         self._h = None
-        if prepared is None:
-            prepared = prepare(A, b, c, dense=dense, reorder=reorder, factor=factor)
         # device row i = caller's row perm[i] (sparse A whose rows the host analysis reordered: minimum degree or RCM)
         self._perm = prepared.perm
         self.m, self.n = prepared.m, prepared.n
@@ -303,6 +323,10 @@ class IpmSolver:
                 self.factor, self.order_info = "dense", None
         else:
             self._check(lib.ipm_set_A_dense(h, C.c_void_p(A.ctypes.data), self.n, 0))
+        self.ub = prepared.ub                       # None: no finite bound (the unbounded code runs)
+        self.bounded = 0 if self.ub is None else int(np.isfinite(self.ub).sum())
+        if self.ub is not None:
+            self._check(lib.ipm_set_bounds(h, _dptr(self.ub)))
         self._check(lib.ipm_set_bc(h, _dptr(b), _dptr(c)))
         self.stats = None
 
@@ -342,9 +366,27 @@ class IpmSolver:
         out[self._perm] = v
         return out
 
-    def set_state(self, x, y, s):
+    def set_state(self, x, y, s, w=None, z=None):
+        """(w, z): the upper slacks and their duals of a bounded solver (entries outside the bounded set are ignored);
+        None keeps what the solver holds (w = z = 1 on the bounded set after construction or init_state)."""
         x, y, s = _col(x, self.n, "x"), self._rows_in(_col(y, self.m, "y")), _col(s, self.n, "s")
+        if (w is None) != (z is None):
+            raise ValueError("give both w and z or neither")
+        if w is not None:
+            if not self.bounded:
+                raise ValueError("w / z given but the solver has no finite upper bound")
+            w, z = _col(w, self.n, "w"), _col(z, self.n, "z")
         self._check(self._lib.ipm_set_state(self._h, _dptr(x), _dptr(y), _dptr(s)))
+        if w is not None:
+            self._check(self._lib.ipm_set_bound_state(self._h, _dptr(w), _dptr(z)))
+
+    def get_bound_state(self):
+        """(w, z) of a bounded solver as (n, 1) arrays (0 outside the bounded set); None without bounds."""
+        if not self.bounded:
+            return None
+        w, z = np.empty(self.n), np.empty(self.n)
+        self._check(self._lib.ipm_get_bound_state(self._h, _dptr(w), _dptr(z)))
+        return w.reshape(-1, 1), z.reshape(-1, 1)
 
     def get_state(self):
         x, y, s = np.empty(self.n), np.empty(self.m), np.empty(self.n)
@@ -448,6 +490,8 @@ class IpmSolver:
         y = self.normal_solve(A @ c, reuse_factor=True)
         s = c - A.T @ y
         x = np.asarray(x).ravel(); s = np.asarray(s).ravel()
+        if self.bounded:
+            return self._mehrotra_start_bounded(x, np.asarray(y).ravel(), s)
         x = x + max(-1.5 * x.min(), 0.0)
         s = s + max(-1.5 * s.min(), 0.0)
         xs = 0.5 * float(x @ s)
@@ -456,6 +500,31 @@ class IpmSolver:
         x = x + xs / s.sum()
         s = s + xs / x.sum()
         return x, np.asarray(y).ravel(), s
+
+    def _mehrotra_start_bounded(self, x, y, r):
+        """Mehrotra's recipe extended to 0 <= x <= u -> (x, y, s, w, z): w = u - x; on U the reduced cost r = c - A^T y splits
+        into s = max(r, 0), z = max(-r, 0) (so s - z = r); (x, w) and (s, z) are shifted into the positive orthant together
+        and balanced with x.s + w.z.  Outside U, w = z = 0 and s = r as in the unbounded recipe."""
+        U = np.isfinite(self.ub)
+        w = np.zeros(self.n); z = np.zeros(self.n)
+        w[U] = self.ub[U] - x[U]
+        s = r.copy()
+        s[U] = np.maximum(r[U], 0.0)
+        z[U] = np.maximum(-r[U], 0.0)
+        xmin = min(x.min(), w[U].min())
+        smin = min(s.min(), z[U].min())
+        dp, dd = max(-1.5 * xmin, 0.0), max(-1.5 * smin, 0.0)
+        x = x + dp; w[U] += dp
+        s = s + dd; z[U] += dd
+        xs = 0.5 * float(x @ s + w[U] @ z[U])
+        sx, ss = float(x.sum() + w[U].sum()), float(s.sum() + z[U].sum())
+        if not (np.isfinite(xs) and ss > 0 and sx > 0 and xs > 0):
+            w[U], z[U] = 1.0, 1.0
+            return np.ones(self.n), np.ones(self.m), np.ones(self.n), w, z          # degenerate data: the reference's start
+        x = x + xs / ss; w[U] += xs / ss
+        sx = float(x.sum() + w[U].sum())                 # (after the primal correction, as in the unbounded recipe)
+        s = s + xs / sx; z[U] += xs / sx
+        return x, y, s, w, z
 
     def solve_linear(self, B, rhs):
         """B z = rhs for the CALLER's dense SPD matrix (main.py:176-182): the row order this handle keeps its own A in
@@ -540,8 +609,8 @@ class LockstepBatch:
 
 def lockstep_eligible(solver):
     """Can this IpmSolver join solve_lockstep?  Sparse A on the dense-tile factor, more than 128 rows (the small LPs have their fused
-    single-workgroup kernel, the sparse-factor LPs their tree sweeps)."""
-    return bool(solver.sparse and solver.factor != "sparse" and not solver.schedule()["fused_small"])
+    single-workgroup kernel, the sparse-factor LPs their tree sweeps).  A solver with upper bounds has no lockstep twin."""
+    return bool(solver.sparse and solver.factor != "sparse" and not solver.bounded and not solver.schedule()["fused_small"])
 
 
 def _info(solver, cTlb=0.0):
@@ -562,13 +631,15 @@ def last_info():
 
 
 def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
-                    history=False, **opts):
+                    history=False, ub=None, **opts):
     """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
     start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start().
     history=True adds info["history"], the per-iteration records (IpmSolver.history()).  An LP whose A has more
     than 5 % dependent rows (the QAP family) is solved with the 1e-14 Tikhonov shift, switched on by the library
-    after the first factorization (info["auto_regularized"] == 1; auto_regularize=False keeps it off)."""
+    after the first factorization (info["auto_regularized"] == 1; auto_regularize=False keeps it off).
+    ub: native upper bounds 0 <= x <= ub (+inf = none): info["bounded"] = |U| and, when |U| > 0, info["w"], info["z"]."""
     global _last_info
+    ub = _upper_bounds(ub, np.asarray(c).reshape(-1).shape[0])
     if start == "mehrotra" and not opts.get("regularize") and os.environ.get("IPM_AUTO_REGULARIZE", "1") != "0":
         # the least-squares start factors A A^T: guarded pivots there are dependent rows of A.  Where they are a
         # sizeable fraction of the rows (the QAP family: 9-16 %; every other Netlib file: at most 2.7 %) the guard alone
@@ -580,7 +651,7 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
                 opts = dict(opts, regularize=1e-14)
     import time as _time
     t0 = _time.perf_counter()
-    with IpmSolver(A, b, c, device=device, **opts) as sv:
+    with IpmSolver(A, b, c, device=device, ub=ub, **opts) as sv:
         t1 = _time.perf_counter()
         if start == "mehrotra":
             sv.set_state(*sv.mehrotra_start())
@@ -592,6 +663,9 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
         t2 = _time.perf_counter()
         x, y, s = sv.get_state()
         info = _info(sv)
+        info["bounded"] = sv.bounded
+        if sv.bounded:
+            info["w"], info["z"] = sv.get_bound_state()
         if history:
             info["history"] = sv.history()
         fac = sv.factor
@@ -612,9 +686,10 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     return x, y, s, info
 
 
-def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, **opts):
-    """min c^T x s.t. Ax=b, x>=0 by the Mehrotra predictor-corrector loop on the GPU -> (x, y, s)."""
-    x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, **opts)
+def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, **opts):
+    """min c^T x s.t. Ax=b, x>=0 (and x <= ub where ub is finite) by the Mehrotra predictor-corrector loop on the GPU
+    -> (x, y, s)."""
+    x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub, **opts)
     return x, y, s
 
 
