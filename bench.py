@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- IPM iterations/sec of the HIP Newton/KKT path on the dense synthetic LP.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one full Mehrotra predictor-corrector iteration (stop
 test, form A D^2 A^T, Cholesky, two solves, two ratio tests, update) on the BASELINE.json
@@ -14,11 +14,16 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): the single-LP dense
 not shard ("replicas only"): every rank solves its own replica, no data-path
 collective; value = N*K / max-over-ranks time  (weak scaling).
 
-The LAST stdout line (rank 0) is ONE compact JSON object (< 2 KB: `compact_line`) with the contract keys plus `roofline`,
-`cpu_baseline` and the headline numbers of the Netlib legs; the full record (per-LP tables, notes) is printed as an
-earlier line prefixed `BENCH_DETAIL ` and written to bench_detail.json.  The full record carries `roofline` (the dominant kernel,
-the fp64-MFMA A D^2 A^T contraction, timed with HIP events on the solver's stream inside the
-timed region) and `cpu_baseline` (the NumPy normal-equations oracle on the host cores,
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs
+and prints the result line.  Everything else the benchmark measures or checks runs only with --full: the phase
+breakdown (an untimed pass of its own), the objective check against the reference trajectory, the CPU baselines and
+the Netlib legs (each of which --no-cpu-baseline / --no-netlib still turns off).
+
+The LAST stdout line (rank 0) is ONE compact JSON object (< 2 KB: `compact_line`) with the contract keys plus `roofline`
+and, with --full, `cpu_baseline` and the headline numbers of the Netlib legs; the full record (per-LP tables, notes) is
+printed as an earlier line prefixed `BENCH_DETAIL ` and written to bench_detail.json.  The record carries `roofline` (the
+dominant kernel, the fp64-MFMA A D^2 A^T contraction, timed with HIP events on the solver's stream inside the
+timed region) and, with --full, `cpu_baseline` (the NumPy normal-equations oracle on the host cores,
 bounded sample, rank 0 at N=1 only), `cpu_baseline_reference_algorithm` (one iteration of the
 reference's OWN algorithm -- dense (m+2n) KKT matrix, two LAPACK gesv, main.py:13-21/185-244 --
 restated by the oracle, same rank/N) and the second half of BASELINE.json's metric on this GPU:
@@ -26,7 +31,7 @@ restated by the oracle, same rank/N) and the second half of BASELINE.json's metr
 = the 26-LP parity set, each with its own `roofline`, `cpu_baseline` (one time-bounded oracle pass)
 and a per-LP table carrying setup/solve/teardown seconds and the library's hidden recoveries
 (`timeouts_recovered`, `serial_launches`).  `--workload netlib` runs a set sharded over the ranks
-with the same keys.
+with the same keys (its `cpu_baseline` with --full as well).
 """
 import argparse
 import json
@@ -550,7 +555,7 @@ def netlib_main(args):
                "roofline": netlib_roofline(names, probs, flops, rec, elapsed, world),
                "summary": summ, "wall_seconds": elapsed, "regularize": args.regularize, "start_point": args.start,
                "per_lp": per_lp_table(names, rec)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = netlib_cpu_baseline(names, probs, tol_gap=1e-6 if general else None, max_iter=999 if general else 300)
             cb["gpu_seconds_same_sample"] = float(sum(r[7] for r in rec if names[int(r[0])] in cb["sample_names"]))
             out["cpu_baseline"] = cb
@@ -567,16 +572,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--m", type=int, default=M_DEFAULT)
     ap.add_argument("--n", type=int, default=N_DEFAULT)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-netlib", action="store_true", help="dense workload: skip the Netlib leg of the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, measure and check everything else: dense = the phase breakdown, the "
+                         "objective check, the CPU baselines and the Netlib legs; netlib = the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-netlib", action="store_true", help="dense workload, --full: skip the Netlib legs")
     ap.add_argument("--workload", default="dense", choices=["dense", "netlib"],
                     help="dense: IPM iterations/s on the synthetic LP (default, the headline metric); "
                          "netlib: LPs/s over the committed Netlib fixtures, sharded over the ranks")
     ap.add_argument("--netlib-set", default="all", choices=["all", "parity", "general"],
                     help="all 73 valid standard-form files, the 26 on which the reference converges, or the 72 general-form "
                          "files (benchmarks_full) through the general-form front end")
-    ap.add_argument("--emulate-world", type=int, default=8, help="Netlib: also solve the static shards of this many ranks one after the other on this GPU (0 = skip)")
-    ap.add_argument("--netlib-reps", type=int, default=3, help="dense workload: runs of each Netlib leg of the default line (the median one is reported)")
+    ap.add_argument("--emulate-world", type=int, default=8, help="dense workload, --full: after the Netlib legs, also solve the static shards of this many ranks one after the other on this GPU (0 = skip)")
+    ap.add_argument("--netlib-reps", type=int, default=3, help="dense workload, --full: runs of each Netlib leg (the median one is reported)")
     ap.add_argument("--max-m", type=int, default=1 << 30, help="netlib: skip LPs with more rows")
     ap.add_argument("--workers", type=int, default=8, help="netlib: LPs in flight per GPU, each on one stream (1 = strictly one at a time, with the look-ahead)")
     ap.add_argument("--schedule", default="dynamic", choices=["dynamic", "static"],
@@ -650,10 +658,11 @@ def main():
         dump_outputs(args.dump_outputs, dict({"x": x, "y": y, "s": s},
                                              **{k: v for k, v in st.items() if k != "solve_ms"}))
 
-    # phase breakdown from a separate, untimed pass (nine event records per step cost ~1 %)
-    _, phases_all, _ = run(min(args.steps, RESET_EVERY), profile=2)
-    torch.cuda.synchronize()
     KB = min(args.steps, RESET_EVERY)
+    if args.full:
+        # phase breakdown from a separate, untimed pass (nine event records per step cost ~1 %)
+        _, phases_all, _ = run(KB, profile=2)
+        torch.cuda.synchronize()
 
     if rank == 0:
         K = args.steps
@@ -699,56 +708,58 @@ def main():
                          "fused_formation_and_factorization": fused,
                          "flops_per_launch": flops_form, "avg_launch_ms": form_ms},
             "phases_ms_per_step": {"form": form_ms, "form_is": "the fused worker launch (formation + factorization beside the chain)" if fused else "the formation kernel",
-                                   "factor": phases_all[1] / KB, "trisolve": phases_all[2] / KB,
-                                   "other": phases_all[3] / KB, "device_total": dev_ms / K,
-                                   "note": "form and device_total from the timed region; the rest from an untimed pass"
-                                           + (" on the SERIAL path (formation then factorization, what profiling level 2 runs): its form + factor is what the fused launch replaces" if fused else "")},
+                                   "device_total": dev_ms / K, "note": "form and device_total from the timed region"},
             "whole_iteration": {"flops_per_iteration": flops_per_iteration(m, n),
                                 "tflops": flops_per_iteration(m, n) * its_per_s / ngpu / 1e12,
                                 "frac_of_fp64_mfma_peak": flops_per_iteration(m, n) * its_per_s / ngpu / 1e12 / PEAK_FP64_MFMA_TFLOPS},
             "objective_after_last_block": st["objective"],
         }
-        # guard against a fast-but-wrong kernel variant, on EVERY run: the objective after the first min(steps, 20)
-        # iterations from the start point (its own untimed pass when the last timed block was a partial one) is compared
-        # at the default size with the REFERENCE's own trajectory (tests/golden/dense_syn_4096x8192.npz, generated by
-        # importing the reference); at other sizes with the same iterations under the one-level factorization
-        # (IPM_TWO_LEVEL=0, no overlapped formation) on a second handle
-        kchk = min(args.steps, RESET_EVERY)
-        if args.steps % RESET_EVERY == 0:
-            obj_chk = st["objective"]
-        else:
-            sv.set_profiling(0)
-            sv.init_state(0.0)
-            obj_chk = sv.iterate(kchk)["objective"]
-        fx = os.path.join(ROOT, "tests", "golden", "dense_syn_%dx%d.npz" % (m, n))
-        if os.path.exists(fx):
-            ref_obj = float(np.load(fx)["objective_after_iteration"][kchk - 1])
-            ok = abs(obj_chk - ref_obj) <= 1e-6 * max(1.0, abs(ref_obj))
-            out["objective_check_against"] = "reference trajectory, iteration %d: %.12e" % (kchk, ref_obj)
-        else:
-            sv.close()
-            saved = {k: os.environ.get(k) for k in ("IPM_TWO_LEVEL", "IPM_FUSED_FACTOR")}
-            os.environ["IPM_TWO_LEVEL"] = "0"; os.environ["IPM_FUSED_FACTOR"] = "0"
-            sv1 = ipm.IpmSolver(A, b, c, device=dev)
-            sv1.init_state(0.0)
-            ref_obj = sv1.iterate(kchk)["objective"]
-            sv1.close()
-            for k, v in saved.items():
-                if v is None:
-                    del os.environ[k]
-                else:
-                    os.environ[k] = v
-            ok = abs(obj_chk - ref_obj) <= 1e-9 * max(1.0, abs(ref_obj))
-            out["objective_check_against"] = "same %d iterations with IPM_TWO_LEVEL=0 IPM_FUSED_FACTOR=0: %.12e" % (kchk, ref_obj)
-        out["objective_check"] = "ok" if ok else "MISMATCH"
-        out["objective_checked"] = obj_chk
-        if not ok:
-            print("bench: objective after %d iterations is %.12e, expected %.12e" % (kchk, obj_chk, ref_obj), file=sys.stderr)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["phases_ms_per_step"].update(
+                factor=phases_all[1] / KB, trisolve=phases_all[2] / KB, other=phases_all[3] / KB,
+                note="form and device_total from the timed region; the rest from an untimed pass"
+                + (" on the SERIAL path (formation then factorization, what profiling level 2 runs): its form + factor is what the fused launch replaces" if fused else ""))
+            # guard against a fast-but-wrong kernel variant: the objective after the first min(steps, 20)
+            # iterations from the start point (its own untimed pass when the last timed block was a partial one) is compared
+            # at the default size with the REFERENCE's own trajectory (tests/golden/dense_syn_4096x8192.npz, generated by
+            # importing the reference); at other sizes with the same iterations under the one-level factorization
+            # (IPM_TWO_LEVEL=0, no overlapped formation) on a second handle
+            kchk = min(args.steps, RESET_EVERY)
+            if args.steps % RESET_EVERY == 0:
+                obj_chk = st["objective"]
+            else:
+                sv.set_profiling(0)
+                sv.init_state(0.0)
+                obj_chk = sv.iterate(kchk)["objective"]
+            fx = os.path.join(ROOT, "tests", "golden", "dense_syn_%dx%d.npz" % (m, n))
+            if os.path.exists(fx):
+                ref_obj = float(np.load(fx)["objective_after_iteration"][kchk - 1])
+                ok = abs(obj_chk - ref_obj) <= 1e-6 * max(1.0, abs(ref_obj))
+                out["objective_check_against"] = "reference trajectory, iteration %d: %.12e" % (kchk, ref_obj)
+            else:
+                sv.close()
+                saved = {k: os.environ.get(k) for k in ("IPM_TWO_LEVEL", "IPM_FUSED_FACTOR")}
+                os.environ["IPM_TWO_LEVEL"] = "0"; os.environ["IPM_FUSED_FACTOR"] = "0"
+                sv1 = ipm.IpmSolver(A, b, c, device=dev)
+                sv1.init_state(0.0)
+                ref_obj = sv1.iterate(kchk)["objective"]
+                sv1.close()
+                for k, v in saved.items():
+                    if v is None:
+                        del os.environ[k]
+                    else:
+                        os.environ[k] = v
+                ok = abs(obj_chk - ref_obj) <= 1e-9 * max(1.0, abs(ref_obj))
+                out["objective_check_against"] = "same %d iterations with IPM_TWO_LEVEL=0 IPM_FUSED_FACTOR=0: %.12e" % (kchk, ref_obj)
+            out["objective_check"] = "ok" if ok else "MISMATCH"
+            out["objective_checked"] = obj_chk
+            if not ok:
+                print("bench: objective after %d iterations is %.12e, expected %.12e" % (kchk, obj_chk, ref_obj), file=sys.stderr)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(A, b, c)
             if (m, n) == (M_DEFAULT, N_DEFAULT):
                 out["cpu_baseline_reference_algorithm"] = cpu_baseline_reference_algorithm(A, b, c)
-        if world == 1 and not args.no_netlib and (m, n) == (M_DEFAULT, N_DEFAULT):
+        if args.full and world == 1 and not args.no_netlib and (m, n) == (M_DEFAULT, N_DEFAULT):
             # second half of the headline metric on the same GPU, eight LPs in flight (one stream each):
             #   netlib_all = the metric's own config, BASELINE.json configs[3]: ALL 73 valid benchmarks/ LPs (the loop of
             #                script.py:147-173 over the suite);

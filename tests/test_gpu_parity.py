@@ -1060,6 +1060,40 @@ print("RCCL_ONE_RANK_OK")
     assert line["summary"]["timeouts_recovered"] == 0 and line["summary"]["serial_launches"] == 0
 
 
+def test_bench_plain_and_full_lines(tmp_path):
+    """bench.py, dense workload, in its own processes: a plain run prints the contract keys and the roofline of its timed
+    steps and dumps the iterate, but runs none of the extras; --full adds the untimed phase pass and the objective check
+    (here against a second handle: no reference trajectory is committed for this size)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--m", "1024", "--n", "2048", "--steps", "3",
+            "--warmup", "1"]
+
+    def run(extra):
+        out = subprocess.run(base + extra, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        lines = out.stdout.strip().splitlines()
+        detail = [ln for ln in lines if ln.startswith("BENCH_DETAIL ")]
+        assert len(detail) == 1
+        return json.loads(lines[-1]), json.loads(detail[0][len("BENCH_DETAIL "):])
+
+    plain, plain_detail = run(["--dump-outputs", str(tmp_path / "dump")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in plain, k
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    for k in ("objective_check", "cpu_baseline", "cpu_baseline_reference_algorithm", "netlib_all", "netlib"):
+        assert k not in plain, k
+    for nm, size in (("x", 2048), ("y", 1024), ("s", 2048)):
+        v = np.load(tmp_path / "dump" / (nm + ".npy"))
+        assert v.size == size and np.all(np.isfinite(v))
+    assert not set(("factor", "trisolve", "other")) & set(plain_detail["phases_ms_per_step"])
+    full, full_detail = run(["--full", "--no-netlib", "--no-cpu-baseline"])
+    assert full["objective_check"] == "ok" and "cpu_baseline" not in full and "netlib_all" not in full
+    assert set(("factor", "trisolve", "other")) <= set(full_detail["phases_ms_per_step"])
+
+
 def test_plain_c_driver():
     """examples/c_driver.c: the C ABI from plain C in its own process (no Python, no torch; the library allocates its
     workspace and stream): the reference's ex1 optimum -775 (main.py:1253) and a random 300 x 700 LP."""

@@ -11,7 +11,7 @@ if [ "$1" != "skip_tests" ]; then
   timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/a_pytest.log 2>&1 || { tail -40 $O/a_pytest.log; exit 1; }
   tail -2 $O/a_pytest.log
 fi
-timeout -k 10 600 python bench.py > $O/a_bench.json 2> $O/a_bench.err || { tail -20 $O/a_bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/a_bench.json 2> $O/a_bench.err || { tail -20 $O/a_bench.err; exit 1; }
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/a_bench.json").read().strip().splitlines()[-1])

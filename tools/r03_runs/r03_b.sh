@@ -6,7 +6,7 @@ R=$PWD; O=$R/gpurun_out; mkdir -p $O
 timeout -k 10 600 python -m pytest tests/test_gpu_fused_factor.py -x -q > $O/b_pytest.log 2>&1 || { tail -40 $O/b_pytest.log; exit 1; }
 tail -2 $O/b_pytest.log
 for FF in 0 1; do
-  IPM_FUSED_FACTOR=$FF timeout -k 10 300 python bench.py --no-netlib --no-cpu-baseline --steps 40 > $O/b_bench_ff$FF.json 2> $O/b_bench_ff$FF.err || { tail -5 $O/b_bench_ff$FF.err; exit 1; }
+  IPM_FUSED_FACTOR=$FF timeout -k 10 300 python bench.py --full --no-netlib --no-cpu-baseline --steps 40 > $O/b_bench_ff$FF.json 2> $O/b_bench_ff$FF.err || { tail -5 $O/b_bench_ff$FF.err; exit 1; }
   python - $FF <<'PY'
 import json,sys
 d=json.loads(open("gpurun_out/b_bench_ff%s.json"%sys.argv[1]).read().strip().splitlines()[-1])

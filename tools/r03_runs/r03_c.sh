@@ -7,7 +7,7 @@ IPM_FF_DEBUG=1 timeout -k 10 600 python -m pytest tests/test_gpu_fused_factor.py
 tail -1 $O/c_pytest.log
 run() {  # name, env...
   local name=$1; shift
-  env "$@" timeout -k 10 200 python bench.py --no-netlib --no-cpu-baseline --steps 40 > $O/c_$name.json 2> $O/c_$name.err || { tail -3 $O/c_$name.err; return 1; }
+  env "$@" timeout -k 10 200 python bench.py --full --no-netlib --no-cpu-baseline --steps 40 > $O/c_$name.json 2> $O/c_$name.err || { tail -3 $O/c_$name.err; return 1; }
   python - $name <<'PY'
 import json,sys
 d=json.loads(open("gpurun_out/c_%s.json"%sys.argv[1]).read().strip().splitlines()[-1])

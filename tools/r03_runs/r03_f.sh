@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 O=gpurun_out; mkdir -p $O
 run() {
   local name=$1; shift
-  env "$@" timeout -k 10 200 python bench.py --no-netlib --no-cpu-baseline --steps 40 > $O/f2_$name.json 2> $O/f2_$name.err || { tail -3 $O/f2_$name.err; return 1; }
+  env "$@" timeout -k 10 200 python bench.py --full --no-netlib --no-cpu-baseline --steps 40 > $O/f2_$name.json 2> $O/f2_$name.err || { tail -3 $O/f2_$name.err; return 1; }
   python - $name <<'PY'
 import json,sys
 d=json.loads(open("gpurun_out/f2_%s.json"%sys.argv[1]).read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ if [ "$1" != "skip_tests" ]; then
   timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/f_pytest.log 2>&1 || { tail -40 $O/f_pytest.log; exit 1; }
   tail -2 $O/f_pytest.log
 fi
-timeout -k 10 600 python bench.py > $O/f_bench.json 2> $O/f_bench.err || { tail -20 $O/f_bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/f_bench.json 2> $O/f_bench.err || { tail -20 $O/f_bench.err; exit 1; }
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/f_bench.json").read().strip().splitlines()[-1])
@@ -47,12 +47,12 @@ PY
 rm -f $O/f_trace/*.db $O/f_trace/*/*.db
 IPM_FF_PROF=1 timeout -k 10 200 python bench.py --no-netlib --no-cpu-baseline --steps 20 --warmup 2 2>&1 >/dev/null | grep -A10 "ff prof" > $O/f_cycle_profile.txt; cat $O/f_cycle_profile.txt
 bash tools/ff_sizes.sh > $O/f_sizes.txt 2>&1; cat $O/f_sizes.txt
-timeout -k 10 400 python bench.py --m 16384 --n 32768 --steps 5 --warmup 1 --no-netlib --no-cpu-baseline > $O/f_dense16k.json 2> $O/f_dense16k.err || { tail -5 $O/f_dense16k.err; exit 1; }
+timeout -k 10 400 python bench.py --full --m 16384 --n 32768 --steps 5 --warmup 1 --no-netlib --no-cpu-baseline > $O/f_dense16k.json 2> $O/f_dense16k.err || { tail -5 $O/f_dense16k.err; exit 1; }
 python -c "
 import json
 d=json.loads(open('gpurun_out/f_dense16k.json').read().strip().splitlines()[-1]); print('16k', d['value'], d['roofline']['frac'], d['roofline']['traffic_source'], d['objective_check'])"
 # the default line once more, now that the PMC pass of THIS kernel source is in profiles/ (roofline.traffic)
-timeout -k 10 600 python bench.py > $O/f_bench_final.json 2> $O/f_bench_final.err || { tail -20 $O/f_bench_final.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/f_bench_final.json 2> $O/f_bench_final.err || { tail -20 $O/f_bench_final.err; exit 1; }
 python -c "
 import json
 d=json.loads(open('gpurun_out/f_bench_final.json').read().strip().splitlines()[-1]); print('final', round(d['value'],2), d['roofline']['frac'], d['roofline']['traffic'], d['roofline']['traffic_source'], d['objective_check'], round(d['netlib_all']['value'],2), round(d['netlib']['value'],2))"

@@ -25,7 +25,7 @@ import json
 d=json.loads(open('gpurun_out/g_netlib_w$W.json').read().strip().splitlines()[-1]); s=d.get('summary', d.get('config', {}))
 print('workers $W:', round(d['value'],2), 'LPs/s, wall', round(d.get('wall_seconds', 0),3))"
 done
-timeout -k 10 400 python bench.py --m 16384 --n 32768 --steps 5 --warmup 1 --no-netlib --no-cpu-baseline > $O/g_dense16k.json 2> $O/g_dense16k.err || { tail -5 $O/g_dense16k.err; exit 1; }
+timeout -k 10 400 python bench.py --full --m 16384 --n 32768 --steps 5 --warmup 1 --no-netlib --no-cpu-baseline > $O/g_dense16k.json 2> $O/g_dense16k.err || { tail -5 $O/g_dense16k.err; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/g16k_trace $O/g16k_pmc_*
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/g16k_trace -o p -- python3 $R/bench.py --m 16384 --n 32768 --steps 5 --warmup 1 --no-netlib --no-cpu-baseline > $O/g16k_trace.log 2>&1 || { tail -5 $O/g16k_trace.log; exit 1; }
@@ -38,7 +38,7 @@ python tools/prof_db_stats.py $O/g16k_trace 16 > $O/g16k_kernel_stats.txt; head 
 rm -f $O/g16k_trace/*.db $O/g16k_trace/*/*.db
 python tools/pmc_form_kernel.py --out $O/g16k_pmc_form_kernel.json --shape 16384 32768 $O/g16k_pmc_* | tail -14
 cp $O/g16k_pmc_form_kernel.json profiles/r03_pmc_form_kernel_16k.json
-timeout -k 10 400 python bench.py --m 16384 --n 32768 --steps 5 --warmup 1 --no-netlib --no-cpu-baseline > $O/g_dense16k.json 2> $O/g_dense16k.err || { tail -5 $O/g_dense16k.err; exit 1; }
+timeout -k 10 400 python bench.py --full --m 16384 --n 32768 --steps 5 --warmup 1 --no-netlib --no-cpu-baseline > $O/g_dense16k.json 2> $O/g_dense16k.err || { tail -5 $O/g_dense16k.err; exit 1; }
 python -c "
 import json
 d=json.loads(open('gpurun_out/g_dense16k.json').read().strip().splitlines()[-1]); print('16k', d['value'], d['roofline']['frac'], d['roofline']['traffic'], d['roofline']['traffic_source'], d['objective_check'], d['phases_ms_per_step'])"

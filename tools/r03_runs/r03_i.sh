@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 O=gpurun_out; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/i_pytest.log 2>&1 || { tail -40 $O/i_pytest.log; exit 1; }
 tail -2 $O/i_pytest.log
-timeout -k 10 600 python bench.py > $O/i_bench.json 2> $O/i_bench.err || { tail -20 $O/i_bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/i_bench.json 2> $O/i_bench.err || { tail -20 $O/i_bench.err; exit 1; }
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/i_bench.json").read().strip().splitlines()[-1])

@@ -10,7 +10,7 @@ for T in 0 1; do
   IPM_RAGGED_GROUPS=$T timeout -k 10 300 python tools/sparse_factor_check.py --no-sparse PILOT87 MAROS-R7 BNL2 PILOT 2>&1 | grep -v "^$\|amdgpu.ids" | awk -v t=$T '{print "IPM_RAGGED_GROUPS=" t " lone", $1, $3, $4, $(NF-2), $(NF-1)}'
   for mn in "3584 7168" "4480 8960"; do
     set -- $mn
-    IPM_RAGGED_GROUPS=$T timeout -k 10 200 python bench.py --m $1 --n $2 --no-netlib --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | python -c "
+    IPM_RAGGED_GROUPS=$T timeout -k 10 200 python bench.py --full --m $1 --n $2 --no-netlib --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('IPM_RAGGED_GROUPS=$T dense %5d x %5d: %7.2f it/s  %.3f ms  %s' % ($1, $2, d['value'], d['ms_per_step'], d['objective_check']))"
   done

@@ -9,7 +9,7 @@ if [ "$1" != "skip_tests" ]; then
   tail -2 $O/r04_final_pytest.log
 fi
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
-timeout -k 10 600 python bench.py > $O/r04_bench_first.log 2> $O/r04_bench_first.err || { tail -20 $O/r04_bench_first.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/r04_bench_first.log 2> $O/r04_bench_first.err || { tail -20 $O/r04_bench_first.err; exit 1; }
 tail -1 $O/r04_bench_first.log | wc -c
 timeout -k 10 300 python bench.py --workload netlib --netlib-set all > $O/r04_final_netlib_all73.log 2> $O/r04_final_netlib_all73.err || { tail -5 $O/r04_final_netlib_all73.err; exit 1; }
 tail -1 $O/r04_final_netlib_all73.log | cut -c1-300
@@ -28,7 +28,7 @@ python tools/pmc_form_kernel.py --kernel form_factor_roles_kernel --out $O/r04_p
 cp $O/r04_pmc_form_kernel_fused.json profiles/r04_pmc_form_kernel_fused.json
 rm -rf $O/f_trace $O/f_pmc_*
 # the default line once more, now that the PMC pass of THIS kernel source is in profiles/ (roofline.traffic)
-timeout -k 10 600 python bench.py > $O/r04_final_bench.log 2> $O/r04_final_bench.err || { tail -20 $O/r04_final_bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/r04_final_bench.log 2> $O/r04_final_bench.err || { tail -20 $O/r04_final_bench.err; exit 1; }
 tail -1 $O/r04_final_bench.log > $O/r04_final_bench.json
 python - <<'PY'
 import json

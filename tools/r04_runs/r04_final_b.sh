@@ -4,7 +4,7 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 R=$PWD; O=$R/gpurun_out; mkdir -p $O
-timeout -k 10 500 python bench.py --m 16384 --n 32768 --steps 5 --warmup 1 --no-netlib > $O/r04_final_dense16k.log 2> $O/r04_final_dense16k.err || { tail -5 $O/r04_final_dense16k.err; exit 1; }
+timeout -k 10 500 python bench.py --full --m 16384 --n 32768 --steps 5 --warmup 1 --no-netlib > $O/r04_final_dense16k.log 2> $O/r04_final_dense16k.err || { tail -5 $O/r04_final_dense16k.err; exit 1; }
 tail -1 $O/r04_final_dense16k.log | cut -c1-900
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/g_trace $O/g_pmc_*
@@ -19,7 +19,7 @@ python tools/pmc_form_kernel.py --kernel adat_syrk_kernel --out $O/r04_pmc_form_
 cp $O/r04_pmc_form_kernel_16k.json profiles/r04_pmc_form_kernel_16k.json
 rm -rf $O/g_trace $O/g_pmc_*
 # config 5 once more with the PMC file of this source in profiles/ (roofline.traffic)
-timeout -k 10 500 python bench.py --m 16384 --n 32768 --steps 5 --warmup 1 --no-netlib > $O/r04_final_dense16k.log 2> $O/r04_final_dense16k.err || { tail -5 $O/r04_final_dense16k.err; exit 1; }
+timeout -k 10 500 python bench.py --full --m 16384 --n 32768 --steps 5 --warmup 1 --no-netlib > $O/r04_final_dense16k.log 2> $O/r04_final_dense16k.err || { tail -5 $O/r04_final_dense16k.err; exit 1; }
 tail -1 $O/r04_final_dense16k.log > $O/r04_final_dense16k.json; cut -c1-900 $O/r04_final_dense16k.json
 timeout -k 10 300 python bench.py --m 8192 --n 16384 --steps 10 --warmup 2 --no-netlib --no-cpu-baseline > $O/r04_final_dense8k.log 2> $O/r04_final_dense8k.err || { tail -5 $O/r04_final_dense8k.err; exit 1; }
 tail -1 $O/r04_final_dense8k.log > $O/r04_final_dense8k.json; cut -c1-500 $O/r04_final_dense8k.json

@@ -1,6 +1,6 @@
 # the default bench line's Netlib legs run three times in one process: do repeated runs keep their speed?  (stream reuse, batch.py)
 cd "$GRAFT_REPO_ROOT"
-python bench.py --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 print('dense %.1f it/s' % d['value'])
