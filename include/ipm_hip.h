@@ -48,7 +48,11 @@ enum {
     IPM_STATUS_RUNNING = 0,    /* stop test still true                     main.py:780 */
     IPM_STATUS_CONVERGED = 1,  /* check_optimality() returned False        main.py:162-173 */
     IPM_STATUS_MAX_ITER = 2,   /* k reached the cap (5000/50000)           main.py:725,780 */
-    IPM_STATUS_NAN = 3         /* non-finite iterate / residual            main.py:1141-1148 */
+    IPM_STATUS_NAN = 3,        /* non-finite iterate / residual            main.py:1141-1148 */
+    /* (4 is taken by an internal status of the fused small-LP kernel) */
+    /* With IPM_FLAG_DETECT_INFEASIBILITY only (ipm_get_certificate gives the certificate): */
+    IPM_STATUS_PRIMAL_INFEASIBLE = 5,  /* a Farkas ray y, z of the dual was found: the LP has no feasible point */
+    IPM_STATUS_DUAL_INFEASIBLE = 6     /* a ray x of the primal was found: the LP is unbounded (if feasible) */
 };
 
 /* ipm_options.flags */
@@ -83,7 +87,19 @@ enum {
     /* The handle is created for ipm_solve_batch (the LOCKSTEP batch: iteration k of several LPs in the same launches): implies
      * IPM_FLAG_SINGLE_STREAM | IPM_FLAG_NO_DEVICE_POLLING and block-step triangular solves, so that every launch of its iteration has
      * a batched twin.  Such a handle still works with every other entry point (ipm_solve included: same arithmetic, one LP). */
-    IPM_FLAG_LOCKSTEP = 16
+    IPM_FLAG_LOCKSTEP = 16,
+    /* Detect infeasible and unbounded LPs.  At every stop test whose convergence test says "continue" (never
+     * under ipm_iterate) the iterate (x, y, s, w, z) is tested, with beta = b^T y - u_U^T z_U and gamma = -c^T x:
+     *   primal infeasible (status 5): beta > 0 and max_j max((A^T y - z)_j, 0) <= eps_p * beta;
+     *     certificate y / beta, z / beta:  A^T y^ - z^ <= eps_p, z^ >= 0, b^T y^ - u^T z^ = 1;
+     *   dual infeasible (status 6): gamma > 0 and max(||A x||_inf, max_{j in U} x_j) <= eps_d * gamma;
+     *     certificate x / gamma:  x^ >= 0, ||A x^||_inf <= eps_d, x^_U <= eps_d, c^T x^ = -1.
+     * eps_p = eps_d = 1e-8 unless ipm_set_infeasibility_tol says otherwise.  The tests only read what the iteration computes
+     * anyway (five extra reductions per stop test); they change no iterate, so a flagged solve follows the unflagged one bit for
+     * bit until it stops.  They certify what the infeasible-start iteration runs towards and do not guarantee detection: an LP
+     * whose iterate overflows before its ray is clean still ends in IPM_STATUS_NAN.  Without the flag the kernels are
+     * exactly those of a build without this feature.  A flagged handle may join the lockstep batch, next to unflagged ones. */
+    IPM_FLAG_DETECT_INFEASIBILITY = 32
 };
 
 typedef struct ipm_handle ipm_handle;
@@ -232,6 +248,15 @@ const char* ipm_batch_last_error(const ipm_batch* b);
 int ipm_batch_add(ipm_batch* b, ipm_handle* h, double tol_p, double tol_d, double tol_gap, int32_t max_iter, int32_t* index);
 int ipm_batch_step(ipm_batch* b, int32_t* finished, int32_t cap, int32_t* n_finished, int32_t* n_active);
 int ipm_batch_stats(ipm_batch* b, int32_t index, ipm_stats* stats);
+/* Tolerances of the infeasibility tests (IPM_FLAG_DETECT_INFEASIBILITY), each in (0, 1); default 1e-8 / 1e-8.  Takes effect
+ * with the next solve (for the lockstep batch: with the next ipm_batch_add). */
+int ipm_set_infeasibility_tol(ipm_handle* h, double eps_p, double eps_d);
+/* The certificate of the last solve, which must have ended in IPM_STATUS_PRIMAL_INFEASIBLE or IPM_STATUS_DUAL_INFEASIBLE
+ * (IPM_ERR_STATE otherwise).  Host arrays, each may be NULL: y (length m, in the handle's row order) and z (length n, 0 outside
+ * the bounded set) = (y, z) / beta for status 5, zeros for 6; x (length n) = x / gamma for status 6, zeros for 5.
+ * info (may be NULL): {kind (5 / 6), normalisation (beta / gamma), measured violation of the normalised certificate
+ * (max (A^T y^ - z^)_+, or max(||A x^||_inf, max x^_U)), iteration k of the detection}. */
+int ipm_get_certificate(ipm_handle* h, double* y, double* z, double* x, double info[4]);
 /* Per-iteration records of the last ipm_solve / ipm_iterate, oldest first: min(iterations, IPM_HISTORY_CAPACITY,
  * capacity) records are written to `out` (host) and their number to *count. */
 int ipm_get_history(ipm_handle* h, ipm_iter_record* out, int32_t capacity, int32_t* count);

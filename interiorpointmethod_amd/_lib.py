@@ -18,17 +18,19 @@ EXPORTS = [
     "ipm_abi_version", "ipm_device_count", "ipm_default_options", "ipm_workspace_bytes", "ipm_workspace_bytes_csc", "ipm_workspace_bytes_opts",
     "ipm_create", "ipm_destroy", "ipm_last_error", "ipm_set_A_dense", "ipm_set_A_csc",
     "ipm_set_bc", "ipm_set_state", "ipm_get_state", "ipm_init_state", "ipm_set_bounds", "ipm_set_bound_state", "ipm_get_bound_state", "ipm_newton_direction",
-    "ipm_iterate", "ipm_solve", "ipm_solve_batch", "ipm_batch_create", "ipm_batch_destroy", "ipm_batch_last_error", "ipm_batch_add", "ipm_batch_step", "ipm_batch_stats", "ipm_get_history", "ipm_get_schedule", "ipm_order_rows", "ipm_get_factor_info", "ipm_solve_linear", "ipm_lu_solve", "ipm_lu_factor", "ipm_normal_solve", "ipm_form_normal_matrix", "ipm_get_factor",
+    "ipm_iterate", "ipm_solve", "ipm_solve_batch", "ipm_batch_create", "ipm_batch_destroy", "ipm_batch_last_error", "ipm_batch_add", "ipm_batch_step", "ipm_batch_stats", "ipm_get_history", "ipm_set_infeasibility_tol", "ipm_get_certificate", "ipm_get_schedule", "ipm_order_rows", "ipm_get_factor_info", "ipm_solve_linear", "ipm_lu_solve", "ipm_lu_factor", "ipm_normal_solve", "ipm_form_normal_matrix", "ipm_get_factor",
     "ipm_set_profiling", "ipm_get_phase_ms", "ipm_debug_get_stamps", "ipm_debug_ff_schedule", "ipm_debug_ff_trace", "ipm_debug_get_block_inverse", "ipm_debug_ls_merge",
 ]
 
 IPM_OK = 0
 STATUS_RUNNING, STATUS_CONVERGED, STATUS_MAX_ITER, STATUS_NAN = 0, 1, 2, 3
+STATUS_PRIMAL_INFEASIBLE, STATUS_DUAL_INFEASIBLE = 5, 6     # with FLAG_DETECT_INFEASIBILITY only
 FLAG_NO_DEVICE_POLLING = 1      # include/ipm_hip.h: IPM_FLAG_NO_DEVICE_POLLING
 FLAG_NO_AUTO_REGULARIZE = 2     # include/ipm_hip.h: IPM_FLAG_NO_AUTO_REGULARIZE
 FLAG_SINGLE_STREAM = 4          # include/ipm_hip.h: IPM_FLAG_SINGLE_STREAM
 FLAG_SPARSE_FACTOR = 8          # include/ipm_hip.h: IPM_FLAG_SPARSE_FACTOR
 FLAG_LOCKSTEP = 16              # include/ipm_hip.h: IPM_FLAG_LOCKSTEP
+FLAG_DETECT_INFEASIBILITY = 32  # include/ipm_hip.h: IPM_FLAG_DETECT_INFEASIBILITY
 ERR_WORKSPACE = -4
 ABI_VERSION = 4
 HISTORY_CAPACITY = 1024         # IPM_HISTORY_CAPACITY
@@ -136,6 +138,8 @@ def load():
     lib.ipm_batch_stats.argtypes = [vp, i32, C.POINTER(Stats)]
     lib.ipm_get_history.argtypes = [vp, C.POINTER(IterRecord), i32, C.POINTER(i32)]
     lib.ipm_get_schedule.argtypes = [vp, C.POINTER(i32)]
+    lib.ipm_set_infeasibility_tol.argtypes = [vp, dbl, dbl]
+    lib.ipm_get_certificate.argtypes = [vp, pd, pd, pd, pd]
     lib.ipm_order_rows.argtypes = [i64, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), pd]
     lib.ipm_get_factor_info.argtypes = [vp, C.POINTER(i64)]
     lib.ipm_solve_linear.argtypes = [vp, pd, i64, pd, pd, C.POINTER(i32)]

@@ -76,15 +76,17 @@ def _guarded(solve_fn, problem, **kw):
 
 
 def solve_one(problem, device=0, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, concurrent=False, start="reference",
-              tol_gap=None):
-    """Solve one LP (A, b, c) on `device` with the HIP path -> dict of statistics."""
+              tol_gap=None, detect_infeasibility=False):
+    """Solve one LP (A, b, c) on `device` with the HIP path -> dict of statistics.  detect_infeasibility: the record's status
+    may be 5 (primal infeasible) or 6 (dual infeasible, i.e. unbounded); DESIGN.md 4-C."""
     from . import _lib
     from .solver import solve_with_info
     A, b, c = problem
     t0 = time.perf_counter()
     try:
         _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device,
-                                        regularize=regularize, concurrent=concurrent, start=start, tol_gap=tol_gap)
+                                        regularize=regularize, concurrent=concurrent, start=start, tol_gap=tol_gap,
+                                        detect_infeasibility=detect_infeasibility)
         info = dict(info)
     except Exception as e:          # every failure becomes a record: the rank must still reach the all-gather
         import sys
@@ -195,7 +197,8 @@ def _lockstep_streams(device, n):
     return have[:n]
 
 
-def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, tol_gap=None, **_):
+def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, tol_gap=None,
+                         detect_infeasibility=False, **_):
     """Solve problems[i] for i in ids on this rank's GPU with the LOCKSTEP BATCH -> (len(ids), NF) records.
 
     `workers` host threads prepare the LPs (host analysis, handle, upload), largest first.  An LP of more than 128 rows on the
@@ -218,7 +221,7 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
         from .solver import solve_with_info
         A, b, c = problem
         _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, regularize=regularize,
-                                        concurrent=True, tol_gap=tol_gap, prepared=prepared)
+                                        concurrent=True, tol_gap=tol_gap, prepared=prepared, detect_infeasibility=detect_infeasibility)
         return dict(info)
 
     def wants_lockstep(i):
@@ -234,7 +237,8 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
             # would take the sparse one: inside a batch an LP whose program is shorter than the class leader's adds no launches
             prepared = prepare(A, b, c, factor=("dense" if wants_lockstep(i) and A.shape[0] <= LOCKSTEP_DENSE_ROWS else None))
             if wants_lockstep(i) and prepared.factor != "sparse":
-                sv = IpmSolver(A, b, c, device=device, regularize=regularize, lockstep=True, concurrent=True, prepared=prepared)
+                sv = IpmSolver(A, b, c, device=device, regularize=regularize, lockstep=True, concurrent=True, prepared=prepared,
+                               detect_infeasibility=detect_infeasibility)
                 if lockstep_eligible(sv):
                     sv.init_state(y0)
                     ready.put((row, i, sv, time.perf_counter() - t0))
@@ -525,7 +529,8 @@ def summarize(records):
     status = records[:, 1]
     conv = status == 1.0
     return dict(n=int(records.shape[0]), converged=int(conv.sum()), max_iter=int((status == 2.0).sum()),
-                nan=int((status == 3.0).sum()), invalid=int((status == STATUS_INVALID_INPUT).sum()),
+                nan=int((status == 3.0).sum()), primal_infeasible=int((status == 5.0).sum()),
+                dual_infeasible=int((status == 6.0).sum()), invalid=int((status == STATUS_INVALID_INPUT).sum()),
                 errors=int((status == STATUS_ERROR).sum()),
                 total_iterations=int(records[:, 2].sum()), solve_seconds_sum=float(records[:, 7].sum()),
                 pivots_fixed=int(records[:, 8].sum()),

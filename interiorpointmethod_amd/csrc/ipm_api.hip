@@ -170,6 +170,11 @@ struct ipm_handle {
     bool bnd = false;                     // a finite bound is set: the bounded kernel instantiations run
     int bnd_nU = 0;                       // |U|
     double* bnd_mem = nullptr;            // u | w | z | dwa | dza | dw | dz | qz | roll-back w | roll-back z
+    // infeasibility detection (IPM_FLAG_DETECT_INFEASIBILITY): the Detect kernel instantiations run
+    bool detect = false;
+    double det_eps_p = 1e-8, det_eps_d = 1e-8;   // ipm_set_infeasibility_tol
+    double* det = nullptr;                // [4] record of the last detection (workspace): kind, normalisation, violation, k
+    double* cert_mem = nullptr;           // x | y | z of ipm_get_certificate (own allocation, made on first use)
     int* fixed = nullptr;
     Scalars* h_sc = nullptr;          // pinned host mirror
     bool haveA = false, haveBC = false, haveState = false, predictor_valid = false;
@@ -280,7 +285,7 @@ static GemmNT gemm_defaults() {
 struct Layout {
     int64_t mp, np;
     int nblk, rc_chunks, rows_per_chunk, vblk;
-    size_t off_A, off_B, off_inv, off_nvec, off_mvec, off_atp, off_part, off_sc, off_fixed, off_hist, off_snap, off_slab, total;
+    size_t off_A, off_B, off_inv, off_nvec, off_mvec, off_atp, off_part, off_det, off_sc, off_fixed, off_hist, off_snap, off_slab, total;
     size_t off_rowptr, off_colind, off_rval, off_colptr, off_rowind, off_cval, off_order;
 };
 static const int N_NVEC = 11;   // x s c rc d v q dxa dsa dx ds
@@ -317,7 +322,8 @@ static Layout make_layout(int64_t m, int64_t n, int64_t sparse_nnz = 0, bool no_
     L.off_nvec = take(sizeof(double) * L.np * N_NVEC);
     L.off_mvec = take(sizeof(double) * L.mp * N_MVEC);
     L.off_atp = take(sizeof(double) * L.rc_chunks * L.np);
-    L.off_part = take(sizeof(double) * P_NSLOT * MAXPART);
+    L.off_part = take(sizeof(double) * P_NSLOT_DETECT * MAXPART);     // (the slots of the infeasibility tests included)
+    L.off_det = take(sizeof(double) * 4);
     L.off_sc = take(sizeof(Scalars));
     L.off_fixed = take(256);
     L.off_hist = take(sizeof(IterRec) * HIST_CAP);
@@ -447,6 +453,7 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     h->dya = mv + 5 * L.mp; h->dy = mv + 6 * L.mp;
     h->atp = (double*)(base + L.off_atp);
     h->part = (double*)(base + L.off_part);
+    h->det = (double*)(base + L.off_det);
     h->sc = (Scalars*)(base + L.off_sc);
     h->fixed = (int*)(base + L.off_fixed);
     h->hist = (IterRec*)(base + L.off_hist);
@@ -486,6 +493,7 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     CREATE_TRY(hipEventCreate(&h->ev0));
     CREATE_TRY(hipEventCreate(&h->ev1));
     if (const char* e = getenv("IPM_LOOKAHEAD")) h->lookahead = atoi(e);
+    h->detect = (h->opt.flags & IPM_FLAG_DETECT_INFEASIBILITY) != 0;
     if (h->opt.flags & IPM_FLAG_LOCKSTEP) { h->lockstep = 1; h->opt.flags |= IPM_FLAG_SINGLE_STREAM | IPM_FLAG_NO_DEVICE_POLLING; }
     if (h->opt.flags & IPM_FLAG_SINGLE_STREAM) h->lookahead = 0;
     if (const char* e = getenv("IPM_GROUPED_TRSV")) h->grouped_trsv = atoi(e);
@@ -605,7 +613,7 @@ extern "C" int ipm_destroy(ipm_handle* h) {
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->h_sc) { std::lock_guard<std::mutex> lock(g_hsc_mutex); g_hsc_pool.push_back(h->h_sc); h->h_sc = nullptr; }
-    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
+    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
         dev_free(h->device, h->stream, p);
     ff_release(h);
     free_sparse_factor(h);
@@ -1156,6 +1164,7 @@ extern "C" int ipm_set_state(ipm_handle* h, const double* x, const double* y, co
     HIP_TRY(h, hipMemcpyAsync(h->s, s, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->haveState = true; h->predictor_valid = false; h->fresh_state = true;
+    h->h_sc->status = 0;                                       // (a certificate describes the iterate of its detection only)
     return IPM_OK;
 }
 
@@ -1253,6 +1262,7 @@ extern "C" int ipm_init_state(ipm_handle* h, double y0) {
     if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->haveState = true; h->predictor_valid = false; h->fresh_state = true;
+    h->h_sc->status = 0;                                       // (a certificate describes the iterate of its detection only)
     return IPM_OK;
 }
 
@@ -1302,15 +1312,25 @@ static void launch_gemv_t(ipm_handle* h, const double* u, hipStream_t st = nullp
                        h->atp, &h->sc->done);
 }
 
-// r_b, r_c, d, predictor v, stop test
+static DetArgs det_args(const ipm_handle* h) { return DetArgs{h->det_eps_p, h->det_eps_d, h->det}; }
+
+// r_b, r_c, d, predictor v, stop test (and, with IPM_FLAG_DETECT_INFEASIBILITY, the infeasibility tests): the one launch site of the
+// stop test of every multi-kernel path (dense, sparse envelope, sparse factor, fused formation + factorization, lockstep)
 static int enqueue_residuals(ipm_handle* h, hipStream_t st = nullptr) {
     if (!st) st = h->stream;
     VecArgs a = vec_args(h);
     launch_gemv_n(h, h->x, 1.0, -1.0, h->b, h->rb, st);             // r_b = A x - b
     launch_gemv_t(h, h->y, st);                                     // A^T y (partials)
-    if (h->bnd) {                                                   // (a bounded handle is never recorded: ls_eligible)
+    if (h->bnd && h->detect) {
+        hipLaunchKernelGGL(prepare_bounded_detect_kernel, dim3(h->vblk), dim3(VBLK), 0, st, a, bnd_args(h));
+        hipLaunchKernelGGL(stop_test_bounded_detect_kernel, dim3(1), dim3(64), 0, st, a, bnd_args(h), det_args(h));
+    } else if (h->bnd) {                                            // (a bounded handle is never recorded: ls_eligible)
         hipLaunchKernelGGL(prepare_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, st, a, bnd_args(h));
         hipLaunchKernelGGL(stop_test_bounded_kernel, dim3(1), dim3(64), 0, st, a, bnd_args(h));
+    } else if (h->detect) {                                         // the infeasibility tests: their own lockstep twins
+        const LsVecDet p{a, det_args(h)};
+        if (!ls_push(h, LS_PREPARE_DETECT, (unsigned)h->vblk, p)) hipLaunchKernelGGL(prepare_detect_kernel, dim3(h->vblk), dim3(VBLK), 0, st, a);
+        if (!ls_push(h, LS_STOP_TEST_DETECT, 1u, p)) hipLaunchKernelGGL(stop_test_detect_kernel, dim3(1), dim3(64), 0, st, a, det_args(h));
     } else {
         if (!ls_push(h, LS_PREPARE, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(prepare_kernel, dim3(h->vblk), dim3(VBLK), 0, st, a);
         if (!ls_push(h, LS_STOP_TEST, 1u, LsVecA{a, 0})) hipLaunchKernelGGL(stop_test_kernel, dim3(1), dim3(64), 0, st, a);
@@ -2405,7 +2425,9 @@ static int enqueue_small(ipm_handle* h, int max_steps, int auto_reg) {
     a.sc = h->sc; a.hist = h->hist;
     a.eps = h->opt.pivot_guard_eps; a.big = h->opt.pivot_guard_big; a.shift_rel = h->shift_rel;
     a.max_steps = max_steps; a.auto_reg = auto_reg;
-    if (h->bnd) hipLaunchKernelGGL(small_lp_bounded_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a, bnd_args(h));
+    if (h->bnd && h->detect) hipLaunchKernelGGL(small_lp_bounded_detect_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a, bnd_args(h), det_args(h));
+    else if (h->bnd) hipLaunchKernelGGL(small_lp_bounded_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a, bnd_args(h));
+    else if (h->detect) hipLaunchKernelGGL(small_lp_detect_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a, det_args(h));
     else hipLaunchKernelGGL(small_lp_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
@@ -2841,6 +2863,36 @@ extern "C" int ipm_solve_batch(ipm_handle** hs, int32_t n, double tol_p, double 
     while (!rc && nact > 0) rc = ipm_batch_step(b, fin.data(), n, &nfin, &nact);
     if (rc) { snprintf(hs[0]->err, sizeof hs[0]->err, "%s", b->err); return rc; }
     if (stats) for (int i = 0; i < n; ++i) ipm_batch_stats(b, i, &stats[i]);
+    return IPM_OK;
+}
+
+// ------------------------------------------------------------------------------- infeasibility detection
+extern "C" int ipm_set_infeasibility_tol(ipm_handle* h, double eps_p, double eps_d) {
+    if (!h || !(eps_p > 0.0) || !(eps_d > 0.0) || !(eps_p < 1.0) || !(eps_d < 1.0))
+        return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_infeasibility_tol: tolerances must lie in (0, 1)");
+    h->det_eps_p = eps_p; h->det_eps_d = eps_d;
+    return IPM_OK;
+}
+
+extern "C" int ipm_get_certificate(ipm_handle* h, double* y, double* z, double* x, double info[4]) {
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_certificate: NULL handle");
+    const int status = h->h_sc ? h->h_sc->status : 0;
+    if (status != IPM_STATUS_PRIMAL_INFEASIBLE && status != IPM_STATUS_DUAL_INFEASIBLE)
+        return fail(h, IPM_ERR_STATE, "ipm_get_certificate: the last solve ended in status %d, not in an infeasibility detection (5 / 6)", status);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)h->n, m = (size_t)h->m;
+    if (!h->cert_mem) HIP_TRY(h, dev_malloc(h->device, h->stream, (void**)&h->cert_mem, sizeof(double) * (2 * n + m)));
+    const unsigned grid = (unsigned)std::min<size_t>((std::max(n, m) + 255) / 256, 256);
+    hipLaunchKernelGGL(certificate_kernel, dim3(grid), dim3(256), 0, h->stream, h->x, h->y, h->bnd ? bnd_args(h).z : nullptr, h->det,
+                       (int)m, (int)n, h->cert_mem);
+    HIP_TRY(h, hipGetLastError());
+    double rec[4];
+    HIP_TRY(h, hipMemcpyAsync(rec, h->det, sizeof rec, hipMemcpyDeviceToHost, h->stream));
+    if (x) HIP_TRY(h, hipMemcpyAsync(x, h->cert_mem, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    if (y) HIP_TRY(h, hipMemcpyAsync(y, h->cert_mem + n, sizeof(double) * m, hipMemcpyDeviceToHost, h->stream));
+    if (z) HIP_TRY(h, hipMemcpyAsync(z, h->cert_mem + n + m, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (info) for (int i = 0; i < 4; ++i) info[i] = rec[i];
     return IPM_OK;
 }
 

@@ -30,7 +30,8 @@ namespace ipm {
 enum LsType {
     LS_SPMV_CSR = 0, LS_SPMV_CSC_T, LS_PREPARE, LS_STOP_TEST, LS_ZERO, LS_ADAT_LIST, LS_ADAT_SPARSE, LS_ADAT_SPARSE_GLOBAL, LS_MAXDIAG,
     LS_POTRF, LS_GEMM_32_128_32, LS_GEMM_64_64_16, LS_GEMM_64_128_16, LS_GEMM_128_128_16, LS_GEMM_32_32_32, LS_CHOL_UPDATE, LS_TRSV_FWD, LS_TRSV_BWD,
-    LS_DIRECTION, LS_MU_AFF, LS_CORR_RHS, LS_UPDATE, LS_GEMV_N, LS_GEMV_T, LS_SUB_PARTIALS, LS_GROUP_DIAG_T, LS_GEMM_32_32_32_BATCHED, LS_NTYPES
+    LS_DIRECTION, LS_MU_AFF, LS_CORR_RHS, LS_UPDATE, LS_GEMV_N, LS_GEMV_T, LS_SUB_PARTIALS, LS_GROUP_DIAG_T, LS_GEMM_32_32_32_BATCHED,
+    LS_PREPARE_DETECT, LS_STOP_TEST_DETECT, LS_NTYPES
 };
 
 constexpr int LS_ARG_BYTES = 304;
@@ -45,6 +46,7 @@ struct LsRec {                                // one LP's share of one global st
 };
 
 struct LsVecA { VecArgs a; int corr; };
+struct LsVecDet { VecArgs a; DetArgs dt; };             // the infeasibility tests of a handle with IPM_FLAG_DETECT_INFEASIBILITY
 struct LsSpmv { SparseA A; int mp; const double* v; double sa, sb; const double* add; double* out; const int* done; };
 struct LsSpmvT { SparseA A; int np; const double* u; double* w; const int* done; };
 struct LsZero { double* p; int64_t n; const int* done; };
@@ -55,7 +57,7 @@ struct LsGemvT { const double* A; int64_t lda; int rows_per_chunk, np; const dou
 struct LsSubPart { double* z; const double* part; int np, rc; const int* done; };
 struct LsGroupDiagT { const double* invD; double* XT; double* X; int b0, GS; const int* done; };
 struct LsMaxdiag { const double* B; int64_t ld; int n; double* out; const int* done; };
-static_assert(sizeof(LsVecA) <= LS_ARG_BYTES && sizeof(GemmNT) <= LS_ARG_BYTES && sizeof(PotrfDiag) <= LS_ARG_BYTES && sizeof(LsAdatList) <= LS_ARG_BYTES, "LsRec::args");
+static_assert(sizeof(LsVecA) <= LS_ARG_BYTES && sizeof(GemmNT) <= LS_ARG_BYTES && sizeof(PotrfDiag) <= LS_ARG_BYTES && sizeof(LsAdatList) <= LS_ARG_BYTES && sizeof(LsVecDet) <= LS_ARG_BYTES, "LsRec::args");
 
 // block -> (LP, block of that LP's launch): the LPs' first blocks are ascending; every wave looks its own block up
 #define LS_ENTER(ARGT)                                                                                                  \
@@ -70,6 +72,8 @@ __global__ __launch_bounds__(256) void ls_spmv_csr(const LsRec* recs, const unsi
 __global__ __launch_bounds__(256) void ls_spmv_csc_t(const LsRec* recs, const unsigned count) { LS_ENTER(LsSpmvT); spmv_csc_t_kernel_body(p.A, p.np, p.u, p.w, p.done, bx, r_.gridx); }
 __global__ __launch_bounds__(VBLK) void ls_prepare(const LsRec* recs, const unsigned count) { LS_ENTER(LsVecA); prepare_kernel_body(p.a, bx, r_.gridx); }
 __global__ __launch_bounds__(64) void ls_stop_test(const LsRec* recs, const unsigned count) { LS_ENTER(LsVecA); stop_test_kernel_body(p.a, bx, r_.gridx); }
+__global__ __launch_bounds__(VBLK) void ls_prepare_detect(const LsRec* recs, const unsigned count) { LS_ENTER(LsVecDet); prepare_kernel_body<false, true>(p.a, bx, r_.gridx); }
+__global__ __launch_bounds__(64) void ls_stop_test_detect(const LsRec* recs, const unsigned count) { LS_ENTER(LsVecDet); stop_test_kernel_body<false, true>(p.a, bx, r_.gridx, BndArgs{}, p.dt); }
 __global__ __launch_bounds__(256) void ls_zero(const LsRec* recs, const unsigned count) { LS_ENTER(LsZero); zero_unless_done_kernel_body(p.p, p.n, p.done, bx, r_.gridx); }
 __global__ __launch_bounds__(256) void ls_adat_list(const LsRec* recs, const unsigned count) {
     LS_ENTER(LsAdatList);
@@ -124,6 +128,8 @@ inline hipError_t ls_launch(int type, const LsRec* d_recs, unsigned count, unsig
         case LS_SPMV_CSC_T: hipLaunchKernelGGL(ls_spmv_csc_t, g, dim3(256), 0, st, d_recs, count); break;
         case LS_PREPARE: hipLaunchKernelGGL(ls_prepare, g, dim3(VBLK), 0, st, d_recs, count); break;
         case LS_STOP_TEST: hipLaunchKernelGGL(ls_stop_test, g, dim3(64), 0, st, d_recs, count); break;
+        case LS_PREPARE_DETECT: hipLaunchKernelGGL(ls_prepare_detect, g, dim3(VBLK), 0, st, d_recs, count); break;
+        case LS_STOP_TEST_DETECT: hipLaunchKernelGGL(ls_stop_test_detect, g, dim3(64), 0, st, d_recs, count); break;
         case LS_ZERO: hipLaunchKernelGGL(ls_zero, g, dim3(256), 0, st, d_recs, count); break;
         case LS_ADAT_LIST: hipLaunchKernelGGL(ls_adat_list, g, dim3(256), 0, st, d_recs, count); break;
         case LS_ADAT_SPARSE: hipLaunchKernelGGL(ls_adat_sparse, g, dim3(256), lds, st, d_recs, count); break;

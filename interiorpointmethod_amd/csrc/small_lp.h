@@ -70,8 +70,10 @@ __device__ __forceinline__ void block_reduce512(double (&v)[NV], double* red) {
 
 // Bounded = true: native upper bounds (vector_ops.h BndArgs) -- the same loop with the w / z terms folded into
 // the same reductions (r_u^2 into ||r_b||^2, w.z into x.s, the w / z ratios into the step minima); no extra LDS.
-template <bool Bounded>
-__device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd) {
+// Detect = true: the infeasibility tests of vector_ops.h (detect_fire) in the stop test, from sums and maxima the residual passes
+// gather on the side (b.y, u_U.z_U, max (A^T y - z)_+, max |A x|, max x_U).
+template <bool Bounded, bool Detect = false>
+__device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt = DetArgs{}) {
     __shared__ __attribute__((aligned(16))) double W[NB * WLD];
     __shared__ double dinv_s[NB];
     __shared__ double ys[NB], rbs[NB], t1s[NB], zs[NB], dys[NB];
@@ -91,6 +93,7 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd) {
     }
     __syncthreads();
 
+    double dby = 0.0, duz = 0.0, dmaty = 0.0, dmax = 0.0, dmxu = 0.0;      // Detect: this thread's share of the test quantities
     // r_b = A x - b into rbs (4 lanes per row), returns this thread's share of ||r_b||^2
     auto residual_rows = [&]() {
         double rb2 = 0.0;
@@ -102,6 +105,9 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd) {
             acc += __shfl_xor(acc, 1, 4);
             const double r = acc - a.b[row4];
             if (l4 == 0) { rbs[row4] = r; rb2 = r * r; }
+            if constexpr (Detect) {
+                if (l4 == 0) { dby = a.b[row4] * ys[row4]; dmax = fabs(acc); }
+            }
         }
         return rb2;
     };
@@ -126,8 +132,10 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd) {
                     rcj = w + sj - zj - cj; dj = bnd_theta(xj, sj, wj, zj); r4 = wj * zj; ru_j2 = ruj * ruj;
                     bd.qz[j] = r4 / wj;
                     vj = dj * (rcj - qj + (r4 - zj * ruj) / wj);
+                    if constexpr (Detect) { duz += uj * zj; dmaty = fmax(dmaty, w - zj); dmxu = fmax(dmxu, xj); }
                 } else {
                     vj = dj * (rcj - qj);
+                    if constexpr (Detect) dmaty = fmax(dmaty, w);
                 }
                 a.rc[j] = rcj; a.d[j] = dj; a.q[j] = qj; a.v[j] = vj;
                 rc2 += rcj * rcj; xs += r3; xs += r4; cx += cj * xj; ru2 += ru_j2;
@@ -135,11 +143,13 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd) {
                 const double rcj = w + sj - cj, dj = xj / sj, r3 = xj * sj;
                 a.rc[j] = rcj; a.d[j] = dj; a.q[j] = r3 / xj; a.v[j] = dj * (rcj - r3 / xj);
                 rc2 += rcj * rcj; xs += r3; cx += cj * xj;
+                if constexpr (Detect) dmaty = fmax(dmaty, w);
             }
         }
     };
     // stop test of check_optimality (main.py:162-173): thread 0, result in `go`
-    auto stop_test = [&](double rb2, double rc2, double gap, double obj) {
+    // (Detect: ds = {b.y, u_U.z_U}, dm = {max (A^T y - z)_+, max |A x|, max x_U}, reduced over the workgroup)
+    auto stop_test = [&](double rb2, double rc2, double gap, double obj, const double* ds, const double* dm) {
         if (tid == 0) {
             const double rb = sqrt(rb2), rcn = sqrt(rc2);
             sc->rb_norm = rb; sc->rc_norm = rcn; sc->gap = gap; sc->obj = obj;
@@ -154,6 +164,8 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd) {
                     const bool finite = (rb == rb) && (rcn == rcn) && (gap == gap) && (fabs(rb) < 1.7e308) &&
                                         (fabs(rcn) < 1.7e308) && (fabs(gap) < 1.7e308);
                     sc->status = finite ? 1 : 3; sc->done = 1; cont_loop = 0;
+                } else if (Detect && detect_fire(dt, sc, ds[0] - ds[1], dm[0], -obj, fmax(dm[1], dm[2]))) {
+                    cont_loop = 0;
                 } else if (sc->k >= sc->max_iter) {
                     sc->status = 2; sc->done = 1; cont_loop = 0;
                 }
@@ -225,7 +237,16 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd) {
         residual_cols(r4[1], r4[2], r4[3]);
         if constexpr (Bounded) r4[0] += ru2;
         block_reduce512<4, false>(r4, red);
-        stop_test(r4[0], r4[1], r4[2], r4[3]);
+        double ds[2] = {0.0, 0.0}, dm[3] = {0.0, 0.0, 0.0};
+        if constexpr (Detect) {
+            ds[0] = dby; ds[1] = duz;
+            block_reduce512<2, false>(ds, red);
+            dm[0] = -dmaty; dm[1] = -dmax; dm[2] = -dmxu;                    // max = -min of the negated values
+            block_reduce512<3, true>(dm, red);
+            dm[0] = -dm[0]; dm[1] = -dm[1]; dm[2] = -dm[2];
+            duz = 0.0; dmaty = 0.0; dmxu = 0.0;
+        }
+        stop_test(r4[0], r4[1], r4[2], r4[3], ds, dm);
         __syncthreads();
         if (!go || steps >= a.max_steps) break;
         const double mu = sh[0];
@@ -336,5 +357,7 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd) {
 
 __global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) { small_lp_body<false>(a, BndArgs{}); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_bounded_kernel(SmallLP a, BndArgs bd) { small_lp_body<true>(a, bd); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_detect_kernel(SmallLP a, DetArgs dt) { small_lp_body<false, true>(a, BndArgs{}, dt); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_bounded_detect_kernel(SmallLP a, BndArgs bd, DetArgs dt) { small_lp_body<true, true>(a, bd, dt); }
 
 }  // namespace ipm

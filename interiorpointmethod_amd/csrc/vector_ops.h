@@ -48,6 +48,8 @@ constexpr int HIST_CAP = 1024;
 
 // partial-sum slots (each MAXPART doubles)
 enum { P_RC2 = 0, P_XS, P_CX, P_RB2, P_MINP_AFF, P_MIND_AFF, P_MUAFF, P_MINP, P_MIND, P_NSLOT };
+// slots of the infeasibility tests (Detect instantiations only): b.y, u_U.z_U, max (A^T y - z)_+, max |A x|, max x_U
+enum { P_BY = P_NSLOT, P_UZ, P_MATY, P_MAX, P_MXU, P_NSLOT_DETECT };
 
 __device__ __forceinline__ double block_sum(double v, double* red) {
     const int tid = threadIdx.x;
@@ -73,6 +75,7 @@ __device__ __forceinline__ double block_min(double v, double* red) {
     __syncthreads();
     return r;
 }
+__device__ __forceinline__ double block_max(double v, double* red) { return -block_min(-v, red); }
 __device__ __forceinline__ double sum_partials(const double* part, int slot, int nblk) {
     double s = 0.0;
     for (int i = 0; i < nblk; ++i) s += part[slot * MAXPART + i];
@@ -81,6 +84,11 @@ __device__ __forceinline__ double sum_partials(const double* part, int slot, int
 __device__ __forceinline__ double min_partials(const double* part, int slot, int nblk) {
     double s = 1.0;                                  // min(np.append(ratios, 1)), main.py:309
     for (int i = 0; i < nblk; ++i) s = fmin(s, part[slot * MAXPART + i]);
+    return s;
+}
+__device__ __forceinline__ double max_partials(const double* part, int slot, int nblk) {
+    double s = 0.0;                                  // the maxima are of non-negative quantities
+    for (int i = 0; i < nblk; ++i) s = fmax(s, part[slot * MAXPART + i]);
     return s;
 }
 
@@ -181,18 +189,22 @@ __device__ __forceinline__ double col_sum(const double* atp, int rc_chunks, int 
 // r_c = A^T y + s - c ; d = x/s ; predictor v = d*(r_c - r3/x) ; partial ||r_c||^2, x.s, c.x, ||r_b||^2
 // Bounded, on U: r_c -= z ; r_u = x + w - u ; d = theta ; v = theta (r_c - r3/x + (r4 - z r_u)/w) with r4 = w z ;
 // r_u^2 joins ||r_b||^2 and w z joins x.s
-template <bool Bounded = false>
+// Detect (IPM_FLAG_DETECT_INFEASIBILITY): also the partials of the infeasibility tests (P_BY .. P_MXU) -- reads of what the
+// pass holds anyway (A^T y from col_sum, A x = r_b + b), no extra pass over A
+template <bool Bounded = false, bool Detect = false>
 __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     __shared__ double red[VBLK];
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     double rc2 = 0.0, xs = 0.0, cx = 0.0, rb2 = 0.0;
+    double by = 0.0, uz = 0.0, maty = 0.0, max_ = 0.0, mxu = 0.0;      // Detect only
     for (int j = gid; j < a.n; j += gsz) {
         double xj = a.x[j], sj = a.s[j];
         if constexpr (Bounded) {
             const double uj = bd.u[j];
             if (bnd_in(uj)) {
                 const double wj = bd.w[j], zj = bd.z[j];
-                const double rcj = col_sum(a.atp, a.rc_chunks, a.np, j) + sj - zj - a.c[j];
+                const double atyj = col_sum(a.atp, a.rc_chunks, a.np, j);
+                const double rcj = atyj + sj - zj - a.c[j];
                 const double ruj = xj + wj - uj;
                 const double dj = bnd_theta(xj, sj, wj, zj);
                 const double r3 = xj * sj, r4 = wj * zj;
@@ -206,10 +218,12 @@ __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx
                 xs += r4;
                 cx += a.c[j] * xj;
                 rb2 += ruj * ruj;
+                if constexpr (Detect) { uz += uj * zj; maty = fmax(maty, atyj - zj); mxu = fmax(mxu, xj); }
                 continue;
             }
         }
-        double rcj = col_sum(a.atp, a.rc_chunks, a.np, j) + sj - a.c[j];
+        const double atyj = col_sum(a.atp, a.rc_chunks, a.np, j);
+        double rcj = atyj + sj - a.c[j];
         double dj = xj / sj;
         double r3 = xj * sj;
         a.rc[j] = rcj;
@@ -219,18 +233,32 @@ __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx
         rc2 += rcj * rcj;
         xs += r3;
         cx += a.c[j] * xj;
+        if constexpr (Detect) maty = fmax(maty, atyj);
     }
-    for (int i = gid; i < a.m; i += gsz) { double r = a.rb[i]; rb2 += r * r; }
+    for (int i = gid; i < a.m; i += gsz) {
+        double r = a.rb[i]; rb2 += r * r;
+        if constexpr (Detect) { const double bi = a.b[i]; by += bi * a.y[i]; max_ = fmax(max_, fabs(r + bi)); }
+    }
     rc2 = block_sum(rc2, red); xs = block_sum(xs, red); cx = block_sum(cx, red); rb2 = block_sum(rb2, red);
+    if constexpr (Detect) { by = block_sum(by, red); uz = block_sum(uz, red); maty = block_max(maty, red); max_ = block_max(max_, red); mxu = block_max(mxu, red); }
     if (threadIdx.x == 0) {
         a.part[P_RC2 * MAXPART + bx_] = rc2;
         a.part[P_XS * MAXPART + bx_] = xs;
         a.part[P_CX * MAXPART + bx_] = cx;
         a.part[P_RB2 * MAXPART + bx_] = rb2;
+        if constexpr (Detect) {
+            a.part[P_BY * MAXPART + bx_] = by;
+            a.part[P_UZ * MAXPART + bx_] = uz;
+            a.part[P_MATY * MAXPART + bx_] = maty;
+            a.part[P_MAX * MAXPART + bx_] = max_;
+            a.part[P_MXU * MAXPART + bx_] = mxu;
+        }
     }
 }
 __global__ __launch_bounds__(VBLK) void prepare_kernel(VecArgs a) { prepare_kernel_body(a, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void prepare_bounded_kernel(VecArgs a, BndArgs bd) { prepare_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
+__global__ __launch_bounds__(VBLK) void prepare_detect_kernel(VecArgs a) { prepare_kernel_body<false, true>(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(VBLK) void prepare_bounded_detect_kernel(VecArgs a, BndArgs bd) { prepare_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd); }
 
 // d = x / s only (main.py:223): what the formation of A D^2 A^T needs; the full prepare_kernel follows on the residual
 // stream while the factorization runs (ipm_api.hip, enqueue_iteration).  Bounded: d = theta on U.
@@ -249,10 +277,33 @@ __device__ __forceinline__ void scaling_kernel_body(VecArgs a, BndArgs bd = BndA
 __global__ __launch_bounds__(VBLK) void scaling_kernel(VecArgs a) { scaling_kernel_body(a); }
 __global__ __launch_bounds__(VBLK) void scaling_bounded_kernel(VecArgs a, BndArgs bd) { scaling_kernel_body<true>(a, bd); }
 
+// Infeasibility tests of IPM_FLAG_DETECT_INFEASIBILITY, on the iterate of a stop test that said "continue":
+//   primal infeasible: beta = b.y - u_U.z_U > 0 and max_j (A^T y - z)_j+ <= eps_p beta   (certificate y / beta, z / beta)
+//   dual infeasible:   gamma = -c.x > 0 and max(||A x||_inf, max x_U) <= eps_d gamma      (certificate x / gamma)
+// Maxima, not sums of squares: the iterate runs along a ray and |y| reaches 1e87 before the test fires.
+struct DetArgs {
+    double eps_p, eps_d;
+    double* out;                   // [4]: kind (5 / 6), normalisation (beta / gamma), violation / normalisation, k at detection
+};
+constexpr int IPM_STATUS_PRIMAL_INFEASIBLE_ = 5, IPM_STATUS_DUAL_INFEASIBLE_ = 6;   // include/ipm_hip.h
+// one thread; true (and done, status, dt.out set) when a test fires
+__device__ __forceinline__ bool detect_fire(DetArgs dt, Scalars* sc, double beta, double vp, double gamma, double vd) {
+    int kind = 0;
+    double nrm = 0.0, viol = 0.0;
+    if (beta > 0.0 && beta < 1.7e308 && vp <= dt.eps_p * beta) { kind = IPM_STATUS_PRIMAL_INFEASIBLE_; nrm = beta; viol = vp; }
+    else if (gamma > 0.0 && gamma < 1.7e308 && vd <= dt.eps_d * gamma) { kind = IPM_STATUS_DUAL_INFEASIBLE_; nrm = gamma; viol = vd; }
+    if (!kind) return false;
+    dt.out[0] = (double)kind; dt.out[1] = nrm; dt.out[2] = viol / nrm; dt.out[3] = (double)sc->k;
+    sc->status = kind;
+    sc->done = 1;
+    return true;
+}
+
 // stop test of check_optimality (main.py:162-173) -- one thread.
 // Bounded: ||r_b||^2 carries r_u^2 and the gap w.z (prepare_kernel), b_norm is ||(b, u_U)|| (ipm_set_bounds), mu divides by n + |U|.
-template <bool Bounded = false>
-__device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
+// Detect: the infeasibility tests (detect_fire) where the convergence test says "continue", before the iteration cap.
+template <bool Bounded = false, bool Detect = false>
+__device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, DetArgs dt = DetArgs{}) {
     if (threadIdx.x != 0 || bx_ != 0) return;
     Scalars* sc = a.sc;
     if (sc->done) return;
@@ -272,6 +323,9 @@ __device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned 
                       (fabs(gap) < 1.7e308);
         sc->status = finite ? 1 : 3;
         sc->done = 1;
+    } else if (Detect && detect_fire(dt, sc, sum_partials(a.part, P_BY, a.nblk) - sum_partials(a.part, P_UZ, a.nblk),
+                                     max_partials(a.part, P_MATY, a.nblk), -obj,
+                                     fmax(max_partials(a.part, P_MAX, a.nblk), max_partials(a.part, P_MXU, a.nblk)))) {
     } else if (sc->k >= sc->max_iter) {
         sc->status = 2;
         sc->done = 1;
@@ -279,6 +333,23 @@ __device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned 
 }
 __global__ void stop_test_kernel(VecArgs a) { stop_test_kernel_body(a, blockIdx.x, gridDim.x); }
 __global__ void stop_test_bounded_kernel(VecArgs a, BndArgs bd) { stop_test_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
+__global__ void stop_test_detect_kernel(VecArgs a, DetArgs dt) { stop_test_kernel_body<false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, dt); }
+__global__ void stop_test_bounded_detect_kernel(VecArgs a, BndArgs bd, DetArgs dt) { stop_test_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd, dt); }
+
+// The certificate of a detection (ipm_get_certificate): kind 5 -> (y / beta, z / beta), kind 6 -> x / gamma; the other parts 0.
+// out = [x (n) | y (m) | z (n)]; z = nullptr without bounds.
+__global__ __launch_bounds__(256) void certificate_kernel(const double* x, const double* y, const double* z, const double* det, int m, int n,
+                                                          double* out) {
+    const int gid = blockIdx.x * 256 + threadIdx.x, gsz = gridDim.x * 256;
+    const bool primal = det[0] == (double)IPM_STATUS_PRIMAL_INFEASIBLE_;
+    const double sc = 1.0 / det[1];
+    double *ox = out, *oy = out + n, *oz = out + n + m;
+    for (int j = gid; j < n; j += gsz) {
+        ox[j] = primal ? 0.0 : x[j] * sc;
+        oz[j] = (primal && z) ? z[j] * sc : 0.0;
+    }
+    for (int i = gid; i < m; i += gsz) oy[i] = primal ? y[i] * sc : 0.0;
+}
 
 // direction recovery + ratio test.  corr == 0: (dxa, dsa) from dya with q = r3/x;
 // corr == 1: (dx, ds) from dy with the corrector q.  Bounded, on U: dw = -r_u - dx, dz = -(r4 + z dw)/w (qz = r4/w), and the

@@ -180,30 +180,52 @@ def native_form(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None)
     return F
 
 
+def _ray_native(F, v):
+    """A vector over the columns of a NativeForm -> over the get_Abc columns (0 at the removed fixed columns); no lb shift."""
+    out = np.zeros(F.lb0.shape[0])
+    out[F.keep] = np.asarray(v, dtype=np.float64).reshape(-1)
+    return out
+
+
 def new_interior_sparse(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None, tol=1e-20, device=0,
-                        return_info=False, start="reference", bounds="fold"):
+                        return_info=False, start="reference", bounds="fold", detect_infeasibility=False):
     """Drop-in for main.py:1081-1245: convert to standard form, run the predictor-corrector loop on the GPU
     (e1 = e2 = tol, e3 = 1e-6, at most 999 iterations, x = y = s = 1), return the objective.
     bounds="fold" (default, the reference's way): every finite upper bound becomes a row and a slack column of A.
     bounds="native": native_form() -- the bounds stay in the Newton system (ipm_set_bounds), fixed variables are removed
-    on the host; info["bounded"] = |U|, info["fixed_removed"], info["x"] = the original variables."""
+    on the host; info["bounded"] = |U|, info["fixed_removed"], info["x"] = the original variables.
+    detect_infeasibility=True (IPM_FLAG_DETECT_INFEASIBILITY): +inf for an LP detected infeasible, -inf for one
+    detected unbounded, and info["certificate"] (None otherwise) as IpmSolver.certificate() of the problem solved, with y the row
+    multipliers in get_Abc order (inequality rows, then equality rows, then -- bounds="fold" -- the folded bound rows), plus
+    x_original: the ray on the original variables (unbounded), and, for bounds="native", x and z over the get_Abc columns."""
     if bounds not in ("fold", "native"):
         raise ValueError('bounds must be "fold" or "native"')
     if bounds == "native":
         F = native_form(c, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=lb, ub=ub)
         x, _, _, info = _solver.solve_with_info(F.A, F.b, F.c, tol=tol, tol_gap=1e-6, max_iter=999, y0=1.0, device=device,
-                                                start=start, ub=F.u)
+                                                start=start, ub=F.u, detect_infeasibility=detect_infeasibility)
         info["fixed_removed"] = int(F.fixed.size)
         info["x"] = F.x_original(x)
         offset = F.offset
+        cert = info.get("certificate")
+        if cert is not None:
+            cert["x"], cert["z"] = _ray_native(F, cert["x"]), _ray_native(F, cert["z"])
+            cert["x_original"] = cert["x"][:F.n].copy()
     else:
         A, b, cs, offset = standard_form(c, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=lb, ub=ub)
         _, _, _, info = _solver.solve_with_info(A, b, cs, tol=tol, tol_gap=1e-6, max_iter=999, y0=1.0, device=device,
-                                                start=start)            # start="mehrotra": optional, not the reference's
+                                                start=start,            # start="mehrotra": optional, not the reference's
+                                                detect_infeasibility=detect_infeasibility)
+        cert = info.get("certificate")
+        if cert is not None:
+            n0 = np.asarray(c).reshape(-1).shape[0]
+            cert["x_original"] = np.asarray(cert["x"]).reshape(-1)[:n0].copy()    # the first n columns are x' = x - lb
     obj = info["objective"]
     if info["status"] == 3:                      # NaN iterate: the reference returns the last finite objective it saw
         obj = info["objective_last_finite"]      # (main.py:1227-1233)
     obj = obj + offset
+    if detect_infeasibility:
+        obj = _solver._verdict(info, obj)
     return (obj, info) if return_info else obj
 
 

@@ -29,7 +29,7 @@ try:  # scipy is optional on the host side (dense inputs work without it)
 except Exception:  # pragma: no cover
     _sp = None
 
-STATUS_NAMES = {0: "running", 1: "converged", 2: "max_iter", 3: "nan"}
+STATUS_NAMES = {0: "running", 1: "converged", 2: "max_iter", 3: "nan", 5: "primal_infeasible", 6: "dual_infeasible"}
 
 
 def _dptr(a):
@@ -255,9 +255,13 @@ class IpmSolver:
 
     def __init__(self, A, b, c, device=0, eta=0.91, pivot_guard_eps=1e-30, pivot_guard_big=1e64,
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
-                 auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None):
+                 auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
+                 infeasibility_tol=(1e-8, 1e-8)):
         """ub: native upper bounds 0 <= x <= ub (length n, +inf = none), checked on the host before any device
-        is touched.  The normal matrix keeps order m; a bounded solver cannot join the lockstep batch."""
+        is touched.  The normal matrix keeps order m; a bounded solver cannot join the lockstep batch.
+        detect_infeasibility: the stop test also tests the iterate for a certificate of primal infeasibility (status 5) or of
+        unboundedness (status 6) with the tolerances infeasibility_tol = (eps_p, eps_d) (IPM_FLAG_DETECT_INFEASIBILITY,
+        DESIGN.md 4-C); certificate() returns it.  Off by default: the solve is then exactly the reference's loop."""
         if prepared is None:
             prepared = prepare(A, b, c, dense=dense, reorder=reorder, factor=factor, ub=ub)
         elif ub is not None:
@@ -286,7 +290,9 @@ class IpmSolver:
         opts.flags = (_lib.FLAG_LOCKSTEP if lockstep else 0) | \
                      ((_lib.FLAG_NO_DEVICE_POLLING | _lib.FLAG_SINGLE_STREAM) if concurrent else 0) | \
                      (0 if auto_regularize else _lib.FLAG_NO_AUTO_REGULARIZE) | \
-                     (_lib.FLAG_SPARSE_FACTOR if self.factor == "sparse" else 0)
+                     (_lib.FLAG_SPARSE_FACTOR if self.factor == "sparse" else 0) | \
+                     (_lib.FLAG_DETECT_INFEASIBILITY if detect_infeasibility else 0)
+        self.detect_infeasibility = bool(detect_infeasibility)
         nbytes = C.c_size_t(0)
         self.sparse = _sp is not None and _sp.issparse(A)
         if self.sparse:                      # A stays sparse on the device (CSR + CSC, sparse formation of B)
@@ -328,6 +334,9 @@ class IpmSolver:
         if self.ub is not None:
             self._check(lib.ipm_set_bounds(h, _dptr(self.ub)))
         self._check(lib.ipm_set_bc(h, _dptr(b), _dptr(c)))
+        if detect_infeasibility:
+            eps_p, eps_d = infeasibility_tol
+            self._check(lib.ipm_set_infeasibility_tol(h, float(eps_p), float(eps_d)))
         self.stats = None
 
     # -- plumbing
@@ -423,6 +432,19 @@ class IpmSolver:
         n = C.c_int32(0)
         self._check(self._lib.ipm_get_history(self._h, buf, _lib.HISTORY_CAPACITY, C.byref(n)))
         return [{k: getattr(buf[i], k) for k, _ in _lib.IterRecord._fields_} for i in range(n.value)]
+
+    def certificate(self):
+        """The certificate of the last solve when it ended in status 5 (primal infeasible) or 6 (dual infeasible, i.e.
+        unbounded), else None: dict with kind ("primal_infeasible" / "dual_infeasible"), y (length m, the caller's row order),
+        z and x (length n), normalization (beta = b.y - u.z, or gamma = -c.x), violation (of the normalised certificate, as the
+        device measured it) and k (iteration of the detection).  Kind 5: A^T y - z <= violation, z >= 0, b.y - u.z = 1 (x = 0);
+        kind 6: x >= 0, ||A x||_inf <= violation, c.x = -1 (y = z = 0).  verify_certificate() checks one from the data."""
+        if self.stats is None or self.stats["status"] not in (_lib.STATUS_PRIMAL_INFEASIBLE, _lib.STATUS_DUAL_INFEASIBLE):
+            return None
+        y, z, x, info = np.empty(self.m), np.empty(self.n), np.empty(self.n), np.empty(4)
+        self._check(self._lib.ipm_get_certificate(self._h, _dptr(y), _dptr(z), _dptr(x), _dptr(info)))
+        return {"kind": STATUS_NAMES[int(info[0])], "y": self._rows_out(y), "z": z, "x": x,
+                "normalization": float(info[1]), "violation": float(info[2]), "k": int(info[3])}
 
     def schedule(self):
         """How the handle runs its factorization (ipm_get_schedule): dict for tests and diagnostics."""
@@ -631,13 +653,14 @@ def last_info():
 
 
 def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
-                    history=False, ub=None, **opts):
+                    history=False, ub=None, detect_infeasibility=False, **opts):
     """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
     start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start().
     history=True adds info["history"], the per-iteration records (IpmSolver.history()).  An LP whose A has more
     than 5 % dependent rows (the QAP family) is solved with the 1e-14 Tikhonov shift, switched on by the library
     after the first factorization (info["auto_regularized"] == 1; auto_regularize=False keeps it off).
-    ub: native upper bounds 0 <= x <= ub (+inf = none): info["bounded"] = |U| and, when |U| > 0, info["w"], info["z"]."""
+    ub: native upper bounds 0 <= x <= ub (+inf = none): info["bounded"] = |U| and, when |U| > 0, info["w"], info["z"].
+    detect_infeasibility=True: the solve may end in status 5 / 6 (IpmSolver); info["certificate"] = IpmSolver.certificate()."""
     global _last_info
     ub = _upper_bounds(ub, np.asarray(c).reshape(-1).shape[0])
     if start == "mehrotra" and not opts.get("regularize") and os.environ.get("IPM_AUTO_REGULARIZE", "1") != "0":
@@ -651,6 +674,8 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
                 opts = dict(opts, regularize=1e-14)
     import time as _time
     t0 = _time.perf_counter()
+    if detect_infeasibility:
+        opts = dict(opts, detect_infeasibility=True)
     with IpmSolver(A, b, c, device=device, ub=ub, **opts) as sv:
         t1 = _time.perf_counter()
         if start == "mehrotra":
@@ -668,6 +693,8 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
             info["w"], info["z"] = sv.get_bound_state()
         if history:
             info["history"] = sv.history()
+        if detect_infeasibility:
+            info["certificate"] = sv.certificate()
         fac = sv.factor
         # the library's hidden recoveries (batch.RECORD_FIELDS): polls that timed out and were rolled back and repeated,
         # and sparse-factor sweeps that ran as one workgroup after such a time-out
@@ -693,17 +720,61 @@ def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, **opts):
     return x, y, s
 
 
-def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0):
-    """Drop-in for main.py:760-815: start x=s=y=1, cap 5000, returns sum(x*c) - cTlb."""
-    _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=5000, y0=1.0, device=device)
-    return info["objective"] - float(cTlb)
+def _verdict(info, value):
+    """+inf for a detected infeasible LP, -inf for a detected unbounded one (the convention of an LP's optimal value)."""
+    if info["status"] == _lib.STATUS_PRIMAL_INFEASIBLE:
+        return np.inf
+    if info["status"] == _lib.STATUS_DUAL_INFEASIBLE:
+        return -np.inf
+    return value
 
 
-def interior(A, b, c, tol=1e-20, device=0):
-    """Drop-in for main.py:707-757 (dense path: y0=0, cap 50000); returns the objective."""
+def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False):
+    """Drop-in for main.py:760-815: start x=s=y=1, cap 5000, returns sum(x*c) - cTlb.  detect_infeasibility=True: +inf for an
+    LP detected infeasible, -inf for one detected unbounded."""
+    _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=5000, y0=1.0, device=device,
+                                    detect_infeasibility=detect_infeasibility)
+    return _verdict(info, info["objective"] - float(cTlb))
+
+
+def interior(A, b, c, tol=1e-20, device=0, detect_infeasibility=False):
+    """Drop-in for main.py:707-757 (dense path: y0=0, cap 50000); returns the objective (detect_infeasibility: as
+    interior_sparse)."""
     _, _, _, info = solve_with_info(np.asarray(A, dtype=np.float64), b, c, tol=tol, max_iter=50000, y0=0.0,
-                                    device=device)
-    return info["objective"]
+                                    device=device, detect_infeasibility=detect_infeasibility)
+    return _verdict(info, info["objective"])
+
+
+def verify_certificate(A, b, c, cert, ub=None):
+    """Recompute, in float64 from the problem data alone, how far `cert` (IpmSolver.certificate(): kind, y, z, x; y in the
+    caller's row order) is from an exact certificate of min c.x, A x = b, 0 <= x <= ub -> the violation (0 = exact):
+      primal_infeasible: y^ = y / t, z^ = z / t with t = b.y - u.z (must be > 0): max(max(A^T y^ - z^)_+, max(-z^)_+);
+      dual_infeasible:   x^ = x / t with t = -c.x (must be > 0): max(||A x^||_inf, max(-x^)_+, max x^_U).
+    +inf when the normalisation is not positive (no certificate at all).  Pure NumPy / SciPy: no device is touched."""
+    kind = cert["kind"] if isinstance(cert, dict) else cert
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    c = np.asarray(c, dtype=np.float64).reshape(-1)
+    n = c.shape[0]
+    u = np.full(n, np.inf) if ub is None else np.asarray(ub, dtype=np.float64).reshape(-1)
+    U = np.isfinite(u)
+    if kind == "primal_infeasible":
+        y = np.asarray(cert["y"], dtype=np.float64).reshape(-1)
+        z = np.zeros(n) if cert.get("z") is None else np.asarray(cert["z"], dtype=np.float64).reshape(-1)
+        z = np.where(U, z, 0.0)
+        t = float(b @ y - u[U] @ z[U])
+        if not t > 0.0 or not np.isfinite(t):
+            return np.inf
+        aty = np.asarray(A.T @ y).reshape(-1) / t - z / t
+        return float(max(np.max(aty, initial=0.0), np.max(-z / t, initial=0.0), 0.0))
+    if kind == "dual_infeasible":
+        x = np.asarray(cert["x"], dtype=np.float64).reshape(-1)
+        t = float(-(c @ x))
+        if not t > 0.0 or not np.isfinite(t):
+            return np.inf
+        xh = x / t
+        ax = np.asarray(A @ xh).reshape(-1)
+        return float(max(np.max(np.abs(ax), initial=0.0), np.max(-xh, initial=0.0), np.max(xh[U], initial=0.0)))
+    raise ValueError("cert kind must be 'primal_infeasible' or 'dual_infeasible', not %r" % (kind,))
 
 
 _METHODS = ("normal", "full", "kkt")
