@@ -1,6 +1,6 @@
 // form_factor.h -- FUSED formation + factorization for dense handles (gfx950): B = A diag(d) A^T (main.py:224 of the
 // reference) and ALL of its blocked Cholesky (the factorization inside main.py:180 / :226), the pivot chain included, in ONE
-// persistent launch of as many workgroups as the device has CUs (form_factor_roles_kernel).
+// persistent launch of as many workgroups as the device has CUs (form_factor_roles_kernel_mfma_first).
 //
 // Why.  Formation (2.15 ms at 4096 x 8192) and factorization (2.14 ms) used to be strictly serial, although the
 // factorization is a latency chain of 32 x (potrf_diag + two small GEMMs) that keeps a handful of CUs busy.  Two things are
@@ -24,7 +24,10 @@
 // BK = 16 stages on the schedule of adat_syrk_kernel (0.87 of the fp64 MFMA peak standalone, tools/ff_gemm_bench.hip);
 // ff_gemm_pipe for the updates -- 128 x 128, waves 2 x 4, BK = 32, software pipelined; ff_gemm for the panel product with P
 // taken from the accumulators through LDS.  Operands global -> registers -> LDS (rows padded: conflict-free ds_read_b64
-// fragment reads), double buffered, one barrier per stage.  DESIGN.md 4-F has the measurements and the rejected variants.
+// fragment reads), double buffered, one barrier per stage.  HEAD (form_factor_roles_kernel_mfma_first, the launch that runs):
+// the stage loops of ff_gemm_pair and ff_gemm_pipe have no branch, and each stage opens with the MFMAs of the previous
+// stage's last k-step; form_factor_roles_kernel keeps the previous schedule as the tests' bitwise reference.  DESIGN.md 4-F
+// has the measurements and the rejected variants.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -164,10 +167,11 @@ __device__ __forceinline__ void ff_gemm(const double* __restrict__ Pg, int64_t l
 // The same product, software pipelined (the schedule of adat_syrk_f64.h carried over to 8 waves and BK = 32): fragment
 // reads run one k-step ahead through two register sets; the next stage's operands -- fetched from memory a whole stage
 // earlier -- are written to the other LDS buffer between the MFMAs of the second-to-last k-step; the stage barrier follows,
-// and the LAST k-step's eight MFMAs (fragments already in registers) issue right behind it while the first fragments of the
-// next stage are read.  A wave's MFMA stream therefore continues across the barrier, and no LDS or memory latency sits in
-// front of an MFMA.  Same operand tiles, same summation order as ff_gemm: results are bit-identical to it.
-template <bool SCALE>
+// and the LAST k-step's eight MFMAs (fragments already in registers) issue right behind it (HEAD: with the loads of stage
+// s + 2 and the first fragment reads of stage s + 1 between their rows; otherwise while those reads are in flight).  A wave's MFMA stream therefore continues across the barrier,
+// and no LDS or memory latency sits in front of an MFMA.  Same operand tiles, same summation order as ff_gemm: results are
+// bit-identical to it.
+template <bool SCALE, bool HEAD>
 __device__ __forceinline__ void ff_gemm_pipe(const double* __restrict__ Pg, int64_t ldp, const double* __restrict__ Qg, int64_t ldq,
                                              const double* __restrict__ w, int ns, double* lds, f64x4 (&acc)[4][2]) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -210,16 +214,21 @@ __device__ __forceinline__ void ff_gemm_pipe(const double* __restrict__ Pg, int6
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[set][i], fb[set][j], acc[i][j], 0, 0, 0);
     };
+    auto mfma_row = [&](int set, int i) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[set][i], fb[set][j], acc[i][j], 0, 0, 0);
+    };
     // prologue: stage 0 in LDS, loads of stage 1 in flight, first fragments in set 0
     issue_loads(0);
 #pragma unroll
     for (int u = 0; u < 4; ++u) { store_q(0, u); store_p(0, u); }
     __syncthreads();
-    if (1 < ns) issue_loads(1);
+    if (HEAD) issue_loads(min(1, ns - 1));                    // HEAD: branch-free past the last stage, as in ff_gemm_pair
+    else if (1 < ns) issue_loads(1);
     read_frags(0, 0, 0);
     for (int s = 0; s < ns; ++s) {
         const int buf = s & 1;
-        const bool more = s + 1 < ns;
+        const bool more = HEAD || s + 1 < ns;
 #pragma unroll
         for (int kk = 0; kk < 6; ++kk) {                      // k-steps 0 .. 5: prefetch kk + 1, multiply kk
             read_frags((kk + 1) & 1, buf, kk + 1);
@@ -238,11 +247,26 @@ __device__ __forceinline__ void ff_gemm_pipe(const double* __restrict__ Pg, int6
             __builtin_amdgcn_sched_barrier(0);
         }
         __syncthreads();                                      // stage s + 1 visible; every read of stage s is issued
-        if (s + 2 < ns) issue_loads(s + 2);
-        if (more) read_frags(0, buf ^ 1, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma8(1);                                             // k-step 7
-        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (HEAD) {
+            // k-step 7 opens the stage, the loads and the next stage's first fragments go out between its MFMA rows
+            mfma_row(1, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            issue_loads(min(s + 2, ns - 1));
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_row(1, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            read_frags(0, buf ^ 1, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_row(1, 2);
+            mfma_row(1, 3);
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            if (s + 2 < ns) issue_loads(s + 2);
+            if (more) read_frags(0, buf ^ 1, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma8(1);                                         // k-step 7
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
     __syncthreads();                                          // (the caller may reuse the LDS at once)
 }
@@ -258,6 +282,7 @@ constexpr int FF_POP_P = 256 * FF_PLDT, FF_POP_Q = 128 * FF_PLDT;     // doubles
 static_assert(2 * (FF_POP_P + FF_POP_Q) <= FF_LDS_DOUBLES, "pair engine LDS");
 
 // P0 / P1: first row of the upper / lower tile's 128-row panel of A (an invalid half is given any valid panel).
+template <bool HEAD>
 __device__ __forceinline__ void ff_gemm_pair(const double* __restrict__ P0, const double* __restrict__ P1, const double* __restrict__ Qg,
                                              int64_t ld, const double* __restrict__ w, int ns, double* lds, f64x4 (&acc)[4][4]) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -304,17 +329,25 @@ __device__ __forceinline__ void ff_gemm_pair(const double* __restrict__ P0, cons
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[set][i], fb[set][j], acc[i][j], 0, 0, 0);
     };
+    auto mfma_row = [&](int set, int i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[set][i], fb[set][j], acc[i][j], 0, 0, 0);
+    };
     issue_loads(0);
 #pragma unroll
     for (int u = 0; u < 2; ++u) store_q(0, u);
 #pragma unroll
     for (int u = 0; u < 4; ++u) store_p(0, u);
     __syncthreads();
-    if (1 < ns) issue_loads(1);
+    // HEAD: the loop has no branch: past the last stage the loads repeat stage ns - 1 and the stores and fragment reads go to
+    // the idle buffer, so the scheduling barriers below hold across the whole stage (a branch splits the block, and the
+    // compiler then moves k-step 3 behind the loads and reads of the next stage)
+    if (HEAD) issue_loads(min(1, ns - 1));
+    else if (1 < ns) issue_loads(1);
     read_frags(0, 0, 0);
     for (int s = 0; s < ns; ++s) {
         const int buf = s & 1;
-        const bool more = s + 1 < ns;
+        const bool more = HEAD || s + 1 < ns;
         read_frags(1, buf, 1);
         __builtin_amdgcn_sched_barrier(0);
         mfma16(0);                                              // k-step 0
@@ -334,11 +367,27 @@ __device__ __forceinline__ void ff_gemm_pair(const double* __restrict__ P0, cons
             __builtin_amdgcn_sched_barrier(0);
         }
         __syncthreads();
-        if (s + 2 < ns) issue_loads(s + 2);
-        if (more) read_frags(0, buf ^ 1, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma16(1);                                              // k-step 3
-        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (HEAD) {
+            // k-step 3 (fragments already in registers) opens the stage behind the barrier, the loads two stages ahead and the
+            // first fragments of the next stage go out between its MFMA rows: the matrix pipe does not wait for their issue
+            mfma_row(1, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            issue_loads(min(s + 2, ns - 1));
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_row(1, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            read_frags(0, buf ^ 1, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_row(1, 2);
+            mfma_row(1, 3);
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            if (s + 2 < ns) issue_loads(s + 2);
+            if (more) read_frags(0, buf ^ 1, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma16(1);                                          // k-step 3
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
     __syncthreads();
 }
@@ -472,7 +521,7 @@ enum { FFP_TICKET = 0, FFP_FGEMM, FFP_FSTORE, FFP_TWAIT, FFP_TGEMM, FFP_TBASE, F
 // Everything the persistent launch of chain_mode 1 needs: the workers' arguments and those of the two chain roles.
 struct FFRoles { FFChain chain; FFCrit crit; unsigned* role; };
 
-template <bool TRACE, bool ROLES>
+template <bool TRACE, bool ROLES, bool HEAD>
 __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles* r) {
     __shared__ __attribute__((aligned(16))) double lds[FF_LDS_DOUBLES];
     __shared__ unsigned ticket_s;
@@ -563,7 +612,7 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles*
                 for (int j = 0; j < 4; ++j) pacc[i][j] = (f64x4){0.0, 0.0, 0.0, 0.0};
             const int r_up = up ? ti : ti + 1, r_lo = lo ? ti + 1 : ti;
             if (s1 > s0)
-                ff_gemm_pair(g.A + (int64_t)r_up * 128 * g.lda + (int64_t)s0 * FF_PBK, g.A + (int64_t)r_lo * 128 * g.lda + (int64_t)s0 * FF_PBK,
+                ff_gemm_pair<HEAD>(g.A + (int64_t)r_up * 128 * g.lda + (int64_t)s0 * FF_PBK, g.A + (int64_t)r_lo * 128 * g.lda + (int64_t)s0 * FF_PBK,
                              g.A + (int64_t)tc * 128 * g.lda + (int64_t)s0 * FF_PBK, g.lda, g.d + (int64_t)s0 * FF_PBK, s1 - s0, lds, pacc);
             FF_PROF(FFP_FGEMM);
             {
@@ -618,7 +667,7 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles*
         FF_PROF(FFP_TWAIT);
         FF_TRACE(1);
         if (j1 > j0)
-            ff_gemm_pipe<false>(g.B + (int64_t)ti * 128 * g.ldb + (int64_t)j0 * 128, g.ldb,
+            ff_gemm_pipe<false, HEAD>(g.B + (int64_t)ti * 128 * g.ldb + (int64_t)j0 * 128, g.ldb,
                                 g.B + (int64_t)tc * 128 * g.ldb + (int64_t)j0 * 128, g.ldb, nullptr, (j1 - j0) * (128 / FF_BK), lds, acc);
         FF_PROF(FFP_TGEMM);
         // new tile = [old tile] + [formation slabs, in chunk order] - acc
@@ -711,13 +760,20 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles*
 template <bool TRACE>
 __global__ __launch_bounds__(FF_THREADS, 2) void form_factor_kernel(FFArgs g) {
     if (g.done && *g.done) return;
-    form_factor_body<TRACE, false>(g, nullptr);
+    form_factor_body<TRACE, false, false>(g, nullptr);
 }
 // chain_mode 1: one launch of as many workgroups as the device has CUs; the chain and the critical products are roles
 template <bool TRACE>
 __global__ __launch_bounds__(FF_THREADS, 2) void form_factor_roles_kernel(FFArgs g, FFRoles r) {
     if (g.done && *g.done) return;
-    form_factor_body<TRACE, true>(g, &r);
+    form_factor_body<TRACE, true, false>(g, &r);
+}
+// The same launch on the engines' MFMA-first stage schedule (HEAD): what enqueue_form_factor runs.  Bit-identical to
+// form_factor_roles_kernel, which stays as the reference the tests compare it with (IPM_FF_REF_ENGINE=1 selects it).
+template <bool TRACE>
+__global__ __launch_bounds__(FF_THREADS, 2) void form_factor_roles_kernel_mfma_first(FFArgs g, FFRoles r) {
+    if (g.done && *g.done) return;
+    form_factor_body<TRACE, true, true>(g, &r);
 }
 
 // One wave that waits (bounded) until *flag >= value: the gate in front of the kernels of ANOTHER stream that may only run once

@@ -132,6 +132,7 @@ struct ipm_handle {
     // IPM_FF_MAX_NBLK / IPM_FUSED_FACTOR=force|0 override.
     int ff_min_nblk = 16, ff_max_nblk = 72;
     bool ff_forced = false;
+    bool ff_ref_engine = false;           // IPM_FF_REF_ENGINE=1: form_factor_roles_kernel (the engines' previous stage schedule), the reference of tests/test_gpu_ff_engines.py
     int ff_chain_mode = 1;                // FFModel::chain_mode: 1 = the pivot chain as roles of the ONE persistent launch; 0 (three launches per step on a second stream beside 7/8 of the CUs) is refused by ipm_create
     int ff_q = 4;                         // formation chunks per tile (IPM_FF_Q)
     int ff_workers = 0;                   // WORKER workgroups of the persistent launch (set by ff_build from the CU count, no switch)
@@ -562,6 +563,7 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
             return rc_;
         }
     }
+    if (const char* e = getenv("IPM_FF_REF_ENGINE")) h->ff_ref_engine = atoi(e) != 0;
     if (const char* e = getenv("IPM_FF_Q")) h->ff_q = std::max(1, std::min(16, atoi(e)));
     CREATE_TRY(hipEventCreateWithFlags(&h->ev_ffjoin, hipEventDisableTiming));
     h->ev_diag.assign(h->nblk, nullptr); h->ev_crit.assign(h->nblk, nullptr); h->ev_bulk.assign(h->nblk, nullptr);
@@ -1814,8 +1816,15 @@ static int enqueue_form_factor(ipm_handle* h, hipEvent_t* ev, int mid_step, int 
     {
         if (h->ff_chain_mode) {
             const dim3 grid((unsigned)h->ff_workers + 1u + (unsigned)FF_CRIT_WGS);
-            if (a.prof || a.trace) hipLaunchKernelGGL((form_factor_roles_kernel<true>), grid, dim3(FF_THREADS), 0, sw, a, roles);
-            else hipLaunchKernelGGL((form_factor_roles_kernel<false>), grid, dim3(FF_THREADS), 0, sw, a, roles);
+            const bool instr = a.prof || a.trace;
+            if (h->ff_ref_engine) {
+                if (instr) hipLaunchKernelGGL((form_factor_roles_kernel<true>), grid, dim3(FF_THREADS), 0, sw, a, roles);
+                else hipLaunchKernelGGL((form_factor_roles_kernel<false>), grid, dim3(FF_THREADS), 0, sw, a, roles);
+            } else if (instr) {
+                hipLaunchKernelGGL((form_factor_roles_kernel_mfma_first<true>), grid, dim3(FF_THREADS), 0, sw, a, roles);
+            } else {
+                hipLaunchKernelGGL((form_factor_roles_kernel_mfma_first<false>), grid, dim3(FF_THREADS), 0, sw, a, roles);
+            }
         } else {
             const dim3 grid((unsigned)h->ff_workers);
             if (a.prof || a.trace) hipLaunchKernelGGL((form_factor_kernel<true>), grid, dim3(FF_THREADS), 0, sw, a);

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(FF_THREADS, 2) void bench_kernel(const double* A, i
         const double* P = A + (int64_t)ti * 128 * lda;
         const double* Q = A + (int64_t)tc * 128 * lda;
         if (V == 0) ff_gemm<true, false>(P, lda, Q, lda, d, ns, lds, acc, nullptr);
-        else ff_gemm_pipe<true>(P, lda, Q, lda, d, ns, lds, acc);
+        else ff_gemm_pipe<true, true>(P, lda, Q, lda, d, ns, lds, acc);
     }
     double* o = out + (size_t)blockIdx.x * 128 * 128 + (wm * 64 + fk) * 128 + wn * 32 + fr;
     for (int i = 0; i < 4; ++i) for (int j = 0; j < 2; ++j) for (int q = 0; q < 4; ++q) o[(i * 16 + 4 * q) * 128 + j * 16] = acc[i][j][q];
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(FF_THREADS, 2) void bench_pair_kernel(const double*
     for (int r = 0; r < reps; ++r) {
         const int ti = 2 * ((blockIdx.x + 7 * r) % (nblk / 2)), tc = (blockIdx.x * 3 + r) % nblk;
         const int64_t ko = spread ? (int64_t)((5 * blockIdx.x + r) % 4) * 16 * ns16 : 0;
-        ff_gemm_pair(A + (int64_t)ti * 128 * lda + ko, A + (int64_t)(ti + 1) * 128 * lda + ko, A + (int64_t)tc * 128 * lda + ko, lda, d + ko, ns16, lds, acc);
+        ff_gemm_pair<true>(A + (int64_t)ti * 128 * lda + ko, A + (int64_t)(ti + 1) * 128 * lda + ko, A + (int64_t)tc * 128 * lda + ko, lda, d + ko, ns16, lds, acc);
     }
     double* o = out + (size_t)blockIdx.x * 256 * 128 + (wm * 64 + fk) * 128 + wn * 64 + fr;
     for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) for (int q = 0; q < 4; ++q) o[(i * 16 + 4 * q) * 128 + j * 16] = acc[i][j][q];
