@@ -6,11 +6,12 @@
 // replaces main.py:224 + the factorization inside main.py:180/:226 of the reference, fused):
 //   F(i,c,q)          one of Q K-chunks of the formation of the tile PAIR (i,c), (i+1,c), i even: raw partial tiles into the
 //                     slabs (tile, q) of the two tiles (a half above the diagonal or below the matrix is dropped)
+//   D(i)              max diag(B) over the rows of block i straight from A and d (the pivot guard's scale); these head the list
 //   T(i,c,[j0,j1))    tile (i,c) -= sum_{j0<=j<j1} L(i,j) L(c,j)^T, optionally + the Q formation slabs (ADD_BASE, once per
 //                     tile, any time after its F chunks), optionally followed by the panel solve L(i,c) = tile inv(L(c,c))^T
 //                     (PANEL, once, after everything else of the tile and after the diagonal block c is factored)
-// and, outside the list, the PIVOT CHAIN on its own stream and its own CUs: potrf(k) of diagonal block k, the panel solve
-// of tile (k+1,k) and the update of tile (k+1,k+1) by column k (the existing kernels of potrf_f64.h / gemm_nt_f64.h).
+// and, outside the list, the PIVOT CHAIN as roles of the same launch (form_factor.h: ff_chain_role, one workgroup; ff_crit_role,
+// four): potrf(k) of diagonal block k, the panel solve of tile (k+1,k) and the update of tile (k+1,k+1) by column k.
 // The chain's tiles get everything else from the workers: tile (k+1,k) columns [0,k), tile (k,k) columns [0,k-1).
 //
 // Why an ordered list and one ticket counter: a worker takes the next item of the list, waits (bounded spin) for what the
@@ -38,7 +39,7 @@
 namespace ipm {
 
 struct FFItem {
-    unsigned char type;        // FF_F / FF_T
+    unsigned char type;        // FF_F / FF_T / FF_D
     unsigned char i, c;        // tile
     unsigned char q;           // F: K-chunk (slab index)
     union {
@@ -47,7 +48,7 @@ struct FFItem {
         struct { unsigned short s0, s1; } f;              // F: stage range [s0, s1) of the K loop (BK = 32 stages)
     };
 };
-enum { FF_F = 0, FF_T = 1, FF_D = 2 };     // FF_D(i): max diag(B) over the rows of block i straight from A and d (chain_mode 1)
+enum { FF_F = 0, FF_T = 1, FF_D = 2 };     // FF_D(i): max diag(B) over the rows of block i straight from A and d
 enum { FF_INIT = 1, FF_ADD_BASE = 2, FF_PANEL = 4, FF_SIG_DIAG = 8 };     // SIG_DIAG: the finished diagonal tile is handed to the chain (dready[i] += 10)
 constexpr int FF_MAX_NBLK = 96;
 
@@ -59,23 +60,18 @@ constexpr int FF_MAX_NBLK = 96;
 FF_HD inline int ff_tile(int i, int c) { return i * (i + 1) / 2 + c; }
 
 struct FFModel {                       // durations in microseconds, calibrated on an item trace of the launch itself (MI355X, 512-thread
-                                       // workgroups, one per CU; tools/ff_trace.py -> profiles/r04_ff_item_trace_baseline.txt, tools/ff_replay.py)
-    double f_over = 17.9, f_stage = 3.91;      // formation chunk: fixed + per BK = 16 stage of a 256 x 128 tile pair
-    double t_over = 4.1, t_col = 15.8;         // update item: fixed + per 128-column block of L applied
-    double t_rmw = 2.0, t_panel = 21.0;        // reading the tile back (all but its first item); the product with inv(L_cc)
-    double t_base = 13.0;                      // adding ONE formation slab (53 us for four before the register-major slab layout)
-    double d_item = 140.0;                     // one FF_D item (diag(B) of 128 rows straight from A and d)
-    double gap = 0.8, handoff = 1.5;           // end of an item -> next ticket; counter bump -> visible to a spinning consumer
-    // the pivot chain: potrf_diag of one block, and -- chain_mode 0 only -- its two small GEMM launches with the launch gaps
-    double potrf = 36.0, cpanel = 8.0, cupdate = 5.0, g_potrf_panel = 3.5, g_panel_update = 3.5, g_update_potrf = 4.0;
-    double chain_start = 220.0;                // chain_mode 0: ff_maxdiag_kernel in front of the first potrf_diag
-    // The chain = per step k: potrf_diag of block k, the panel solve of tile (k+1,k), the update of tile (k+1,k+1) by column k.
-    // chain_mode 0: THREE LAUNCHES per step on a second stream, on CUs the worker launch leaves free (one per shader engine), with
-    //               ff_maxdiag_kernel in front;
-    // chain_mode 1: TWO PERSISTENT launches enqueued before the workers (ff_chain_kernel: one workgroup, the diagonal blocks;
-    //               ff_crit_kernel: four workgroups, the two small products of every step in 32-row strips) -- no launch gaps, and
-    //               every other CU works; FF_D items (max diag(B), the pivot guard's scale) head the list.
-    int chain_mode = 0;
+                                       // workgroups, one per CU; tools/ff_trace.py -> profiles/r04_ff_item_trace_roles_kernel.txt: the
+                                       // replay of the list under these values, tools/ff_replay.py, ends at 3347 us, the launch it
+                                       // models at 3355 us)
+    double f_over = 6.1, f_stage = 4.02;       // formation chunk: fixed + per BK = 16 stage of a 256 x 128 tile pair
+    double t_over = 7.0, t_col = 15.9;         // update item: fixed + per 128-column block of L applied
+    double t_rmw = 1.0, t_panel = 18.3;        // reading the tile back (all but its first item); the product with inv(L_cc)
+    double t_base = 6.75;                      // adding ONE formation slab
+    double d_item = 130.0;                     // one FF_D item (diag(B) of 128 rows straight from A and d)
+    double gap = 0.8, handoff = 1.0;           // end of an item -> next ticket; counter bump -> visible to a spinning consumer
+    // The pivot chain = per step k: potrf_diag of block k (one workgroup), then the panel solve of tile (k+1,k) and the update of
+    // tile (k+1,k+1) by column k (four workgroups, 32-row strips), one hand-off after each: roles of the launch, no launch gaps.
+    double potrf = 36.8, cpanel = 7.3, cupdate = 7.3;
     int batch = 4;                     // columns of L per bulk update item
     int tail = 2;                      // newest columns of a tile applied one at a time (a batch that ends at column j cannot start before
                                        // L(.,j) exists, i.e. one pipeline step before the tile's final item is due)
@@ -83,13 +79,6 @@ struct FFModel {                       // durations in microseconds, calibrated 
                                        // finish their chunks in lockstep
     int nstages = 512;                 // K / 16 of the formation
     int q_last = 0;                    // > 0: chunks per pair for the pairs of the last two block rows (shorter chunks pack the end)
-    // calibration of chain_mode 1 (profiles/r04_ff_item_trace_roles_kernel.txt: the replay of the list under these values ends
-    // at 3347 us, the launch it models at 3355 us)
-    void roles_calibration() {
-        chain_mode = 1;
-        f_over = 6.1; f_stage = 4.02; t_over = 7.0; t_col = 15.9; t_rmw = 1.0; t_panel = 18.3; t_base = 6.75; d_item = 130.0;
-        potrf = 36.8; cpanel = 7.3; cupdate = 7.3; handoff = 1.0; chain_start = 0.0;
-    }
 };
 
 struct FFSchedule {
@@ -137,7 +126,6 @@ inline void ff_build_schedule(int nblk, int Q, int W, const FFModel& M_in, FFSch
         }
     }
     const FFModel& M = Mx;
-    const int mode = M.chain_mode;
     enum Kind { K_F, K_T, K_D, K_POTRF, K_CPANEL, K_CUPDATE };
     struct Node {
         Kind kind; int i = 0, c = 0, q = 0, j0 = 0, j1 = 0, flags = 0, seq = 0, s0 = 0, s1 = 0;
@@ -151,11 +139,10 @@ inline void ff_build_schedule(int nblk, int Q, int W, const FFModel& M_in, FFSch
     auto edge = [&](int a, int b) { nd[(size_t)a].succ.push_back(b); nd[(size_t)b].npred++; };
     // ---- chain
     std::vector<int> potrf((size_t)nblk), cpan, cupd;
-    const double g1 = mode ? M.handoff : M.g_potrf_panel, g2 = mode ? M.handoff : M.g_panel_update, g3 = mode ? M.handoff : M.g_update_potrf;
-    for (int k = 0; k < nblk; ++k) { potrf[(size_t)k] = add(K_POTRF, M.potrf + g1); nd.back().i = k; }
+    for (int k = 0; k < nblk; ++k) { potrf[(size_t)k] = add(K_POTRF, M.potrf + M.handoff); nd.back().i = k; }
     cpan.resize((size_t)nblk - 1); cupd.resize((size_t)nblk - 1);
-    for (int k = 0; k + 1 < nblk; ++k) { cpan[(size_t)k] = add(K_CPANEL, M.cpanel + g2); nd.back().i = k; }
-    for (int k = 0; k + 1 < nblk; ++k) { cupd[(size_t)k] = add(K_CUPDATE, M.cupdate + g3); nd.back().i = k; }
+    for (int k = 0; k + 1 < nblk; ++k) { cpan[(size_t)k] = add(K_CPANEL, M.cpanel + M.handoff); nd.back().i = k; }
+    for (int k = 0; k + 1 < nblk; ++k) { cupd[(size_t)k] = add(K_CUPDATE, M.cupdate + M.handoff); nd.back().i = k; }
     for (int k = 0; k + 1 < nblk; ++k) { edge(potrf[(size_t)k], cpan[(size_t)k]); edge(cpan[(size_t)k], cupd[(size_t)k]); edge(cupd[(size_t)k], potrf[(size_t)k + 1]); }
     // ---- update items per tile
     std::vector<std::vector<int>> titems((size_t)ntile);
@@ -230,9 +217,9 @@ inline void ff_build_schedule(int nblk, int Q, int W, const FFModel& M_in, FFSch
             }
     }
     for (int t = 0; t < ntile; ++t) { Node& x = nd[(size_t)base_item[(size_t)t]]; x.flags |= FF_ADD_BASE; x.dur += M.t_base * out.tile_q[(size_t)t]; }
-    // ---- FF_D items (chain_mode 1): the pivot guard's scale before the first diagonal block is factored
+    // ---- FF_D items: the pivot guard's scale before the first diagonal block is factored
     std::vector<int> ditems;
-    if (mode) for (int i = 0; i < nblk; ++i) { const int id = add(K_D, M.d_item + M.gap); nd[(size_t)id].i = i; edge(id, potrf[0]); ditems.push_back(id); }
+    for (int i = 0; i < nblk; ++i) { const int id = add(K_D, M.d_item + M.gap); nd[(size_t)id].i = i; edge(id, potrf[0]); ditems.push_back(id); }
     // ---- bottom levels
     const int N = (int)nd.size();
     {
@@ -268,8 +255,7 @@ inline void ff_build_schedule(int nblk, int Q, int W, const FFModel& M_in, FFSch
                 if (--y.left == 0) {
                     if (y.kind == K_T) avail_T.insert(PI(-y.bl, v));
                     else if (y.kind != K_F && y.kind != K_D) {     // chain nodes run by themselves as soon as their inputs are there
-                        const double st = (y.kind == K_POTRF && y.i == 0 && !mode) ? std::max(y.est, M.chain_start) : y.est;
-                        y.fin = st + y.dur;
+                        y.fin = y.est + y.dur;
                         rel.push_back(v);
                     }
                 }

@@ -9,10 +9,7 @@
 //   * Roles: every workgroup takes 139 KB of LDS (exactly one per CU) and first draws a role number from a counter: 0 = the pivot
 //     chain (ff_chain_role: potrf_diag_body per diagonal block in LDS), 1 .. 4 = the critical products of every step (ff_crit_role:
 //     32-row strips of L(k+1,k) and of the update of tile (k+1,k+1)), everybody else a worker.  Roles are claimed by workgroups
-//     that are RUNNING, so the chain is never the workgroup that did not get a CU, and no CU is kept free for anybody.  (Round 3
-//     ran the chain as separate launches on a second stream beside 224 workers and kept one CU per shader engine empty for
-//     them: workgroups are dealt to XCDs and engines in a fixed rotation whatever is free -- tools/ff_reserve_probe.hip; this
-//     structure is still selectable with IPM_FF_CHAIN_MODE=0 and is what form_factor_kernel + the chain launches of enqueue_form_factor do.)
+//     that are RUNNING, so the chain is never the workgroup that did not get a CU, and no CU is kept free for anybody.
 //   * Bulk work: the WORKERS draw items from one ordered list (ff_schedule.h): formation chunks (a K range of a 256 x 128 PAIR
 //     of tiles, partial sums to slabs) interleaved with update / panel-solve items of the factorization, in the start order of a
 //     bottom-level list scheduling of the item DAG.  Formation commutes with the updates (tile = sum of slabs - sum_j L_ij
@@ -406,7 +403,7 @@ __device__ __forceinline__ void ff_publish_begin() {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// The PIVOT CHAIN as a ROLE of the persistent launch (FFModel::chain_mode 1): the first workgroup to arrive factors the diagonal
+// The PIVOT CHAIN as a ROLE of the persistent launch: the first workgroup to arrive factors the diagonal
 // blocks in order, each as soon as its tile has been handed over (dready[k]), and publishes L_kk / inv(L_kk) (potrfdone[k]).  No
 // launch boundaries on the chain and no CUs kept free for chain launches: ONE launch of as many workgroups as the chip has CUs,
 // dealt evenly by the dispatcher whatever its rotation (separate persistent launches are not: a workgroup whose turn falls on a
@@ -453,10 +450,10 @@ __device__ __forceinline__ void ff_chain_role(const FFChain& c, double* lds) {
     }
 }
 
-// The two small products of every chain step as the role of the next FOUR workgroups to arrive (chain_mode 1), each owning a 32-row
+// The two small products of every chain step as the role of the next FOUR workgroups to arrive, each owning a 32-row
 // strip: L(k+1,k) = tile inv(L_kk)^T in place (a workgroup owns whole rows: BN = N = 128), then tile (k+1,k+1) -= L(k+1,k)
 // L(k+1,k)^T (strip x all rows of L(k+1,k); the part above the diagonal is computed too and never read).  The products are
-// gemm_nt_body<32,128,32,1,8> -- the kernels the launch-per-step chain uses -- with the hand-offs of the fused launch around
+// gemm_nt_body<32,128,32,1,8> -- the kernel the serial path launches per chain step -- with the hand-offs of the fused launch around
 // them: lfinal[k+1] += 1 per strip (4 = the tile is final L), dready[k+1] += 1 per strip (potrf waits for 4).
 struct FFCrit {
     double* B; int64_t ldb; const double* invD;
@@ -518,22 +515,20 @@ enum { FFP_TICKET = 0, FFP_FGEMM, FFP_FSTORE, FFP_TWAIT, FFP_TGEMM, FFP_TBASE, F
 
 // TRACE: the diagnostic instantiation (IPM_FF_PROF / IPM_FF_TRACE_ITEMS) carries the stamps; the shipped one none of their
 // code -- the worker loop sits at the register limit and every extra path costs spills.
-// Everything the persistent launch of chain_mode 1 needs: the workers' arguments and those of the two chain roles.
+// Everything the persistent launch needs beside the workers' arguments: those of the two chain roles and the role counter.
 struct FFRoles { FFChain chain; FFCrit crit; unsigned* role; };
 
-template <bool TRACE, bool ROLES, bool HEAD>
-__device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles* r) {
+template <bool TRACE, bool HEAD>
+__device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles& r) {
     __shared__ __attribute__((aligned(16))) double lds[FF_LDS_DOUBLES];
     __shared__ unsigned ticket_s;
-    if (ROLES) {
-        // roles by ARRIVAL: 0 = the pivot chain, 1 .. 4 = the strips of the critical products, everybody else works
-        if (threadIdx.x == 0) ticket_s = __hip_atomic_fetch_add(r->role, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const unsigned role = ticket_s;
-        __syncthreads();
-        if (role == 0u) { ff_chain_role(r->chain, lds); return; }
-        if (role <= (unsigned)FF_CRIT_WGS) { ff_crit_role(r->crit, (int)role - 1, lds); return; }
-    }
+    // roles by ARRIVAL: 0 = the pivot chain, 1 .. 4 = the strips of the critical products, everybody else works
+    if (threadIdx.x == 0) ticket_s = __hip_atomic_fetch_add(r.role, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    const unsigned role = ticket_s;
+    __syncthreads();
+    if (role == 0u) { ff_chain_role(r.chain, lds); return; }
+    if (role <= (unsigned)FF_CRIT_WGS) { ff_crit_role(r.crit, (int)role - 1, lds); return; }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
@@ -757,74 +752,28 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles*
     }
 }
 
-template <bool TRACE>
-__global__ __launch_bounds__(FF_THREADS, 2) void form_factor_kernel(FFArgs g) {
-    if (g.done && *g.done) return;
-    form_factor_body<TRACE, false, false>(g, nullptr);
-}
-// chain_mode 1: one launch of as many workgroups as the device has CUs; the chain and the critical products are roles
+// One launch of as many workgroups as the device has CUs; the chain and the critical products are roles
 template <bool TRACE>
 __global__ __launch_bounds__(FF_THREADS, 2) void form_factor_roles_kernel(FFArgs g, FFRoles r) {
     if (g.done && *g.done) return;
-    form_factor_body<TRACE, true, false>(g, &r);
+    form_factor_body<TRACE, false>(g, r);
 }
 // The same launch on the engines' MFMA-first stage schedule (HEAD): what enqueue_form_factor runs.  Bit-identical to
 // form_factor_roles_kernel, which stays as the reference the tests compare it with (IPM_FF_REF_ENGINE=1 selects it).
 template <bool TRACE>
 __global__ __launch_bounds__(FF_THREADS, 2) void form_factor_roles_kernel_mfma_first(FFArgs g, FFRoles r) {
     if (g.done && *g.done) return;
-    form_factor_body<TRACE, true, true>(g, &r);
+    form_factor_body<TRACE, true>(g, r);
 }
 
 // One wave that waits (bounded) until *flag >= value: the gate in front of the kernels of ANOTHER stream that may only run once
-// the persistent launch has reached a step (chain_mode 1: stream events cannot mark a point inside a launch).  It becomes
+// the persistent launch has reached a step (stream events cannot mark a point inside a launch).  It becomes
 // resident when a CU has room -- at the latest when the first workers leave -- and holds 64 threads while it waits.
 __global__ __launch_bounds__(64) void ff_gate_kernel(const unsigned* flag, unsigned value, unsigned* timeout, const int* done) {
     if (done && *done) return;
     if (threadIdx.x == 0) {
         ff_wait_ge(flag, value, timeout);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-}
-
-// diag(B) of the true rows straight from A and d -> its maximum (the pivot guard's scale, needed BEFORE the first diagonal
-// block is factored, i.e. long before B is complete on the fused path).  One wave per row; rows' maxima through LDS; the
-// block maxima go to `part`, the last block to arrive (ticket) reduces them in index order (max is order independent anyway).
-__global__ __launch_bounds__(256) void ff_maxdiag_kernel(const double* __restrict__ A, int64_t lda, int m, int n, const double* __restrict__ d,
-                                                         double* part, unsigned* ticket, double* out, const int* done) {
-    if (done && *done) return;
-    __shared__ double red[4];
-    __shared__ unsigned last_s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double mx = -1.7976931348623157e308;
-    for (int row = blockIdx.x * 4 + wave; row < m; row += gridDim.x * 4) {
-        const double* a = A + (int64_t)row * lda;
-        double s = 0.0;
-        for (int k = lane * 2; k < n; k += 128) {
-            const f64x2 v = *reinterpret_cast<const f64x2*>(a + k);
-            const f64x2 w = *reinterpret_cast<const f64x2*>(d + k);
-            s = __builtin_fma(v.x * v.x, w.x, s);
-            s = __builtin_fma(v.y * v.y, w.y, s);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        mx = (s > mx) ? s : mx;                      // NaN never wins (as in maxdiag_kernel)
-    }
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double b = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-        part[blockIdx.x] = b;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        last_s = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (last_s == gridDim.x - 1) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            double r = -1.7976931348623157e308;
-            for (unsigned i = 0; i < gridDim.x; ++i) r = fmax(r, __hip_atomic_load(part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            *out = r;
-        }
     }
 }
 

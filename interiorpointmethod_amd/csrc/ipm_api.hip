@@ -58,7 +58,7 @@ struct ipm_handle {
     hipStream_t stream2 = nullptr;            // bulk stream of the Cholesky look-ahead
     hipStream_t stream3 = nullptr;            // residual stream: r_b, r_c, stop test and the predictor rhs under the factorization
     hipEvent_t ev_mid = nullptr, ev_res = nullptr, ev_grp = nullptr, ev_last = nullptr;
-    std::vector<hipEvent_t> ev_diag, ev_crit, ev_bulk;
+    std::vector<hipEvent_t> ev_crit, ev_bulk;
     hipEvent_t ev_fork = nullptr;
     int lookahead = 1;
     int grouped_trsv = 1;                 // group inverses + GEMV solves (trsv_grouped.h); IPM_GROUPED_TRSV=0 disables
@@ -133,7 +133,6 @@ struct ipm_handle {
     int ff_min_nblk = 16, ff_max_nblk = 72;
     bool ff_forced = false;
     bool ff_ref_engine = false;           // IPM_FF_REF_ENGINE=1: form_factor_roles_kernel (the engines' previous stage schedule), the reference of tests/test_gpu_ff_engines.py
-    int ff_chain_mode = 1;                // FFModel::chain_mode: 1 = the pivot chain as roles of the ONE persistent launch; 0 (three launches per step on a second stream beside 7/8 of the CUs) is refused by ipm_create
     int ff_q = 4;                         // formation chunks per tile (IPM_FF_Q)
     int ff_workers = 0;                   // WORKER workgroups of the persistent launch (set by ff_build from the CU count, no switch)
     int* d_ff_tile_items = nullptr;       // [tile_items | tile_q]
@@ -141,11 +140,9 @@ struct ipm_handle {
     bool ff_built = false, ff_last = false;
     FFSchedule ff_sched;
     FFItem* d_ff_items = nullptr;         // the work list in ticket order
-    unsigned* d_ff_flags = nullptr;       // ticket[16] | maxdiag ticket[8] | dbg[8] | fcount[ntile] | tprog[ntile] | lfinal[nblk] | dready[nblk] | potrfdone[nblk]
+    unsigned* d_ff_flags = nullptr;       // ticket[16] | reserved[8] | dbg[8] | fcount[ntile] | tprog[ntile] | lfinal[nblk] | dready[nblk] | potrfdone[nblk]
     size_t ff_flag_words = 0;
     double* ff_slab = nullptr;            // [ntile][Q][128*128]
-    double* ff_part = nullptr;            // [256] block maxima of ff_maxdiag_kernel
-    hipEvent_t ev_ffjoin = nullptr;
     long long* ff_trace = nullptr;        // IPM_FF_TRACE_ITEMS=1: [nitems][4] per-item time line + [nblk][12] chain kernels (ipm_debug_ff_trace)
     long long* ff_prof = nullptr;         // IPM_FF_PROF=1: [workers][16] cycle profile of the persistent launch (accumulates)
     const int* fdone = nullptr;           // `done` word the formation / factorization kernels test (null: Scalars::done; the overlapped
@@ -554,21 +551,18 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     if (const char* e = getenv("IPM_FUSED_FACTOR")) { if (!strcmp(e, "force")) { h->ff_enabled = 1; h->ff_min_nblk = 3; h->ff_forced = true; } else h->ff_enabled = atoi(e); }
     if (const char* e = getenv("IPM_FF_MAX_NBLK")) h->ff_max_nblk = atoi(e);
     if (const char* e = getenv("IPM_FF_CHAIN_MODE")) {
-        // chain_mode 0 (round 3: the chain as three launches per step beside 224 workers) is refused: beside the current kernels its
-        // fused launch hit a recovered hand-off time-out in a plain test sequence at 16 blocks.  The host list generator
-        // still models it (ipm_debug_ff_schedule, tools/ff_tune.py).
+        // 0 asked for the chain as three launches per step beside 224 workers: that structure met a recovered hand-off time-out and
+        // has been removed.  Whoever asks for it by name is told so, not given another structure silently.
         if (atoi(e) == 0) {
-            int rc_ = fail(nullptr, IPM_ERR_INVALID_ARG, "IPM_FF_CHAIN_MODE=0 is not supported (the fused launch runs chain mode 1 only)");
+            int rc_ = fail(nullptr, IPM_ERR_INVALID_ARG, "IPM_FF_CHAIN_MODE=0 is not supported (that structure of the fused launch was removed)");
             ipm_destroy(h);
             return rc_;
         }
     }
     if (const char* e = getenv("IPM_FF_REF_ENGINE")) h->ff_ref_engine = atoi(e) != 0;
     if (const char* e = getenv("IPM_FF_Q")) h->ff_q = std::max(1, std::min(16, atoi(e)));
-    CREATE_TRY(hipEventCreateWithFlags(&h->ev_ffjoin, hipEventDisableTiming));
-    h->ev_diag.assign(h->nblk, nullptr); h->ev_crit.assign(h->nblk, nullptr); h->ev_bulk.assign(h->nblk, nullptr);
+    h->ev_crit.assign(h->nblk, nullptr); h->ev_bulk.assign(h->nblk, nullptr);
     for (int k = 0; k < h->nblk; ++k) {
-        CREATE_TRY(hipEventCreateWithFlags(&h->ev_diag[k], hipEventDisableTiming));
         CREATE_TRY(hipEventCreateWithFlags(&h->ev_crit[k], hipEventDisableTiming));
         CREATE_TRY(hipEventCreateWithFlags(&h->ev_bulk[k], hipEventDisableTiming));
     }
@@ -602,7 +596,7 @@ extern "C" int ipm_destroy(ipm_handle* h) {
     if (h->counted) g_live[h->device].fetch_sub(1, std::memory_order_acq_rel);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->stream2) (void)hipStreamSynchronize(h->stream2);
-    for (auto& v : {&h->ev_diag, &h->ev_crit, &h->ev_bulk})
+    for (auto& v : {&h->ev_crit, &h->ev_bulk})
         for (hipEvent_t e : *v) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->stream3) { (void)hipStreamSynchronize(h->stream3); (void)hipStreamDestroy(h->stream3); }
@@ -610,7 +604,6 @@ extern "C" int ipm_destroy(ipm_handle* h) {
     if (h->ev_res) (void)hipEventDestroy(h->ev_res);
     if (h->ev_grp) (void)hipEventDestroy(h->ev_grp);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
-    if (h->ev_ffjoin) (void)hipEventDestroy(h->ev_ffjoin);
     if (h->stream2) (void)hipStreamDestroy(h->stream2);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1675,21 +1668,14 @@ static int ff_build(ipm_handle* h) {
     if (h->ff_workers <= 0) {
         hipDeviceProp_t prop;
         HIP_TRY(h, hipGetDeviceProperties(&prop, h->device));
-        // One workgroup per CU on all CUs but ONE PER SHADER ENGINE -- 7 of the 8 CUs of each of the 32 engines on MI355X =
-        // 224 workers; the 32 CUs left empty host the chain's kernels.  Measured (2048 x 4100, 16 blocks): with 248 / 247
-        // workers a workgroup of a chain kernel can wait forever (always, resp. usually: the launch then ends through its
-        // spin bounds), with 240 / 232 in 1 of 6 / 5 of 8 runs, with 224 never -- the dispatcher deals workgroups to XCDs
-        // and engines round-robin without regard to where the free CUs are, so EVERY engine needs a free one.
-        h->ff_workers = std::max(8, prop.multiProcessorCount - prop.multiProcessorCount / 8);
-        // chain_mode 1: ONE launch of as many workgroups as there are CUs (dealt evenly whatever the dispatcher's rotation); the chain
-        // and the four strips of its critical products are roles of that launch, everybody else works
-        if (h->ff_chain_mode) h->ff_workers = std::max(8, prop.multiProcessorCount - 1 - FF_CRIT_WGS);
+        // ONE launch of as many workgroups as there are CUs (dealt evenly whatever the dispatcher's rotation); the chain and the four
+        // strips of its critical products are roles of that launch, everybody else works
+        h->ff_workers = std::max(8, prop.multiProcessorCount - 1 - FF_CRIT_WGS);
     }
     const int nstages = (int)(h->np / FF_PBK);               // BK = 16 stages of the pair engine
     const int Q = std::max(1, std::min(h->ff_q, nstages));
     h->ff_q = Q;
     FFModel M;
-    if (h->ff_chain_mode) M.roles_calibration();
     M.nstages = nstages;
     ff_build_schedule(h->nblk, Q, h->ff_workers, M, h->ff_sched, std::max(Q, std::min(16, nstages)));
     h->ff_qmax = 1;                                           // slab capacity per tile = the most chunks any tile is formed in
@@ -1727,7 +1713,6 @@ static int ff_build(ipm_handle* h) {
     h->ff_flag_words = 32 + 2 * ntile + 3 * (size_t)h->nblk;
     HIP_TRY(h, dev_malloc(h->device, h->stream, (void**)&h->d_ff_flags, sizeof(unsigned) * 2 * h->ff_flag_words));     // live words + diagnostic snapshot
     HIP_TRY(h, dev_malloc(h->device, h->stream, (void**)&h->ff_slab, sizeof(double) * ntile * (size_t)h->ff_qmax * 128 * 128));
-    HIP_TRY(h, dev_malloc(h->device, h->stream, (void**)&h->ff_part, sizeof(double) * 256));
     if (getenv("IPM_FF_PROF")) {
         HIP_TRY(h, dev_malloc(h->device, h->stream, (void**)&h->ff_prof, sizeof(long long) * 16 * ((size_t)h->ff_workers + 1)));
         HIP_TRY(h, hipMemsetAsync(h->ff_prof, 0, sizeof(long long) * 16 * ((size_t)h->ff_workers + 1), h->stream));
@@ -1745,7 +1730,7 @@ static int ff_build(ipm_handle* h) {
 // ff_ok and the schedule + buffers are there.  A failure of ff_build (an allocation, an internal check) is not an error of the
 // solve: what was allocated is freed, the handle stops using the fused launch and the iteration runs formation then factorization.
 static void ff_release(ipm_handle* h) {
-    for (void** p : {(void**)&h->d_ff_items, (void**)&h->d_ff_flags, (void**)&h->ff_slab, (void**)&h->ff_part, (void**)&h->ff_prof, (void**)&h->ff_trace,
+    for (void** p : {(void**)&h->d_ff_items, (void**)&h->d_ff_flags, (void**)&h->ff_slab, (void**)&h->ff_prof, (void**)&h->ff_trace,
                      (void**)&h->d_ff_tile_items}) { dev_free(h->device, h->stream, *p); *p = nullptr; }
     h->ff_built = false;
 }
@@ -1759,47 +1744,39 @@ static bool ff_use(ipm_handle* h) {
     return false;
 }
 
-// One persistent worker launch (formation chunks + every update / panel solve outside the pivot chain) on the main stream and
-// the pivot chain -- potrf_diag(k), panel solve of tile (k+1,k), update of tile (k+1,k+1) -- on the second stream, coupled
-// through device counters only.  `ev` (optional): ev[1] / ev[2] bracket the worker launch.
+// The one persistent launch on the main stream: the pivot chain (one workgroup), the four strips of its critical products and the
+// workers (formation chunks, max diag(B), every update / panel solve outside the chain) are roles of it, coupled through device
+// counters only.  Behind it, on the residual stream, a gate on the chain's progress and what may run from that step on.
+// `ev` (optional): ev[1] / ev[2] bracket the launch.
 static int enqueue_form_factor(ipm_handle* h, hipEvent_t* ev, int mid_step, int ginv_step) {
     if (!h->ff_built) return fail(h, IPM_ERR_STATE, "fused factor: schedule not built");
     const int nblk = h->nblk;
     const size_t ntile = (size_t)nblk * (nblk + 1) / 2;
     const int* done = h->fdone ? h->fdone : &h->sc->done;
-    hipStream_t sw = h->stream, sm = h->stream2;
-    unsigned* F = h->d_ff_flags;
-    unsigned *ticket = F, *mticket = F + 16, *dbg = F + 24, *fcount = F + 32, *tprog = fcount + ntile, *lfinal = tprog + ntile, *dready = lfinal + nblk,
+    hipStream_t sw = h->stream;
+    unsigned* F = h->d_ff_flags;                               // (layout at the field: tools/ff_debug.py decodes by offset)
+    unsigned *ticket = F, *dbg = F + 24, *fcount = F + 32, *tprog = fcount + ntile, *lfinal = tprog + ntile, *dready = lfinal + nblk,
              *potrfdone = dready + nblk;
     unsigned* timeout = h->d_flags + 2 * (size_t)nblk;
     h->ff_potrfdone = potrfdone;                               // (the gate of the last group's inverses polls its last word: enqueue_iteration)
     HIP_TRY(h, hipMemsetAsync(F, 0, sizeof(unsigned) * h->ff_flag_words, sw));
     HIP_TRY(h, hipEventRecord(h->ev_fork, sw));
-    if (!h->ff_chain_mode) HIP_TRY(h, hipStreamWaitEvent(sm, h->ev_fork, 0));
     long long* ctrace = h->ff_trace ? h->ff_trace + 4 * h->ff_sched.items.size() : nullptr;
+    // the pivot chain and its two small products are ROLES of the launch (claimed by arrival); max diag(B) comes from the FF_D
+    // items at the head of the work list
     FFRoles roles;
     memset(&roles, 0, sizeof roles);
-    if (h->ff_chain_mode) {
-        // the pivot chain and its two small products are ROLES of the one persistent launch (claimed by arrival); max diag(B)
-        // comes from the FF_D items at the head of the work list
-        FFChain& c = roles.chain;
-        c.B = h->B; c.ldb = h->mp; c.invD = h->invD;
-        c.maxbits = (const unsigned long long*)(F + 8); c.dcount = F + 10; c.maxdiag_out = &h->sc->maxdiag;
-        c.dready = dready; c.potrfdone = potrfdone; c.timeout = timeout; c.dbg = dbg; c.trace = ctrace;
-        c.eps = h->opt.pivot_guard_eps; c.big = h->opt.pivot_guard_big; c.shift_rel = h->shift_rel;
-        c.fixed = &h->sc->fixed; c.done = done; c.nblk = nblk; c.m = (int)h->m;
-        FFCrit& cc = roles.crit;
-        cc.B = h->B; cc.ldb = h->mp; cc.invD = h->invD; cc.tprog = tprog; cc.tile_items = h->d_ff_tile_items;
-        cc.potrfdone = potrfdone; cc.lfinal = lfinal; cc.dready = dready; cc.timeout = timeout; cc.dbg = dbg; cc.trace = ctrace;
-        cc.done = done; cc.nblk = nblk;
-        roles.role = F + 3;
-    } else {
-        // the pivot guard's scale max diag(B) over the true rows, straight from A and d (B is complete only at the very end
-        // here): on the chain's stream in front of potrf_diag(0), i.e. on the CUs the workers leave free, beside their first
-        // formation chunks -- the first diagonal tile is not ready before those are done anyway
-        hipLaunchKernelGGL(ff_maxdiag_kernel, dim3(256), dim3(256), 0, sm, h->A, h->np, (int)h->m, (int)h->np, h->d, h->ff_part, mticket,
-                           &h->sc->maxdiag, done);
-    }
+    FFChain& c = roles.chain;
+    c.B = h->B; c.ldb = h->mp; c.invD = h->invD;
+    c.maxbits = (const unsigned long long*)(F + 8); c.dcount = F + 10; c.maxdiag_out = &h->sc->maxdiag;
+    c.dready = dready; c.potrfdone = potrfdone; c.timeout = timeout; c.dbg = dbg; c.trace = ctrace;
+    c.eps = h->opt.pivot_guard_eps; c.big = h->opt.pivot_guard_big; c.shift_rel = h->shift_rel;
+    c.fixed = &h->sc->fixed; c.done = done; c.nblk = nblk; c.m = (int)h->m;
+    FFCrit& cc = roles.crit;
+    cc.B = h->B; cc.ldb = h->mp; cc.invD = h->invD; cc.tprog = tprog; cc.tile_items = h->d_ff_tile_items;
+    cc.potrfdone = potrfdone; cc.lfinal = lfinal; cc.dready = dready; cc.timeout = timeout; cc.dbg = dbg; cc.trace = ctrace;
+    cc.done = done; cc.nblk = nblk;
+    roles.role = F + 3;
     FFArgs a;
     memset(&a, 0, sizeof a);
     a.A = h->A; a.lda = h->np; a.d = h->d; a.B = h->B; a.ldb = h->mp; a.invD = h->invD; a.slab = h->ff_slab;
@@ -1814,92 +1791,36 @@ static int enqueue_form_factor(ipm_handle* h, hipEvent_t* ev, int mid_step, int 
     a.nblk = nblk; a.Q = h->ff_qmax; a.nstages = (int)(h->np / FF_PBK); a.m = (int)h->m;
     if (ev) HIP_TRY(h, hipEventRecord(ev[1], sw));
     {
-        if (h->ff_chain_mode) {
-            const dim3 grid((unsigned)h->ff_workers + 1u + (unsigned)FF_CRIT_WGS);
-            const bool instr = a.prof || a.trace;
-            if (h->ff_ref_engine) {
-                if (instr) hipLaunchKernelGGL((form_factor_roles_kernel<true>), grid, dim3(FF_THREADS), 0, sw, a, roles);
-                else hipLaunchKernelGGL((form_factor_roles_kernel<false>), grid, dim3(FF_THREADS), 0, sw, a, roles);
-            } else if (instr) {
-                hipLaunchKernelGGL((form_factor_roles_kernel_mfma_first<true>), grid, dim3(FF_THREADS), 0, sw, a, roles);
-            } else {
-                hipLaunchKernelGGL((form_factor_roles_kernel_mfma_first<false>), grid, dim3(FF_THREADS), 0, sw, a, roles);
-            }
+        const dim3 grid((unsigned)h->ff_workers + 1u + (unsigned)FF_CRIT_WGS);
+        const bool instr = a.prof || a.trace;
+        if (h->ff_ref_engine) {
+            if (instr) hipLaunchKernelGGL((form_factor_roles_kernel<true>), grid, dim3(FF_THREADS), 0, sw, a, roles);
+            else hipLaunchKernelGGL((form_factor_roles_kernel<false>), grid, dim3(FF_THREADS), 0, sw, a, roles);
+        } else if (instr) {
+            hipLaunchKernelGGL((form_factor_roles_kernel_mfma_first<true>), grid, dim3(FF_THREADS), 0, sw, a, roles);
         } else {
-            const dim3 grid((unsigned)h->ff_workers);
-            if (a.prof || a.trace) hipLaunchKernelGGL((form_factor_kernel<true>), grid, dim3(FF_THREADS), 0, sw, a);
-            else hipLaunchKernelGGL((form_factor_kernel<false>), grid, dim3(FF_THREADS), 0, sw, a);
+            hipLaunchKernelGGL((form_factor_roles_kernel_mfma_first<false>), grid, dim3(FF_THREADS), 0, sw, a, roles);
         }
     }
     if (ev) HIP_TRY(h, hipEventRecord(ev[2], sw));
     HIP_TRY(h, hipGetLastError());
-    h->n_counter_steps = 0; h->n_event_steps = 0; h->last_gs = 1;
-    if (h->ff_chain_mode) {
-        // Everything the residual stream does -- the inverses of the complete 1024-row groups, r_b, r_c, the stop test, the
-        // predictor's right-hand side -- sits behind a GATE that opens when the chain has factored block `gate_step`: no stream
-        // event can mark a point inside the persistent launch, and every CU is taken until the workers leave, which they do from
-        // about that step on (all items drawn).  Enqueued after the launch; ev_res joins it into the main stream as before.
-        h->n_counter_steps = nblk;
-        const int gate_step = ginv_step >= 0 ? ginv_step : mid_step;
-        if (gate_step >= 0) {
-            HIP_TRY(h, hipStreamWaitEvent(h->stream3, h->ev_fork, 0));            // (the hand-off words are zeroed)
-            hipLaunchKernelGGL(ff_gate_kernel, dim3(1), dim3(64), 0, h->stream3, potrfdone + gate_step, 1u, timeout, done);
-            if (ginv_step >= 0) { int rc_ = enqueue_group_inverses(h, 0, (ginv_step + 1) / h->gsz, h->stream3); if (rc_) return rc_; }
-            if (mid_step >= 0) {
-                int rc_ = enqueue_residuals(h, h->stream3);
-                if (rc_) return rc_;
-                launch_gemv_n(h, h->v, -1.0, -1.0, h->rb, h->t1, h->stream3);   // predictor rhs = -r_b - A (d*t)
-                HIP_TRY(h, hipEventRecord(h->ev_res, h->stream3));
-            }
-        }
-        HIP_TRY(h, hipGetLastError());
-        h->ff_last = true;
-        return IPM_OK;
-    }
-    for (int k = 0; k < nblk; ++k) {
-        PotrfDiag pd;
-        pd.Bkk = h->B + (int64_t)k * NB * (h->mp + 1); pd.ld = h->mp;
-        pd.inv = h->invD + (int64_t)k * NB * NB;
-        pd.maxdiag = &h->sc->maxdiag; pd.eps = h->opt.pivot_guard_eps; pd.big = h->opt.pivot_guard_big; pd.shift_rel = h->shift_rel;
-        pd.fixed = &h->sc->fixed; pd.done = done; pd.stamps = nullptr;
-        pd.wait_on = dready + k; pd.wait_count = 10; pd.signal = potrfdone + k; pd.timeout = timeout; pd.dbg = dbg; pd.dbg_tag = (unsigned)k;
-        pd.trace = ctrace ? ctrace + 12 * (size_t)k : nullptr;
-        pd.nt = potrf_panels(h, k);
-        pd.rows = (int)(h->m - (int64_t)k * NB);
-        hipLaunchKernelGGL(potrf_diag_kernel<false>, dim3(1), dim3(PD_THREADS), 0, sm, pd);
-        ++h->n_counter_steps;
-        if (k == ginv_step) {
-            HIP_TRY(h, hipEventRecord(h->ev_grp, sm));
-            HIP_TRY(h, hipStreamWaitEvent(h->stream3, h->ev_grp, 0));
-            int rc_ = enqueue_group_inverses(h, 0, (k + 1) / h->gsz, h->stream3);
+    h->n_counter_steps = nblk; h->n_event_steps = 0; h->last_gs = 1;
+    // Everything the residual stream does -- the inverses of the complete 1024-row groups, r_b, r_c, the stop test, the
+    // predictor's right-hand side -- sits behind a GATE that opens when the chain has factored block `gate_step`: no stream
+    // event can mark a point inside the persistent launch, and every CU is taken until the workers leave, which they do from
+    // about that step on (all items drawn).  Enqueued after the launch; ev_res joins it into the main stream as before.
+    const int gate_step = ginv_step >= 0 ? ginv_step : mid_step;
+    if (gate_step >= 0) {
+        HIP_TRY(h, hipStreamWaitEvent(h->stream3, h->ev_fork, 0));            // (the hand-off words are zeroed)
+        hipLaunchKernelGGL(ff_gate_kernel, dim3(1), dim3(64), 0, h->stream3, potrfdone + gate_step, 1u, timeout, done);
+        if (ginv_step >= 0) { int rc_ = enqueue_group_inverses(h, 0, (ginv_step + 1) / h->gsz, h->stream3); if (rc_) return rc_; }
+        if (mid_step >= 0) {
+            int rc_ = enqueue_residuals(h, h->stream3);
             if (rc_) return rc_;
+            launch_gemv_n(h, h->v, -1.0, -1.0, h->rb, h->t1, h->stream3);   // predictor rhs = -r_b - A (d*t)
+            HIP_TRY(h, hipEventRecord(h->ev_res, h->stream3));
         }
-        if (k == mid_step) { int rc_ = enqueue_residual_stream(h, sm); if (rc_) return rc_; }
-        if (k + 1 >= nblk) break;
-        double* panel = h->B + (int64_t)(k + 1) * NB * h->mp + (int64_t)k * NB;
-        GemmNT tc = gemm_defaults();                                // L(k+1,k) = tile inv(L_kk)^T, in place
-        tc.tile_order = nullptr; tc.batch = 1; tc.batch2 = 1;
-        tc.P = panel; tc.ldp = h->mp; tc.Q = pd.inv; tc.ldq = NB; tc.w = nullptr;
-        tc.C = panel; tc.ldc = h->mp; tc.M = NB; tc.N = NB; tc.K = NB;
-        tc.alpha = 1.0; tc.beta = 0.0; tc.lower = 0; tc.unit_diag_from = -1; tc.done = done;
-        tc.wait_on = tprog + ff_tile(k + 1, k); tc.wait_count = (unsigned)h->ff_sched.tile_items[(size_t)ff_tile(k + 1, k)];
-        tc.signal = lfinal + (k + 1); tc.timeout = timeout;         // four workgroups, one count each: 4 = one final tile
-        tc.dbg = dbg; tc.dbg_tag = 1000u + (unsigned)k;
-        tc.trace = ctrace ? ctrace + 12 * (size_t)k + 4 : nullptr;
-        HIP_TRY(h, (launch_gemm_nt<32, 128, 32, 1, 8>(tc, sm)));
-        GemmNT uc = gemm_defaults();                                // tile (k+1,k+1) -= L(k+1,k) L(k+1,k)^T
-        uc.tile_order = nullptr; uc.batch = 1; uc.batch2 = 1;
-        uc.P = panel; uc.ldp = h->mp; uc.Q = panel; uc.ldq = h->mp; uc.w = nullptr;
-        uc.C = h->B + (int64_t)(k + 1) * NB * (h->mp + 1); uc.ldc = h->mp; uc.M = NB; uc.N = NB; uc.K = NB;
-        uc.alpha = -1.0; uc.beta = 1.0; uc.lower = 1; uc.unit_diag_from = -1; uc.done = done;
-        uc.wait_on = tprog + ff_tile(k + 1, k + 1); uc.wait_count = (unsigned)h->ff_sched.tile_items[(size_t)ff_tile(k + 1, k + 1)];
-        uc.signal = dready + (k + 1); uc.timeout = timeout;         // ten 32 x 32 sub-tiles, one count each
-        uc.dbg = dbg; uc.dbg_tag = 2000u + (unsigned)k;
-        uc.trace = ctrace ? ctrace + 12 * (size_t)k + 8 : nullptr;
-        HIP_TRY(h, (launch_gemm_nt<32, 32, 32, 2, 2>(uc, sm)));
     }
-    HIP_TRY(h, hipEventRecord(h->ev_ffjoin, sm));
-    HIP_TRY(h, hipStreamWaitEvent(sw, h->ev_ffjoin, 0));
     HIP_TRY(h, hipGetLastError());
     h->ff_last = true;
     return IPM_OK;
@@ -1910,9 +1831,9 @@ extern "C" int ipm_debug_ff_schedule(int32_t nblk, int32_t q, int32_t workers, u
     if (nblk < 1 || nblk > FF_MAX_NBLK || q < 1 || q > 16 || workers < 1 || !count) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_debug_ff_schedule: bad arguments");
     static_assert(sizeof(FFItem) == 8, "work item layout");
     FFSchedule S;
+    if (const char* e = getenv("IPM_FF_CHAIN_MODE")) if (atoi(e) == 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "IPM_FF_CHAIN_MODE=0 is not supported (that structure of the fused launch was removed)");     // as ipm_create
     FFModel M;
     M.nstages = 512;                                          // K = 8192 (the headline size's formation), BK = 16 stages
-    if (!(getenv("IPM_FF_CHAIN_MODE") && atoi(getenv("IPM_FF_CHAIN_MODE")) == 0)) M.roles_calibration();
     ff_build_schedule(nblk, q, workers, M, S, std::max(q, 16));
     *count = (int32_t)S.items.size();
     if (items) memcpy(items, S.items.data(), sizeof(FFItem) * std::min<size_t>(S.items.size(), (size_t)std::max(0, capacity)));
@@ -2190,7 +2111,7 @@ static int enqueue_iteration(ipm_handle* h, hipEvent_t* ev) {
         if (gstep >= 0) {
             // the last group's inverse (nine dependent launches, ~80 us) goes to the residual stream as well: the forward
             // sweep of the predictor over the earlier groups runs beside it and only its last step waits
-            if (h->ff_last && h->ff_chain_mode && h->ff_potrfdone) {
+            if (h->ff_last && h->ff_potrfdone) {
                 // fused launch: the residual stream does not wait for an EVENT behind the launch (in the kernel trace both streams
                 // then resumed 45 us after the launch's last wave: two streams waiting for each other's events) but for the chain's
                 // last hand-off word, like the gate of the earlier groups: behind it the whole factor is released at agent scope

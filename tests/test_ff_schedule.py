@@ -151,10 +151,10 @@ def test_work_list_is_deterministic_and_its_simulated_time_beats_the_serial_path
 
 
 # -------------------------------------------------------------------------------- every generator setting yields a valid list
-# Each knob alone, chain mode 0 (modelled by the host generator for tools/ff_tune.py only; ipm_create refuses it) and the
-# duration-model perturbations that the GPU order-invariance test runs, from 16 blocks (the default rule's lower end) to
-# FF_MAX_NBLK = 96 (tile indices and column ranges of a work item are unsigned char fields, the largest values only occur there).  251 workers = chain mode 1 on 256 CUs (256 - 1 - FF_CRIT_WGS).
-SETTINGS = KNOBS + [("IPM_FF_CHAIN_MODE", "0")] + [("IPM_FF_MODEL", m) for m in MODELS]
+# Each knob alone and the duration-model perturbations that the GPU order-invariance test runs, from 16 blocks (the default rule's
+# lower end) to FF_MAX_NBLK = 96 (tile indices and column ranges of a work item are unsigned char fields, the largest values only
+# occur there).  251 workers = the launch on 256 CUs (256 - 1 - FF_CRIT_WGS).
+SETTINGS = KNOBS + [("IPM_FF_MODEL", m) for m in MODELS]
 
 
 def _check_cuts(nblk, q, items, stagger=0.3, q_last=0):
@@ -179,7 +179,7 @@ def test_every_generator_setting_gives_a_complete_list_in_dependency_order(built
     assert replay(nblk, q, items, tile_items, q_last=q_last) == nblk
     assert sim[0] > 0 and sim[1] > 0
     _check_cuts(nblk, q, items, stagger=float(val) if var == "IPM_FF_STAGGER" else 0.3, q_last=q_last)
-    assert bool((items[:, 0] == D).any()) == (var != "IPM_FF_CHAIN_MODE")          # FF_D items head the chain-mode-1 list only
+    assert (items[:nblk, 0] == D).all() and not (items[nblk:, 0] == D).any()        # FF_D items, one per block, head every list
     t = items[items[:, 0] == T]
     if var == "IPM_FF_BATCH":                                                        # the bulk items really are that wide
         assert (t[:, 5] - t[:, 4]).max() == int(val)
@@ -187,6 +187,18 @@ def test_every_generator_setting_gives_a_complete_list_in_dependency_order(built
         i, c = nblk - 1, nblk - 3
         cols = [(j0, j1) for (_ty, ii, cc, _q, j0, j1, *_r) in t if ii == i and cc == c]
         assert cols[-int(val):] == [(j, j + 1) for j in range(c - int(val), c)], cols
+
+
+def test_chain_mode_0_is_refused_by_the_generator_too(built_lib, monkeypatch):
+    """The structure IPM_FF_CHAIN_MODE=0 selected has been removed: the debug entry point refuses it as ipm_create does (asserted on
+    the GPU in tests/test_gpu_ff_schedule.py) and models no other structure in its place."""
+    lib = _lib.load()
+    count = C.c_int32(0)
+    monkeypatch.setenv("IPM_FF_CHAIN_MODE", "0")
+    assert lib.ipm_debug_ff_schedule(16, 4, 251, None, 0, C.byref(count), None, None) != 0
+    assert "IPM_FF_CHAIN_MODE=0" in lib.ipm_last_error(None).decode()
+    monkeypatch.setenv("IPM_FF_CHAIN_MODE", "1")
+    assert lib.ipm_debug_ff_schedule(16, 4, 251, None, 0, C.byref(count), None, None) == 0 and count.value > 0
 
 
 def _producers(items, nblk):

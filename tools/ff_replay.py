@@ -12,7 +12,8 @@ INIT, ADD_BASE, PANEL, SIG0 = 1, 2, 4, 8
 
 
 class Model:
-    """chain_mode 0 (three launches per chain step beside 224 workers), calibrated on profiles/r04_ff_item_trace_baseline.txt"""
+    """chain_mode 0 (three launches per chain step beside 224 workers), calibrated on profiles/r04_ff_item_trace_baseline.txt:
+    historical, no such launch exists any more (kept to replay that recorded trace)"""
     f_over, f_stage = 17.9, 3.91          # F chunk: us fixed + per BK=16 stage
     t_over, t_col, t_base, t_panel, t_rmw = 4.1, 15.8, 53.0, 21.0, 2.0     # t_base: FOUR slabs
     gap = 0.8                             # end of an item -> next ticket drawn
@@ -24,7 +25,7 @@ class Model:
 
 
 class ModelRoles(Model):
-    """chain_mode 1 (the chain as roles of the one launch, 251 workers), calibrated on profiles/r04_ff_item_trace_roles_kernel.txt"""
+    """the launch that runs (mode=1: the chain as roles of the one launch, 251 workers), calibrated on profiles/r04_ff_item_trace_roles_kernel.txt"""
     f_over, f_stage = 6.1, 4.02
     t_over, t_col, t_base, t_panel, t_rmw = 7.0, 15.9, 27.0, 18.3, 1.0
     d_item = 397.0

@@ -26,7 +26,7 @@ def main():
     ap.add_argument("dirs", nargs="+")
     ap.add_argument("--out", required=True)
     ap.add_argument("--shape", type=int, nargs=2, default=[4096, 8192])
-    ap.add_argument("--kernel", default="adat_syrk_kernel", help="adat_syrk_kernel (serial path) or form_factor_kernel (fused path)")
+    ap.add_argument("--kernel", default="adat_syrk_kernel", help="adat_syrk_kernel (serial path) or form_factor_roles_kernel (fused path)")
     args = ap.parse_args()
     import bench
     acc = collections.defaultdict(list)
