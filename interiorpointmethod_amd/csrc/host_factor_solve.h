@@ -1,0 +1,417 @@
+// host_factor_solve.h -- host side, unit 4: formation of B = A D A^T, the look-ahead Cholesky schedule (dense) and the launches of
+// the sparse factor, the group inverses and the triangular sweeps.
+#pragma once
+static inline bool sp_on(const ipm_handle* h) { return h->spf && !h->spf_off; }
+// Sparse factor: one launch per LEVEL of the panel tree (the kernel boundary is the hand-off, nothing spins) instead of one
+// launch per sweep with flag hand-offs between tasks.  Chosen by IPM_SP_MODE=level, and automatically wherever the handle
+// shares the device -- IPM_FLAG_NO_DEVICE_POLLING (batched mode) or more than one live handle: spinning consumers next to
+// other LPs' kernels are what turned STOCFOR3's 0.10 s into 1.4-1.7 s in a shared run, and the level form measured equal
+// under contention (73-LP suite 3.11-3.15 s vs 3.20-3.32 s).  Same arithmetic, bit-identical results.
+static inline bool sp_level(const ipm_handle* h) {
+    if (h->sp_serial || h->sp_level_mode < 0) return false;
+    if (h->sp_level_mode > 0 || (h->opt.flags & IPM_FLAG_NO_DEVICE_POLLING)) return true;
+    return !alone_on_device(h);
+}
+static inline unsigned sp_launch_grid(ipm_handle* h) {
+    if (h->sp_serial) { ++h->sp_serial_launches; return 1u; }
+    return (unsigned)h->sp_grid;
+}
+// The launches of one walk of the panel tree, launch(grid, recs, count).  by_level: one launch per level, leaves or root first,
+// of min(level's records, sp_grid) workgroups -- the kernel boundary is the hand-off (~5 us against ~8-20 us for a flag hand-off
+// inside one launch), nothing spins, concurrent handles interleave at launch granularity.  Else (task mode) one launch over all records.
+template <class Launch>
+static void sp_walk(ipm_handle* h, bool by_level, bool leaves_first, Launch launch) {
+    if (!by_level) { launch(sp_launch_grid(h), h->spF.rec, 0); return; }
+    const size_t nlev = h->sp_lvlptr.empty() ? 0 : h->sp_lvlptr.size() - 1;
+    for (size_t i = 0; i < nlev; ++i) {
+        const size_t l = leaves_first ? i : nlev - 1 - i;
+        const int cnt = h->sp_lvlptr[l + 1] - h->sp_lvlptr[l];
+        launch((unsigned)std::min(cnt, h->sp_grid), h->sp_rec_level + h->sp_lvlptr[l], cnt);
+    }
+}
+
+// Dense B and inv(L_kk) for a handle whose workspace carries none (layout_no_dense): allocated on first use by a dense entry
+// point, stream-ordered, freed in ipm_destroy.  A no-op everywhere else.
+static int ensure_dense_B(ipm_handle* h) {
+    if (h->B && h->invD) return IPM_OK;
+    if (!h->no_dense) return fail(h, IPM_ERR_STATE, "handle has no dense normal-matrix buffer");
+    if ((!h->B_own && dev_malloc(h->device, h->stream, (void**)&h->B_own, sizeof(double) * (size_t)h->mp * h->mp) != hipSuccess) ||
+        (!h->invD_own && dev_malloc(h->device, h->stream, (void**)&h->invD_own, sizeof(double) * (size_t)h->nblk * NB * NB) != hipSuccess))
+        return fail(h, IPM_ERR_HIP, "dense normal-matrix buffer (%lld x %lld doubles) could not be allocated", (long long)h->mp, (long long)h->mp);   // (what was allocated stays owned: freed in ipm_destroy, reused by a later call)
+    HIP_TRY(h, hipMemsetAsync(h->invD_own, 0, sizeof(double) * (size_t)h->nblk * NB * NB, h->stream));
+    h->B = h->B_own; h->invD = h->invD_own;
+    return IPM_OK;
+}
+
+// B = A diag(d) A^T (lower tiles), unit diagonal on padding rows
+static int enqueue_form(ipm_handle* h, const double* d, bool dense_image = false) {
+    if (sp_on(h) && !dense_image) {
+        // the entries of B go straight into the panels of the sparse factor (one thread per slot, fixed term order)
+        hipLaunchKernelGGL(sp_form_kernel, dim3((unsigned)((h->sp_nslot + 255) / 256)), dim3(256), 0, h->stream, h->sp_fptr, h->sp_fcol,
+                           h->sp_fcoef, h->sp_nslot, d, h->spF.L, &h->sc->maxdiag, &h->sc->done);
+        hipLaunchKernelGGL(sp_maxdiag_kernel, dim3((unsigned)((h->m + 255) / 256)), dim3(256), 0, h->stream, h->spF.L, h->sp_diagpos, (int)h->m, &h->sc->maxdiag,
+                           &h->sc->done);
+        HIP_TRY(h, hipGetLastError());
+        return IPM_OK;
+    }
+    if (int rc_ = ensure_dense_B(h)) return rc_;
+    if (h->sparse && h->list_form) {
+        const int64_t nB = h->mp * h->mp;                       // even (mp is a multiple of 128)
+        const unsigned zgrid = (unsigned)std::min<int64_t>((nB / 2 + 255) / 256, 4096);
+        if (!ls_push(h, LS_ZERO, zgrid, LsZero{h->B, nB, &h->sc->done}))
+            hipLaunchKernelGGL(zero_unless_done_kernel, dim3(zgrid), dim3(256), 0, h->stream, h->B, nB, &h->sc->done);
+        const int work = h->sm_nb + (int)(h->mp - h->m);
+        const LsAdatList pl{h->sm_bptr, h->ls_bi, h->ls_bk, h->sm_bcol, h->sm_bcoef, h->ls_bak, h->sm_nb, d, h->B, h->mp, (int)h->m, (int)h->mp, &h->sc->done};
+        if (!ls_push(h, LS_ADAT_LIST, (unsigned)((work + 255) / 256), pl))
+            hipLaunchKernelGGL(adat_list_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, h->stream, h->sm_bptr, h->ls_bi, h->ls_bk,
+                               h->sm_bcol, h->sm_bcoef, h->ls_bak, h->sm_nb, d, h->B, h->mp, (int)h->m, (int)h->mp, &h->sc->done);
+        HIP_TRY(h, hipGetLastError());
+        return IPM_OK;
+    }
+    if (h->sparse) {
+        const LsAdatSp ps{sparse_view(h), d, h->B, h->mp, (int)h->mp, &h->sc->done};
+        if (h->mp <= SP_LDS_MAX_MP) {          // dynamic-LDS attribute set per device in ipm_create
+            if (!ls_push(h, LS_ADAT_SPARSE, (unsigned)h->mp, ps, (unsigned)(h->mp * sizeof(double))))
+                hipLaunchKernelGGL(adat_sparse_kernel, dim3((unsigned)h->mp), dim3(256), (size_t)h->mp * sizeof(double), h->stream,
+                                   sparse_view(h), d, h->B, h->mp, (int)h->mp, &h->sc->done);
+        } else if (!ls_push(h, LS_ADAT_SPARSE_GLOBAL, (unsigned)h->mp, ps)) {
+            hipLaunchKernelGGL(adat_sparse_global_kernel, dim3((unsigned)h->mp), dim3(256), 0, h->stream, sparse_view(h), d,
+                               h->B, h->mp, (int)h->mp, &h->sc->done);
+        }
+        HIP_TRY(h, hipGetLastError());
+        return IPM_OK;
+    }
+    // the dedicated software-pipelined kernel (adat_syrk_f64.h; the generic gemm_nt kernel it replaced in round 2 computes the same bits)
+    HIP_TRY(h, launch_adat_syrk(h->A, h->np, d, h->B, h->mp, (int)h->mp, (int)h->np, (int)h->m, factor_done(h),
+                                h->d_tile_order, h->stream, h->slab, 512));
+    return IPM_OK;
+}
+
+// X_g, XT_g = inv of every 1024 x 1024 diagonal group of the factor and its transpose (trsv_grouped.h):
+// recursive doubling 128 -> 256 -> 512 -> 1024, three GEMMs per level batched over (pairs in a group,
+// groups).  After enqueue_factor, on the main stream.
+static int enqueue_group_inverses(ipm_handle* h, int g0 = 0, int g1 = -1, hipStream_t st = nullptr) {
+    if (sp_on(h)) return IPM_OK;
+    if (!h->grouped_trsv) return IPM_OK;
+    const int GS = h->gsz;
+    const int64_t GR = (int64_t)GS * 128;
+    if (g1 < 0) g1 = h->nblk / GS;
+    if (!st) st = h->stream;
+    const int nG = g1 - g0;                               // groups [g0, g1)
+    if (nG <= 0) return IPM_OK;
+    const int* done = &h->sc->done;
+    if (!ls_push(h, LS_GROUP_DIAG_T, 16u * (unsigned)(nG * GS), LsGroupDiagT{h->invD, h->gXT, h->gX, g0 * GS, GS, done}))
+        hipLaunchKernelGGL(group_diag_transpose_kernel, dim3(4, 4, nG * GS), dim3(32, 8), 0, st, h->invD, h->gXT, h->gX, g0 * GS, GS, done);
+    const int64_t gXs = GR * GR, gL = GR * (h->mp + 1), gSs = (GR / 2) * (GR / 2);   // group strides in X/XT, L, S
+    double* gXT = h->gXT + g0 * gXs; double* gX = h->gX + g0 * gXs; double* gS = h->gS + g0 * gSs;
+    const double* Lg = h->B + g0 * gL;
+    for (int hs = 128; hs < GR; hs *= 2) {
+        const int np = (int)(GR / (2 * hs));              // pairs per group
+        GemmNT t = gemm_defaults();
+        t.done = done;
+        t.M = hs; t.N = hs; t.K = hs; t.batch = np; t.batch2 = nG;
+        const int64_t pX = (int64_t)2 * hs * (GR + 1);                                 // pair strides in X, XT
+        const int64_t pL = (int64_t)2 * hs * (h->mp + 1);
+        const int64_t pS = (int64_t)hs * hs;
+        GemmNT a = t;                                     // S = XT11 * L21^T
+        a.P = gXT; a.ldp = GR; a.sP = pX; a.sP2 = gXs;
+        a.Q = Lg + (int64_t)hs * h->mp; a.ldq = h->mp; a.sQ = pL; a.sQ2 = gL;
+        a.C = gS; a.ldc = hs; a.sC = pS; a.sC2 = gSs;
+        HIP_TRY(h, (launch_gemm_nt<32, 32, 32, 2, 2>(a, st)));      // 32 x 32 tiles (4x the workgroups of 64 x 64: 0.17 -> 0.12 ms)
+        GemmNT b = t;                                     // X21 = -X22 * S^T
+        b.P = gX + (int64_t)hs * GR + hs; b.ldp = GR; b.sP = pX; b.sP2 = gXs;
+        b.Q = gS; b.ldq = hs; b.sQ = pS; b.sQ2 = gSs;
+        b.C = gX + (int64_t)hs * GR; b.ldc = GR; b.sC = pX; b.sC2 = gXs; b.alpha = -1.0;
+        HIP_TRY(h, (launch_gemm_nt<32, 32, 32, 2, 2>(b, st)));
+        GemmNT c = t;                                     // XT12 = -S * X22^T
+        c.P = gS; c.ldp = hs; c.sP = pS; c.sP2 = gSs;
+        c.Q = gX + (int64_t)hs * GR + hs; c.ldq = GR; c.sQ = pX; c.sQ2 = gXs;
+        c.C = gXT + hs; c.ldc = GR; c.sC = pX; c.sC2 = gXs; c.alpha = -1.0;
+        HIP_TRY(h, (launch_gemm_nt<32, 32, 32, 2, 2>(c, st)));
+    }
+    HIP_TRY(h, hipGetLastError());
+    return IPM_OK;
+}
+
+// 16-wide panels of diagonal block k that hold rows of the LP (the rest of the block is padding: unit diagonal): potrf_diag
+// factors only those -- the last real block of an LP whose row count is no multiple of 128, and the blocks the layout pads with
+static inline int potrf_panels(const ipm_handle* h, int k) {
+    if (h->shift_rel != 0.0) return NB / 16;              // (the Tikhonov shift touches every diagonal entry: keep the full block)
+    const int64_t real = h->m - (int64_t)k * NB;
+    return real >= NB ? NB / 16 : (int)std::max<int64_t>(1, (real + 15) / 16);
+}
+
+// blocked guarded Cholesky of B in place (lower), right-looking with one step of look-ahead:
+//   main stream : potrf_diag(k) -> [wait bulk(k-1)] -> panel rows of block k+1 -> update of tile (k+1,k+1)
+//   bulk stream : [wait diag(k)] panel rows >= k+2 -> [wait crit(k)] rest of the trailing update
+// so the serial diagonal-block factorization of step k+1 overlaps the bulk update of step k.
+// sp_fwd_rhs (sparse factor only): right-hand side whose forward substitution rides on the factorization (z -> h->t2); the next
+// enqueue_potrs of that right-hand side then runs the backward sweep only (h->sp_fwd_fused).
+static int enqueue_factor(ipm_handle* h, bool use_env = false, int mid_step = -1, int ginv_step = -1, const double* sp_fwd_rhs = nullptr) {
+    if (sp_on(h)) {                     // multifrontal sparse Cholesky: one launch walks the elimination tree
+        if (!h->sp_fuse_fwd) sp_fwd_rhs = nullptr;
+        h->sp_fwd_fused = sp_fwd_rhs;
+        const unsigned ep = ++h->sp_epoch;
+        sp_walk(h, sp_level(h), /*leaves_first=*/true, [&](unsigned grid, const SpRec* recs, int count) {
+            hipLaunchKernelGGL((sp_chol_kernel<SPC_THREADS, false>), dim3(grid), dim3(SPC_THREADS), h->sp_lds_chol, h->stream, h->spF, ep,
+                               &h->sc->maxdiag, h->opt.pivot_guard_eps, h->opt.pivot_guard_big, h->shift_rel, &h->sc->fixed,
+                               h->sp_lds_doubles, recs, count, sp_fwd_rhs, h->t2, h->sp_fv_off);
+        });
+        HIP_TRY(h, hipGetLastError());
+        return IPM_OK;
+    }
+    if (int rc_ = ensure_dense_B(h)) return rc_;
+    const int* done = factor_done(h);
+    use_env = use_env && h->use_env;
+    // threshold scale = max diag over the TRUE rows only (padding rows carry a unit diagonal)
+    if (!ls_push(h, LS_MAXDIAG, 1u, LsMaxdiag{h->B, h->mp, (int)h->m, &h->sc->maxdiag, done}))
+        hipLaunchKernelGGL(maxdiag_kernel, dim3(1), dim3(256), 0, h->stream, h->B, h->mp, (int)h->m, &h->sc->maxdiag, done);
+    const bool la = lookahead_on(h);
+    // group size of the two-level schedule.  Measured (factor, ms): 16384 x 32768: 39.7 / 34.9 / 33.4 / 32.9 / 32.5 for groups
+    // of 1 / 2 / 3 / 4 / 6; 8192 x 16384: 7.87 / 7.46 / 7.34 / 7.34 for 1 / 2 / 3 / 4; but 4096 x 8192: 2.21 -> 2.36 with groups
+    // of 2 (half of its steps are bound by the pivot chain, which grouping lengthens): on from 48 blocks.
+    // IPM_TWO_LEVEL=0 disables, IPM_GROUP_STEPS=n forces a group size (>= 8 blocks).
+    int gs = 1;
+    if (la && !use_env && h->two_level != 0) {
+        if (h->group_steps > 0) gs = h->nblk >= 8 ? h->group_steps : 1;
+        else if (h->nblk >= 96) gs = 4;
+        else if (h->nblk >= 48) gs = 3;
+    }
+    // Group table: uniform groups of gs block columns (from 48 blocks on; one-level below that -- pairing only the head of the
+    // factorization was measured and does not pay below 48 blocks either: 2.158 / 2.157 / 2.182 / 2.213 ms for 0 / 4 / 8 / 16 paired steps)
+    std::vector<int> grp_lo(h->nblk), grp_hi(h->nblk);
+    for (int k = 0; k < h->nblk; ++k) {
+        if (gs > 1) { grp_lo[k] = (k / gs) * gs; grp_hi[k] = std::min(grp_lo[k] + gs, h->nblk); }
+        else { grp_lo[k] = k; grp_hi[k] = k + 1; }
+    }
+    h->last_gs = gs;
+    hipStream_t sm = h->stream, sb = la ? h->stream2 : h->stream;
+    const bool fs = polls_device(h);                      // device-polled hand-offs (only while this is the one live handle on the device)
+    h->n_counter_steps = 0; h->n_event_steps = 0;
+    std::vector<unsigned> bulk_wgs(h->nblk, 0u);          // workgroups of the bulk update of each step
+    if (la) {
+        if (fs) HIP_TRY(h, hipMemsetAsync(h->d_bulk_done, 0, sizeof(unsigned) * 2 * (size_t)h->nblk, sm));
+        HIP_TRY(h, hipEventRecord(h->ev_fork, sm));
+        HIP_TRY(h, hipStreamWaitEvent(sb, h->ev_fork, 0));
+    }
+    for (int k = 0; k < h->nblk; ++k) {
+        PotrfDiag pd;
+        pd.Bkk = h->B + (int64_t)k * NB * (h->mp + 1); pd.ld = h->mp;
+        pd.inv = h->invD + (int64_t)k * NB * NB;
+        pd.maxdiag = &h->sc->maxdiag; pd.eps = h->opt.pivot_guard_eps; pd.big = h->opt.pivot_guard_big; pd.shift_rel = h->shift_rel;
+        pd.fixed = &h->sc->fixed; pd.done = done; pd.stamps = nullptr;
+        pd.wait_on = nullptr; pd.wait_count = 0; pd.signal = nullptr; pd.timeout = nullptr; pd.dbg = nullptr; pd.dbg_tag = 0;
+        pd.trace = nullptr;
+        pd.nt = potrf_panels(h, k);
+        pd.rows = (int)(h->m - (int64_t)k * NB);
+        if (h->stamp_buf && k == 0) {
+            pd.stamps = h->stamp_buf;
+            if (getenv("IPM_POTRF_SKIP")) pd.dbg_tag = (unsigned)atoi(getenv("IPM_POTRF_SKIP"));
+            hipLaunchKernelGGL(potrf_diag_kernel<true>, dim3(1), dim3(PD_THREADS), 0, sm, pd);
+        } else if (!ls_push(h, LS_POTRF, 1u, pd)) {
+            hipLaunchKernelGGL(potrf_diag_kernel<false>, dim3(1), dim3(PD_THREADS), 0, sm, pd);
+        }
+        if (k == ginv_step) {
+            // blocks 0 .. k are final (the diagonal block k was just factored, every panel block left of it in these rows is
+            // ordered before it through the look-ahead hand-offs): the inverses of the complete 1024-row groups go to the
+            // residual stream, only the last group's is left for after the factorization
+            HIP_TRY(h, hipEventRecord(h->ev_grp, sm));
+            HIP_TRY(h, hipStreamWaitEvent(h->stream3, h->ev_grp, 0));
+            int rc_ = enqueue_group_inverses(h, 0, (k + 1) / h->gsz, h->stream3);
+            if (rc_) return rc_;
+        }
+        if (k == mid_step) { int rc_ = enqueue_residual_stream(h, sm); if (rc_) return rc_; }
+        int rem = (int)(h->mp - (int64_t)(k + 1) * NB);
+        if (rem <= 0) break;
+        if (use_env) {                                              // rows below the envelope are zero and stay zero
+            rem = std::min(rem, (h->env_last[k] - k) * NB);
+            if (rem <= 0) {                                         // nothing below the diagonal block in this column
+                if (la) HIP_TRY(h, hipEventRecord(h->ev_bulk[k], sb));
+                continue;
+            }
+        }
+        double* panel = h->B + (int64_t)(k + 1) * NB * h->mp + (int64_t)k * NB;
+        GemmNT t = gemm_defaults();                                 // L_ik = B_ik inv(L_kk)^T, in place
+        t.P = panel; t.ldp = h->mp; t.Q = pd.inv; t.ldq = NB;
+        t.C = panel; t.ldc = h->mp; t.M = rem; t.N = NB; t.K = NB;
+        t.lower = 0; t.done = done;
+        GemmNT u = gemm_defaults();                                 // B_ij -= L_ik L_jk^T
+        u.P = panel; u.ldp = h->mp; u.Q = panel; u.ldq = h->mp;
+        u.C = h->B + (int64_t)(k + 1) * NB * (h->mp + 1); u.ldc = h->mp; u.M = rem; u.N = rem; u.K = NB;
+        u.alpha = -1.0; u.beta = 1.0; u.lower = 1; u.done = done;
+        if (!la) {
+            // one stream (batched mode, small handles): panel and update are BOTH on the dependent chain of the step.  With few
+            // trailing blocks the chip is empty anyway: narrower tiles (32-row panel strips on 8 waves / 64 x 64 update tiles) are
+            // latency-shorter kernels -- ss_small_blocks = trailing blocks up to which they are used (IPM_SS_SMALL_TILES)
+            if (rem <= h->ss_small_blocks * NB) {
+                HIP_TRY(h, (launch_gemm_nt<32, 128, 32, 1, 8>(t, sm)));
+                HIP_TRY(h, (launch_gemm_nt<64, 64, 16, 2, 2>(u, sm)));
+                continue;
+            }
+            HIP_TRY(h, (launch_gemm_nt<64, 128, 16, 2, 2>(t, sm)));
+            if (h->bulk_variant == 7) HIP_TRY(h, (launch_gemm_nt<128, 128, 16, 2, 2>(u, sm)));
+            else HIP_TRY(h, launch_chol_update(u, sm));
+            continue;
+        }
+        // one event per step on the main stream (after the critical panel rows): every extra record / wait
+        // costs the pivot chain ~6-12 us of command-processor time (profiles/, trace of a step)
+        GemmNT tc = t; tc.M = NB;                                   // critical panel rows: block row k+1
+        if (k >= 1) {     // the previous bulk update either signalled a counter (small grids) or recorded an event
+            if (bulk_wgs[k - 1] > 0) { tc.wait_on = h->d_bulk_done + (k - 1); tc.wait_count = bulk_wgs[k - 1]; tc.timeout = timeout_word(h); }
+            else HIP_TRY(h, hipStreamWaitEvent(sm, h->ev_bulk[k - 1], 0));
+        }
+        // bulk side: the (small) panel launch of the bulk stream polls the completion counter of the critical
+        // panel launch instead of a stream event, unless it is large enough to crowd the CUs while it spins
+        const int tb_wgs = (rem - NB) / 64;
+        // SAFETY: a polling launch holds LDS on every CU it lands on; potrf_diag needs a CU with 133 KB free and
+        // sits upstream of the signal, so a wide poller deadlocks the chain until its spin bound expires
+        // (observed at m = 16384 with 254 pollers).  Only launches that leave most CUs untouched may poll.
+        const bool crit_flag = fs && rem > NB && tb_wgs <= 64;
+        if (crit_flag) tc.signal = h->d_bulk_done + h->nblk + k;
+        // NOTE the panel solve is IN PLACE (C = P): a workgroup must own whole rows, i.e. BN == N == 128.  Tiles narrower
+        // than the panel (tried: 16 workgroups of 32 x 32) race -- one workgroup overwrites columns another still reads.
+        HIP_TRY(h, (launch_gemm_nt<32, 128, 32, 1, 8>(tc, sm)));     // 8 waves, BK=32: 4 stages
+        if (!crit_flag) HIP_TRY(h, hipEventRecord(h->ev_crit[k], sm));
+        // Two-level blocking (dense handles): the steps come in groups of `gs` block columns.  A step updates only the
+        // remaining columns of its group (a window of K = 128 tiles) and DEFERS the rest of its trailing update; the last
+        // step of the group applies all of them at once with K = 128 gs -- the group's panels are adjacent block columns
+        // of L, i.e. one k-contiguous operand -- so the trailing matrix, whose read-modify-write is what bounds a
+        // K = 128 update (16 flop/byte), is streamed once per group instead of once per step.
+        const int g0 = grp_lo[k], gend = grp_hi[k];                  // group = block columns [g0, gend)
+        const bool grouped = gend - g0 > 1;
+        const bool grp_inner = grouped && k + 1 < gend;             // not the last column of its group: window only
+        const bool grp_last = grouped && !grp_inner;
+        if (grp_last && k > g0) {                                   // operands: block columns g0..k, rows >= k+1
+            u.P = panel - (int64_t)(k - g0) * NB; u.Q = u.P; u.K = (k - g0 + 1) * NB;
+        }
+        GemmNT uc = u; uc.M = NB; uc.N = NB;                        // critical tile (k+1,k+1)
+        HIP_TRY(h, (launch_gemm_nt<32, 32, 32, 2, 2>(uc, sm)));      // 10 sub-tiles of 32x32
+        if (!crit_flag) HIP_TRY(h, hipStreamWaitEvent(sb, h->ev_crit[k], 0));
+        if (rem > NB) {
+            GemmNT tb = t; tb.C = panel + (int64_t)NB * h->mp; tb.P = tb.C; tb.M = rem - NB;
+            if (crit_flag) { tb.wait_on = h->d_bulk_done + h->nblk + k; tb.wait_count = NB / 32; tb.timeout = timeout_word(h); }   // workgroups of the critical panel launch
+            HIP_TRY(h, (launch_gemm_nt<64, 128, 16, 2, 2>(tb, sb)));
+            GemmNT ub = u;
+            const int nt = rem / NB;
+            if (grp_inner) {
+                // window: tiles (i, j), i >= k+2, k+1 <= j < gend:  B(i,j) -= L(i,k) L(j,k)^T as ONE rectangular GEMM.
+                // Inside the group it also touches a few tiles above the diagonal (i < j), which nobody reads.
+                const int wn = gend - (k + 1);
+                ub.P = panel + (int64_t)NB * h->mp; ub.Q = panel;
+                ub.C = h->B + (int64_t)(k + 2) * NB * h->mp + (int64_t)(k + 1) * NB;
+                ub.M = rem - NB; ub.N = std::min(wn * NB, rem); ub.lower = 0;
+                if (fs) { bulk_wgs[k] = (unsigned)((ub.M / NB) * (ub.N / NB)); ub.signal = h->d_bulk_done + k; ++h->n_counter_steps; }
+                else ++h->n_event_steps;
+                if (h->bulk_variant == 7) HIP_TRY(h, (launch_gemm_nt<128, 128, 16, 2, 2>(ub, sb)));
+                else HIP_TRY(h, launch_chol_update(ub, sb));
+                HIP_TRY(h, hipEventRecord(h->ev_bulk[k], sb));
+                continue;
+            }
+            const int ub_wgs = nt * (nt + 1) / 2 - 1;
+            // the per-workgroup release (L2 write-back) of the counter protocol only pays in the latency-bound
+            // regime; a throughput-bound update (thousands of tiles: 16k: 40 -> 50 ms) keeps the stream event
+            if (fs && ub_wgs <= 1024) {
+                bulk_wgs[k] = (unsigned)ub_wgs;
+                ub.signal = h->d_bulk_done + k;
+                ++h->n_counter_steps;
+            } else ++h->n_event_steps;
+            if (h->bulk_variant == 7) HIP_TRY(h, (launch_gemm_nt<128, 128, 16, 2, 2>(ub, sb, nullptr, 512, /*skip_first=*/1)));   // the generic kernel (rounds 1-2)
+            else HIP_TRY(h, launch_chol_update(ub, sb, /*skip_first=*/1));
+        }
+        HIP_TRY(h, hipEventRecord(h->ev_bulk[k], sb));
+    }
+    if (la) HIP_TRY(h, hipStreamWaitEvent(sm, h->ev_bulk[h->nblk - 2], 0));
+    HIP_TRY(h, hipGetLastError());
+    return IPM_OK;
+}
+
+static void launch_dense_gemv_n(ipm_handle* h, const double* A, int64_t lda, int rows, int cols, const double* v, double sa,
+                                double sb, const double* add, double* out) {
+    if (ls_push(h, LS_GEMV_N, (unsigned)((rows + 3) / 4), LsGemvN{A, lda, rows, cols, v, sa, sb, add, out, &h->sc->done})) return;
+    hipLaunchKernelGGL(gemv_n_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, h->stream, A, lda, rows, cols, v, sa, sb,
+                       add, out, &h->sc->done);
+}
+
+// Block-step substitution over the blocks [k0, nblk), one launch per block step: forward sweep L z = r, then the backward sweep
+// L^T out = z inside the envelope.  k0 = 0 is the whole solve; k0 > 0 the blocks behind the last full group (ragged groups).
+static void enqueue_block_steps(ipm_handle* h, int k0, double* r, double* z, double* out) {
+    TrsvStep a;
+    a.L = h->B; a.ld = h->mp; a.inv = h->invD; a.done = &h->sc->done;
+    a.r = r; a.z = z; a.j0 = 0;
+    for (int k = k0; k < h->nblk; ++k) {
+        a.k = k;
+        const int nb = h->use_env ? h->env_last[k] - k + 1 : h->nblk - k;
+        if (!ls_push(h, LS_TRSV_FWD, (unsigned)nb, a)) hipLaunchKernelGGL(trsv_fwd_step_kernel, dim3(nb), dim3(256), 0, h->stream, a);
+    }
+    a.r = z; a.z = out;
+    for (int k = h->nblk - 1; k >= k0; --k) {
+        a.k = k;
+        a.j0 = h->use_env ? h->env_first[k] : 0;
+        if (!ls_push(h, LS_TRSV_BWD, (unsigned)(k - a.j0 + 1), a)) hipLaunchKernelGGL(trsv_bwd_step_kernel, dim3(k - a.j0 + 1), dim3(256), 0, h->stream, a);
+    }
+}
+
+// out = B^{-1} r with the 1024-row group inverses: 4 group steps per sweep at m = 4096
+// wait_last (optional): event after which the LAST group's inverse is available; the forward sweep over the earlier groups
+// does not need it and runs ahead of the wait
+static int enqueue_potrs_grouped(ipm_handle* h, double* r, double* out, hipEvent_t wait_last = nullptr) {
+    const int GS = h->gsz;
+    const int GR = GS * 128;
+    const int nG = h->nblk / GS;
+    const int* done = &h->sc->done;
+    double* z = h->t2;
+    for (int g = 0; g < nG; ++g) {                                        // forward: L z = r
+        if (wait_last && g == nG - 1) HIP_TRY(h, hipStreamWaitEvent(h->stream, wait_last, 0));
+        launch_dense_gemv_n(h, h->gX + (int64_t)g * GR * GR, GR, GR, GR, r + (int64_t)g * GR, 1.0, 0.0, nullptr, z + (int64_t)g * GR);
+        int below = (int)(h->mp - (int64_t)(g + 1) * GR);
+        if (h->use_env) below = std::min(below, (int)((int64_t)(h->env_last[(g + 1) * GS - 1] + 1) * NB - (int64_t)(g + 1) * GR));
+        if (below > 0) {
+            double* rb = r + (int64_t)(g + 1) * GR;
+            launch_dense_gemv_n(h, h->B + (int64_t)(g + 1) * GR * h->mp + (int64_t)g * GR, h->mp, below, GR, z + (int64_t)g * GR, -1.0, 1.0,
+                                rb, rb);
+        }
+    }
+    // blocks behind the last full group (ragged groups): one launch per block step, as without groups
+    enqueue_block_steps(h, nG * GS, r, z, out);
+    for (int g = nG - 1; g >= 0; --g) {                                   // backward: L^T w = z
+        launch_dense_gemv_n(h, h->gXT + (int64_t)g * GR * GR, GR, GR, GR, z + (int64_t)g * GR, 1.0, 0.0, nullptr, out + (int64_t)g * GR);
+        int left = g * GR;
+        const int c0 = h->use_env ? std::min(left, h->env_first[g * GS] * NB) : 0;   // columns left of c0 are zero in these rows
+        left -= c0;
+        if (left > 0) {
+            dim3 grid((unsigned)((left + 511) / 512), 16);
+            if (!ls_push(h, LS_GEMV_T, grid.x * 16u, LsGemvT{h->B + (int64_t)g * GR * h->mp + c0, h->mp, GR / 16, left, out + (int64_t)g * GR, h->gPart, done, grid.x}))
+                hipLaunchKernelGGL(gemv_t_kernel, grid, dim3(256), 0, h->stream, h->B + (int64_t)g * GR * h->mp + c0, h->mp, GR / 16, left,
+                                   out + (int64_t)g * GR, h->gPart, done);
+            if (!ls_push(h, LS_SUB_PARTIALS, (unsigned)((left + 255) / 256), LsSubPart{z + c0, h->gPart, left, 16, done}))
+                hipLaunchKernelGGL(sub_partials_kernel, dim3((unsigned)((left + 255) / 256)), dim3(256), 0, h->stream, z + c0, h->gPart, left, 16, done);
+        }
+    }
+    HIP_TRY(h, hipGetLastError());
+    return IPM_OK;
+}
+
+// out = B^{-1} r  (r is consumed; uses t2 as the intermediate)
+static int enqueue_potrs(ipm_handle* h, double* r, double* out, hipEvent_t wait_last = nullptr) {
+    if (sp_on(h)) {                     // forward and backward sweep over the elimination tree, one launch each
+        const int rm = std::max(16, h->sp_rmax);
+        unsigned ep = ++h->sp_epoch;
+        const bool fwd_done = h->sp_fwd_fused != nullptr && h->sp_fwd_fused == r;       // the factorization carried L z = r already (z in t2)
+        h->sp_fwd_fused = nullptr;
+        const bool by_level = sp_level(h);                  // (evaluated once for both sweeps)
+        if (!fwd_done) sp_walk(h, by_level, /*leaves_first=*/true, [&](unsigned grid, const SpRec* recs, int count) {
+            hipLaunchKernelGGL((sp_fwd_kernel<SPC_THREADS, false>), dim3(grid), dim3(SPC_THREADS), h->sp_lds_solve, h->stream, h->spF, ep, r, h->t2, rm, recs, count);
+        });
+        if (!by_level) ep = ++h->sp_epoch;                   // the level-mode sweeps share one epoch, task mode takes one per sweep
+        sp_walk(h, by_level, /*leaves_first=*/false, [&](unsigned grid, const SpRec* recs, int count) {
+            hipLaunchKernelGGL((sp_bwd_kernel<SPC_THREADS, false>), dim3(grid), dim3(SPC_THREADS), 0, h->stream, h->spF, ep, h->t2, out, recs, count);
+        });
+        HIP_TRY(h, hipGetLastError());
+        return IPM_OK;
+    }
+    if (h->grouped_trsv) return enqueue_potrs_grouped(h, r, out, wait_last);
+    if (wait_last) HIP_TRY(h, hipStreamWaitEvent(h->stream, wait_last, 0));
+    enqueue_block_steps(h, 0, r, h->t2, out);
+    HIP_TRY(h, hipGetLastError());
+    return IPM_OK;
+}

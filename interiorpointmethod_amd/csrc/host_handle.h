@@ -1,0 +1,355 @@
+// host_handle.h -- host side of libipm_hip.so, unit 1: the handle, the scheduling predicates every launch site shares, error
+// reporting, the stream-ordered memory pool, the workspace layout and the argument views of the handle's device arrays.
+// Single translation unit: included by ipm_api.hip after the kernel headers, `static` functions only.
+#pragma once
+static thread_local char g_err[512] = "";
+
+// Live handles per device.  The device-polled hand-offs of the Cholesky look-ahead are only safe while ONE handle
+// drives the GPU (its two streams then sit on hardware queues of their own); with more than one live handle on a
+// device every factorization uses stream events instead (enqueue_factor).  Counted at create / destroy.
+static const int MAX_DEVICES = 64;
+static std::atomic<int> g_live[MAX_DEVICES];
+static std::atomic<bool> g_attr_set[MAX_DEVICES];      // per-device function attributes (dynamic LDS of adat_sparse)
+
+struct ipm_handle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    hipStream_t stream2 = nullptr;            // bulk stream of the Cholesky look-ahead
+    hipStream_t stream3 = nullptr;            // residual stream: r_b, r_c, stop test and the predictor rhs under the factorization
+    hipEvent_t ev_mid = nullptr, ev_res = nullptr, ev_grp = nullptr, ev_last = nullptr;
+    std::vector<hipEvent_t> ev_crit, ev_bulk;
+    hipEvent_t ev_fork = nullptr;
+    int lookahead = 1;
+    int grouped_trsv = 1;                 // group inverses + GEMV solves (trsv_grouped.h); IPM_GROUPED_TRSV=0 disables
+    int gsz = 0;                          // 128-blocks per group: 8 from 16 blocks on (ragged: leftover blocks are solved step by step), else the largest of 8/4/2 dividing nblk
+    double *gXT = nullptr, *gX = nullptr, *gS = nullptr, *gPart = nullptr;   // own allocation
+    unsigned* d_bulk_done = nullptr;      // [nblk] workgroup-completion counters of the bulk trailing updates
+    bool no_dense = false;                // B / invD / slab are not in the workspace (layout_no_dense); B_own, invD_own once ensure_dense_B ran
+    double* B_own = nullptr; double* invD_own = nullptr;
+    int group_steps = 0;                  // > 0: forced group size of the two-level schedule
+    int two_level = 1;                    // group the Cholesky steps: K = 128*gs trailing updates (IPM_TWO_LEVEL=0 disables)
+    int bulk_variant = 0;                 // 0: chol_update_kernel (adat_syrk schedule, round 3); 7: the generic kernel of rounds 1-2 (bit-identical, tested)
+    int ss_small_blocks = 16;             // single-stream handles: trailing blocks up to which the narrow-tile panel / update kernels are used (73-LP suite, 8 in flight:
+                                          // 12.4 / 13.5 / 14.1 / 14.5 / 14.4 LPs/s for 0 / 4 / 8 / 16 / 64 blocks)
+    int flag_sync = 1;                    // main stream polls d_bulk_done instead of waiting on a stream event
+    int last_gs = 1, n_counter_steps = 0, n_event_steps = 0, timeouts_recovered = 0;   // ipm_get_schedule
+    bool counted = false;                 // this handle is in g_live
+    // fused single-workgroup path for small sparse LPs (small_lp.h): product list of B's lower entries, own allocation
+    bool small = false;
+    int fused_small = 1;                  // IPM_FUSED_SMALL=0: always the multi-kernel path
+    bool list_form = false;               // sparse handle, 128 < m, <= 1536 padded rows: B from the product list (adat_list_kernel)
+    int list_form_opt = 1;                // IPM_LIST_FORM=0: one workgroup per row of B (adat_sparse_kernel)
+    int *ls_bi = nullptr, *ls_bk = nullptr;
+    double* ls_bak = nullptr;             // list path: sm_bcoef holds a_ij, ls_bak a_kj (the products are formed on the device)
+    int sm_nb = 0;
+    int *sm_bptr = nullptr, *sm_bcol = nullptr;
+    unsigned short *sm_bi = nullptr, *sm_bk = nullptr;
+    double* sm_bcoef = nullptr;
+    // multifrontal sparse Cholesky (sparse_chol.h), IPM_FLAG_SPARSE_FACTOR: structures built by ipm_set_A_csc, own allocations
+    bool spf = false;                     // the sparse factor serves this handle
+    bool spf_off = false;                 // set around calls that factor a caller's dense matrix (ipm_solve_linear)
+    bool sp_serial = false;               // after a hand-off time-out: one workgroup per launch (never waits)
+    SpFactor spF;                         // device view
+    std::vector<void*> sp_allocs;
+    int *sp_fptr = nullptr, *sp_fcol = nullptr;
+    double* sp_fcoef = nullptr;
+    long long* sp_diagpos = nullptr;
+    long long sp_nslot = 0, sp_nu = 0, sp_terms = 0;
+    int sp_height = 0, sp_rmax = 0, sp_grid = 1, sp_serial_launches = 0, sp_nvirtual = 0;
+    size_t sp_lds_chol = 0, sp_lds_solve = 0;
+    int sp_fv_off = 0;                    // doubles of sp_chol_kernel's dynamic LDS in front of the forward substitution's r-vector
+    int sp_fuse_fwd = 1;                  // the predictor's forward substitution rides on the factorization (IPM_SP_FUSE_FWD=0: own sweep)
+    const double* sp_fwd_fused = nullptr; // right-hand side whose forward substitution the last factorization carried (z in t2)
+    int sp_lds_doubles = 16, sp_threads = 256;
+    int sp_level_mode = 0;                // 1 (IPM_SP_MODE=level): one launch per level of the panel tree, no in-kernel hand-offs; -1 (=task): one
+                                          // launch per sweep even when the device is shared; 0: sp_level() decides
+    std::vector<int> sp_lvlptr;           // [levels + 1] into the level-ordered records
+    SpRec* sp_rec_level = nullptr;
+    unsigned sp_epoch = 0;
+    double shift_rel = 0.0;               // Tikhonov shift in effect (opt.regularize, or 1e-14 switched on by ipm_solve)
+    int auto_reg = 0;                     // 1: the shift was switched on automatically
+    unsigned* d_flags = nullptr;          // [2*nblk] hand-off flags + 1 timeout word (own allocation)
+    int64_t m = 0, n = 0, mp = 0, np = 0;
+    int nblk = 0, rc_chunks = 0, rows_per_chunk = 0, vblk = 0;
+    ipm_options opt;
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    bool own_ws = false;
+    // device arrays (all inside the workspace)
+    double *A = nullptr, *B = nullptr, *invD = nullptr;
+    double *x = nullptr, *s = nullptr, *c = nullptr, *rc = nullptr, *d = nullptr, *v = nullptr, *q = nullptr;
+    double *dxa = nullptr, *dsa = nullptr, *dx = nullptr, *ds = nullptr;
+    double *y = nullptr, *b = nullptr, *rb = nullptr, *t1 = nullptr, *t2 = nullptr, *dya = nullptr, *dy = nullptr;
+    double *atp = nullptr, *part = nullptr, *slab = nullptr;
+    // fused formation + factorization (form_factor.h): dense handles of FF_MIN_NBLK .. FF_MAX_NBLK blocks that have the device to
+    // themselves run ONE persistent worker launch beside the pivot chain instead of formation followed by factorization
+    int ff_enabled = 1;                   // IPM_FUSED_FACTOR=0 disables, =force also below FF_MIN_NBLK blocks (tests)
+    // Where the fused launch is the default.  Measured on MI355X, it/s fused / serial (tools/ff_sizes.sh, profiles/r04_ff_sizes_fused_vs_serial.txt;
+    // n = 2m unless noted): 1536: 903 / 941 -- 2048: 684 / 640 -- 2560: 514 / 439 -- 3072: 422 / 302 -- 3584: 335 / 242 -- 4096: 259 / 208 --
+    // 5120: 150 / 113 -- 6144: 93.3 / 79.6 -- 8192: 41.8 / 40.0 -- 10240: 22.3 / 22.4 -- 4096 x 4608: 358 / 267 -- 4096 x 16384: 152 / 137 --
+    // 4096 x 32768: 85.5 / 87.1 (the formation dominates there and the serial kernel forms faster).  So: 16 .. 72 blocks while n <= 6 m.
+    // IPM_FF_MAX_NBLK / IPM_FUSED_FACTOR=force|0 override.
+    int ff_min_nblk = 16, ff_max_nblk = 72;
+    bool ff_forced = false;
+    bool ff_ref_engine = false;           // IPM_FF_REF_ENGINE=1: form_factor_roles_kernel (the engines' previous stage schedule), the reference of tests/test_gpu_ff_engines.py
+    int ff_q = 4;                         // formation chunks per tile (IPM_FF_Q)
+    int ff_workers = 0;                   // WORKER workgroups of the persistent launch (set by ff_build from the CU count, no switch)
+    int* d_ff_tile_items = nullptr;       // [tile_items | tile_q]
+    int ff_qmax = 16;                     // slab capacity per tile (the first block rows are formed in more, shorter chunks)
+    bool ff_built = false, ff_last = false;
+    FFSchedule ff_sched;
+    FFItem* d_ff_items = nullptr;         // the work list in ticket order
+    unsigned* d_ff_flags = nullptr;       // ticket[16] | reserved[8] | dbg[8] | fcount[ntile] | tprog[ntile] | lfinal[nblk] | dready[nblk] | potrfdone[nblk]
+    size_t ff_flag_words = 0;
+    double* ff_slab = nullptr;            // [ntile][Q][128*128]
+    long long* ff_trace = nullptr;        // IPM_FF_TRACE_ITEMS=1: [nitems][4] per-item time line + [nblk][12] chain kernels (ipm_debug_ff_trace)
+    long long* ff_prof = nullptr;         // IPM_FF_PROF=1: [workers][16] cycle profile of the persistent launch (accumulates)
+    const int* fdone = nullptr;           // `done` word the formation / factorization kernels test (null: Scalars::done; the overlapped
+                                          // path points it at the per-iteration latch Scalars::done_f)
+    // Tile envelope (skyline) of A A^T for sparse handles, from the structure of A in the caller's row order:
+    // env_last[k] = last 128-row block with a structural nonzero at or left of column block k (monotone).  Blocks
+    // below it are exactly zero in B and stay zero in L, so the panel solves, trailing updates and triangular
+    // solves skip them.  The Python host reorders the rows (reverse Cuthill-McKee) to make the envelope small.
+    std::vector<int> env_last, env_first;     // env_first[i] = first column block with env_last >= i
+    bool use_env = false;
+    int envelope = 1;                         // IPM_ENVELOPE=0 disables
+    bool sparse = false;                 // A kept as CSR + CSC on the device
+    int64_t nnz_cap = 0, nnz = 0;
+    int* d_tile_order = nullptr;         // 2-D patch order of the lower 128x128 tiles of B (L2 reuse)
+    int *d_rowptr = nullptr, *d_colind = nullptr, *d_colptr = nullptr, *d_rowind = nullptr;
+    double *d_rval = nullptr, *d_cval = nullptr;
+    long long* stamp_buf = nullptr;       // diagnostic only (IPM_POTRF_STAMPS=1)
+    unsigned* ff_potrfdone = nullptr;     // fused launch: the chain's hand-off words of the launch enqueued last (one per block)
+    Scalars* sc = nullptr;
+    IterRec* hist = nullptr;              // [HIST_CAP] per-iteration records (ring)
+    double* snap = nullptr;               // roll-back copy of (x, y, s) + Scalars (poll time-out / auto-regularize restart)
+    // native upper bounds (ipm_set_bounds): own allocation of BND_VECS n-vectors, made on first use
+    bool bnd = false;                     // a finite bound is set: the bounded kernel instantiations run
+    int bnd_nU = 0;                       // |U|
+    double* bnd_mem = nullptr;            // u | w | z | dwa | dza | dw | dz | qz | roll-back w | roll-back z
+    // infeasibility detection (IPM_FLAG_DETECT_INFEASIBILITY): the Detect kernel instantiations run
+    bool detect = false;
+    double det_eps_p = 1e-8, det_eps_d = 1e-8;   // ipm_set_infeasibility_tol
+    double* det = nullptr;                // [4] record of the last detection (workspace): kind, normalisation, violation, k
+    double* cert_mem = nullptr;           // x | y | z of ipm_get_certificate (own allocation, made on first use)
+    int* fixed = nullptr;
+    Scalars* h_sc = nullptr;          // pinned host mirror
+    bool haveA = false, haveBC = false, haveState = false, predictor_valid = false;
+    bool fresh_state = true;              // the iterate was (re)set: the next ipm_iterate counts its steps from k = 0
+    int profiling = 0;                    // 0 off, 1 events around the A D^2 A^T kernel only, 2 every phase
+    double phase_ms[4] = {0, 0, 0, 0};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // lockstep batch (lockstep.h, ipm_solve_batch): while non-null, every launch site of the single-stream iteration path RECORDS
+    // (kernel type, grid, arguments) here instead of launching
+    std::vector<struct LsLaunch>* ls_rec = nullptr;
+    bool ls_cut = false;                  // a launch without a lockstep twin was met while recording
+    int lockstep = 0;                     // IPM_FLAG_LOCKSTEP: created for ipm_solve_batch (block-step substitutions: every launch of the iteration is recordable)
+    // switches ipm_create acts on once (read_env_switches)
+    unsigned spin_limit = 1u << 22;       // IPM_TEST_SPIN_LIMIT: spin bound of the device-side hand-offs (test knob, see gemm_nt_f64.h)
+    bool ragged_groups = true;            // IPM_RAGGED_GROUPS=0: group inverses only where the group size divides the block count
+    bool ls_block_steps = false, potrf_stamps = false, ff_chain_mode0 = false;   // IPM_LS_BLOCK_STEPS (A/B: block-step substitutions in the lockstep
+                                          // batch), IPM_POTRF_STAMPS (allocate stamp_buf), IPM_FF_CHAIN_MODE=0 was asked for (refused by ipm_create)
+    char err[512] = "";
+};
+struct LsLaunch { int type; LsRec rec; };
+template <class A> static bool ls_push(ipm_handle* h, int type, unsigned gridx, const A& a, unsigned lds = 0) {
+    if (!h->ls_rec) return false;
+    static_assert(sizeof(A) <= LS_ARG_BYTES, "LsRec::args too small");
+    LsLaunch L;
+    memset(&L, 0, sizeof L);
+    L.type = type; L.rec.gridx = gridx; L.rec.lds = lds;
+    memcpy(L.rec.args, &a, sizeof(A));
+    h->ls_rec->push_back(L);
+    return true;
+}
+
+// the message goes to the thread's record and to `err` (char[512] of a handle or a batch, may be null); returns `code`
+static int vfail(char* err, int code, const char* fmt, va_list ap) {
+    char buf[512];
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    snprintf(g_err, sizeof g_err, "%s", buf);
+    if (err) snprintf(err, 512, "%s", buf);
+    return code;
+}
+static int fail(ipm_handle* h, int code, const char* fmt, ...) { va_list ap; va_start(ap, fmt); code = vfail(h ? h->err : nullptr, code, fmt, ap); va_end(ap); return code; }
+
+#define HIP_TRY(h, call)                                                                      \
+    do {                                                                                      \
+        hipError_t e_ = (call);                                                               \
+        if (e_ != hipSuccess)                                                                 \
+            return fail((h), IPM_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
+                        __FILE__, __LINE__);                                                  \
+    } while (0)
+
+static inline int64_t round_up(int64_t v, int64_t q) { return (v + q - 1) / q * q; }
+
+// ------------------------------------------------------------------------------- scheduling rules, each stated once
+static inline int live_on_device(const ipm_handle* h) { return h->device < MAX_DEVICES ? g_live[h->device].load(std::memory_order_acquire) : 1; }
+static inline bool alone_on_device(const ipm_handle* h) { return live_on_device(h) <= 1; }      // device-polled hand-offs are allowed (see g_live)
+static inline bool lookahead_on(const ipm_handle* h) { return h->lookahead != 0 && h->nblk > 2 && h->stream2 != nullptr; }
+// wants_polling: the handle ASKS for device-polled hand-offs in the look-ahead; polls_device: a launch enqueued now gets them.
+// may_poll (host_iteration.h) decides about the roll-back snapshot with wants_polling, WITHOUT alone_on_device: the live-handle
+// count can change between the snapshot and the launch, so the snapshot rule is deliberately the conservative superset of the
+// launch rule -- a launch that polls always has a snapshot to roll back to.
+static inline bool wants_polling(const ipm_handle* h) { return lookahead_on(h) && h->flag_sync != 0; }
+static inline bool polls_device(const ipm_handle* h) { return wants_polling(h) && alone_on_device(h); }
+static inline unsigned* timeout_word(const ipm_handle* h) { return h->d_flags + 2 * (size_t)h->nblk; }      // time-out word of the device-side hand-offs
+static inline const int* factor_done(const ipm_handle* h) { return h->fdone ? h->fdone : &h->sc->done; }    // `done` word formation / factorization test
+
+// Device memory the handle owns besides its workspace.  STREAM-ORDERED (hipMallocAsync / hipFreeAsync on the handle's
+// stream, pool kept for reuse): a plain hipFree synchronises the whole device, and with several LPs in flight every one
+// of a handle's ~30 frees waited for the other LPs' queued iterations -- measured in the 73-LP suite: STOCFOR3 0.46 s of
+// solve and 1.14 s of teardown, SIERRA 0.12 s and 1.19 s.
+static std::atomic<int> g_pool_state[64];       // per device: 0 unknown, 1 stream-ordered allocation available, 2 not
+static hipMemPool_t g_pool[64];                 // the library's OWN pool per device (never the device's default pool: its
+                                                // attributes belong to the host application)
+static std::mutex g_pool_mutex;
+static bool async_alloc_ok(int device) {
+    if (device < 0 || device >= 64) return false;
+    int st = g_pool_state[device].load(std::memory_order_acquire);
+    if (st == 0) {
+        std::lock_guard<std::mutex> lock(g_pool_mutex);
+        st = g_pool_state[device].load(std::memory_order_acquire);
+        if (st != 0) return st == 1;
+        int supported = 0;
+        if (hipDeviceGetAttribute(&supported, hipDeviceAttributeMemoryPoolsSupported, device) == hipSuccess && supported) {
+            hipMemPoolProps props;
+            memset(&props, 0, sizeof props);
+            props.allocType = hipMemAllocationTypePinned;
+            props.handleTypes = hipMemHandleTypeNone;
+            props.location.type = hipMemLocationTypeDevice;
+            props.location.id = device;
+            hipMemPool_t pool = nullptr;
+            if (hipMemPoolCreate(&pool, &props) == hipSuccess && pool) {
+                // freed blocks stay in the pool up to this many bytes, so the next handle reuses them (the sparse factor of
+                // one LP is ~20 blocks); beyond it they go back to the device at the next synchronisation point instead of
+                // staying resident for the life of the process
+                uint64_t keep = (uint64_t)2 << 30;
+                (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
+                g_pool[device] = pool;
+                st = 1;
+            }
+        }
+        if (st == 0) st = 2;
+        g_pool_state[device].store(st, std::memory_order_release);
+    }
+    return st == 1;
+}
+static hipError_t dev_malloc(int device, hipStream_t stream, void** p, size_t bytes) {
+    if (bytes == 0) bytes = 16;
+    if (async_alloc_ok(device)) return hipMallocFromPoolAsync(p, bytes, g_pool[device], stream);
+    return hipMalloc(p, bytes);
+}
+static void dev_free(int device, hipStream_t stream, void* p) {
+    if (!p) return;
+    if (async_alloc_ok(device)) (void)hipFreeAsync(p, stream); else (void)hipFree(p);
+}
+// pinned host mirrors of the scalar record are recycled, never freed (hipHostFree synchronises too)
+static std::mutex g_hsc_mutex;
+static std::vector<Scalars*> g_hsc_pool;
+
+static GemmNT gemm_defaults() {
+    GemmNT g;
+    memset(&g, 0, sizeof g);
+    g.alpha = 1.0; g.unit_diag_from = -1; g.batch = 1; g.batch2 = 1;
+    return g;
+}
+
+// ------------------------------------------------------------------------------- layout
+struct Layout {
+    int64_t mp, np;
+    int nblk, rc_chunks, rows_per_chunk, vblk;
+    size_t off_A, off_B, off_inv, off_nvec, off_mvec, off_atp, off_part, off_det, off_sc, off_fixed, off_hist, off_snap, off_slab, total;
+    size_t off_rowptr, off_colind, off_rval, off_colptr, off_rowind, off_cval, off_order;
+};
+static const int N_NVEC = 11;   // x s c rc d v q dxa dsa dx ds
+static const int N_MVEC = 7;    // y b rb t1 t2 dya dy
+
+// no_dense: the handle factors with the sparse multifrontal Cholesky (IPM_FLAG_SPARSE_FACTOR on a sparse handle beyond the fused
+// small-LP size) -- B, inv(L_kk) and the split-K slab are not part of the workspace; ensure_dense_B allocates them if a
+// dense entry point (ipm_form_normal_matrix, ipm_get_factor, ipm_solve_linear) is ever called on such a handle.
+static bool layout_no_dense(int64_t m, int64_t sparse_nnz, unsigned flags) { return sparse_nnz > 0 && (flags & IPM_FLAG_SPARSE_FACTOR) && m > 128; }
+static Layout make_layout(int64_t m, int64_t n, int64_t sparse_nnz = 0, bool no_dense = false) {
+    Layout L;
+    L.mp = round_up(m, NB);
+    {   // the grouped triangular solves (trsv_grouped.h) need whole 1024-row groups: pad a little further when that
+        // costs at most 1/8 more blocks (identity rows are cheap; 4 x nblk dependent launches per iteration are not)
+        const int64_t nb = L.mp / NB, nb8 = round_up(nb, 8);
+        if (nb >= 16 && (nb8 - nb) * 8 <= nb) L.mp = nb8 * NB;
+    }
+    L.np = round_up(n, 64);
+    L.nblk = (int)(L.mp / NB);
+    int64_t c64 = L.mp / 64;
+    L.rc_chunks = (int)(c64 <= 32 ? c64 : 32);          // <= 32 row chunks of A^T u partials (mp/64 must divide evenly)
+    while (L.mp % L.rc_chunks) --L.rc_chunks;
+    L.rows_per_chunk = (int)(L.mp / L.rc_chunks);
+    while ((int64_t)L.rc_chunks * L.rows_per_chunk < L.mp) ++L.rows_per_chunk;   // (exact by construction)
+    int64_t mx = m > n ? m : n;
+    int64_t vb = (mx + VBLK - 1) / VBLK;          // one element per thread until MAXPART blocks
+    L.vblk = (int)(vb < 1 ? 1 : (vb > MAXPART ? MAXPART : vb));
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    if (sparse_nnz > 0) { L.rc_chunks = 1; L.rows_per_chunk = (int)L.mp; }
+    L.off_A = take(sparse_nnz > 0 ? 0 : sizeof(double) * L.mp * L.np);
+    L.off_B = take(no_dense ? 0 : sizeof(double) * L.mp * L.mp);
+    L.off_inv = take(no_dense ? 0 : sizeof(double) * L.nblk * NB * NB);
+    L.off_nvec = take(sizeof(double) * L.np * N_NVEC);
+    L.off_mvec = take(sizeof(double) * L.mp * N_MVEC);
+    L.off_atp = take(sizeof(double) * L.rc_chunks * L.np);
+    L.off_part = take(sizeof(double) * P_NSLOT_DETECT * MAXPART);     // (the slots of the infeasibility tests included)
+    L.off_det = take(sizeof(double) * 4);
+    L.off_sc = take(sizeof(Scalars));
+    L.off_fixed = take(256);
+    L.off_hist = take(sizeof(IterRec) * HIST_CAP);
+    L.off_snap = take(sizeof(double) * (2 * L.np + L.mp) + sizeof(Scalars));
+    L.off_slab = take(no_dense ? 0 : sizeof(double) * (size_t)kSlabTiles * 128 * 128);   // split-K partial tiles (64 MB)
+    L.off_order = take(sizeof(int) * ((size_t)L.nblk * (L.nblk + 1) / 2));
+    L.off_rowptr = take(sparse_nnz > 0 ? sizeof(int) * (m + 1) : 0);
+    L.off_colptr = take(sparse_nnz > 0 ? sizeof(int) * (n + 1) : 0);
+    L.off_colind = take(sparse_nnz > 0 ? sizeof(int) * sparse_nnz : 0);
+    L.off_rowind = take(sparse_nnz > 0 ? sizeof(int) * sparse_nnz : 0);
+    L.off_rval = take(sparse_nnz > 0 ? sizeof(double) * sparse_nnz : 0);
+    L.off_cval = take(sparse_nnz > 0 ? sizeof(double) * sparse_nnz : 0);
+    L.total = off;
+    return L;
+}
+
+__global__ void set_params_kernel(Scalars* sc, double e1, double e2, double e3, double eta, int max_iter,
+                                  int force, int reset) {
+    sc->e1 = e1; sc->e2 = e2; sc->e3 = e3; sc->eta = eta;
+    sc->max_iter = max_iter; sc->force = force;
+    sc->done = 0; sc->done_f = 0; sc->status = 0;
+    if (reset) { sc->k = 0; sc->fixed = 0; sc->fixed_first = 0; sc->obj_last_finite = __builtin_nan(""); }
+}
+
+static VecArgs vec_args(ipm_handle* h) {
+    VecArgs a;
+    a.m = (int)h->m; a.n = (int)h->n; a.np = (int)h->np; a.rc_chunks = h->rc_chunks; a.nblk = h->vblk;
+    a.atp = h->atp; a.x = h->x; a.y = h->y; a.s = h->s; a.b = h->b; a.c = h->c;
+    a.rb = h->rb; a.rc = h->rc; a.d = h->d; a.v = h->v; a.q = h->q;
+    a.dxa = h->dxa; a.dya = h->dya; a.dsa = h->dsa; a.dx = h->dx; a.dy = h->dy; a.ds = h->ds;
+    a.part = h->part; a.sc = h->sc; a.hist = h->hist;
+    return a;
+}
+
+static SparseA sparse_view(const ipm_handle* h) {
+    SparseA A;
+    A.rowptr = h->d_rowptr; A.colind = h->d_colind; A.rval = h->d_rval;
+    A.colptr = h->d_colptr; A.rowind = h->d_rowind; A.cval = h->d_cval;
+    A.m = (int)h->m; A.n = (int)h->n;
+    return A;
+}
+
+// native upper bounds: views into the BND_VECS n-vectors of ipm_set_bounds
+static const int BND_VECS = 10;
+static BndArgs bnd_args(ipm_handle* h) {
+    const size_t np = (size_t)h->np;
+    double* p = h->bnd_mem;
+    BndArgs b;
+    b.u = p; b.w = p + np; b.z = p + 2 * np; b.dwa = p + 3 * np; b.dza = p + 4 * np; b.dw = p + 5 * np; b.dz = p + 6 * np;
+    b.qz = p + 7 * np; b.nU = h->bnd_nU;
+    return b;
+}
+
+static DetArgs det_args(const ipm_handle* h) { return DetArgs{h->det_eps_p, h->det_eps_d, h->det}; }

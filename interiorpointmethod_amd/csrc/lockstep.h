@@ -11,7 +11,7 @@
 //
 // How.  Nothing about an LP's arithmetic changes: the handle's own launch sequence (enqueue_iteration, single-stream path) is
 // RECORDED once -- every launch site pushes (kernel type, grid, argument struct) instead of launching -- and the records of all
-// LPs are merged, each LP's order preserved, into global steps of one kernel type each (ipm_api.hip: ls_merge).  The device
+// LPs are merged, each LP's order preserved, into global steps of one kernel type each (host_lockstep.h: ls_merge).  The device
 // code of a step is the body of the kernel the handle would have launched (X_kernel_body, shared with the one-LP kernels), so a
 // lockstep solve is BIT-IDENTICAL to the same handle solved alone (tests/test_gpu_lockstep.py).
 #pragma once

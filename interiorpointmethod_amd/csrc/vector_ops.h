@@ -261,7 +261,7 @@ __global__ __launch_bounds__(VBLK) void prepare_detect_kernel(VecArgs a) { prepa
 __global__ __launch_bounds__(VBLK) void prepare_bounded_detect_kernel(VecArgs a, BndArgs bd) { prepare_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd); }
 
 // d = x / s only (main.py:223): what the formation of A D^2 A^T needs; the full prepare_kernel follows on the residual
-// stream while the factorization runs (ipm_api.hip, enqueue_iteration).  Bounded: d = theta on U.
+// stream while the factorization runs (host_iteration.h, enqueue_iteration).  Bounded: d = theta on U.
 template <bool Bounded = false>
 __device__ __forceinline__ void scaling_kernel_body(VecArgs a, BndArgs bd = BndArgs{}) {
     if (blockIdx.x == 0 && threadIdx.x == 0) a.sc->done_f = a.sc->done;      // latch for this iteration's factorization

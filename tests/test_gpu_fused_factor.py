@@ -90,7 +90,7 @@ def test_fused_path_factor_of_a_given_scaling(monkeypatch):
 
 
 def test_default_rule_selects_the_fused_path_where_it_was_measured_faster():
-    """The selection rule (ipm_api.hip: 16 .. 72 blocks, n <= 6 m; profiles/r04_ff_sizes_fused_vs_serial.txt): the headline size and
+    """The selection rule (host_fused.h: ff_ok, 16 .. 72 blocks, n <= 6 m; profiles/r04_ff_sizes_fused_vs_serial.txt): the headline size and
     a 16-block LP run fused, a very wide LP (formation-dominated) and a small one do not."""
     for (m, n), want in (((4096, 8192), 1), ((2048, 4096), 1), ((1536, 3072), 0), ((2048, 16384), 0)):
         A, b, c = synthetic_lp(m, n, seed=1)
