@@ -58,26 +58,16 @@ static int enqueue_form(ipm_handle* h, const double* d, bool dense_image = false
     if (h->sparse && h->list_form) {
         const int64_t nB = h->mp * h->mp;                       // even (mp is a multiple of 128)
         const unsigned zgrid = (unsigned)std::min<int64_t>((nB / 2 + 255) / 256, 4096);
-        if (!ls_push(h, LS_ZERO, zgrid, LsZero{h->B, nB, &h->sc->done}))
-            hipLaunchKernelGGL(zero_unless_done_kernel, dim3(zgrid), dim3(256), 0, h->stream, h->B, nB, &h->sc->done);
+        launch_twin<LS_ZERO>(h, zgrid, {h->B, nB, &h->sc->done});
         const int work = h->sm_nb + (int)(h->mp - h->m);
-        const LsAdatList pl{h->sm_bptr, h->ls_bi, h->ls_bk, h->sm_bcol, h->sm_bcoef, h->ls_bak, h->sm_nb, d, h->B, h->mp, (int)h->m, (int)h->mp, &h->sc->done};
-        if (!ls_push(h, LS_ADAT_LIST, (unsigned)((work + 255) / 256), pl))
-            hipLaunchKernelGGL(adat_list_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, h->stream, h->sm_bptr, h->ls_bi, h->ls_bk,
-                               h->sm_bcol, h->sm_bcoef, h->ls_bak, h->sm_nb, d, h->B, h->mp, (int)h->m, (int)h->mp, &h->sc->done);
+        launch_twin<LS_ADAT_LIST>(h, (unsigned)((work + 255) / 256), {h->sm_bptr, h->ls_bi, h->ls_bk, h->sm_bcol, h->sm_bcoef, h->ls_bak, h->sm_nb, d, h->B, h->mp, (int)h->m, (int)h->mp, &h->sc->done});
         HIP_TRY(h, hipGetLastError());
         return IPM_OK;
     }
     if (h->sparse) {
         const LsAdatSp ps{sparse_view(h), d, h->B, h->mp, (int)h->mp, &h->sc->done};
-        if (h->mp <= SP_LDS_MAX_MP) {          // dynamic-LDS attribute set per device in ipm_create
-            if (!ls_push(h, LS_ADAT_SPARSE, (unsigned)h->mp, ps, (unsigned)(h->mp * sizeof(double))))
-                hipLaunchKernelGGL(adat_sparse_kernel, dim3((unsigned)h->mp), dim3(256), (size_t)h->mp * sizeof(double), h->stream,
-                                   sparse_view(h), d, h->B, h->mp, (int)h->mp, &h->sc->done);
-        } else if (!ls_push(h, LS_ADAT_SPARSE_GLOBAL, (unsigned)h->mp, ps)) {
-            hipLaunchKernelGGL(adat_sparse_global_kernel, dim3((unsigned)h->mp), dim3(256), 0, h->stream, sparse_view(h), d,
-                               h->B, h->mp, (int)h->mp, &h->sc->done);
-        }
+        if (h->mp <= SP_LDS_MAX_MP) launch_twin<LS_ADAT_SPARSE>(h, (unsigned)h->mp, ps, nullptr, (unsigned)(h->mp * sizeof(double)));   // dynamic-LDS attribute set per device in ipm_create
+        else launch_twin<LS_ADAT_SPARSE_GLOBAL>(h, (unsigned)h->mp, ps);
         HIP_TRY(h, hipGetLastError());
         return IPM_OK;
     }
@@ -100,8 +90,7 @@ static int enqueue_group_inverses(ipm_handle* h, int g0 = 0, int g1 = -1, hipStr
     const int nG = g1 - g0;                               // groups [g0, g1)
     if (nG <= 0) return IPM_OK;
     const int* done = &h->sc->done;
-    if (!ls_push(h, LS_GROUP_DIAG_T, 16u * (unsigned)(nG * GS), LsGroupDiagT{h->invD, h->gXT, h->gX, g0 * GS, GS, done}))
-        hipLaunchKernelGGL(group_diag_transpose_kernel, dim3(4, 4, nG * GS), dim3(32, 8), 0, st, h->invD, h->gXT, h->gX, g0 * GS, GS, done);
+    launch_twin<LS_GROUP_DIAG_T>(h, 16u * (unsigned)(nG * GS), {h->invD, h->gXT, h->gX, g0 * GS, GS, done}, st);
     const int64_t gXs = GR * GR, gL = GR * (h->mp + 1), gSs = (GR / 2) * (GR / 2);   // group strides in X/XT, L, S
     double* gXT = h->gXT + g0 * gXs; double* gX = h->gX + g0 * gXs; double* gS = h->gS + g0 * gSs;
     const double* Lg = h->B + g0 * gL;
@@ -164,8 +153,7 @@ static int enqueue_factor(ipm_handle* h, bool use_env = false, int mid_step = -1
     const int* done = factor_done(h);
     use_env = use_env && h->use_env;
     // threshold scale = max diag over the TRUE rows only (padding rows carry a unit diagonal)
-    if (!ls_push(h, LS_MAXDIAG, 1u, LsMaxdiag{h->B, h->mp, (int)h->m, &h->sc->maxdiag, done}))
-        hipLaunchKernelGGL(maxdiag_kernel, dim3(1), dim3(256), 0, h->stream, h->B, h->mp, (int)h->m, &h->sc->maxdiag, done);
+    launch_twin<LS_MAXDIAG>(h, 1u, {h->B, h->mp, (int)h->m, &h->sc->maxdiag, done});
     const bool la = lookahead_on(h);
     // group size of the two-level schedule.  Measured (factor, ms): 16384 x 32768: 39.7 / 34.9 / 33.4 / 32.9 / 32.5 for groups
     // of 1 / 2 / 3 / 4 / 6; 8192 x 16384: 7.87 / 7.46 / 7.34 / 7.34 for 1 / 2 / 3 / 4; but 4096 x 8192: 2.21 -> 2.36 with groups
@@ -204,13 +192,11 @@ static int enqueue_factor(ipm_handle* h, bool use_env = false, int mid_step = -1
         pd.trace = nullptr;
         pd.nt = potrf_panels(h, k);
         pd.rows = (int)(h->m - (int64_t)k * NB);
-        if (h->stamp_buf && k == 0) {
+        if (h->stamp_buf && k == 0) {                               // (IPM_POTRF_STAMPS: the stamping instantiation has no twin)
             pd.stamps = h->stamp_buf;
             if (getenv("IPM_POTRF_SKIP")) pd.dbg_tag = (unsigned)atoi(getenv("IPM_POTRF_SKIP"));
-            hipLaunchKernelGGL(potrf_diag_kernel<true>, dim3(1), dim3(PD_THREADS), 0, sm, pd);
-        } else if (!ls_push(h, LS_POTRF, 1u, pd)) {
-            hipLaunchKernelGGL(potrf_diag_kernel<false>, dim3(1), dim3(PD_THREADS), 0, sm, pd);
-        }
+            launch_untwinned(h, potrf_diag_kernel<true>, dim3(1), dim3(PD_THREADS), sm, pd);
+        } else launch_twin<LS_POTRF>(h, 1u, pd, sm);
         if (k == ginv_step) {
             // blocks 0 .. k are final (the diagonal block k was just factored, every panel block left of it in these rows is
             // ordered before it through the look-ahead hand-offs): the inverses of the complete 1024-row groups go to the
@@ -242,7 +228,8 @@ static int enqueue_factor(ipm_handle* h, bool use_env = false, int mid_step = -1
         if (!la) {
             // one stream (batched mode, small handles): panel and update are BOTH on the dependent chain of the step.  With few
             // trailing blocks the chip is empty anyway: narrower tiles (32-row panel strips on 8 waves / 64 x 64 update tiles) are
-            // latency-shorter kernels -- ss_small_blocks = trailing blocks up to which they are used (IPM_SS_SMALL_TILES)
+            // latency-shorter kernels -- ss_small_blocks = trailing blocks up to which they are used (16, or every step of a
+            // lockstep handle: fixed by ipm_create, no environment switch reads it)
             if (rem <= h->ss_small_blocks * NB) {
                 HIP_TRY(h, (launch_gemm_nt<32, 128, 32, 1, 8>(t, sm)));
                 HIP_TRY(h, (launch_gemm_nt<64, 64, 16, 2, 2>(u, sm)));
@@ -327,9 +314,7 @@ static int enqueue_factor(ipm_handle* h, bool use_env = false, int mid_step = -1
 
 static void launch_dense_gemv_n(ipm_handle* h, const double* A, int64_t lda, int rows, int cols, const double* v, double sa,
                                 double sb, const double* add, double* out) {
-    if (ls_push(h, LS_GEMV_N, (unsigned)((rows + 3) / 4), LsGemvN{A, lda, rows, cols, v, sa, sb, add, out, &h->sc->done})) return;
-    hipLaunchKernelGGL(gemv_n_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, h->stream, A, lda, rows, cols, v, sa, sb,
-                       add, out, &h->sc->done);
+    launch_twin<LS_GEMV_N>(h, (unsigned)((rows + 3) / 4), {A, lda, rows, cols, v, sa, sb, add, out, &h->sc->done});
 }
 
 // Block-step substitution over the blocks [k0, nblk), one launch per block step: forward sweep L z = r, then the backward sweep
@@ -341,13 +326,13 @@ static void enqueue_block_steps(ipm_handle* h, int k0, double* r, double* z, dou
     for (int k = k0; k < h->nblk; ++k) {
         a.k = k;
         const int nb = h->use_env ? h->env_last[k] - k + 1 : h->nblk - k;
-        if (!ls_push(h, LS_TRSV_FWD, (unsigned)nb, a)) hipLaunchKernelGGL(trsv_fwd_step_kernel, dim3(nb), dim3(256), 0, h->stream, a);
+        launch_twin<LS_TRSV_FWD>(h, (unsigned)nb, a);
     }
     a.r = z; a.z = out;
     for (int k = h->nblk - 1; k >= k0; --k) {
         a.k = k;
         a.j0 = h->use_env ? h->env_first[k] : 0;
-        if (!ls_push(h, LS_TRSV_BWD, (unsigned)(k - a.j0 + 1), a)) hipLaunchKernelGGL(trsv_bwd_step_kernel, dim3(k - a.j0 + 1), dim3(256), 0, h->stream, a);
+        launch_twin<LS_TRSV_BWD>(h, (unsigned)(k - a.j0 + 1), a);
     }
 }
 
@@ -379,12 +364,9 @@ static int enqueue_potrs_grouped(ipm_handle* h, double* r, double* out, hipEvent
         const int c0 = h->use_env ? std::min(left, h->env_first[g * GS] * NB) : 0;   // columns left of c0 are zero in these rows
         left -= c0;
         if (left > 0) {
-            dim3 grid((unsigned)((left + 511) / 512), 16);
-            if (!ls_push(h, LS_GEMV_T, grid.x * 16u, LsGemvT{h->B + (int64_t)g * GR * h->mp + c0, h->mp, GR / 16, left, out + (int64_t)g * GR, h->gPart, done, grid.x}))
-                hipLaunchKernelGGL(gemv_t_kernel, grid, dim3(256), 0, h->stream, h->B + (int64_t)g * GR * h->mp + c0, h->mp, GR / 16, left,
-                                   out + (int64_t)g * GR, h->gPart, done);
-            if (!ls_push(h, LS_SUB_PARTIALS, (unsigned)((left + 255) / 256), LsSubPart{z + c0, h->gPart, left, 16, done}))
-                hipLaunchKernelGGL(sub_partials_kernel, dim3((unsigned)((left + 255) / 256)), dim3(256), 0, h->stream, z + c0, h->gPart, left, 16, done);
+            const unsigned gx = (unsigned)((left + 511) / 512);      // blocks per row chunk, 16 row chunks
+            launch_twin<LS_GEMV_T>(h, gx * 16u, {h->B + (int64_t)g * GR * h->mp + c0, h->mp, GR / 16, left, out + (int64_t)g * GR, h->gPart, done, gx});
+            launch_twin<LS_SUB_PARTIALS>(h, (unsigned)((left + 255) / 256), {z + c0, h->gPart, left, 16, done});
         }
     }
     HIP_TRY(h, hipGetLastError());

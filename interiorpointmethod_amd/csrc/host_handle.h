@@ -140,8 +140,7 @@ struct ipm_handle {
     int profiling = 0;                    // 0 off, 1 events around the A D^2 A^T kernel only, 2 every phase
     double phase_ms[4] = {0, 0, 0, 0};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // lockstep batch (lockstep.h, ipm_solve_batch): while non-null, every launch site of the single-stream iteration path RECORDS
-    // (kernel type, grid, arguments) here instead of launching
+    // lockstep batch (lockstep.h, ipm_solve_batch): while non-null, launch_twin (below) RECORDS here instead of launching
     std::vector<struct LsLaunch>* ls_rec = nullptr;
     bool ls_cut = false;                  // a launch without a lockstep twin was met while recording
     int lockstep = 0;                     // IPM_FLAG_LOCKSTEP: created for ipm_solve_batch (block-step substitutions: every launch of the iteration is recordable)
@@ -153,15 +152,23 @@ struct ipm_handle {
     char err[512] = "";
 };
 struct LsLaunch { int type; LsRec rec; };
-template <class A> static bool ls_push(ipm_handle* h, int type, unsigned gridx, const A& a, unsigned lds = 0) {
-    if (!h->ls_rec) return false;
-    static_assert(sizeof(A) <= LS_ARG_BYTES, "LsRec::args too small");
-    LsLaunch L;
-    memset(&L, 0, sizeof L);
-    L.type = type; L.rec.gridx = gridx; L.rec.lds = lds;
-    memcpy(L.rec.args, &a, sizeof(A));
+// A launch site of the iteration names its kernel type and fills ONE argument struct (lockstep.h: LsTwin<T>): the launch is recorded
+// while a program is being recorded (record_twin: also the GEMM launchers' way in, ls_gemm_hook), else the single-LP kernel runs.
+template <LsType T> static void record_twin(ipm_handle* h, unsigned gridx, const LsArgs<T>& a, unsigned lds = 0) {
+    LsLaunch L{};
+    L.type = T; L.rec.gridx = gridx; L.rec.lds = lds;
+    memcpy(L.rec.args, &a, sizeof a);
     h->ls_rec->push_back(L);
-    return true;
+}
+template <LsType T> static void launch_twin(ipm_handle* h, unsigned grid, const LsArgs<T>& a, hipStream_t st = nullptr, unsigned lds = 0) {
+    if (h->ls_rec) record_twin<T>(h, grid, a, lds);
+    else LsTwin<T>::single(a, grid, lds, st ? st : h->stream);
+}
+// A launch WITHOUT a twin that shares an if / else chain with recorded sites: while recording nothing is launched and the program
+// is marked cut, so that ls_record_program refuses the handle instead of keeping a program with a hole.
+template <class... P, class... Q> static void launch_untwinned(ipm_handle* h, void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t st, const Q&... args) {
+    if (h->ls_rec) h->ls_cut = true;
+    else hipLaunchKernelGGL(kernel, grid, block, 0, st ? st : h->stream, args...);
 }
 
 // the message goes to the thread's record and to `err` (char[512] of a handle or a batch, may be null); returns `code`

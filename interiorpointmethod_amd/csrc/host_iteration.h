@@ -1,47 +1,26 @@
 // host_iteration.h -- host side, unit 6: the launch sequence of one Mehrotra predictor-corrector iteration, the scalar read-back,
 // the roll-back / recovery after a poll time-out, and the loops built on them (ipm_newton_direction, ipm_iterate, ipm_solve).
 #pragma once
+// the tail the predictor (corr = 0) and the corrector (corr = 1) share: dy = B^{-1} t1, A^T dy, then the x and s parts of the direction
+static int enqueue_solve_direction(ipm_handle* h, hipEvent_t* ev, double* dy, int corr, hipEvent_t wait_last = nullptr) {
+    if (ev) HIP_TRY(h, hipEventRecord(ev[0], h->stream));
+    int rc = enqueue_potrs(h, h->t1, dy, wait_last);
+    if (rc) return rc;
+    if (ev) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
+    launch_gemv_t(h, dy);
+    launch_direction(h, corr);
+    HIP_TRY(h, hipGetLastError());
+    return IPM_OK;
+}
 static int enqueue_predictor(ipm_handle* h, hipEvent_t* ev, bool have_rhs = false, hipEvent_t wait_last = nullptr) {
-    VecArgs a = vec_args(h);
     if (!have_rhs) launch_gemv_n(h, h->v, -1.0, -1.0, h->rb, h->t1);   // rhs = -r_b - A (d*t)
-    if (ev) HIP_TRY(h, hipEventRecord(ev[0], h->stream));
-    int rc = enqueue_potrs(h, h->t1, h->dya, wait_last);
-    if (rc) return rc;
-    if (ev) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
-    launch_gemv_t(h, h->dya);
-    if (h->bnd) hipLaunchKernelGGL(direction_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, 0, bnd_args(h));
-    else if (!ls_push(h, LS_DIRECTION, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(direction_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, 0);
-    HIP_TRY(h, hipGetLastError());
-    return IPM_OK;
+    return enqueue_solve_direction(h, ev, h->dya, 0, wait_last);
 }
-
 static int enqueue_corrector(ipm_handle* h, hipEvent_t* ev) {
-    VecArgs a = vec_args(h);
-    if (h->bnd) {
-        hipLaunchKernelGGL(mu_aff_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, bnd_args(h));
-        hipLaunchKernelGGL(corrector_rhs_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, bnd_args(h));
-    } else {
-        if (!ls_push(h, LS_MU_AFF, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(mu_aff_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);
-        if (!ls_push(h, LS_CORR_RHS, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(corrector_rhs_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);
-    }
+    launch_mu_aff(h);
+    launch_corrector_rhs(h);
     launch_gemv_n(h, h->v, -1.0, -1.0, h->rb, h->t1);
-    if (ev) HIP_TRY(h, hipEventRecord(ev[0], h->stream));
-    int rc = enqueue_potrs(h, h->t1, h->dy);
-    if (rc) return rc;
-    if (ev) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
-    launch_gemv_t(h, h->dy);
-    if (h->bnd) hipLaunchKernelGGL(direction_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, 1, bnd_args(h));
-    else if (!ls_push(h, LS_DIRECTION, (unsigned)h->vblk, LsVecA{a, 1})) hipLaunchKernelGGL(direction_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, 1);
-    HIP_TRY(h, hipGetLastError());
-    return IPM_OK;
-}
-
-static int enqueue_update(ipm_handle* h) {
-    VecArgs a = vec_args(h);
-    if (h->bnd) hipLaunchKernelGGL(update_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, bnd_args(h));
-    else if (!ls_push(h, LS_UPDATE, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(update_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);
-    HIP_TRY(h, hipGetLastError());
-    return IPM_OK;
+    return enqueue_solve_direction(h, ev, h->dy, 1);
 }
 
 // events per profiled iteration: 0 start, 1 before form, 2 after form, 3 after factor,
@@ -54,9 +33,7 @@ static int enqueue_iteration(ipm_handle* h, hipEvent_t* ev) {
     if (overlap_residuals(h)) {
         // d = x/s -> formation -> factorization, with the residuals, the stop test and the predictor rhs on the residual
         // stream under the chain-bound tail of the factorization
-        VecArgs a = vec_args(h);
-        if (h->bnd) hipLaunchKernelGGL(scaling_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, bnd_args(h));
-        else hipLaunchKernelGGL(scaling_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);
+        launch_scaling(h);
         const bool fused = ff_use(h);                        // evaluated ONCE per iteration (the live-handle count can change under it)
         if (ev && !fused) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
         // the stop test of THIS iterate runs on the residual stream while the factorization is in flight: formation and
@@ -102,7 +79,8 @@ static int enqueue_iteration(ipm_handle* h, hipEvent_t* ev) {
             if ((rc = enqueue_predictor(h, nullptr, /*have_rhs=*/true))) return rc;
         }
         if ((rc = enqueue_corrector(h, nullptr))) return rc;
-        if ((rc = enqueue_update(h))) return rc;
+        launch_update(h);
+        HIP_TRY(h, hipGetLastError());
         return IPM_OK;
     }
     if (all) HIP_TRY(h, hipEventRecord(ev[0], h->stream));
@@ -129,7 +107,8 @@ static int enqueue_iteration(ipm_handle* h, hipEvent_t* ev) {
     if (all) HIP_TRY(h, hipEventRecord(ev[3], h->stream));
     if ((rc = enqueue_predictor(h, all ? ev + 4 : nullptr, have_rhs))) return rc;
     if ((rc = enqueue_corrector(h, all ? ev + 6 : nullptr))) return rc;
-    if ((rc = enqueue_update(h))) return rc;
+    launch_update(h);
+    HIP_TRY(h, hipGetLastError());
     if (all) HIP_TRY(h, hipEventRecord(ev[8], h->stream));
     return IPM_OK;
 }
@@ -232,9 +211,7 @@ extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, do
             if ((rc = enqueue_factor(h, true))) return rc;
             if ((rc = enqueue_group_inverses(h))) return rc;
             if ((rc = enqueue_predictor(h, nullptr))) return rc;
-            VecArgs a = vec_args(h);
-            if (h->bnd) hipLaunchKernelGGL(mu_aff_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a, bnd_args(h));
-            else hipLaunchKernelGGL(mu_aff_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, a);   // alpha_aff for stats
+            launch_mu_aff(h);                                   // alpha_aff for stats
             bool tmo = false;
             if ((rc = read_scalars(h, &tmo))) return rc;
             if (!tmo) break;

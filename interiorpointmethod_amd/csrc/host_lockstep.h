@@ -2,22 +2,18 @@
 // the merge into global steps, ipm_batch_* and ipm_solve_batch.
 #pragma once
 // ------------------------------------------------------------------------------- lockstep batch (lockstep.h)
+// the GEMM launchers' way into a recording: the type is the one whose declared tile shape (lockstep.h) is the launcher's instantiation
+template <LsType... T> static bool ls_record_gemm(ipm_handle* h, int bm, int bn, int bk, int wm, int wn, const GemmNT& g, unsigned grid) {
+    return ((LsTwin<T>::is(bm, bn, bk, wm, wn) && (record_twin<T>(h, grid, g), true)) || ...);
+}
 static void ls_gemm_hook(void* ctx, int bm, int bn, int bk, int wm, int wn, const GemmNT& g, int grid) {
     ipm_handle* h = (ipm_handle*)ctx;
-    int type = -1;
-    if (bm == -1) type = LS_CHOL_UPDATE;
-    else if (bm == 32 && bn == 128 && bk == 32 && wm == 1 && wn == 8) type = LS_GEMM_32_128_32;
-    else if (bm == 64 && bn == 64 && bk == 16) type = LS_GEMM_64_64_16;
-    else if (bm == 64 && bn == 128 && bk == 16) type = LS_GEMM_64_128_16;
-    else if (bm == 128 && bn == 128 && bk == 16 && wm == 2 && wn == 2) type = LS_GEMM_128_128_16;
-    else if (bm == 32 && bn == 32 && bk == 32) type = LS_GEMM_32_32_32;
-    if (g.batch > 1 || g.batch2 > 1) {                       // the group inverses' batched products: 3-D grid packed into the LP's block range
-        if (type != LS_GEMM_32_32_32) { h->ls_cut = true; return; }
-        ls_push(h, LS_GEMM_32_32_32_BATCHED, (unsigned)grid * (unsigned)g.batch * (unsigned)g.batch2, g);
-        return;
-    }
-    if (type < 0 || g.wait_on || g.signal) { h->ls_cut = true; return; }      // not recordable: ls_record_program reports it
-    ls_push(h, type, (unsigned)grid, g);
+    bool ok;
+    if (g.batch > 1 || g.batch2 > 1)                         // the group inverses' batched products: 3-D grid packed into the LP's block range
+        ok = ls_record_gemm<LS_GEMM_32_32_32_BATCHED>(h, bm, bn, bk, wm, wn, g, (unsigned)grid * (unsigned)g.batch * (unsigned)g.batch2);
+    else                                                     // (a device-polled hand-off has no twin)
+        ok = !g.wait_on && !g.signal && ls_record_gemm<LS_CHOL_UPDATE, LS_GEMM_32_128_32, LS_GEMM_64_64_16, LS_GEMM_64_128_16, LS_GEMM_128_128_16, LS_GEMM_32_32_32>(h, bm, bn, bk, wm, wn, g, (unsigned)grid);
+    if (!ok) h->ls_cut = true;                               // not recordable: ls_record_program reports it
 }
 static bool ls_eligible(const ipm_handle* h) {
     return h->lockstep && !h->bnd && h->sparse && !h->small && !h->spf && h->lookahead == 0 && h->stream2 == nullptr && h->B && h->invD &&
@@ -204,24 +200,21 @@ extern "C" int ipm_batch_step(ipm_batch* b, int32_t* finished, int32_t cap, int3
     }
     const auto t_mid = std::chrono::steady_clock::now();
     static const bool ls_prof = getenv("IPM_LS_PROF") != nullptr;      // diagnostic: a synchronisation after every launch, wall time per kernel type
-    if (ls_prof) {
-        static double tot[LS_NTYPES]; static long cnt[LS_NTYPES]; static long calls = 0;
-        for (int c = 0; c < b->chunk; ++c)
-            for (const LsStep& st : b->steps) {
-                const auto t0 = std::chrono::steady_clock::now();
-                B_TRY(b, ls_launch(st.type, b->d_recs + st.offset, st.count, st.blocks, st.lds, S));
-                B_TRY(b, hipStreamSynchronize(S));
-                tot[st.type] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); cnt[st.type]++;
-            }
-        if (++calls % 25 == 0) {
-            fprintf(stderr, "[lockstep prof] %zu active, %zu steps; us per launch (launches) by type:", b->active.size(), b->steps.size());
-            for (int t = 0; t < LS_NTYPES; ++t) if (cnt[t]) fprintf(stderr, " %d:%.1f(%ld)", t, 1e6 * tot[t] / cnt[t], cnt[t]);
-            fprintf(stderr, "\n");
-            for (int t = 0; t < LS_NTYPES; ++t) { tot[t] = 0; cnt[t] = 0; }
-        }
-    } else
+    static double tot[LS_NTYPES]; static long cnt[LS_NTYPES]; static long calls = 0;
     for (int c = 0; c < b->chunk; ++c)
-        for (const LsStep& st : b->steps) B_TRY(b, ls_launch(st.type, b->d_recs + st.offset, st.count, st.blocks, st.lds, S));
+        for (const LsStep& st : b->steps) {
+            const auto t0 = ls_prof ? std::chrono::steady_clock::now() : t_mid;
+            B_TRY(b, ls_launch(st.type, b->d_recs + st.offset, st.count, st.blocks, st.lds, S));
+            if (!ls_prof) continue;
+            B_TRY(b, hipStreamSynchronize(S));
+            tot[st.type] += secs(t0); cnt[st.type]++;
+        }
+    if (ls_prof && ++calls % 25 == 0) {
+        fprintf(stderr, "[lockstep prof] %zu active, %zu steps; us per launch (launches) by type:", b->active.size(), b->steps.size());
+        for (int t = 0; t < LS_NTYPES; ++t) if (cnt[t]) fprintf(stderr, " %d:%.1f(%ld)", t, 1e6 * tot[t] / cnt[t], cnt[t]);
+        fprintf(stderr, "\n");
+        for (int t = 0; t < LS_NTYPES; ++t) { tot[t] = 0; cnt[t] = 0; }
+    }
     for (int i : b->active) B_TRY(b, hipMemcpyAsync(b->hs[(size_t)i]->h_sc, b->hs[(size_t)i]->sc, sizeof(Scalars), hipMemcpyDeviceToHost, S));
     b->t_enqueue += secs(t_mid); b->n_launch += (long)b->chunk * (long)b->steps.size();
     const auto t_w = std::chrono::steady_clock::now();

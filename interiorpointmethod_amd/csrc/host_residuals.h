@@ -3,52 +3,50 @@
 #pragma once
 static void launch_gemv_n(ipm_handle* h, const double* v, double sa, double sb, const double* add, double* out,
                           hipStream_t st = nullptr) {
-    if (!st) st = h->stream;
-    if (h->sparse) {
-        const LsSpmv p{sparse_view(h), (int)h->mp, v, sa, sb, add, out, &h->sc->done};
-        if (ls_push(h, LS_SPMV_CSR, (unsigned)((h->mp + 15) / 16), p)) return;
-        hipLaunchKernelGGL(spmv_csr_kernel, dim3((unsigned)((h->mp + 15) / 16)), dim3(256), 0, st, sparse_view(h),
-                           (int)h->mp, v, sa, sb, add, out, &h->sc->done);
-        return;
-    }
-    hipLaunchKernelGGL(gemv_n_kernel, dim3((unsigned)(h->mp / 4)), dim3(256), 0, st, h->A, h->np, (int)h->mp,
-                       (int)h->np, v, sa, sb, add, out, &h->sc->done);
+    if (h->sparse) launch_twin<LS_SPMV_CSR>(h, (unsigned)((h->mp + 15) / 16), {sparse_view(h), (int)h->mp, v, sa, sb, add, out, &h->sc->done}, st);
+    else launch_untwinned(h, gemv_n_kernel, dim3((unsigned)(h->mp / 4)), dim3(256), st, h->A, h->np, (int)h->mp, (int)h->np, v, sa, sb, add, out, &h->sc->done);
 }
 static void launch_gemv_t(ipm_handle* h, const double* u, hipStream_t st = nullptr) {
-    if (!st) st = h->stream;
-    if (h->sparse) {
-        const LsSpmvT p{sparse_view(h), (int)h->np, u, h->atp, &h->sc->done};
-        if (ls_push(h, LS_SPMV_CSC_T, (unsigned)((h->np + 15) / 16), p)) return;
-        hipLaunchKernelGGL(spmv_csc_t_kernel, dim3((unsigned)((h->np + 15) / 16)), dim3(256), 0, st, sparse_view(h),
-                           (int)h->np, u, h->atp, &h->sc->done);
-        return;
-    }
-    dim3 grid((unsigned)((h->np + 511) / 512), (unsigned)h->rc_chunks);
-    hipLaunchKernelGGL(gemv_t_kernel, grid, dim3(256), 0, st, h->A, h->np, h->rows_per_chunk, (int)h->np, u,
-                       h->atp, &h->sc->done);
+    if (h->sparse) launch_twin<LS_SPMV_CSC_T>(h, (unsigned)((h->np + 15) / 16), {sparse_view(h), (int)h->np, u, h->atp, &h->sc->done}, st);
+    else launch_untwinned(h, gemv_t_kernel, dim3((unsigned)((h->np + 511) / 512), (unsigned)h->rc_chunks), dim3(256), st, h->A, h->np, h->rows_per_chunk, (int)h->np, u, h->atp, &h->sc->done);
 }
+
+// The vector steps of the iteration, ONE launch function each: it holds the step's fork between the plain kernel and the detect
+// kernel (both have lockstep twins) and the bounded kernels (none: a bounded handle is never recorded, ls_eligible).
+template <LsType T> static void launch_vec_step(ipm_handle* h, void (*bounded)(VecArgs, BndArgs), hipStream_t st = nullptr) {
+    if (h->bnd) launch_untwinned(h, bounded, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
+    else launch_twin<T>(h, (unsigned)h->vblk, {vec_args(h), 0}, st);
+}
+static void launch_prepare(ipm_handle* h, hipStream_t st) {
+    if (h->bnd && h->detect) launch_untwinned(h, prepare_bounded_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
+    else if (h->detect) launch_twin<LS_PREPARE_DETECT>(h, (unsigned)h->vblk, {vec_args(h), det_args(h)}, st);
+    else launch_vec_step<LS_PREPARE>(h, prepare_bounded_kernel, st);
+}
+static void launch_stop_test(ipm_handle* h, hipStream_t st) {
+    if (h->bnd && h->detect) launch_untwinned(h, stop_test_bounded_detect_kernel, dim3(1), dim3(64), st, vec_args(h), bnd_args(h), det_args(h));
+    else if (h->bnd) launch_untwinned(h, stop_test_bounded_kernel, dim3(1), dim3(64), st, vec_args(h), bnd_args(h));
+    else if (h->detect) launch_twin<LS_STOP_TEST_DETECT>(h, 1u, {vec_args(h), det_args(h)}, st);
+    else launch_twin<LS_STOP_TEST>(h, 1u, {vec_args(h), 0}, st);
+}
+static void launch_scaling(ipm_handle* h) {      // (residual-stream iteration only, which is never recorded: no twin, nothing to refuse)
+    if (h->bnd) hipLaunchKernelGGL(scaling_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), bnd_args(h));
+    else hipLaunchKernelGGL(scaling_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h));
+}
+static void launch_direction(ipm_handle* h, int corr) {
+    if (h->bnd) launch_untwinned(h, direction_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), corr, bnd_args(h));
+    else launch_twin<LS_DIRECTION>(h, (unsigned)h->vblk, {vec_args(h), corr});
+}
+static void launch_mu_aff(ipm_handle* h) { launch_vec_step<LS_MU_AFF>(h, mu_aff_bounded_kernel); }
+static void launch_corrector_rhs(ipm_handle* h) { launch_vec_step<LS_CORR_RHS>(h, corrector_rhs_bounded_kernel); }
+static void launch_update(ipm_handle* h) { launch_vec_step<LS_UPDATE>(h, update_bounded_kernel); }
 
 // r_b, r_c, d, predictor v, stop test (and, with IPM_FLAG_DETECT_INFEASIBILITY, the infeasibility tests): the one launch site of the
 // stop test of every multi-kernel path (dense, sparse envelope, sparse factor, fused formation + factorization, lockstep)
 static int enqueue_residuals(ipm_handle* h, hipStream_t st = nullptr) {
-    if (!st) st = h->stream;
-    VecArgs a = vec_args(h);
     launch_gemv_n(h, h->x, 1.0, -1.0, h->b, h->rb, st);             // r_b = A x - b
     launch_gemv_t(h, h->y, st);                                     // A^T y (partials)
-    if (h->bnd && h->detect) {
-        hipLaunchKernelGGL(prepare_bounded_detect_kernel, dim3(h->vblk), dim3(VBLK), 0, st, a, bnd_args(h));
-        hipLaunchKernelGGL(stop_test_bounded_detect_kernel, dim3(1), dim3(64), 0, st, a, bnd_args(h), det_args(h));
-    } else if (h->bnd) {                                            // (a bounded handle is never recorded: ls_eligible)
-        hipLaunchKernelGGL(prepare_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, st, a, bnd_args(h));
-        hipLaunchKernelGGL(stop_test_bounded_kernel, dim3(1), dim3(64), 0, st, a, bnd_args(h));
-    } else if (h->detect) {                                         // the infeasibility tests: their own lockstep twins
-        const LsVecDet p{a, det_args(h)};
-        if (!ls_push(h, LS_PREPARE_DETECT, (unsigned)h->vblk, p)) hipLaunchKernelGGL(prepare_detect_kernel, dim3(h->vblk), dim3(VBLK), 0, st, a);
-        if (!ls_push(h, LS_STOP_TEST_DETECT, 1u, p)) hipLaunchKernelGGL(stop_test_detect_kernel, dim3(1), dim3(64), 0, st, a, det_args(h));
-    } else {
-        if (!ls_push(h, LS_PREPARE, (unsigned)h->vblk, LsVecA{a, 0})) hipLaunchKernelGGL(prepare_kernel, dim3(h->vblk), dim3(VBLK), 0, st, a);
-        if (!ls_push(h, LS_STOP_TEST, 1u, LsVecA{a, 0})) hipLaunchKernelGGL(stop_test_kernel, dim3(1), dim3(64), 0, st, a);
-    }
+    launch_prepare(h, st);
+    launch_stop_test(h, st);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }

@@ -10,13 +10,15 @@
 // mix.  The launch count of a batch iteration is then that of its LONGEST program, not the sum.
 //
 // How.  Nothing about an LP's arithmetic changes: the handle's own launch sequence (enqueue_iteration, single-stream path) is
-// RECORDED once -- every launch site pushes (kernel type, grid, argument struct) instead of launching -- and the records of all
-// LPs are merged, each LP's order preserved, into global steps of one kernel type each (host_lockstep.h: ls_merge).  The device
+// RECORDED once -- every launch site is one launch_twin<T> call (host_handle.h; the types: LsTwin<T> below), which records (kernel
+// type, grid, argument struct) instead of launching -- and the records of all LPs are merged, each LP's order preserved, into global steps of one kernel type each (host_lockstep.h: ls_merge).  The device
 // code of a step is the body of the kernel the handle would have launched (X_kernel_body, shared with the one-LP kernels), so a
 // lockstep solve is BIT-IDENTICAL to the same handle solved alone (tests/test_gpu_lockstep.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
+#include <utility>
 
 #include "chol_update_f64.h"
 #include "gemm_nt_f64.h"
@@ -57,7 +59,6 @@ struct LsGemvT { const double* A; int64_t lda; int rows_per_chunk, np; const dou
 struct LsSubPart { double* z; const double* part; int np, rc; const int* done; };
 struct LsGroupDiagT { const double* invD; double* XT; double* X; int b0, GS; const int* done; };
 struct LsMaxdiag { const double* B; int64_t ld; int n; double* out; const int* done; };
-static_assert(sizeof(LsVecA) <= LS_ARG_BYTES && sizeof(GemmNT) <= LS_ARG_BYTES && sizeof(PotrfDiag) <= LS_ARG_BYTES && sizeof(LsAdatList) <= LS_ARG_BYTES && sizeof(LsVecDet) <= LS_ARG_BYTES, "LsRec::args");
 
 // block -> (LP, block of that LP's launch): the LPs' first blocks are ascending; every wave looks its own block up
 #define LS_ENTER(ARGT)                                                                                                  \
@@ -68,22 +69,58 @@ static_assert(sizeof(LsVecA) <= LS_ARG_BYTES && sizeof(GemmNT) <= LS_ARG_BYTES &
     const unsigned bx = blockIdx.x - r_.start;                                                                          \
     const ARGT& p = *reinterpret_cast<const ARGT*>(r_.args)
 
-__global__ __launch_bounds__(256) void ls_spmv_csr(const LsRec* recs, const unsigned count) { LS_ENTER(LsSpmv); spmv_csr_kernel_body(p.A, p.mp, p.v, p.sa, p.sb, p.add, p.out, p.done, bx, r_.gridx); }
-__global__ __launch_bounds__(256) void ls_spmv_csc_t(const LsRec* recs, const unsigned count) { LS_ENTER(LsSpmvT); spmv_csc_t_kernel_body(p.A, p.np, p.u, p.w, p.done, bx, r_.gridx); }
-__global__ __launch_bounds__(VBLK) void ls_prepare(const LsRec* recs, const unsigned count) { LS_ENTER(LsVecA); prepare_kernel_body(p.a, bx, r_.gridx); }
-__global__ __launch_bounds__(64) void ls_stop_test(const LsRec* recs, const unsigned count) { LS_ENTER(LsVecA); stop_test_kernel_body(p.a, bx, r_.gridx); }
-__global__ __launch_bounds__(VBLK) void ls_prepare_detect(const LsRec* recs, const unsigned count) { LS_ENTER(LsVecDet); prepare_kernel_body<false, true>(p.a, bx, r_.gridx); }
-__global__ __launch_bounds__(64) void ls_stop_test_detect(const LsRec* recs, const unsigned count) { LS_ENTER(LsVecDet); stop_test_kernel_body<false, true>(p.a, bx, r_.gridx, BndArgs{}, p.dt); }
-__global__ __launch_bounds__(256) void ls_zero(const LsRec* recs, const unsigned count) { LS_ENTER(LsZero); zero_unless_done_kernel_body(p.p, p.n, p.done, bx, r_.gridx); }
-__global__ __launch_bounds__(256) void ls_adat_list(const LsRec* recs, const unsigned count) {
-    LS_ENTER(LsAdatList);
+// ONE DECLARATION PER TYPE, next to its ls_* wrapper kernel: LsTwin<T> = the argument struct, the block dimension and `single`, the
+// launch of the single-LP kernel from that struct with the field list the wrapper passes to X_kernel_body.  launch_twin<T> (host
+// side) records the struct or calls `single`; ls_launch takes wrapper and block dimension from here.  The GEMM types state `is`
+// instead -- the launcher instantiation they record: launch_gemm_nt / launch_chol_update hand their struct to ls_gemm_hook.
+template <LsType T> struct LsTwin;
+template <LsType T> using LsArgs = typename LsTwin<T>::Args;
+template <class A, unsigned THREADS> struct LsTwinOf {
+    static_assert(sizeof(A) <= LS_ARG_BYTES && std::is_trivially_copyable<A>::value, "LsRec::args");
+    using Args = A;
+    static constexpr unsigned threads = THREADS;
+    static dim3 block() { return dim3(THREADS); }
+};
+// `single` of a type whose single-LP kernel has the 1-D grid of the record
+#define LS_SINGLE(KERNEL, ...)                                                                                          \
+    static void single(const Args& p, unsigned grid, unsigned lds, hipStream_t st) { hipLaunchKernelGGL(KERNEL, dim3(grid), block(), lds, st, __VA_ARGS__); }
+// head of the wrapper kernel of type T (optional: the second argument of __launch_bounds__), bound to the type for ls_launch
+using LsKernel = void (*)(const LsRec*, unsigned);
+template <LsType T> inline constexpr LsKernel ls_kernel = nullptr;
+#define LS_KERNEL(T, NAME, ...)                                                                                         \
+    __global__ __launch_bounds__(LsTwin<T>::threads, ##__VA_ARGS__) void NAME(const LsRec* recs, const unsigned count); \
+    template <> inline constexpr LsKernel ls_kernel<T> = NAME;                                                          \
+    __global__ __launch_bounds__(LsTwin<T>::threads, ##__VA_ARGS__) void NAME(const LsRec* recs, const unsigned count)
+
+template <> struct LsTwin<LS_SPMV_CSR> : LsTwinOf<LsSpmv, 256> { LS_SINGLE(spmv_csr_kernel, p.A, p.mp, p.v, p.sa, p.sb, p.add, p.out, p.done) };
+LS_KERNEL(LS_SPMV_CSR, ls_spmv_csr) { LS_ENTER(LsArgs<LS_SPMV_CSR>); spmv_csr_kernel_body(p.A, p.mp, p.v, p.sa, p.sb, p.add, p.out, p.done, bx, r_.gridx); }
+template <> struct LsTwin<LS_SPMV_CSC_T> : LsTwinOf<LsSpmvT, 256> { LS_SINGLE(spmv_csc_t_kernel, p.A, p.np, p.u, p.w, p.done) };
+LS_KERNEL(LS_SPMV_CSC_T, ls_spmv_csc_t) { LS_ENTER(LsArgs<LS_SPMV_CSC_T>); spmv_csc_t_kernel_body(p.A, p.np, p.u, p.w, p.done, bx, r_.gridx); }
+template <> struct LsTwin<LS_PREPARE> : LsTwinOf<LsVecA, VBLK> { LS_SINGLE(prepare_kernel, p.a) };
+LS_KERNEL(LS_PREPARE, ls_prepare) { LS_ENTER(LsArgs<LS_PREPARE>); prepare_kernel_body(p.a, bx, r_.gridx); }
+template <> struct LsTwin<LS_STOP_TEST> : LsTwinOf<LsVecA, 64> { LS_SINGLE(stop_test_kernel, p.a) };
+LS_KERNEL(LS_STOP_TEST, ls_stop_test) { LS_ENTER(LsArgs<LS_STOP_TEST>); stop_test_kernel_body(p.a, bx, r_.gridx); }
+template <> struct LsTwin<LS_PREPARE_DETECT> : LsTwinOf<LsVecDet, VBLK> { LS_SINGLE(prepare_detect_kernel, p.a) };
+LS_KERNEL(LS_PREPARE_DETECT, ls_prepare_detect) { LS_ENTER(LsArgs<LS_PREPARE_DETECT>); prepare_kernel_body<false, true>(p.a, bx, r_.gridx); }
+template <> struct LsTwin<LS_STOP_TEST_DETECT> : LsTwinOf<LsVecDet, 64> { LS_SINGLE(stop_test_detect_kernel, p.a, p.dt) };
+LS_KERNEL(LS_STOP_TEST_DETECT, ls_stop_test_detect) { LS_ENTER(LsArgs<LS_STOP_TEST_DETECT>); stop_test_kernel_body<false, true>(p.a, bx, r_.gridx, BndArgs{}, p.dt); }
+template <> struct LsTwin<LS_ZERO> : LsTwinOf<LsZero, 256> { LS_SINGLE(zero_unless_done_kernel, p.p, p.n, p.done) };
+LS_KERNEL(LS_ZERO, ls_zero) { LS_ENTER(LsArgs<LS_ZERO>); zero_unless_done_kernel_body(p.p, p.n, p.done, bx, r_.gridx); }
+template <> struct LsTwin<LS_ADAT_LIST> : LsTwinOf<LsAdatList, 256> { LS_SINGLE(adat_list_kernel, p.bptr, p.bi, p.bk, p.bcol, p.bai, p.bak, p.nb, p.d, p.B, p.ldb, p.m, p.mp, p.done) };
+LS_KERNEL(LS_ADAT_LIST, ls_adat_list) {
+    LS_ENTER(LsArgs<LS_ADAT_LIST>);
     adat_list_kernel_body(p.bptr, p.bi, p.bk, p.bcol, p.bai, p.bak, p.nb, p.d, p.B, p.ldb, p.m, p.mp, p.done, bx, r_.gridx);
 }
-__global__ __launch_bounds__(256) void ls_adat_sparse(const LsRec* recs, const unsigned count) { LS_ENTER(LsAdatSp); adat_sparse_kernel_body(p.A, p.d, p.B, p.ldb, p.mp, p.done, bx, r_.gridx); }
-__global__ __launch_bounds__(256) void ls_adat_sparse_global(const LsRec* recs, const unsigned count) { LS_ENTER(LsAdatSp); adat_sparse_global_kernel_body(p.A, p.d, p.B, p.ldb, p.mp, p.done, bx, r_.gridx); }
-__global__ __launch_bounds__(256) void ls_maxdiag(const LsRec* recs, const unsigned count) { LS_ENTER(LsMaxdiag); maxdiag_kernel_body(p.B, p.ld, p.n, p.out, p.done, bx, r_.gridx); }
-__global__ __launch_bounds__(PD_THREADS) void ls_potrf(const LsRec* recs, const unsigned count) {
-    LS_ENTER(PotrfDiag);
+// (the one type with dynamic LDS: `lds` of the launch site, the largest among the LPs of a step in ls_launch)
+template <> struct LsTwin<LS_ADAT_SPARSE> : LsTwinOf<LsAdatSp, 256> { LS_SINGLE(adat_sparse_kernel, p.A, p.d, p.B, p.ldb, p.mp, p.done) };
+LS_KERNEL(LS_ADAT_SPARSE, ls_adat_sparse) { LS_ENTER(LsArgs<LS_ADAT_SPARSE>); adat_sparse_kernel_body(p.A, p.d, p.B, p.ldb, p.mp, p.done, bx, r_.gridx); }
+template <> struct LsTwin<LS_ADAT_SPARSE_GLOBAL> : LsTwinOf<LsAdatSp, 256> { LS_SINGLE(adat_sparse_global_kernel, p.A, p.d, p.B, p.ldb, p.mp, p.done) };
+LS_KERNEL(LS_ADAT_SPARSE_GLOBAL, ls_adat_sparse_global) { LS_ENTER(LsArgs<LS_ADAT_SPARSE_GLOBAL>); adat_sparse_global_kernel_body(p.A, p.d, p.B, p.ldb, p.mp, p.done, bx, r_.gridx); }
+template <> struct LsTwin<LS_MAXDIAG> : LsTwinOf<LsMaxdiag, 256> { LS_SINGLE(maxdiag_kernel, p.B, p.ld, p.n, p.out, p.done) };
+LS_KERNEL(LS_MAXDIAG, ls_maxdiag) { LS_ENTER(LsArgs<LS_MAXDIAG>); maxdiag_kernel_body(p.B, p.ld, p.n, p.out, p.done, bx, r_.gridx); }
+template <> struct LsTwin<LS_POTRF> : LsTwinOf<PotrfDiag, PD_THREADS> { LS_SINGLE(potrf_diag_kernel<false>, p) };
+LS_KERNEL(LS_POTRF, ls_potrf) {
+    LS_ENTER(LsArgs<LS_POTRF>);
     if (p.done && *p.done) return;                           // (no signal word on this path: a lockstep handle never polls)
     __shared__ __attribute__((aligned(16))) double W[NB * WLD];
     __shared__ double dinv_s[NB];
@@ -96,24 +133,56 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 2 < 2 ? 1 : 2) void ls_ge
     __shared__ __attribute__((aligned(16))) double lds[2 * (BM + BN) * (BK + 2)];
     gemm_nt_body<BM, BN, BK, WM, WN, false>(p, (int)bx, 0, 0, lds);
 }
-__global__ __launch_bounds__(256, 2) void ls_chol_update(const LsRec* recs, const unsigned count) { LS_ENTER(GemmNT); chol_update_kernel_body(p, bx, r_.gridx); }
-__global__ __launch_bounds__(256) void ls_trsv_fwd(const LsRec* recs, const unsigned count) { LS_ENTER(TrsvStep); trsv_fwd_step_kernel_body(p, bx, r_.gridx); }
-__global__ __launch_bounds__(256) void ls_trsv_bwd(const LsRec* recs, const unsigned count) { LS_ENTER(TrsvStep); trsv_bwd_step_kernel_body(p, bx, r_.gridx); }
-__global__ __launch_bounds__(VBLK) void ls_direction(const LsRec* recs, const unsigned count) { LS_ENTER(LsVecA); direction_kernel_body(p.a, p.corr, bx, r_.gridx); }
-__global__ __launch_bounds__(VBLK) void ls_mu_aff(const LsRec* recs, const unsigned count) { LS_ENTER(LsVecA); mu_aff_kernel_body(p.a, bx, r_.gridx); }
-__global__ __launch_bounds__(VBLK) void ls_corr_rhs(const LsRec* recs, const unsigned count) { LS_ENTER(LsVecA); corrector_rhs_kernel_body(p.a, bx, r_.gridx); }
-__global__ __launch_bounds__(VBLK) void ls_update(const LsRec* recs, const unsigned count) { LS_ENTER(LsVecA); update_kernel_body(p.a, bx, r_.gridx); }
+template <int BM_, int BN_, int BK_, int WM_, int WN_> struct LsGemmTwin : LsTwinOf<GemmNT, 64 * WM_ * WN_> {
+    static constexpr bool is(int bm, int bn, int bk, int wm, int wn) { return bm == BM_ && bn == BN_ && bk == BK_ && wm == WM_ && wn == WN_; }   // the instantiation of launch_gemm_nt this type records
+};
+#define LS_GEMM_TWIN(T, ...)                                                                                            \
+    template <> struct LsTwin<T> : LsGemmTwin<__VA_ARGS__> {};                                                          \
+    template <> inline constexpr LsKernel ls_kernel<T> = ls_gemm<__VA_ARGS__>;
+LS_GEMM_TWIN(LS_GEMM_32_128_32, 32, 128, 32, 1, 8)
+LS_GEMM_TWIN(LS_GEMM_64_64_16, 64, 64, 16, 2, 2)
+LS_GEMM_TWIN(LS_GEMM_64_128_16, 64, 128, 16, 2, 2)
+LS_GEMM_TWIN(LS_GEMM_128_128_16, 128, 128, 16, 2, 2)
+LS_GEMM_TWIN(LS_GEMM_32_32_32, 32, 32, 32, 2, 2)
+template <> struct LsTwin<LS_CHOL_UPDATE> : LsTwinOf<GemmNT, 256> { static constexpr bool is(int bm, int, int, int, int) { return bm == -1; } };      // (what launch_chol_update hands to the hook)
+LS_KERNEL(LS_CHOL_UPDATE, ls_chol_update, 2) { LS_ENTER(LsArgs<LS_CHOL_UPDATE>); chol_update_kernel_body(p, bx, r_.gridx); }
+template <> struct LsTwin<LS_TRSV_FWD> : LsTwinOf<TrsvStep, 256> { LS_SINGLE(trsv_fwd_step_kernel, p) };
+LS_KERNEL(LS_TRSV_FWD, ls_trsv_fwd) { LS_ENTER(LsArgs<LS_TRSV_FWD>); trsv_fwd_step_kernel_body(p, bx, r_.gridx); }
+template <> struct LsTwin<LS_TRSV_BWD> : LsTwinOf<TrsvStep, 256> { LS_SINGLE(trsv_bwd_step_kernel, p) };
+LS_KERNEL(LS_TRSV_BWD, ls_trsv_bwd) { LS_ENTER(LsArgs<LS_TRSV_BWD>); trsv_bwd_step_kernel_body(p, bx, r_.gridx); }
+template <> struct LsTwin<LS_DIRECTION> : LsTwinOf<LsVecA, VBLK> { LS_SINGLE(direction_kernel, p.a, p.corr) };
+LS_KERNEL(LS_DIRECTION, ls_direction) { LS_ENTER(LsArgs<LS_DIRECTION>); direction_kernel_body(p.a, p.corr, bx, r_.gridx); }
+template <> struct LsTwin<LS_MU_AFF> : LsTwinOf<LsVecA, VBLK> { LS_SINGLE(mu_aff_kernel, p.a) };
+LS_KERNEL(LS_MU_AFF, ls_mu_aff) { LS_ENTER(LsArgs<LS_MU_AFF>); mu_aff_kernel_body(p.a, bx, r_.gridx); }
+template <> struct LsTwin<LS_CORR_RHS> : LsTwinOf<LsVecA, VBLK> { LS_SINGLE(corrector_rhs_kernel, p.a) };
+LS_KERNEL(LS_CORR_RHS, ls_corr_rhs) { LS_ENTER(LsArgs<LS_CORR_RHS>); corrector_rhs_kernel_body(p.a, bx, r_.gridx); }
+template <> struct LsTwin<LS_UPDATE> : LsTwinOf<LsVecA, VBLK> { LS_SINGLE(update_kernel, p.a) };
+LS_KERNEL(LS_UPDATE, ls_update) { LS_ENTER(LsArgs<LS_UPDATE>); update_kernel_body(p.a, bx, r_.gridx); }
 
-__global__ __launch_bounds__(256) void ls_gemv_n(const LsRec* recs, const unsigned count) { LS_ENTER(LsGemvN); gemv_n_kernel_body(p.A, p.lda, p.mp, p.np, p.v, p.sa, p.sb, p.add, p.out, p.done, bx, r_.gridx); }
-__global__ __launch_bounds__(256) void ls_gemv_t(const LsRec* recs, const unsigned count) { LS_ENTER(LsGemvT); gemv_t_kernel_body(p.A, p.lda, p.rows_per_chunk, p.np, p.u, p.part, p.done, bx % p.gx, bx / p.gx); }
-__global__ __launch_bounds__(256) void ls_sub_partials(const LsRec* recs, const unsigned count) { LS_ENTER(LsSubPart); sub_partials_kernel_body(p.z, p.part, p.np, p.rc, p.done, bx, r_.gridx); }
-__global__ __launch_bounds__(256) void ls_group_diag_t(const LsRec* recs, const unsigned count) {      // block (32, 8); grid (4, 4, blocks) packed
-    LS_ENTER(LsGroupDiagT);
+template <> struct LsTwin<LS_GEMV_N> : LsTwinOf<LsGemvN, 256> { LS_SINGLE(gemv_n_kernel, p.A, p.lda, p.mp, p.np, p.v, p.sa, p.sb, p.add, p.out, p.done) };
+LS_KERNEL(LS_GEMV_N, ls_gemv_n) { LS_ENTER(LsArgs<LS_GEMV_N>); gemv_n_kernel_body(p.A, p.lda, p.mp, p.np, p.v, p.sa, p.sb, p.add, p.out, p.done, bx, r_.gridx); }
+template <> struct LsTwin<LS_GEMV_T> : LsTwinOf<LsGemvT, 256> {      // single-LP grid (gx, row chunks), packed as gx * chunks
+    static void single(const Args& p, unsigned grid, unsigned, hipStream_t st) {
+        hipLaunchKernelGGL(gemv_t_kernel, dim3(p.gx, grid / p.gx), block(), 0, st, p.A, p.lda, p.rows_per_chunk, p.np, p.u, p.part, p.done);
+    }
+};
+LS_KERNEL(LS_GEMV_T, ls_gemv_t) { LS_ENTER(LsArgs<LS_GEMV_T>); gemv_t_kernel_body(p.A, p.lda, p.rows_per_chunk, p.np, p.u, p.part, p.done, bx % p.gx, bx / p.gx); }
+template <> struct LsTwin<LS_SUB_PARTIALS> : LsTwinOf<LsSubPart, 256> { LS_SINGLE(sub_partials_kernel, p.z, p.part, p.np, p.rc, p.done) };
+LS_KERNEL(LS_SUB_PARTIALS, ls_sub_partials) { LS_ENTER(LsArgs<LS_SUB_PARTIALS>); sub_partials_kernel_body(p.z, p.part, p.np, p.rc, p.done, bx, r_.gridx); }
+template <> struct LsTwin<LS_GROUP_DIAG_T> : LsTwinOf<LsGroupDiagT, 32 * 8> {      // block (32, 8); single-LP grid (4, 4, blocks), packed as 16 * blocks
+    static dim3 block() { return dim3(32, 8); }
+    static void single(const Args& p, unsigned grid, unsigned, hipStream_t st) {
+        hipLaunchKernelGGL(group_diag_transpose_kernel, dim3(4, 4, grid / 16), block(), 0, st, p.invD, p.XT, p.X, p.b0, p.GS, p.done);
+    }
+};
+LS_KERNEL(LS_GROUP_DIAG_T, ls_group_diag_t) {
+    LS_ENTER(LsArgs<LS_GROUP_DIAG_T>);
     group_diag_transpose_kernel_body(p.invD, p.XT, p.X, p.b0, p.GS, p.done, bx & 3u, (bx >> 2) & 3u, bx >> 4);
 }
 // the batched form of the NT contraction (group inverses: blockIdx.y = pair, blockIdx.z = group), its 3-D grid packed
-__global__ __launch_bounds__(256, 2) void ls_gemm_32_batched(const LsRec* recs, const unsigned count) {
-    LS_ENTER(GemmNT);
+template <> struct LsTwin<LS_GEMM_32_32_32_BATCHED> : LsGemmTwin<32, 32, 32, 2, 2> {};
+LS_KERNEL(LS_GEMM_32_32_32_BATCHED, ls_gemm_32_batched, 2) {
+    LS_ENTER(LsArgs<LS_GEMM_32_32_32_BATCHED>);
     if (p.done && *p.done) return;
     __shared__ __attribute__((aligned(16))) double lds[2 * (32 + 32) * (32 + 2)];
     const unsigned gx = (unsigned)p.n_direct;
@@ -121,41 +190,14 @@ __global__ __launch_bounds__(256, 2) void ls_gemm_32_batched(const LsRec* recs, 
 }
 
 // launch one global step: `count` (<= LS_MAX_GROUP) LPs, `blocks` = the sum of their grids, `lds` = the largest dynamic LDS among them
-inline hipError_t ls_launch(int type, const LsRec* d_recs, unsigned count, unsigned blocks, unsigned lds, hipStream_t st) {
-    const dim3 g(blocks);
-    switch (type) {
-        case LS_SPMV_CSR: hipLaunchKernelGGL(ls_spmv_csr, g, dim3(256), 0, st, d_recs, count); break;
-        case LS_SPMV_CSC_T: hipLaunchKernelGGL(ls_spmv_csc_t, g, dim3(256), 0, st, d_recs, count); break;
-        case LS_PREPARE: hipLaunchKernelGGL(ls_prepare, g, dim3(VBLK), 0, st, d_recs, count); break;
-        case LS_STOP_TEST: hipLaunchKernelGGL(ls_stop_test, g, dim3(64), 0, st, d_recs, count); break;
-        case LS_PREPARE_DETECT: hipLaunchKernelGGL(ls_prepare_detect, g, dim3(VBLK), 0, st, d_recs, count); break;
-        case LS_STOP_TEST_DETECT: hipLaunchKernelGGL(ls_stop_test_detect, g, dim3(64), 0, st, d_recs, count); break;
-        case LS_ZERO: hipLaunchKernelGGL(ls_zero, g, dim3(256), 0, st, d_recs, count); break;
-        case LS_ADAT_LIST: hipLaunchKernelGGL(ls_adat_list, g, dim3(256), 0, st, d_recs, count); break;
-        case LS_ADAT_SPARSE: hipLaunchKernelGGL(ls_adat_sparse, g, dim3(256), lds, st, d_recs, count); break;
-        case LS_ADAT_SPARSE_GLOBAL: hipLaunchKernelGGL(ls_adat_sparse_global, g, dim3(256), 0, st, d_recs, count); break;
-        case LS_MAXDIAG: hipLaunchKernelGGL(ls_maxdiag, g, dim3(256), 0, st, d_recs, count); break;
-        case LS_POTRF: hipLaunchKernelGGL(ls_potrf, g, dim3(PD_THREADS), 0, st, d_recs, count); break;
-        case LS_GEMM_32_128_32: hipLaunchKernelGGL((ls_gemm<32, 128, 32, 1, 8>), g, dim3(512), 0, st, d_recs, count); break;
-        case LS_GEMM_64_64_16: hipLaunchKernelGGL((ls_gemm<64, 64, 16, 2, 2>), g, dim3(256), 0, st, d_recs, count); break;
-        case LS_GEMM_64_128_16: hipLaunchKernelGGL((ls_gemm<64, 128, 16, 2, 2>), g, dim3(256), 0, st, d_recs, count); break;
-        case LS_GEMM_128_128_16: hipLaunchKernelGGL((ls_gemm<128, 128, 16, 2, 2>), g, dim3(256), 0, st, d_recs, count); break;
-        case LS_GEMM_32_32_32: hipLaunchKernelGGL((ls_gemm<32, 32, 32, 2, 2>), g, dim3(256), 0, st, d_recs, count); break;
-        case LS_CHOL_UPDATE: hipLaunchKernelGGL(ls_chol_update, g, dim3(256), 0, st, d_recs, count); break;
-        case LS_TRSV_FWD: hipLaunchKernelGGL(ls_trsv_fwd, g, dim3(256), 0, st, d_recs, count); break;
-        case LS_TRSV_BWD: hipLaunchKernelGGL(ls_trsv_bwd, g, dim3(256), 0, st, d_recs, count); break;
-        case LS_DIRECTION: hipLaunchKernelGGL(ls_direction, g, dim3(VBLK), 0, st, d_recs, count); break;
-        case LS_MU_AFF: hipLaunchKernelGGL(ls_mu_aff, g, dim3(VBLK), 0, st, d_recs, count); break;
-        case LS_CORR_RHS: hipLaunchKernelGGL(ls_corr_rhs, g, dim3(VBLK), 0, st, d_recs, count); break;
-        case LS_UPDATE: hipLaunchKernelGGL(ls_update, g, dim3(VBLK), 0, st, d_recs, count); break;
-        case LS_GEMV_N: hipLaunchKernelGGL(ls_gemv_n, g, dim3(256), 0, st, d_recs, count); break;
-        case LS_GEMV_T: hipLaunchKernelGGL(ls_gemv_t, g, dim3(256), 0, st, d_recs, count); break;
-        case LS_SUB_PARTIALS: hipLaunchKernelGGL(ls_sub_partials, g, dim3(256), 0, st, d_recs, count); break;
-        case LS_GROUP_DIAG_T: hipLaunchKernelGGL(ls_group_diag_t, g, dim3(32, 8), 0, st, d_recs, count); break;
-        case LS_GEMM_32_32_32_BATCHED: hipLaunchKernelGGL(ls_gemm_32_batched, g, dim3(256), 0, st, d_recs, count); break;
-        default: return hipErrorInvalidValue;
-    }
+template <int... T> inline hipError_t ls_launch_in(std::integer_sequence<int, T...>, int type, const LsRec* d_recs, unsigned count, unsigned blocks, unsigned lds, hipStream_t st) {
+    static const struct { LsKernel kernel; dim3 block; } step[] = {{ls_kernel<(LsType)T>, LsTwin<(LsType)T>::block()}...};
+    if (type < 0 || type >= LS_NTYPES) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(step[type].kernel, dim3(blocks), step[type].block, lds, st, d_recs, count);
     return hipGetLastError();
+}
+inline hipError_t ls_launch(int type, const LsRec* d_recs, unsigned count, unsigned blocks, unsigned lds, hipStream_t st) {
+    return ls_launch_in(std::make_integer_sequence<int, LS_NTYPES>{}, type, d_recs, count, blocks, lds, st);
 }
 
 }  // namespace ipm

@@ -75,7 +75,7 @@ def test_lockstep_batch_restarts_a_rank_deficient_lp_with_the_automatic_shift():
             sv.close()
 
 
-def test_lockstep_rejects_handles_it_cannot_serve():
+def test_lockstep_rejects_handles_it_cannot_serve(monkeypatch):
     A, b, c = _load("AFIRO")                                   # 27 rows: the fused single-workgroup kernel serves it
     with ipm.IpmSolver(A, b, c, lockstep=True) as sv:
         sv.init_state(1.0)
@@ -87,6 +87,17 @@ def test_lockstep_rejects_handles_it_cannot_serve():
         sv.init_state(1.0)
         with pytest.raises(ipm.IpmError):
             ipm.solve_lockstep([sv])
+    # an eligible handle whose iteration holds a launch without a lockstep twin (the stamping potrf of block 0, IPM_POTRF_STAMPS=1
+    # at creation): refused when its program is recorded -- nothing may be launched then, and no program kept that lacks the launch
+    monkeypatch.setenv("IPM_POTRF_STAMPS", "1")
+    with ipm.IpmSolver(A, b, c, lockstep=True, factor="dense") as sv:
+        monkeypatch.delenv("IPM_POTRF_STAMPS")
+        sv.init_state(1.0)
+        assert ipm.lockstep_eligible(sv)
+        with pytest.raises(ipm.IpmError) as ei:
+            ipm.solve_lockstep([sv])
+        assert ei.value.code == -5                             # IPM_ERR_STATE
+        assert "without a lockstep twin" in str(ei.value)
 
 
 def test_lockstep_batch_lets_an_lp_join_between_two_steps():
