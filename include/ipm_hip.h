@@ -248,6 +248,23 @@ const char* ipm_batch_last_error(const ipm_batch* b);
 int ipm_batch_add(ipm_batch* b, ipm_handle* h, double tol_p, double tol_d, double tol_gap, int32_t max_iter, int32_t* index);
 int ipm_batch_step(ipm_batch* b, int32_t* finished, int32_t cap, int32_t* n_finished, int32_t* n_active);
 int ipm_batch_stats(ipm_batch* b, int32_t index, ipm_stats* stats);
+/* The SMALL-LP BATCH: ipm_solve for n handles of the fused single-workgroup path (sparse A of at most 128 rows, csrc/small_lp.h) in
+ * ONE launch per kernel variant, one workgroup per LP -- a few hundred or thousand small LPs (scenario sweeps, parametric right-hand
+ * sides, the AFIRO class of Netlib) fill the GPU's compute units where a loop of ipm_solve keeps one of them busy.  Every handle must be
+ * served by that path (ipm_get_schedule out[9] == 1), live on the same device, have A, b, c and a state set and profiling off
+ * (IPM_ERR_STATE otherwise); handles with upper bounds (ipm_set_bounds), with IPM_FLAG_DETECT_INFEASIBILITY and plain ones may be mixed
+ * freely in one call.  IPM_ERR_INVALID_ARG, with the offending index in ipm_last_error(NULL), for a NULL handle, a handle that is not on
+ * the small path, a handle on another device and the same handle twice (two workgroups would race on one state); n < 0 or handles ==
+ * NULL with n > 0 likewise; n == 0 returns IPM_OK and touches no device.  stream: a hipStream_t ON THE HANDLES' DEVICE the launches go to
+ * (the caller's to guarantee: a stream does not tell its device), NULL = the first handle's stream; the handles may own any streams -- the batch stream waits (stream events) for each distinct one before the launch,
+ * and the call returns with everything complete.  Same arguments and per-handle semantics as ipm_solve: stop test first, iteration
+ * cap, and the automatic Tikhonov shift -- the handles whose first factorization asks for it (and only they) are launched a second
+ * time with it, so a call is at most two rounds, each with one host synchronisation however large n is.  Afterwards ipm_get_state,
+ * ipm_get_bound_state, ipm_get_history and ipm_get_certificate work on each handle as after ipm_solve.  stats (may be NULL): n records,
+ * stats[i] describes handle i, with solve_ms the device time of the whole batch (as ipm_solve_batch).  The workgroups never
+ * communicate and an LP's arithmetic is that of ipm_solve on it alone: bit-identical iterates, whatever the order of the handles. */
+int ipm_solve_small_batch(ipm_handle** handles, int32_t n, double tol_p, double tol_d, double tol_gap, int32_t max_iter, void* stream,
+                          ipm_stats* stats);
 /* Tolerances of the infeasibility tests (IPM_FLAG_DETECT_INFEASIBILITY), each in (0, 1); default 1e-8 / 1e-8.  Takes effect
  * with the next solve (for the lockstep batch: with the next ipm_batch_add). */
 int ipm_set_infeasibility_tol(ipm_handle* h, double eps_p, double eps_d);

@@ -198,7 +198,7 @@ def _lockstep_streams(device, n):
 
 
 def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, tol_gap=None,
-                         detect_infeasibility=False, **_):
+                         detect_infeasibility=False, small_batch=False, **_):
     """Solve problems[i] for i in ids on this rank's GPU with the LOCKSTEP BATCH -> (len(ids), NF) records.
 
     `workers` host threads prepare the LPs (host analysis, handle, upload), largest first.  An LP of more than 128 rows on the
@@ -208,14 +208,42 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
     128 rows (fused single-workgroup kernel), the sparse multifrontal factor above LOCKSTEP_DENSE_ROWS rows -- are solved one after
     the other on LOCKSTEP_CLASSIC_THREADS streams, and by the class threads once their batch has finished.  Finished LPs are read
     back and destroyed by the pool while the batches run on.  Per-LP results are those of a one-at-a-time solve of the same
-    handle, bit for bit (tests/test_gpu_lockstep.py)."""
+    handle, bit for bit (tests/test_gpu_lockstep.py).
+
+    small_batch=True (opt-in): the LPs of up to 128 rows that the fused single-workgroup kernel serves are not solved one after the
+    other but collected, and ONE ipm_solve_small_batch call solves them, one workgroup per LP, once every LP of the shard is set up
+    (solver.solve_small_batch_solvers).  Same records, bit for bit (tests/test_gpu_small_batch.py)."""
     import queue
     from concurrent.futures import ThreadPoolExecutor
     from . import _lib
-    from .solver import IpmSolver, LockstepBatch, _info, lockstep_eligible, prepare
+    from .solver import IpmSolver, LockstepBatch, _info, lockstep_eligible, prepare, small_batch_eligible, solve_small_batch_solvers
     rec = np.zeros((len(ids), NF), dtype=np.float64)
     import threading
     classic_q = queue.Queue()
+    small_ready, small_lock = [], threading.Lock()      # small_batch: (row, lp id, solver, setup seconds) of the LPs that wait for the one call
+    # the rank's streams, the same ones in every call: one per size class, then the one-at-a-time runners'
+    ncls, nclassic = len(LOCKSTEP_CLASSES) + 1, max(1, LOCKSTEP_CLASSIC_THREADS)
+    streams = _lockstep_streams(device, ncls + nclassic)
+    # The small batch SHARES the first one-at-a-time runner's stream on purpose: a further stream would be the fifth beside the batches
+    # and the runner, one more than the four hardware queues (see LOCKSTEP_CLASSIC_THREADS).  Its handles' uploads interleave with that
+    # runner's LPs; the one call comes after every set-up has finished and returns complete.
+    small_stream = streams[ncls] if small_batch else None
+
+    def small_setup(problem, device=0, row=None, i=None, prepared=None, t0=None):
+        # the handle classic() would create for this LP; False: the library does not put it on the small path
+        A, b, c = problem
+        sv = IpmSolver(A, b, c, device=device, regularize=regularize, concurrent=True, prepared=prepared, detect_infeasibility=detect_infeasibility)
+        try:
+            if not small_batch_eligible(sv):
+                sv.close()
+                return False
+            sv.init_state(y0)
+        except Exception:
+            sv.close()
+            raise
+        with small_lock:
+            small_ready.append((row, i, sv, time.perf_counter() - t0))
+        return True
 
     def classic(problem, device=0, prepared=None):
         from .solver import solve_with_info
@@ -246,6 +274,9 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
                     return
                 sv.close()
                 sv = None
+            if small_batch and A.shape[0] <= 128 and \
+                    _in_own_stream(small_setup, problems[i], device, dict(row=row, i=i, prepared=prepared, t0=t0), stream=small_stream):
+                return
             classic_q.put((row, i, prepared, t0))         # solved by a classic runner thread (few streams: see LOCKSTEP_CLASSIC_THREADS)
             return
         except Exception as e:          # every failure becomes a record: the rank must still reach the all-gather
@@ -299,7 +330,6 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
             if m <= lim:
                 return k
         return len(LOCKSTEP_CLASSES)
-    ncls = len(LOCKSTEP_CLASSES) + 1
     ready = [queue.Queue() for _ in range(ncls)]
 
     def one_cls(row_i):
@@ -356,8 +386,6 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
         if expected[k] and __import__("os").environ.get("IPM_LOCKSTEP_STEAL", "1") != "0":
             classic_runner(streams[k])  # its batch is finished, its stream idle: help with the LPs outside the batches
 
-    nclassic = max(1, LOCKSTEP_CLASSIC_THREADS)
-    streams = _lockstep_streams(device, ncls + nclassic)
     runners = [threading.Thread(target=run_class_then_classic, args=(k,)) for k in range(ncls)]
     crunners = [threading.Thread(target=classic_runner, args=(streams[ncls + j],)) for j in range(nclassic)]
     for t in runners + crunners:
@@ -366,6 +394,23 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
         f.result()                       # every LP is set up: the classic queue is complete
     for _ in crunners + runners:
         classic_q.put(None)
+    if small_ready:                      # the small LPs of the shard: one call, one workgroup per LP
+        small_ready.sort(key=lambda item: item[0])
+        t_join = time.perf_counter()
+        try:
+            solve_small_batch_solvers([item[2] for item in small_ready], tol=tol, max_iter=max_iter, tol_gap=tol_gap, stream=small_stream)
+            t_done = time.perf_counter()
+            for item in small_ready:
+                finish(item, t_join, t_done)
+        except Exception as e:          # the whole call failed: its LPs become error records, the rank must still reach the all-gather
+            import sys
+            print("[batch] small-LP batch failed: %s: %s" % (type(e).__name__, e), file=sys.stderr, flush=True)
+            for item in small_ready:
+                rec[item[0]] = _row(item[1], dict(_error_info(), seconds=0.0))
+                try:
+                    item[2].close()
+                except Exception:
+                    pass
     for t in runners + crunners:
         t.join()
     for f in tails:

@@ -238,8 +238,8 @@ extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, do
     return IPM_OK;
 }
 
-// whole loop of a small sparse LP in one launch of one workgroup (small_lp.h)
-static int enqueue_small(ipm_handle* h, int max_steps, int auto_reg) {
+// arguments of the fused small-LP kernels for this handle (small_lp.h): the single-LP launch and the items of ipm_solve_small_batch
+static SmallLP small_args(ipm_handle* h, int max_steps, int auto_reg) {
     SmallLP a;
     a.A = sparse_view(h); a.m = (int)h->m; a.n = (int)h->n; a.nt = (int)((h->m + 15) / 16);
     a.bptr = h->sm_bptr; a.bi = h->sm_bi; a.bk = h->sm_bk; a.bcol = h->sm_bcol; a.bcoef = h->sm_bcoef; a.nb = h->sm_nb;
@@ -248,6 +248,12 @@ static int enqueue_small(ipm_handle* h, int max_steps, int auto_reg) {
     a.sc = h->sc; a.hist = h->hist;
     a.eps = h->opt.pivot_guard_eps; a.big = h->opt.pivot_guard_big; a.shift_rel = h->shift_rel;
     a.max_steps = max_steps; a.auto_reg = auto_reg;
+    return a;
+}
+
+// whole loop of a small sparse LP in one launch of one workgroup (small_lp.h)
+static int enqueue_small(ipm_handle* h, int max_steps, int auto_reg) {
+    const SmallLP a = small_args(h, max_steps, auto_reg);
     if (h->bnd && h->detect) hipLaunchKernelGGL(small_lp_bounded_detect_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a, bnd_args(h), det_args(h));
     else if (h->bnd) hipLaunchKernelGGL(small_lp_bounded_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a, bnd_args(h));
     else if (h->detect) hipLaunchKernelGGL(small_lp_detect_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a, det_args(h));

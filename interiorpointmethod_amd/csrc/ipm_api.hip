@@ -51,6 +51,7 @@ using namespace ipm;
 #include "host_iteration.h"
 #include "host_lockstep.h"
 #include "host_lu.h"
+#include "host_small_batch.h"
 
 // ------------------------------------------------------------------------------- library
 extern "C" int ipm_abi_version(void) { return IPM_ABI_VERSION; }

@@ -360,4 +360,49 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_bounded_kernel(SmallLP a,
 __global__ __launch_bounds__(PD_THREADS) void small_lp_detect_kernel(SmallLP a, DetArgs dt) { small_lp_body<false, true>(a, BndArgs{}, dt); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_bounded_detect_kernel(SmallLP a, BndArgs bd, DetArgs dt) { small_lp_body<true, true>(a, bd, dt); }
 
+// ------------------------------------------------------------------------------- batch of small LPs (ipm_solve_small_batch)
+// One launch, one workgroup per LP: workgroup blockIdx.x reads item blockIdx.x of a table in device memory -- the arguments the
+// single-LP kernel gets in its kernel-argument segment -- and runs the SAME body on it.  The workgroups never talk to each other
+// (no atomics, no polling), so the dispatcher may run them in any order and in any number of rounds over the compute units; an LP's
+// arithmetic is that of its one-at-a-time launch, bit for bit.  The body keeps ~133 KB of static LDS per instantiation, so the four
+// variants stay four kernels: the host sorts the table by variant and launches one grid per variant present.
+enum { SMALL_PLAIN = 0, SMALL_BOUNDED = 1, SMALL_DETECT = 2, SMALL_BOUNDED_DETECT = 3, SMALL_NVARIANTS = 4 };
+struct SmallItem {
+    SmallLP lp;
+    BndArgs bd;
+    DetArgs dt;
+    double eta;                                          // the handle's step damping (small_batch_params_kernel)
+    int variant;                                         // SMALL_*
+    int index;                                           // position of the handle in the caller's array (the gathered record goes there)
+};
+
+// the index is the workgroup's own: the loads are wave-uniform and the item ends up in scalar registers like kernel arguments do
+template <bool Bounded, bool Detect>
+__device__ __forceinline__ void small_lp_batch_body(const SmallItem* __restrict__ items) {
+    const SmallItem it = items[blockIdx.x];
+    small_lp_body<Bounded, Detect>(it.lp, it.bd, it.dt);
+}
+__global__ __launch_bounds__(PD_THREADS) void small_lp_batch_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, false>(items); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, false>(items); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_batch_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, true>(items); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, true>(items); }
+
+// what set_params_kernel(sc, e1, e2, e3, eta, max_iter, force = 0, reset = 1) does for one LP, for every item: one thread per item
+__global__ __launch_bounds__(256) void small_batch_params_kernel(const SmallItem* __restrict__ items, int n, double e1, double e2, double e3, int max_iter) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    Scalars* sc = items[i].lp.sc;
+    sc->e1 = e1; sc->e2 = e2; sc->e3 = e3; sc->eta = items[i].eta;
+    sc->max_iter = max_iter; sc->force = 0;
+    sc->done = 0; sc->done_f = 0; sc->status = 0;
+    sc->k = 0; sc->fixed = 0; sc->fixed_first = 0; sc->obj_last_finite = __builtin_nan("");
+}
+
+// every item's scalar record into ONE contiguous array (slot = the item's index): the host reads all statistics with one copy
+__global__ __launch_bounds__(256) void small_batch_gather_kernel(const SmallItem* __restrict__ items, int n, Scalars* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[items[i].index] = *items[i].lp.sc;
+}
+
 }  // namespace ipm

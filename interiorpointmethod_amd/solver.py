@@ -635,6 +635,106 @@ def lockstep_eligible(solver):
     return bool(solver.sparse and solver.factor != "sparse" and not solver.bounded and not solver.schedule()["fused_small"])
 
 
+def small_batch_eligible(solver):
+    """Can this IpmSolver join solve_small_batch_solvers?  The library serves it with the fused single-workgroup kernel (sparse A of
+    at most 128 rows whose product list fits: ipm_get_schedule out[9] == 1).  Bounds and infeasibility detection do not matter."""
+    return bool(solver.schedule()["fused_small"])
+
+
+def solve_small_batch_solvers(solvers, tol=1e-8, max_iter=5000, tol_gap=None, stream=None):
+    """ipm_solve_small_batch: solve the LPs of `solvers` (IpmSolver objects on the fused small-LP path, one device, a state set) in ONE
+    launch per kernel variant, one workgroup per LP -> list of statistics dicts, one per solver (also in solver.stats).  Plain,
+    bounded and detect_infeasibility solvers may be mixed.  Per-LP semantics and arithmetic are those of IpmSolver.solve on each of
+    them alone (bit-identical iterates); get_state / get_bound_state / history / certificate work afterwards as after solve().  The
+    solvers stay alive: set_state / init_state and another call re-solve them.  stream: a torch.cuda.Stream for the launches
+    (None: the first solver's stream).  ValueError, naming the index, for a solver that is not on the small path."""
+    lib = _lib.load()
+    solvers = list(solvers)
+    n = len(solvers)
+    if n == 0:
+        return []
+    for i, sv in enumerate(solvers):
+        if not small_batch_eligible(sv):
+            raise ValueError("solver %d (%d x %d) is not on the fused small-LP path (sparse A, at most %d rows)"
+                             % (i, sv.m, sv.n, FUSED_SMALL_MAX_ROWS))
+    hs = (C.c_void_p * n)(*[sv._h for sv in solvers])
+    st = (_lib.Stats * n)()
+    e3 = tol if tol_gap is None else tol_gap
+    code = lib.ipm_solve_small_batch(hs, n, float(tol), float(tol), float(e3), int(max_iter),
+                                     C.c_void_p(stream.cuda_stream) if stream is not None else None, st)
+    _lib.check(None, code)
+    out = []
+    for sv, s_ in zip(solvers, st):
+        sv.stats = s_.as_dict()
+        out.append(sv.stats)
+    return out
+
+
+def _small_batch_host_check(problems, ub):
+    """Host part of solve_small_batch (no device is touched): shapes, the row limit of the small path and the bounds ->
+    list of (A as CSC, b, c, ub)."""
+    if _sp is None:
+        raise ImportError("solve_small_batch needs scipy (the small-LP path serves sparse handles)")
+    problems = list(problems)
+    if ub is not None and len(ub) != len(problems):
+        raise ValueError("ub has %d entries, expected one per problem (%d)" % (len(ub), len(problems)))
+    out = []
+    for i, (A, b, c) in enumerate(problems):
+        shape = A.shape if hasattr(A, "shape") else np.asarray(A).shape
+        if len(shape) != 2:
+            raise ValueError("problem %d: A must be 2-D" % i)
+        if shape[0] > FUSED_SMALL_MAX_ROWS:
+            raise ValueError("problem %d has %d rows: the small-LP batch serves LPs of at most %d rows"
+                             % (i, shape[0], FUSED_SMALL_MAX_ROWS))
+        A = _sp.csc_matrix(A, dtype=np.float64)               # dense A too: the small path serves sparse handles
+        if A.nnz == 0:
+            raise ValueError("problem %d: A has no nonzero entry" % i)
+        try:
+            u = _upper_bounds(None if ub is None else ub[i], shape[1])
+        except ValueError as e:
+            raise ValueError("problem %d: %s" % (i, e)) from e
+        out.append((A, b, c, u))
+    return out
+
+
+def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, ub=None, detect_infeasibility=False,
+                      regularize=0.0):
+    """Solve many small LPs at once -> list of (x, y, s, info), one per problem, each what solve_with_info returns for it alone.
+
+    problems: list of (A, b, c) with at most 128 rows each; a dense A is converted to CSC.  ub: None or one entry per problem (None or
+    a length-n vector, +inf = none).  One IpmSolver per LP on the current torch stream, init_state(y0), ONE ipm_solve_small_batch
+    call (one workgroup per LP), read-back, close.  An LP the library does not put on the small path (more than 128 rows, or a
+    product list of A D^2 A^T beyond its cap) raises ValueError naming its index before anything is launched."""
+    checked = _small_batch_host_check(problems, ub)
+    solvers = []
+    try:
+        for i, (A, b, c, u) in enumerate(checked):
+            sv = IpmSolver(A, b, c, device=device, regularize=regularize, ub=u, detect_infeasibility=detect_infeasibility)
+            solvers.append(sv)
+            if not small_batch_eligible(sv):
+                raise ValueError("problem %d (%d x %d) is not served by the fused small-LP path (its product list is too large)"
+                                 % (i, sv.m, sv.n))
+            sv.init_state(y0)
+        solve_small_batch_solvers(solvers, tol=tol, max_iter=max_iter, tol_gap=tol_gap)
+        out = []
+        for sv in solvers:
+            x, y, s = sv.get_state()
+            info = _info(sv)
+            info["bounded"] = sv.bounded
+            if sv.bounded:
+                info["w"], info["z"] = sv.get_bound_state()
+            if detect_infeasibility:
+                info["certificate"] = sv.certificate()
+            info["timeouts_recovered"] = sv.schedule()["timeouts_recovered"]
+            info["serial_launches"] = 0
+            info["factor_path"] = sv.factor
+            out.append((x, y, s, info))
+        return out
+    finally:
+        for sv in solvers:
+            sv.close()
+
+
 def _info(solver, cTlb=0.0):
     st = dict(solver.stats)
     st["status_name"] = STATUS_NAMES.get(st["status"], "?")
