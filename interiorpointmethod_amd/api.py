@@ -1,0 +1,165 @@
+"""Host-side mirror of the reference's interior-point call surface, running on libipm_hip.so.
+
+Same names and argument meaning as the reference (payakorn/InteriorPointMethod):
+
+    solve(A, b, c)                      -> (x, y, s)      the north-star seam
+    interior_sparse(A, b, c, cTlb, tol) -> objective - cTlb          main.py:760-815
+    interior(A, b, c, tol)              -> objective                 main.py:707-757 (returns None there)
+    (direction_*, solve_linear: kkt.py)
+
+A is a scipy sparse matrix (any format; the reference passes CSC) or a dense array; b, c are (len,) or (len, 1) of any numeric dtype
+(the .mat files hold int16/uint8) and are cast to float64 here.  Outputs are fresh (len, 1) float64 arrays like the reference's."""
+import os
+
+import numpy as np
+
+from . import _lib
+from .analysis import _upper_bounds
+from .handle import STATUS_NAMES, IpmSolver
+
+
+def _info(solver, cTlb=0.0):
+    st = dict(solver.stats)
+    st["status_name"] = STATUS_NAMES.get(st["status"], "?")
+    st["rp"] = st["rp_norm"] / (1.0 + st["b_norm"])          # reference scaling, main.py:170
+    st["rd"] = st["rd_norm"] / (1.0 + st["c_norm"])          # main.py:171
+    st["objective_minus_cTlb"] = st["objective"] - cTlb
+    return st
+
+
+def _solve_info(solver, history=False, certificate=False):
+    """THE information record of a solved IpmSolver: _info, the bounded set (with w, z), on request history and certificate, the
+    library's hidden recoveries (batch.RECORD_FIELDS): polls that timed out and were rolled back and repeated, sparse-factor sweeps
+    that ran as one workgroup after such a time-out (0 where no sparse factor exists), and the factorization path."""
+    info = _info(solver)
+    info["bounded"] = solver.bounded
+    if solver.bounded:
+        info["w"], info["z"] = solver.get_bound_state()
+    if history:
+        info["history"] = solver.history()
+    if certificate:
+        info["certificate"] = solver.certificate()
+    info["timeouts_recovered"] = solver.schedule()["timeouts_recovered"]
+    fi = solver.factor_info()
+    info["serial_launches"] = fi["serial_launches"] if fi else 0
+    info["factor_path"] = solver.factor
+    return info
+
+
+_last_info = None
+
+
+def last_info():
+    """Statistics of the most recent solve()/interior*() call in this process."""
+    return _last_info
+
+
+def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
+                    history=False, ub=None, detect_infeasibility=False, **opts):
+    """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
+    start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start().
+    history=True adds info["history"], the per-iteration records (IpmSolver.history()).  An LP whose A has more
+    than 5 % dependent rows (the QAP family) is solved with the 1e-14 Tikhonov shift, switched on by the library
+    after the first factorization (info["auto_regularized"] == 1; auto_regularize=False keeps it off).
+    ub: native upper bounds 0 <= x <= ub (+inf = none): info["bounded"] = |U| and, when |U| > 0, info["w"], info["z"].
+    detect_infeasibility=True: the solve may end in status 5 / 6 (IpmSolver); info["certificate"] = IpmSolver.certificate()."""
+    global _last_info
+    ub = _upper_bounds(ub, np.asarray(c).reshape(-1).shape[0])
+    if start == "mehrotra" and not opts.get("regularize") and os.environ.get("IPM_AUTO_REGULARIZE", "1") != "0":
+        # the least-squares start factors A A^T: guarded pivots there are dependent rows of A.  Where they are a
+        # sizeable fraction of the rows (the QAP family: 9-16 %; every other Netlib file: at most 2.7 %) the guard alone
+        # stalls the loop and the 1e-14 Tikhonov shift is switched on; a handful of dependent rows is left
+        # to the guard (the shift breaks 25FV47, BNL1, D6CUBE, WOOD1P, which have 1-11 of them)
+        with IpmSolver(A, b, c, device=device, **opts) as probe:
+            probe.normal_solve(np.zeros(probe.m))
+            if probe.last_pivots_fixed > 0.05 * probe.m:
+                opts = dict(opts, regularize=1e-14)
+    import time as _time
+    t0 = _time.perf_counter()
+    if detect_infeasibility:
+        opts = dict(opts, detect_infeasibility=True)
+    with IpmSolver(A, b, c, device=device, ub=ub, **opts) as sv:
+        t1 = _time.perf_counter()
+        if start == "mehrotra":
+            sv.set_state(*sv.mehrotra_start())
+        elif start == "reference":
+            sv.init_state(y0)
+        else:
+            raise ValueError('start must be "reference" or "mehrotra"')
+        sv.solve(tol=tol, max_iter=max_iter, tol_gap=tol_gap)
+        t2 = _time.perf_counter()
+        x, y, s = sv.get_state()
+        info = _solve_info(sv, history=history, certificate=detect_infeasibility)
+    t3 = _time.perf_counter()
+    # host-side phases of the call (seconds): handle creation + upload + symbolic analysis, the solve, read-back + destroy
+    info["setup_seconds"], info["solve_seconds"], info["teardown_seconds"] = t1 - t0, t2 - t1, t3 - t2
+    if os.environ.get("IPM_LP_TIMING"):
+        import sys
+        print("[lp-timing] m=%d factor=%s setup %.3f solve %.3f (device %.3f) teardown %.3f" %
+              (sv.m, info["factor_path"], t1 - t0, t2 - t1, info["solve_ms"] * 1e-3, t3 - t2), file=sys.stderr, flush=True)
+    _last_info = info
+    return x, y, s, info
+
+
+def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, **opts):
+    """min c^T x s.t. Ax=b, x>=0 (and x <= ub where ub is finite) by the Mehrotra predictor-corrector loop on the GPU
+    -> (x, y, s)."""
+    x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub, **opts)
+    return x, y, s
+
+
+def _verdict(info, value):
+    """+inf for a detected infeasible LP, -inf for a detected unbounded one (the convention of an LP's optimal value)."""
+    if info["status"] == _lib.STATUS_PRIMAL_INFEASIBLE:
+        return np.inf
+    if info["status"] == _lib.STATUS_DUAL_INFEASIBLE:
+        return -np.inf
+    return value
+
+
+def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False):
+    """Drop-in for main.py:760-815: start x=s=y=1, cap 5000, returns sum(x*c) - cTlb.  detect_infeasibility=True: +inf for an
+    LP detected infeasible, -inf for one detected unbounded."""
+    _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=5000, y0=1.0, device=device,
+                                    detect_infeasibility=detect_infeasibility)
+    return _verdict(info, info["objective"] - float(cTlb))
+
+
+def interior(A, b, c, tol=1e-20, device=0, detect_infeasibility=False):
+    """Drop-in for main.py:707-757 (dense path: y0=0, cap 50000); returns the objective (detect_infeasibility: as
+    interior_sparse)."""
+    _, _, _, info = solve_with_info(np.asarray(A, dtype=np.float64), b, c, tol=tol, max_iter=50000, y0=0.0,
+                                    device=device, detect_infeasibility=detect_infeasibility)
+    return _verdict(info, info["objective"])
+
+
+def verify_certificate(A, b, c, cert, ub=None):
+    """Recompute, in float64 from the problem data alone, how far `cert` (IpmSolver.certificate(): kind, y, z, x; y in the
+    caller's row order) is from an exact certificate of min c.x, A x = b, 0 <= x <= ub -> the violation (0 = exact):
+      primal_infeasible: y^ = y / t, z^ = z / t with t = b.y - u.z (must be > 0): max(max(A^T y^ - z^)_+, max(-z^)_+);
+      dual_infeasible:   x^ = x / t with t = -c.x (must be > 0): max(||A x^||_inf, max(-x^)_+, max x^_U).
+    +inf when the normalisation is not positive (no certificate at all).  Pure NumPy / SciPy: no device is touched."""
+    kind = cert["kind"] if isinstance(cert, dict) else cert
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    c = np.asarray(c, dtype=np.float64).reshape(-1)
+    n = c.shape[0]
+    u = np.full(n, np.inf) if ub is None else np.asarray(ub, dtype=np.float64).reshape(-1)
+    U = np.isfinite(u)
+    if kind == "primal_infeasible":
+        y = np.asarray(cert["y"], dtype=np.float64).reshape(-1)
+        z = np.zeros(n) if cert.get("z") is None else np.asarray(cert["z"], dtype=np.float64).reshape(-1)
+        z = np.where(U, z, 0.0)
+        t = float(b @ y - u[U] @ z[U])
+        if not t > 0.0 or not np.isfinite(t):
+            return np.inf
+        aty = np.asarray(A.T @ y).reshape(-1) / t - z / t
+        return float(max(np.max(aty, initial=0.0), np.max(-z / t, initial=0.0), 0.0))
+    if kind == "dual_infeasible":
+        x = np.asarray(cert["x"], dtype=np.float64).reshape(-1)
+        t = float(-(c @ x))
+        if not t > 0.0 or not np.isfinite(t):
+            return np.inf
+        xh = x / t
+        ax = np.asarray(A @ xh).reshape(-1)
+        return float(max(np.max(np.abs(ax), initial=0.0), np.max(-xh, initial=0.0), np.max(xh[U], initial=0.0)))
+    raise ValueError("cert kind must be 'primal_infeasible' or 'dual_infeasible', not %r" % (kind,))

@@ -12,9 +12,20 @@ driver loop of script.py:147-173 over the Netlib files.
 """
 from __future__ import annotations
 
+import os
+import queue
+import sys
+import threading
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
+
+from . import _lib
+from .analysis import prepare
+from .api import _solve_info, solve_with_info
+from .batches import LockstepBatch, lockstep_eligible, small_batch_eligible, solve_small_batch_solvers
+from .handle import IpmSolver
 
 # One record per LP.  The first nine fields are the statistics SURVEY.md 8e names; the rest make the library's hidden
 # recoveries and the host-side phases of a solve visible in the gathered table: `timeouts_recovered` = device hand-off
@@ -57,6 +68,15 @@ def _error_info(status=STATUS_ERROR):
     return dict(status=status, iterations=0, objective=nan, rp=nan, rd=nan, gap=nan, pivots_fixed=0)
 
 
+def _error_info_for(exc):
+    """The record of an LP whose solve raised exc: IPM_ERR_INVALID_INPUT is a status of its own."""
+    return _error_info(STATUS_INVALID_INPUT if getattr(exc, "code", None) == _lib.ERR_INVALID_INPUT else STATUS_ERROR)
+
+
+def _report_failure(A, exc):
+    print("[batch] %d x %d LP failed: %s: %s" % (A.shape[0], A.shape[1], type(exc).__name__, exc), file=sys.stderr, flush=True)
+
+
 def _row(i, info):
     """info dict of one solve -> its record row."""
     return [float(i), float(info["status"]), float(info["iterations"]), float(info["objective"]), float(info["rp"]),
@@ -70,7 +90,6 @@ def _guarded(solve_fn, problem, **kw):
     try:
         return dict(solve_fn(problem, **kw))
     except Exception as e:
-        import sys
         print("[batch] LP failed: %s: %s" % (type(e).__name__, e), file=sys.stderr, flush=True)
         return _error_info()
 
@@ -79,8 +98,6 @@ def solve_one(problem, device=0, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0
               tol_gap=None, detect_infeasibility=False):
     """Solve one LP (A, b, c) on `device` with the HIP path -> dict of statistics.  detect_infeasibility: the record's status
     may be 5 (primal infeasible) or 6 (dual infeasible, i.e. unbounded); DESIGN.md 4-C."""
-    from . import _lib
-    from .solver import solve_with_info
     A, b, c = problem
     t0 = time.perf_counter()
     try:
@@ -89,10 +106,8 @@ def solve_one(problem, device=0, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0
                                         detect_infeasibility=detect_infeasibility)
         info = dict(info)
     except Exception as e:          # every failure becomes a record: the rank must still reach the all-gather
-        import sys
-        print("[batch] %d x %d LP failed: %s: %s" % (A.shape[0], A.shape[1], type(e).__name__, e), file=sys.stderr,
-              flush=True)
-        info = _error_info(STATUS_INVALID_INPUT if getattr(e, "code", None) == _lib.ERR_INVALID_INPUT else STATUS_ERROR)
+        _report_failure(A, e)
+        info = _error_info_for(e)
     info["seconds"] = time.perf_counter() - t0
     return info
 
@@ -126,7 +141,6 @@ def solve_shard(problems, ids, device=0, solve_fn=solve_one, workers=1, **kw):
     each solve alone is 10-25 % slower without the look-ahead.  Results do not depend on the interleaving (every handle
     is independent and deterministic, and both schedules perform the same arithmetic)."""
     rec = np.zeros((len(ids), NF), dtype=np.float64)
-    import queue
     free_streams = queue.Queue()        # the rank's worker streams, the same ones in every call (see _lockstep_streams)
     for st in _lockstep_streams(device, max(1, workers)):
         free_streams.put(st)
@@ -155,7 +169,6 @@ def solve_shard(problems, ids, device=0, solve_fn=solve_one, workers=1, **kw):
         for r in rows:
             one(r)
         return rec
-    from concurrent.futures import ThreadPoolExecutor
     size = lambda r: problems[r[1]][0].shape[0]                     # noqa: E731
     for r in [r for r in rows if size(r) > SMALL_ROWS]:
         one(r)
@@ -166,15 +179,15 @@ def solve_shard(problems, ids, device=0, solve_fn=solve_one, workers=1, **kw):
 
 
 # Tuning of solve_shard_lockstep (one MI355X, the 73 Netlib LPs; DESIGN.md 6 has the sweeps):
-LOCKSTEP_MAX_ROWS = int(__import__("os").environ.get("IPM_LOCKSTEP_MAX_ROWS", 1 << 30))
+LOCKSTEP_MAX_ROWS = int(os.environ.get("IPM_LOCKSTEP_MAX_ROWS", 1 << 30))
 # row limits of the size classes (one batch, one stream, one host thread per class; the last class is open ended).  Every step of a
 # batch lasts as long as its slowest LP's kernel, so very different sizes in one batch inflate each other's chain
-LOCKSTEP_CLASSES = [int(v) for v in __import__("os").environ.get("IPM_LOCKSTEP_CLASSES", "2200,3500").split(",") if v]
+LOCKSTEP_CLASSES = [int(v) for v in os.environ.get("IPM_LOCKSTEP_CLASSES", "2200,3500").split(",") if v]
 # host threads (= streams) for the LPs outside the batches (up to 128 rows, sparse factor), solved one after the other.  Batches +
 # these should not be more than the four hardware queues HIP multiplexes its streams onto: a fifth stream costs 25 % of the suite
-LOCKSTEP_CLASSIC_THREADS = int(__import__("os").environ.get("IPM_LOCKSTEP_CLASSIC_THREADS", 1))
+LOCKSTEP_CLASSIC_THREADS = int(os.environ.get("IPM_LOCKSTEP_CLASSIC_THREADS", 1))
 # up to this many rows an LP takes the dense-tile factor (and joins a batch) even where a lone solve would take the sparse one
-LOCKSTEP_DENSE_ROWS = int(__import__("os").environ.get("IPM_LOCKSTEP_DENSE_ROWS", 3500))
+LOCKSTEP_DENSE_ROWS = int(os.environ.get("IPM_LOCKSTEP_DENSE_ROWS", 3500))
 
 
 _LOCKSTEP_STREAMS = {}      # device -> the streams of solve_shard_lockstep, created ONCE back to back
@@ -197,6 +210,216 @@ def _lockstep_streams(device, n):
     return have[:n]
 
 
+class _LockstepShard:
+    """One solve_shard_lockstep call: its state and its steps.  An item is (record row, LP id, solver, setup seconds): a ready handle."""
+
+    def __init__(self, problems, ids, device, workers, small_batch, y0, stop_kw, handle_kw):
+        self.problems, self.ids, self.device, self.workers, self.small_batch, self.y0 = problems, ids, device, workers, small_batch, y0
+        self.stop_kw = stop_kw              # tol, max_iter, tol_gap: of every solve of the shard
+        self.handle_kw = handle_kw          # device, regularize, concurrent=True, detect_infeasibility: of every handle of the shard
+        self.rec = np.zeros((len(ids), NF), dtype=np.float64)
+        self.classic_q = queue.Queue()      # (row, lp id, prepared, t0) of the LPs solved one after the other | None = no more
+        self.small_ready, self.small_lock = [], threading.Lock()      # small_batch: the items that wait for the one call
+        # the rank's streams, the same ones in every call: one per size class, then the one-at-a-time runners'
+        self.ncls, self.nclassic = len(LOCKSTEP_CLASSES) + 1, max(1, LOCKSTEP_CLASSIC_THREADS)
+        self.streams = _lockstep_streams(device, self.ncls + self.nclassic)
+        # The small batch SHARES the first one-at-a-time runner's stream on purpose: a further stream would be the fifth beside the batches
+        # and the runner, one more than the four hardware queues (see LOCKSTEP_CLASSIC_THREADS).  Its handles' uploads interleave with that
+        # runner's LPs; the one call comes after every set-up has finished and returns complete.
+        self.small_stream = self.streams[self.ncls] if small_batch else None
+        self.ready = [queue.Queue() for _ in range(self.ncls)]      # per class: items | None = a setup task ended without a handle
+        self.tails, self.tails_lock = [], threading.Lock()          # read-back + destroy of the finished LPs, on the pool
+        self._classify()
+
+    # -- classification of the LPs
+    def _rows_of(self, i):
+        return self.problems[i][0].shape[0]
+
+    def _wants_lockstep(self, i):
+        return 128 < self._rows_of(i) <= LOCKSTEP_MAX_ROWS
+
+    def _cls_of(self, i):
+        # Size classes: ONE batch per class, each on a stream of its own, run from a host thread of its own.  In a batch every global step
+        # lasts as long as its slowest LP's kernel, so LPs of very different size in one batch inflate each other's chain (measured: all 53
+        # LPs in one batch run 5.4 ms per iteration where the largest alone needs 2.5); a class of similar LPs keeps the chain at its leader's.
+        for k, lim in enumerate(LOCKSTEP_CLASSES):
+            if self._rows_of(i) <= lim:
+                return k
+        return len(LOCKSTEP_CLASSES)
+
+    def _classify(self):
+        # the lockstep candidates first (largest first: a batch should start with its longest chains), then the rest
+        self.rows = sorted(enumerate(self.ids), key=lambda r: (not self._wants_lockstep(r[1]), -self._rows_of(r[1]), r[1]))
+        self.expected = [0] * self.ncls     # per class: the set-up tasks its batch waits for
+        for _, i in self.rows:
+            if self._wants_lockstep(i):
+                self.expected[self._cls_of(i)] += 1
+
+    # -- records
+    def _record(self, row, i, info, t0):
+        info.setdefault("seconds", time.perf_counter() - t0)
+        self.rec[row] = _row(i, info)
+
+    def _abandon(self, items):
+        for item in items:
+            self.rec[item[0]] = _row(item[1], dict(_error_info(), seconds=0.0))
+            try:
+                item[2].close()
+            except Exception:
+                pass
+
+    def _finish(self, item, t_join, t_done):
+        row, i, sv, setup_s = item
+        t3 = time.perf_counter()
+        try:
+            info = _solve_info(sv)
+        except Exception:
+            info = _error_info()
+        sv.close()
+        info["setup_seconds"], info["solve_seconds"], info["teardown_seconds"] = setup_s, t_done - t_join, time.perf_counter() - t3
+        info["seconds"] = setup_s + (t_done - t_join)
+        self.rec[row] = _row(i, info)
+
+    # -- the pool: set-up of every LP (host analysis, handle, upload)
+    def _small_setup(self, problem, device=0, row=None, i=None, prepared=None, t0=None):
+        # the handle _classic() would create for this LP; False: the library does not put it on the small path
+        A, b, c = problem
+        sv = IpmSolver(A, b, c, prepared=prepared, **self.handle_kw)
+        try:
+            if not small_batch_eligible(sv):
+                sv.close()
+                return False
+            sv.init_state(self.y0)
+        except Exception:
+            sv.close()
+            raise
+        with self.small_lock:
+            self.small_ready.append((row, i, sv, time.perf_counter() - t0))
+        return True
+
+    def _setup(self, row_i):
+        row, i = row_i
+        A, b, c = self.problems[i]
+        ready = self.ready[self._cls_of(i)]
+        t0 = time.perf_counter()
+        sv, handed = None, False
+        try:
+            # host analysis ONCE: row order, factor path.  Up to LOCKSTEP_DENSE_ROWS rows the dense-tile factor even where a lone solve
+            # would take the sparse one: inside a batch an LP whose program is shorter than the class leader's adds no launches
+            prepared = prepare(A, b, c, factor=("dense" if self._wants_lockstep(i) and A.shape[0] <= LOCKSTEP_DENSE_ROWS else None))
+            if self._wants_lockstep(i) and prepared.factor != "sparse":
+                sv = IpmSolver(A, b, c, lockstep=True, prepared=prepared, **self.handle_kw)
+                if lockstep_eligible(sv):
+                    sv.init_state(self.y0)
+                    ready.put((row, i, sv, time.perf_counter() - t0))
+                    handed = True
+                    return
+                sv.close()
+                sv = None
+            if self.small_batch and A.shape[0] <= 128 and \
+                    _in_own_stream(self._small_setup, self.problems[i], self.device, dict(row=row, i=i, prepared=prepared, t0=t0),
+                                   stream=self.small_stream):
+                return
+            self.classic_q.put((row, i, prepared, t0))    # solved by a classic runner thread (few streams: see LOCKSTEP_CLASSIC_THREADS)
+            return
+        except Exception as e:          # every failure becomes a record: the rank must still reach the all-gather
+            _report_failure(A, e)
+            if sv is not None:
+                sv.close()
+            info = _error_info_for(e)
+        finally:
+            if self._wants_lockstep(i) and not handed:
+                ready.put(None)
+        self._record(row, i, info, t0)
+
+    # -- the one-at-a-time runners: the LPs no batch serves
+    def _classic(self, problem, device=0, prepared=None):
+        A, b, c = problem
+        _, _, _, info = solve_with_info(A, b, c, y0=self.y0, prepared=prepared, **self.stop_kw, **self.handle_kw)
+        return dict(info)
+
+    def _classic_runner(self, own):     # own: ONE stream per runner for all its LPs (a new stream per LP walks through the hardware queues)
+        while True:
+            item = self.classic_q.get()
+            if item is None:
+                return
+            row, i, prepared, t0 = item
+            try:
+                info = _in_own_stream(self._classic, self.problems[i], self.device, dict(prepared=prepared), stream=own)
+            except Exception as e:
+                _report_failure(self.problems[i][0], e)
+                info = _error_info_for(e)
+            self._record(row, i, info, t0)
+
+    # -- the lockstep loop of one size class
+    def _run_class(self, k):
+        arrived, joined = 0, {}
+        if self.expected[k] == 0:
+            return
+        try:
+            with LockstepBatch(device=self.device, stream=self.streams[k], **self.stop_kw) as lb:
+                while arrived < self.expected[k] or lb.active > 0:
+                    # every handle that is ready joins now; with nothing running, wait for the next one
+                    while arrived < self.expected[k]:
+                        try:
+                            item = self.ready[k].get(block=(lb.active == 0))
+                        except queue.Empty:
+                            break
+                        arrived += 1
+                        if item is not None:
+                            joined[id(item[2])] = (item, time.perf_counter())
+                            lb.add(item[2])
+                    if lb.active == 0:
+                        continue
+                    done = lb.step()
+                    t_done = time.perf_counter()
+                    for sv in done:
+                        item, t_join = joined.pop(id(sv))
+                        with self.tails_lock:
+                            self.tails.append(self.pool.submit(self._finish, item, t_join, t_done))
+        except Exception as e:          # the handles still in the batch become error records: the rank must still reach the all-gather
+            print("[batch] lockstep batch failed: %s: %s" % (type(e).__name__, e), file=sys.stderr, flush=True)
+            self._abandon([item for item, _t in joined.values()])
+
+    def _run_class_then_classic(self, k):
+        self._run_class(k)
+        if self.expected[k] and os.environ.get("IPM_LOCKSTEP_STEAL", "1") != "0":
+            self._classic_runner(self.streams[k])   # its batch is finished, its stream idle: help with the LPs outside the batches
+
+    # -- the optional small batch: the small LPs of the shard in one call, one workgroup per LP
+    def _run_small_batch(self):
+        self.small_ready.sort(key=lambda item: item[0])
+        t_join = time.perf_counter()
+        try:
+            solve_small_batch_solvers([item[2] for item in self.small_ready], stream=self.small_stream, **self.stop_kw)
+            t_done = time.perf_counter()
+            for item in self.small_ready:
+                self._finish(item, t_join, t_done)
+        except Exception as e:          # the whole call failed: its LPs become error records, the rank must still reach the all-gather
+            print("[batch] small-LP batch failed: %s: %s" % (type(e).__name__, e), file=sys.stderr, flush=True)
+            self._abandon(self.small_ready)
+
+    def run(self):
+        self.pool = ThreadPoolExecutor(max_workers=max(1, self.workers))
+        futs = [self.pool.submit(self._setup, r) for r in self.rows]
+        runners = [threading.Thread(target=self._run_class_then_classic, args=(k,)) for k in range(self.ncls)]
+        crunners = [threading.Thread(target=self._classic_runner, args=(self.streams[self.ncls + j],)) for j in range(self.nclassic)]
+        for t in runners + crunners:
+            t.start()
+        for f in futs:
+            f.result()                       # every LP is set up: the classic queue is complete
+        for _ in crunners + runners:
+            self.classic_q.put(None)
+        if self.small_ready:
+            self._run_small_batch()
+        for t in runners + crunners:
+            t.join()
+        for f in self.tails:
+            f.result()
+        self.pool.shutdown()
+        return self.rec
+
+
 def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, tol_gap=None,
                          detect_infeasibility=False, small_batch=False, **_):
     """Solve problems[i] for i in ids on this rank's GPU with the LOCKSTEP BATCH -> (len(ids), NF) records.
@@ -212,211 +435,9 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
 
     small_batch=True (opt-in): the LPs of up to 128 rows that the fused single-workgroup kernel serves are not solved one after the
     other but collected, and ONE ipm_solve_small_batch call solves them, one workgroup per LP, once every LP of the shard is set up
-    (solver.solve_small_batch_solvers).  Same records, bit for bit (tests/test_gpu_small_batch.py)."""
-    import queue
-    from concurrent.futures import ThreadPoolExecutor
-    from . import _lib
-    from .solver import IpmSolver, LockstepBatch, _info, lockstep_eligible, prepare, small_batch_eligible, solve_small_batch_solvers
-    rec = np.zeros((len(ids), NF), dtype=np.float64)
-    import threading
-    classic_q = queue.Queue()
-    small_ready, small_lock = [], threading.Lock()      # small_batch: (row, lp id, solver, setup seconds) of the LPs that wait for the one call
-    # the rank's streams, the same ones in every call: one per size class, then the one-at-a-time runners'
-    ncls, nclassic = len(LOCKSTEP_CLASSES) + 1, max(1, LOCKSTEP_CLASSIC_THREADS)
-    streams = _lockstep_streams(device, ncls + nclassic)
-    # The small batch SHARES the first one-at-a-time runner's stream on purpose: a further stream would be the fifth beside the batches
-    # and the runner, one more than the four hardware queues (see LOCKSTEP_CLASSIC_THREADS).  Its handles' uploads interleave with that
-    # runner's LPs; the one call comes after every set-up has finished and returns complete.
-    small_stream = streams[ncls] if small_batch else None
-
-    def small_setup(problem, device=0, row=None, i=None, prepared=None, t0=None):
-        # the handle classic() would create for this LP; False: the library does not put it on the small path
-        A, b, c = problem
-        sv = IpmSolver(A, b, c, device=device, regularize=regularize, concurrent=True, prepared=prepared, detect_infeasibility=detect_infeasibility)
-        try:
-            if not small_batch_eligible(sv):
-                sv.close()
-                return False
-            sv.init_state(y0)
-        except Exception:
-            sv.close()
-            raise
-        with small_lock:
-            small_ready.append((row, i, sv, time.perf_counter() - t0))
-        return True
-
-    def classic(problem, device=0, prepared=None):
-        from .solver import solve_with_info
-        A, b, c = problem
-        _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, regularize=regularize,
-                                        concurrent=True, tol_gap=tol_gap, prepared=prepared, detect_infeasibility=detect_infeasibility)
-        return dict(info)
-
-    def wants_lockstep(i):
-        return 128 < problems[i][0].shape[0] <= LOCKSTEP_MAX_ROWS
-
-    def one(row_i, ready):          # ready: queue of (row, lp id, solver, setup seconds) | None = a setup task ended without a handle
-        row, i = row_i
-        A, b, c = problems[i]
-        t0 = time.perf_counter()
-        sv, handed = None, False
-        try:
-            # host analysis ONCE: row order, factor path.  Up to LOCKSTEP_DENSE_ROWS rows the dense-tile factor even where a lone solve
-            # would take the sparse one: inside a batch an LP whose program is shorter than the class leader's adds no launches
-            prepared = prepare(A, b, c, factor=("dense" if wants_lockstep(i) and A.shape[0] <= LOCKSTEP_DENSE_ROWS else None))
-            if wants_lockstep(i) and prepared.factor != "sparse":
-                sv = IpmSolver(A, b, c, device=device, regularize=regularize, lockstep=True, concurrent=True, prepared=prepared,
-                               detect_infeasibility=detect_infeasibility)
-                if lockstep_eligible(sv):
-                    sv.init_state(y0)
-                    ready.put((row, i, sv, time.perf_counter() - t0))
-                    handed = True
-                    return
-                sv.close()
-                sv = None
-            if small_batch and A.shape[0] <= 128 and \
-                    _in_own_stream(small_setup, problems[i], device, dict(row=row, i=i, prepared=prepared, t0=t0), stream=small_stream):
-                return
-            classic_q.put((row, i, prepared, t0))         # solved by a classic runner thread (few streams: see LOCKSTEP_CLASSIC_THREADS)
-            return
-        except Exception as e:          # every failure becomes a record: the rank must still reach the all-gather
-            import sys
-            print("[batch] %d x %d LP failed: %s: %s" % (A.shape[0], A.shape[1], type(e).__name__, e), file=sys.stderr, flush=True)
-            if sv is not None:
-                sv.close()
-            info = _error_info(STATUS_INVALID_INPUT if getattr(e, "code", None) == _lib.ERR_INVALID_INPUT else STATUS_ERROR)
-        finally:
-            if wants_lockstep(i) and not handed:
-                ready.put(None)
-        info.setdefault("seconds", time.perf_counter() - t0)
-        rec[row] = _row(i, info)
-
-    def classic_runner(own):            # own: ONE stream per runner for all its LPs (a new stream per LP walks through the hardware queues)
-        while True:
-            item = classic_q.get()
-            if item is None:
-                return
-            row, i, prepared, t0 = item
-            try:
-                info = _in_own_stream(classic, problems[i], device, dict(prepared=prepared), stream=own)
-            except Exception as e:
-                import sys
-                A = problems[i][0]
-                print("[batch] %d x %d LP failed: %s: %s" % (A.shape[0], A.shape[1], type(e).__name__, e), file=sys.stderr, flush=True)
-                info = _error_info(STATUS_INVALID_INPUT if getattr(e, "code", None) == _lib.ERR_INVALID_INPUT else STATUS_ERROR)
-            info.setdefault("seconds", time.perf_counter() - t0)
-            rec[row] = _row(i, info)
-
-    def finish(item, t_join, t_done):
-        row, i, sv, setup_s = item
-        t3 = time.perf_counter()
-        try:
-            info = _info(sv)
-            info["timeouts_recovered"] = sv.schedule()["timeouts_recovered"]
-            info["serial_launches"] = 0
-        except Exception:
-            info = _error_info()
-        sv.close()
-        info["setup_seconds"], info["solve_seconds"], info["teardown_seconds"] = setup_s, t_done - t_join, time.perf_counter() - t3
-        info["seconds"] = setup_s + (t_done - t_join)
-        rec[row] = _row(i, info)
-
-    # Size classes: ONE batch per class, each on a stream of its own, run from a host thread of its own.  In a batch every global step
-    # lasts as long as its slowest LP's kernel, so LPs of very different size in one batch inflate each other's chain (measured: all 53
-    # LPs in one batch run 5.4 ms per iteration where the largest alone needs 2.5); a class of similar LPs keeps the chain at its leader's.
-    def cls_of(i):
-        m = problems[i][0].shape[0]
-        for k, lim in enumerate(LOCKSTEP_CLASSES):
-            if m <= lim:
-                return k
-        return len(LOCKSTEP_CLASSES)
-    ready = [queue.Queue() for _ in range(ncls)]
-
-    def one_cls(row_i):
-        k = cls_of(row_i[1])
-        one(row_i, ready[k])
-
-    # the lockstep candidates first (largest first: a batch should start with its longest chains), then the rest
-    rows = sorted(enumerate(ids), key=lambda r: (not wants_lockstep(r[1]), -problems[r[1]][0].shape[0], r[1]))
-    expected = [0] * ncls
-    for r in rows:
-        if wants_lockstep(r[1]):
-            expected[cls_of(r[1])] += 1
-    pool = ThreadPoolExecutor(max_workers=max(1, workers))
-    futs = [pool.submit(one_cls, r) for r in rows]
-    tails, tails_lock = [], threading.Lock()
-
-    def run_class(k):
-        arrived, joined = 0, {}
-        if expected[k] == 0:
-            return
-        try:
-            with LockstepBatch(device=device, tol=tol, max_iter=max_iter, tol_gap=tol_gap, stream=streams[k]) as lb:
-                while arrived < expected[k] or lb.active > 0:
-                    # every handle that is ready joins now; with nothing running, wait for the next one
-                    while arrived < expected[k]:
-                        try:
-                            item = ready[k].get(block=(lb.active == 0))
-                        except queue.Empty:
-                            break
-                        arrived += 1
-                        if item is not None:
-                            joined[id(item[2])] = (item, time.perf_counter())
-                            lb.add(item[2])
-                    if lb.active == 0:
-                        continue
-                    done = lb.step()
-                    t_done = time.perf_counter()
-                    for sv in done:
-                        item, t_join = joined.pop(id(sv))
-                        with tails_lock:
-                            tails.append(pool.submit(finish, item, t_join, t_done))
-        except Exception as e:          # the handles still in the batch become error records: the rank must still reach the all-gather
-            import sys
-            print("[batch] lockstep batch failed: %s: %s" % (type(e).__name__, e), file=sys.stderr, flush=True)
-            for item, _t in joined.values():
-                rec[item[0]] = _row(item[1], dict(_error_info(), seconds=0.0))
-                try:
-                    item[2].close()
-                except Exception:
-                    pass
-
-    def run_class_then_classic(k):
-        run_class(k)
-        if expected[k] and __import__("os").environ.get("IPM_LOCKSTEP_STEAL", "1") != "0":
-            classic_runner(streams[k])  # its batch is finished, its stream idle: help with the LPs outside the batches
-
-    runners = [threading.Thread(target=run_class_then_classic, args=(k,)) for k in range(ncls)]
-    crunners = [threading.Thread(target=classic_runner, args=(streams[ncls + j],)) for j in range(nclassic)]
-    for t in runners + crunners:
-        t.start()
-    for f in futs:
-        f.result()                       # every LP is set up: the classic queue is complete
-    for _ in crunners + runners:
-        classic_q.put(None)
-    if small_ready:                      # the small LPs of the shard: one call, one workgroup per LP
-        small_ready.sort(key=lambda item: item[0])
-        t_join = time.perf_counter()
-        try:
-            solve_small_batch_solvers([item[2] for item in small_ready], tol=tol, max_iter=max_iter, tol_gap=tol_gap, stream=small_stream)
-            t_done = time.perf_counter()
-            for item in small_ready:
-                finish(item, t_join, t_done)
-        except Exception as e:          # the whole call failed: its LPs become error records, the rank must still reach the all-gather
-            import sys
-            print("[batch] small-LP batch failed: %s: %s" % (type(e).__name__, e), file=sys.stderr, flush=True)
-            for item in small_ready:
-                rec[item[0]] = _row(item[1], dict(_error_info(), seconds=0.0))
-                try:
-                    item[2].close()
-                except Exception:
-                    pass
-    for t in runners + crunners:
-        t.join()
-    for f in tails:
-        f.result()
-    pool.shutdown()
-    return rec
+    (batches.solve_small_batch_solvers).  Same records, bit for bit (tests/test_gpu_small_batch.py)."""
+    return _LockstepShard(problems, ids, device, workers, small_batch, y0, dict(tol=tol, max_iter=max_iter, tol_gap=tol_gap),
+                          dict(device=device, regularize=regularize, concurrent=True, detect_infeasibility=detect_infeasibility)).run()
 
 
 def gather_records(local, shard_sizes, dist=None, device=None):
@@ -446,7 +467,6 @@ def make_store(rank, world, host=None, port=None, timeout_s=300):
     """A TCP key-value store for the self-scheduling counter (public torch.distributed.TCPStore API; rank 0 hosts it).
     Control plane only: one small round trip per LP.  The caller may hand the same store to init_process_group."""
     import datetime
-    import os
     import torch.distributed as tdist
     host = host or os.environ.get("MASTER_ADDR", "127.0.0.1")
     port = int(port if port is not None else int(os.environ.get("MASTER_PORT", "29500")) + 1)
@@ -459,7 +479,6 @@ def _solve_dynamic(problems, order, store, key, device, solve_fn, workers, **kw)
     an atomic counter on the rendezvous store.  Iteration counts (14 ... the cap) make a static partition lose up to
     40 % to imbalance; the counter costs one small TCP round trip per LP.  Returns an (n, NF) table whose rows not
     solved on this rank keep id = -1."""
-    import threading
     n = len(problems)
     rec = np.full((n, NF), -1.0)
     lock = threading.Lock()
@@ -488,7 +507,6 @@ def _solve_dynamic(problems, order, store, key, device, solve_fn, workers, **kw)
     if workers <= 1:
         loop(0)
     else:
-        from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=workers) as pool:
             list(pool.map(loop, range(workers)))
     return rec
@@ -514,7 +532,7 @@ def _gather_sparse(rec, dist, device=None):
 # overlap as separate chains (73-LP suite, 61 such LPs on one GPU: 23.5 LPs/s against 14.7 one-at-a-time); with few of them the
 # chains of a batch only wait for each other (26-LP parity set, 17 such LPs: 86-123 LPs/s against 116-140) -- sweeps in
 # profiles/r04_netlib_lockstep_vs_classic_sweep.txt.  The rule counts LPs of more than 128 rows per rank.
-LOCKSTEP_MIN_LPS = int(__import__("os").environ.get("IPM_LOCKSTEP_MIN_LPS", 24))
+LOCKSTEP_MIN_LPS = int(os.environ.get("IPM_LOCKSTEP_MIN_LPS", 24))
 
 
 def lockstep_wanted(problems, world=1, workers=8, mode="auto"):

@@ -1,0 +1,166 @@
+"""The batch front ends over IpmSolver handles: the lockstep batch and the small-LP batch (one workgroup per LP)."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .analysis import FUSED_SMALL_MAX_ROWS, _sp, _upper_bounds
+from .api import _solve_info
+from .handle import IpmSolver, _gap_tol
+
+
+def _handle_array(solvers):           # (the handles as a C array, a Stats array of the same length) for one batched library call
+    n = len(solvers)
+    return (C.c_void_p * n)(*[sv._h for sv in solvers]), (_lib.Stats * n)()
+
+
+def _scatter_stats(solvers, stats):           # each solver takes its statistics record (solver.stats) -> the list of them
+    for sv, st in zip(solvers, stats):
+        sv.stats = st.as_dict()
+    return [sv.stats for sv in solvers]
+
+
+def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None):
+    """ipm_solve_batch: solve the LPs of `solvers` (IpmSolver objects created with lockstep=True on one device, a state set) AT ONCE,
+    iteration k of all of them in the same launches (csrc/lockstep.h) -> list of statistics dicts, one per solver.  Per-LP semantics
+    and arithmetic are those of IpmSolver.solve on each of them alone (bit-identical iterates)."""
+    hs, st = _handle_array(solvers)
+    _lib.check(solvers[0]._h, _lib.load().ipm_solve_batch(hs, len(solvers), tol, tol, _gap_tol(tol, tol_gap), int(max_iter), st))
+    return _scatter_stats(solvers, st)
+
+
+class LockstepBatch:
+    """ipm_batch_*: the lockstep batch, incrementally.  add(solver) lets an IpmSolver (lockstep=True, a state set) JOIN between two
+    steps; step() runs opt.check_every iterations of every active LP in the same launches and returns the solvers that finished,
+    each with its statistics in solver.stats.  The solvers stay owned by the caller (close them after they are reported finished)."""
+
+    def __init__(self, device=0, tol=1e-8, max_iter=5000, tol_gap=None, stream=None):
+        """stream: a torch.cuda.Stream the batch's launches go to (the caller keeps it alive); None: a stream of the batch's own."""
+        self._lib = _lib.load()
+        self._b = C.c_void_p()
+        self._stream = stream
+        _lib.check(None, self._lib.ipm_batch_create(int(device), C.c_void_p(stream.cuda_stream) if stream is not None else None, C.byref(self._b)))
+        self.tol, self.max_iter, self.tol_gap = float(tol), int(max_iter), _gap_tol(tol, tol_gap)
+        self.solvers = []
+        self.active = 0
+
+    def _check(self, code):
+        if code != _lib.IPM_OK:
+            raise _lib.IpmError(code, (self._lib.ipm_batch_last_error(self._b) or b"").decode("utf-8", "replace"))
+
+    def add(self, solver):
+        idx = C.c_int32(-1)
+        self._check(self._lib.ipm_batch_add(self._b, solver._h, self.tol, self.tol, self.tol_gap, self.max_iter, C.byref(idx)))
+        assert idx.value == len(self.solvers)
+        self.solvers.append(solver)
+        self.active += 1
+        return idx.value
+
+    def step(self):
+        cap = max(1, len(self.solvers))
+        fin = (C.c_int32 * cap)()
+        nf, na = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.ipm_batch_step(self._b, fin, cap, C.byref(nf), C.byref(na)))
+        self.active = na.value
+        out, stats = [self.solvers[fin[k]] for k in range(nf.value)], (_lib.Stats * cap)()
+        for k in range(nf.value):
+            self._check(self._lib.ipm_batch_stats(self._b, fin[k], C.byref(stats[k])))
+        _scatter_stats(out, stats)
+        return out
+
+    def close(self):
+        if self._b:
+            self._lib.ipm_batch_destroy(self._b)
+            self._b = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def lockstep_eligible(solver):
+    """Can this IpmSolver join solve_lockstep?  Sparse A on the dense-tile factor, more than 128 rows (the small LPs have their fused
+    single-workgroup kernel, the sparse-factor LPs their tree sweeps).  A solver with upper bounds has no lockstep twin."""
+    return bool(solver.sparse and solver.factor != "sparse" and not solver.bounded and not solver.schedule()["fused_small"])
+
+
+def small_batch_eligible(solver):
+    """Can this IpmSolver join solve_small_batch_solvers?  The library serves it with the fused single-workgroup kernel (sparse A of
+    at most 128 rows whose product list fits: ipm_get_schedule out[9] == 1).  Bounds and infeasibility detection do not matter."""
+    return bool(solver.schedule()["fused_small"])
+
+
+def solve_small_batch_solvers(solvers, tol=1e-8, max_iter=5000, tol_gap=None, stream=None):
+    """ipm_solve_small_batch: solve the LPs of `solvers` (IpmSolver objects on the fused small-LP path, one device, a state set) in ONE
+    launch per kernel variant, one workgroup per LP -> list of statistics dicts, one per solver (also in solver.stats).  Plain,
+    bounded and detect_infeasibility solvers may be mixed.  Per-LP semantics and arithmetic are those of IpmSolver.solve on each of
+    them alone (bit-identical iterates); get_state / get_bound_state / history / certificate work afterwards as after solve().  The
+    solvers stay alive: set_state / init_state and another call re-solve them.  stream: a torch.cuda.Stream for the launches
+    (None: the first solver's stream).  ValueError, naming the index, for a solver that is not on the small path."""
+    lib = _lib.load()
+    solvers = list(solvers)
+    if not solvers:
+        return []
+    for i, sv in enumerate(solvers):
+        if not small_batch_eligible(sv):
+            raise ValueError("solver %d (%d x %d) is not on the fused small-LP path (sparse A, at most %d rows)"
+                             % (i, sv.m, sv.n, FUSED_SMALL_MAX_ROWS))
+    hs, st = _handle_array(solvers)
+    code = lib.ipm_solve_small_batch(hs, len(solvers), float(tol), float(tol), _gap_tol(tol, tol_gap), int(max_iter),
+                                     C.c_void_p(stream.cuda_stream) if stream is not None else None, st)
+    _lib.check(None, code)
+    return _scatter_stats(solvers, st)
+
+
+def _small_batch_host_check(problems, ub):
+    """Host part of solve_small_batch (no device is touched): shapes, the row limit of the small path and the bounds ->
+    list of (A as CSC, b, c, ub)."""
+    if _sp is None:
+        raise ImportError("solve_small_batch needs scipy (the small-LP path serves sparse handles)")
+    problems = list(problems)
+    if ub is not None and len(ub) != len(problems):
+        raise ValueError("ub has %d entries, expected one per problem (%d)" % (len(ub), len(problems)))
+    out = []
+    for i, (A, b, c) in enumerate(problems):
+        shape = A.shape if hasattr(A, "shape") else np.asarray(A).shape
+        if len(shape) != 2:
+            raise ValueError("problem %d: A must be 2-D" % i)
+        if shape[0] > FUSED_SMALL_MAX_ROWS:
+            raise ValueError("problem %d has %d rows: the small-LP batch serves LPs of at most %d rows"
+                             % (i, shape[0], FUSED_SMALL_MAX_ROWS))
+        A = _sp.csc_matrix(A, dtype=np.float64)               # dense A too: the small path serves sparse handles
+        if A.nnz == 0:
+            raise ValueError("problem %d: A has no nonzero entry" % i)
+        try:
+            u = _upper_bounds(None if ub is None else ub[i], shape[1])
+        except ValueError as e:
+            raise ValueError("problem %d: %s" % (i, e)) from e
+        out.append((A, b, c, u))
+    return out
+
+
+def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, ub=None, detect_infeasibility=False,
+                      regularize=0.0):
+    """Solve many small LPs at once -> list of (x, y, s, info), one per problem, each what solve_with_info returns for it alone.
+
+    problems: list of (A, b, c) with at most 128 rows each; a dense A is converted to CSC.  ub: None or one entry per problem (None or
+    a length-n vector, +inf = none).  One IpmSolver per LP on the current torch stream, init_state(y0), ONE ipm_solve_small_batch
+    call (one workgroup per LP), read-back, close.  An LP the library does not put on the small path (more than 128 rows, or a
+    product list of A D^2 A^T beyond its cap) raises ValueError naming its index before anything is launched."""
+    checked = _small_batch_host_check(problems, ub)
+    solvers = []
+    try:
+        for i, (A, b, c, u) in enumerate(checked):
+            sv = IpmSolver(A, b, c, device=device, regularize=regularize, ub=u, detect_infeasibility=detect_infeasibility)
+            solvers.append(sv)
+            if not small_batch_eligible(sv):
+                raise ValueError("problem %d (%d x %d) is not served by the fused small-LP path (its product list is too large)"
+                                 % (i, sv.m, sv.n))
+            sv.init_state(y0)
+        solve_small_batch_solvers(solvers, tol=tol, max_iter=max_iter, tol_gap=tol_gap)
+        return [sv.get_state() + (_solve_info(sv, certificate=detect_infeasibility),) for sv in solvers]
+    finally:
+        for sv in solvers:
+            sv.close()

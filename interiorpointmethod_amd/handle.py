@@ -1,0 +1,323 @@
+"""IpmSolver: one LP bound to one GPU through a libipm_hip handle.  PyTorch only owns the workspace and the stream; all arithmetic is HIP."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+from .analysis import _col, _is_sparse, prepare
+
+STATUS_NAMES = {0: "running", 1: "converged", 2: "max_iter", 3: "nan", 5: "primal_infeasible", 6: "dual_infeasible"}
+
+
+def _dptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _gap_tol(tol, tol_gap):           # the gap tolerance of a solve: tol unless the caller gives one of its own
+    return float(tol if tol_gap is None else tol_gap)
+
+
+class IpmSolver:
+    """One LP bound to one GPU: owns a libipm_hip handle whose workspace is a torch tensor."""
+
+    def __init__(self, A, b, c, device=0, eta=0.91, pivot_guard_eps=1e-30, pivot_guard_big=1e64,
+                 check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
+                 auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
+                 infeasibility_tol=(1e-8, 1e-8)):
+        """ub: native upper bounds 0 <= x <= ub (length n, +inf = none), checked on the host before any device
+        is touched.  The normal matrix keeps order m; a bounded solver cannot join the lockstep batch.
+        detect_infeasibility: the stop test also tests the iterate for a certificate of primal infeasibility (status 5) or of
+        unboundedness (status 6) with the tolerances infeasibility_tol = (eps_p, eps_d) (IPM_FLAG_DETECT_INFEASIBILITY,
+        DESIGN.md 4-C); certificate() returns it.  Off by default: the solve is then exactly the reference's loop."""
+        if prepared is None:
+            prepared = prepare(A, b, c, dense=dense, reorder=reorder, factor=factor, ub=ub)
+        elif ub is not None:
+            raise ValueError("pass ub to prepare() when a Prepared is given")
+        lib = _lib.load()
+        self._lib = lib
+        self._h = None
+        # device row i = caller's row perm[i] (sparse A whose rows the host analysis reordered: minimum degree or RCM)
+        self._perm = prepared.perm
+        self.m, self.n = prepared.m, prepared.n
+        self._host = prepared.host  # caller's row order: used by start-point heuristics only
+        self.factor, self.order_info = prepared.factor, prepared.order_info
+        A, b, c = prepared.A, prepared.b, prepared.c
+        opts = _lib.Options()
+        lib.ipm_default_options(C.byref(opts))
+        opts.eta, opts.pivot_guard_eps, opts.pivot_guard_big = eta, pivot_guard_eps, pivot_guard_big
+        opts.check_every = int(os.environ.get("IPM_CHECK_EVERY") or check_every)
+        opts.regularize = float(regularize)
+        # concurrent=True: this handle shares the GPU with others (batched mode) -- one stream per handle, no look-ahead, no
+        # device polling (include/ipm_hip.h: IPM_FLAG_SINGLE_STREAM).  Without it the library still protects itself (it
+        # counts the live handles per device and falls back to stream events).
+        # lockstep=True: the handle is meant for solve_lockstep (ipm_solve_batch: iteration k of several LPs in the same launches)
+        opts.flags = (_lib.FLAG_LOCKSTEP if lockstep else 0) | \
+                     ((_lib.FLAG_NO_DEVICE_POLLING | _lib.FLAG_SINGLE_STREAM) if concurrent else 0) | \
+                     (0 if auto_regularize else _lib.FLAG_NO_AUTO_REGULARIZE) | \
+                     (_lib.FLAG_SPARSE_FACTOR if self.factor == "sparse" else 0) | \
+                     (_lib.FLAG_DETECT_INFEASIBILITY if detect_infeasibility else 0)
+        self.detect_infeasibility = bool(detect_infeasibility)
+        nbytes = C.c_size_t(0)
+        self.sparse = _is_sparse(A)
+        if self.sparse:                      # A stays sparse on the device (CSR + CSC, sparse formation of B)
+            opts.sparse_nnz = int(A.nnz)
+            # (sized from the options: a sparse-factor handle carries no dense m x m normal matrix)
+            _lib.check(None, lib.ipm_workspace_bytes_opts(self.m, self.n, C.byref(opts), C.byref(nbytes)))
+        else:
+            _lib.check(None, lib.ipm_workspace_bytes(self.m, self.n, C.byref(nbytes)))
+        self.workspace_bytes = nbytes.value
+        ws_ptr, stream = None, None
+        self._ws = None
+        if use_torch:
+            import torch
+            if not torch.cuda.is_available():
+                raise _lib.IpmLibraryError("no ROCm device visible to torch; the HIP path cannot run")
+            dev = torch.device("cuda", device)
+            self._ws = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=dev)   # device buffer only
+            ws_ptr = C.c_void_p(self._ws.data_ptr())
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        h = C.c_void_p()
+        _lib.check(None, lib.ipm_create(int(device), self.m, self.n, C.byref(opts), ws_ptr,
+                                        self.workspace_bytes if ws_ptr else 0, stream, C.byref(h)))
+        self._h = h
+        if self.sparse:
+            indptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
+            indices = np.ascontiguousarray(A.indices, dtype=np.int32)
+            data = np.ascontiguousarray(A.data, dtype=np.float64)
+            self._check(lib.ipm_set_A_csc(h, indptr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          indices.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(data),
+                                          int(data.shape[0])))
+            if self.factor == "sparse" and self.schedule()["fused_small"]:
+                # prepare() never asks for this (analysis._factor_path); a Prepared filled in by other hands may.  The library is the
+                # authority: the fused single-workgroup kernel serves the LP, no sparse factor exists: report the path really taken
+                self.factor, self.order_info = "dense", None
+        else:
+            self._check(lib.ipm_set_A_dense(h, C.c_void_p(A.ctypes.data), self.n, 0))
+        self.ub = prepared.ub                       # None: no finite bound (the unbounded code runs)
+        self.bounded = 0 if self.ub is None else int(np.isfinite(self.ub).sum())
+        if self.ub is not None:
+            self._check(lib.ipm_set_bounds(h, _dptr(self.ub)))
+        self._check(lib.ipm_set_bc(h, _dptr(b), _dptr(c)))
+        if detect_infeasibility:
+            eps_p, eps_d = infeasibility_tol
+            self._check(lib.ipm_set_infeasibility_tol(h, float(eps_p), float(eps_d)))
+        self.stats = None
+
+    # -- plumbing
+    def _check(self, code):
+        _lib.check(self._h, code)
+
+    def close(self):
+        if self._h is not None:
+            self._lib.ipm_destroy(self._h)
+            self._h = None
+            self._ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # -- state
+    def init_state(self, y0=1.0):
+        self._check(self._lib.ipm_init_state(self._h, float(y0)))
+
+    def _rows_in(self, v):          # caller's row order -> device row order
+        return v if self._perm is None else np.ascontiguousarray(v[self._perm])
+
+    def _rows_out(self, v):         # device row order -> caller's row order
+        if self._perm is None:
+            return v
+        out = np.empty_like(v)
+        out[self._perm] = v
+        return out
+
+    def set_state(self, x, y, s, w=None, z=None):
+        """(w, z): the upper slacks and their duals of a bounded solver (entries outside the bounded set are ignored);
+        None keeps what the solver holds (w = z = 1 on the bounded set after construction or init_state)."""
+        x, y, s = _col(x, self.n, "x"), self._rows_in(_col(y, self.m, "y")), _col(s, self.n, "s")
+        if (w is None) != (z is None):
+            raise ValueError("give both w and z or neither")
+        if w is not None:
+            if not self.bounded:
+                raise ValueError("w / z given but the solver has no finite upper bound")
+            w, z = _col(w, self.n, "w"), _col(z, self.n, "z")
+        self._check(self._lib.ipm_set_state(self._h, _dptr(x), _dptr(y), _dptr(s)))
+        if w is not None:
+            self._check(self._lib.ipm_set_bound_state(self._h, _dptr(w), _dptr(z)))
+
+    def get_bound_state(self):
+        """(w, z) of a bounded solver as (n, 1) arrays (0 outside the bounded set); None without bounds."""
+        if not self.bounded:
+            return None
+        w, z = np.empty(self.n), np.empty(self.n)
+        self._check(self._lib.ipm_get_bound_state(self._h, _dptr(w), _dptr(z)))
+        return w.reshape(-1, 1), z.reshape(-1, 1)
+
+    def get_state(self):
+        x, y, s = np.empty(self.n), np.empty(self.m), np.empty(self.n)
+        self._check(self._lib.ipm_get_state(self._h, _dptr(x), _dptr(y), _dptr(s)))
+        return x.reshape(-1, 1), self._rows_out(y).reshape(-1, 1), s.reshape(-1, 1)
+
+    # -- seams
+    def newton_direction(self, corrector=False):
+        dx, dy, ds = np.empty(self.n), np.empty(self.m), np.empty(self.n)
+        st = _lib.Stats()
+        self._check(self._lib.ipm_newton_direction(self._h, 1 if corrector else 0, _dptr(dx), _dptr(dy),
+                                                   _dptr(ds), C.byref(st)))
+        self.stats = st.as_dict()
+        return dx.reshape(-1, 1), self._rows_out(dy).reshape(-1, 1), ds.reshape(-1, 1)
+
+    def iterate(self, n_steps):
+        st = _lib.Stats()
+        self._check(self._lib.ipm_iterate(self._h, int(n_steps), C.byref(st)))
+        self.stats = st.as_dict()
+        return self.stats
+
+    def solve(self, tol=1e-8, max_iter=5000, tol_gap=None):
+        st = _lib.Stats()
+        self._check(self._lib.ipm_solve(self._h, float(tol), float(tol), _gap_tol(tol, tol_gap), int(max_iter), C.byref(st)))
+        self.stats = st.as_dict()
+        return self.stats
+
+    def history(self):
+        """Per-iteration records of the last solve()/iterate() (oldest first; the most recent 1024): list of dicts
+        with k, objective, rp_norm, rd_norm, gap, mu, sigma, alpha_aff_p/d, alpha_p/d, pivots_fixed -- the line the
+        reference prints per iteration (main.py:808-809, :1186)."""
+        buf = (_lib.IterRecord * _lib.HISTORY_CAPACITY)()
+        n = C.c_int32(0)
+        self._check(self._lib.ipm_get_history(self._h, buf, _lib.HISTORY_CAPACITY, C.byref(n)))
+        return [{k: getattr(buf[i], k) for k, _ in _lib.IterRecord._fields_} for i in range(n.value)]
+
+    def certificate(self):
+        """The certificate of the last solve when it ended in status 5 (primal infeasible) or 6 (dual infeasible, i.e.
+        unbounded), else None: dict with kind ("primal_infeasible" / "dual_infeasible"), y (length m, the caller's row order),
+        z and x (length n), normalization (beta = b.y - u.z, or gamma = -c.x), violation (of the normalised certificate, as the
+        device measured it) and k (iteration of the detection).  Kind 5: A^T y - z <= violation, z >= 0, b.y - u.z = 1 (x = 0);
+        kind 6: x >= 0, ||A x||_inf <= violation, c.x = -1 (y = z = 0).  verify_certificate() checks one from the data."""
+        if self.stats is None or self.stats["status"] not in (_lib.STATUS_PRIMAL_INFEASIBLE, _lib.STATUS_DUAL_INFEASIBLE):
+            return None
+        y, z, x, info = np.empty(self.m), np.empty(self.n), np.empty(self.n), np.empty(4)
+        self._check(self._lib.ipm_get_certificate(self._h, _dptr(y), _dptr(z), _dptr(x), _dptr(info)))
+        return {"kind": STATUS_NAMES[int(info[0])], "y": self._rows_out(y), "z": z, "x": x,
+                "normalization": float(info[1]), "violation": float(info[2]), "k": int(info[3])}
+
+    def schedule(self):
+        """How the handle runs its factorization (ipm_get_schedule): dict for tests and diagnostics."""
+        out = (C.c_int32 * 12)()
+        self._check(self._lib.ipm_get_schedule(self._h, out))
+        keys = ("blocks", "group_steps", "grouped_trsv", "device_polling", "counter_steps", "event_steps", "envelope",
+                "live_handles", "timeouts_recovered", "fused_small", "fused_factor", "sparse_level_mode")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def factor_info(self):
+        """Structure of the sparse factor (ipm_get_factor_info) or None for the dense-tile path."""
+        if self.factor != "sparse":
+            return None
+        out = (C.c_int64 * 8)()
+        self._check(self._lib.ipm_get_factor_info(self._h, out))
+        keys = ("panels", "tasks", "height", "widest_front", "factor_entries", "update_entries", "product_terms",
+                "serial_launches")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def set_profiling(self, level=2):
+        """0 off, 1 time the A D^2 A^T kernel only, 2 all phases (True == 2 for old callers)."""
+        level = 2 if level is True else (0 if level is False else int(level))
+        self._check(self._lib.ipm_set_profiling(self._h, level))
+
+    def phase_ms(self):
+        out = (C.c_double * 4)()
+        self._check(self._lib.ipm_get_phase_ms(self._h, out))
+        return dict(form=out[0], factor=out[1], trisolve=out[2], other=out[3])
+
+    # -- kernel-level
+    def form_normal_matrix(self, d):
+        d = _col(d, self.n, "d")
+        B = np.empty((self.m, self.m))
+        self._check(self._lib.ipm_form_normal_matrix(self._h, _dptr(d), _dptr(B), self.m))
+        if self._perm is not None:
+            out = np.empty_like(B)
+            out[np.ix_(self._perm, self._perm)] = B
+            return out
+        return B
+
+    def get_factor(self):
+        """Lower Cholesky factor of the current normal matrix in DEVICE row order (rows self._perm of the caller's
+        A when a reordering was applied)."""
+        L = np.empty((self.m, self.m))
+        self._check(self._lib.ipm_get_factor(self._h, _dptr(L), self.m))
+        return L
+
+    def normal_solve(self, rhs, d=None, reuse_factor=False):
+        """z with (A diag(d) A^T) z = rhs on the device (d = None: ones); reuse_factor keeps the previous factor."""
+        rhs = self._rows_in(_col(rhs, self.m, "rhs"))
+        z = np.empty(self.m)
+        dptr = None if d is None else _dptr(_col(d, self.n, "d"))
+        nfix = C.c_int32(0)
+        self._check(self._lib.ipm_normal_solve(self._h, dptr, _dptr(rhs), _dptr(z), 1 if reuse_factor else 0, C.byref(nfix)))
+        self.last_pivots_fixed = nfix.value          # > 0 with d = 1: A A^T is singular, i.e. A has dependent rows
+        return self._rows_out(z)
+
+    def mehrotra_start(self):
+        """Mehrotra's starting point (SIAM J. Optim. 2 (1992) 575-601, section 7): least-squares x and (y, s), shifted
+        into the positive orthant and balanced.  NOT the reference's start (x = s = 1, sparse_interior.py:193-200): an
+        optional mode that changes the trajectory; two solves with A A^T on the device, the rest is
+        O(nnz) host arithmetic."""
+        A, b, c = self._host
+        x = A.T @ self.normal_solve(b)
+        y = self.normal_solve(A @ c, reuse_factor=True)
+        s = c - A.T @ y
+        x = np.asarray(x).ravel(); s = np.asarray(s).ravel()
+        if self.bounded:
+            return self._mehrotra_start_bounded(x, np.asarray(y).ravel(), s)
+        x = x + max(-1.5 * x.min(), 0.0)
+        s = s + max(-1.5 * s.min(), 0.0)
+        xs = 0.5 * float(x @ s)
+        if not (np.isfinite(xs) and s.sum() > 0 and x.sum() > 0 and xs > 0):
+            return np.ones(self.n), np.ones(self.m), np.ones(self.n)          # degenerate data: the reference's start
+        x = x + xs / s.sum()
+        s = s + xs / x.sum()
+        return x, np.asarray(y).ravel(), s
+
+    def _mehrotra_start_bounded(self, x, y, r):
+        """Mehrotra's recipe extended to 0 <= x <= u -> (x, y, s, w, z): w = u - x; on U the reduced cost r = c - A^T y splits
+        into s = max(r, 0), z = max(-r, 0) (so s - z = r); (x, w) and (s, z) are shifted into the positive orthant together
+        and balanced with x.s + w.z.  Outside U, w = z = 0 and s = r as in the unbounded recipe."""
+        U = np.isfinite(self.ub)
+        w = np.zeros(self.n); z = np.zeros(self.n)
+        w[U] = self.ub[U] - x[U]
+        s = r.copy()
+        s[U] = np.maximum(r[U], 0.0)
+        z[U] = np.maximum(-r[U], 0.0)
+        xmin = min(x.min(), w[U].min())
+        smin = min(s.min(), z[U].min())
+        dp, dd = max(-1.5 * xmin, 0.0), max(-1.5 * smin, 0.0)
+        x = x + dp; w[U] += dp
+        s = s + dd; z[U] += dd
+        xs = 0.5 * float(x @ s + w[U] @ z[U])
+        sx, ss = float(x.sum() + w[U].sum()), float(s.sum() + z[U].sum())
+        if not (np.isfinite(xs) and ss > 0 and sx > 0 and xs > 0):
+            w[U], z[U] = 1.0, 1.0
+            return np.ones(self.n), np.ones(self.m), np.ones(self.n), w, z          # degenerate data: the reference's start
+        x = x + xs / ss; w[U] += xs / ss
+        sx = float(x.sum() + w[U].sum())                 # (after the primal correction, as in the unbounded recipe)
+        s = s + xs / sx; z[U] += xs / sx
+        return x, y, s, w, z
+
+    def solve_linear(self, B, rhs):
+        """B z = rhs for the CALLER's dense SPD matrix (main.py:176-182): the row order this handle keeps its own A in
+        plays no part (ipm_solve_linear factors B as given, without the tile envelope or the sparse factor)."""
+        B = np.ascontiguousarray(np.asarray(B, dtype=np.float64))
+        rhs = _col(rhs, self.m, "rhs")
+        z = np.empty(self.m)
+        nfix = C.c_int32(0)
+        self._check(self._lib.ipm_solve_linear(self._h, _dptr(B), self.m, _dptr(rhs), _dptr(z), C.byref(nfix)))
+        return z.reshape(-1, 1), nfix.value

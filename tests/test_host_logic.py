@@ -147,6 +147,62 @@ def test_bench_netlib_helpers():
     assert len(B.kernel_source_sha()) == 16
 
 
+def _netlib(golden_dir, name):
+    A, b, c, cTlb, valid = matio.load_npz_problem(os.path.join(golden_dir, "netlib", name + ".npz"))
+    return A, b, c
+
+
+def test_prepare_and_path_flops_take_the_same_path(golden_dir):
+    """The solve (prepare) and the roofline denominator (path_flops) read the factorization path from one rule: AFIRO (27 rows, the
+    fused small-LP kernel: never the sparse factor) and STOCFOR2 (2157 rows: "auto" takes the sparse factor)."""
+    from interiorpointmethod_amd import solver as S
+    small, large = _netlib(golden_dir, "AFIRO"), _netlib(golden_dir, "STOCFOR2")
+    assert small[0].shape[0] <= S.FUSED_SMALL_MAX_ROWS and large[0].shape[0] >= 600
+    for factor in ("auto", "dense"):
+        for A, b, c in (small, large):
+            assert S.prepare(A, b, c, factor=factor).factor == S.path_flops(A, factor=factor)[0], (factor, A.shape)
+    assert S.prepare(*small, factor="auto").factor == "dense" and S.prepare(*large, factor="auto").factor == "sparse"
+    assert S.prepare(*large, factor="sparse").factor == S.path_flops(large[0], factor="sparse")[0] == "sparse"
+
+
+@pytest.mark.parametrize("name,expected", [("STOCFOR2", 406148437.3333334),       # the envelope pays after the RCM order (m^3/3 = 3.3e9)
+                                           ("SCTAP3", 884998143.9999999),         # the envelope pays as the rows stand
+                                           ("SHELL", 245438109.0)])               # it does not: m^3/3
+def test_factor_flops_values(golden_dir, name, expected):
+    """factor_flops to the last bit: the numbers of the hand-written envelope sum it held before it shared _tile_envelope_work's."""
+    from interiorpointmethod_amd.solver import factor_flops
+    A = _netlib(golden_dir, name)[0]
+    assert factor_flops(A) == expected
+    assert (expected == A.shape[0] ** 3 / 3.0) == (name == "SHELL")
+
+
+def test_solver_reexports_every_name_its_callers_use():
+    """bench.py, tests/, tools/ and general_form.py reach these names through `solver`: each is the owning module's own object."""
+    from interiorpointmethod_amd import analysis, api, batches, handle, kkt, solver
+    import interiorpointmethod_amd as ipm
+    owners = {
+        analysis: ("FUSED_SMALL_MAX_ROWS", "REORDER_MIN_ROWS", "SPARSE_FACTOR_MIN_ROWS", "Prepared", "prepare", "path_flops", "factor_flops",
+                   "envelope_row_order", "sparse_factor_order", "prefer_sparse_factor", "dense_tile_ms", "_tile_envelope_work",
+                   "_worth_ordering", "_col", "_upper_bounds"),
+        handle: ("IpmSolver", "STATUS_NAMES", "_dptr"),
+        batches: ("LockstepBatch", "solve_lockstep", "lockstep_eligible", "small_batch_eligible", "solve_small_batch_solvers",
+                  "solve_small_batch", "_small_batch_host_check"),
+        api: ("solve", "solve_with_info", "last_info", "interior", "interior_sparse", "verify_certificate", "_info", "_verdict"),
+        kkt: ("direction_predicted_sparse", "direction_corrected_sparse", "direction_predicted", "direction_corrected", "solve_linear",
+              "lu_solve", "lu_factor", "_kkt_matrix", "_kkt_residuals", "_kkt_solve", "_kkt_predicted", "_kkt_corrected", "_dense",
+              "_ratio", "_METHODS", "_square", "_lu_error"),
+    }
+    for owner, names in owners.items():
+        for nm in names:
+            assert hasattr(solver, nm), nm
+            assert getattr(solver, nm) is getattr(owner, nm), nm
+    listed = set(sum(owners.values(), ()))
+    for nm in ipm.__all__:                      # what the package exports from solver is the same object too
+        if nm in listed:
+            assert getattr(ipm, nm) is getattr(solver, nm), nm
+    assert {"IpmSolver", "LockstepBatch", "solve", "solve_with_info", "verify_certificate", "lu_solve", "solve_small_batch"} <= set(ipm.__all__)
+
+
 def test_prepare_is_host_only(golden_dir):
     """solver.prepare -- the host analysis IpmSolver does before it touches the device: no device needed; STOCFOR2 goes to the
     sparse factor with a minimum-degree row order, AFIRO (27 rows) stays dense and unpermuted, a dense ndarray passes through."""

@@ -9,7 +9,7 @@ import pytest
 from scipy import sparse
 
 import interiorpointmethod_amd as ipm
-from interiorpointmethod_amd import _lib, solver
+from interiorpointmethod_amd import _lib, kkt, solver
 from oracle import ipm_oracle as O
 
 
@@ -43,7 +43,7 @@ def test_kkt_assembly_sums_duplicates():
 def test_kkt_rhs_reproduces_reference_full_with_lapack(golden_dir, name, monkeypatch):
     """The assembled systems (matrix + predictor / corrector right-hand sides), solved by CPU LAPACK in place of the
     device LU, give the reference's method="full" directions of the fixture at k = 0 and the middle iterate."""
-    monkeypatch.setattr(solver, "lu_solve", lambda K, rhs, device=0: np.linalg.solve(K, rhs))
+    monkeypatch.setattr(kkt, "lu_solve", lambda K, rhs, device=0: np.linalg.solve(K, rhs))
     z, A = _kat(golden_dir, name)
     b, c = z["b"], z["c"]
     for k in (int(z["iters"][0]), int(z["iters"][1])):

@@ -10,7 +10,7 @@ import pytest
 from scipy import sparse
 
 import interiorpointmethod_amd as ipm
-from interiorpointmethod_amd import _lib, solver
+from interiorpointmethod_amd import _lib, batches
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -52,7 +52,7 @@ def test_more_than_128_rows_is_refused_on_the_host(monkeypatch):
     """The host check runs before any handle exists: IpmSolver is never constructed."""
     def no_device(*a, **k):
         raise AssertionError("a handle was created before the host check refused the batch")
-    monkeypatch.setattr(solver, "IpmSolver", no_device)
+    monkeypatch.setattr(batches, "IpmSolver", no_device)
     rng = np.random.default_rng(0)
     ok = (sparse.random(20, 40, density=0.3, random_state=1, format="csc") + sparse.eye(20, 40, format="csc"), np.ones(20), np.ones(40))
     big = (rng.standard_normal((129, 300)), np.ones(129), np.ones(300))
