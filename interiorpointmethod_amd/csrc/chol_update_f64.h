@@ -13,15 +13,13 @@
 #include <stdint.h>
 #include "adat_syrk_f64.h"
 #include "gemm_nt_f64.h"
+#include "handoff.h"
 
 namespace ipm {
 
 __device__ __forceinline__ void chol_update_kernel_body(GemmNT g, const unsigned bx_, const unsigned gx_) {
     constexpr int BM = 128, BK = 16, LDT = BK + 2, RSTEP = 32;
-    if (g.done && *g.done) {
-        if (g.signal && threadIdx.x == 0) __hip_atomic_fetch_add(g.signal, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
+    if (handoff_skipped(g.done, g.signal)) return;
     __shared__ __attribute__((aligned(16))) double lds[2 * (BM + BM) * LDT];
     double* Ps = lds;                           // [2][128][LDT]
     double* Qs = lds + 2 * BM * LDT;            // [2][128][LDT]
@@ -165,13 +163,8 @@ __device__ __forceinline__ void chol_update_kernel_body(GemmNT g, const unsigned
             for (int q = 0; q < 4; ++q)
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2_t, (double)acc[i][j][q]), rC, voffC, ((i * 16 + 4 * q) * ldc + j * 16) * 8, 0);
     if (g.signal) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_add(g.signal, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        handoff_publish_begin();
+        if (threadIdx.x == 0) __hip_atomic_fetch_add(g.signal, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 __global__ __launch_bounds__(256, 2) void chol_update_kernel(GemmNT g) { chol_update_kernel_body(g, blockIdx.x, gridDim.x); }

@@ -59,6 +59,32 @@ constexpr int FF_MAX_NBLK = 96;
 #endif
 FF_HD inline int ff_tile(int i, int c) { return i * (i + 1) / 2 + c; }
 
+// The hand-off words of the fused launch (ipm_handle::d_ff_flags, zeroed per launch), by word offset -- the ONE statement of the
+// layout: the host (ff_build, enqueue_form_factor, ff_dump_handoffs) and the device (the snapshot of ff_wait_ge) address them through
+// it.  The fixed part; then five arrays sized by nblk (ntile = nblk (nblk + 1) / 2).  A second copy of `count` words behind the live
+// ones takes the diagnostic snapshot.
+struct FFWords {
+    static constexpr unsigned ticket = 0;      // next item of the work list
+    static constexpr unsigned role = 3;        // next role (claimed by arrival)
+    static constexpr unsigned maxbits = 8;     // TWO words, 8-byte aligned: max diag(B) as the bit pattern of a non-negative double
+    static constexpr unsigned dcount = 10;     // FF_D items complete
+    static constexpr unsigned dbg = 24;        // [8] the diagnostic record of the first wait that gave up (handoff.h: HD_*)
+    static constexpr unsigned dbg_end = 32;
+    static constexpr unsigned fcount = 32;     // [ntile] formation chunks complete
+    size_t tprog;                              // [ntile] T items complete (sequence number)
+    size_t lfinal;                             // [nblk] 4 x leading tiles of row r that are final L
+    size_t dready;                             // [nblk] diagonal tile k ready for potrf_diag
+    size_t potrfdone;                          // [nblk] diagonal block k factored, inv(L_kk) written
+    size_t count;                              // words in all
+    FF_HD explicit FFWords(int nblk) {
+        const size_t ntile = (size_t)nblk * ((size_t)nblk + 1) / 2;
+        tprog = fcount + ntile; lfinal = tprog + ntile; dready = lfinal + (size_t)nblk; potrfdone = dready + (size_t)nblk;
+        count = potrfdone + (size_t)nblk;
+    }
+    // first live word, from the address of the diagnostic record
+    FF_HD static const unsigned* base_of_dbg(const unsigned* dbg_words) { return dbg_words - dbg; }
+};
+
 struct FFModel {                       // durations in microseconds, calibrated on an item trace of the launch itself (MI355X, 512-thread
                                        // workgroups, one per CU; tools/ff_trace.py -> profiles/r04_ff_item_trace_roles_kernel.txt: the
                                        // replay of the list under these values, tools/ff_replay.py, ends at 3347 us, the launch it

@@ -14,8 +14,8 @@
 //     of tiles, partial sums to slabs) interleaved with update / panel-solve items of the factorization, in the start order of a
 //     bottom-level list scheduling of the item DAG.  Formation commutes with the updates (tile = sum of slabs - sum_j L_ij
 //     L_cj^T), so the trailing updates do not wait for the formation.
-// Hand-offs between the roles are device counters under the agent-scope release / acquire protocol of gemm_nt_f64.h; every
-// spin is bounded (time-out word -> the host rolls the call back and repeats it on the serial path).
+// Hand-offs between the roles are device counters under the agent-scope release / acquire protocol of handoff.h (the words:
+// FFWords, ff_schedule.h); every spin is bounded (time-out word -> the host rolls the call back and repeats it on the serial path).
 //
 // GEMM engines (8 waves, v_mfma_f64_16x16x4_f64): ff_gemm_pair for the formation -- 256 x 128 per workgroup, waves 4 (M) x 2 (N),
 // BK = 16 stages on the schedule of adat_syrk_kernel (0.87 of the fp64 MFMA peak standalone, tools/ff_gemm_bench.hip);
@@ -31,6 +31,7 @@
 
 #include "ff_schedule.h"
 #include "gemm_nt_f64.h"
+#include "handoff.h"
 #include "potrf_f64.h"
 
 namespace ipm {
@@ -66,26 +67,17 @@ struct FFArgs {
     unsigned* dcount;                  // FF_D items complete
 };
 
-// dbg (optional, 8 words, zeroed per launch): the FIRST wait of the launch that gave up records {1, item, kind, target, seen}
+// The waits of the fused launch (timeout is never null).  dbg (optional, zeroed per launch): the FIRST wait of the launch that gave
+// up records {1, item, kind, target, seen} and, with nw > 0, takes a snapshot of the nw hand-off words BEFORE the time-out word
+// releases the other waiters (the copy sits right behind the live words).
 __device__ __forceinline__ void ff_wait_ge(const unsigned* p, unsigned v, unsigned* timeout, unsigned* dbg = nullptr, unsigned item = 0,
                                            unsigned kind = 0, unsigned nw = 0) {
-    unsigned spins = 0;
-    while (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) {
-        __builtin_amdgcn_s_sleep(2);
-        ++spins;
-        if (spins > ipm_spin_limit || ((spins & 1023u) == 1u && __hip_atomic_load(timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-            if (spins > ipm_spin_limit && dbg && __hip_atomic_fetch_add(dbg, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-                dbg[1] = item; dbg[2] = kind; dbg[3] = v; dbg[4] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                // snapshot of every hand-off word BEFORE the time-out word releases the other waiters (dbg[5] = words, the
-                // copy sits right behind the live words)
-                const unsigned* live = dbg - 24;
-                unsigned* snap = const_cast<unsigned*>(live) + nw;
-                for (unsigned w = 0; w < nw; ++w) snap[w] = __hip_atomic_load(live + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            __hip_atomic_store(timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-        }
-    }
+    (void)handoff_wait<2, false>([=] { return handoff_load(p) >= v; }, {timeout, dbg}, [=] {
+        handoff_record_ge(dbg, item, kind, v, p);
+        const unsigned* live = FFWords::base_of_dbg(dbg);
+        unsigned* snap = const_cast<unsigned*>(live) + nw;
+        for (unsigned w = 0; w < nw; ++w) snap[w] = handoff_load(live + w);
+    });
 }
 
 // acc += P[128 x 32 ns] * (Q[128 x 32 ns] . w)^T  (both operands k-contiguous rows).  SRC_REGS: the P operand of stage s
@@ -389,18 +381,9 @@ __device__ __forceinline__ void ff_gemm_pair(const double* __restrict__ P0, cons
     __syncthreads();
 }
 
-// Hand-off of a tile / slab to workgroups on other CUs and XCDs: plain stores, every storing wave drains its stores, the
-// workgroup meets, ONE lane releases at agent scope (L2 write-back) and the caller's lane 0 then bumps the counters;
-// consumers poll, take one agent-scope acquire and read with plain loads.  (Measured and dropped in round 3: write-through
+// Hand-off of a tile / slab to workgroups on other CUs and XCDs: handoff_publish_begin, then lane 0 bumps the counters; consumers
+// poll (ff_wait_ge), take one handoff_acquire and read with plain loads.  (Measured and dropped in round 3: write-through
 // sc1 stores without the release -- 8-byte write-through stores from the MFMA layout cost more than the one fence.)
-__device__ __forceinline__ void ff_publish_begin() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-}
 
 // ------------------------------------------------------------------------------------------------------------------------
 // The PIVOT CHAIN as a ROLE of the persistent launch: the first workgroup to arrive factors the diagonal
@@ -426,9 +409,8 @@ __device__ __forceinline__ void ff_chain_role(const FFChain& c, double* lds) {
     double* maxdiag_p = dinv_s + NB;
     const int tid = threadIdx.x;
     if (tid == 0) {
-        ff_wait_ge(c.dcount, (unsigned)c.nblk, c.timeout, c.dbg, 9000u, 8, 0);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ff_wait_ge(c.dcount, (unsigned)c.nblk, c.timeout, c.dbg, 9000u, HK_DCOUNT, 0);
+        handoff_acquire();
         const double mx = __longlong_as_double((long long)__hip_atomic_load(c.maxbits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         *maxdiag_p = mx;
         *c.maxdiag_out = mx;
@@ -479,10 +461,9 @@ __device__ __forceinline__ void ff_crit_role(const FFCrit& c, const int strip, d
         if (tr) tr[4] = (long long)wall_clock64();
         if (tid == 0) {
             const int t = ff_tile(k + 1, k);
-            ff_wait_ge(c.tprog + t, (unsigned)c.tile_items[t], c.timeout, c.dbg, 1000u + (unsigned)k, 6, 0);
-            ff_wait_ge(c.potrfdone + k, 1u, c.timeout, c.dbg, 1000u + (unsigned)k, 6, 0);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            ff_wait_ge(c.tprog + t, (unsigned)c.tile_items[t], c.timeout, c.dbg, 1000u + (unsigned)k, HK_GEMM, 0);
+            ff_wait_ge(c.potrfdone + k, 1u, c.timeout, c.dbg, 1000u + (unsigned)k, HK_GEMM, 0);
+            handoff_acquire();
         }
         __syncthreads();
         if (tr) tr[5] = (long long)wall_clock64();
@@ -492,10 +473,9 @@ __device__ __forceinline__ void ff_crit_role(const FFCrit& c, const int strip, d
         if (tr) { tr[6] = (long long)wall_clock64(); tr[8] = tr[6]; }
         if (tid == 0) {
             const int t = ff_tile(k + 1, k + 1);
-            ff_wait_ge(c.lfinal + (k + 1), 4u * (unsigned)(k + 1), c.timeout, c.dbg, 2000u + (unsigned)k, 6, 0);
-            ff_wait_ge(c.tprog + t, (unsigned)c.tile_items[t], c.timeout, c.dbg, 2000u + (unsigned)k, 6, 0);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            ff_wait_ge(c.lfinal + (k + 1), 4u * (unsigned)(k + 1), c.timeout, c.dbg, 2000u + (unsigned)k, HK_GEMM, 0);
+            ff_wait_ge(c.tprog + t, (unsigned)c.tile_items[t], c.timeout, c.dbg, 2000u + (unsigned)k, HK_GEMM, 0);
+            handoff_acquire();
         }
         __syncthreads();
         if (tr) tr[9] = (long long)wall_clock64();
@@ -589,7 +569,7 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles&
                 mx = (sacc > mx) ? sacc : mx;            // NaN never wins
             }
             if (lane == 0) atomicMax(g.maxbits, (unsigned long long)__double_as_longlong(mx));
-            ff_publish_begin();
+            handoff_publish_begin();
             if (tid == 0) __hip_atomic_fetch_add(g.dcount, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             FF_TRACE(2);
             continue;
@@ -629,7 +609,7 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles&
                                 *reinterpret_cast<f64x2*>(sb + ((i * 4 + j) * 2 + hq) * 128) = (f64x2){pacc[i][j][2 * hq], pacc[i][j][2 * hq + 1]};
                 }
             }
-            ff_publish_begin();
+            handoff_publish_begin();
             if (tid == 0) {
                 if (up) __hip_atomic_fetch_add(g.fcount + ff_tile(ti, tc), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (lo) __hip_atomic_fetch_add(g.fcount + ff_tile(ti + 1, tc), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -649,14 +629,13 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles&
         const int j0 = it.t.j0, j1 = it.t.j1;
         const int flags = it.t.flags, seq = it.t.seq;
         if (tid == 0) {
-            if (flags & FF_ADD_BASE) ff_wait_ge(g.fcount + tile, (unsigned)g.tile_q[tile], g.timeout, g.dbg, n, 1, g.dbg_words);
-            if (!(flags & FF_INIT)) ff_wait_ge(g.tprog + tile, (unsigned)seq - 1u, g.timeout, g.dbg, n, 2, g.dbg_words);
+            if (flags & FF_ADD_BASE) ff_wait_ge(g.fcount + tile, (unsigned)g.tile_q[tile], g.timeout, g.dbg, n, HK_FCOUNT, g.dbg_words);
+            if (!(flags & FF_INIT)) ff_wait_ge(g.tprog + tile, (unsigned)seq - 1u, g.timeout, g.dbg, n, HK_TPROG, g.dbg_words);
             if (j1 > j0) {
-                ff_wait_ge(g.lfinal + ti, 4u * (unsigned)j1, g.timeout, g.dbg, n, 3, g.dbg_words);
-                if (tc != ti) ff_wait_ge(g.lfinal + tc, 4u * (unsigned)j1, g.timeout, g.dbg, n, 4, g.dbg_words);
+                ff_wait_ge(g.lfinal + ti, 4u * (unsigned)j1, g.timeout, g.dbg, n, HK_LFINAL_ROW, g.dbg_words);
+                if (tc != ti) ff_wait_ge(g.lfinal + tc, 4u * (unsigned)j1, g.timeout, g.dbg, n, HK_LFINAL_COL, g.dbg_words);
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            handoff_acquire();
         }
         __syncthreads();
         FF_PROF(FFP_TWAIT);
@@ -717,9 +696,8 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles&
         if (flags & FF_PANEL) {
             // L(ti,tc) = tile inv(L(tc,tc))^T: the tile goes back through LDS stage by stage as the P operand
             if (tid == 0) {
-                ff_wait_ge(g.potrfdone + tc, 1u, g.timeout, g.dbg, n, 5, g.dbg_words);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                ff_wait_ge(g.potrfdone + tc, 1u, g.timeout, g.dbg, n, HK_POTRFDONE, g.dbg_words);
+                handoff_acquire();
             }
             __syncthreads();
             FF_PROF(FFP_PWAIT);
@@ -740,7 +718,7 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles&
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) bt[(int64_t)(i * 16 + 4 * q) * g.ldb + j * 16] = val[i][j][q];
-        ff_publish_begin();
+        handoff_publish_begin();
         if (tid == 0) {
             __hip_atomic_store(g.tprog + tile, (unsigned)seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (flags & FF_PANEL) __hip_atomic_fetch_add(g.lfinal + ti, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -773,7 +751,7 @@ __global__ __launch_bounds__(64) void ff_gate_kernel(const unsigned* flag, unsig
     if (done && *done) return;
     if (threadIdx.x == 0) {
         ff_wait_ge(flag, value, timeout);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        handoff_acquire<false>();
     }
 }
 

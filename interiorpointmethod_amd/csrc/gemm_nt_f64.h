@@ -25,12 +25,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace ipm {
+#include "handoff.h"
 
-// Bound of every device-side hand-off spin (polls of ~0.2 us: about 0.7 s).  A wait that runs into it sets the handle's time-out
-// word; the host rolls the call back and repeats it on a path that does not poll.  TEST KNOB: the environment variable
-// IPM_TEST_SPIN_LIMIT (read at ipm_create) lowers it so that the recovery paths can be driven on purpose (tests only).
-__device__ unsigned ipm_spin_limit = 1u << 22;
+namespace ipm {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
@@ -59,12 +56,12 @@ struct GemmNT {
     // Cross-stream hand-off without stream events (an event wait costs the pivot chain ~8 us of command-
     // processor time per Cholesky step): a producer launch on another stream bumps *signal once per
     // workgroup after an agent-scope release; a SMALL consumer launch polls *wait_on >= wait_count from one
-    // lane (bounded), then acquires.  Only launches of a few workgroups may wait (no CU starvation).
+    // lane (bounded), then acquires (handoff.h).  Only launches of a few workgroups may wait (no CU starvation).
     unsigned* signal;           // may be null
     const unsigned* wait_on;    // may be null
     unsigned wait_count;
     unsigned* timeout;          // set to 1 when the bounded poll gave up (surfaced as an error by the host)
-    unsigned* dbg; unsigned dbg_tag;   // diagnostic (may be null): the first poll of a call that ran into its bound records {1, tag, 6, target, seen}
+    unsigned* dbg; unsigned dbg_tag;   // diagnostic (may be null): the first poll of a call that ran into its bound records {1, tag, HK_GEMM, target, seen}
     long long* trace;                  // diagnostic (may be null): wall_clock64 of workgroup 0 at {start, inputs ready, done}
 };
 
@@ -80,7 +77,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 // One workgroup's share of the contraction (tile picked from bx; by, bz = batch indices); lds: 2 (BM + BN)(BK + 2) doubles.
-// The body of gemm_nt_f64_kernel, and of the persistent critical-step launch of the fused factorization (ff_crit_kernel).
+// The body of gemm_nt_f64_kernel, and of the critical products of the fused factorization (ff_crit_role, form_factor.h).
 template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, bool SCALE>
 __device__ __forceinline__ void gemm_nt_body(const GemmNT& g, const int bx, const int by, const int bz, double* lds) {
     constexpr bool STORE_EARLY = false;   // measured: writing the next stage before the last k-step is slower (54 vs 60 TFLOP/s)
@@ -247,13 +244,8 @@ __device__ __forceinline__ void gemm_nt_body(const GemmNT& g, const int bx, cons
                 cbase[(int64_t)(i * 16 + 4 * q) * g.ldc + j * 16] = v;
             }
     if (g.signal) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every storing wave drains its stores
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_add(g.signal, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        handoff_publish_begin();
+        if (threadIdx.x == 0) __hip_atomic_fetch_add(g.signal, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (g.trace && threadIdx.x == 0 && bx == 0) g.trace[2] = (long long)wall_clock64();
 }
@@ -261,33 +253,13 @@ __device__ __forceinline__ void gemm_nt_body(const GemmNT& g, const int bx, cons
 template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, bool SCALE>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N) / 2 < 2 ? 1 : 2)   // (<= two waves per SIMD: the register budget of the tiles)
 void gemm_nt_f64_kernel(GemmNT g) {
-    if (g.done && *g.done) {
-        // a skipped producer still signals: the stop test may flip `done` while a factorization is in flight (it runs
-        // on the residual stream), and a consumer that passed its own check must not spin on a counter nobody bumps
-        if (g.signal && threadIdx.x == 0) __hip_atomic_fetch_add(g.signal, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
+    if (handoff_skipped(g.done, g.signal)) return;
     if (g.trace && threadIdx.x == 0 && blockIdx.x == 0) g.trace[0] = (long long)wall_clock64();
     if (g.wait_on) {
+        // (a wait that gives up does not hang: the host rolls the call back and repeats it with stream events)
         if (threadIdx.x == 0) {
-            unsigned spins = 0;
-            while (__hip_atomic_load(g.wait_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < g.wait_count) {
-                __builtin_amdgcn_s_sleep(4);
-                ++spins;
-                // give up (no hang; the host rolls the call back and repeats it with stream events): after ~1 s of
-                // waiting, or at once when an earlier poll of this call already gave up
-                if (spins > ipm_spin_limit || ((spins & 1023u) == 1u && g.timeout &&
-                                           __hip_atomic_load(g.timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-                    if (spins > ipm_spin_limit && g.dbg && __hip_atomic_fetch_add(g.dbg, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-                        g.dbg[1] = g.dbg_tag; g.dbg[2] = 6u; g.dbg[3] = g.wait_count;
-                        g.dbg[4] = __hip_atomic_load(g.wait_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    if (g.timeout) __hip_atomic_store(g.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    break;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            (void)handoff_wait_ge<4, true>(g.wait_on, g.wait_count, {g.timeout, g.dbg}, g.dbg_tag, HK_GEMM);
+            handoff_acquire();
         }
         __syncthreads();
     }

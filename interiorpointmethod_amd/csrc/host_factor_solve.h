@@ -142,7 +142,7 @@ static int enqueue_factor(ipm_handle* h, bool use_env = false, int mid_step = -1
         h->sp_fwd_fused = sp_fwd_rhs;
         const unsigned ep = ++h->sp_epoch;
         sp_walk(h, sp_level(h), /*leaves_first=*/true, [&](unsigned grid, const SpRec* recs, int count) {
-            hipLaunchKernelGGL((sp_chol_kernel<SPC_THREADS, false>), dim3(grid), dim3(SPC_THREADS), h->sp_lds_chol, h->stream, h->spF, ep,
+            hipLaunchKernelGGL((sp_chol_kernel<SPC_THREADS>), dim3(grid), dim3(SPC_THREADS), h->sp_lds_chol, h->stream, h->spF, ep,
                                &h->sc->maxdiag, h->opt.pivot_guard_eps, h->opt.pivot_guard_big, h->shift_rel, &h->sc->fixed,
                                h->sp_lds_doubles, recs, count, sp_fwd_rhs, h->t2, h->sp_fv_off);
         });
@@ -382,11 +382,11 @@ static int enqueue_potrs(ipm_handle* h, double* r, double* out, hipEvent_t wait_
         h->sp_fwd_fused = nullptr;
         const bool by_level = sp_level(h);                  // (evaluated once for both sweeps)
         if (!fwd_done) sp_walk(h, by_level, /*leaves_first=*/true, [&](unsigned grid, const SpRec* recs, int count) {
-            hipLaunchKernelGGL((sp_fwd_kernel<SPC_THREADS, false>), dim3(grid), dim3(SPC_THREADS), h->sp_lds_solve, h->stream, h->spF, ep, r, h->t2, rm, recs, count);
+            hipLaunchKernelGGL((sp_fwd_kernel<SPC_THREADS>), dim3(grid), dim3(SPC_THREADS), h->sp_lds_solve, h->stream, h->spF, ep, r, h->t2, rm, recs, count);
         });
         if (!by_level) ep = ++h->sp_epoch;                   // the level-mode sweeps share one epoch, task mode takes one per sweep
         sp_walk(h, by_level, /*leaves_first=*/false, [&](unsigned grid, const SpRec* recs, int count) {
-            hipLaunchKernelGGL((sp_bwd_kernel<SPC_THREADS, false>), dim3(grid), dim3(SPC_THREADS), 0, h->stream, h->spF, ep, h->t2, out, recs, count);
+            hipLaunchKernelGGL((sp_bwd_kernel<SPC_THREADS>), dim3(grid), dim3(SPC_THREADS), 0, h->stream, h->spF, ep, h->t2, out, recs, count);
         });
         HIP_TRY(h, hipGetLastError());
         return IPM_OK;

@@ -66,7 +66,7 @@ static int ff_build(ipm_handle* h) {
     HIP_TRY(h, dev_malloc(h->device, h->stream, (void**)&h->d_ff_tile_items, sizeof(int) * 2 * ntile));
     HIP_TRY(h, hipMemcpyAsync(h->d_ff_tile_items, h->ff_sched.tile_items.data(), sizeof(int) * ntile, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->d_ff_tile_items + ntile, h->ff_sched.tile_q.data(), sizeof(int) * ntile, hipMemcpyHostToDevice, h->stream));
-    h->ff_flag_words = 32 + 2 * ntile + 3 * (size_t)h->nblk;
+    h->ff_flag_words = FFWords(h->nblk).count;
     HIP_TRY(h, dev_malloc(h->device, h->stream, (void**)&h->d_ff_flags, sizeof(unsigned) * 2 * h->ff_flag_words));     // live words + diagnostic snapshot
     HIP_TRY(h, dev_malloc(h->device, h->stream, (void**)&h->ff_slab, sizeof(double) * ntile * (size_t)h->ff_qmax * 128 * 128));
     if (getenv("IPM_FF_PROF")) {
@@ -110,9 +110,10 @@ static int enqueue_form_factor(ipm_handle* h, hipEvent_t* ev, int mid_step, int 
     const size_t ntile = (size_t)nblk * (nblk + 1) / 2;
     const int* done = factor_done(h);
     hipStream_t sw = h->stream;
-    unsigned* F = h->d_ff_flags;                               // (layout at the field: tools/ff_debug.py decodes by offset)
-    unsigned *ticket = F, *dbg = F + 24, *fcount = F + 32, *tprog = fcount + ntile, *lfinal = tprog + ntile, *dready = lfinal + nblk,
-             *potrfdone = dready + nblk;
+    unsigned* F = h->d_ff_flags;
+    const FFWords W(nblk);
+    unsigned *ticket = F + W.ticket, *dbg = F + W.dbg, *fcount = F + W.fcount, *tprog = F + W.tprog, *lfinal = F + W.lfinal,
+             *dready = F + W.dready, *potrfdone = F + W.potrfdone;
     unsigned* timeout = timeout_word(h);
     h->ff_potrfdone = potrfdone;                               // (the gate of the last group's inverses polls its last word: enqueue_iteration)
     HIP_TRY(h, hipMemsetAsync(F, 0, sizeof(unsigned) * h->ff_flag_words, sw));
@@ -124,7 +125,7 @@ static int enqueue_form_factor(ipm_handle* h, hipEvent_t* ev, int mid_step, int 
     memset(&roles, 0, sizeof roles);
     FFChain& c = roles.chain;
     c.B = h->B; c.ldb = h->mp; c.invD = h->invD;
-    c.maxbits = (const unsigned long long*)(F + 8); c.dcount = F + 10; c.maxdiag_out = &h->sc->maxdiag;
+    c.maxbits = (const unsigned long long*)(F + W.maxbits); c.dcount = F + W.dcount; c.maxdiag_out = &h->sc->maxdiag;
     c.dready = dready; c.potrfdone = potrfdone; c.timeout = timeout; c.dbg = dbg; c.trace = ctrace;
     c.eps = h->opt.pivot_guard_eps; c.big = h->opt.pivot_guard_big; c.shift_rel = h->shift_rel;
     c.fixed = &h->sc->fixed; c.done = done; c.nblk = nblk; c.m = (int)h->m;
@@ -132,7 +133,7 @@ static int enqueue_form_factor(ipm_handle* h, hipEvent_t* ev, int mid_step, int 
     cc.B = h->B; cc.ldb = h->mp; cc.invD = h->invD; cc.tprog = tprog; cc.tile_items = h->d_ff_tile_items;
     cc.potrfdone = potrfdone; cc.lfinal = lfinal; cc.dready = dready; cc.timeout = timeout; cc.dbg = dbg; cc.trace = ctrace;
     cc.done = done; cc.nblk = nblk;
-    roles.role = F + 3;
+    roles.role = F + W.role;
     FFArgs a;
     memset(&a, 0, sizeof a);
     a.A = h->A; a.lda = h->np; a.d = h->d; a.B = h->B; a.ldb = h->mp; a.invD = h->invD; a.slab = h->ff_slab;
@@ -143,7 +144,7 @@ static int enqueue_form_factor(ipm_handle* h, hipEvent_t* ev, int mid_step, int 
     a.trace = h->ff_trace;
     a.prof = h->ff_prof;
     a.tile_q = h->d_ff_tile_items + ntile;
-    a.maxbits = (unsigned long long*)(F + 8); a.dcount = F + 10;
+    a.maxbits = (unsigned long long*)(F + W.maxbits); a.dcount = F + W.dcount;
     a.nblk = nblk; a.Q = h->ff_qmax; a.nstages = (int)(h->np / FF_PBK); a.m = (int)h->m;
     if (ev) HIP_TRY(h, hipEventRecord(ev[1], sw));
     {
@@ -239,18 +240,21 @@ static void ff_dump_profile(ipm_handle* h) {
 static void ff_dump_handoffs(ipm_handle* h) {
     std::vector<unsigned> F(h->ff_flag_words);
     (void)hipMemcpy(F.data(), h->d_ff_flags, sizeof(unsigned) * F.size(), hipMemcpyDeviceToHost);
-    if (F[24] && F[26] < 6) {           // a worker wait gave up first: show the snapshot it took instead of the final state
+    const int nb = h->nblk;
+    const FFWords W(nb);
+    const unsigned* rec = F.data() + W.dbg;                    // the record of the first wait that gave up (handoff.h)
+    const bool worker = rec[HD_COUNT] && rec[HD_KIND] < HK_ROLES;
+    if (worker) {                       // a worker wait gave up first: show the snapshot it took instead of the final state
         std::vector<unsigned> S(h->ff_flag_words);
         (void)hipMemcpy(S.data(), h->d_ff_flags + h->ff_flag_words, sizeof(unsigned) * S.size(), hipMemcpyDeviceToHost);
-        for (size_t w = 0; w < F.size(); ++w) if (w < 24 || w >= 32) F[w] = S[w];
+        for (size_t w = 0; w < F.size(); ++w) if (w < W.dbg || w >= W.dbg_end) F[w] = S[w];
         fprintf(stderr, "[ff debug] (snapshot taken by the first wait that gave up)\n");
     }
-    const int nb = h->nblk; const size_t nt = (size_t)nb * (nb + 1) / 2;
-    const unsigned *fc = F.data() + 32, *tp = fc + nt, *lf = tp + nt, *dr = lf + nb, *pd = dr + nb;
-    fprintf(stderr, "[ff debug] ticket %u of %zu items; first worker wait that gave up: count %u item %u kind %u target %u seen %u\n", F[0],
-            h->ff_sched.items.size(), F[24], F[25], F[26], F[27], F[28]);
-    if (F[24] && F[26] < 6 && F[25] < h->ff_sched.items.size()) {
-        const FFItem& it = h->ff_sched.items[F[25]];
+    const unsigned *fc = F.data() + W.fcount, *tp = F.data() + W.tprog, *lf = F.data() + W.lfinal, *dr = F.data() + W.dready, *pd = F.data() + W.potrfdone;
+    fprintf(stderr, "[ff debug] ticket %u of %zu items; first worker wait that gave up: count %u item %u kind %u target %u seen %u\n", F[W.ticket],
+            h->ff_sched.items.size(), rec[HD_COUNT], rec[HD_TAG], rec[HD_KIND], rec[HD_TARGET], rec[HD_SEEN]);
+    if (worker && rec[HD_TAG] < h->ff_sched.items.size()) {
+        const FFItem& it = h->ff_sched.items[rec[HD_TAG]];
         fprintf(stderr, "  that item: T(%d,%d)[%d,%d) flags %d seq %d\n", it.i, it.c, it.t.j0, it.t.j1, it.t.flags, it.t.seq);
     }
     fprintf(stderr, "  potrfdone:");

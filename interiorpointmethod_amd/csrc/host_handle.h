@@ -100,8 +100,8 @@ struct ipm_handle {
     bool ff_built = false, ff_last = false;
     FFSchedule ff_sched;
     FFItem* d_ff_items = nullptr;         // the work list in ticket order
-    unsigned* d_ff_flags = nullptr;       // ticket[16] | reserved[8] | dbg[8] | fcount[ntile] | tprog[ntile] | lfinal[nblk] | dready[nblk] | potrfdone[nblk]
-    size_t ff_flag_words = 0;
+    unsigned* d_ff_flags = nullptr;       // the hand-off words (layout: FFWords, ff_schedule.h) + as many again for the diagnostic snapshot
+    size_t ff_flag_words = 0;             // FFWords::count
     double* ff_slab = nullptr;            // [ntile][Q][128*128]
     long long* ff_trace = nullptr;        // IPM_FF_TRACE_ITEMS=1: [nitems][4] per-item time line + [nblk][12] chain kernels (ipm_debug_ff_trace)
     long long* ff_prof = nullptr;         // IPM_FF_PROF=1: [workers][16] cycle profile of the persistent launch (accumulates)
@@ -145,7 +145,7 @@ struct ipm_handle {
     bool ls_cut = false;                  // a launch without a lockstep twin was met while recording
     int lockstep = 0;                     // IPM_FLAG_LOCKSTEP: created for ipm_solve_batch (block-step substitutions: every launch of the iteration is recordable)
     // switches ipm_create acts on once (read_env_switches)
-    unsigned spin_limit = 1u << 22;       // IPM_TEST_SPIN_LIMIT: spin bound of the device-side hand-offs (test knob, see gemm_nt_f64.h)
+    unsigned spin_limit = 1u << 22;       // IPM_TEST_SPIN_LIMIT: spin bound of the device-side hand-offs (test knob, see handoff.h)
     bool ragged_groups = true;            // IPM_RAGGED_GROUPS=0: group inverses only where the group size divides the block count
     bool ls_block_steps = false, potrf_stamps = false, ff_chain_mode0 = false;   // IPM_LS_BLOCK_STEPS (A/B: block-step substitutions in the lockstep
                                           // batch), IPM_POTRF_STAMPS (allocate stamp_buf), IPM_FF_CHAIN_MODE=0 was asked for (refused by ipm_create)

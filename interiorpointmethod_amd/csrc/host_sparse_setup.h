@@ -232,12 +232,9 @@ static int build_sparse_factor(ipm_handle* h, const std::vector<int>& cp, const 
         // fronts beyond ~5000 rows: the forward sweep's update vector + diagonal block pass the default dynamic-LDS limit
         const int cap = 96 * 1024;
         if (h->sp_lds_solve > (size_t)cap || h->sp_lds_chol > (size_t)cap) return fail(h, IPM_ERR_INVALID_ARG, "sparse factor: a front of %d rows exceeds the LDS budget of the sweeps", S.rmax);
-        HIP_TRY(h, hipFuncSetAttribute((const void*)sp_fwd_kernel<SPC_THREADS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-        HIP_TRY(h, hipFuncSetAttribute((const void*)sp_chol_kernel<SPC_THREADS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+        HIP_TRY(h, hipFuncSetAttribute((const void*)sp_fwd_kernel<SPC_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+        HIP_TRY(h, hipFuncSetAttribute((const void*)sp_chol_kernel<SPC_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
     }
-    // Fence-free hand-off (write-through stores + sc1 loads) is OPT-IN (IPM_SP_SC1=1): it passes every test and is 8-12 % faster
-    // per sweep at STOCFOR3 (0.358 / 0.182 / 0.141 -> 0.328 / 0.161 / 0.132 ms), but this kernel runs several workgroups per CU,
-    // outside the configurations that form is documented for; the release / acquire pair is the default.
     {   // workgroups the chip holds at once: LDS- or wave-limited (32 waves per CU)
         const size_t lds = std::max(h->sp_lds_chol, h->sp_lds_solve) + 512;
         const int wave_cap = threads == 64 ? 16 : 8;

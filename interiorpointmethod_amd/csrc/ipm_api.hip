@@ -202,7 +202,7 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     h->d_rowptr = (int*)(base + L.off_rowptr); h->d_colptr = (int*)(base + L.off_colptr);
     h->d_colind = (int*)(base + L.off_colind); h->d_rowind = (int*)(base + L.off_rowind);
     h->d_rval = (double*)(base + L.off_rval); h->d_cval = (double*)(base + L.off_cval);
-    {   // test knob (see gemm_nt_f64.h): spin bound of the device-side hand-offs; set in every case, so that a later handle restores the default
+    {   // test knob (see handoff.h): spin bound of the device-side hand-offs; set in every case, so that a later handle restores the default
         CREATE_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(ipm_spin_limit), &h->spin_limit, sizeof h->spin_limit, 0, hipMemcpyHostToDevice, h->stream));
         CREATE_TRY(hipStreamSynchronize(h->stream));
     }

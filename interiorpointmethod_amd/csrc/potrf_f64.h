@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "gemm_nt_f64.h"
+#include "handoff.h"
 
 namespace ipm {
 
@@ -50,7 +51,7 @@ struct PotrfDiag {
     const unsigned* wait_on; unsigned wait_count;
     unsigned* signal;
     unsigned* timeout;
-    unsigned* dbg; unsigned dbg_tag;   // diagnostic (may be null): see GemmNT::dbg; kind 7
+    unsigned* dbg; unsigned dbg_tag;   // diagnostic (may be null): see GemmNT::dbg; kind HK_POTRF
     int nt;                            // 16-wide panels to factor (1 .. 8): the rows from 16 nt on are PADDING rows (unit diagonal, nothing else):
                                        // L and inv(L) are the identity there, exactly what factoring them gives, without the pivots
     int rows;                          // rows of the block that are rows of the matrix (m - 128 k, may exceed NB): the guard skips the rest
@@ -433,7 +434,7 @@ __device__ __forceinline__ int potrf_lds(double* W, double* dinv_s, int nt, doub
 }
 
 // One diagonal block: wait for it (optional), factor it in the LDS workspace W, write L_kk and inv(L_kk), signal (optional).
-// The body of potrf_diag_kernel and of every step of ff_chain_kernel (form_factor.h).
+// The body of potrf_diag_kernel and of every step of the fused launch's chain role (ff_chain_role, form_factor.h).
 template <bool STAMP>
 __device__ __forceinline__ void potrf_diag_body(const PotrfDiag& a, double* W, double* dinv_s) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -441,22 +442,8 @@ __device__ __forceinline__ void potrf_diag_body(const PotrfDiag& a, double* W, d
     if (a.trace && tid == 0) a.trace[0] = (long long)wall_clock64();
     if (a.wait_on) {
         if (tid == 0) {
-            unsigned spins = 0;
-            while (__hip_atomic_load(a.wait_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < a.wait_count) {
-                __builtin_amdgcn_s_sleep(2);
-                ++spins;
-                if (spins > ipm_spin_limit || ((spins & 1023u) == 1u && a.timeout &&
-                                           __hip_atomic_load(a.timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-                    if (spins > ipm_spin_limit && a.dbg && __hip_atomic_fetch_add(a.dbg, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-                        a.dbg[1] = a.dbg_tag; a.dbg[2] = 7u; a.dbg[3] = a.wait_count;
-                        a.dbg[4] = __hip_atomic_load(a.wait_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    if (a.timeout) __hip_atomic_store(a.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    break;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            (void)handoff_wait_ge<2, true>(a.wait_on, a.wait_count, {a.timeout, a.dbg}, a.dbg_tag, HK_POTRF);
+            handoff_acquire();
         }
         __syncthreads();
     }
@@ -639,23 +626,15 @@ __device__ __forceinline__ void potrf_diag_body(const PotrfDiag& a, double* W, d
     IPM_STAMP(40);
     if (lane == 0 && wave == 0 && nfix) atomicAdd(a.fixed, nfix);
     if (a.signal) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every storing wave drains its stores
-        __syncthreads();
-        if (tid == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_add(a.signal, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        handoff_publish_begin();
+        if (tid == 0) __hip_atomic_fetch_add(a.signal, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (a.trace && tid == 0) a.trace[2] = (long long)wall_clock64();
 }
 
 template <bool STAMP>
 __global__ __launch_bounds__(PD_THREADS) void potrf_diag_kernel(PotrfDiag a) {
-    if (a.done && *a.done) {
-        if (a.signal && threadIdx.x == 0) __hip_atomic_fetch_add(a.signal, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
+    if (handoff_skipped(a.done, a.signal)) return;
     __shared__ __attribute__((aligned(16))) double W[NB * WLD];
     __shared__ double dinv_s[NB];
     potrf_diag_body<STAMP>(a, W, dinv_s);

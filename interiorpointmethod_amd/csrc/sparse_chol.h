@@ -17,12 +17,13 @@
 // counter in topological order (ascending top panel; the backward sweep descending), so a task only ever waits for tasks
 // that were drawn before it, by workgroups that are running: the launch cannot deadlock whatever the occupancy.  Inside a
 // task the panels run back to back in one workgroup; across tasks the hand-off is the release / acquire flag protocol of
-// gemm_nt_f64.h (every storing wave drains, barrier, lane 0: agent release + flag; consumer: relaxed poll, agent acquire,
+// handoff.h (every storing wave drains, barrier, lane 0: agent release + flag; consumer: relaxed poll, agent acquire,
 // barrier).  Spins are bounded and set the handle's time-out word (the host then reruns the launch with one workgroup,
 // which never waits).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "handoff.h"
 #include "potrf_f64.h"
 
 namespace ipm {
@@ -83,65 +84,14 @@ struct SpFactor {
     const int* done;
 };
 
+// Hand-off between tasks (handoff.h): a panel's flag holds the epoch of the launch that completed it.  The lanes of wave 0 poll
+// one child each, then handoff_acquire_barrier(tid < 64); the producer: handoff_publish_begin, lane 0 stores the epoch.
 __device__ __forceinline__ bool sp_wait(const unsigned* flag, unsigned epoch, unsigned* timeout) {
-    unsigned spins = 0;
-    while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch) {
-        __builtin_amdgcn_s_sleep(2);
-        ++spins;
-        if (spins > ipm_spin_limit || ((spins & 1023u) == 1u && __hip_atomic_load(timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-            __hip_atomic_store(timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return false;
-        }
-    }
-    return true;
+    return handoff_wait<2, false>([=] { return handoff_load(flag) == epoch; }, {timeout, nullptr}, [] {});
 }
-
-// consumer side of a hand-off: lanes of wave 0 poll the flags; then that wave's agent acquire, its wait, the barrier
-__device__ __forceinline__ void sp_acquire_barrier() {
-    if (threadIdx.x < 64) {                  // the polling wave: its fence invalidates this CU's L1 for the whole workgroup
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-}
-// producer side: every storing wave drains, barrier, lane 0 releases and stores the flag
 __device__ __forceinline__ void sp_publish(unsigned* flag, unsigned epoch) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// Hand-off WITHOUT fences (template parameter SC1; opt-in, IPM_SP_SC1=1): every byte another workgroup will read is stored write-through
-// (agent-scope relaxed atomic store = global_store ... sc1) and every load of such bytes is an sc1 load (bypasses this CU's L1);
-// producer: every storing wave drains (s_waitcnt vmcnt(0)), workgroup barrier, lane 0 stores the flag sc1; consumer: wave 0
-// polls the flag sc1, workgroup barrier, sc1 loads.  (MI355X_MICROARCH.md, inter-workgroup visibility, "valid forms": conditions
-// (1)-(3).)  Measured at STOCFOR3: a level of the tree costs ~10 us with the fence pair (release 1.7-6.5 us + acquire 1.7 us
-// + poll) against 1.4-3.9 us for the panel itself; without the fences a sweep is 8-12 % faster.  SC1 = false (the default)
-// keeps plain accesses and the release / acquire fences.
-template <bool SC1> __device__ __forceinline__ double sp_ld(const double* p) {
-    if constexpr (SC1) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return *p;
-}
-template <bool SC1> __device__ __forceinline__ void sp_st(double* p, double v) {
-    if constexpr (SC1) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
-template <bool SC1> __device__ __forceinline__ void sp_consume_barrier() {
-    if constexpr (SC1) { asm volatile("" ::: "memory"); __syncthreads(); }
-    else sp_acquire_barrier();
-}
-template <bool SC1> __device__ __forceinline__ void sp_signal(unsigned* flag, unsigned epoch) {
-    if constexpr (SC1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every storing wave drains its write-through stores
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        sp_publish(flag, epoch);
-    }
+    handoff_publish_begin();
+    if (threadIdx.x == 0) __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // draw the next task (workgroup-uniform); the last workgroup to leave resets the two counters for the next launch
@@ -203,7 +153,7 @@ __global__ __launch_bounds__(256) void sp_maxdiag_kernel(const double* L, const 
 // workgroup barrier between children -- the work is the children's entries, not (front entries) x (children), and the
 // order of additions is fixed.  Fan-in nodes (w = 0) only do this step.  Everything a panel needs to start (its sizes,
 // offsets and those of its children) sits in one record in task order (SpRec), read with uniform loads.
-template <int NT, bool SC1>
+template <int NT>
 __global__ __launch_bounds__(NT) void sp_chol_kernel(SpFactor f, unsigned epoch, const double* maxdiag, double eps,
                                                               double big, double shift_rel, int* fixed, int lds,
                                                               const SpRec* __restrict__ recs, int lvl_count,
@@ -242,7 +192,7 @@ __global__ __launch_bounds__(NT) void sp_chol_kernel(SpFactor f, unsigned epoch,
             const int ldp = front ? sp_front_stride(r) : sp_panel_stride(w);
             if (!level && rc.wait_children) {
                 if (tid < nchild && rc.ch[tid].ext) (void)sp_wait(flag + rc.ch[tid].K, epoch, f.timeout);   // (a time-out poisons the results; the host reruns the launch)
-                sp_consume_barrier<SC1>();
+                handoff_acquire_barrier(tid < 64);
             } else {
                 __syncthreads();                            // the previous panel of this task is complete (its U is in memory)
             }
@@ -261,7 +211,7 @@ __global__ __launch_bounds__(NT) void sp_chol_kernel(SpFactor f, unsigned epoch,
                     if (bl < w) P[a * ldp + bl] = Lp[a * w + bl];
                     else if (bl < ldp - 2) P[a * ldp + bl] = 0.0;
                 }
-                if (kids) for (int idx = tid; idx < p * p; idx += NT) sp_st<SC1>(Up + idx, 0.0);
+                if (kids) for (int idx = tid; idx < p * p; idx += NT) Up[idx] = 0.0;
             }
             __syncthreads();
             if (shift != 0.0) {
@@ -285,17 +235,17 @@ __global__ __launch_bounds__(NT) void sp_chol_kernel(SpFactor f, unsigned epoch,
                         if (e < pc * pc) {
                             const int i = e / pc, j = e - i * pc;
                             if (j <= i) {
-                                v[k] = sp_ld<SC1>(Uc + e);
+                                v[k] = Uc[e];
                                 const int a = rel[i], b = rel[j];
                                 tg[k] = (front || b < w) ? -(long long)(a * ldp + b) - 2 : (long long)(a - w) * p + (b - w);
                             }
                         }
                     }
 #pragma unroll
-                    for (int k = 0; k < SPC_BATCH; ++k) old[k] = tg[k] >= 0 ? sp_ld<SC1>(Up + tg[k]) : 0.0;
+                    for (int k = 0; k < SPC_BATCH; ++k) old[k] = tg[k] >= 0 ? Up[tg[k]] : 0.0;
 #pragma unroll
                     for (int k = 0; k < SPC_BATCH; ++k) {
-                        if (tg[k] >= 0) sp_st<SC1>(Up + tg[k], old[k] + v[k]);
+                        if (tg[k] >= 0) Up[tg[k]] = old[k] + v[k];
                         else if (tg[k] <= -2) P[-(tg[k] + 2)] += v[k];
                     }
                 }
@@ -338,7 +288,7 @@ __global__ __launch_bounds__(NT) void sp_chol_kernel(SpFactor f, unsigned epoch,
                     cr[t] = -1; cu[t] = 0.0;
                     if (t < nchild) {
                         const int pc = rc.ch[t].pc;
-                        if (tid < pc) { cu[t] = sp_ld<SC1>(f.uvec + rc.ch[t].relptr + tid); cr[t] = f.crel[rc.ch[t].relptr + tid]; }
+                        if (tid < pc) { cu[t] = *(f.uvec + rc.ch[t].relptr + tid); cr[t] = f.crel[rc.ch[t].relptr + tid]; }
                     }
                 }
                 __syncthreads();
@@ -350,7 +300,7 @@ __global__ __launch_bounds__(NT) void sp_chol_kernel(SpFactor f, unsigned epoch,
                         if (pc > NT) {
                             const double* uc = f.uvec + rc.ch[t].relptr;
                             const int* rel = f.crel + rc.ch[t].relptr;
-                            for (int i = NT + tid; i < pc; i += NT) fv[rel[i]] += sp_ld<SC1>(uc + i);
+                            for (int i = NT + tid; i < pc; i += NT) fv[rel[i]] += uc[i];
                         }
                         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                     }
@@ -373,7 +323,7 @@ __global__ __launch_bounds__(NT) void sp_chol_kernel(SpFactor f, unsigned epoch,
                         const double* row = P + a * ldp;
                         double dot = 0.0;
                         for (int c = 0; c < w; ++c) dot += row[c] * fv[c];
-                        sp_st<SC1>(uv + a, fv[a] - dot);
+                        uv[a] = fv[a] - dot;
                     }
                 }
             }
@@ -386,7 +336,7 @@ __global__ __launch_bounds__(NT) void sp_chol_kernel(SpFactor f, unsigned epoch,
                     const double* rb = P + (w + j) * ldp;
                     double dot = 0.0;
                     for (int c = 0; c < w; ++c) dot += ra[c] * rb[c];
-                    sp_st<SC1>(Up + idx, ra[w + j] - dot);
+                    Up[idx] = ra[w + j] - dot;
                 }
             } else if (w > 0 && p > 0) {
                 // matrix cores: one 16 x 16 tile of U per wave pass, v_mfma_f64_16x16x4_f64 over the w columns (zero padded to a
@@ -418,18 +368,18 @@ __global__ __launch_bounds__(NT) void sp_chol_kernel(SpFactor f, unsigned epoch,
                     for (int q = 0; q < 4; ++q) {
                         const int i = 16 * I + fk + 4 * q;
                         on[q] = i < p && j <= i;
-                        old[q] = (on[q] && kids) ? sp_ld<SC1>(Up + (long long)i * p + j) : 0.0;
+                        old[q] = (on[q] && kids) ? *(Up + (long long)i * p + j) : 0.0;
                     }
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int i = 16 * I + fk + 4 * q;
-                        if (on[q]) sp_st<SC1>(Up + (long long)i * p + j, old[q] - (acc0[q] + acc1[q]));
+                        if (on[q]) *(Up + (long long)i * p + j) = old[q] - (acc0[q] + acc1[q]);
                     }
                 }
             }
             for (int idx = tid; idx < r * w; idx += NT) { const int a = idx / w, b = idx - a * w; Lp[idx] = P[a * ldp + b]; }
             if (tid < w) f.dinv[rc.c0 + tid] = rs[tid];             // 1 / L_cc for the substitutions (a multiply per step instead of a divide)
-            if (!level && rc.publish) sp_signal<SC1>(flag + rc.J, epoch);
+            if (!level && rc.publish) sp_publish(flag + rc.J, epoch);
         }
     }
     if (tid == 0 && nfix) atomicAdd(fixed, nfix);
@@ -439,7 +389,7 @@ __global__ __launch_bounds__(NT) void sp_chol_kernel(SpFactor f, unsigned epoch,
 // ------------------------------------------------------------------------------------------------------------ L z = rhs
 // z may alias rhs.  Panel J: f = rhs(J's columns) + children's update vectors (child-major, as the factorization);
 // z_J = L_JJ^{-1} f_top; the rows below get f_below - L_21 z_J, handed to the parent.  Dynamic LDS: rmax + 1024 doubles.
-template <int NT, bool SC1>
+template <int NT>
 __global__ __launch_bounds__(NT) void sp_fwd_kernel(SpFactor f, unsigned epoch, const double* rhs, double* z, int rmax,
                    const SpRec* __restrict__ recs, int lvl_count) {
     if (f.done && *f.done) return;
@@ -466,7 +416,7 @@ __global__ __launch_bounds__(NT) void sp_fwd_kernel(SpFactor f, unsigned epoch, 
             const int r = rc.r, w = rc.w, nchild = rc.nchild;
             if (!level && rc.wait_children) {
                 if (tid < nchild && rc.ch[tid].ext) (void)sp_wait(flag + rc.ch[tid].K, epoch, f.timeout);
-                sp_consume_barrier<SC1>();
+                handoff_acquire_barrier(tid < 64);
             } else {
                 __syncthreads();
             }
@@ -486,7 +436,7 @@ __global__ __launch_bounds__(NT) void sp_fwd_kernel(SpFactor f, unsigned epoch, 
                 if (t < nchild) {
                     const int pc = rc.ch[t].pc;
                     all_short = all_short && pc <= NT;
-                    if (tid < pc) { cu[t] = sp_ld<SC1>(f.uvec + rc.ch[t].relptr + tid); cr[t] = f.crel[rc.ch[t].relptr + tid]; }
+                    if (tid < pc) { cu[t] = *(f.uvec + rc.ch[t].relptr + tid); cr[t] = f.crel[rc.ch[t].relptr + tid]; }
                 }
             }
             __syncthreads();
@@ -498,7 +448,7 @@ __global__ __launch_bounds__(NT) void sp_fwd_kernel(SpFactor f, unsigned epoch, 
                     if (pc > NT) {
                         const double* uc = f.uvec + rc.ch[t].relptr;
                         const int* rel = f.crel + rc.ch[t].relptr;
-                        for (int i = NT + tid; i < pc; i += NT) fv[rel[i]] += sp_ld<SC1>(uc + i);
+                        for (int i = NT + tid; i < pc; i += NT) fv[rel[i]] += uc[i];
                     }
                     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 }
@@ -522,10 +472,10 @@ __global__ __launch_bounds__(NT) void sp_fwd_kernel(SpFactor f, unsigned epoch, 
                     const double* row = Lp + (long long)a * w;
                     double dot = 0.0;
                     for (int c = 0; c < w; ++c) dot += row[c] * fv[c];
-                    sp_st<SC1>(uv + a, fv[a] - dot);
+                    uv[a] = fv[a] - dot;
                 }
             }
-            if (!level && rc.publish) sp_signal<SC1>(flag + rc.J, epoch);
+            if (!level && rc.publish) sp_publish(flag + rc.J, epoch);
         }
     }
     if (!level) sp_leave(ctr);
@@ -534,7 +484,7 @@ __global__ __launch_bounds__(NT) void sp_fwd_kernel(SpFactor f, unsigned epoch, 
 // ------------------------------------------------------------------------------------------------------------ L^T x = z
 // x may alias z.  Panels in DESCENDING order: x_J = L_JJ^{-T} (z_J - L_21^T x(rows below)); the rows below belong to
 // ancestors, whose x is final once the parent's flag is up.
-template <int NT, bool SC1>
+template <int NT>
 __global__ __launch_bounds__(NT) void sp_bwd_kernel(SpFactor f, unsigned epoch, const double* z, double* x, const SpRec* __restrict__ recs, int lvl_count) {
     if (f.done && *f.done) return;
     constexpr int NSL = NT / 32;
@@ -562,7 +512,7 @@ __global__ __launch_bounds__(NT) void sp_bwd_kernel(SpFactor f, unsigned epoch, 
             const int r = rc.r, w = rc.w, p = r - w;
             if (!level && rc.publish) {                              // the parent belongs to another task
                 if (tid == 0) (void)sp_wait(flag + rc.parent, epoch, f.timeout);
-                sp_consume_barrier<SC1>();
+                handoff_acquire_barrier(tid < 64);
             } else {
                 __syncthreads();
             }
@@ -573,7 +523,7 @@ __global__ __launch_bounds__(NT) void sp_bwd_kernel(SpFactor f, unsigned epoch, 
                 {
                     const int c = tid & (SPC_WCAP - 1), sl = tid >> 5;          // NT threads = 32 columns x NSL slices
                     double acc = 0.0;
-                    if (c < w) for (int i = sl; i < p; i += NSL) acc += Lp[(long long)(w + i) * w + c] * sp_ld<SC1>(x + rows[w + i]);
+                    if (c < w) for (int i = sl; i < p; i += NSL) acc += Lp[(long long)(w + i) * w + c] * x[rows[w + i]];
                     part[sl * SPC_WCAP + c] = acc;
                 }
                 for (int idx = tid; idx < w * w; idx += NT) D[idx] = Lp[idx];
@@ -591,10 +541,10 @@ __global__ __launch_bounds__(NT) void sp_bwd_kernel(SpFactor f, unsigned epoch, 
                         if (tid == c) ga = xc;
                         else if (tid < c) ga -= D[c * w + tid] * xc;
                     }
-                    if (tid < w) sp_st<SC1>(x + rc.c0 + tid, ga);
+                    if (tid < w) *(x + rc.c0 + tid) = ga;
                 }
             }
-            if (!level && rc.wait_children) sp_signal<SC1>(flag + rc.J, epoch);       // some child belongs to another task: it waits for this x
+            if (!level && rc.wait_children) sp_publish(flag + rc.J, epoch);       // some child belongs to another task: it waits for this x
         }
     }
     if (!level) sp_leave(ctr);

@@ -3,7 +3,7 @@
 Every cross-workgroup / cross-stream hand-off of the library is a bounded spin on a device counter; a wait that runs into its
 bound sets the handle's time-out word, the host rolls the call back to its snapshot and repeats it on a path that does not poll,
 and the handle keeps that path (csrc/host_iteration.h: read_scalars / poll_fallback).  No committed run had ever taken that path.
-The test knob IPM_TEST_SPIN_LIMIT (read at ipm_create, csrc/gemm_nt_f64.h) lowers the bound to a few polls, so that the FIRST
+The test knob IPM_TEST_SPIN_LIMIT (read at ipm_create, csrc/handoff.h) lowers the bound to a few polls, so that the FIRST
 wait of each kind that really has to wait gives up.  One run per path: (a) the fused formation + factorization launch, (b) the
 polled look-ahead of the blocked Cholesky, (c) the task hand-offs of the sparse multifrontal factor.  Checked: the call completes,
 the recovery is counted, the handle stays on the non-polling path, and the result is BIT-IDENTICAL to a handle that was put on
