@@ -5,7 +5,7 @@
 // What is being scheduled (dense handles, 128 x 128 tiles (i, c), i >= c, of B = A D^2 A^T and of its Cholesky factor;
 // replaces main.py:224 + the factorization inside main.py:180/:226 of the reference, fused):
 //   F(i,c,q)          one of Q K-chunks of the formation of the tile PAIR (i,c), (i+1,c), i even: raw partial tiles into the
-//                     slabs (tile, q) of the two tiles (a half above the diagonal or below the matrix is dropped)
+//                     slabs (tile, q) of the two tiles (a half above the diagonal or below the matrix is not computed)
 //   D(i)              max diag(B) over the rows of block i straight from A and d (the pivot guard's scale); these head the list
 //   T(i,c,[j0,j1))    tile (i,c) -= sum_{j0<=j<j1} L(i,j) L(c,j)^T, optionally + the Q formation slabs (ADD_BASE, once per
 //                     tile, any time after its F chunks), optionally followed by the panel solve L(i,c) = tile inv(L(c,c))^T
@@ -90,6 +90,9 @@ struct FFModel {                       // durations in microseconds, calibrated 
                                        // replay of the list under these values, tools/ff_replay.py, ends at 3347 us, the launch it
                                        // models at 3355 us)
     double f_over = 6.1, f_stage = 4.02;       // formation chunk: fixed + per BK = 16 stage of a 256 x 128 tile pair
+    double f_stage_half = 2.1;                 // ... per stage of a pair with ONE live tile (the other above the diagonal or below the
+                                               // matrix): the half-live engine of form_factor.h, four MFMA waves instead of eight
+                                               // (profiles/r06_ff_item_trace_half_pairs.txt: 8.5 + 2.08 per stage; 2.1 beside f_over)
     double t_over = 7.0, t_col = 15.9;         // update item: fixed + per 128-column block of L applied
     double t_rmw = 1.0, t_panel = 18.3;        // reading the tile back (all but its first item); the product with inv(L_cc)
     double t_base = 6.75;                      // adding ONE formation slab
@@ -143,7 +146,7 @@ inline void ff_build_schedule(int nblk, int Q, int W, const FFModel& M_in, FFSch
             const size_t eq = kv.find('=');
             if (eq != std::string::npos) {
                 const std::string k = kv.substr(0, eq); const double v = atof(kv.c_str() + eq + 1);
-                struct { const char* n; double* p; } tab[] = {{"f_over", &Mx.f_over}, {"f_stage", &Mx.f_stage}, {"t_over", &Mx.t_over}, {"t_col", &Mx.t_col},
+                struct { const char* n; double* p; } tab[] = {{"f_over", &Mx.f_over}, {"f_stage", &Mx.f_stage}, {"f_stage_half", &Mx.f_stage_half}, {"t_over", &Mx.t_over}, {"t_col", &Mx.t_col},
                     {"t_rmw", &Mx.t_rmw}, {"t_panel", &Mx.t_panel}, {"t_base", &Mx.t_base}, {"d_item", &Mx.d_item}, {"potrf", &Mx.potrf},
                     {"cpanel", &Mx.cpanel}, {"cupdate", &Mx.cupdate}, {"handoff", &Mx.handoff}, {"gap", &Mx.gap}};
                 for (auto& t : tab) if (k == t.n) *t.p = v;
@@ -233,7 +236,8 @@ inline void ff_build_schedule(int nblk, int Q, int W, const FFModel& M_in, FFSch
                 for (int k = 0; k < q; ++k) { acc += len[(size_t)k]; cut[(size_t)k + 1] = (int)(M.nstages * acc / tot + 0.5); }
                 cut[(size_t)q] = M.nstages;
                 for (int k = 0; k < q; ++k) {
-                    const int id = add(K_F, M.f_over + M.f_stage * (cut[(size_t)k + 1] - cut[(size_t)k]) + M.gap);
+                    const bool half = c > i || i + 1 >= nblk;      // one tile of the pair does not exist
+                    const int id = add(K_F, M.f_over + (half ? M.f_stage_half : M.f_stage) * (cut[(size_t)k + 1] - cut[(size_t)k]) + M.gap);
                     Node& x = nd[(size_t)id];
                     x.i = i; x.c = c; x.q = k; x.s0 = cut[(size_t)k]; x.s1 = cut[(size_t)k + 1];
                     fch.push_back(id);

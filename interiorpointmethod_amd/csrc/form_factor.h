@@ -23,7 +23,8 @@
 // taken from the accumulators through LDS.  Operands global -> registers -> LDS (rows padded: conflict-free ds_read_b64
 // fragment reads), double buffered, one barrier per stage.  HEAD (form_factor_roles_kernel_mfma_first, the launch that runs):
 // the stage loops of ff_gemm_pair and ff_gemm_pipe have no branch, and each stage opens with the MFMAs of the previous
-// stage's last k-step; form_factor_roles_kernel keeps the previous schedule as the tests' bitwise reference.  DESIGN.md 4-F
+// stage's last k-step, and a pair with one tile above the diagonal or below the matrix runs on the live tile's four waves
+// alone (HALF); form_factor_roles_kernel keeps the previous schedule as the tests' bitwise reference.  DESIGN.md 4-F
 // has the measurements and the rejected variants.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -271,29 +272,38 @@ constexpr int FF_POP_P = 256 * FF_PLDT, FF_POP_Q = 128 * FF_PLDT;     // doubles
 static_assert(2 * (FF_POP_P + FF_POP_Q) <= FF_LDS_DOUBLES, "pair engine LDS");
 
 // P0 / P1: first row of the upper / lower tile's 128-row panel of A (an invalid half is given any valid panel).
-template <bool HEAD>
+// HALF (with HEAD only): ONE half of the pair is live, lh = 0 the upper tile, 1 the lower, wave-uniform per item; P0 is the
+// live tile's panel and P1 is not read.  The dead half -- above the diagonal or below the matrix -- costs no memory
+// traffic, no LDS and no MFMA: all eight waves stage the column panel and the live row panel (into the live half's rows
+// of Ps), the four waves of the dead half (one per SIMD) then only keep the stage barriers, and the four live waves run
+// the stage loop of the full pair, i.e. the same MFMA sequence per accumulator: bit-identical results.
+template <bool HEAD, bool HALF = false>
 __device__ __forceinline__ void ff_gemm_pair(const double* __restrict__ P0, const double* __restrict__ P1, const double* __restrict__ Qg,
-                                             int64_t ld, const double* __restrict__ w, int ns, double* lds, f64x4 (&acc)[4][4]) {
+                                             int64_t ld, const double* __restrict__ w, int ns, double* lds, f64x4 (&acc)[4][4], int lh = 0) {
+    static_assert(HEAD || !HALF, "the half-live engine exists on the MFMA-first schedule only");
+    constexpr int NP = HALF ? 2 : 4;             // 64-row groups of the P operand a thread stages
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int fr = lane & 15, fk = lane >> 4;
-    double* Ps = lds;                            // [2][256][18]
+    double* Ps = lds;                            // [2][256][18] (HALF: the live tile's 128 rows of each buffer are in use)
     double* Qs = lds + 2 * FF_POP_P;             // [2][128][18]
     // staging: thread -> 16-byte chunk ch (of 8) of rows r0 + 64 u: P u < 4 (256 rows), Q u < 2 (128 rows)
     const int ch = tid & 7, r0 = tid >> 3;
     const double* pP0 = P0 + (int64_t)r0 * ld + ch * 2;
-    const double* pP1 = P1 + (int64_t)r0 * ld + ch * 2;
+    const double* pP1 = HALF ? nullptr : P1 + (int64_t)r0 * ld + ch * 2;
     const double* pQ = Qg + (int64_t)r0 * ld + ch * 2;
-    f64x2 pr[4], qr[2], wr;
+    f64x2 pr[NP], qr[2], wr;
     auto issue_loads = [&](int s) {
         wr = *reinterpret_cast<const f64x2*>(w + (int64_t)s * FF_PBK + ch * 2);
 #pragma unroll
         for (int u = 0; u < 2; ++u) qr[u] = *reinterpret_cast<const f64x2*>(pQ + (int64_t)u * 64 * ld + (int64_t)s * FF_PBK);
 #pragma unroll
         for (int u = 0; u < 2; ++u) pr[u] = *reinterpret_cast<const f64x2*>(pP0 + (int64_t)u * 64 * ld + (int64_t)s * FF_PBK);
+        if constexpr (!HALF) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) pr[2 + u] = *reinterpret_cast<const f64x2*>(pP1 + (int64_t)u * 64 * ld + (int64_t)s * FF_PBK);
+            for (int u = 0; u < 2; ++u) pr[2 + u] = *reinterpret_cast<const f64x2*>(pP1 + (int64_t)u * 64 * ld + (int64_t)s * FF_PBK);
+        }
     };
     const int st_off = r0 * FF_PLDT + ch * 2;
     auto store_q = [&](int buf, int u) {
@@ -301,7 +311,8 @@ __device__ __forceinline__ void ff_gemm_pair(const double* __restrict__ P0, cons
         v.x *= wr.x; v.y *= wr.y;
         *reinterpret_cast<f64x2*>(Qs + buf * FF_POP_Q + u * 64 * FF_PLDT + st_off) = v;
     };
-    auto store_p = [&](int buf, int u) { *reinterpret_cast<f64x2*>(Ps + buf * FF_POP_P + u * 64 * FF_PLDT + st_off) = pr[u]; };
+    const int st_off_p = HALF ? st_off + lh * 128 * FF_PLDT : st_off;
+    auto store_p = [&](int buf, int u) { *reinterpret_cast<f64x2*>(Ps + buf * FF_POP_P + u * 64 * FF_PLDT + st_off_p) = pr[u]; };
     const int fa_off = (wm * 64 + fr) * FF_PLDT + fk, fb_off = (wn * 64 + fr) * FF_PLDT + fk;
     double fa[2][4], fb[2][4];
     auto read_frags = [&](int set, int buf, int kk) {
@@ -326,13 +337,25 @@ __device__ __forceinline__ void ff_gemm_pair(const double* __restrict__ P0, cons
 #pragma unroll
     for (int u = 0; u < 2; ++u) store_q(0, u);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) store_p(0, u);
+    for (int u = 0; u < NP; ++u) store_p(0, u);
     __syncthreads();
     // HEAD: the loop has no branch: past the last stage the loads repeat stage ns - 1 and the stores and fragment reads go to
     // the idle buffer, so the scheduling barriers below hold across the whole stage (a branch splits the block, and the
     // compiler then moves k-step 3 behind the loads and reads of the next stage)
     if (HEAD) issue_loads(min(1, ns - 1));
     else if (1 < ns) issue_loads(1);
+    if (HALF && (wm >> 1) != lh) {
+        // a wave of the dead half: its share of the staging, barrier for barrier with the live waves' loop below
+        for (int s = 0; s < ns; ++s) {
+            const int buf = s & 1;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) { store_q(buf ^ 1, u); store_p(buf ^ 1, u); }
+            __syncthreads();
+            issue_loads(min(s + 2, ns - 1));
+        }
+        __syncthreads();
+        return;
+    }
     read_frags(0, 0, 0);
     for (int s = 0; s < ns; ++s) {
         const int buf = s & 1;
@@ -352,7 +375,7 @@ __device__ __forceinline__ void ff_gemm_pair(const double* __restrict__ P0, cons
         for (int i = 0; i < 4; ++i) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[0][i], fb[0][j], acc[i][j], 0, 0, 0);
-            if (more) { if (i < 2) store_q(buf ^ 1, i); store_p(buf ^ 1, i); }
+            if (more) { if (i < 2) store_q(buf ^ 1, i); if (i < NP) store_p(buf ^ 1, i); }
             __builtin_amdgcn_sched_barrier(0);
         }
         __syncthreads();
@@ -576,8 +599,8 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles&
         }
         if (it.type == FF_F) {
             // ---- one K-chunk of the formation of the tile PAIR (ti, tc), (ti + 1, tc): raw partial tiles -> slabs (tile, q).
-            //      A half above the diagonal (ti < tc) or below the matrix (ti + 1 == nblk) is computed on a stand-in panel and
-            //      dropped.
+            //      A half above the diagonal (ti < tc) or below the matrix (ti + 1 == nblk) is dead (never both): HEAD runs the
+            //      half-live engine on such a pair; the reference schedule computes the dead half on a stand-in panel and drops it.
             const bool up = ti >= tc, lo = ti + 1 < g.nblk;
             const int s0 = it.f.s0, s1 = min(g.nstages, (int)it.f.s1);
             f64x4 pacc[4][4];
@@ -586,9 +609,14 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles&
 #pragma unroll
                 for (int j = 0; j < 4; ++j) pacc[i][j] = (f64x4){0.0, 0.0, 0.0, 0.0};
             const int r_up = up ? ti : ti + 1, r_lo = lo ? ti + 1 : ti;
-            if (s1 > s0)
-                ff_gemm_pair<HEAD>(g.A + (int64_t)r_up * 128 * g.lda + (int64_t)s0 * FF_PBK, g.A + (int64_t)r_lo * 128 * g.lda + (int64_t)s0 * FF_PBK,
-                             g.A + (int64_t)tc * 128 * g.lda + (int64_t)s0 * FF_PBK, g.lda, g.d + (int64_t)s0 * FF_PBK, s1 - s0, lds, pacc);
+            if (s1 > s0) {
+                if (HEAD && !(up && lo))
+                    ff_gemm_pair<HEAD, HEAD>(g.A + (int64_t)r_up * 128 * g.lda + (int64_t)s0 * FF_PBK, nullptr, g.A + (int64_t)tc * 128 * g.lda + (int64_t)s0 * FF_PBK,
+                                             g.lda, g.d + (int64_t)s0 * FF_PBK, s1 - s0, lds, pacc, up ? 0 : 1);
+                else
+                    ff_gemm_pair<HEAD>(g.A + (int64_t)r_up * 128 * g.lda + (int64_t)s0 * FF_PBK, g.A + (int64_t)r_lo * 128 * g.lda + (int64_t)s0 * FF_PBK,
+                                       g.A + (int64_t)tc * 128 * g.lda + (int64_t)s0 * FF_PBK, g.lda, g.d + (int64_t)s0 * FF_PBK, s1 - s0, lds, pacc);
+            }
             FF_PROF(FFP_FGEMM);
             {
                 const int pm = wave >> 1, pn = wave & 1;              // the pair engine's wave grid: 4 (M) x 2 (N)

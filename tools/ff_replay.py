@@ -27,6 +27,7 @@ class Model:
 class ModelRoles(Model):
     """the launch that runs (mode=1: the chain as roles of the one launch, 251 workers), calibrated on profiles/r04_ff_item_trace_roles_kernel.txt"""
     f_over, f_stage = 6.1, 4.02
+    f_stage_half = 2.1                    # pair with one live tile (above the diagonal / below the matrix): half-live engine
     t_over, t_col, t_base, t_panel, t_rmw = 7.0, 15.9, 27.0, 18.3, 1.0
     d_item = 397.0
     potrf, cpanel, cupdate = 36.8, 7.3, 7.3
@@ -124,7 +125,8 @@ def replay(items, nblk, W=224, M=Model, tile_q=None, verbose=False, mode=0):
             heapq.heappush(free, (e + M.gap, w))
             continue
         if typ[k] == FF_F:
-            e = t0 + M.f_over + M.f_stage * max(0, s1[k] - s0[k])
+            half = tc[k] > ti[k] or ti[k] + 1 >= nblk
+            e = t0 + M.f_over + (getattr(M, "f_stage_half", M.f_stage) if half else M.f_stage) * max(0, s1[k] - s0[k])
             for r in (ti[k], ti[k] + 1):
                 if r >= tc[k] and r < nblk:
                     t = tile_id(r, tc[k])
