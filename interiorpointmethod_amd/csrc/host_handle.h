@@ -323,12 +323,7 @@ static Layout make_layout(int64_t m, int64_t n, int64_t sparse_nnz = 0, bool no_
 }
 
 __global__ void set_params_kernel(Scalars* sc, double e1, double e2, double e3, double eta, int max_iter,
-                                  int force, int reset) {
-    sc->e1 = e1; sc->e2 = e2; sc->e3 = e3; sc->eta = eta;
-    sc->max_iter = max_iter; sc->force = force;
-    sc->done = 0; sc->done_f = 0; sc->status = 0;
-    if (reset) { sc->k = 0; sc->fixed = 0; sc->fixed_first = 0; sc->obj_last_finite = __builtin_nan(""); }
-}
+                                  int force, int reset) { start_solve(sc, e1, e2, e3, eta, max_iter, force, reset); }
 
 static VecArgs vec_args(ipm_handle* h) {
     VecArgs a;

@@ -251,13 +251,32 @@ static SmallLP small_args(ipm_handle* h, int max_steps, int auto_reg) {
     return a;
 }
 
+static int small_variant(const ipm_handle* h) { return (h->bnd ? SMALL_BOUNDED : 0) | (h->detect ? SMALL_DETECT : 0); }
+static SmallItem small_item(ipm_handle* h, int index, int max_steps, int auto_reg) {
+    SmallItem it;
+    memset(&it, 0, sizeof it);
+    it.lp = small_args(h, max_steps, auto_reg);
+    if (h->bnd) it.bd = bnd_args(h);
+    it.dt = det_args(h);
+    it.eta = h->opt.eta;
+    it.variant = small_variant(h);
+    it.index = index;
+    return it;
+}
+// The variant -> kernel table of the fused small-LP path, once: `one` (a host item) launches the single-LP kernel of variant v on
+// it, otherwise the batch kernel of variant v runs `grid` workgroups on the device table d_items.
+static void launch_small(int v, hipStream_t S, const SmallItem* one, const SmallItem* d_items, unsigned grid) {
+    const dim3 g(one ? 1u : grid), b(PD_THREADS);
+    if (v == SMALL_PLAIN) { if (one) hipLaunchKernelGGL(small_lp_kernel, g, b, 0, S, one->lp); else hipLaunchKernelGGL(small_lp_batch_kernel, g, b, 0, S, d_items); }
+    else if (v == SMALL_BOUNDED) { if (one) hipLaunchKernelGGL(small_lp_bounded_kernel, g, b, 0, S, one->lp, one->bd); else hipLaunchKernelGGL(small_lp_batch_bounded_kernel, g, b, 0, S, d_items); }
+    else if (v == SMALL_DETECT) { if (one) hipLaunchKernelGGL(small_lp_detect_kernel, g, b, 0, S, one->lp, one->dt); else hipLaunchKernelGGL(small_lp_batch_detect_kernel, g, b, 0, S, d_items); }
+    else { if (one) hipLaunchKernelGGL(small_lp_bounded_detect_kernel, g, b, 0, S, one->lp, one->bd, one->dt); else hipLaunchKernelGGL(small_lp_batch_bounded_detect_kernel, g, b, 0, S, d_items); }
+}
+
 // whole loop of a small sparse LP in one launch of one workgroup (small_lp.h)
 static int enqueue_small(ipm_handle* h, int max_steps, int auto_reg) {
-    const SmallLP a = small_args(h, max_steps, auto_reg);
-    if (h->bnd && h->detect) hipLaunchKernelGGL(small_lp_bounded_detect_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a, bnd_args(h), det_args(h));
-    else if (h->bnd) hipLaunchKernelGGL(small_lp_bounded_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a, bnd_args(h));
-    else if (h->detect) hipLaunchKernelGGL(small_lp_detect_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a, det_args(h));
-    else hipLaunchKernelGGL(small_lp_kernel, dim3(1), dim3(PD_THREADS), 0, h->stream, a);
+    const SmallItem it = small_item(h, 0, max_steps, auto_reg);
+    launch_small(it.variant, h->stream, &it, nullptr, 1);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }

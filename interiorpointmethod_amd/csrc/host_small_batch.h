@@ -2,18 +2,6 @@
 // launch per kernel variant, one workgroup per LP.
 #pragma once
 // ------------------------------------------------------------------------------- batch of small LPs (small_lp.h)
-static int small_variant(const ipm_handle* h) { return (h->bnd ? SMALL_BOUNDED : 0) | (h->detect ? SMALL_DETECT : 0); }
-static SmallItem small_item(ipm_handle* h, int index, int max_steps, int auto_reg) {
-    SmallItem it;
-    memset(&it, 0, sizeof it);
-    it.lp = small_args(h, max_steps, auto_reg);
-    if (h->bnd) it.bd = bnd_args(h);
-    it.dt = det_args(h);
-    it.eta = h->opt.eta;
-    it.variant = small_variant(h);
-    it.index = index;
-    return it;
-}
 // Dispatch order: by variant (one grid each), inside a variant by estimated cost per iteration, largest first, so that the long LPs
 // start first and the tail of the grid is short.  The estimate is the entry count of the product list times the panel count:
 // for a dense B that is (16 nt)^2 / 2 * nt, the scale of the Cholesky's flops, and for a sparse one it follows the formation.
@@ -44,12 +32,7 @@ static int small_batch_round(ipm_handle* h0, ipm_handle** hs, const std::vector<
     int off = 0;
     for (int v = 0; v < SMALL_NVARIANTS; ++v) {
         if (!count[v]) continue;
-        const dim3 grid((unsigned)count[v]), block(PD_THREADS);
-        const SmallItem* part = d_items + off;
-        if (v == SMALL_PLAIN) hipLaunchKernelGGL(small_lp_batch_kernel, grid, block, 0, S, part);
-        else if (v == SMALL_BOUNDED) hipLaunchKernelGGL(small_lp_batch_bounded_kernel, grid, block, 0, S, part);
-        else if (v == SMALL_DETECT) hipLaunchKernelGGL(small_lp_batch_detect_kernel, grid, block, 0, S, part);
-        else hipLaunchKernelGGL(small_lp_batch_bounded_detect_kernel, grid, block, 0, S, part);
+        launch_small(v, S, nullptr, d_items + off, (unsigned)count[v]);
         off += count[v];
     }
     hipLaunchKernelGGL(small_batch_gather_kernel, dim3(g256), dim3(256), 0, S, d_items, cnt, d_sc);

@@ -1,0 +1,187 @@
+// iteration_rules.h -- the Mehrotra predictor-corrector iteration, stated once (gfx950): the device-resident state of a solve
+// and the per-column and per-scalar rules of one iteration.  vector_ops.h (one kernel per step: the dense, sparse, fused-factor
+// and lockstep paths) and small_lp.h (the whole loop in one workgroup) call these.
+//
+// A rule works on column j, or on scalars that one thread holds.  It loads and stores that column's entries and adds the column's
+// terms to the calling thread's own running sums and minima, in a fixed order; it never combines values of different threads.
+// The calling path owns where the vectors live, how it obtains (A^T dy)_j (passed in as a value), every reduction across threads
+// and the order of its additions.
+// `Cols` is VecArgs or SmallLP: a rule uses the column pointers both name alike (x, s, rc, d, v, q, dxa, dsa, dx, ds).
+// Bounded = native upper bounds (BndArgs), Detect = the infeasibility tests (DetArgs).
+//
+// Two rules are NOT here yet and are still written out in both files, to be kept identical by hand: the predictor column
+// (prepare_kernel_body / residual_cols) and the stop decision (stop_test_kernel_body / the stop_test lambda).  Every shared
+// spelling tried for them moved the register or scratch sizes of one side: prepare_kernel 50 -> 44..48 VGPRs,
+// prepare_bounded_kernel 60 -> 68, stop_test_kernel 26 -> 22, small_lp_detect_kernel 80 -> 84 B of scratch,
+// small_lp_bounded_detect_kernel 48 -> 0 B.
+//
+// Reference code the rules restate (paths in the reference repo):
+//   residuals r_b, r_c, r3          main.py:66-73   (test_create_rhs_predicted)
+//   stop test                       main.py:162-173 (check_optimality)
+//   predictor rhs / recovery        main.py:223-228 (direction_predicted_sparse "normal")
+//   ratio tests                     main.py:305-322 (predicted_stepsize), :604-626 (full_stepsize)
+//   mu, mu_aff, sigma               main.py:588-601 (duality_gap)
+//   corrector complementarity rhs   main.py:150-152 (create_rhs_corrected)
+//   iterate update                  main.py:694-696 (corrected)
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace ipm {
+
+// device-resident scalar state of a solve
+struct Scalars {
+    double b_norm, c_norm;
+    double rb_norm, rc_norm, gap, obj;
+    double mu, mu_aff, sigma;
+    double alpha_aff_p, alpha_aff_d, alpha_p, alpha_d;
+    double maxdiag;
+    double e1, e2, e3, eta;
+    double obj_last_finite;      // last finite c^T x seen by the stop test (main.py:1227-1233 returns it on NaN)
+    int done, status, k, max_iter, fixed, force, fixed_first;   // fixed_first: guarded pivots of the first factorization
+    int done_f;                  // `done` as it stood when the iteration's formation began (scaling_kernel): what the formation and
+                                 // factorization kernels of the overlapped path test, so that a stop test that flips `done` while
+                                 // they are in flight (it runs on the residual stream) never leaves B half factored
+};
+
+// per-iteration record (include/ipm_hip.h: ipm_iter_record), written by record_iteration into a ring
+struct IterRec {
+    int k, fixed;
+    double obj, rb, rc, gap, mu, sigma, aap, aad, ap, ad;
+};
+constexpr int HIST_CAP = 1024;
+
+// Native upper bounds 0 <= x <= u: the bounded instantiations (Bounded = true) take these.  Every array is an
+// n-vector; outside the bounded set U, u = +inf and w = z = dw = dz = 0, so the streams stay coalesced and no index gather is
+// needed.  qz = r_4 / w of the current direction (the z-analogue of q).
+struct BndArgs {
+    const double* u;
+    double *w, *z, *dwa, *dza, *dw, *dz, *qz;
+    int nU;                        // |U|
+};
+__device__ __forceinline__ bool bnd_in(double u) { return u < 1.7976931348623157e308; }     // finite bound (u is never NaN)
+// theta_j = 1 / (s/x + z/w) on U: the diagonal of D^2 (scaling_kernel and prepare_kernel write it concurrently: one expression)
+__device__ __forceinline__ double bnd_theta(double x, double s, double w, double z) { return 1.0 / (s / x + z / w); }
+// the number of complementarity pairs: mu = (x.s + w.z) / (n + |U|), and mu_aff alike
+template <bool Bounded>
+__device__ __forceinline__ double pair_count(int n, const BndArgs& bd) { return Bounded ? (double)(n + bd.nU) : (double)n; }
+
+// Infeasibility tests of IPM_FLAG_DETECT_INFEASIBILITY, on the iterate of a stop test that said "continue":
+//   primal infeasible: beta = b.y - u_U.z_U > 0 and max_j (A^T y - z)_j+ <= eps_p beta   (certificate y / beta, z / beta)
+//   dual infeasible:   gamma = -c.x > 0 and max(||A x||_inf, max x_U) <= eps_d gamma      (certificate x / gamma)
+// Maxima, not sums of squares: the iterate runs along a ray and |y| reaches 1e87 before the test fires.
+struct DetArgs {
+    double eps_p, eps_d;
+    double* out;                   // [4]: kind (5 / 6), normalisation (beta / gamma), violation / normalisation, k at detection
+};
+constexpr int IPM_STATUS_PRIMAL_INFEASIBLE_ = 5, IPM_STATUS_DUAL_INFEASIBLE_ = 6;   // include/ipm_hip.h
+// one thread; true (and done, status, dt.out set) when a test fires
+__device__ __forceinline__ bool detect_fire(DetArgs dt, Scalars* sc, double beta, double vp, double gamma, double vd) {
+    int kind = 0;
+    double nrm = 0.0, viol = 0.0;
+    if (beta > 0.0 && beta < 1.7e308 && vp <= dt.eps_p * beta) { kind = IPM_STATUS_PRIMAL_INFEASIBLE_; nrm = beta; viol = vp; }
+    else if (gamma > 0.0 && gamma < 1.7e308 && vd <= dt.eps_d * gamma) { kind = IPM_STATUS_DUAL_INFEASIBLE_; nrm = gamma; viol = vd; }
+    if (!kind) return false;
+    dt.out[0] = (double)kind; dt.out[1] = nrm; dt.out[2] = viol / nrm; dt.out[3] = (double)sc->k;
+    sc->status = kind;
+    sc->done = 1;
+    return true;
+}
+
+// start of a solve (force: no stop decision, ipm_iterate; reset: a new solve, not a continuation)
+__device__ __forceinline__ void start_solve(Scalars* sc, double e1, double e2, double e3, double eta, int max_iter, int force, int reset) {
+    sc->e1 = e1; sc->e2 = e2; sc->e3 = e3; sc->eta = eta;
+    sc->max_iter = max_iter; sc->force = force;
+    sc->done = 0; sc->done_f = 0; sc->status = 0;
+    if (reset) { sc->k = 0; sc->fixed = 0; sc->fixed_first = 0; sc->obj_last_finite = __builtin_nan(""); }
+}
+
+// Direction recovery from w = (A^T dy)_j with the current q, v (main.py:227-228) and the ratio tests (main.py:305-322): this
+// thread's running minima minp (over x, w) and mind (over s, z).  Bounded, on U: dw = -r_u - dx, dz = -(r4 + z dw)/w (qz = r4/w);
+// dw = dz = 0 outside U.  (DX, DS, DW, DZ): the affine or the corrected direction.  xj, sj = x[j], s[j]: each path loads them on
+// its own side of the product with A^T, and its register allocation depends on that.
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void direction_column(const Cols& a, const BndArgs& bd, int j, double w, double* DX, double* DS, double* DW,
+                                                 double* DZ, double xj, double sj, double& minp, double& mind) {
+    const double dxj = a.d[j] * w + a.v[j];
+    const double dsj = (-sj * dxj) / xj - a.q[j];
+    DX[j] = dxj; DS[j] = dsj;
+    if (dxj < 0.0) minp = fmin(minp, -xj / dxj);
+    if (dsj < 0.0) mind = fmin(mind, -sj / dsj);
+    if constexpr (Bounded) {
+        const double uj = bd.u[j];
+        double dwj = 0.0, dzj = 0.0;
+        if (bnd_in(uj)) {
+            const double wj = bd.w[j], zj = bd.z[j];
+            dwj = -(xj + wj - uj) - dxj;
+            dzj = (-zj * dwj) / wj - bd.qz[j];
+            if (dwj < 0.0) minp = fmin(minp, -wj / dwj);
+            if (dzj < 0.0) mind = fmin(mind, -zj / dzj);
+        }
+        DW[j] = dwj; DZ[j] = dzj;
+    }
+}
+
+// column j's terms of (x + a_p dxa).(s + a_d dsa) and, Bounded, (w + a_p dwa).(z + a_d dza) (0 outside U), added to this thread's
+// running sum in that order                                                        main.py:579-584, 598
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void mu_aff_column(const Cols& a, const BndArgs& bd, int j, double ap, double ad, double& acc) {
+    acc += (a.x[j] + ap * a.dxa[j]) * (a.s[j] + ad * a.dsa[j]);
+    if constexpr (Bounded) acc += (bd.w[j] + ap * bd.dwa[j]) * (bd.z[j] + ad * bd.dza[j]);
+}
+
+// centring: mu_aff = (the reduced sum of mu_aff_column) / pairs ; sigma = (mu_aff / mu)^3          main.py:588-601
+struct Centring { double mu_aff, sigma; };
+template <bool Bounded>
+__device__ __forceinline__ Centring centring(double sum, double mu, int n, const BndArgs& bd) {
+    const double mu_aff = sum / pair_count<Bounded>(n, bd);
+    const double r = mu_aff / mu;
+    return {mu_aff, r * r * r};
+}
+
+// corrector column, sm = sigma mu: r3c = x s + dxa dsa - sm ; q = r3c/x ; v = d (r_c - q)             main.py:150-152
+// Bounded, on U: r4c = w z + dwa dza - sm ; qz = r4c/w ; v = theta (r_c - q + (r4c - z r_u)/w)
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void corrector_column(const Cols& a, const BndArgs& bd, int j, double sm) {
+    const double xj = a.x[j];
+    const double r3c = xj * a.s[j] + a.dxa[j] * a.dsa[j] - sm;
+    const double qj = r3c / xj;
+    a.q[j] = qj;
+    if constexpr (Bounded) {
+        const double uj = bd.u[j];
+        if (bnd_in(uj)) {
+            const double wj = bd.w[j], zj = bd.z[j];
+            const double r4c = wj * zj + bd.dwa[j] * bd.dza[j] - sm;
+            bd.qz[j] = r4c / wj;
+            a.v[j] = a.d[j] * (a.rc[j] - qj + (r4c - zj * (xj + wj - uj)) / wj);
+            return;
+        }
+    }
+    a.v[j] = a.d[j] * (a.rc[j] - qj);
+}
+
+// damped step from the reduced ratio-test minimum (main.py:604-626) and the column update x += a_p dx ; s += a_d ds
+// (Bounded: w += a_p dw ; z += a_d dz)  (main.py:694-696); y += a_d dy stays with the path, which knows where y lives
+__device__ __forceinline__ double damped_step(double eta, double ratio_min) { return fmin(1.0, eta * ratio_min); }
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void update_column(const Cols& a, const BndArgs& bd, int j, double ap, double ad) {
+    a.x[j] += ap * a.dx[j];
+    a.s[j] += ad * a.ds[j];
+    if constexpr (Bounded) {
+        bd.w[j] += ap * bd.dw[j];
+        bd.z[j] += ad * bd.dz[j];
+    }
+}
+
+// end of an iteration -- one thread: the IterRec of iteration k into the ring, the step lengths, k += 1.  mu, sigma and the affine
+// step lengths come as values: the multi-kernel path reads them from *sc, where earlier kernels left them; the one-workgroup loop
+// holds them in registers and stores mu_aff, sigma and the affine step lengths itself.
+__device__ __forceinline__ void record_iteration(Scalars* sc, IterRec* hist, double mu, double sigma, double aap, double aad, double ap, double ad) {
+    const int k = sc->k;
+    IterRec r;
+    r.k = k; r.fixed = sc->fixed; r.obj = sc->obj; r.rb = sc->rb_norm; r.rc = sc->rc_norm; r.gap = sc->gap;
+    r.mu = mu; r.sigma = sigma; r.aap = aap; r.aad = aad; r.ap = ap; r.ad = ad;
+    hist[k % HIST_CAP] = r;
+    sc->alpha_p = ap; sc->alpha_d = ad; sc->k = k + 1;
+}
+
+}  // namespace ipm

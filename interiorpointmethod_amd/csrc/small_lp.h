@@ -13,8 +13,11 @@
 //     diagonal blocks -- on nt panels instead of 8; both triangular solves are matvecs with inv(L) in LDS.
 //   * Reductions are wave shuffles + a fixed-order sum over the 8 waves: bitwise reproducible.
 //
-// Same mathematics, constants and stop test as vector_ops.h; the summation orders differ from the
-// multi-kernel path, so iterates agree to rounding, not bit for bit (tests compare both against the reference).
+// The rules of the iteration are iteration_rules.h, shared with the multi-kernel path (vector_ops.h), except the predictor column
+// (residual_cols) and the stop decision (stop_test), which restate prepare_kernel and stop_test_kernel of vector_ops.h: same
+// mathematics, constants and stop test.  This file owns what this path does around the rules: A and the vectors
+// as placed above, (A^T y)_j as a CSC dot product with y in LDS, the normal equations, and the reductions.  Their summation orders
+// differ from the multi-kernel path's, so iterates agree to rounding, not bit for bit (tests compare both against the reference).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -68,9 +71,9 @@ __device__ __forceinline__ void block_reduce512(double (&v)[NV], double* red) {
     }
 }
 
-// Bounded = true: native upper bounds (vector_ops.h BndArgs) -- the same loop with the w / z terms folded into
+// Bounded = true: native upper bounds (BndArgs) -- the same loop with the w / z terms folded into
 // the same reductions (r_u^2 into ||r_b||^2, w.z into x.s, the w / z ratios into the step minima); no extra LDS.
-// Detect = true: the infeasibility tests of vector_ops.h (detect_fire) in the stop test, from sums and maxima the residual passes
+// Detect = true: the infeasibility tests (detect_fire) in the stop test, from sums and maxima the residual passes
 // gather on the side (b.y, u_U.z_U, max (A^T y - z)_+, max |A x|, max x_U).
 template <bool Bounded, bool Detect = false>
 __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt = DetArgs{}) {
@@ -201,30 +204,14 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
         }
         __syncthreads();
     };
-    // (dx, ds) from dys with the current q, v; ratio-test minima (main.py:227-228, 305-322)
+    // direction_column over the columns with (A^T dy)_j from dys; this thread's ratio-test minima
     auto direction = [&](double* DX, double* DS, double& minp, double& mind) {
         for (int j = tid; j < n; j += PD_THREADS) {
             const int pb = a.A.colptr[j], pe = a.A.colptr[j + 1];
             double w = 0.0;
             for (int p = pb; p < pe; ++p) w += a.A.cval[p] * dys[a.A.rowind[p]];
             const double xj = a.x[j], sj = a.s[j];
-            const double dxj = a.d[j] * w + a.v[j];
-            const double dsj = (-sj * dxj) / xj - a.q[j];
-            DX[j] = dxj; DS[j] = dsj;
-            if (dxj < 0.0) minp = fmin(minp, -xj / dxj);
-            if (dsj < 0.0) mind = fmin(mind, -sj / dsj);
-            if constexpr (Bounded) {
-                const double uj = bd.u[j];
-                double dwj = 0.0, dzj = 0.0;
-                if (bnd_in(uj)) {
-                    const double wj = bd.w[j], zj = bd.z[j];
-                    dwj = -(xj + wj - uj) - dxj;
-                    dzj = (-zj * dwj) / wj - bd.qz[j];
-                    if (dwj < 0.0) minp = fmin(minp, -wj / dwj);
-                    if (dzj < 0.0) mind = fmin(mind, -zj / dzj);
-                }
-                DWp[j] = dwj; DZp[j] = dzj;
-            }
+            direction_column<Bounded>(a, bd, j, w, DX, DS, DWp, DZp, xj, sj, minp, mind);
         }
     };
 
@@ -296,58 +283,26 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
         block_reduce512<2, true>(mn, red);
         const double aap = mn[0], aad = mn[1];
         double ma[1] = {0.0};
-        for (int j = tid; j < n; j += PD_THREADS) {
-            ma[0] += (a.x[j] + aap * a.dxa[j]) * (a.s[j] + aad * a.dsa[j]);
-            if constexpr (Bounded) ma[0] += (bd.w[j] + aap * bd.dwa[j]) * (bd.z[j] + aad * bd.dza[j]);      // 0 outside U
-        }
+        for (int j = tid; j < n; j += PD_THREADS) mu_aff_column<Bounded>(a, bd, j, aap, aad, ma[0]);
         block_reduce512<1, false>(ma, red);
-        const double mu_aff = ma[0] / (Bounded ? (double)(n + bd.nU) : (double)n);
-        const double rr = mu_aff / mu;
-        const double sigma = rr * rr * rr;
-        const double sm = sigma * mu;
-        // ---------------------------------------------------------------- corrector (main.py:150-152), same factor
-        for (int j = tid; j < n; j += PD_THREADS) {
-            const double xj = a.x[j];
-            const double qj = (xj * a.s[j] + a.dxa[j] * a.dsa[j] - sm) / xj;
-            a.q[j] = qj;
-            if constexpr (Bounded) {
-                const double uj = bd.u[j];
-                if (bnd_in(uj)) {
-                    const double wj = bd.w[j], zj = bd.z[j];
-                    const double r4c = wj * zj + bd.dwa[j] * bd.dza[j] - sm;
-                    bd.qz[j] = r4c / wj;
-                    a.v[j] = a.d[j] * (a.rc[j] - qj + (r4c - zj * (xj + wj - uj)) / wj);
-                    continue;
-                }
-            }
-            a.v[j] = a.d[j] * (a.rc[j] - qj);
-        }
+        const Centring ct = centring<Bounded>(ma[0], mu, n, bd);
+        const double sm = ct.sigma * mu;
+        // ---------------------------------------------------------------- corrector, same factor
+        for (int j = tid; j < n; j += PD_THREADS) corrector_column<Bounded>(a, bd, j, sm);
         __syncthreads();
         solve_normal();
         double mc[2] = {1.0, 1.0};
         if constexpr (Bounded) { DWp = bd.dw; DZp = bd.dz; }
         direction(a.dx, a.ds, mc[0], mc[1]);
         block_reduce512<2, true>(mc, red);
-        // ---------------------------------------------------------------- damped step (main.py:604-626, 694-696)
+        // ---------------------------------------------------------------- damped step
         const double eta = sc->eta;
-        const double ap = fmin(1.0, eta * mc[0]), ad = fmin(1.0, eta * mc[1]);
-        for (int j = tid; j < n; j += PD_THREADS) {
-            a.x[j] += ap * a.dx[j];
-            a.s[j] += ad * a.ds[j];
-            if constexpr (Bounded) {
-                bd.w[j] += ap * bd.dw[j];
-                bd.z[j] += ad * bd.dz[j];
-            }
-        }
+        const double ap = damped_step(eta, mc[0]), ad = damped_step(eta, mc[1]);
+        for (int j = tid; j < n; j += PD_THREADS) update_column<Bounded>(a, bd, j, ap, ad);
         if (tid < m) ys[tid] += ad * dys[tid];
         if (tid == 0) {
-            const int k = sc->k;
-            IterRec r;
-            r.k = k; r.fixed = sc->fixed; r.obj = sc->obj; r.rb = sc->rb_norm; r.rc = sc->rc_norm; r.gap = sc->gap;
-            r.mu = mu; r.sigma = sigma; r.aap = aap; r.aad = aad; r.ap = ap; r.ad = ad;
-            a.hist[k % HIST_CAP] = r;
-            sc->mu_aff = mu_aff; sc->sigma = sigma; sc->alpha_aff_p = aap; sc->alpha_aff_d = aad;
-            sc->alpha_p = ap; sc->alpha_d = ad; sc->k = k + 1;
+            record_iteration(sc, a.hist, mu, ct.sigma, aap, aad, ap, ad);
+            sc->mu_aff = ct.mu_aff; sc->sigma = ct.sigma; sc->alpha_aff_p = aap; sc->alpha_aff_d = aad;
         }
         ++steps;
         __syncthreads();
@@ -387,15 +342,11 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_kernel(cons
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, true>(items); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, true>(items); }
 
-// what set_params_kernel(sc, e1, e2, e3, eta, max_iter, force = 0, reset = 1) does for one LP, for every item: one thread per item
+// start_solve(force = 0, reset = 1) for every item, as set_params_kernel does for one LP: one thread per item
 __global__ __launch_bounds__(256) void small_batch_params_kernel(const SmallItem* __restrict__ items, int n, double e1, double e2, double e3, int max_iter) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    Scalars* sc = items[i].lp.sc;
-    sc->e1 = e1; sc->e2 = e2; sc->e3 = e3; sc->eta = items[i].eta;
-    sc->max_iter = max_iter; sc->force = 0;
-    sc->done = 0; sc->done_f = 0; sc->status = 0;
-    sc->k = 0; sc->fixed = 0; sc->fixed_first = 0; sc->obj_last_finite = __builtin_nan("");
+    start_solve(items[i].lp.sc, e1, e2, e3, items[i].eta, max_iter, 0, 1);
 }
 
 // every item's scalar record into ONE contiguous array (slot = the item's index): the host reads all statistics with one copy

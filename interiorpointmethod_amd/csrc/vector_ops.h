@@ -1,16 +1,12 @@
 // vector_ops.h -- the HBM-bound part of one interior-point iteration (gfx950): dense GEMV
-// passes over A and the fused elementwise/reduction kernels between them.
+// passes over A and the fused elementwise/reduction kernels between them, one kernel per step.
 //
-// Reference code these kernels restate (paths in the reference repo):
-//   residuals r_b, r_c, r3          main.py:66-73   (test_create_rhs_predicted)
-//   stop test                       main.py:162-173 (check_optimality)
-//   predictor rhs / recovery        main.py:223-228 (direction_predicted_sparse "normal")
-//   ratio tests                     main.py:305-322 (predicted_stepsize), :604-626 (full_stepsize)
-//   mu, mu_aff, sigma               main.py:588-601 (duality_gap)
-//   corrector complementarity rhs   main.py:150-152 (create_rhs_corrected)
-//   iterate update                  main.py:694-696 (corrected)
-//
-// All reductions are two-level with a fixed order (per-block partials, then every consumer
+// The state of a solve and the rules of the iteration that this path shares with the one-workgroup loop (small_lp.h) are in
+// iteration_rules.h: direction recovery and ratio tests, mu_aff, centring, corrector column, damped step and update, iteration
+// record, start of a solve.  The predictor column (prepare_kernel) and the stop decision (stop_test_kernel) are still written out
+// here AND in small_lp.h (main.py:66-73, :162-173, :223-228 of the reference repo); iteration_rules.h says why.  Beyond that, this
+// file owns what this path does around the rules: grid-stride loops over global memory, (A^T y)_j from the GEMV-T partials
+// (col_sum), and the reductions.  All reductions are two-level with a fixed order (per-block partials, then every consumer
 // re-sums the <= 64 partials in index order), so a solve is bitwise reproducible; no fp64
 // atomics are used.  Scalars (norms, alpha, sigma, mu, stop flag) never leave the device
 // inside an iteration.
@@ -18,33 +14,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "gemm_nt_f64.h"
+#include "iteration_rules.h"
 
 namespace ipm {
 
 constexpr int VBLK = 256;        // threads per vector-kernel block
 constexpr int MAXPART = 64;      // max blocks (= partials) of a vector kernel
-
-// device-resident scalar state of a solve
-struct Scalars {
-    double b_norm, c_norm;
-    double rb_norm, rc_norm, gap, obj;
-    double mu, mu_aff, sigma;
-    double alpha_aff_p, alpha_aff_d, alpha_p, alpha_d;
-    double maxdiag;
-    double e1, e2, e3, eta;
-    double obj_last_finite;      // last finite c^T x seen by the stop test (main.py:1227-1233 returns it on NaN)
-    int done, status, k, max_iter, fixed, force, fixed_first;   // fixed_first: guarded pivots of the first factorization
-    int done_f;                  // `done` as it stood when the iteration's formation began (scaling_kernel): what the formation and
-                                 // factorization kernels of the overlapped path test, so that a stop test that flips `done` while
-                                 // they are in flight (it runs on the residual stream) never leaves B half factored
-};
-
-// per-iteration record (include/ipm_hip.h: ipm_iter_record), written by update_kernel into a ring
-struct IterRec {
-    int k, fixed;
-    double obj, rb, rc, gap, mu, sigma, aap, aad, ap, ad;
-};
-constexpr int HIST_CAP = 1024;
 
 // partial-sum slots (each MAXPART doubles)
 enum { P_RC2 = 0, P_XS, P_CX, P_RB2, P_MINP_AFF, P_MIND_AFF, P_MUAFF, P_MINP, P_MIND, P_NSLOT };
@@ -157,18 +132,6 @@ struct VecArgs {
     IterRec* hist;                 // [HIST_CAP] ring of per-iteration records
 };
 
-// Native upper bounds 0 <= x <= u: the bounded instantiations (Bounded = true) of the kernels below take
-// these.  Every array is an n-vector; outside the bounded set U, u = +inf and w = z = dw = dz = 0, so the streams stay
-// coalesced and no index gather is needed.  qz = r_4 / w of the current direction (the z-analogue of VecArgs::q).
-struct BndArgs {
-    const double* u;
-    double *w, *z, *dwa, *dza, *dw, *dz, *qz;
-    int nU;                        // |U|: mu = (x.s + w.z) / (n + |U|)
-};
-__device__ __forceinline__ bool bnd_in(double u) { return u < 1.7976931348623157e308; }     // finite bound (u is never NaN)
-// theta_j = 1 / (s/x + z/w) on U: the diagonal of D^2 (scaling_kernel and prepare_kernel write it concurrently: one expression)
-__device__ __forceinline__ double bnd_theta(double x, double s, double w, double z) { return 1.0 / (s / x + z / w); }
-
 // sum over the row chunks of the GEMV-T partials, in chunk order (fixed order: bitwise reproducible).  Eight loads are in
 // flight at a time: a plain loop waits for every load before it issues the next one (32 chunks = 32 L2 latencies, 13 us of
 // direction_kernel's 13 us at n = 8192).
@@ -277,28 +240,6 @@ __device__ __forceinline__ void scaling_kernel_body(VecArgs a, BndArgs bd = BndA
 __global__ __launch_bounds__(VBLK) void scaling_kernel(VecArgs a) { scaling_kernel_body(a); }
 __global__ __launch_bounds__(VBLK) void scaling_bounded_kernel(VecArgs a, BndArgs bd) { scaling_kernel_body<true>(a, bd); }
 
-// Infeasibility tests of IPM_FLAG_DETECT_INFEASIBILITY, on the iterate of a stop test that said "continue":
-//   primal infeasible: beta = b.y - u_U.z_U > 0 and max_j (A^T y - z)_j+ <= eps_p beta   (certificate y / beta, z / beta)
-//   dual infeasible:   gamma = -c.x > 0 and max(||A x||_inf, max x_U) <= eps_d gamma      (certificate x / gamma)
-// Maxima, not sums of squares: the iterate runs along a ray and |y| reaches 1e87 before the test fires.
-struct DetArgs {
-    double eps_p, eps_d;
-    double* out;                   // [4]: kind (5 / 6), normalisation (beta / gamma), violation / normalisation, k at detection
-};
-constexpr int IPM_STATUS_PRIMAL_INFEASIBLE_ = 5, IPM_STATUS_DUAL_INFEASIBLE_ = 6;   // include/ipm_hip.h
-// one thread; true (and done, status, dt.out set) when a test fires
-__device__ __forceinline__ bool detect_fire(DetArgs dt, Scalars* sc, double beta, double vp, double gamma, double vd) {
-    int kind = 0;
-    double nrm = 0.0, viol = 0.0;
-    if (beta > 0.0 && beta < 1.7e308 && vp <= dt.eps_p * beta) { kind = IPM_STATUS_PRIMAL_INFEASIBLE_; nrm = beta; viol = vp; }
-    else if (gamma > 0.0 && gamma < 1.7e308 && vd <= dt.eps_d * gamma) { kind = IPM_STATUS_DUAL_INFEASIBLE_; nrm = gamma; viol = vd; }
-    if (!kind) return false;
-    dt.out[0] = (double)kind; dt.out[1] = nrm; dt.out[2] = viol / nrm; dt.out[3] = (double)sc->k;
-    sc->status = kind;
-    sc->done = 1;
-    return true;
-}
-
 // stop test of check_optimality (main.py:162-173) -- one thread.
 // Bounded: ||r_b||^2 carries r_u^2 and the gap w.z (prepare_kernel), b_norm is ||(b, u_U)|| (ipm_set_bounds), mu divides by n + |U|.
 // Detect: the infeasibility tests (detect_fire) where the convergence test says "continue", before the iteration cap.
@@ -351,9 +292,8 @@ __global__ __launch_bounds__(256) void certificate_kernel(const double* x, const
     for (int i = gid; i < m; i += gsz) oy[i] = primal ? y[i] * sc : 0.0;
 }
 
-// direction recovery + ratio test.  corr == 0: (dxa, dsa) from dya with q = r3/x;
-// corr == 1: (dx, ds) from dy with the corrector q.  Bounded, on U: dw = -r_u - dx, dz = -(r4 + z dw)/w (qz = r4/w), and the
-// ratio tests also run over w (primal) and z (dual); dw = dz = 0 outside U.
+// direction_column + ratio test.  corr == 0: (dxa, dsa[, dwa, dza]) from dya with the predictor's q;
+// corr == 1: (dx, ds[, dw, dz]) from dy with the corrector's q.
 template <bool Bounded = false>
 __device__ __forceinline__ void direction_kernel_body(VecArgs a, int corr, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     if (a.sc->done) return;
@@ -363,26 +303,9 @@ __device__ __forceinline__ void direction_kernel_body(VecArgs a, int corr, const
     double* DS = corr ? a.ds : a.dsa;
     double mp_ = 1.0, md_ = 1.0;
     for (int j = gid; j < a.n; j += gsz) {
-        double xj = a.x[j], sj = a.s[j];
-        double w = col_sum(a.atp, a.rc_chunks, a.np, j);
-        double dxj = a.d[j] * w + a.v[j];                 // main.py:227
-        double dsj = (-sj * dxj) / xj - a.q[j];           // main.py:228
-        DX[j] = dxj; DS[j] = dsj;
-        if (dxj < 0.0) mp_ = fmin(mp_, -xj / dxj);
-        if (dsj < 0.0) md_ = fmin(md_, -sj / dsj);
-        if constexpr (Bounded) {
-            const double uj = bd.u[j];
-            double dwj = 0.0, dzj = 0.0;
-            if (bnd_in(uj)) {
-                const double wj = bd.w[j], zj = bd.z[j];
-                dwj = -(xj + wj - uj) - dxj;
-                dzj = (-zj * dwj) / wj - bd.qz[j];
-                if (dwj < 0.0) mp_ = fmin(mp_, -wj / dwj);
-                if (dzj < 0.0) md_ = fmin(md_, -zj / dzj);
-            }
-            (corr ? bd.dw : bd.dwa)[j] = dwj;
-            (corr ? bd.dz : bd.dza)[j] = dzj;
-        }
+        const double xj = a.x[j], sj = a.s[j];
+        const double w = col_sum(a.atp, a.rc_chunks, a.np, j);
+        direction_column<Bounded>(a, bd, j, w, DX, DS, corr ? bd.dw : bd.dwa, corr ? bd.dz : bd.dza, xj, sj, mp_, md_);
     }
     mp_ = block_min(mp_, red); md_ = block_min(md_, red);
     if (threadIdx.x == 0) {
@@ -393,7 +316,7 @@ __device__ __forceinline__ void direction_kernel_body(VecArgs a, int corr, const
 __global__ __launch_bounds__(VBLK) void direction_kernel(VecArgs a, int corr) { direction_kernel_body(a, corr, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void direction_bounded_kernel(VecArgs a, int corr, BndArgs bd) { direction_kernel_body<true>(a, corr, blockIdx.x, gridDim.x, bd); }
 
-// partial sums of (x + a_p dxa).(s + a_d dsa)      main.py:579-584, 598   (Bounded: + (w + a_p dwa).(z + a_d dza))
+// partial sums of mu_aff_column at the affine step lengths
 template <bool Bounded = false>
 __device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     if (a.sc->done) return;
@@ -402,10 +325,7 @@ __device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_
     const double ap = min_partials(a.part, P_MINP_AFF, a.nblk);
     const double ad = min_partials(a.part, P_MIND_AFF, a.nblk);
     double acc = 0.0;
-    for (int j = gid; j < a.n; j += gsz) {
-        acc += (a.x[j] + ap * a.dxa[j]) * (a.s[j] + ad * a.dsa[j]);
-        if constexpr (Bounded) acc += (bd.w[j] + ap * bd.dwa[j]) * (bd.z[j] + ad * bd.dza[j]);      // 0 outside U
-    }
+    for (int j = gid; j < a.n; j += gsz) mu_aff_column<Bounded>(a, bd, j, ap, ad, acc);
     acc = block_sum(acc, red);
     if (threadIdx.x == 0) {
         a.part[P_MUAFF * MAXPART + bx_] = acc;
@@ -415,65 +335,34 @@ __device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_
 __global__ __launch_bounds__(VBLK) void mu_aff_kernel(VecArgs a) { mu_aff_kernel_body(a, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void mu_aff_bounded_kernel(VecArgs a, BndArgs bd) { mu_aff_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 
-// corrector: r3c = x s + dxa dsa - sigma mu ; q = r3c/x ; v = d (r_c - q)     main.py:150-152
-// Bounded, on U: r4c = w z + dwa dza - sigma mu ; qz = r4c/w ; v = theta (r_c - q + (r4c - z r_u)/w) ; mu_aff over n + |U|
+// centring from the re-summed partials of mu_aff_kernel, then corrector_column
 template <bool Bounded = false>
 __device__ __forceinline__ void corrector_rhs_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     if (a.sc->done) return;
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     const double mu = a.sc->mu;
-    const double mu_aff = sum_partials(a.part, P_MUAFF, a.nblk) / (Bounded ? (double)(a.n + bd.nU) : (double)a.n);
-    const double r = mu_aff / mu;
-    const double sigma = r * r * r;
-    const double sm = sigma * mu;
-    for (int j = gid; j < a.n; j += gsz) {
-        double xj = a.x[j];
-        double r3c = xj * a.s[j] + a.dxa[j] * a.dsa[j] - sm;
-        double qj = r3c / xj;
-        a.q[j] = qj;
-        if constexpr (Bounded) {
-            const double uj = bd.u[j];
-            if (bnd_in(uj)) {
-                const double wj = bd.w[j], zj = bd.z[j];
-                const double r4c = wj * zj + bd.dwa[j] * bd.dza[j] - sm;
-                bd.qz[j] = r4c / wj;
-                a.v[j] = a.d[j] * (a.rc[j] - qj + (r4c - zj * (xj + wj - uj)) / wj);
-                continue;
-            }
-        }
-        a.v[j] = a.d[j] * (a.rc[j] - qj);
-    }
-    if (gid == 0) { a.sc->mu_aff = mu_aff; a.sc->sigma = sigma; }
+    const Centring ct = centring<Bounded>(sum_partials(a.part, P_MUAFF, a.nblk), mu, a.n, bd);
+    const double sm = ct.sigma * mu;
+    for (int j = gid; j < a.n; j += gsz) corrector_column<Bounded>(a, bd, j, sm);
+    if (gid == 0) { a.sc->mu_aff = ct.mu_aff; a.sc->sigma = ct.sigma; }
 }
 __global__ __launch_bounds__(VBLK) void corrector_rhs_kernel(VecArgs a) { corrector_rhs_kernel_body(a, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void corrector_rhs_bounded_kernel(VecArgs a, BndArgs bd) { corrector_rhs_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 
-// x += a_p dx ; y += a_d dy ; s += a_d ds ; k += 1          main.py:604-626, 694-696   (Bounded: w += a_p dw ; z += a_d dz)
+// damped_step from the re-summed ratio-test minima, update_column, y += a_d dy, record_iteration
 template <bool Bounded = false>
 __device__ __forceinline__ void update_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     if (a.sc->done) return;
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     const double eta = a.sc->eta;
-    const double ap = fmin(1.0, eta * min_partials(a.part, P_MINP, a.nblk));
-    const double ad = fmin(1.0, eta * min_partials(a.part, P_MIND, a.nblk));
-    for (int j = gid; j < a.n; j += gsz) {
-        a.x[j] += ap * a.dx[j];
-        a.s[j] += ad * a.ds[j];
-        if constexpr (Bounded) {
-            bd.w[j] += ap * bd.dw[j];
-            bd.z[j] += ad * bd.dz[j];
-        }
-    }
+    const double ap = damped_step(eta, min_partials(a.part, P_MINP, a.nblk));
+    const double ad = damped_step(eta, min_partials(a.part, P_MIND, a.nblk));
+    for (int j = gid; j < a.n; j += gsz) update_column<Bounded>(a, bd, j, ap, ad);
     for (int i = gid; i < a.m; i += gsz) a.y[i] += ad * a.dy[i];
     if (gid == 0) {
         Scalars* sc = a.sc;
-        const int k = sc->k;
-        if (k == 0) sc->fixed_first = sc->fixed;
-        IterRec r;
-        r.k = k; r.fixed = sc->fixed; r.obj = sc->obj; r.rb = sc->rb_norm; r.rc = sc->rc_norm; r.gap = sc->gap;
-        r.mu = sc->mu; r.sigma = sc->sigma; r.aap = sc->alpha_aff_p; r.aad = sc->alpha_aff_d; r.ap = ap; r.ad = ad;
-        a.hist[k % HIST_CAP] = r;
-        sc->alpha_p = ap; sc->alpha_d = ad; sc->k = k + 1;
+        if (sc->k == 0) sc->fixed_first = sc->fixed;
+        record_iteration(sc, a.hist, sc->mu, sc->sigma, sc->alpha_aff_p, sc->alpha_aff_d, ap, ad);
     }
 }
 __global__ __launch_bounds__(VBLK) void update_kernel(VecArgs a) { update_kernel_body(a, blockIdx.x, gridDim.x); }
