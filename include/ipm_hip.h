@@ -194,6 +194,19 @@ int ipm_set_state(ipm_handle* h, const double* x, const double* y, const double*
 int ipm_get_state(ipm_handle* h, double* x, double* y, double* s);                    /* host */
 /* x = s = 1, y = y0: sparse_interior.py:193-200 (y0=1) / main.py:287-302 (y0=0); with bounds set also w = z = 1 on U */
 int ipm_init_state(ipm_handle* h, double y0);
+/* Mehrotra's starting point (SIAM J. Optim. 2 (1992) 575-601, section 7) computed ON THE DEVICE from the handle's own A, b, c (and u):
+ * x = A^T (A A^T)^-1 b and y = (A A^T)^-1 A c, s = c - A^T y, shifted into the positive orthant and balanced; with bounds set also
+ * (w, z): w = u - x and the reduced cost split into s = max(r, 0), z = max(-r, 0) on U, (x, w) and (s, z) shifted together and
+ * balanced with x.s + w.z.  Not the reference's start: an optional mode that changes the trajectory.  A A^T is
+ * factored with the handle's current guard and `regularize` settings exactly as ipm_normal_solve(h, NULL, ...) does; *pivots_fixed
+ * (may be NULL) = its guarded pivots, i.e. the dependent rows of A.  No host arithmetic, no host copy of A; one stream
+ * synchronisation at the end (plus ipm_normal_solve's retry after a recovered poll time-out).  Degenerate data (x.s + w.z not finite
+ * or not positive, or a non-positive sum) gives the reference's start x = s = 1, y = 1, w = z = 1 on U, decided on the device.  y is
+ * in the handle's row order, as ipm_get_state returns it.  Works on every handle kind (dense, sparse on the envelope factor,
+ * IPM_FLAG_SPARSE_FACTOR, IPM_FLAG_LOCKSTEP before ipm_batch_add, the fused small path), bounded or not, and leaves the handle as
+ * ipm_init_state does (the iteration count and the history restart with the next solve).  IPM_ERR_INVALID_ARG for a NULL handle,
+ * IPM_ERR_STATE without A or without (b, c). */
+int ipm_init_state_mehrotra(ipm_handle* h, int32_t* pivots_fixed);
 
 /* ---- native upper bounds 0 <= x <= u ------------------------------------------------- */
 /* u: host array of length n, +inf where x_j has no upper bound; u == NULL (or all +inf) removes the bounds, and the
@@ -265,6 +278,13 @@ int ipm_batch_stats(ipm_batch* b, int32_t index, ipm_stats* stats);
  * communicate and an LP's arithmetic is that of ipm_solve on it alone: bit-identical iterates, whatever the order of the handles. */
 int ipm_solve_small_batch(ipm_handle** handles, int32_t n, double tol_p, double tol_d, double tol_gap, int32_t max_iter, void* stream,
                           ipm_stats* stats);
+/* ipm_init_state_mehrotra for n handles of the fused small-LP path in ONE launch per variant (plain / bounded), one workgroup per LP.
+ * Arguments are checked exactly as by ipm_solve_small_batch (NULL handle, not on the small path, other device, the same handle twice:
+ * IPM_ERR_INVALID_ARG; n == 0: IPM_OK, no device touched), except that no state is needed (IPM_ERR_STATE without A or (b, c)); `stream`
+ * has the same meaning and the same event waits on the handles' own streams apply.  pivots_fixed (may be NULL): n counts,
+ * pivots_fixed[i] is handle i's.  The workgroups never communicate: each handle's (x, y, s[, w, z]) is bit-identical to
+ * ipm_init_state_mehrotra on it alone, whatever the order of the handles.  One host synchronisation however large n is. */
+int ipm_init_small_batch_mehrotra(ipm_handle** handles, int32_t n, void* stream, int32_t* pivots_fixed);
 /* Tolerances of the infeasibility tests (IPM_FLAG_DETECT_INFEASIBILITY), each in (0, 1); default 1e-8 / 1e-8.  Takes effect
  * with the next solve (for the lockstep batch: with the next ipm_batch_add). */
 int ipm_set_infeasibility_tol(ipm_handle* h, double eps_p, double eps_d);

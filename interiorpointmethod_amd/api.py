@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .analysis import _upper_bounds
-from .handle import STATUS_NAMES, IpmSolver
+from .handle import STATUS_NAMES, IpmSolver, mehrotra_started, shift_allowed, wants_shift
 
 
 def _info(solver, cTlb=0.0):
@@ -54,38 +54,44 @@ def last_info():
     return _last_info
 
 
+def _auto_regularize():          # the process-wide switch of the 5 % rule (handle.wants_shift)
+    return os.environ.get("IPM_AUTO_REGULARIZE", "1") != "0"
+
+
 def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
-                    history=False, ub=None, detect_infeasibility=False, **opts):
+                    history=False, ub=None, detect_infeasibility=False, device_start=False, **opts):
     """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
-    start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start().
+    start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start(), or with
+    device_start=True IpmSolver.init_state_mehrotra(): the same start computed on the device (no host copy of A, one
+    synchronisation; equal to rounding, so the trajectory may differ in the last bits).
     history=True adds info["history"], the per-iteration records (IpmSolver.history()).  An LP whose A has more
     than 5 % dependent rows (the QAP family) is solved with the 1e-14 Tikhonov shift, switched on by the library
     after the first factorization (info["auto_regularized"] == 1; auto_regularize=False keeps it off).
     ub: native upper bounds 0 <= x <= ub (+inf = none): info["bounded"] = |U| and, when |U| > 0, info["w"], info["z"].
     detect_infeasibility=True: the solve may end in status 5 / 6 (IpmSolver); info["certificate"] = IpmSolver.certificate()."""
     global _last_info
+    if start not in ("reference", "mehrotra"):
+        raise ValueError('start must be "reference" or "mehrotra"')
     ub = _upper_bounds(ub, np.asarray(c).reshape(-1).shape[0])
-    if start == "mehrotra" and not opts.get("regularize") and os.environ.get("IPM_AUTO_REGULARIZE", "1") != "0":
-        # the least-squares start factors A A^T: guarded pivots there are dependent rows of A.  Where they are a
-        # sizeable fraction of the rows (the QAP family: 9-16 %; every other Netlib file: at most 2.7 %) the guard alone
-        # stalls the loop (DESIGN.md 2) and the 1e-14 Tikhonov shift is switched on; a handful of dependent rows is left
-        # to the guard (the shift breaks 25FV47, BNL1, D6CUBE, WOOD1P, which have 1-11 of them)
+    on_device = start == "mehrotra" and device_start
+    if start == "mehrotra" and not on_device and shift_allowed(opts.get("regularize"), _auto_regularize()):
+        # the least-squares start factors A A^T: guarded pivots there are dependent rows of A (handle.wants_shift: the 5 % rule).
+        # The device start reports the count itself; the host recipe asks a probe handle for it.
         with IpmSolver(A, b, c, device=device, **opts) as probe:
             probe.normal_solve(np.zeros(probe.m))
-            if probe.last_pivots_fixed > 0.05 * probe.m:
+            if wants_shift(probe.last_pivots_fixed, probe.m):
                 opts = dict(opts, regularize=1e-14)
     import time as _time
     t0 = _time.perf_counter()
     if detect_infeasibility:
         opts = dict(opts, detect_infeasibility=True)
-    with IpmSolver(A, b, c, device=device, ub=ub, **opts) as sv:
+    make = lambda **extra: IpmSolver(A, b, c, device=device, ub=ub, **dict(opts, **extra))          # noqa: E731
+    with (mehrotra_started(make, opts.get("regularize"), _auto_regularize()) if on_device else make()) as sv:
         t1 = _time.perf_counter()
-        if start == "mehrotra":
+        if start == "mehrotra" and not on_device:
             sv.set_state(*sv.mehrotra_start())
         elif start == "reference":
             sv.init_state(y0)
-        else:
-            raise ValueError('start must be "reference" or "mehrotra"')
         sv.solve(tol=tol, max_iter=max_iter, tol_gap=tol_gap)
         t2 = _time.perf_counter()
         x, y, s = sv.get_state()

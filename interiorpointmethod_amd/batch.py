@@ -23,9 +23,9 @@ import numpy as np
 
 from . import _lib
 from .analysis import prepare
-from .api import _solve_info, solve_with_info
+from .api import _auto_regularize, _solve_info, solve_with_info
 from .batches import LockstepBatch, lockstep_eligible, small_batch_eligible, solve_small_batch_solvers
-from .handle import IpmSolver
+from .handle import IpmSolver, mehrotra_started
 
 # One record per LP.  The first nine fields are the statistics SURVEY.md 8e names; the rest make the library's hidden
 # recoveries and the host-side phases of a solve visible in the gathered table: `timeouts_recovered` = device hand-off
@@ -95,15 +95,16 @@ def _guarded(solve_fn, problem, **kw):
 
 
 def solve_one(problem, device=0, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, concurrent=False, start="reference",
-              tol_gap=None, detect_infeasibility=False):
+              tol_gap=None, detect_infeasibility=False, device_start=False):
     """Solve one LP (A, b, c) on `device` with the HIP path -> dict of statistics.  detect_infeasibility: the record's status
-    may be 5 (primal infeasible) or 6 (dual infeasible, i.e. unbounded); DESIGN.md 4-C."""
+    may be 5 (primal infeasible) or 6 (dual infeasible, i.e. unbounded); DESIGN.md 4-C.  device_start: with start="mehrotra", the
+    start is computed on the device (solve_with_info)."""
     A, b, c = problem
     t0 = time.perf_counter()
     try:
         _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device,
                                         regularize=regularize, concurrent=concurrent, start=start, tol_gap=tol_gap,
-                                        detect_infeasibility=detect_infeasibility)
+                                        detect_infeasibility=detect_infeasibility, device_start=device_start)
         info = dict(info)
     except Exception as e:          # every failure becomes a record: the rank must still reach the all-gather
         _report_failure(A, e)
@@ -213,8 +214,9 @@ def _lockstep_streams(device, n):
 class _LockstepShard:
     """One solve_shard_lockstep call: its state and its steps.  An item is (record row, LP id, solver, setup seconds): a ready handle."""
 
-    def __init__(self, problems, ids, device, workers, small_batch, y0, stop_kw, handle_kw):
+    def __init__(self, problems, ids, device, workers, small_batch, y0, stop_kw, handle_kw, start="reference"):
         self.problems, self.ids, self.device, self.workers, self.small_batch, self.y0 = problems, ids, device, workers, small_batch, y0
+        self.start = start                  # "reference": init_state(y0); "mehrotra": the device start, on the set-up thread's stream
         self.stop_kw = stop_kw              # tol, max_iter, tol_gap: of every solve of the shard
         self.handle_kw = handle_kw          # device, regularize, concurrent=True, detect_infeasibility: of every handle of the shard
         self.rec = np.zeros((len(ids), NF), dtype=np.float64)
@@ -280,16 +282,29 @@ class _LockstepShard:
         info["seconds"] = setup_s + (t_done - t_join)
         self.rec[row] = _row(i, info)
 
-    # -- the pool: set-up of every LP (host analysis, handle, upload)
+    # -- the pool: set-up of every LP (host analysis, handle, upload, start)
+    def _started(self, A, b, c, prepared, **kw):
+        """The handle of one LP at the shard's start: init_state(y0), or Mehrotra's start computed on the device (with the 5 % rule,
+        handle.mehrotra_started)."""
+        make = lambda **extra: IpmSolver(A, b, c, prepared=prepared, **dict(self.handle_kw, **kw, **extra))          # noqa: E731
+        if self.start == "mehrotra":
+            return mehrotra_started(make, self.handle_kw.get("regularize"), _auto_regularize())
+        sv = make()
+        try:
+            sv.init_state(self.y0)
+        except Exception:
+            sv.close()
+            raise
+        return sv
+
     def _small_setup(self, problem, device=0, row=None, i=None, prepared=None, t0=None):
         # the handle _classic() would create for this LP; False: the library does not put it on the small path
         A, b, c = problem
-        sv = IpmSolver(A, b, c, prepared=prepared, **self.handle_kw)
+        sv = self._started(A, b, c, prepared)
         try:
             if not small_batch_eligible(sv):
                 sv.close()
                 return False
-            sv.init_state(self.y0)
         except Exception:
             sv.close()
             raise
@@ -308,9 +323,8 @@ class _LockstepShard:
             # would take the sparse one: inside a batch an LP whose program is shorter than the class leader's adds no launches
             prepared = prepare(A, b, c, factor=("dense" if self._wants_lockstep(i) and A.shape[0] <= LOCKSTEP_DENSE_ROWS else None))
             if self._wants_lockstep(i) and prepared.factor != "sparse":
-                sv = IpmSolver(A, b, c, lockstep=True, prepared=prepared, **self.handle_kw)
+                sv = self._started(A, b, c, prepared, lockstep=True)      # (the start runs on the handle's own stream, before it joins)
                 if lockstep_eligible(sv):
-                    sv.init_state(self.y0)
                     ready.put((row, i, sv, time.perf_counter() - t0))
                     handed = True
                     return
@@ -335,7 +349,7 @@ class _LockstepShard:
     # -- the one-at-a-time runners: the LPs no batch serves
     def _classic(self, problem, device=0, prepared=None):
         A, b, c = problem
-        _, _, _, info = solve_with_info(A, b, c, y0=self.y0, prepared=prepared, **self.stop_kw, **self.handle_kw)
+        _, _, _, info = solve_with_info(A, b, c, y0=self.y0, prepared=prepared, start=self.start, device_start=True, **self.stop_kw, **self.handle_kw)
         return dict(info)
 
     def _classic_runner(self, own):     # own: ONE stream per runner for all its LPs (a new stream per LP walks through the hardware queues)
@@ -421,7 +435,7 @@ class _LockstepShard:
 
 
 def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, tol_gap=None,
-                         detect_infeasibility=False, small_batch=False, **_):
+                         detect_infeasibility=False, small_batch=False, start="reference", **_):
     """Solve problems[i] for i in ids on this rank's GPU with the LOCKSTEP BATCH -> (len(ids), NF) records.
 
     `workers` host threads prepare the LPs (host analysis, handle, upload), largest first.  An LP of more than 128 rows on the
@@ -435,9 +449,16 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
 
     small_batch=True (opt-in): the LPs of up to 128 rows that the fused single-workgroup kernel serves are not solved one after the
     other but collected, and ONE ipm_solve_small_batch call solves them, one workgroup per LP, once every LP of the shard is set up
-    (batches.solve_small_batch_solvers).  Same records, bit for bit (tests/test_gpu_small_batch.py)."""
+    (batches.solve_small_batch_solvers).  Same records, bit for bit (tests/test_gpu_small_batch.py).
+
+    start="mehrotra": every handle's set-up thread computes Mehrotra's starting point on the device (IpmSolver.init_state_mehrotra, with
+    the 5 % rule of handle.wants_shift) on its worker stream before the handle joins its batch, the small-batch handles included; the
+    LPs solved one after the other start the same way.  start="reference": every record is what it was without the keyword."""
+    if start not in ("reference", "mehrotra"):
+        raise ValueError('start must be "reference" or "mehrotra"')
     return _LockstepShard(problems, ids, device, workers, small_batch, y0, dict(tol=tol, max_iter=max_iter, tol_gap=tol_gap),
-                          dict(device=device, regularize=regularize, concurrent=True, detect_infeasibility=detect_infeasibility)).run()
+                          dict(device=device, regularize=regularize, concurrent=True, detect_infeasibility=detect_infeasibility),
+                          start=start).run()
 
 
 def gather_records(local, shard_sizes, dist=None, device=None):
@@ -578,7 +599,7 @@ def run_batch(problems, costs=None, device=0, dist=None, gather_device=None, sol
         return _gather_sparse(local, dist, device=gather_device), seconds
     shards = lpt_partition(costs, world)
     if lockstep:
-        local = solve_shard_lockstep(problems, shards[rank], device=device, workers=workers, **{k: v for k, v in kw.items() if k != "start"})
+        local = solve_shard_lockstep(problems, shards[rank], device=device, workers=workers, **kw)
     else:
         local = solve_shard(problems, shards[rank], device=device, solve_fn=solve_fn, workers=workers, **kw)
     seconds = time.perf_counter() - t0

@@ -5,8 +5,8 @@ import numpy as np
 
 from . import _lib
 from .analysis import FUSED_SMALL_MAX_ROWS, _sp, _upper_bounds
-from .api import _solve_info
-from .handle import IpmSolver, _gap_tol
+from .api import _auto_regularize, _solve_info
+from .handle import IpmSolver, _gap_tol, wants_shift
 
 
 def _handle_array(solvers):           # (the handles as a C array, a Stats array of the same length) for one batched library call
@@ -114,6 +114,28 @@ def solve_small_batch_solvers(solvers, tol=1e-8, max_iter=5000, tol_gap=None, st
     return _scatter_stats(solvers, st)
 
 
+def init_small_batch_mehrotra(solvers, stream=None):
+    """ipm_init_small_batch_mehrotra: Mehrotra's starting point (IpmSolver.init_state_mehrotra) for every solver of `solvers` (on the
+    fused small-LP path, one device) in ONE launch per kernel variant, one workgroup per LP -> list of the guarded-pivot counts of
+    A A^T, one per solver (also in solver.last_pivots_fixed).  Each solver's state is bit-identical to its own init_state_mehrotra().
+    stream: a torch.cuda.Stream for the launches (None: the first solver's stream).  ValueError, naming the index, for a solver that
+    is not on the small path."""
+    lib = _lib.load()
+    solvers = list(solvers)
+    if not solvers:
+        return []
+    for i, sv in enumerate(solvers):
+        if not small_batch_eligible(sv):
+            raise ValueError("solver %d (%d x %d) is not on the fused small-LP path (sparse A, at most %d rows)"
+                             % (i, sv.m, sv.n, FUSED_SMALL_MAX_ROWS))
+    hs, _ = _handle_array(solvers)
+    nfix = (C.c_int32 * len(solvers))()
+    _lib.check(None, lib.ipm_init_small_batch_mehrotra(hs, len(solvers), C.c_void_p(stream.cuda_stream) if stream is not None else None, nfix))
+    for sv, k in zip(solvers, nfix):
+        sv.last_pivots_fixed = int(k)
+    return [int(k) for k in nfix]
+
+
 def _small_batch_host_check(problems, ub):
     """Host part of solve_small_batch (no device is touched): shapes, the row limit of the small path and the bounds ->
     list of (A as CSC, b, c, ub)."""
@@ -142,13 +164,18 @@ def _small_batch_host_check(problems, ub):
 
 
 def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, ub=None, detect_infeasibility=False,
-                      regularize=0.0):
+                      regularize=0.0, start="reference"):
     """Solve many small LPs at once -> list of (x, y, s, info), one per problem, each what solve_with_info returns for it alone.
 
     problems: list of (A, b, c) with at most 128 rows each; a dense A is converted to CSC.  ub: None or one entry per problem (None or
     a length-n vector, +inf = none).  One IpmSolver per LP on the current torch stream, init_state(y0), ONE ipm_solve_small_batch
-    call (one workgroup per LP), read-back, close.  An LP the library does not put on the small path (more than 128 rows, or a
-    product list of A D^2 A^T beyond its cap) raises ValueError naming its index before anything is launched."""
+    call (one workgroup per LP), read-back, close.  start="mehrotra": ONE ipm_init_small_batch_mehrotra call instead of the
+    init_state(y0) loop (each LP then equals solve_with_info(start="mehrotra", device_start=True) for it alone; an LP past the 5 % rule
+    of handle.wants_shift gets its handle again with regularize=1e-14 and its own start).  An LP the library does not put on the
+    small path (more than 128 rows, or a product list of A D^2 A^T beyond its cap) raises ValueError naming its index before anything
+    is launched."""
+    if start not in ("reference", "mehrotra"):
+        raise ValueError('start must be "reference" or "mehrotra"')
     checked = _small_batch_host_check(problems, ub)
     solvers = []
     try:
@@ -158,7 +185,15 @@ def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_g
             if not small_batch_eligible(sv):
                 raise ValueError("problem %d (%d x %d) is not served by the fused small-LP path (its product list is too large)"
                                  % (i, sv.m, sv.n))
-            sv.init_state(y0)
+            if start == "reference":
+                sv.init_state(y0)
+        if start == "mehrotra":
+            for i, nfix in enumerate(init_small_batch_mehrotra(solvers)):
+                if wants_shift(nfix, solvers[i].m, regularize, _auto_regularize()):
+                    A, b, c, u = checked[i]
+                    solvers[i].close()
+                    solvers[i] = IpmSolver(A, b, c, device=device, regularize=1e-14, ub=u, detect_infeasibility=detect_infeasibility)
+                    solvers[i].init_state_mehrotra()
         solve_small_batch_solvers(solvers, tol=tol, max_iter=max_iter, tol_gap=tol_gap)
         return [sv.get_state() + (_solve_info(sv, certificate=detect_infeasibility),) for sv in solvers]
     finally:

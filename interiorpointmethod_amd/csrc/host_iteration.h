@@ -281,6 +281,45 @@ static int enqueue_small(ipm_handle* h, int max_steps, int auto_reg) {
     return IPM_OK;
 }
 
+// The kernels of Mehrotra's start on the fused small-LP path (small_lp.h, small_start_body): the single-LP kernel on a host item, or
+// `grid` workgroups of the batch kernel on the device table d_items.  The start has two variants only (the tests of a Detect handle
+// play no part in it).
+static void launch_small_start(bool bounded, hipStream_t S, const SmallItem* one, const SmallItem* d_items, unsigned grid) {
+    const dim3 g(one ? 1u : grid), b(PD_THREADS);
+    if (!bounded) { if (one) hipLaunchKernelGGL(small_start_kernel, g, b, 0, S, one->lp); else hipLaunchKernelGGL(small_start_batch_kernel, g, b, 0, S, d_items); }
+    else { if (one) hipLaunchKernelGGL(small_start_bounded_kernel, g, b, 0, S, one->lp, one->bd); else hipLaunchKernelGGL(small_start_batch_bounded_kernel, g, b, 0, S, d_items); }
+}
+
+// what every entry that sets a new iterate leaves in the handle (ipm_init_state, ipm_set_state)
+static void mark_fresh_state(ipm_handle* h) {
+    h->haveState = true; h->predictor_valid = false; h->fresh_state = true;
+    h->h_sc->status = 0;                                       // (a certificate describes the iterate of its detection only)
+}
+
+extern "C" int ipm_init_state_mehrotra(ipm_handle* h, int32_t* pivots_fixed) {
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_init_state_mehrotra: NULL handle");
+    if (!h->haveA) return fail(h, IPM_ERR_STATE, "ipm_init_state_mehrotra: A not set");
+    if (!h->haveBC) return fail(h, IPM_ERR_STATE, "ipm_init_state_mehrotra: (b, c) not set");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    for (int attempt = 0;; ++attempt) {                     // second pass only after a recovered poll time-out
+        hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, h->stream, h->sc, 1e-8, 1e-8, 1e-8, h->opt.eta, 1 << 30, 1, 1);
+        if (h->small) {
+            const SmallItem it = small_item(h, 0, 0, 0);
+            launch_small_start(h->bnd, h->stream, &it, nullptr, 1);
+            HIP_TRY(h, hipGetLastError());
+        } else if ((rc = enqueue_mehrotra_start(h))) return rc;
+        bool tmo = false;
+        if ((rc = read_scalars(h, &tmo))) return rc;           // the one synchronisation
+        if (!tmo) break;
+        if (attempt) return fail(h, IPM_ERR_HIP, "hand-off time-out persists with stream events");
+        poll_fallback(h);
+    }
+    if (pivots_fixed) *pivots_fixed = h->h_sc->fixed;
+    mark_fresh_state(h);
+    return IPM_OK;
+}
+
 extern "C" int ipm_iterate(ipm_handle* h, int32_t n_steps, ipm_stats* stats) {
     int rc = check_ready(h, "ipm_iterate");
     if (rc) return rc;

@@ -1,4 +1,4 @@
-// host_small_batch.h -- host side, unit 9: ipm_solve_small_batch, many small LPs (fused single-workgroup path, small_lp.h) in one
+// host_small_batch.h -- host side, unit 9: ipm_solve_small_batch and ipm_init_small_batch_mehrotra, many small LPs (fused single-workgroup path, small_lp.h) in one
 // launch per kernel variant, one workgroup per LP.
 #pragma once
 // ------------------------------------------------------------------------------- batch of small LPs (small_lp.h)
@@ -43,17 +43,16 @@ static int small_batch_round(ipm_handle* h0, ipm_handle** hs, const std::vector<
     return IPM_OK;
 }
 
-extern "C" int ipm_solve_small_batch(ipm_handle** hs, int32_t n, double tol_p, double tol_d, double tol_gap, int32_t max_iter, void* stream,
-                                     ipm_stats* stats) {
-    if (n < 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_small_batch: n = %d < 0", (int)n);
-    if (n == 0) return IPM_OK;                               // nothing to do: no device is touched
-    if (!hs) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_small_batch: handles is NULL (n = %d)", (int)n);
-    if (max_iter < 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_small_batch: max_iter < 0");
+// the argument rules both batch entries share: n, the array, and per handle NULL / not on the small path / another device / twice
+static int small_batch_check_handles(const char* who, ipm_handle** hs, int32_t n) {
+    if (n < 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: n = %d < 0", who, (int)n);
+    if (n == 0) return IPM_OK;
+    if (!hs) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handles is NULL (n = %d)", who, (int)n);
     for (int i = 0; i < n; ++i) {
         ipm_handle* h = hs[i];
-        if (!h) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_small_batch: handle %d is NULL", i);
-        if (!h->small) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_small_batch: handle %d is not on the fused small-LP path (sparse A of at most %d rows; ipm_get_schedule out[9])", i, SMALL_MAX_M);
-        if (h->device != hs[0]->device) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_small_batch: handle %d lives on device %d, handle 0 on device %d", i, h->device, hs[0]->device);
+        if (!h) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d is NULL", who, i);
+        if (!h->small) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d is not on the fused small-LP path (sparse A of at most %d rows; ipm_get_schedule out[9])", who, i, SMALL_MAX_M);
+        if (h->device != hs[0]->device) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d lives on device %d, handle 0 on device %d", who, i, h->device, hs[0]->device);
     }
     {   // the same handle twice: two workgroups would race on one state
         std::vector<std::pair<const ipm_handle*, int>> seen((size_t)n);
@@ -61,8 +60,33 @@ extern "C" int ipm_solve_small_batch(ipm_handle** hs, int32_t n, double tol_p, d
         std::sort(seen.begin(), seen.end());
         for (int i = 1; i < n; ++i)
             if (seen[(size_t)i].first == seen[(size_t)i - 1].first)
-                return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_small_batch: handle %d is the same handle as handle %d", seen[(size_t)i].second, seen[(size_t)i - 1].second);
+                return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d is the same handle as handle %d", who, seen[(size_t)i].second, seen[(size_t)i - 1].second);
     }
+    return IPM_OK;
+}
+// whatever the handles did on their own streams is complete before the batch touches them: one event per distinct stream
+static int small_batch_wait_streams(ipm_handle** hs, int32_t n, hipStream_t S) {
+    ipm_handle* h0 = hs[0];
+    std::vector<hipStream_t> waited;
+    for (int i = 0; i < n; ++i) {
+        ipm_handle* h = hs[i];
+        if (h->stream == S || std::find(waited.begin(), waited.end(), h->stream) != waited.end()) continue;
+        HIP_TRY(h0, hipEventRecord(h->ev_fork, h->stream));
+        HIP_TRY(h0, hipStreamWaitEvent(S, h->ev_fork, 0));
+        waited.push_back(h->stream);
+    }
+    return IPM_OK;
+}
+struct SmallBatchMem {                                       // the item table and the gathered records of a batch call, released on every return path
+    int device; hipStream_t S; SmallItem* items = nullptr; Scalars* sc = nullptr;
+    ~SmallBatchMem() { dev_free(device, S, items); dev_free(device, S, sc); }
+};
+
+extern "C" int ipm_solve_small_batch(ipm_handle** hs, int32_t n, double tol_p, double tol_d, double tol_gap, int32_t max_iter, void* stream,
+                                     ipm_stats* stats) {
+    if (int rc_ = small_batch_check_handles("ipm_solve_small_batch", hs, n)) return rc_;
+    if (n == 0) return IPM_OK;                               // nothing to do: no device is touched
+    if (max_iter < 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_small_batch: max_iter < 0");
     for (int i = 0; i < n; ++i) {
         ipm_handle* h = hs[i];
         if (!h->haveA || !h->haveBC || !h->haveState) return fail(nullptr, IPM_ERR_STATE, "ipm_solve_small_batch: handle %d: A, (b,c) and a state must be set first", i);
@@ -71,25 +95,13 @@ extern "C" int ipm_solve_small_batch(ipm_handle** hs, int32_t n, double tol_p, d
     ipm_handle* h0 = hs[0];
     HIP_TRY(h0, hipSetDevice(h0->device));
     hipStream_t S = stream ? (hipStream_t)stream : h0->stream;
-    {   // whatever the handles did on their own streams is complete before the batch touches them: one event per distinct stream
-        std::vector<hipStream_t> waited;
-        for (int i = 0; i < n; ++i) {
-            ipm_handle* h = hs[i];
-            if (h->stream == S || std::find(waited.begin(), waited.end(), h->stream) != waited.end()) continue;
-            HIP_TRY(h0, hipEventRecord(h->ev_fork, h->stream));
-            HIP_TRY(h0, hipStreamWaitEvent(S, h->ev_fork, 0));
-            waited.push_back(h->stream);
-        }
-    }
+    if (int rc_ = small_batch_wait_streams(hs, n, S)) return rc_;
     for (int i = 0; i < n; ++i) {                            // as ipm_solve starts a solve
         ipm_handle* h = hs[i];
         h->predictor_valid = false; h->fresh_state = false;
         if (h->auto_reg) { h->auto_reg = 0; h->shift_rel = h->opt.regularize; }
     }
-    struct Mem {                                             // released on every return path
-        int device; hipStream_t S; SmallItem* items = nullptr; Scalars* sc = nullptr;
-        ~Mem() { dev_free(device, S, items); dev_free(device, S, sc); }
-    } mem{h0->device, S};
+    SmallBatchMem mem{h0->device, S};
     HIP_TRY(h0, dev_malloc(h0->device, S, (void**)&mem.items, sizeof(SmallItem) * (size_t)n));
     HIP_TRY(h0, dev_malloc(h0->device, S, (void**)&mem.sc, sizeof(Scalars) * (size_t)n));
     std::vector<SmallItem> items;
@@ -110,5 +122,50 @@ extern "C" int ipm_solve_small_batch(ipm_handle** hs, int32_t n, double tol_p, d
     float ms = 0.f;
     HIP_TRY(h0, hipEventElapsedTime(&ms, h0->ev0, h0->ev1));
     if (stats) for (int i = 0; i < n; ++i) fill_stats(hs[i], &stats[i], ms);
+    return IPM_OK;
+}
+
+// Mehrotra's starting point for n handles of the small path in one launch per variant (plain / bounded), one workgroup per LP: the
+// batch form of ipm_init_state_mehrotra, with one copy of the scalar records to the host and one synchronisation.
+extern "C" int ipm_init_small_batch_mehrotra(ipm_handle** hs, int32_t n, void* stream, int32_t* pivots_fixed) {
+    if (int rc_ = small_batch_check_handles("ipm_init_small_batch_mehrotra", hs, n)) return rc_;
+    if (n == 0) return IPM_OK;                               // nothing to do: no device is touched
+    for (int i = 0; i < n; ++i)
+        if (!hs[i]->haveA || !hs[i]->haveBC) return fail(nullptr, IPM_ERR_STATE, "ipm_init_small_batch_mehrotra: handle %d: A and (b,c) must be set first", i);
+    ipm_handle* h0 = hs[0];
+    HIP_TRY(h0, hipSetDevice(h0->device));
+    hipStream_t S = stream ? (hipStream_t)stream : h0->stream;
+    if (int rc_ = small_batch_wait_streams(hs, n, S)) return rc_;
+    SmallBatchMem mem{h0->device, S};
+    HIP_TRY(h0, dev_malloc(h0->device, S, (void**)&mem.items, sizeof(SmallItem) * (size_t)n));
+    HIP_TRY(h0, dev_malloc(h0->device, S, (void**)&mem.sc, sizeof(Scalars) * (size_t)n));
+    std::vector<int> order((size_t)n);
+    for (int i = 0; i < n; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {      // plain first, inside a variant the long LPs first (small_cost)
+        if (hs[a]->bnd != hs[b]->bnd) return !hs[a]->bnd;
+        return small_cost(hs[a]) > small_cost(hs[b]);
+    });
+    std::vector<SmallItem> items((size_t)n);
+    int nplain = 0;
+    for (int p = 0; p < n; ++p) {
+        items[(size_t)p] = small_item(hs[order[(size_t)p]], p, 0, 0);
+        if (!hs[order[(size_t)p]]->bnd) ++nplain;
+    }
+    HIP_TRY(h0, hipMemcpyAsync(mem.items, items.data(), sizeof(SmallItem) * (size_t)n, hipMemcpyHostToDevice, S));
+    const unsigned g256 = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(small_batch_params_kernel, dim3(g256), dim3(256), 0, S, mem.items, (int)n, 1e-8, 1e-8, 1e-8, 1 << 30);
+    if (nplain) launch_small_start(false, S, nullptr, mem.items, (unsigned)nplain);
+    if (n - nplain) launch_small_start(true, S, nullptr, mem.items + nplain, (unsigned)(n - nplain));
+    hipLaunchKernelGGL(small_batch_gather_kernel, dim3(g256), dim3(256), 0, S, mem.items, (int)n, mem.sc);
+    HIP_TRY(h0, hipGetLastError());
+    std::vector<Scalars> host_sc((size_t)n);
+    HIP_TRY(h0, hipMemcpyAsync(host_sc.data(), mem.sc, sizeof(Scalars) * (size_t)n, hipMemcpyDeviceToHost, S));
+    HIP_TRY(h0, hipStreamSynchronize(S));
+    for (int p = 0; p < n; ++p) {
+        ipm_handle* h = hs[order[(size_t)p]];
+        *h->h_sc = host_sc[(size_t)p];
+        if (pivots_fixed) pivots_fixed[order[(size_t)p]] = h->h_sc->fixed;
+        mark_fresh_state(h);
+    }
     return IPM_OK;
 }

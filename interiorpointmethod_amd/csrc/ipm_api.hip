@@ -365,8 +365,7 @@ extern "C" int ipm_set_state(ipm_handle* h, const double* x, const double* y, co
     HIP_TRY(h, hipMemcpyAsync(h->y, y, sizeof(double) * h->m, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->s, s, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->haveState = true; h->predictor_valid = false; h->fresh_state = true;
-    h->h_sc->status = 0;                                       // (a certificate describes the iterate of its detection only)
+    mark_fresh_state(h);
     return IPM_OK;
 }
 
@@ -463,8 +462,7 @@ extern "C" int ipm_init_state(ipm_handle* h, double y0) {
     int rc = enqueue_init_state(h, y0);
     if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->haveState = true; h->predictor_valid = false; h->fresh_state = true;
-    h->h_sc->status = 0;                                       // (a certificate describes the iterate of its detection only)
+    mark_fresh_state(h);
     return IPM_OK;
 }
 

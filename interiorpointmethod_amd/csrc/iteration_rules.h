@@ -1,6 +1,7 @@
 // iteration_rules.h -- the Mehrotra predictor-corrector iteration, stated once (gfx950): the device-resident state of a solve
 // and the per-column and per-scalar rules of one iteration.  vector_ops.h (one kernel per step: the dense, sparse, fused-factor
 // and lockstep paths) and small_lp.h (the whole loop in one workgroup) call these.
+// Also here, for the same two callers: the per-column rules of Mehrotra's starting point on the device (start_*, further down).
 //
 // A rule works on column j, or on scalars that one thread holds.  It loads and stores that column's entries and adds the column's
 // terms to the calling thread's own running sums and minima, in a fixed order; it never combines values of different threads.
@@ -169,6 +170,81 @@ __device__ __forceinline__ void update_column(const Cols& a, const BndArgs& bd, 
     if constexpr (Bounded) {
         bd.w[j] += ap * bd.dw[j];
         bd.z[j] += ad * bd.dz[j];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Mehrotra's starting point (SIAM J. Optim. 2 (1992) 575-601, section 7), the per-column rules of the device start
+// (ipm_init_state_mehrotra): the least-squares x = A^T (A A^T)^-1 b and r = c - A^T (A A^T)^-1 A c come in as values, the calling path
+// owns the solves, the products with A^T and every reduction.  Bounded, on U: w = u - x and r splits into s = max(r, 0), z = max(-r, 0);
+// outside U, w = z = 0.  The arithmetic per column, and its order, is that of IpmSolver.mehrotra_start (handle.py).
+//
+// least-squares primal column: x (and w) as computed; this thread's running minimum over x and w_U
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void start_primal_column(const Cols& a, const BndArgs& bd, int j, double xj, double& mn) {
+    a.x[j] = xj;
+    mn = fmin(mn, xj);
+    if constexpr (Bounded) {
+        const double uj = bd.u[j];
+        double wj = 0.0;
+        if (bnd_in(uj)) { wj = uj - xj; mn = fmin(mn, wj); }
+        bd.w[j] = wj;
+    }
+}
+// least-squares dual column from the reduced cost r_j; this thread's running minimum over s and z_U
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void start_dual_column(const Cols& a, const BndArgs& bd, int j, double rj, double& mn) {
+    double sj = rj;
+    if constexpr (Bounded) {
+        double zj = 0.0;
+        if (bnd_in(bd.u[j])) { sj = fmax(rj, 0.0); zj = fmax(-rj, 0.0); mn = fmin(mn, zj); }
+        bd.z[j] = zj;
+    }
+    a.s[j] = sj;
+    mn = fmin(mn, sj);
+}
+// shift into the positive orthant from a reduced minimum: max(-1.5 min, 0)
+__device__ __forceinline__ double start_shift(double mn) { return fmax(-1.5 * mn, 0.0); }
+// x += dp, s += dd (on U: w += dp, z += dd); column j's terms of x.s + w.z, sum s + sum z_U and sum x + sum w_U
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void start_shift_column(const Cols& a, const BndArgs& bd, int j, double dp, double dd, double& xs, double& ss, double& sx) {
+    const double xj = a.x[j] + dp, sj = a.s[j] + dd;
+    a.x[j] = xj; a.s[j] = sj;
+    xs += xj * sj; ss += sj; sx += xj;
+    if constexpr (Bounded) {
+        if (bnd_in(bd.u[j])) {
+            const double wj = bd.w[j] + dp, zj = bd.z[j] + dd;
+            bd.w[j] = wj; bd.z[j] = zj;
+            xs += wj * zj; ss += zj; sx += wj;
+        }
+    }
+}
+// degenerate data (xs = (x.s + w.z) / 2 not finite or not positive, or a non-positive sum): the reference's start instead
+__device__ __forceinline__ bool start_degenerate(double xs, double ss, double sx) { return !(fabs(xs) < 1.7e308 && ss > 0.0 && sx > 0.0 && xs > 0.0); }
+// primal correction x += pc (on U: w += pc); column j's terms of sum x + sum w_U after it
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void start_primal_correct_column(const Cols& a, const BndArgs& bd, int j, double pc, double& sx) {
+    const double xj = a.x[j] + pc;
+    a.x[j] = xj; sx += xj;
+    if constexpr (Bounded) {
+        if (bnd_in(bd.u[j])) { const double wj = bd.w[j] + pc; bd.w[j] = wj; sx += wj; }
+    }
+}
+// dual correction s += dc (on U: z += dc)
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void start_dual_correct_column(const Cols& a, const BndArgs& bd, int j, double dc) {
+    a.s[j] += dc;
+    if constexpr (Bounded) {
+        if (bnd_in(bd.u[j])) bd.z[j] += dc;
+    }
+}
+// the reference's start in column j, what ipm_init_state leaves: x = s = 1 (w = z = 1 on U, 0 outside)
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void start_reference_column(const Cols& a, const BndArgs& bd, int j) {
+    a.x[j] = 1.0; a.s[j] = 1.0;
+    if constexpr (Bounded) {
+        const double o = bnd_in(bd.u[j]) ? 1.0 : 0.0;
+        bd.w[j] = o; bd.z[j] = o;
     }
 }
 

@@ -18,6 +18,7 @@
 // mathematics, constants and stop test.  This file owns what this path does around the rules: A and the vectors
 // as placed above, (A^T y)_j as a CSC dot product with y in LDS, the normal equations, and the reductions.  Their summation orders
 // differ from the multi-kernel path's, so iterates agree to rounding, not bit for bit (tests compare both against the reference).
+// Below the loop: Mehrotra's starting point of such an LP in one launch (small_start_body), single and batched.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -348,6 +349,117 @@ __global__ __launch_bounds__(256) void small_batch_params_kernel(const SmallItem
     if (i >= n) return;
     start_solve(items[i].lp.sc, e1, e2, e3, items[i].eta, max_iter, 0, 1);
 }
+
+// ------------------------------------------------------------------------------- Mehrotra's starting point (ipm_init_state_mehrotra)
+// The start of a small LP in one launch of one workgroup: B = A A^T from the product list with d = 1 into the same
+// LDS image W the loop uses, the same guarded potrf_lds, both solves as matvecs with inv(L) from LDS, (A^T u)_j and (A^T y)_j as CSC
+// dot products with the m-vector in LDS, the shifts and the balance from block_reduce512.  The per-column rules are
+// iteration_rules.h (start_*), shared with the multi-kernel path.  No LDS beyond what small_lp_body declares; the n-vectors stay in
+// global memory and every thread keeps its own columns (j = tid, tid + 512, ...) from the first pass to the last, so the passes
+// need no barrier between them beyond those of the reductions.  Leaves the guarded-pivot count in sc->fixed.
+template <bool Bounded>
+__device__ __forceinline__ void small_start_body(SmallLP a, BndArgs bd) {
+    __shared__ __attribute__((aligned(16))) double W[NB * WLD];
+    __shared__ double dinv_s[NB];
+    __shared__ double ys[NB], t1s[NB], zs[NB];
+    __shared__ double red[8 * 4];
+
+    const int tid = threadIdx.x;
+    const int m = a.m, n = a.n, nt = a.nt, mt = 16 * a.nt;
+    const int row4 = tid >> 2, l4 = tid & 3;            // 4 lanes per row of A / of the triangular matvecs
+    Scalars* sc = a.sc;
+
+    // ---------------------------------------------------------------- B = A A^T into W, guarded Cholesky (as small_lp_body, d = 1)
+    for (int idx = tid; idx < mt * WLD; idx += PD_THREADS) W[idx] = 0.0;
+    __syncthreads();
+    double mx[1] = {-1.7976931348623157e308};
+    for (int e = tid; e < a.nb; e += PD_THREADS) {
+        const int i = a.bi[e], k = a.bk[e];
+        double acc = 0.0;
+        for (int t = a.bptr[e]; t < a.bptr[e + 1]; ++t) acc += a.bcoef[t];
+        W[i * WLD + k] = acc;
+        if (i != k && (i >> 4) == (k >> 4)) W[k * WLD + i] = acc;
+        if (i == k) mx[0] = (acc > mx[0]) ? acc : mx[0];
+    }
+    if (tid >= m && tid < mt) W[tid * WLD + tid] = 1.0;
+    {
+        double ng[1] = {-mx[0]};
+        block_reduce512<1, true>(ng, red);
+        mx[0] = -ng[0];
+    }
+    if (a.shift_rel != 0.0 && tid < mt) W[tid * WLD + tid] += a.shift_rel * mx[0];
+    __syncthreads();
+    const int nfix = potrf_lds<false>(W, dinv_s, nt, a.eps * mx[0], a.big, m, nullptr);
+    if (tid == 0) { sc->maxdiag = mx[0]; sc->fixed = nfix; }
+
+    // out = (L L^T)^-1 t1s with X = inv(L) from LDS (the two matvecs of small_lp_body's solve_normal)
+    auto solve = [&](double* out) {
+        __syncthreads();
+        if (row4 < mt) {
+            double acc = 0.0;
+            for (int k = l4; k <= row4; k += 4) acc += W[k * WLD + row4 + 1] * t1s[k];
+            acc += __shfl_xor(acc, 2, 4);
+            acc += __shfl_xor(acc, 1, 4);
+            if (l4 == 0) zs[row4] = acc;
+        }
+        __syncthreads();
+        if (row4 < mt) {
+            double acc = 0.0;
+            for (int i = row4 + l4; i < mt; i += 4) acc += W[row4 * WLD + i + 1] * zs[i];
+            acc += __shfl_xor(acc, 2, 4);
+            acc += __shfl_xor(acc, 1, 4);
+            if (l4 == 0) out[row4] = acc;
+        }
+        __syncthreads();
+    };
+    auto at_dot = [&](int j) {                            // (A^T ys)_j
+        double w = 0.0;
+        for (int p = a.A.colptr[j]; p < a.A.colptr[j + 1]; ++p) w += a.A.cval[p] * ys[a.A.rowind[p]];
+        return w;
+    };
+
+    // ---------------------------------------------------------------- x = A^T (A A^T)^-1 b
+    if (tid < NB) t1s[tid] = tid < m ? a.b[tid] : 0.0;
+    solve(ys);
+    double mn[2] = {__builtin_inf(), __builtin_inf()};
+    for (int j = tid; j < n; j += PD_THREADS) start_primal_column<Bounded>(a, bd, j, at_dot(j), mn[0]);
+    __syncthreads();                                      // ys is rewritten below
+    // ---------------------------------------------------------------- y = (A A^T)^-1 A c ; r = c - A^T y
+    if (tid < NB) t1s[tid] = 0.0;
+    __syncthreads();
+    if (row4 < m) {
+        double acc = 0.0;
+        for (int p = a.A.rowptr[row4] + l4; p < a.A.rowptr[row4 + 1]; p += 4) acc += a.A.rval[p] * a.c[a.A.colind[p]];
+        acc += __shfl_xor(acc, 2, 4);
+        acc += __shfl_xor(acc, 1, 4);
+        if (l4 == 0) t1s[row4] = acc;
+    }
+    solve(ys);
+    for (int j = tid; j < n; j += PD_THREADS) start_dual_column<Bounded>(a, bd, j, a.c[j] - at_dot(j), mn[1]);
+    // ---------------------------------------------------------------- shifts, balance or fallback
+    block_reduce512<2, true>(mn, red);
+    const double dp = start_shift(mn[0]), dd = start_shift(mn[1]);
+    double t3[3] = {0.0, 0.0, 0.0};                       // x.s + w.z, sum s + sum z_U, sum x + sum w_U
+    for (int j = tid; j < n; j += PD_THREADS) start_shift_column<Bounded>(a, bd, j, dp, dd, t3[0], t3[1], t3[2]);
+    block_reduce512<3, false>(t3, red);
+    const double xs = 0.5 * t3[0];
+    if (start_degenerate(xs, t3[1], t3[2])) {             // the same reduced values in every thread: all take this branch or none
+        for (int j = tid; j < n; j += PD_THREADS) start_reference_column<Bounded>(a, bd, j);
+        if (tid < m) a.y[tid] = 1.0;
+        return;
+    }
+    const double pc = xs / t3[1];
+    double sx[1] = {0.0};
+    for (int j = tid; j < n; j += PD_THREADS) start_primal_correct_column<Bounded>(a, bd, j, pc, sx[0]);
+    block_reduce512<1, false>(sx, red);
+    const double dc = xs / sx[0];
+    for (int j = tid; j < n; j += PD_THREADS) start_dual_correct_column<Bounded>(a, bd, j, dc);
+    if (tid < m) a.y[tid] = ys[tid];
+}
+__global__ __launch_bounds__(PD_THREADS) void small_start_kernel(SmallLP a) { small_start_body<false>(a, BndArgs{}); }
+__global__ __launch_bounds__(PD_THREADS) void small_start_bounded_kernel(SmallLP a, BndArgs bd) { small_start_body<true>(a, bd); }
+__global__ __launch_bounds__(PD_THREADS) void small_start_batch_kernel(const SmallItem* __restrict__ items) { const SmallItem it = items[blockIdx.x]; small_start_body<false>(it.lp, it.bd); }
+__global__ __launch_bounds__(PD_THREADS) void small_start_batch_bounded_kernel(const SmallItem* __restrict__ items) { const SmallItem it = items[blockIdx.x]; small_start_body<true>(it.lp, it.bd); }
 
 // every item's scalar record into ONE contiguous array (slot = the item's index): the host reads all statistics with one copy
 __global__ __launch_bounds__(256) void small_batch_gather_kernel(const SmallItem* __restrict__ items, int n, Scalars* __restrict__ out) {

@@ -368,6 +368,96 @@ __device__ __forceinline__ void update_kernel_body(VecArgs a, const unsigned bx_
 __global__ __launch_bounds__(VBLK) void update_kernel(VecArgs a) { update_kernel_body(a, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void update_bounded_kernel(VecArgs a, BndArgs bd) { update_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 
+// ---------------------------------------------------------------------------------------
+// Mehrotra's starting point on the device (ipm_init_state_mehrotra): the column work between the two solves with
+// A A^T and after them.  The rules are iteration_rules.h (start_*); the reductions are the two-level fixed-order ones of this file.
+// Entries beyond n (and rows beyond m) are never written: they keep the zeros ipm_init_state leaves there.
+// ---------------------------------------------------------------------------------------
+enum { PS_MIN_P = 0, PS_MIN_D, PS_XS, PS_SS, PS_SX, PS_SX2 };      // partial slots of the start (the iteration's slots are free then)
+
+__device__ __forceinline__ double start_min_partials(const double* part, int slot, int nblk) {
+    double s = __builtin_inf();
+    for (int i = 0; i < nblk; ++i) s = fmin(s, part[slot * MAXPART + i]);
+    return s;
+}
+struct StartSums { double xs, ss, sx; };      // (x.s + w.z) / 2, sum s + sum z_U, sum x + sum w_U after the shifts
+__device__ __forceinline__ StartSums start_sums(const double* part, int nblk) {
+    return {0.5 * sum_partials(part, PS_XS, nblk), sum_partials(part, PS_SS, nblk), sum_partials(part, PS_SX, nblk)};
+}
+
+// finishes the A^T partials in col_sum's order.  Dual = false: x = A^T u (Bounded: w = u - x on U) and the partial minima of (x, w_U);
+// Dual = true: r = c - A^T y, s = r (Bounded, on U: s = max(r, 0), z = max(-r, 0)), the partial minima of (s, z_U), and y = dy
+template <bool Bounded, bool Dual>
+__device__ __forceinline__ void start_ls_kernel_body(VecArgs a, BndArgs bd = BndArgs{}) {
+    __shared__ double red[VBLK];
+    const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
+    double mn = __builtin_inf();
+    for (int j = gid; j < a.n; j += gsz) {
+        const double t = col_sum(a.atp, a.rc_chunks, a.np, j);
+        if constexpr (Dual) start_dual_column<Bounded>(a, bd, j, a.c[j] - t, mn);
+        else start_primal_column<Bounded>(a, bd, j, t, mn);
+    }
+    if constexpr (Dual) for (int i = gid; i < a.m; i += gsz) a.y[i] = a.dy[i];
+    mn = block_min(mn, red);
+    if (threadIdx.x == 0) a.part[(Dual ? PS_MIN_D : PS_MIN_P) * MAXPART + blockIdx.x] = mn;
+}
+__global__ __launch_bounds__(VBLK) void start_primal_kernel(VecArgs a) { start_ls_kernel_body<false, false>(a); }
+__global__ __launch_bounds__(VBLK) void start_primal_bounded_kernel(VecArgs a, BndArgs bd) { start_ls_kernel_body<true, false>(a, bd); }
+__global__ __launch_bounds__(VBLK) void start_dual_kernel(VecArgs a) { start_ls_kernel_body<false, true>(a); }
+__global__ __launch_bounds__(VBLK) void start_dual_bounded_kernel(VecArgs a, BndArgs bd) { start_ls_kernel_body<true, true>(a, bd); }
+
+// scalar phase 1: the shifts from the re-reduced minima, applied; partial sums of x.s + w.z, sum s + sum z_U, sum x + sum w_U
+template <bool Bounded>
+__device__ __forceinline__ void start_shift_kernel_body(VecArgs a, BndArgs bd = BndArgs{}) {
+    __shared__ double red[VBLK];
+    const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
+    const double dp = start_shift(start_min_partials(a.part, PS_MIN_P, a.nblk));
+    const double dd = start_shift(start_min_partials(a.part, PS_MIN_D, a.nblk));
+    double xs = 0.0, ss = 0.0, sx = 0.0;
+    for (int j = gid; j < a.n; j += gsz) start_shift_column<Bounded>(a, bd, j, dp, dd, xs, ss, sx);
+    xs = block_sum(xs, red); ss = block_sum(ss, red); sx = block_sum(sx, red);
+    if (threadIdx.x == 0) {
+        a.part[PS_XS * MAXPART + blockIdx.x] = xs;
+        a.part[PS_SS * MAXPART + blockIdx.x] = ss;
+        a.part[PS_SX * MAXPART + blockIdx.x] = sx;
+    }
+}
+__global__ __launch_bounds__(VBLK) void start_shift_kernel(VecArgs a) { start_shift_kernel_body<false>(a); }
+__global__ __launch_bounds__(VBLK) void start_shift_bounded_kernel(VecArgs a, BndArgs bd) { start_shift_kernel_body<true>(a, bd); }
+
+// scalar phase 2: degenerate data -> the reference's start (x = s = 1, y = 1, w = z = 1 on U) and nothing else; otherwise the
+// primal correction x += xs / ss and the partial sums of sum x + sum w_U after it
+template <bool Bounded>
+__device__ __forceinline__ void start_primal_correct_kernel_body(VecArgs a, BndArgs bd = BndArgs{}) {
+    __shared__ double red[VBLK];
+    const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
+    const StartSums t = start_sums(a.part, a.nblk);
+    if (start_degenerate(t.xs, t.ss, t.sx)) {                     // (the same decision in every thread of every block: all leave)
+        for (int j = gid; j < a.n; j += gsz) start_reference_column<Bounded>(a, bd, j);
+        for (int i = gid; i < a.m; i += gsz) a.y[i] = 1.0;
+        return;
+    }
+    const double pc = t.xs / t.ss;
+    double sx = 0.0;
+    for (int j = gid; j < a.n; j += gsz) start_primal_correct_column<Bounded>(a, bd, j, pc, sx);
+    sx = block_sum(sx, red);
+    if (threadIdx.x == 0) a.part[PS_SX2 * MAXPART + blockIdx.x] = sx;
+}
+__global__ __launch_bounds__(VBLK) void start_primal_correct_kernel(VecArgs a) { start_primal_correct_kernel_body<false>(a); }
+__global__ __launch_bounds__(VBLK) void start_primal_correct_bounded_kernel(VecArgs a, BndArgs bd) { start_primal_correct_kernel_body<true>(a, bd); }
+
+// scalar phase 3: the dual correction s += xs / (sum x + sum w_U); nothing on degenerate data (phase 2 wrote the reference's start)
+template <bool Bounded>
+__device__ __forceinline__ void start_dual_correct_kernel_body(VecArgs a, BndArgs bd = BndArgs{}) {
+    const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
+    const StartSums t = start_sums(a.part, a.nblk);
+    if (start_degenerate(t.xs, t.ss, t.sx)) return;
+    const double dc = t.xs / sum_partials(a.part, PS_SX2, a.nblk);
+    for (int j = gid; j < a.n; j += gsz) start_dual_correct_column<Bounded>(a, bd, j, dc);
+}
+__global__ __launch_bounds__(VBLK) void start_dual_correct_kernel(VecArgs a) { start_dual_correct_kernel_body<false>(a); }
+__global__ __launch_bounds__(VBLK) void start_dual_correct_bounded_kernel(VecArgs a, BndArgs bd) { start_dual_correct_kernel_body<true>(a, bd); }
+
 // out[i] = value for i < n (fill)
 __global__ void fill_kernel(double* out, int n, double value) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
