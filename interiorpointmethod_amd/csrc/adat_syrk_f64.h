@@ -2,22 +2,18 @@
 // fp64 MFMA (v_mfma_f64_16x16x4_f64) for gfx950.  Replaces the two scipy SpGEMMs of main.py:224 (reference repo).
 //
 // Same tiling, LDS image, summation order and split-K tail as the generic gemm_nt_f64_kernel<128,128,16,2,2,true>
-// (results are bit-identical to it); what differs is the schedule of one K stage (BK = 16, four MFMA k-steps):
+// (results are bit-identical to it); what differs:
 //
-//   * Fragment reads are software pipelined one k-step ahead through two register sets (Fa, Fb): the ds_reads of
-//     k-step kk+1 are issued before the 16 MFMAs of k-step kk, so no LDS latency is exposed inside a stage.  The
-//     generic kernel reads all fragments of two k-steps, waits, multiplies (two exposed LDS round trips per stage).
-//   * The stage barrier sits BEFORE the last k-step instead of after it: the next stage's operands are written to
-//     the other LDS buffer during k-step 2, the barrier follows, and the first fragments of the next stage are
-//     fetched while the 16 MFMAs of k-step 3 run -- the MFMA stream of a wave continues across the stage boundary.
+//   * The schedule of one K stage (BK = 16, four MFMA k-steps) is mfma_stage_pipe (mfma_stage_pipe.h): fragment reads one
+//     k-step ahead through two register sets, the stage barrier before the last k-step.
 //   * Operands are fetched with buffer loads (one VGPR offset per thread, row and k offsets in SGPRs) instead of
 //     nine 64-bit per-lane pointers: the kernel fits its 256 VGPRs without scratch.
 //
 // Measured on MI355X, standalone, random data (tools/syrk_bench.hip, profiles/r02_syrk_ab_3way.log), against the generic
 // kernel: 2.011 vs 2.075 ms at 4096 x 8192 (68.3 TFLOP/s = 0.87 of the fp64 MFMA peak), 15.56 vs 16.00 ms at 8192 x
 // 16384 (0.90), 124.4 vs 127.4 ms at 16384 x 32768 (70.7 TFLOP/s = 0.90).  A variant with TWO staging register sets
-// (loads 1.75 stages in flight, inline-asm loads, hand-counted vmcnt; tools/adat_syrk_2set.h) was built and rejected:
-// 2.016 / 15.67 / 128.3 ms -- the loads were never the limit.  Inside the solver the same launch takes 2.19 ms: it
+// (loads 1.75 stages in flight, inline-asm loads, hand-counted vmcnt) was built and rejected: 2.016 / 15.67 / 128.3 ms
+// in the same log -- the loads were never the limit.  Inside the solver the same launch takes 2.19 ms: it
 // follows 2.2 ms of the Cholesky pivot chain, and the power manager grants a lower clock after light load
 // (tools/syrk_bench.hip ctx, tools/clock_probe.hip: 2.01 ms back to back, 2.33 ms after 2.8 ms on one workgroup).
 //
@@ -26,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "gemm_nt_f64.h"
+#include "mfma_stage_pipe.h"
 
 namespace ipm {
 
@@ -108,68 +105,27 @@ __global__ __launch_bounds__(256, 2) void adat_syrk_kernel(AdatSyrk g) {
 
     const int fr = lane & 15, fk = lane >> 4;
     const int fa_off = (wm * 64 + fr) * LDT + fk, fb_off = (wn * 64 + fr) * LDT + fk;
-    double fa[2][4], fb[2][4];                                  // two fragment register sets
-    auto read_frags = [&](int set, int buf, int kk) {
+    auto read_frags = [&](double (&fa)[4], double (&fb)[4], int buf, int kk) {
         const double* pa = Ps + buf * BM * LDT + fa_off + kk * 4;
         const double* qb = Qs + buf * BM * LDT + fb_off + kk * 4;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fa[set][i] = pa[i * 16 * LDT];
+        for (int i = 0; i < 4; ++i) fa[i] = pa[i * 16 * LDT];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) fb[set][j] = qb[j * 16 * LDT];
+        for (int j = 0; j < 4; ++j) fb[j] = qb[j * 16 * LDT];
     };
     f64x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f64x4){0.0, 0.0, 0.0, 0.0};
-    auto mfma16 = [&](int set) {
+    auto store_stage = [&](int buf) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i) store_q(buf, i);
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[set][i], fb[set][j], acc[i][j], 0, 0, 0);
+        for (int i = 0; i < 4; ++i) store_p(buf, i);
     };
-
-    // ---- prologue: stage kbeg into LDS, loads of stage kbeg+1 in flight, first fragments in Fa
-    issue_loads(kbeg);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) store_q(kbeg & 1, i);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) store_p(kbeg & 1, i);
-    __syncthreads();
-    if (kbeg + 1 < kend) issue_loads(kbeg + 1);
-    read_frags(0, kbeg & 1, 0);
-
-    for (int kt = kbeg; kt < kend; ++kt) {
-        const int buf = kt & 1;
-        const bool more = kt + 1 < kend;
-        read_frags(1, buf, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma16(0);                                              // k-step 0
-        __builtin_amdgcn_sched_barrier(0);
-        read_frags(0, buf, 2);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma16(1);                                              // k-step 1
-        __builtin_amdgcn_sched_barrier(0);
-        read_frags(1, buf, 3);
-        __builtin_amdgcn_sched_barrier(0);
-        // k-step 2, with the next stage's operands written to the other LDS buffer between its MFMA rows (the global
-        // loads were issued three k-steps ago; their waits sit behind 4 MFMAs each instead of in front of all 16)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[0][i], fb[0][j], acc[i][j], 0, 0, 0);
-            if (more) { store_q(buf ^ 1, i); store_p(buf ^ 1, i); }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();                                        // writes of stage kt+1 visible; reads of stage kt issued
-        if (kt + 2 < kend) issue_loads(kt + 2);
-        if (more) read_frags(0, buf ^ 1, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma16(1);                                              // k-step 3
-        __builtin_amdgcn_sched_barrier(0);
-    }
+    auto store_behind_row = [&](int buf, int i) { store_q(buf, i); store_p(buf, i); };
+    mfma_stage_pipe<4, 4, 4>(kbeg, kend, acc, issue_loads, store_stage, store_behind_row, read_frags);
 
     // ---- epilogue: D[row=(l>>4)+4q][col=l&15]
     if (slab_out) {                                             // split-K partial: raw tile, summed later

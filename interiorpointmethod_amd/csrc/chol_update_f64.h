@@ -3,9 +3,8 @@
 // for gfx950.  Part of the factorization behind main.py:180 / :226 of the reference (scipy's spsolve there).
 //
 // Same tiling, tile enumeration, summation order and epilogue arithmetic as gemm_nt_f64_kernel<128,128,16,2,2,false>
-// (results are bit-identical to it, tests/test_gpu_kernels.py); what differs is the stage schedule, which is the one of
-// adat_syrk_kernel (adat_syrk_f64.h): fragment reads one k-step ahead through two register sets, the stage barrier
-// before the LAST k-step with the next stage written to the other LDS buffer between the MFMA rows of k-step 2, operands
+// (results are bit-identical to it: tests/test_gpu_parity.py and tests/test_gpu_pivot_guard.py compare IPM_BULK_VARIANT=0
+// against 7); what differs is the stage schedule, mfma_stage_pipe (mfma_stage_pipe.h) as in adat_syrk_kernel, and operands
 // fetched with buffer loads (one VGPR offset per thread).  The generic kernel needs 256 VGPRs + 17 spilled for this
 // shape; this one keeps its K loop free of scratch (two 8-byte spills in the epilogue).
 #pragma once
@@ -14,6 +13,7 @@
 #include "adat_syrk_f64.h"
 #include "gemm_nt_f64.h"
 #include "handoff.h"
+#include "mfma_stage_pipe.h"
 
 namespace ipm {
 
@@ -69,65 +69,27 @@ __device__ __forceinline__ void chol_update_kernel_body(GemmNT g, const unsigned
 
     const int fr = lane & 15, fk = lane >> 4;
     const int fa_off = (wm * 64 + fr) * LDT + fk, fb_off = (wn * 64 + fr) * LDT + fk;
-    double fa[2][4], fb[2][4];
-    auto read_frags = [&](int set, int buf, int kk) {
+    auto read_frags = [&](double (&fa)[4], double (&fb)[4], int buf, int kk) {
         const double* pa = Ps + buf * BM * LDT + fa_off + kk * 4;
         const double* qb = Qs + buf * BM * LDT + fb_off + kk * 4;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fa[set][i] = pa[i * 16 * LDT];
+        for (int i = 0; i < 4; ++i) fa[i] = pa[i * 16 * LDT];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) fb[set][j] = qb[j * 16 * LDT];
+        for (int j = 0; j < 4; ++j) fb[j] = qb[j * 16 * LDT];
     };
     f64x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f64x4){0.0, 0.0, 0.0, 0.0};
-    auto mfma16 = [&](int set) {
+    auto store_stage = [&](int buf) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i) store_q(buf, i);
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[set][i], fb[set][j], acc[i][j], 0, 0, 0);
+        for (int i = 0; i < 4; ++i) store_p(buf, i);
     };
-
-    issue_loads(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) store_q(0, i);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) store_p(0, i);
-    __syncthreads();
-    if (1 < nk) issue_loads(1);
-    read_frags(0, 0, 0);
-
-    for (int kt = 0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        const bool more = kt + 1 < nk;
-        read_frags(1, buf, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma16(0);
-        __builtin_amdgcn_sched_barrier(0);
-        read_frags(0, buf, 2);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma16(1);
-        __builtin_amdgcn_sched_barrier(0);
-        read_frags(1, buf, 3);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[0][i], fb[0][j], acc[i][j], 0, 0, 0);
-            if (more) { store_q(buf ^ 1, i); store_p(buf ^ 1, i); }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();
-        if (kt + 2 < nk) issue_loads(kt + 2);
-        if (more) read_frags(0, buf ^ 1, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma16(1);
-        __builtin_amdgcn_sched_barrier(0);
-    }
+    auto store_behind_row = [&](int buf, int i) { store_q(buf, i); store_p(buf, i); };
+    mfma_stage_pipe<4, 4, 4>(0, nk, acc, issue_loads, store_stage, store_behind_row, read_frags);
 
     // ---- epilogue (the arithmetic of the generic kernel): D[row=(l>>4)+4q][col=l&15]
     // C through a buffer resource as well: one VGPR offset per thread, the 64 row / column offsets of a thread are scalars

@@ -18,8 +18,9 @@
 // FFWords, ff_schedule.h); every spin is bounded (time-out word -> the host rolls the call back and repeats it on the serial path).
 //
 // GEMM engines (8 waves, v_mfma_f64_16x16x4_f64): ff_gemm_pair for the formation -- 256 x 128 per workgroup, waves 4 (M) x 2 (N),
-// BK = 16 stages on the schedule of adat_syrk_kernel (0.87 of the fp64 MFMA peak standalone, tools/ff_gemm_bench.hip);
-// ff_gemm_pipe for the updates -- 128 x 128, waves 2 x 4, BK = 32, software pipelined; ff_gemm for the panel product with P
+// BK = 16 stages on the schedule of mfma_stage_pipe.h (0.87 of the fp64 MFMA peak standalone, tools/ff_gemm_bench.hip);
+// ff_gemm_pipe for the updates -- 128 x 128, waves 2 x 4, BK = 32, the same schedule (both on copies of their own: the
+// reason is at the end of that header's comment); ff_gemm for the panel product with P
 // taken from the accumulators through LDS.  Operands global -> registers -> LDS (rows padded: conflict-free ds_read_b64
 // fragment reads), double buffered, one barrier per stage.  HEAD (form_factor_roles_kernel_mfma_first, the launch that runs):
 // the stage loops of ff_gemm_pair and ff_gemm_pipe have no branch, and each stage opens with the MFMAs of the previous
@@ -154,7 +155,7 @@ __device__ __forceinline__ void ff_gemm(const double* __restrict__ Pg, int64_t l
     }
 }
 
-// The same product, software pipelined (the schedule of adat_syrk_f64.h carried over to 8 waves and BK = 32): fragment
+// The same product, software pipelined (the schedule of mfma_stage_pipe.h carried over to 8 waves and BK = 32): fragment
 // reads run one k-step ahead through two register sets; the next stage's operands -- fetched from memory a whole stage
 // earlier -- are written to the other LDS buffer between the MFMAs of the second-to-last k-step; the stage barrier follows,
 // and the LAST k-step's eight MFMAs (fragments already in registers) issue right behind it (HEAD: with the loads of stage
@@ -263,7 +264,7 @@ __device__ __forceinline__ void ff_gemm_pipe(const double* __restrict__ Pg, int6
 
 // ------------------------------------------------------------------------------------------------------------------------
 // FORMATION engine: TWO vertically adjacent tiles at once -- a 256 x 128 block of B = A diag(d) A^T -- by the 8 waves as
-// 4 (M) x 2 (N), each wave 64 x 64 = 4 x 4 MFMA tiles: per wave exactly the proven schedule of adat_syrk_f64.h (16 MFMAs per
+// 4 (M) x 2 (N), each wave 64 x 64 = 4 x 4 MFMA tiles: per wave exactly the proven schedule of mfma_stage_pipe.h (16 MFMAs per
 // k-step against 8 fragment reads, BK = 16 stages, fragment reads one k-step ahead, next stage written to LDS under the
 // third k-step, barrier, last k-step behind it), and the column panel (Q operand, with the d scaling) is fetched once for
 // both tiles.  acc: [4][4] per wave; rows of the block = wm * 64 + ..., i.e. waves 0-3 hold the upper tile, 4-7 the lower.
