@@ -220,6 +220,35 @@ int ipm_set_bounds(ipm_handle* h, const double* u);
 int ipm_set_bound_state(ipm_handle* h, const double* w, const double* z);
 int ipm_get_bound_state(ipm_handle* h, double* w, double* z);
 
+/* ---- equilibration: power-of-two Ruiz row / column scaling -------------- */
+/* Scale the handle's LP on the device to R A C, R b, C c, u / C with diagonal R, C whose entries are exact powers of two, so that
+ * scaling and unscaling introduce no rounding at all.  Rule (csrc/equilibrate.h): simultaneous Ruiz passes on |A| in the infinity
+ * norm; a row or column whose largest magnitude in the current scaled matrix is v = f 2^e, f in [0.5, 1), has its factor
+ * multiplied by 2^(-floor(e / 2)); empty rows and columns keep factor 1.  A pass changes nothing exactly when every non-empty row
+ * and column maximum lies in [0.5, 2), so max_passes (0 .. 1024) is a cap, not a tuning knob: the cap runs on the device without
+ * host synchronisation, passes behind the fixed point are no-ops.  A and every value table derived from it are rewritten once.
+ * Requires A; b, c and u may be set before or after.  Off unless called: an unscaled handle runs exactly the code it ran before.
+ * info (may be NULL): {passes that changed a factor, log2(max / min) of the non-empty row maxima before scaling, the same after,
+ * log2(max / min) of the non-empty column maxima after}.  max_passes = 0, or data already at the fixed point: the handle stays
+ * unscaled (info is still written).  IPM_ERR_STATE without A or on an already scaled handle.  Preconditions: finite data, and no
+ * nonzero entry of A, b, c, u that the factors push into the subnormal range or to overflow -- checked on the device:
+ * IPM_ERR_INVALID_INPUT, and the handle stays unscaled.  b, c or u that enter an already scaled handle meet the same precondition
+ * on the way in: ipm_set_bc / ipm_set_bounds return IPM_ERR_INVALID_INPUT and keep what the handle held.
+ * ONE BOUNDARY RULE from then on: data entering a scaled handle is scaled on the way in, data leaving it is unscaled on the way
+ * out, all of it exact.  In: ipm_set_bc (R b, C c) and ipm_set_bounds (u / C), which recompute the norms; ipm_set_state (x / C,
+ * y / R, s C); ipm_set_bound_state (w / C, z C).  Out: ipm_get_state (C x', R y', s' / C), ipm_get_bound_state (C w', z' / C),
+ * ipm_newton_direction (C dx', R dy', ds' / C), ipm_get_certificate (y by R, x by C, z by 1 / C: a certificate of the caller's LP).
+ * Everything else acts on the SCALED problem: the stop test and the infeasibility tests, the history, rp / rd / gap / mu and the
+ * norms in ipm_stats, ipm_init_state and ipm_init_state_mehrotra (x = s = 1 etc. of the scaled LP), and the seams
+ * ipm_form_normal_matrix, ipm_normal_solve and ipm_get_factor (A means R A C there).  The objective c'^T x' equals c^T x.  The
+ * iterate must be set or initialised after this call (w = z = 1 on the bounded set are kept).  The batches need nothing: a scaled
+ * handle is a handle with different data, scaled and unscaled ones mix freely, the unscale happens in the getters.
+ * ipm_set_A_dense / ipm_set_A_csc make the handle unscaled again (its bounds return to the caller's units; b and c must be set
+ * again); an A they reject leaves the scaled handle as it was.  The factors are the library's own allocation, freed by ipm_destroy; ipm_workspace_bytes* do not change. */
+int ipm_equilibrate(ipm_handle* h, int32_t max_passes, double info[4]);
+/* The factors: r (length m, the handle's row order) and c (length n), each may be NULL; all ones on an unscaled handle. */
+int ipm_get_scaling(ipm_handle* h, double* r, double* c);
+
 /* ---- direction seam (main.py:197 / :247) ------------------------------------------- */
 /* corrector == 0: predictor direction at the current state (forms and factors A D^2 A^T).
  * corrector == 1: corrector direction; requires a preceding predictor call at the same

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .analysis import _upper_bounds
-from .handle import STATUS_NAMES, IpmSolver, mehrotra_started, shift_allowed, wants_shift
+from .handle import SCALE_PASSES, STATUS_NAMES, IpmSolver, check_scale, mehrotra_started, shift_allowed, wants_shift
 
 
 def _info(solver, cTlb=0.0):
@@ -43,7 +43,24 @@ def _solve_info(solver, history=False, certificate=False):
     fi = solver.factor_info()
     info["serial_launches"] = fi["serial_launches"] if fi else 0
     info["factor_path"] = solver.factor
+    if solver.scale is not None:
+        info["scale"] = dict(solver.scale_info)
+        info["rp_unscaled"], info["rd_unscaled"] = unscaled_residuals(solver)
     return info
+
+
+def unscaled_residuals(solver):
+    """The reference's relative residuals ||A x - b|| / (1 + ||b||) and ||A^T y + s - z - c|| / (1 + ||c||) (main.py:170-171) of the
+    iterate the solver RETURNS, against the caller's own data: what the stop test of a scaled solve meant in the caller's units.
+    Host arithmetic on the arrays the solver already holds."""
+    A, b, c = solver._host
+    x, y, s = (np.asarray(v).reshape(-1) for v in solver.get_state())
+    b, c = np.asarray(b, dtype=np.float64).reshape(-1), np.asarray(c, dtype=np.float64).reshape(-1)
+    rd = np.asarray(A.T @ y).reshape(-1) + s - c
+    if solver.bounded:
+        rd = rd - solver.get_bound_state()[1].reshape(-1)
+    rp = np.asarray(A @ x).reshape(-1) - b
+    return float(np.linalg.norm(rp) / (1.0 + np.linalg.norm(b))), float(np.linalg.norm(rd) / (1.0 + np.linalg.norm(c)))
 
 
 _last_info = None
@@ -59,7 +76,8 @@ def _auto_regularize():          # the process-wide switch of the 5 % rule (hand
 
 
 def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
-                    history=False, ub=None, detect_infeasibility=False, device_start=False, **opts):
+                    history=False, ub=None, detect_infeasibility=False, device_start=False, scale=None, scale_passes=SCALE_PASSES,
+                    **opts):
     """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
     start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start(), or with
     device_start=True IpmSolver.init_state_mehrotra(): the same start computed on the device (no host copy of A, one
@@ -68,10 +86,14 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     than 5 % dependent rows (the QAP family) is solved with the 1e-14 Tikhonov shift, switched on by the library
     after the first factorization (info["auto_regularized"] == 1; auto_regularize=False keeps it off).
     ub: native upper bounds 0 <= x <= ub (+inf = none): info["bounded"] = |U| and, when |U| > 0, info["w"], info["z"].
-    detect_infeasibility=True: the solve may end in status 5 / 6 (IpmSolver); info["certificate"] = IpmSolver.certificate()."""
+    detect_infeasibility=True: the solve may end in status 5 / 6 (IpmSolver); info["certificate"] = IpmSolver.certificate().
+    scale="ruiz": the LP is equilibrated on the device first (IpmSolver); the statistics are then the SCALED problem's, and
+    info["scale"], info["rp_unscaled"], info["rd_unscaled"] say what they mean in the caller's units (unscaled_residuals)."""
     global _last_info
     if start not in ("reference", "mehrotra"):
         raise ValueError('start must be "reference" or "mehrotra"')
+    if check_scale(scale) is not None:
+        opts = dict(opts, scale=scale, scale_passes=scale_passes)
     ub = _upper_bounds(ub, np.asarray(c).reshape(-1).shape[0])
     on_device = start == "mehrotra" and device_start
     if start == "mehrotra" and not on_device and shift_allowed(opts.get("regularize"), _auto_regularize()):
@@ -107,10 +129,11 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     return x, y, s, info
 
 
-def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, **opts):
+def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, scale=None, scale_passes=SCALE_PASSES, **opts):
     """min c^T x s.t. Ax=b, x>=0 (and x <= ub where ub is finite) by the Mehrotra predictor-corrector loop on the GPU
     -> (x, y, s)."""
-    x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub, **opts)
+    x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub, scale=scale,
+                                 scale_passes=scale_passes, **opts)
     return x, y, s
 
 
@@ -123,11 +146,11 @@ def _verdict(info, value):
     return value
 
 
-def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False):
+def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False, scale=None, scale_passes=SCALE_PASSES):
     """Drop-in for main.py:760-815: start x=s=y=1, cap 5000, returns sum(x*c) - cTlb.  detect_infeasibility=True: +inf for an
-    LP detected infeasible, -inf for one detected unbounded."""
+    LP detected infeasible, -inf for one detected unbounded.  scale: as solve_with_info (off by default)."""
     _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=5000, y0=1.0, device=device,
-                                    detect_infeasibility=detect_infeasibility)
+                                    detect_infeasibility=detect_infeasibility, scale=scale, scale_passes=scale_passes)
     return _verdict(info, info["objective"] - float(cTlb))
 
 

@@ -6,7 +6,7 @@ import numpy as np
 from . import _lib
 from .analysis import FUSED_SMALL_MAX_ROWS, _sp, _upper_bounds
 from .api import _auto_regularize, _solve_info
-from .handle import IpmSolver, _gap_tol, wants_shift
+from .handle import SCALE_PASSES, IpmSolver, _gap_tol, check_scale, wants_shift
 
 
 def _handle_array(solvers):           # (the handles as a C array, a Stats array of the same length) for one batched library call
@@ -164,7 +164,7 @@ def _small_batch_host_check(problems, ub):
 
 
 def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, ub=None, detect_infeasibility=False,
-                      regularize=0.0, start="reference"):
+                      regularize=0.0, start="reference", scale=None, scale_passes=SCALE_PASSES):
     """Solve many small LPs at once -> list of (x, y, s, info), one per problem, each what solve_with_info returns for it alone.
 
     problems: list of (A, b, c) with at most 128 rows each; a dense A is converted to CSC.  ub: None or one entry per problem (None or
@@ -173,14 +173,16 @@ def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_g
     init_state(y0) loop (each LP then equals solve_with_info(start="mehrotra", device_start=True) for it alone; an LP past the 5 % rule
     of handle.wants_shift gets its handle again with regularize=1e-14 and its own start).  An LP the library does not put on the
     small path (more than 128 rows, or a product list of A D^2 A^T beyond its cap) raises ValueError naming its index before anything
-    is launched."""
+    is launched.  scale="ruiz": every LP is equilibrated on the device first (IpmSolver; off by default)."""
     if start not in ("reference", "mehrotra"):
         raise ValueError('start must be "reference" or "mehrotra"')
+    check_scale(scale)
     checked = _small_batch_host_check(problems, ub)
     solvers = []
     try:
         for i, (A, b, c, u) in enumerate(checked):
-            sv = IpmSolver(A, b, c, device=device, regularize=regularize, ub=u, detect_infeasibility=detect_infeasibility)
+            sv = IpmSolver(A, b, c, device=device, regularize=regularize, ub=u, detect_infeasibility=detect_infeasibility, scale=scale,
+                           scale_passes=scale_passes)
             solvers.append(sv)
             if not small_batch_eligible(sv):
                 raise ValueError("problem %d (%d x %d) is not served by the fused small-LP path (its product list is too large)"
@@ -192,7 +194,8 @@ def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_g
                 if wants_shift(nfix, solvers[i].m, regularize, _auto_regularize()):
                     A, b, c, u = checked[i]
                     solvers[i].close()
-                    solvers[i] = IpmSolver(A, b, c, device=device, regularize=1e-14, ub=u, detect_infeasibility=detect_infeasibility)
+                    solvers[i] = IpmSolver(A, b, c, device=device, regularize=1e-14, ub=u, detect_infeasibility=detect_infeasibility,
+                                           scale=scale, scale_passes=scale_passes)
                     solvers[i].init_state_mehrotra()
         solve_small_batch_solvers(solvers, tol=tol, max_iter=max_iter, tol_gap=tol_gap)
         return [sv.get_state() + (_solve_info(sv, certificate=detect_infeasibility),) for sv in solvers]

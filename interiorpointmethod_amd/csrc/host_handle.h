@@ -133,6 +133,10 @@ struct ipm_handle {
     double det_eps_p = 1e-8, det_eps_d = 1e-8;   // ipm_set_infeasibility_tol
     double* det = nullptr;                // [4] record of the last detection (workspace): kind, normalisation, violation, k
     double* cert_mem = nullptr;           // x | y | z of ipm_get_certificate (own allocation, made on first use)
+    // power-of-two equilibration (ipm_equilibrate): the device holds the SCALED problem; the factors live here, on the
+    // host, where the boundary rule applies them (host_equilibrate.h)
+    bool scaled = false;
+    std::vector<double> eq_r, eq_c;       // R (length m, the handle's row order), C (length n)
     int* fixed = nullptr;
     Scalars* h_sc = nullptr;          // pinned host mirror
     bool haveA = false, haveBC = false, haveState = false, predictor_valid = false;

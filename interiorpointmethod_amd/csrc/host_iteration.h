@@ -234,6 +234,7 @@ extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, do
     }
     if (corrector && (rc = read_scalars(h))) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    eq_out(h, dx, h->eq_c, false); eq_out(h, dy, h->eq_r, false); eq_out(h, ds, h->eq_c, true);      // scaled handle: C dx', R dy', ds' / C
     fill_stats(h, stats, 0.0);
     return IPM_OK;
 }

@@ -339,6 +339,7 @@ extern "C" int ipm_set_A_csc(ipm_handle* h, const int32_t* colptr, const int32_t
         }
         const int64_t nz = (int64_t)ri.size();
         if (nz > h->nnz_cap) return fail(h, IPM_ERR_INVALID_ARG, "nnz %lld exceeds the handle's sparse_nnz %lld", (long long)nz, (long long)h->nnz_cap);
+        if (int rc_ = eq_reset(h)) return rc_;               // a valid new A: the handle is unscaled again (host_equilibrate.h)
         std::vector<int> rp(h->m + 1, 0), ci((size_t)nz); std::vector<double> rv((size_t)nz);
         for (int64_t q = 0; q < nz; ++q) rp[ri[q] + 1]++;
         for (int64_t i = 0; i < h->m; ++i) rp[i + 1] += rp[i];
@@ -474,6 +475,7 @@ extern "C" int ipm_set_A_csc(ipm_handle* h, const int32_t* colptr, const int32_t
             img[(int64_t)i * h->np + j] += val[p];      // duplicates sum, as scipy's csc constructor does
         }
     }
+    if (int rc_ = eq_reset(h)) { free(img); return rc_; }      // a valid new A: the handle is unscaled again (host_equilibrate.h)
     hipError_t e = hipMemcpyAsync(h->A, img, sizeof(double) * h->mp * h->np, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     free(img);

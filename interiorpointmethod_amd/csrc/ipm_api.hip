@@ -33,6 +33,7 @@
 #include "form_factor.h"
 #include "lockstep.h"
 #include "lockstep_merge.h"
+#include "equilibrate.h"
 
 #include <algorithm>
 #include <atomic>
@@ -44,6 +45,7 @@
 using namespace ipm;
 
 #include "host_handle.h"
+#include "host_equilibrate.h"
 #include "host_sparse_setup.h"
 #include "host_residuals.h"
 #include "host_factor_solve.h"
@@ -335,6 +337,7 @@ extern "C" int ipm_set_A_dense(ipm_handle* h, const double* A, int64_t ld, int i
     if (h->sparse) return fail(h, IPM_ERR_STATE, "ipm_set_A_dense: the handle was created for a sparse A (sparse_nnz > 0)");
     HIP_TRY(h, hipSetDevice(h->device));
     if (!is_device && !all_finite(A, h->m, h->n, ld)) return fail(h, IPM_ERR_INVALID_INPUT, "A has non-finite entries");
+    if (int rc_ = eq_reset(h)) return rc_;
     HIP_TRY(h, hipMemsetAsync(h->A, 0, sizeof(double) * h->mp * h->np, h->stream));
     HIP_TRY(h, hipMemcpy2DAsync(h->A, sizeof(double) * h->np, A, sizeof(double) * ld, sizeof(double) * h->n, h->m,
                                 is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
@@ -347,11 +350,14 @@ extern "C" int ipm_set_bc(ipm_handle* h, const double* b, const double* c) {
     if (!h || !b || !c) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_bc: bad arguments");
     if (!all_finite(b, 1, h->m, h->m) || !all_finite(c, 1, h->n, h->n)) return fail(h, IPM_ERR_INVALID_INPUT, "b or c has non-finite entries");
     HIP_TRY(h, hipSetDevice(h->device));
+    std::vector<double> bs, cs;                                  // scaled handle: R b, C c (host_equilibrate.h)
+    const double *b0 = b, *c0 = c;
+    b = eq_in(h, bs, b, h->eq_r, false); c = eq_in(h, cs, c, h->eq_c, false);
+    if (!eq_in_range(h, b0, b, (size_t)h->m) || !eq_in_range(h, c0, c, (size_t)h->n))
+        return fail(h, IPM_ERR_INVALID_INPUT, "ipm_set_bc: the handle's scaling would push an entry of b or c out of the normal fp64 range");
     HIP_TRY(h, hipMemcpyAsync(h->b, b, sizeof(double) * h->m, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->c, c, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
-    if (h->bnd) hipLaunchKernelGGL(bnd_norm2_kernel, dim3(1), dim3(VBLK), 0, h->stream, h->b, (int)h->m, bnd_args(h).u, (int)h->n, &h->sc->b_norm);
-    else hipLaunchKernelGGL(norm2_kernel, dim3(1), dim3(VBLK), 0, h->stream, h->b, (int)h->m, &h->sc->b_norm);
-    hipLaunchKernelGGL(norm2_kernel, dim3(1), dim3(VBLK), 0, h->stream, h->c, (int)h->n, &h->sc->c_norm);
+    enqueue_bc_norms(h);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->haveBC = true; h->predictor_valid = false;
@@ -361,6 +367,8 @@ extern "C" int ipm_set_bc(ipm_handle* h, const double* b, const double* c) {
 extern "C" int ipm_set_state(ipm_handle* h, const double* x, const double* y, const double* s) {
     if (!h || !x || !y || !s) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_state: bad arguments");
     HIP_TRY(h, hipSetDevice(h->device));
+    std::vector<double> xs, ys, ss;                              // scaled handle: x / C, y / R, s C
+    x = eq_in(h, xs, x, h->eq_c, true); y = eq_in(h, ys, y, h->eq_r, true); s = eq_in(h, ss, s, h->eq_c, false);
     HIP_TRY(h, hipMemcpyAsync(h->x, x, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->y, y, sizeof(double) * h->m, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->s, s, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
@@ -376,6 +384,7 @@ extern "C" int ipm_get_state(ipm_handle* h, double* x, double* y, double* s) {
     if (y) HIP_TRY(h, hipMemcpyAsync(y, h->y, sizeof(double) * h->m, hipMemcpyDeviceToHost, h->stream));
     if (s) HIP_TRY(h, hipMemcpyAsync(s, h->s, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    eq_out(h, x, h->eq_c, false); eq_out(h, y, h->eq_r, false); eq_out(h, s, h->eq_c, true);      // scaled handle: C x', R y', s' / C
     return IPM_OK;
 }
 
@@ -408,6 +417,9 @@ extern "C" int ipm_set_bounds(ipm_handle* h, const double* u) {
     }
     std::vector<double> uu(np, std::numeric_limits<double>::infinity());     // padding columns: unbounded
     std::copy(u, u + h->n, uu.begin());
+    eq_out(h, uu.data(), h->eq_c, true);                        // scaled handle: u / C (+inf stays +inf)
+    if (!eq_in_range(h, u, uu.data(), (size_t)h->n))
+        return fail(h, IPM_ERR_INVALID_INPUT, "ipm_set_bounds: the handle's scaling would push a bound out of the normal fp64 range");
     HIP_TRY(h, hipMemcpyAsync(h->bnd_mem, uu.data(), sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
     h->bnd = true; h->bnd_nU = nU;
     const BndArgs bd = bnd_args(h);
@@ -423,6 +435,8 @@ extern "C" int ipm_set_bound_state(ipm_handle* h, const double* w, const double*
     if (!h->bnd) return fail(h, IPM_ERR_STATE, "ipm_set_bound_state: no finite bound is set (ipm_set_bounds)");
     HIP_TRY(h, hipSetDevice(h->device));
     const BndArgs bd = bnd_args(h);
+    std::vector<double> wsc, zsc;                                // scaled handle: w / C, z C
+    w = eq_in(h, wsc, w, h->eq_c, true); z = eq_in(h, zsc, z, h->eq_c, false);
     HIP_TRY(h, hipMemcpyAsync(bd.w, w, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(bd.z, z, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(bnd_fill_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, bd.u, bd.w, bd.z, (int)h->n, 0.0, 1);
@@ -440,6 +454,7 @@ extern "C" int ipm_get_bound_state(ipm_handle* h, double* w, double* z) {
     if (w) HIP_TRY(h, hipMemcpyAsync(w, bd.w, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     if (z) HIP_TRY(h, hipMemcpyAsync(z, bd.z, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    eq_out(h, w, h->eq_c, false); eq_out(h, z, h->eq_c, true);      // scaled handle: C w', z' / C
     return IPM_OK;
 }
 
@@ -511,6 +526,7 @@ extern "C" int ipm_get_certificate(ipm_handle* h, double* y, double* z, double* 
     if (y) HIP_TRY(h, hipMemcpyAsync(y, h->cert_mem + n, sizeof(double) * m, hipMemcpyDeviceToHost, h->stream));
     if (z) HIP_TRY(h, hipMemcpyAsync(z, h->cert_mem + n + m, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    eq_out(h, x, h->eq_c, false); eq_out(h, y, h->eq_r, false); eq_out(h, z, h->eq_c, true);      // scaled handle: a certificate of the caller's LP
     if (info) for (int i = 0; i < 4; ++i) info[i] = rec[i];
     return IPM_OK;
 }

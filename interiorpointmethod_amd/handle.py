@@ -42,6 +42,16 @@ def mehrotra_started(make, regularize=0.0, auto_regularize=True):
     return sv
 
 
+SCALE_PASSES = 16          # default cap of the Ruiz passes: the cap, not a tuning knob
+
+
+def check_scale(scale):
+    """THE check of the `scale` keyword, before any device is touched: None (off, the default) or "ruiz"."""
+    if scale not in (None, "ruiz"):
+        raise ValueError('scale must be None or "ruiz", not %r' % (scale,))
+    return scale
+
+
 def _gap_tol(tol, tol_gap):           # the gap tolerance of a solve: tol unless the caller gives one of its own
     return float(tol if tol_gap is None else tol_gap)
 
@@ -52,12 +62,17 @@ class IpmSolver:
     def __init__(self, A, b, c, device=0, eta=0.91, pivot_guard_eps=1e-30, pivot_guard_big=1e64,
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
                  auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
-                 infeasibility_tol=(1e-8, 1e-8)):
+                 infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES):
         """ub: native upper bounds 0 <= x <= ub (length n, +inf = none), checked on the host before any device
         is touched.  The normal matrix keeps order m; a bounded solver cannot join the lockstep batch.
         detect_infeasibility: the stop test also tests the iterate for a certificate of primal infeasibility (status 5) or of
         unboundedness (status 6) with the tolerances infeasibility_tol = (eps_p, eps_d) (IPM_FLAG_DETECT_INFEASIBILITY,
-        DESIGN.md 4-C); certificate() returns it.  Off by default: the solve is then exactly the reference's loop."""
+        DESIGN.md 4-C); certificate() returns it.  Off by default: the solve is then exactly the reference's loop.
+        scale="ruiz": ipm_equilibrate once A, b, c and the bounds are set -- power-of-two Ruiz row / column scaling with at most
+        scale_passes passes.  The device then iterates on the scaled LP (stop test, history and statistics are the
+        scaled problem's); states, directions and certificates enter and leave in the caller's units, exactly.  scaling() reports
+        the factors.  Off by default."""
+        self.scale = check_scale(scale)
         if prepared is None:
             prepared = prepare(A, b, c, dense=dense, reorder=reorder, factor=factor, ub=ub)
         elif ub is not None:
@@ -68,7 +83,7 @@ class IpmSolver:
         # device row i = caller's row perm[i] (sparse A whose rows the host analysis reordered: minimum degree or RCM)
         self._perm = prepared.perm
         self.m, self.n = prepared.m, prepared.n
-        self._host = prepared.host  # caller's row order: used by start-point heuristics only
+        self._host = prepared.host  # the caller's (A, b, c), caller's row order: mehrotra_start and api.unscaled_residuals read it
         self.factor, self.order_info = prepared.factor, prepared.order_info
         A, b, c = prepared.A, prepared.b, prepared.c
         opts = _lib.Options()
@@ -130,6 +145,23 @@ class IpmSolver:
         if detect_infeasibility:
             eps_p, eps_d = infeasibility_tol
             self._check(lib.ipm_set_infeasibility_tol(h, float(eps_p), float(eps_d)))
+        self.scale_info = None
+        if self.scale is not None:
+            info = np.zeros(4)
+            ev = None
+            if use_torch:          # the handle runs on torch's current stream: two events bracket what ipm_equilibrate enqueues there
+                ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev[0].record(torch.cuda.current_stream(dev))
+            self._check(lib.ipm_equilibrate(h, int(scale_passes), _dptr(info)))
+            ms = None
+            if ev is not None:
+                ev[1].record(torch.cuda.current_stream(dev))
+                ev[1].synchronize()
+                ms = float(ev[0].elapsed_time(ev[1]))
+            # ms: DEVICE milliseconds of ipm_equilibrate, first launch to last on the handle's stream (the read-back of the pass flags
+            # between the passes and the rewrite lies inside; None for a handle without torch, which has no stream to time on)
+            self.scale_info = dict(passes=int(info[0]), row_spread_before=float(info[1]), row_spread_after=float(info[2]),
+                                   col_spread_after=float(info[3]), ms=ms)
         self.stats = None
 
     # -- plumbing
@@ -176,6 +208,14 @@ class IpmSolver:
         out = np.empty_like(v)
         out[self._perm] = v
         return out
+
+    def scaling(self):
+        """(r, c, info): the power-of-two factors of ipm_equilibrate -- the device solves (R A C, R b, C c, u / C) -- with r in the
+        caller's row order, and info = dict(passes, row_spread_before, row_spread_after, col_spread_after) (log2 of max / min over
+        the non-empty row / column maxima; None when scale is off).  All ones on an unscaled solver."""
+        r, c = np.empty(self.m), np.empty(self.n)
+        self._check(self._lib.ipm_get_scaling(self._h, _dptr(r), _dptr(c)))
+        return self._rows_out(r), c, self.scale_info
 
     def set_state(self, x, y, s, w=None, z=None):
         """(w, z): the upper slacks and their duals of a bounded solver (entries outside the bounded set are ignored);
@@ -307,14 +347,36 @@ class IpmSolver:
         """Mehrotra's starting point (SIAM J. Optim. 2 (1992) 575-601, section 7): least-squares x and (y, s), shifted
         into the positive orthant and balanced.  NOT the reference's start (x = s = 1, sparse_interior.py:193-200): an
         optional mode that changes the trajectory; two solves with A A^T on the device, the rest is
-        O(nnz) host arithmetic."""
+        O(nnz) host arithmetic.
+        A scaled solver (scale="ruiz") works the recipe on the LP its device holds, (R A C, R b, C c, u / C) -- normal_solve factors
+        (R A C)(R A C)^T -- and returns the point unscaled (C x', R y', s' / C, C w', z' / C), which set_state scales back in
+        exactly: the start of the scaled LP, as init_state_mehrotra computes it on the device."""
         A, b, c = self._host
+        ub, rc = self.ub, None
+        if self.scale_info is not None and self.scale_info["passes"]:
+            r, cc, _ = self.scaling()
+            rc = r, cc
+            if _is_sparse(A):
+                A = A.copy()          # canonical CSC (analysis.prepare): the values scale in place, the structure stays
+                A.data = A.data * r[A.indices] * np.repeat(cc, np.diff(A.indptr))
+            else:
+                A = r.reshape(-1, 1) * np.asarray(A, dtype=np.float64) * cc.reshape(1, -1)
+            b, c = r * np.asarray(b, dtype=np.float64).ravel(), cc * np.asarray(c, dtype=np.float64).ravel()
+            ub = None if ub is None else ub / cc
+        out = self._mehrotra_start_of(A, np.asarray(b, dtype=np.float64).ravel(), np.asarray(c, dtype=np.float64).ravel(), ub)
+        if rc is None:
+            return out
+        r, cc = rc
+        x, y, s = out[0] * cc, out[1] * r, out[2] / cc
+        return (x, y, s) if len(out) == 3 else (x, y, s, out[3] * cc, out[4] / cc)
+
+    def _mehrotra_start_of(self, A, b, c, ub):          # the recipe on the LP (A, b, c, ub) that the device holds
         x = A.T @ self.normal_solve(b)
         y = self.normal_solve(A @ c, reuse_factor=True)
         s = c - A.T @ y
         x = np.asarray(x).ravel(); s = np.asarray(s).ravel()
         if self.bounded:
-            return self._mehrotra_start_bounded(x, np.asarray(y).ravel(), s)
+            return self._mehrotra_start_bounded(x, np.asarray(y).ravel(), s, ub)
         x = x + max(-1.5 * x.min(), 0.0)
         s = s + max(-1.5 * s.min(), 0.0)
         xs = 0.5 * float(x @ s)
@@ -324,13 +386,13 @@ class IpmSolver:
         s = s + xs / x.sum()
         return x, np.asarray(y).ravel(), s
 
-    def _mehrotra_start_bounded(self, x, y, r):
+    def _mehrotra_start_bounded(self, x, y, r, ub):
         """Mehrotra's recipe extended to 0 <= x <= u -> (x, y, s, w, z): w = u - x; on U the reduced cost r = c - A^T y splits
         into s = max(r, 0), z = max(-r, 0) (so s - z = r); (x, w) and (s, z) are shifted into the positive orthant together
         and balanced with x.s + w.z.  Outside U, w = z = 0 and s = r as in the unbounded recipe."""
-        U = np.isfinite(self.ub)
+        U = np.isfinite(ub)
         w = np.zeros(self.n); z = np.zeros(self.n)
-        w[U] = self.ub[U] - x[U]
+        w[U] = ub[U] - x[U]
         s = r.copy()
         s[U] = np.maximum(r[U], 0.0)
         z[U] = np.maximum(-r[U], 0.0)
