@@ -45,6 +45,35 @@ def factor_solve(A, d, rhs, eps=1e-30, big=1e64, shift_rel=0.0, wcap=32, lds=768
     return dict(perm=perm.astype(np.int64), L=L, z=z, fixed=nf.value, stats=dict(zip(keys, st)))
 
 
+def panel_table(A, wcap=32, lds=7680, relax=1.0):
+    """The panel tree the device walks for A (csrc/sparse_symbolic.h: order_rows, then analyse with the product's settings)
+    -> dict(perm (new -> old), c0, w, r, nchild, parent, rows): int64 arrays with one entry per node, fan-in nodes (w = 0)
+    included, children before parents; rows: per node the array of its r rows in device order (own columns first)."""
+    A = sp.csc_matrix(A, dtype=np.float64)
+    A.sum_duplicates()
+    A.sort_indices()
+    m, n = A.shape
+    pi = C.POINTER(C.c_int32)
+    ip = np.ascontiguousarray(A.indptr, dtype=np.int32)
+    ii = np.ascontiguousarray(A.indices, dtype=np.int32)
+    cnt = np.zeros(2, dtype=np.int32)
+    fn = load().sppanel_table
+    rc = fn(m, n, ip.ctypes.data_as(pi), ii.ctypes.data_as(pi), wcap, lds, C.c_double(relax), cnt.ctypes.data_as(pi), None, None, None)
+    if rc:
+        raise RuntimeError("sppanel_table failed with code %d" % rc)
+    perm = np.zeros(m, dtype=np.int32)
+    tab = np.zeros((int(cnt[0]), 5), dtype=np.int32)
+    rows = np.zeros(max(1, int(cnt[1])), dtype=np.int32)
+    rc = fn(m, n, ip.ctypes.data_as(pi), ii.ctypes.data_as(pi), wcap, lds, C.c_double(relax), cnt.ctypes.data_as(pi),
+            perm.ctypes.data_as(pi), tab.ctypes.data_as(pi), rows.ctypes.data_as(pi))
+    if rc:
+        raise RuntimeError("sppanel_table failed with code %d" % rc)
+    tab = tab.astype(np.int64)
+    ends = np.cumsum(tab[:, 2])
+    rows = [rows[e - r:e].astype(np.int64) for e, r in zip(ends, tab[:, 2])]
+    return dict(perm=perm.astype(np.int64), c0=tab[:, 0], w=tab[:, 1], r=tab[:, 2], nchild=tab[:, 3], parent=tab[:, 4], rows=rows)
+
+
 def symbolic_structures(A, wcap=32, lds=7680):
     """(perm, etree parent, entries per column of L) as csrc/sparse_symbolic.h computes them (amalgamation off), for
     the independent NumPy check of tests/test_sparse_symbolic.py."""

@@ -190,4 +190,30 @@ int spsym_structures(int m, int n, const int* cp, const int* ri, int wcap, int l
     return 0;
 }
 
+// The panel tree the DEVICE walks, laid open for tests that must know which regime of csrc/sparse_chol.h an input reaches
+// (tests/sparse_cases.py): order_rows, then analyse on the pattern in that order with the product's settings (wcap 32, lds 7680,
+// relax 1.0 -- what ipm_order_rows caches for ipm_set_A_csc; no environment variable is read).  First call with table = nullptr:
+// counts[2] receives the number of nodes (fan-in nodes included) and the total of their row counts.  Second call: perm[m]
+// (new -> old), table[5 nsn], per node {c0, w, r, nchild, parent}, and rows[counts[1]], the row lists of the nodes one after the
+// other (own columns first, then the rows below, ascending).  Returns 0, or a positive code.
+int sppanel_table(int m, int n, const int* cp, const int* ri, int wcap, int lds, double relax, int* counts, int* perm, int* table,
+                  int* rows) {
+    std::vector<int> pv;
+    OrderInfo oi;
+    Pattern P;
+    if (order_rows(m, n, cp, ri, pv, oi, (int64_t)6e7, &P)) return 1;
+    Supernodes S;
+    if (analyse(P, wcap, lds, S, (int64_t)2.5e8, relax)) return 3;
+    if (!table) { counts[0] = S.nsn; counts[1] = (int)S.rows.size(); return 0; }
+    if (counts[0] != S.nsn || counts[1] != (int)S.rows.size()) return 4;
+    for (int i = 0; i < m; ++i) perm[i] = pv[i];
+    for (size_t q = 0; q < S.rows.size(); ++q) rows[q] = S.rows[q];
+    for (int J = 0; J < S.nsn; ++J) {
+        int* t = table + 5 * (size_t)J;
+        t[0] = S.c0[J]; t[1] = S.w[J]; t[2] = (int)(S.rowptr[(size_t)J + 1] - S.rowptr[J]);
+        t[3] = S.childptr[(size_t)J + 1] - S.childptr[J]; t[4] = S.parent[J];
+    }
+    return 0;
+}
+
 }  // extern "C"
