@@ -336,6 +336,11 @@ int ipm_get_history(ipm_handle* h, ipm_iter_record* out, int32_t capacity, int32
  * n <= 3 m that have the device to themselves), out[11] = 1 while a sparse-factor handle runs one launch per level of its panel tree
  * (shared device) instead of one launch per sweep.  (ABI 4: twelve words; ABI 3 had ten.) */
 int ipm_get_schedule(ipm_handle* h, int32_t out[12]);
+/* The same record for callers that know about words added since (additive: ipm_get_schedule keeps its twelve): the first
+ * min(capacity, 13) words are written, *count (optional) receives the number.  out[12] = 1 while A^T dy of the predictor and
+ * the corrector is streamed behind the backward sweeps of the grouped solves (dense handles with a residual stream that poll the
+ * device; IPM_STREAM_AT=0 and a recovered poll time-out switch it off). */
+int ipm_get_schedule_words(ipm_handle* h, int32_t* out, int32_t capacity, int32_t* count);
 
 /* Fill-reducing order of the ROWS of an m x n sparse A (CSC, host) for the Cholesky of A D^2 A^T: minimum degree on
  * the pattern of A A^T followed by the elimination-tree postorder.  Pure host code (no device is touched): the
@@ -401,6 +406,11 @@ int ipm_debug_get_stamps(ipm_handle* h, long long* out);
  * {type, i, c, q, j0, j1, flags, seq} are written to `items`, their number to *count, the number of update items per lower
  * tile (row-major triangle, nblk (nblk + 1) / 2 entries) to tile_items, and the simulated {end of the factorization, end
  * of the formation} in microseconds to sim_us. */
+/* Host only: the pieces A^T dy is cut into behind a backward sweep (csrc/host_factor_solve.h, at_piece_schedule) for a dense
+ * handle of `nblk` 128-row blocks.  layout = {mp, gsz, rc_chunks, rows_per_chunk}; an entry that is 0 on input is replaced by what
+ * ipm_create chooses for that block count.  One triple per sweep event, in sweep order: {first final row, chunk0, chunk1}; the
+ * first min(capacity, events) triples are written, *count = events.  The last triple is the piece the main stream runs. */
+int ipm_debug_at_pieces(int32_t nblk, int32_t layout[4], int32_t* pieces, int32_t capacity, int32_t* count);
 int ipm_debug_ff_schedule(int32_t nblk, int32_t q, int32_t workers, unsigned char* items, int32_t capacity, int32_t* count,
                           int32_t* tile_items, double sim_us[2]);
 int ipm_get_phase_ms(ipm_handle* h, double out[4]);

@@ -110,4 +110,13 @@ __device__ __forceinline__ bool handoff_skipped(const int* done, unsigned* signa
     return false;
 }
 
+// Progress signal at the ENTRY of a kernel, for the stores of the kernel IN FRONT of it in the same stream: that kernel has ended,
+// and a kernel's end releases its stores at agent scope, so nothing is drained or fenced here -- the first lane of the first workgroup
+// stores the word, relaxed.  `value` is the host's epoch count (monotone over the handle's life: the word is never cleared and a
+// roll-back needs no repair).  Called BEFORE the kernel's test of the `done` latch: like handoff_skipped, a kernel that finds the
+// latch set still signals.  The consumer is ff_gate_kernel on another stream (host_iteration.h, the streamed A^T dy pieces).
+__device__ __forceinline__ void handoff_signal_at_entry(unsigned* word, unsigned value) {
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) __hip_atomic_store(word, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 }  // namespace ipm

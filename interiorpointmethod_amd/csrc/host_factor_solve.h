@@ -312,9 +312,11 @@ static int enqueue_factor(ipm_handle* h, bool use_env = false, int mid_step = -1
     return IPM_OK;
 }
 
+// signal (optional): the launch is the signalling entry point and stores `value` to that progress word at its entry (SweepHook below)
 static void launch_dense_gemv_n(ipm_handle* h, const double* A, int64_t lda, int rows, int cols, const double* v, double sa,
-                                double sb, const double* add, double* out) {
-    launch_twin<LS_GEMV_N>(h, (unsigned)((rows + 3) / 4), {A, lda, rows, cols, v, sa, sb, add, out, &h->sc->done});
+                                double sb, const double* add, double* out, unsigned* signal = nullptr, unsigned value = 0) {
+    if (signal) hipLaunchKernelGGL(gemv_n_signal_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, h->stream, A, lda, rows, cols, v, sa, sb, add, out, &h->sc->done, signal, value);
+    else launch_twin<LS_GEMV_N>(h, (unsigned)((rows + 3) / 4), {A, lda, rows, cols, v, sa, sb, add, out, &h->sc->done});
 }
 
 // Block-step substitution over the blocks [k0, nblk), one launch per block step: forward sweep L z = r, then the backward sweep
@@ -336,10 +338,46 @@ static void enqueue_block_steps(ipm_handle* h, int k0, double* r, double* z, dou
     }
 }
 
+// The backward sweep of the grouped solve makes `out` final from its last row upwards, in EVENTS: first the block steps behind the
+// last full group (ragged block counts: rows >= nG * GR), then the groups nG-1 .. 0 (rows >= g * GR), each with its diagonal
+// gemv_n.  A pass over A that reads `out` by row chunks (gemv_t_kernel: chunk `by` = rows by * rows_per_chunk ...) can follow the
+// events: a chunk is computable once ALL its rows lie at or above the event's first final row, so a chunk that straddles a
+// boundary goes with the later event.  One entry per event, in sweep order: the first final row and the row chunks [chunk0, chunk1)
+// that become computable (empty where a chunk is taller than what the event adds).  The chunks of the LAST event (row 0) are what
+// is left when the sweep has ended.  Empty result: the chunks do not tile the rows (no caller then cuts the pass).
+struct AtPiece { int first_row, chunk0, chunk1; };
+static std::vector<AtPiece> at_piece_schedule(int64_t mp, int gsz, int nblk, int rc_chunks, int rows_per_chunk) {
+    std::vector<AtPiece> ev;
+    if (gsz <= 0 || nblk < gsz || rc_chunks <= 0 || rows_per_chunk <= 0 || (int64_t)rc_chunks * rows_per_chunk != mp || mp != (int64_t)nblk * NB) return ev;
+    const int nG = nblk / gsz;
+    const int64_t GR = (int64_t)gsz * NB;
+    int hi = rc_chunks;
+    auto event = [&](int64_t first) {
+        const int lo = (int)std::min<int64_t>(hi, (first + rows_per_chunk - 1) / rows_per_chunk);
+        ev.push_back({(int)first, lo, hi});
+        hi = lo;
+    };
+    if (nblk > nG * gsz) event(nG * GR);
+    for (int g = nG - 1; g >= 0; --g) event(g * GR);
+    return ev;
+}
+// What a caller that follows the events hands to the sweep.  Event e (index into at_piece_schedule) is SIGNALLED by the kernel that
+// follows its last kernel in the stream -- the sweep's gemv_t behind a group's diagonal gemv_n, the next diagonal gemv_n behind the
+// block steps -- which is launched as the signalling entry point and stores base + e + 1 to `word` at its entry
+// (handoff_signal_at_entry: no event record and no launch on the sweep's stream).  released(e) is called once that kernel is
+// enqueued: whatever the caller enqueues to wait for the word is then BEHIND its releaser in enqueue order, the rule that keeps a
+// device-side wait from deadlocking however streams map to hardware queues.  The last event is not signalled and not reported:
+// the sweep has ended, its rows are the caller's to use in stream order.
+struct SweepHook {
+    unsigned* word;
+    unsigned base;
+    std::function<void(int)> released;
+};
+
 // out = B^{-1} r with the 1024-row group inverses: 4 group steps per sweep at m = 4096
 // wait_last (optional): event after which the LAST group's inverse is available; the forward sweep over the earlier groups
 // does not need it and runs ahead of the wait
-static int enqueue_potrs_grouped(ipm_handle* h, double* r, double* out, hipEvent_t wait_last = nullptr) {
+static int enqueue_potrs_grouped(ipm_handle* h, double* r, double* out, hipEvent_t wait_last = nullptr, const SweepHook* hook = nullptr) {
     const int GS = h->gsz;
     const int GR = GS * 128;
     const int nG = h->nblk / GS;
@@ -358,23 +396,32 @@ static int enqueue_potrs_grouped(ipm_handle* h, double* r, double* out, hipEvent
     }
     // blocks behind the last full group (ragged groups): one launch per block step, as without groups
     enqueue_block_steps(h, nG * GS, r, z, out);
+    int e = 0;                                                            // next sweep event (at_piece_schedule)
+    bool pending = hook && h->nblk > nG * GS;                             // event e is complete and the next kernel has to signal it
     for (int g = nG - 1; g >= 0; --g) {                                   // backward: L^T w = z
-        launch_dense_gemv_n(h, h->gXT + (int64_t)g * GR * GR, GR, GR, GR, z + (int64_t)g * GR, 1.0, 0.0, nullptr, out + (int64_t)g * GR);
+        launch_dense_gemv_n(h, h->gXT + (int64_t)g * GR * GR, GR, GR, GR, z + (int64_t)g * GR, 1.0, 0.0, nullptr, out + (int64_t)g * GR,
+                            pending ? hook->word : nullptr, pending ? hook->base + (unsigned)e + 1u : 0u);
+        if (pending) { hook->released(e); ++e; pending = false; }
         int left = g * GR;
         const int c0 = h->use_env ? std::min(left, h->env_first[g * GS] * NB) : 0;   // columns left of c0 are zero in these rows
         left -= c0;
         if (left > 0) {
             const unsigned gx = (unsigned)((left + 511) / 512);      // blocks per row chunk, 16 row chunks
-            launch_twin<LS_GEMV_T>(h, gx * 16u, {h->B + (int64_t)g * GR * h->mp + c0, h->mp, GR / 16, left, out + (int64_t)g * GR, h->gPart, done, gx});
+            const LsArgs<LS_GEMV_T> t{h->B + (int64_t)g * GR * h->mp + c0, h->mp, GR / 16, left, out + (int64_t)g * GR, h->gPart, done, gx};
+            if (hook) {                                              // group g's rows are final: this kernel signals it
+                hipLaunchKernelGGL(gemv_t_signal_kernel, dim3(gx, 16u), dim3(256), 0, h->stream, t.A, t.lda, t.rows_per_chunk, t.np, t.u, t.part, t.done,
+                                   hook->word, hook->base + (unsigned)e + 1u);
+                hook->released(e); ++e;
+            } else launch_twin<LS_GEMV_T>(h, gx * 16u, t);
             launch_twin<LS_SUB_PARTIALS>(h, (unsigned)((left + 255) / 256), {z + c0, h->gPart, left, 16, done});
-        }
+        } else if (hook && g > 0) pending = true;                    // (envelope: nothing left of the group) the next diagonal gemv_n signals
     }
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
 
 // out = B^{-1} r  (r is consumed; uses t2 as the intermediate)
-static int enqueue_potrs(ipm_handle* h, double* r, double* out, hipEvent_t wait_last = nullptr) {
+static int enqueue_potrs(ipm_handle* h, double* r, double* out, hipEvent_t wait_last = nullptr, const SweepHook* hook = nullptr) {
     if (sp_on(h)) {                     // forward and backward sweep over the elimination tree, one launch each
         const int rm = std::max(16, h->sp_rmax);
         unsigned ep = ++h->sp_epoch;
@@ -391,7 +438,7 @@ static int enqueue_potrs(ipm_handle* h, double* r, double* out, hipEvent_t wait_
         HIP_TRY(h, hipGetLastError());
         return IPM_OK;
     }
-    if (h->grouped_trsv) return enqueue_potrs_grouped(h, r, out, wait_last);
+    if (h->grouped_trsv) return enqueue_potrs_grouped(h, r, out, wait_last, hook);      // (a hook is given to grouped sweeps only: stream_at_on)
     if (wait_last) HIP_TRY(h, hipStreamWaitEvent(h->stream, wait_last, 0));
     enqueue_block_steps(h, 0, r, h->t2, out);
     HIP_TRY(h, hipGetLastError());

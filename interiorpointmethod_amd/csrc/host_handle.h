@@ -18,6 +18,13 @@ struct ipm_handle {
     hipStream_t stream2 = nullptr;            // bulk stream of the Cholesky look-ahead
     hipStream_t stream3 = nullptr;            // residual stream: r_b, r_c, stop test and the predictor rhs under the factorization
     hipEvent_t ev_mid = nullptr, ev_res = nullptr, ev_grp = nullptr, ev_last = nullptr;
+    // A^T dy streamed behind the backward sweeps (host_iteration.h): on until a hand-off time-out or IPM_STREAM_AT=0;
+    // at_epoch counts the sweep events signalled so far (the progress word, at_progress_word, holds the last one: monotone, never
+    // cleared; it would wrap after 2^32 events, some 7e8 iterations of one handle); ev_at joins the residual stream's pieces into the
+    // main stream
+    int stream_at = 1;
+    unsigned at_epoch = 0;
+    hipEvent_t ev_at = nullptr;
     std::vector<hipEvent_t> ev_crit, ev_bulk;
     hipEvent_t ev_fork = nullptr;
     int lookahead = 1;
@@ -69,7 +76,7 @@ struct ipm_handle {
     unsigned sp_epoch = 0;
     double shift_rel = 0.0;               // Tikhonov shift in effect (opt.regularize, or 1e-14 switched on by ipm_solve)
     int auto_reg = 0;                     // 1: the shift was switched on automatically
-    unsigned* d_flags = nullptr;          // [2*nblk] hand-off flags + 1 timeout word (own allocation)
+    unsigned* d_flags = nullptr;          // [2*nblk] hand-off flags + 1 timeout word + 1 progress word of the streamed A^T dy (own allocation)
     int64_t m = 0, n = 0, mp = 0, np = 0;
     int nblk = 0, rc_chunks = 0, rows_per_chunk = 0, vblk = 0;
     ipm_options opt;
@@ -206,6 +213,7 @@ static inline bool lookahead_on(const ipm_handle* h) { return h->lookahead != 0 
 static inline bool wants_polling(const ipm_handle* h) { return lookahead_on(h) && h->flag_sync != 0; }
 static inline bool polls_device(const ipm_handle* h) { return wants_polling(h) && alone_on_device(h); }
 static inline unsigned* timeout_word(const ipm_handle* h) { return h->d_flags + 2 * (size_t)h->nblk; }      // time-out word of the device-side hand-offs
+static inline unsigned* at_progress_word(const ipm_handle* h) { return timeout_word(h) + 1; }               // progress word of the streamed A^T dy (d_flags has four spare words)
 static inline const int* factor_done(const ipm_handle* h) { return h->fdone ? h->fdone : &h->sc->done; }    // `done` word formation / factorization test
 
 // Device memory the handle owns besides its workspace.  STREAM-ORDERED (hipMallocAsync / hipFreeAsync on the handle's

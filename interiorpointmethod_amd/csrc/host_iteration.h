@@ -2,12 +2,46 @@
 // the roll-back / recovery after a poll time-out, and the loops built on them (ipm_newton_direction, ipm_iterate, ipm_solve).
 #pragma once
 // the tail the predictor (corr = 0) and the corrector (corr = 1) share: dy = B^{-1} t1, A^T dy, then the x and s parts of the direction
+// Streamed A^T dy (stream_at_on): the backward sweep makes dy final one 1024-row group at a time, last group first, and the
+// pass over A splits by row chunks without changing a bit (launch_gemv_t_rows), so the piece of every sweep event but the last runs
+// on the residual stream while the sweep goes on: a gate on the handle's progress word (the bounded spin of every device-side
+// wait; a time-out is rolled back like any other and poll_fallback drops the streaming for good), then the piece.  The main stream
+// runs the last event's piece itself and joins the residual stream with one event wait -- that event is recorded behind the last
+// streamed piece, which has normally ended by then.
+// h->atp: the corrector's pieces overwrite the predictor's partials, which mu_aff / corrector_rhs / the predictor's direction
+// kernel read -- all of them IN FRONT of the corrector's sweep on the main stream, and a piece runs only behind the gate that a
+// kernel of that sweep opens.  The next iteration's A^T y (residual stream) is enqueued behind these pieces on the same in-order
+// stream, and behind this iteration's last reader through the event it waits for (ev_mid / ev_fork, recorded on the main stream).
 static int enqueue_solve_direction(ipm_handle* h, hipEvent_t* ev, double* dy, int corr, hipEvent_t wait_last = nullptr) {
     if (ev) HIP_TRY(h, hipEventRecord(ev[0], h->stream));
-    int rc = enqueue_potrs(h, h->t1, dy, wait_last);
-    if (rc) return rc;
-    if (ev) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
-    launch_gemv_t(h, dy);
+    std::vector<AtPiece> pieces;
+    if (stream_at_on(h)) pieces = at_piece_schedule(h->mp, h->gsz, h->nblk, h->rc_chunks, h->rows_per_chunk);
+    if (pieces.empty()) {
+        int rc = enqueue_potrs(h, h->t1, dy, wait_last);
+        if (rc) return rc;
+        if (ev) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
+        launch_gemv_t(h, dy);
+    } else {
+        bool streamed = false;
+        SweepHook hook;
+        hook.word = at_progress_word(h); hook.base = h->at_epoch;
+        h->at_epoch += (unsigned)pieces.size();
+        hook.released = [&](int e) {                             // (the kernel that signals event e is enqueued: the gate goes behind it)
+            const AtPiece& p = pieces[(size_t)e];
+            if (p.chunk1 <= p.chunk0) return;
+            hipLaunchKernelGGL(ff_gate_kernel, dim3(1), dim3(64), 0, h->stream3, hook.word, hook.base + (unsigned)e + 1u, timeout_word(h), &h->sc->done);
+            launch_gemv_t_rows(h, dy, p.chunk0, p.chunk1, h->stream3);
+            streamed = true;
+        };
+        int rc = enqueue_potrs(h, h->t1, dy, wait_last, &hook);
+        if (rc) return rc;
+        if (ev) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
+        launch_gemv_t_rows(h, dy, pieces.back().chunk0, pieces.back().chunk1, h->stream);
+        if (streamed) {
+            HIP_TRY(h, hipEventRecord(h->ev_at, h->stream3));
+            HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_at, 0));
+        }
+    }
     launch_direction(h, corr);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
@@ -136,6 +170,7 @@ static int read_scalars(ipm_handle* h, bool* timed_out = nullptr) {
 // call's effect on the iterate (callers restore their snapshot) and run it again.
 static void poll_fallback(ipm_handle* h) {
     if (h->spf) h->sp_serial = true;          // sparse factor: one workgroup per launch from now on (it never waits)
+    h->stream_at = 0;                         // A^T dy goes back behind the sweeps (its gates poll the device too)
     if (h->ff_last) h->ff_enabled = 0;        // the fused launch timed out: serial formation + factorization from now on, look-ahead kept
     else h->flag_sync = 0;
     ++h->timeouts_recovered;

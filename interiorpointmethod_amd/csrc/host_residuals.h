@@ -10,6 +10,15 @@ static void launch_gemv_t(ipm_handle* h, const double* u, hipStream_t st = nullp
     if (h->sparse) launch_twin<LS_SPMV_CSC_T>(h, (unsigned)((h->np + 15) / 16), {sparse_view(h), (int)h->np, u, h->atp, &h->sc->done}, st);
     else launch_untwinned(h, gemv_t_kernel, dim3((unsigned)((h->np + 511) / 512), (unsigned)h->rc_chunks), dim3(256), st, h->A, h->np, h->rows_per_chunk, (int)h->np, u, h->atp, &h->sc->done);
 }
+// The same pass (dense A) over the row chunks [chunk0, chunk1) only: gemv_t_kernel on the sub-range of A, u and the partials, so it
+// writes exactly the partials the full launch writes for those chunks -- each chunk is one workgroup row's own sum, in the same
+// order.  What cuts A^T dy into pieces that follow the backward sweep (host_iteration.h); never recorded.
+static void launch_gemv_t_rows(ipm_handle* h, const double* u, int chunk0, int chunk1, hipStream_t st) {
+    if (chunk1 <= chunk0) return;
+    const int64_t r0 = (int64_t)chunk0 * h->rows_per_chunk;
+    hipLaunchKernelGGL(gemv_t_kernel, dim3((unsigned)((h->np + 511) / 512), (unsigned)(chunk1 - chunk0)), dim3(256), 0, st ? st : h->stream,
+                       h->A + r0 * h->np, h->np, h->rows_per_chunk, (int)h->np, u + r0, h->atp + (int64_t)chunk0 * h->np, &h->sc->done);
+}
 
 // The vector steps of the iteration, ONE launch function each: it holds the step's fork between the plain kernel and the detect
 // kernel (both have lockstep twins) and the bounded kernels (none: a bounded handle is never recorded, ls_eligible).
@@ -67,4 +76,11 @@ static int enqueue_residual_stream(ipm_handle* h, hipStream_t chain) {
 }
 static bool overlap_residuals(const ipm_handle* h) {
     return h->stream3 != nullptr && h->profiling < 2;          // (created for dense handles from 16 blocks on, ipm_create)
+}
+// Is A^T dy streamed behind the backward sweeps (enqueue_solve_direction)?  Dense handles with a residual stream and grouped sweeps,
+// on the fused and the serial factor path alike.  Its pieces sit behind device-polled gates, so the rule of every other polled
+// hand-off holds: only while the handle polls and is alone on its device (polls_device; wants_polling is what may_poll takes the
+// roll-back snapshot by), never after a recovered time-out (poll_fallback), never while a lockstep program is being recorded.
+static bool stream_at_on(const ipm_handle* h) {
+    return h->stream_at != 0 && overlap_residuals(h) && h->grouped_trsv && !h->sparse && polls_device(h) && !h->ls_rec;
 }

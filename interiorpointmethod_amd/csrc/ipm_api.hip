@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include <deque>
+#include <functional>
 #include <vector>
 
 #include "../../include/ipm_hip.h"
@@ -119,6 +120,22 @@ static void read_env_switches(ipm_handle* h) {
     if (const char* e = getenv("IPM_FF_CHAIN_MODE")) h->ff_chain_mode0 = atoi(e) == 0;
     if (const char* e = getenv("IPM_FF_REF_ENGINE")) h->ff_ref_engine = atoi(e) != 0;
     if (const char* e = getenv("IPM_FF_Q")) h->ff_q = std::max(1, std::min(16, atoi(e)));
+    if (const char* e = getenv("IPM_STREAM_AT")) h->stream_at = atoi(e);
+}
+
+// Group size of the grouped triangular solves (0: none).
+// RAGGED groups (round 3): the block count need not be a multiple of the group size -- floor(nblk / gsz) full groups get
+// their explicit inverses, the blocks left over at the end are substituted block by block (enqueue_potrs_grouped).  From
+// 16 blocks on always groups of 8 (19 blocks: 2 groups + 3 steps, 28 launches per iteration's four sweeps + 10 for the
+// inverses instead of 76); 9 .. 15 blocks: the largest of 8 / 4 that divides, else 8 + leftover; below 9 as before.
+static int group_size(int nblk, bool ragged) {
+    int gsz = 0;
+    if (nblk >= 2 * GS_MAX) { if (ragged || nblk % GS_MAX == 0) gsz = GS_MAX; }
+    else {
+        for (int p2 = GS_MAX; p2 >= 2; p2 /= 2) if (nblk % p2 == 0) { gsz = p2; break; }
+        if (ragged && nblk > GS_MAX && gsz < 4) gsz = GS_MAX;
+    }
+    return gsz;
 }
 
 extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* opts, void* workspace,
@@ -224,19 +241,7 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     if (h->lockstep && h->ls_block_steps) h->grouped_trsv = 0;      // (A/B: block-step substitutions in the lockstep batch)
     if (h->lockstep) h->ss_small_blocks = 1 << 20;      // ONE panel / update kernel shape at every step: step k of all LPs of a batch then shares its launches
     if (h->no_dense) h->grouped_trsv = 0;      // the sparse factor has its own sweeps; a dense entry point on such a handle solves block by block
-    h->gsz = 0;
-    if (h->grouped_trsv) {
-        // RAGGED groups (round 3): the block count need not be a multiple of the group size -- floor(nblk / gsz) full groups get
-        // their explicit inverses, the blocks left over at the end are substituted block by block (enqueue_potrs_grouped).  From
-        // 16 blocks on always groups of 8 (19 blocks: 2 groups + 3 steps, 28 launches per iteration's four sweeps + 10 for the
-        // inverses instead of 76); 9 .. 15 blocks: the largest of 8 / 4 that divides, else 8 + leftover; below 9 as before.
-        const bool ragged = h->ragged_groups;      // (IPM_RAGGED_GROUPS=0 restores the old rule)
-        if (h->nblk >= 2 * GS_MAX) { if (ragged || h->nblk % GS_MAX == 0) h->gsz = GS_MAX; }
-        else {
-            for (int p2 = GS_MAX; p2 >= 2; p2 /= 2) if (h->nblk % p2 == 0) { h->gsz = p2; break; }
-            if (ragged && h->nblk > GS_MAX && h->gsz < 4) h->gsz = GS_MAX;
-        }
-    }
+    h->gsz = h->grouped_trsv ? group_size(h->nblk, h->ragged_groups) : 0;      // (IPM_RAGGED_GROUPS=0 restores the old rule)
     if (h->gsz > 0) {
         const size_t nG = (size_t)h->nblk / h->gsz, GR = (size_t)h->gsz * 128;
         CREATE_TRY(dev_malloc(device, h->stream, (void**)&h->gXT, sizeof(double) * nG * GR * GR));
@@ -268,6 +273,7 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     CREATE_TRY(hipEventCreateWithFlags(&h->ev_res, hipEventDisableTiming));
     CREATE_TRY(hipEventCreateWithFlags(&h->ev_grp, hipEventDisableTiming));
     CREATE_TRY(hipEventCreateWithFlags(&h->ev_last, hipEventDisableTiming));
+    CREATE_TRY(hipEventCreateWithFlags(&h->ev_at, hipEventDisableTiming));
     if (h->ff_chain_mode0) {
         // 0 asked for the chain as three launches per step beside 224 workers: that structure met a recovered hand-off time-out and
         // has been removed.  Whoever asks for it by name is told so, not given another structure silently.
@@ -308,6 +314,7 @@ extern "C" int ipm_destroy(ipm_handle* h) {
     if (h->ev_res) (void)hipEventDestroy(h->ev_res);
     if (h->ev_grp) (void)hipEventDestroy(h->ev_grp);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
+    if (h->ev_at) (void)hipEventDestroy(h->ev_at);
     if (h->stream2) (void)hipStreamDestroy(h->stream2);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -549,14 +556,37 @@ extern "C" int ipm_get_history(ipm_handle* h, ipm_iter_record* out, int32_t capa
     return IPM_OK;
 }
 
+static const int SCHEDULE_WORDS = 13;
+extern "C" int ipm_get_schedule_words(ipm_handle* h, int32_t* out, int32_t capacity, int32_t* count) {
+    if (!h || !out || capacity < 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_schedule_words: bad arguments");
+    const int live = live_on_device(h);
+    int32_t w[SCHEDULE_WORDS];
+    w[0] = h->nblk; w[1] = h->last_gs; w[2] = h->grouped_trsv;
+    w[3] = (may_poll(h) && live <= 1) ? 1 : 0;
+    w[4] = h->n_counter_steps; w[5] = h->n_event_steps; w[6] = h->use_env ? 1 : 0; w[7] = live;
+    w[8] = h->timeouts_recovered; w[9] = h->small ? 1 : 0;
+    w[10] = h->ff_last ? 1 : 0; w[11] = (h->spf && sp_level(h)) ? 1 : 0;
+    w[12] = stream_at_on(h) ? 1 : 0;
+    const int n = std::min<int>(capacity, SCHEDULE_WORDS);
+    memcpy(out, w, sizeof(int32_t) * (size_t)n);
+    if (count) *count = n;
+    return IPM_OK;
+}
 extern "C" int ipm_get_schedule(ipm_handle* h, int32_t out[12]) {
     if (!h || !out) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_schedule: bad arguments");
-    const int live = live_on_device(h);
-    out[0] = h->nblk; out[1] = h->last_gs; out[2] = h->grouped_trsv;
-    out[3] = (may_poll(h) && live <= 1) ? 1 : 0;
-    out[4] = h->n_counter_steps; out[5] = h->n_event_steps; out[6] = h->use_env ? 1 : 0; out[7] = live;
-    out[8] = h->timeouts_recovered; out[9] = h->small ? 1 : 0;
-    out[10] = h->ff_last ? 1 : 0; out[11] = (h->spf && sp_level(h)) ? 1 : 0;
+    return ipm_get_schedule_words(h, out, 12, nullptr);
+}
+
+extern "C" int ipm_debug_at_pieces(int32_t nblk, int32_t layout[4], int32_t* pieces, int32_t capacity, int32_t* count) {
+    if (nblk < 1 || nblk > (1 << 13) || !layout || !count) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_debug_at_pieces: bad arguments");
+    const Layout L = make_layout((int64_t)nblk * NB, 64);
+    if (layout[0] <= 0) layout[0] = (int32_t)L.mp;
+    if (layout[1] <= 0) layout[1] = group_size(nblk, true);
+    if (layout[2] <= 0) layout[2] = L.rc_chunks;
+    if (layout[3] <= 0) layout[3] = L.rows_per_chunk;
+    const std::vector<AtPiece> ev = at_piece_schedule(layout[0], layout[1], nblk, layout[2], layout[3]);
+    *count = (int32_t)ev.size();
+    if (pieces) for (size_t e = 0; e < ev.size() && (int64_t)e < capacity; ++e) { pieces[3 * e] = ev[e].first_row; pieces[3 * e + 1] = ev[e].chunk0; pieces[3 * e + 2] = ev[e].chunk1; }
     return IPM_OK;
 }
 

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "gemm_nt_f64.h"
+#include "handoff.h"
 #include "iteration_rules.h"
 
 namespace ipm {
@@ -118,6 +119,23 @@ __device__ __forceinline__ void gemv_t_kernel_body(const double* __restrict__ A,
 __global__ __launch_bounds__(256) void gemv_t_kernel(const double* __restrict__ A, int64_t lda, int rows_per_chunk,
                                                      int np, const double* __restrict__ u, double* part,
                                                      const int* done) { gemv_t_kernel_body(A, lda, rows_per_chunk, np, u, part, done, blockIdx.x, blockIdx.y); }
+
+// The same two kernels with a progress signal at their entry (handoff_signal_at_entry): the backward sweep of the grouped solve
+// launches them where the kernel in front has made a range of rows of its result final, and the pieces of A^T dy that wait for
+// those rows on the residual stream are released without an event or a launch of their own (host_factor_solve.h: SweepHook).
+__global__ __launch_bounds__(256) void gemv_n_signal_kernel(const double* __restrict__ A, int64_t lda, int mp,
+                                                            int np, const double* __restrict__ v, double sa,
+                                                            double sb, const double* __restrict__ add,
+                                                            double* out, const int* done, unsigned* progress, unsigned value) {
+    handoff_signal_at_entry(progress, value);
+    gemv_n_kernel_body(A, lda, mp, np, v, sa, sb, add, out, done, blockIdx.x, gridDim.x);
+}
+__global__ __launch_bounds__(256) void gemv_t_signal_kernel(const double* __restrict__ A, int64_t lda, int rows_per_chunk,
+                                                            int np, const double* __restrict__ u, double* part,
+                                                            const int* done, unsigned* progress, unsigned value) {
+    handoff_signal_at_entry(progress, value);
+    gemv_t_kernel_body(A, lda, rows_per_chunk, np, u, part, done, blockIdx.x, blockIdx.y);
+}
 
 struct VecArgs {
     int m, n, np, rc_chunks;       // true sizes, padded n, number of gemv_t row chunks
