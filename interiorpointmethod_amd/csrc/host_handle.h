@@ -255,10 +255,24 @@ static bool async_alloc_ok(int device) {
     }
     return st == 1;
 }
+// Test knob IPM_TEST_ALLOC_FILL=<byte 0..255>: every device allocation of the library (and the workspace, ipm_create) is filled with
+// that byte on the stream it is first used on, BEFORE any write of the library's own -- so that a result which depends on what the memory
+// held before shows (0xFF: NaN as doubles, -1 as indices; tests/test_gpu_residue.py).  Read at each allocation, so that a test can
+// switch it between two handles of one process.  Unset: -1, and nothing is enqueued.
+static int alloc_fill_byte() {
+    const char* e = getenv("IPM_TEST_ALLOC_FILL");
+    if (!e || !*e) return -1;
+    const int v = atoi(e);
+    return v < 0 || v > 255 ? -1 : v;
+}
+static hipError_t alloc_fill(void* p, size_t bytes, hipStream_t stream) {
+    const int v = alloc_fill_byte();
+    return v < 0 ? hipSuccess : hipMemsetAsync(p, v, bytes, stream);
+}
 static hipError_t dev_malloc(int device, hipStream_t stream, void** p, size_t bytes) {
     if (bytes == 0) bytes = 16;
-    if (async_alloc_ok(device)) return hipMallocFromPoolAsync(p, bytes, g_pool[device], stream);
-    return hipMalloc(p, bytes);
+    const hipError_t e = async_alloc_ok(device) ? hipMallocFromPoolAsync(p, bytes, g_pool[device], stream) : hipMalloc(p, bytes);
+    return e != hipSuccess ? e : alloc_fill(*p, bytes, stream);
 }
 static void dev_free(int device, hipStream_t stream, void* p) {
     if (!p) return;

@@ -19,6 +19,8 @@ struct LuRun {
             return fail(nullptr, IPM_ERR_WORKSPACE, "lu: cannot allocate %zu bytes of device memory for %s: %s", bytes, what, hipGetErrorString(e));
         }
         allocs.push_back(*p);
+        if ((e = alloc_fill(*p, bytes, stream)) != hipSuccess)       // test knob IPM_TEST_ALLOC_FILL (host_handle.h)
+            return fail(nullptr, IPM_ERR_HIP, "lu: filling %s failed: %s", what, hipGetErrorString(e));
         return IPM_OK;
     }
 };

@@ -100,7 +100,8 @@ extern "C" int ipm_workspace_bytes_opts(int64_t m, int64_t n, const ipm_options*
 
 // ------------------------------------------------------------------------------- handle
 // Every IPM_* switch ipm_create reads; what follows from them and the option flags (a flag overrides its switch) is decided in
-// ipm_create.  Read at their own stage: IPM_SP_* (build_sparse_factor), IPM_FF_PROF / IPM_FF_TRACE_ITEMS (ff_build), IPM_LU_NB, ff_schedule.h.
+// ipm_create.  Read at their own stage: IPM_SP_* (build_sparse_factor), IPM_FF_PROF / IPM_FF_TRACE_ITEMS (ff_build), IPM_LU_NB, ff_schedule.h,
+// IPM_TEST_ALLOC_FILL (at every allocation: alloc_fill, host_handle.h).
 static void read_env_switches(ipm_handle* h) {
     if (const char* e = getenv("IPM_TEST_SPIN_LIMIT")) h->spin_limit = (unsigned)std::max(1, atoi(e));
     if (const char* e = getenv("IPM_ENVELOPE")) h->envelope = atoi(e);
@@ -187,6 +188,7 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
         h->own_ws = true;
     }
     char* base = (char*)h->ws;
+    CREATE_TRY(alloc_fill(base, L.total, h->stream));      // test knob IPM_TEST_ALLOC_FILL (host_handle.h): before the uploads and the zeroing below
     h->A = (double*)(base + L.off_A);
     h->B = h->no_dense ? nullptr : (double*)(base + L.off_B);
     h->invD = h->no_dense ? nullptr : (double*)(base + L.off_inv);
