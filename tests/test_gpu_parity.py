@@ -116,9 +116,9 @@ def test_tiny_normal_matrix_is_not_guarded():
 
 # ------------------------------------------------------------------ sparse-A front end
 @pytest.mark.parametrize("m,n,dens", [(5, 9, 0.5), (130, 400, 0.02), (700, 1500, 0.004), (300, 200, 0.05)])
-def test_sparse_formation_and_spmv_match_dense(m, n, dens):
-    """CSR/CSC kernels (sparse_ops.h) against the dense MFMA path on the same matrix, including an
-    empty row and an empty column."""
+def test_sparse_formation_matches_dense(m, n, dens):
+    """The sparse formation of B (sparse_ops.h) against the dense MFMA path on the same matrix, including an
+    empty row and an empty column.  (The SpMVs: tests/test_gpu_sparse_front.py.)"""
     rng = np.random.default_rng(m + n)
     A = sparse.random(m, n, density=dens, random_state=np.random.RandomState(m), format="lil")
     A[0, :] = 0.0
@@ -217,7 +217,7 @@ def test_tile_envelope_skips_only_zeros():
     x0 = rng.uniform(0.5, 1.5, n); y0 = rng.standard_normal(m); s0 = rng.uniform(0.5, 1.5, n)
     b, c = A @ x0, A.T @ y0 + s0
     with ipm.IpmSolver(A, b, c, reorder=None) as sp_, ipm.IpmSolver(A, b, c, dense=True) as de_:
-        assert sp_.sparse
+        assert sp_.sparse and sp_.factor == "dense" and sp_.schedule()["envelope"] == 1
         sp_.init_state(1.0); de_.init_state(1.0)
         for u, v in zip(sp_.newton_direction(False), de_.newton_direction(False)):
             assert rel(u, v) < 1e-10
