@@ -411,6 +411,16 @@ int ipm_debug_get_stamps(ipm_handle* h, long long* out);
  * ipm_create chooses for that block count.  One triple per sweep event, in sweep order: {first final row, chunk0, chunk1}; the
  * first min(capacity, events) triples are written, *count = events.  The last triple is the piece the main stream runs. */
 int ipm_debug_at_pieces(int32_t nblk, int32_t layout[4], int32_t* pieces, int32_t capacity, int32_t* count);
+/* Host only: the step plan of the dense blocked Cholesky (csrc/chol_plan.h, chol_step_plan) of a handle of `nblk` 128-row blocks and m
+ * rows (m <= 0: all of them).  knobs = {look-ahead switch, device polling, two_level, group_steps, ss_small_blocks, shift in effect} as
+ * the handle holds them (look-ahead still needs more than two blocks); env_last: the tile envelope (nblk entries) or NULL.
+ * totals = {look-ahead, polling, group size, counter steps, event steps}; steps (capacity in records, written when >= nblk) receives one
+ * record of IPM_CHOL_STEP_WORDS words per block step: {potrf panels, rows, rem, shape (0 narrow, 1 wide, 2 look-ahead), g0, gend, kcols,
+ * window, crit_wait (0 none, 1 counter, 2 event), crit_count, crit_flag, poll_count, bulk (0 none, 1 counter, 2 event), bulk_count,
+ * bulk_event}. */
+#define IPM_CHOL_STEP_WORDS 15
+int ipm_debug_chol_plan(int32_t nblk, int64_t m, const int32_t knobs[6], const int32_t* env_last, int32_t totals[5], int32_t* steps,
+                        int32_t capacity);
 int ipm_debug_ff_schedule(int32_t nblk, int32_t q, int32_t workers, unsigned char* items, int32_t capacity, int32_t* count,
                           int32_t* tile_items, double sim_us[2]);
 int ipm_get_phase_ms(ipm_handle* h, double out[4]);

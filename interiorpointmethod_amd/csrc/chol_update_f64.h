@@ -140,8 +140,7 @@ inline hipError_t launch_chol_update(GemmNT g, hipStream_t stream, int skip_firs
     const bool plain = !g.w && !g.wait_on && g.unit_diag_from < 0 && g.batch <= 1 && g.batch2 <= 1 && g.M % 128 == 0 && g.N % 128 == 0 &&
                        g.K % 16 == 0 && g.K >= 16 && g.ldp * 128 * 8 < (int64_t)1 << 31 && g.ldq * 128 * 8 < (int64_t)1 << 31 && g.ldc * 128 * 8 < (int64_t)1 << 31;
     if (!plain) return launch_gemm_nt<128, 128, 16, 2, 2>(g, stream, nullptr, 512, skip_first);
-    const int ntm = g.M / 128, ntn = g.N / 128;
-    const int tiles = (g.lower ? ntm * (ntm + 1) / 2 : ntm * ntn) - skip_first;
+    const int tiles = gemm_tiles(g.M, g.N, 128, 128, g.lower, skip_first);
     if (tiles <= 0) return hipSuccess;
     g.tile_offset = skip_first;
     g.n_direct = tiles; g.split_p = 1; g.chunk_stages = g.K / 16; g.slab = nullptr; g.batch = 1; g.batch2 = 1;

@@ -448,7 +448,7 @@ __device__ __forceinline__ void ff_chain_role(const FFChain& c, double* lds) {
         a.fixed = c.fixed; a.done = nullptr; a.stamps = nullptr;
         a.wait_on = c.dready + k; a.wait_count = 4u; a.signal = c.potrfdone + k; a.timeout = c.timeout; a.dbg = c.dbg; a.dbg_tag = (unsigned)k;
         a.trace = c.trace ? c.trace + 12 * (size_t)k : nullptr;
-        const int real = c.m - k * NB;                       // 16-wide panels that hold rows of the LP (potrf_panels of the host)
+        const int real = c.m - k * NB;                       // 16-wide panels that hold rows of the LP (CholStep::potrf_panels of the host, chol_plan.h)
         a.nt = (c.shift_rel != 0.0 || real >= NB) ? NB / 16 : (real + 15) / 16 < 1 ? 1 : (real + 15) / 16;
         a.rows = real;
         potrf_diag_body<false>(a, W, dinv_s);

@@ -316,12 +316,18 @@ constexpr int kSlabTiles = 512;      // capacity of the split-K slab workspace, 
 struct GemmRecorder { void (*fn)(void* ctx, int bm, int bn, int bk, int wm, int wn, const GemmNT& g, int grid); void* ctx; };
 inline thread_local GemmRecorder* g_gemm_recorder = nullptr;
 
+// Output tiles of a launch of M x N in BM x BN tiles -- the lower triangle only (lower != 0) and without the first skip_first of
+// them: the workgroups of an unsplit launch, i.e. what a consumer that polls the launch's completion counter has to wait for.
+// The ONE statement of that count: launch_gemm_nt, launch_chol_update and the step plan of the Cholesky (chol_plan.h) all call it.
+constexpr int gemm_tiles(int M, int N, int BM, int BN, int lower, int skip_first) {
+    return (lower ? (M / BM) * (M / BM + 1) / 2 : (M / BM) * (N / BN)) - skip_first;
+}
+
 // slots = workgroups resident at once (2 per CU for the 128x128 tile).  slab may be null (no split).
 template <int BM, int BN, int BK, int WAVES_M, int WAVES_N>
 inline hipError_t launch_gemm_nt(GemmNT g, hipStream_t stream, double* slab = nullptr, int slots = 512,
                                  int skip_first = 0) {
-    int ntm = g.M / BM, ntn = g.N / BN;
-    int tiles = (g.lower ? ntm * (ntm + 1) / 2 : ntm * ntn) - skip_first;
+    int tiles = gemm_tiles(g.M, g.N, BM, BN, g.lower, skip_first);
     g.tile_offset = skip_first;
     if (tiles <= 0) return hipSuccess;
     if (g.signal || g.wait_on) slab = nullptr;               // hand-off launches are never split

@@ -1,5 +1,5 @@
-// host_factor_solve.h -- host side, unit 4: formation of B = A D A^T, the look-ahead Cholesky schedule (dense) and the launches of
-// the sparse factor, the group inverses and the triangular sweeps.
+// host_factor_solve.h -- host side, unit 4: formation of B = A D A^T, the launches of the dense blocked Cholesky (its look-ahead
+// schedule is the step plan of chol_plan.h), of the sparse factor, the group inverses and the triangular sweeps.
 #pragma once
 static inline bool sp_on(const ipm_handle* h) { return h->spf && !h->spf_off; }
 // Sparse factor: one launch per LEVEL of the panel tree (the kernel boundary is the hand-off, nothing spins) instead of one
@@ -122,67 +122,51 @@ static int enqueue_group_inverses(ipm_handle* h, int g0 = 0, int g1 = -1, hipStr
     return IPM_OK;
 }
 
-// 16-wide panels of diagonal block k that hold rows of the LP (the rest of the block is padding: unit diagonal): potrf_diag
-// factors only those -- the last real block of an LP whose row count is no multiple of 128, and the blocks the layout pads with
-static inline int potrf_panels(const ipm_handle* h, int k) {
-    if (h->shift_rel != 0.0) return NB / 16;              // (the Tikhonov shift touches every diagonal entry: keep the full block)
-    const int64_t real = h->m - (int64_t)k * NB;
-    return real >= NB ? NB / 16 : (int)std::max<int64_t>(1, (real + 15) / 16);
+// Multifrontal sparse Cholesky: one launch walks the elimination tree.
+// sp_fwd_rhs: right-hand side whose forward substitution rides on the factorization (z -> h->t2); the next enqueue_potrs of that
+// right-hand side then runs the backward sweep only (h->sp_fwd_fused).
+static int enqueue_sparse_factor(ipm_handle* h, const double* sp_fwd_rhs) {
+    if (!h->sp_fuse_fwd) sp_fwd_rhs = nullptr;
+    h->sp_fwd_fused = sp_fwd_rhs;
+    const unsigned ep = ++h->sp_epoch;
+    sp_walk(h, sp_level(h), /*leaves_first=*/true, [&](unsigned grid, const SpRec* recs, int count) {
+        hipLaunchKernelGGL((sp_chol_kernel<SPC_THREADS>), dim3(grid), dim3(SPC_THREADS), h->sp_lds_chol, h->stream, h->spF, ep,
+                           &h->sc->maxdiag, h->opt.pivot_guard_eps, h->opt.pivot_guard_big, h->shift_rel, &h->sc->fixed,
+                           h->sp_lds_doubles, recs, count, sp_fwd_rhs, h->t2, h->sp_fv_off);
+    });
+    HIP_TRY(h, hipGetLastError());
+    return IPM_OK;
 }
 
-// blocked guarded Cholesky of B in place (lower), right-looking with one step of look-ahead:
-//   main stream : potrf_diag(k) -> [wait bulk(k-1)] -> panel rows of block k+1 -> update of tile (k+1,k+1)
-//   bulk stream : [wait diag(k)] panel rows >= k+2 -> [wait crit(k)] rest of the trailing update
-// so the serial diagonal-block factorization of step k+1 overlaps the bulk update of step k.
-// sp_fwd_rhs (sparse factor only): right-hand side whose forward substitution rides on the factorization (z -> h->t2); the next
-// enqueue_potrs of that right-hand side then runs the backward sweep only (h->sp_fwd_fused).
-static int enqueue_factor(ipm_handle* h, bool use_env = false, int mid_step = -1, int ginv_step = -1, const double* sp_fwd_rhs = nullptr) {
-    if (sp_on(h)) {                     // multifrontal sparse Cholesky: one launch walks the elimination tree
-        if (!h->sp_fuse_fwd) sp_fwd_rhs = nullptr;
-        h->sp_fwd_fused = sp_fwd_rhs;
-        const unsigned ep = ++h->sp_epoch;
-        sp_walk(h, sp_level(h), /*leaves_first=*/true, [&](unsigned grid, const SpRec* recs, int count) {
-            hipLaunchKernelGGL((sp_chol_kernel<SPC_THREADS>), dim3(grid), dim3(SPC_THREADS), h->sp_lds_chol, h->stream, h->spF, ep,
-                               &h->sc->maxdiag, h->opt.pivot_guard_eps, h->opt.pivot_guard_big, h->shift_rel, &h->sc->fixed,
-                               h->sp_lds_doubles, recs, count, sp_fwd_rhs, h->t2, h->sp_fv_off);
-        });
-        HIP_TRY(h, hipGetLastError());
-        return IPM_OK;
-    }
+// "Which kernel runs the trailing update", stated once: chol_update_kernel, or the generic kernel of rounds 1-2 (IPM_BULK_VARIANT=7)
+static hipError_t launch_trailing_update(const ipm_handle* h, const GemmNT& g, hipStream_t stream, int skip_first) {
+    if (h->bulk_variant == 7) return launch_gemm_nt<128, 128, 16, 2, 2>(g, stream, nullptr, 512, skip_first);
+    return launch_chol_update(g, stream, skip_first);
+}
+
+// blocked guarded Cholesky of B in place (lower).  The schedule -- groups, envelope clip, step shapes, which hand-off is a counter
+// and which an event, every polled count -- is chol_step_plan (chol_plan.h); this function walks the plan, fills the
+// argument structs from a step's record and launches.  mid_step / ginv_step: block steps at which the caller's residual stream
+// and the inverses of the complete groups start (host_iteration.h); they are hooks of the call site, not schedule.
+// sp_fwd_rhs: see enqueue_sparse_factor (sparse factor only).
+static int enqueue_factor(ipm_handle* h, int mid_step = -1, int ginv_step = -1, const double* sp_fwd_rhs = nullptr) {
+    if (sp_on(h)) return enqueue_sparse_factor(h, sp_fwd_rhs);
     if (int rc_ = ensure_dense_B(h)) return rc_;
     const int* done = factor_done(h);
-    use_env = use_env && h->use_env;
     // threshold scale = max diag over the TRUE rows only (padding rows carry a unit diagonal)
     launch_twin<LS_MAXDIAG>(h, 1u, {h->B, h->mp, (int)h->m, &h->sc->maxdiag, done});
-    const bool la = lookahead_on(h);
-    // group size of the two-level schedule.  Measured (factor, ms): 16384 x 32768: 39.7 / 34.9 / 33.4 / 32.9 / 32.5 for groups
-    // of 1 / 2 / 3 / 4 / 6; 8192 x 16384: 7.87 / 7.46 / 7.34 / 7.34 for 1 / 2 / 3 / 4; but 4096 x 8192: 2.21 -> 2.36 with groups
-    // of 2 (half of its steps are bound by the pivot chain, which grouping lengthens): on from 48 blocks.
-    // IPM_TWO_LEVEL=0 disables, IPM_GROUP_STEPS=n forces a group size (>= 8 blocks).
-    int gs = 1;
-    if (la && !use_env && h->two_level != 0) {
-        if (h->group_steps > 0) gs = h->nblk >= 8 ? h->group_steps : 1;
-        else if (h->nblk >= 96) gs = 4;
-        else if (h->nblk >= 48) gs = 3;
-    }
-    // Group table: uniform groups of gs block columns (from 48 blocks on; one-level below that -- pairing only the head of the
-    // factorization was measured and does not pay below 48 blocks either: 2.158 / 2.157 / 2.182 / 2.213 ms for 0 / 4 / 8 / 16 paired steps)
-    std::vector<int> grp_lo(h->nblk), grp_hi(h->nblk);
-    for (int k = 0; k < h->nblk; ++k) {
-        if (gs > 1) { grp_lo[k] = (k / gs) * gs; grp_hi[k] = std::min(grp_lo[k] + gs, h->nblk); }
-        else { grp_lo[k] = k; grp_hi[k] = k + 1; }
-    }
-    h->last_gs = gs;
-    hipStream_t sm = h->stream, sb = la ? h->stream2 : h->stream;
-    const bool fs = polls_device(h);                      // device-polled hand-offs (only while this is the one live handle on the device)
-    h->n_counter_steps = 0; h->n_event_steps = 0;
-    std::vector<unsigned> bulk_wgs(h->nblk, 0u);          // workgroups of the bulk update of each step
-    if (la) {
-        if (fs) HIP_TRY(h, hipMemsetAsync(h->d_bulk_done, 0, sizeof(unsigned) * 2 * (size_t)h->nblk, sm));
+    const CholPlan plan = chol_step_plan(h->nblk, h->m, h->mp, lookahead_on(h), polls_device(h), h->two_level, h->group_steps,
+                                         h->ss_small_blocks, h->shift_rel != 0.0, h->use_env ? h->env_last.data() : nullptr);
+    h->last_gs = plan.gs; h->n_counter_steps = plan.n_counter_steps; h->n_event_steps = plan.n_event_steps;
+    hipStream_t sm = h->stream, sb = plan.lookahead ? h->stream2 : h->stream;
+    unsigned* const bulk_done = h->d_bulk_done;                     // counters: [k] bulk update of step k, [nblk + k] its critical panel
+    if (plan.polling) HIP_TRY(h, hipMemsetAsync(bulk_done, 0, sizeof(unsigned) * 2 * (size_t)h->nblk, sm));
+    if (plan.lookahead) {
         HIP_TRY(h, hipEventRecord(h->ev_fork, sm));
         HIP_TRY(h, hipStreamWaitEvent(sb, h->ev_fork, 0));
     }
     for (int k = 0; k < h->nblk; ++k) {
+        const CholStep& s = plan.steps[k];
         PotrfDiag pd;
         pd.Bkk = h->B + (int64_t)k * NB * (h->mp + 1); pd.ld = h->mp;
         pd.inv = h->invD + (int64_t)k * NB * NB;
@@ -190,8 +174,8 @@ static int enqueue_factor(ipm_handle* h, bool use_env = false, int mid_step = -1
         pd.fixed = &h->sc->fixed; pd.done = done; pd.stamps = nullptr;
         pd.wait_on = nullptr; pd.wait_count = 0; pd.signal = nullptr; pd.timeout = nullptr; pd.dbg = nullptr; pd.dbg_tag = 0;
         pd.trace = nullptr;
-        pd.nt = potrf_panels(h, k);
-        pd.rows = (int)(h->m - (int64_t)k * NB);
+        pd.nt = s.potrf_panels;
+        pd.rows = s.rows;
         if (h->stamp_buf && k == 0) {                               // (IPM_POTRF_STAMPS: the stamping instantiation has no twin)
             pd.stamps = h->stamp_buf;
             if (getenv("IPM_POTRF_SKIP")) pd.dbg_tag = (unsigned)atoi(getenv("IPM_POTRF_SKIP"));
@@ -207,107 +191,56 @@ static int enqueue_factor(ipm_handle* h, bool use_env = false, int mid_step = -1
             if (rc_) return rc_;
         }
         if (k == mid_step) { int rc_ = enqueue_residual_stream(h, sm); if (rc_) return rc_; }
-        int rem = (int)(h->mp - (int64_t)(k + 1) * NB);
-        if (rem <= 0) break;
-        if (use_env) {                                              // rows below the envelope are zero and stay zero
-            rem = std::min(rem, (h->env_last[k] - k) * NB);
-            if (rem <= 0) {                                         // nothing below the diagonal block in this column
-                if (la) HIP_TRY(h, hipEventRecord(h->ev_bulk[k], sb));
-                continue;
-            }
+        if (s.rem <= 0) {                                           // the last block column, or nothing below the diagonal block in this one
+            if (s.bulk_event) HIP_TRY(h, hipEventRecord(h->ev_bulk[k], sb));
+            continue;
         }
         double* panel = h->B + (int64_t)(k + 1) * NB * h->mp + (int64_t)k * NB;
         GemmNT t = gemm_defaults();                                 // L_ik = B_ik inv(L_kk)^T, in place
         t.P = panel; t.ldp = h->mp; t.Q = pd.inv; t.ldq = NB;
-        t.C = panel; t.ldc = h->mp; t.M = rem; t.N = NB; t.K = NB;
+        t.C = panel; t.ldc = h->mp; t.M = s.rem; t.N = NB; t.K = NB;
         t.lower = 0; t.done = done;
-        GemmNT u = gemm_defaults();                                 // B_ij -= L_ik L_jk^T
-        u.P = panel; u.ldp = h->mp; u.Q = panel; u.ldq = h->mp;
-        u.C = h->B + (int64_t)(k + 1) * NB * (h->mp + 1); u.ldc = h->mp; u.M = rem; u.N = rem; u.K = NB;
+        GemmNT u = gemm_defaults();                                 // B_ij -= L_ik L_jk^T: block columns k-kcols+1 .. k of L, rows >= k+1
+        u.P = panel - (int64_t)(s.kcols - 1) * NB; u.ldp = h->mp; u.Q = u.P; u.ldq = h->mp;
+        u.C = h->B + (int64_t)(k + 1) * NB * (h->mp + 1); u.ldc = h->mp; u.M = s.rem; u.N = s.rem; u.K = s.kcols * NB;
         u.alpha = -1.0; u.beta = 1.0; u.lower = 1; u.done = done;
-        if (!la) {
-            // one stream (batched mode, small handles): panel and update are BOTH on the dependent chain of the step.  With few
-            // trailing blocks the chip is empty anyway: narrower tiles (32-row panel strips on 8 waves / 64 x 64 update tiles) are
-            // latency-shorter kernels -- ss_small_blocks = trailing blocks up to which they are used (16, or every step of a
-            // lockstep handle: fixed by ipm_create, no environment switch reads it)
-            if (rem <= h->ss_small_blocks * NB) {
-                HIP_TRY(h, (launch_gemm_nt<32, 128, 32, 1, 8>(t, sm)));
-                HIP_TRY(h, (launch_gemm_nt<64, 64, 16, 2, 2>(u, sm)));
-                continue;
-            }
+        if (s.shape == CS_NARROW) {
+            HIP_TRY(h, (launch_gemm_nt<32, 128, 32, 1, 8>(t, sm)));
+            HIP_TRY(h, (launch_gemm_nt<64, 64, 16, 2, 2>(u, sm)));
+        } else if (s.shape == CS_WIDE) {
             HIP_TRY(h, (launch_gemm_nt<64, 128, 16, 2, 2>(t, sm)));
-            if (h->bulk_variant == 7) HIP_TRY(h, (launch_gemm_nt<128, 128, 16, 2, 2>(u, sm)));
-            else HIP_TRY(h, launch_chol_update(u, sm));
-            continue;
-        }
-        // one event per step on the main stream (after the critical panel rows): every extra record / wait
-        // costs the pivot chain ~6-12 us of command-processor time (profiles/, trace of a step)
-        GemmNT tc = t; tc.M = NB;                                   // critical panel rows: block row k+1
-        if (k >= 1) {     // the previous bulk update either signalled a counter (small grids) or recorded an event
-            if (bulk_wgs[k - 1] > 0) { tc.wait_on = h->d_bulk_done + (k - 1); tc.wait_count = bulk_wgs[k - 1]; tc.timeout = timeout_word(h); }
-            else HIP_TRY(h, hipStreamWaitEvent(sm, h->ev_bulk[k - 1], 0));
-        }
-        // bulk side: the (small) panel launch of the bulk stream polls the completion counter of the critical
-        // panel launch instead of a stream event, unless it is large enough to crowd the CUs while it spins
-        const int tb_wgs = (rem - NB) / 64;
-        // SAFETY: a polling launch holds LDS on every CU it lands on; potrf_diag needs a CU with 133 KB free and
-        // sits upstream of the signal, so a wide poller deadlocks the chain until its spin bound expires
-        // (observed at m = 16384 with 254 pollers).  Only launches that leave most CUs untouched may poll.
-        const bool crit_flag = fs && rem > NB && tb_wgs <= 64;
-        if (crit_flag) tc.signal = h->d_bulk_done + h->nblk + k;
-        // NOTE the panel solve is IN PLACE (C = P): a workgroup must own whole rows, i.e. BN == N == 128.  Tiles narrower
-        // than the panel (tried: 16 workgroups of 32 x 32) race -- one workgroup overwrites columns another still reads.
-        HIP_TRY(h, (launch_gemm_nt<32, 128, 32, 1, 8>(tc, sm)));     // 8 waves, BK=32: 4 stages
-        if (!crit_flag) HIP_TRY(h, hipEventRecord(h->ev_crit[k], sm));
-        // Two-level blocking (dense handles): the steps come in groups of `gs` block columns.  A step updates only the
-        // remaining columns of its group (a window of K = 128 tiles) and DEFERS the rest of its trailing update; the last
-        // step of the group applies all of them at once with K = 128 gs -- the group's panels are adjacent block columns
-        // of L, i.e. one k-contiguous operand -- so the trailing matrix, whose read-modify-write is what bounds a
-        // K = 128 update (16 flop/byte), is streamed once per group instead of once per step.
-        const int g0 = grp_lo[k], gend = grp_hi[k];                  // group = block columns [g0, gend)
-        const bool grouped = gend - g0 > 1;
-        const bool grp_inner = grouped && k + 1 < gend;             // not the last column of its group: window only
-        const bool grp_last = grouped && !grp_inner;
-        if (grp_last && k > g0) {                                   // operands: block columns g0..k, rows >= k+1
-            u.P = panel - (int64_t)(k - g0) * NB; u.Q = u.P; u.K = (k - g0 + 1) * NB;
-        }
-        GemmNT uc = u; uc.M = NB; uc.N = NB;                        // critical tile (k+1,k+1)
-        HIP_TRY(h, (launch_gemm_nt<32, 32, 32, 2, 2>(uc, sm)));      // 10 sub-tiles of 32x32
-        if (!crit_flag) HIP_TRY(h, hipStreamWaitEvent(sb, h->ev_crit[k], 0));
-        if (rem > NB) {
-            GemmNT tb = t; tb.C = panel + (int64_t)NB * h->mp; tb.P = tb.C; tb.M = rem - NB;
-            if (crit_flag) { tb.wait_on = h->d_bulk_done + h->nblk + k; tb.wait_count = NB / 32; tb.timeout = timeout_word(h); }   // workgroups of the critical panel launch
-            HIP_TRY(h, (launch_gemm_nt<64, 128, 16, 2, 2>(tb, sb)));
-            GemmNT ub = u;
-            const int nt = rem / NB;
-            if (grp_inner) {
-                // window: tiles (i, j), i >= k+2, k+1 <= j < gend:  B(i,j) -= L(i,k) L(j,k)^T as ONE rectangular GEMM.
-                // Inside the group it also touches a few tiles above the diagonal (i < j), which nobody reads.
-                const int wn = gend - (k + 1);
-                ub.P = panel + (int64_t)NB * h->mp; ub.Q = panel;
-                ub.C = h->B + (int64_t)(k + 2) * NB * h->mp + (int64_t)(k + 1) * NB;
-                ub.M = rem - NB; ub.N = std::min(wn * NB, rem); ub.lower = 0;
-                if (fs) { bulk_wgs[k] = (unsigned)((ub.M / NB) * (ub.N / NB)); ub.signal = h->d_bulk_done + k; ++h->n_counter_steps; }
-                else ++h->n_event_steps;
-                if (h->bulk_variant == 7) HIP_TRY(h, (launch_gemm_nt<128, 128, 16, 2, 2>(ub, sb)));
-                else HIP_TRY(h, launch_chol_update(ub, sb));
-                HIP_TRY(h, hipEventRecord(h->ev_bulk[k], sb));
-                continue;
+            HIP_TRY(h, launch_trailing_update(h, u, sm, 0));
+        } else {
+            // one event per step on the main stream (after the critical panel rows): every extra record / wait
+            // costs the pivot chain ~6-12 us of command-processor time (profiles/, trace of a step)
+            GemmNT tc = t; tc.M = NB;                               // critical panel rows: block row k+1
+            if (s.crit_wait == CH_COUNTER) { tc.wait_on = bulk_done + (k - 1); tc.wait_count = (unsigned)s.crit_count; tc.timeout = timeout_word(h); }
+            else if (s.crit_wait == CH_EVENT) HIP_TRY(h, hipStreamWaitEvent(sm, h->ev_bulk[k - 1], 0));
+            if (s.crit_flag) tc.signal = bulk_done + h->nblk + k;
+            // NOTE the panel solve is IN PLACE (C = P): a workgroup must own whole rows, i.e. BN == N == 128.  Tiles narrower
+            // than the panel (tried: 16 workgroups of 32 x 32) race -- one workgroup overwrites columns another still reads.
+            HIP_TRY(h, (launch_gemm_nt<32, 128, 32, 1, 8>(tc, sm)));     // 8 waves, BK=32: 4 stages
+            if (!s.crit_flag) HIP_TRY(h, hipEventRecord(h->ev_crit[k], sm));
+            GemmNT uc = u; uc.M = NB; uc.N = NB;                    // critical tile (k+1,k+1)
+            HIP_TRY(h, (launch_gemm_nt<32, 32, 32, 2, 2>(uc, sm)));      // 10 sub-tiles of 32x32
+            if (!s.crit_flag) HIP_TRY(h, hipStreamWaitEvent(sb, h->ev_crit[k], 0));
+            if (s.bulk != CH_NONE) {
+                GemmNT tb = t; tb.C = panel + (int64_t)NB * h->mp; tb.P = tb.C; tb.M = s.rem - NB;
+                if (s.crit_flag) { tb.wait_on = bulk_done + h->nblk + k; tb.wait_count = (unsigned)s.poll_count; tb.timeout = timeout_word(h); }
+                HIP_TRY(h, (launch_gemm_nt<64, 128, 16, 2, 2>(tb, sb)));
+                GemmNT ub = u;
+                if (s.window) {                                     // tiles (i, j), i >= k+2, k+1 <= j < k+1+window, as one rectangular GEMM
+                    ub.P = tb.C; ub.Q = panel;
+                    ub.C = h->B + (int64_t)(k + 2) * NB * h->mp + (int64_t)(k + 1) * NB;
+                    ub.M = s.rem - NB; ub.N = s.window * NB; ub.lower = 0;
+                }
+                if (s.bulk == CH_COUNTER) ub.signal = bulk_done + k;
+                HIP_TRY(h, launch_trailing_update(h, ub, sb, /*skip_first=*/s.window ? 0 : 1));
             }
-            const int ub_wgs = nt * (nt + 1) / 2 - 1;
-            // the per-workgroup release (L2 write-back) of the counter protocol only pays in the latency-bound
-            // regime; a throughput-bound update (thousands of tiles: 16k: 40 -> 50 ms) keeps the stream event
-            if (fs && ub_wgs <= 1024) {
-                bulk_wgs[k] = (unsigned)ub_wgs;
-                ub.signal = h->d_bulk_done + k;
-                ++h->n_counter_steps;
-            } else ++h->n_event_steps;
-            if (h->bulk_variant == 7) HIP_TRY(h, (launch_gemm_nt<128, 128, 16, 2, 2>(ub, sb, nullptr, 512, /*skip_first=*/1)));   // the generic kernel (rounds 1-2)
-            else HIP_TRY(h, launch_chol_update(ub, sb, /*skip_first=*/1));
         }
-        HIP_TRY(h, hipEventRecord(h->ev_bulk[k], sb));
+        if (s.bulk_event) HIP_TRY(h, hipEventRecord(h->ev_bulk[k], sb));
     }
-    if (la) HIP_TRY(h, hipStreamWaitEvent(sm, h->ev_bulk[h->nblk - 2], 0));
+    if (plan.lookahead) HIP_TRY(h, hipStreamWaitEvent(sm, h->ev_bulk[h->nblk - 2], 0));
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
@@ -455,7 +388,7 @@ static int enqueue_mehrotra_start(ipm_handle* h) {
     const unsigned gn = (unsigned)((h->n + 255) / 256);
     hipLaunchKernelGGL(fill_kernel, dim3(gn), dim3(256), 0, h->stream, h->d, (int)h->n, 1.0);
     if ((rc = enqueue_form(h, h->d))) return rc;
-    if ((rc = enqueue_factor(h, true))) return rc;
+    if ((rc = enqueue_factor(h))) return rc;
     if ((rc = enqueue_group_inverses(h))) return rc;
     const VecArgs va = vec_args(h);
     const dim3 g(h->vblk), b(VBLK);

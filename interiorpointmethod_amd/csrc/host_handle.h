@@ -6,7 +6,7 @@ static thread_local char g_err[512] = "";
 
 // Live handles per device.  The device-polled hand-offs of the Cholesky look-ahead are only safe while ONE handle
 // drives the GPU (its two streams then sit on hardware queues of their own); with more than one live handle on a
-// device every factorization uses stream events instead (enqueue_factor).  Counted at create / destroy.
+// device every factorization uses stream events instead (polls_device is an input of the step plan, chol_plan.h).  Counted at create / destroy.
 static const int MAX_DEVICES = 64;
 static std::atomic<int> g_live[MAX_DEVICES];
 static std::atomic<bool> g_attr_set[MAX_DEVICES];      // per-device function attributes (dynamic LDS of adat_sparse)
@@ -205,7 +205,8 @@ static inline int64_t round_up(int64_t v, int64_t q) { return (v + q - 1) / q * 
 // ------------------------------------------------------------------------------- scheduling rules, each stated once
 static inline int live_on_device(const ipm_handle* h) { return h->device < MAX_DEVICES ? g_live[h->device].load(std::memory_order_acquire) : 1; }
 static inline bool alone_on_device(const ipm_handle* h) { return live_on_device(h) <= 1; }      // device-polled hand-offs are allowed (see g_live)
-static inline bool lookahead_on(const ipm_handle* h) { return h->lookahead != 0 && h->nblk > 2 && h->stream2 != nullptr; }
+static inline bool lookahead_wanted(int lookahead, int nblk) { return lookahead != 0 && nblk > 2; }      // (ipm_create makes the bulk stream then)
+static inline bool lookahead_on(const ipm_handle* h) { return lookahead_wanted(h->lookahead, h->nblk) && h->stream2 != nullptr; }
 // wants_polling: the handle ASKS for device-polled hand-offs in the look-ahead; polls_device: a launch enqueued now gets them.
 // may_poll (host_iteration.h) decides about the roll-back snapshot with wants_polling, WITHOUT alone_on_device: the live-handle
 // count can change between the snapshot and the launch, so the snapshot rule is deliberately the conservative superset of the

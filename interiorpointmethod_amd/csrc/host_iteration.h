@@ -86,7 +86,7 @@ static int enqueue_iteration(ipm_handle* h, hipEvent_t* ev) {
         const int nG = h->grouped_trsv ? h->nblk / h->gsz : 0;
         const int gstep = (nG >= 2 && (nG - 1) * h->gsz - 1 < rstep) ? (nG - 1) * h->gsz - 1 : -1;
         if (fused) { if ((rc = enqueue_form_factor(h, ev, rstep, gstep))) return rc; }
-        else if ((rc = enqueue_factor(h, true, rstep, gstep))) return rc;
+        else if ((rc = enqueue_factor(h, rstep, gstep))) return rc;
         h->fdone = nullptr;
         if (gstep >= 0) {
             // the last group's inverse (nine dependent launches, ~80 us) goes to the residual stream as well: the forward
@@ -134,8 +134,8 @@ static int enqueue_iteration(ipm_handle* h, hipEvent_t* ev) {
             // substitution ride on the factorization (four walks of the elimination tree per iteration instead of five)
             launch_gemv_n(h, h->v, -1.0, -1.0, h->rb, h->t1);   // rhs = -r_b - A (d*t)
             have_rhs = true;
-            if ((rc = enqueue_factor(h, true, -1, -1, h->t1))) return rc;
-        } else if ((rc = enqueue_factor(h, true))) return rc;
+            if ((rc = enqueue_factor(h, -1, -1, h->t1))) return rc;
+        } else if ((rc = enqueue_factor(h))) return rc;
     }
     if ((rc = enqueue_group_inverses(h))) return rc;
     if (all) HIP_TRY(h, hipEventRecord(ev[3], h->stream));
@@ -243,7 +243,7 @@ extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, do
             hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, h->stream, h->sc, 1e-8, 1e-8, 1e-8, h->opt.eta, 1 << 30, 1, 0);
             if ((rc = enqueue_residuals(h))) return rc;
             if ((rc = enqueue_form(h, h->d))) return rc;
-            if ((rc = enqueue_factor(h, true))) return rc;
+            if ((rc = enqueue_factor(h))) return rc;
             if ((rc = enqueue_group_inverses(h))) return rc;
             if ((rc = enqueue_predictor(h, nullptr))) return rc;
             launch_mu_aff(h);                                   // alpha_aff for stats

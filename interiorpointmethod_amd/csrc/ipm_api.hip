@@ -34,6 +34,7 @@
 #include "form_factor.h"
 #include "lockstep.h"
 #include "lockstep_merge.h"
+#include "chol_plan.h"
 #include "equilibrate.h"
 
 #include <algorithm>
@@ -263,7 +264,7 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     CREATE_TRY(hipMemsetAsync(h->d_bulk_done, 0, sizeof(unsigned) * (2 * (size_t)h->nblk + 4), h->stream));
     if (h->opt.flags & IPM_FLAG_NO_DEVICE_POLLING) h->flag_sync = 0;
     if (h->potrf_stamps) { CREATE_TRY(dev_malloc(device, h->stream, (void**)&h->stamp_buf, 8 * 64 * sizeof(long long))); CREATE_TRY(hipMemsetAsync(h->stamp_buf, 0, 8 * 64 * sizeof(long long), h->stream)); }
-    if (h->lookahead != 0 && h->nblk > 2)                  // (a single-stream handle creates no second stream: see stream3 below)
+    if (lookahead_wanted(h->lookahead, h->nblk))           // (a single-stream handle creates no second stream: see stream3 below)
         CREATE_TRY(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
     CREATE_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     // The residual stream exists only where it is used (dense handles from 16 blocks on): the HIP runtime maps streams onto a
@@ -592,6 +593,18 @@ extern "C" int ipm_debug_at_pieces(int32_t nblk, int32_t layout[4], int32_t* pie
     return IPM_OK;
 }
 
+extern "C" int ipm_debug_chol_plan(int32_t nblk, int64_t m, const int32_t knobs[6], const int32_t* env_last, int32_t totals[5], int32_t* steps,
+                                   int32_t capacity) {
+    if (nblk < 1 || nblk > (1 << 13) || !knobs || !totals) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_debug_chol_plan: bad arguments");
+    static_assert(CHOL_STEP_WORDS == IPM_CHOL_STEP_WORDS && sizeof(CholStep) == sizeof(int32_t) * IPM_CHOL_STEP_WORDS, "plan record layout");
+    const int64_t mp = (int64_t)nblk * NB;
+    const bool la = lookahead_wanted(knobs[0], nblk);
+    const CholPlan p = chol_step_plan(nblk, m > 0 && m <= mp ? m : mp, mp, la, la && knobs[1] != 0, knobs[2], knobs[3], knobs[4], knobs[5] != 0, env_last);
+    totals[0] = p.lookahead; totals[1] = p.polling; totals[2] = p.gs; totals[3] = p.n_counter_steps; totals[4] = p.n_event_steps;
+    if (steps && capacity >= nblk) memcpy(steps, p.steps.data(), sizeof(CholStep) * (size_t)nblk);
+    return IPM_OK;
+}
+
 // ------------------------------------------------------------------------------- kernel-level entry points
 extern "C" int ipm_form_normal_matrix(ipm_handle* h, const double* d, double* B, int64_t ldb) {
     if (!h || !d || !B || ldb < h->m) return fail(h, IPM_ERR_INVALID_ARG, "ipm_form_normal_matrix: bad arguments");
@@ -627,7 +640,7 @@ extern "C" int ipm_normal_solve(ipm_handle* h, const double* d, const double* rh
                 hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->d, (int)h->n, 1.0);
             }
             if ((rc = enqueue_form(h, h->d))) return rc;
-            if ((rc = enqueue_factor(h, true))) return rc;
+            if ((rc = enqueue_factor(h))) return rc;
             if ((rc = enqueue_group_inverses(h))) return rc;
         }
         HIP_TRY(h, hipMemsetAsync(h->t1, 0, sizeof(double) * h->mp, h->stream));
