@@ -95,7 +95,8 @@ struct FFModel {                       // durations in microseconds, calibrated 
                                                // (profiles/r06_ff_item_trace_half_pairs.txt: 8.5 + 2.08 per stage; 2.1 beside f_over)
     double t_over = 7.0, t_col = 15.9;         // update item: fixed + per 128-column block of L applied
     double t_rmw = 1.0, t_panel = 18.3;        // reading the tile back (all but its first item); the product with inv(L_cc)
-    double t_base = 6.75;                      // adding ONE formation slab
+    double t_base = 2.3;                       // adding ONE formation slab, streamed (profiles/ff_item_trace_item_costs_parent_vs_this.txt;
+                                               // 6.75 with one exposed round trip per slab)
     double d_item = 130.0;                     // one FF_D item (diag(B) of 128 rows straight from A and d)
     double gap = 0.8, handoff = 1.0;           // end of an item -> next ticket; counter bump -> visible to a spinning consumer
     // The pivot chain = per step k: potrf_diag of block k (one workgroup), then the panel solve of tile (k+1,k) and the update of

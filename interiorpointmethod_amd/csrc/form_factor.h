@@ -25,7 +25,8 @@
 // fragment reads), double buffered, one barrier per stage.  HEAD (form_factor_roles_kernel_mfma_first, the launch that runs):
 // the stage loops of ff_gemm_pair and ff_gemm_pipe have no branch, and each stage opens with the MFMAs of the previous
 // stage's last k-step, and a pair with one tile above the diagonal or below the matrix runs on the live tile's four waves
-// alone (HALF); form_factor_roles_kernel keeps the previous schedule as the tests' bitwise reference.  DESIGN.md 4-F
+// alone (HALF), and an update item adds its tile's formation slabs as one stream of loads (FF_BASE_DEPTH);
+// form_factor_roles_kernel keeps the previous schedule as the tests' bitwise reference.  DESIGN.md 4-F
 // has the measurements and the rejected variants.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -81,6 +82,11 @@ __device__ __forceinline__ void ff_wait_ge(const unsigned* p, unsigned v, unsign
         for (unsigned w = 0; w < nw; ++w) snap[w] = handoff_load(live + w);
     });
 }
+
+// Rounds of the streamed base add that are in flight (HEAD): one round = one register group i of one slab = 4 loads of 16 bytes
+// = 8 VGPRs per lane.  1, 2 or 4; 4 is the 32 temporaries of the slab-at-a-time add, and the register report of the launch is the
+// same with it (2 measured the same 2.3 us per slab against 7.3 slab at a time: DESIGN.md 4-F).
+constexpr int FF_BASE_DEPTH = 4;
 
 // acc += P[128 x 32 ns] * (Q[128 x 32 ns] . w)^T  (both operands k-contiguous rows).  SRC_REGS: the P operand of stage s
 // comes from `src` (a 128 x 128 tile held in accumulator layout by the waves with wn == s) instead of memory.
@@ -657,6 +663,10 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles&
             for (int j = 0; j < 2; ++j) acc[i][j] = (f64x4){0.0, 0.0, 0.0, 0.0};
         const int j0 = it.t.j0, j1 = it.t.j1;
         const int flags = it.t.flags, seq = it.t.seq;
+        // HEAD: the tile's slab count is fetched HERE, by every lane: as a load in front of the streamed base add its wait
+        // would drain the old tile's loads before the first slab's are out
+        int qn_v = 0;
+        if (HEAD && (flags & FF_ADD_BASE)) qn_v = g.tile_q[tile];
         if (tid == 0) {
             if (flags & FF_ADD_BASE) ff_wait_ge(g.fcount + tile, (unsigned)g.tile_q[tile], g.timeout, g.dbg, n, HK_FCOUNT, g.dbg_words);
             if (!(flags & FF_INIT)) ff_wait_ge(g.tprog + tile, (unsigned)seq - 1u, g.timeout, g.dbg, n, HK_TPROG, g.dbg_words);
@@ -667,6 +677,7 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles&
             handoff_acquire();
         }
         __syncthreads();
+        const int qn_s = __builtin_amdgcn_readfirstlane(qn_v);      // (HEAD; wave-uniform: a scalar register across the update product)
         FF_PROF(FFP_TWAIT);
         FF_TRACE(1);
         if (j1 > j0)
@@ -688,7 +699,44 @@ __device__ __forceinline__ void form_factor_body(const FFArgs& g, const FFRoles&
 #pragma unroll
                     for (int q = 0; q < 4; ++q) val[i][j][q] = bt[(int64_t)(i * 16 + 4 * q) * g.ldb + j * 16];
         }
-        if (flags & FF_ADD_BASE) {
+        if constexpr (HEAD) {
+            // STREAMED: the adds run as rounds (slab c, register group i), FF_BASE_DEPTH of them in flight in a ring of as many
+            // 8-VGPR slots: a round is added as soon as IT has arrived (loads return in order: a partial vmcnt wait) and its slot
+            // is refilled at once with the round FF_BASE_DEPTH ahead, across the slab boundary.  The loads of the old tile above
+            // (straight into val, not waited for) head the same stream, so the whole base add exposes one memory latency instead
+            // of one per slab.  Every element still receives old, slab 0, slab 1, ... in this order: bit-identical.  The last
+            // slab is peeled: a branch around the refills would meet the stream with two different counts of loads in flight,
+            // and the wait behind it would have to assume the smaller one.
+            if (flags & FF_ADD_BASE) {
+                constexpr int D = FF_BASE_DEPTH;
+                static_assert(D == 1 || D == 2 || D == 4, "a ring slot serves the same register groups in every slab");
+                const int qn = qn_s;
+                // the lane's offset is made opaque HERE: every address of the stream then derives from one register pair computed
+                // in the item.  Left to itself the compiler keeps loop-invariant 64-bit lane bases (one per slab distance) across
+                // the whole item loop and spills them, and a reload in front of the stream (scratch loads count in vmcnt, in
+                // order) drains the old tile's loads
+                unsigned loff = (unsigned)((wm * 2 + (wn >> 1)) * 4096 + (wn & 1) * 512 + lane * 2);
+                asm volatile("" : "+v"(loff));
+                const double* sb = g.slab + ((size_t)tile * g.Q * (128 * 128) + loff);
+                f64x2 ring[D][4];
+                auto fill = [&](const double* s, int i) {
+#pragma unroll
+                    for (int jh = 0; jh < 4; ++jh) ring[i % D][jh] = *reinterpret_cast<const f64x2*>(s + (i * 8 + jh) * 128);
+                };
+                auto add = [&](int i) {
+#pragma unroll
+                    for (int jh = 0; jh < 4; ++jh) { val[i][jh >> 1][2 * (jh & 1)] += ring[i % D][jh].x; val[i][jh >> 1][2 * (jh & 1) + 1] += ring[i % D][jh].y; }
+                };
+#pragma unroll
+                for (int i = 0; i < D; ++i) fill(sb, i);
+                for (int c = 0; c + 1 < qn; ++c, sb += 128 * 128) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) { add(i); fill(sb + ((i + D) >> 2) * (128 * 128), (i + D) & 3); }
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { add(i); if (i + D < 4) fill(sb, i + D); }
+            }
+        } else if (flags & FF_ADD_BASE) {
             const int qn = g.tile_q[tile];
             // (a second register set that keeps slab c + 1 in flight while slab c is added was tried: the kernel then spills 483
             //  VGPRs -- the worker loop sits at the register limit)

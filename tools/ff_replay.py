@@ -28,7 +28,7 @@ class ModelRoles(Model):
     """the launch that runs (mode=1: the chain as roles of the one launch, 251 workers), calibrated on profiles/r04_ff_item_trace_roles_kernel.txt"""
     f_over, f_stage = 6.1, 4.02
     f_stage_half = 2.1                    # pair with one live tile (above the diagonal / below the matrix): half-live engine
-    t_over, t_col, t_base, t_panel, t_rmw = 7.0, 15.9, 27.0, 18.3, 1.0
+    t_over, t_col, t_base, t_panel, t_rmw = 7.0, 15.9, 9.2, 18.3, 1.0       # t_base: FOUR slabs, streamed (27.0 slab at a time)
     d_item = 397.0
     potrf, cpanel, cupdate = 36.8, 7.3, 7.3
     g_potrf_panel, g_panel_update, g_update_potrf = 1.0, 1.5, 1.0
