@@ -248,15 +248,15 @@ static int enqueue_factor(ipm_handle* h, int mid_step = -1, int ginv_step = -1, 
 // signal (optional): the launch is the signalling entry point and stores `value` to that progress word at its entry (SweepHook below)
 static void launch_dense_gemv_n(ipm_handle* h, const double* A, int64_t lda, int rows, int cols, const double* v, double sa,
                                 double sb, const double* add, double* out, unsigned* signal = nullptr, unsigned value = 0) {
-    if (signal) hipLaunchKernelGGL(gemv_n_signal_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, h->stream, A, lda, rows, cols, v, sa, sb, add, out, &h->sc->done, signal, value);
-    else launch_twin<LS_GEMV_N>(h, (unsigned)((rows + 3) / 4), {A, lda, rows, cols, v, sa, sb, add, out, &h->sc->done});
+    if (signal) hipLaunchKernelGGL(gemv_n_signal_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, h->stream, A, lda, rows, cols, v, sa, sb, add, out, solve_done(h), signal, value);
+    else launch_twin<LS_GEMV_N>(h, (unsigned)((rows + 3) / 4), {A, lda, rows, cols, v, sa, sb, add, out, solve_done(h)});
 }
 
 // Block-step substitution over the blocks [k0, nblk), one launch per block step: forward sweep L z = r, then the backward sweep
 // L^T out = z inside the envelope.  k0 = 0 is the whole solve; k0 > 0 the blocks behind the last full group (ragged groups).
 static void enqueue_block_steps(ipm_handle* h, int k0, double* r, double* z, double* out) {
     TrsvStep a;
-    a.L = h->B; a.ld = h->mp; a.inv = h->invD; a.done = &h->sc->done;
+    a.L = h->B; a.ld = h->mp; a.inv = h->invD; a.done = solve_done(h);
     a.r = r; a.z = z; a.j0 = 0;
     for (int k = k0; k < h->nblk; ++k) {
         a.k = k;
@@ -314,7 +314,7 @@ static int enqueue_potrs_grouped(ipm_handle* h, double* r, double* out, hipEvent
     const int GS = h->gsz;
     const int GR = GS * 128;
     const int nG = h->nblk / GS;
-    const int* done = &h->sc->done;
+    const int* done = solve_done(h);
     double* z = h->t2;
     for (int g = 0; g < nG; ++g) {                                        // forward: L z = r
         if (wait_last && g == nG - 1) HIP_TRY(h, hipStreamWaitEvent(h->stream, wait_last, 0));
@@ -361,12 +361,14 @@ static int enqueue_potrs(ipm_handle* h, double* r, double* out, hipEvent_t wait_
         const bool fwd_done = h->sp_fwd_fused != nullptr && h->sp_fwd_fused == r;       // the factorization carried L z = r already (z in t2)
         h->sp_fwd_fused = nullptr;
         const bool by_level = sp_level(h);                  // (evaluated once for both sweeps)
+        SpFactor F = h->spF;                                // the sweeps test the word of whoever asks for the solve (solve_done)
+        F.done = solve_done(h);
         if (!fwd_done) sp_walk(h, by_level, /*leaves_first=*/true, [&](unsigned grid, const SpRec* recs, int count) {
-            hipLaunchKernelGGL((sp_fwd_kernel<SPC_THREADS>), dim3(grid), dim3(SPC_THREADS), h->sp_lds_solve, h->stream, h->spF, ep, r, h->t2, rm, recs, count);
+            hipLaunchKernelGGL((sp_fwd_kernel<SPC_THREADS>), dim3(grid), dim3(SPC_THREADS), h->sp_lds_solve, h->stream, F, ep, r, h->t2, rm, recs, count);
         });
         if (!by_level) ep = ++h->sp_epoch;                   // the level-mode sweeps share one epoch, task mode takes one per sweep
         sp_walk(h, by_level, /*leaves_first=*/false, [&](unsigned grid, const SpRec* recs, int count) {
-            hipLaunchKernelGGL((sp_bwd_kernel<SPC_THREADS>), dim3(grid), dim3(SPC_THREADS), 0, h->stream, h->spF, ep, h->t2, out, recs, count);
+            hipLaunchKernelGGL((sp_bwd_kernel<SPC_THREADS>), dim3(grid), dim3(SPC_THREADS), 0, h->stream, F, ep, h->t2, out, recs, count);
         });
         HIP_TRY(h, hipGetLastError());
         return IPM_OK;

@@ -135,6 +135,13 @@ struct ipm_handle {
     bool bnd = false;                     // a finite bound is set: the bounded kernel instantiations run
     int bnd_nU = 0;                       // |U|
     double* bnd_mem = nullptr;            // u | w | z | dwa | dza | dw | dz | qz | roll-back w | roll-back z
+    // centrality correctors (ipm_set_centrality_correctors): up to mcc_k rounds per iteration re-use its factor.
+    // mcc_mem: the candidate vectors, own allocation made on first use (mcc_ensure).  sdone: while the launches of a round are
+    // enqueued, the word its products with A and its substitutions test in place of Scalars::done (solve_done)
+    int mcc_k = 0;
+    double* mcc_mem = nullptr;            // q v dx ds r3 r3g | qz dw dz r4 r4g (n-vectors) | dy (m-vector) | partial minima [2][MAXPART] | MccCtl | its roll-back copy
+    MccCtl mcc_host = MccCtl{};           // host copy of the rounds' record, read back with the scalar record (read_scalars)
+    const int* sdone = nullptr;
     // infeasibility detection (IPM_FLAG_DETECT_INFEASIBILITY): the Detect kernel instantiations run
     bool detect = false;
     double det_eps_p = 1e-8, det_eps_d = 1e-8;   // ipm_set_infeasibility_tol
@@ -215,6 +222,7 @@ static inline bool wants_polling(const ipm_handle* h) { return lookahead_on(h) &
 static inline bool polls_device(const ipm_handle* h) { return wants_polling(h) && alone_on_device(h); }
 static inline unsigned* timeout_word(const ipm_handle* h) { return h->d_flags + 2 * (size_t)h->nblk; }      // time-out word of the device-side hand-offs
 static inline unsigned* at_progress_word(const ipm_handle* h) { return timeout_word(h) + 1; }               // progress word of the streamed A^T dy (d_flags has four spare words)
+static inline const int* solve_done(const ipm_handle* h) { return h->sdone ? h->sdone : &h->sc->done; }       // `done` word the products with A and the substitutions test
 static inline const int* factor_done(const ipm_handle* h) { return h->fdone ? h->fdone : &h->sc->done; }    // `done` word formation / factorization test
 
 // Device memory the handle owns besides its workspace.  STREAM-ORDERED (hipMallocAsync / hipFreeAsync on the handle's
@@ -379,6 +387,35 @@ static BndArgs bnd_args(ipm_handle* h) {
     b.u = p; b.w = p + np; b.z = p + 2 * np; b.dwa = p + 3 * np; b.dza = p + 4 * np; b.dw = p + 5 * np; b.dz = p + 6 * np;
     b.qz = p + 7 * np; b.nU = h->bnd_nU;
     return b;
+}
+
+// centrality correctors: views into mcc_mem.  mcc_vec_args / mcc_bnd_args are the handle's views with the candidate's arrays in place.
+static const int MCC_NVECS = 11;
+static const int MCC_CTL_DOUBLES = 8;   // room of one MccCtl
+static_assert(sizeof(MccCtl) <= sizeof(double) * MCC_CTL_DOUBLES, "MccCtl outgrew its slot");
+static size_t mcc_doubles(const ipm_handle* h) { return (size_t)MCC_NVECS * h->np + (size_t)h->mp + 2 * MAXPART + 2 * MCC_CTL_DOUBLES; }
+static MccCtl* mcc_ctl(const ipm_handle* h) { return (MccCtl*)(h->mcc_mem + (size_t)MCC_NVECS * h->np + (size_t)h->mp + 2 * MAXPART); }
+static VecArgs mcc_vec_args(ipm_handle* h) {
+    const size_t np = (size_t)h->np;
+    double* p = h->mcc_mem;
+    VecArgs c = vec_args(h);
+    c.q = p; c.v = p + np; c.dx = p + 2 * np; c.ds = p + 3 * np; c.dy = p + MCC_NVECS * np;
+    return c;
+}
+static BndArgs mcc_bnd_args(ipm_handle* h) {
+    const size_t np = (size_t)h->np;
+    double* p = h->mcc_mem;
+    BndArgs b = bnd_args(h);
+    b.qz = p + 6 * np; b.dw = p + 7 * np; b.dz = p + 8 * np;
+    return b;
+}
+static MccArgs mcc_args(ipm_handle* h, int first) {
+    const size_t np = (size_t)h->np;
+    double* p = h->mcc_mem;
+    MccArgs g;
+    g.r3 = p + 4 * np; g.r3g = p + 5 * np; g.r4 = p + 9 * np; g.r4g = p + 10 * np;
+    g.part = p + MCC_NVECS * np + (size_t)h->mp; g.ctl = mcc_ctl(h); g.first = first;
+    return g;
 }
 
 static DetArgs det_args(const ipm_handle* h) { return DetArgs{h->det_eps_p, h->det_eps_d, h->det}; }

@@ -57,6 +57,63 @@ static int enqueue_corrector(ipm_handle* h, hipEvent_t* ev) {
     return enqueue_solve_direction(h, ev, h->dy, 1);
 }
 
+// Centrality correctors: up to mcc_k rounds between the corrector and the update, each the corrector's pipeline
+// again with this iteration's factor -- target / right-hand side, rhs = -r_b - A v_g, dy_g = B^{-1} rhs, A^T dy_g, the candidate
+// direction, the accept decision.  Nothing is enqueued with mcc_k = 0.  The products with A and the substitutions test
+// MccCtl::rdone (solve_done), which the round's target kernel sets: after a rejected round the later rounds of the iteration are
+// launches that return at entry.  t1 / t2 are free here (the corrector's solve consumed them) and the candidate vectors are mcc_mem.
+// A^T dy_g is the UNSTREAMED pass on the main stream (streaming it behind the sweep is left out): it overwrites h->atp, whose last
+// reader of the Mehrotra corrector (direction_kernel) lies in front of it on this stream.  The next writer of h->atp is the next
+// iteration's A^T y on the residual stream; it waits for ev_mid (enqueue_residual_stream) or, on the fused path, ev_fork
+// (enqueue_form_factor), both recorded on the MAIN stream inside that iteration's factorization -- behind launch_update and so
+// behind every round's mcc_direction_kernel, the last reader of h->atp, in stream order.
+static int mcc_ensure(ipm_handle* h) {
+    if (h->mcc_mem) return IPM_OK;
+    const size_t bytes = sizeof(double) * mcc_doubles(h);
+    if (dev_malloc(h->device, h->stream, (void**)&h->mcc_mem, bytes) != hipSuccess)
+        return fail(h, IPM_ERR_HIP, "centrality correctors: %lld doubles could not be allocated", (long long)mcc_doubles(h));
+    HIP_TRY(h, hipMemsetAsync(h->mcc_mem, 0, bytes, h->stream));      // (the padding of v_g is read by the product with A: zeros)
+    return IPM_OK;
+}
+// start of a solve / of an iterate sequence whose iteration count restarts: the tallies restart with it (a handle that never ran a
+// round has no record and nothing is enqueued).  With K > 0 the record is made here, in front of the roll-back snapshot.
+// With K = 0 nothing is enqueued here, in read_scalars or in enqueue_snapshot, also on a handle that ran rounds before (mcc_on):
+// where the count restarts, the host copy of the tallies is cleared on the host.
+static bool mcc_on(const ipm_handle* h) { return h->mcc_k > 0 && h->mcc_mem != nullptr; }
+static int mcc_start(ipm_handle* h, bool reset) {
+    if (h->mcc_k <= 0) { if (reset) h->mcc_host = MccCtl{}; return IPM_OK; }
+    int rc = mcc_ensure(h);
+    if (rc) return rc;
+    if (reset) HIP_TRY(h, hipMemsetAsync(mcc_ctl(h), 0, sizeof(MccCtl), h->stream));
+    return IPM_OK;
+}
+// A handle that went onto the fused small path AFTER K > 0 was set (ipm_set_A_csc decides the path): its loop runs in one workgroup
+// and has no rounds, so the solve entries refuse instead of dropping the option.
+static int mcc_check_path(ipm_handle* h, const char* who) {
+    if (h->small && h->mcc_k > 0)
+        return fail(h, IPM_ERR_INVALID_ARG, "%s: %d centrality correctors are set but the handle runs the fused small-LP kernel, which has no rounds (ipm_set_centrality_correctors(h, 0))", who, h->mcc_k);
+    return IPM_OK;
+}
+static int enqueue_corrector_rounds(ipm_handle* h) {
+    if (h->mcc_k <= 0) return IPM_OK;
+    int rc = mcc_ensure(h);
+    if (rc) return rc;
+    struct Word { ipm_handle* h; ~Word() { h->sdone = nullptr; } } word{h};
+    const VecArgs c = mcc_vec_args(h);
+    for (int r = 0; r < h->mcc_k; ++r) {
+        launch_mcc_target(h, r == 0);
+        h->sdone = &mcc_ctl(h)->rdone;
+        launch_gemv_n(h, c.v, -1.0, -1.0, h->rb, h->t1);
+        if ((rc = enqueue_potrs(h, h->t1, c.dy))) return rc;
+        launch_gemv_t(h, c.dy);
+        h->sdone = nullptr;
+        launch_mcc_direction(h);
+        launch_mcc_accept(h);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return IPM_OK;
+}
+
 // events per profiled iteration: 0 start, 1 before form, 2 after form, 3 after factor,
 // 4/5 around predictor solve, 6/7 around corrector solve, 8 end
 static const int EV_PER_IT = 9;
@@ -113,6 +170,7 @@ static int enqueue_iteration(ipm_handle* h, hipEvent_t* ev) {
             if ((rc = enqueue_predictor(h, nullptr, /*have_rhs=*/true))) return rc;
         }
         if ((rc = enqueue_corrector(h, nullptr))) return rc;
+        if ((rc = enqueue_corrector_rounds(h))) return rc;
         launch_update(h);
         HIP_TRY(h, hipGetLastError());
         return IPM_OK;
@@ -141,6 +199,7 @@ static int enqueue_iteration(ipm_handle* h, hipEvent_t* ev) {
     if (all) HIP_TRY(h, hipEventRecord(ev[3], h->stream));
     if ((rc = enqueue_predictor(h, all ? ev + 4 : nullptr, have_rhs))) return rc;
     if ((rc = enqueue_corrector(h, all ? ev + 6 : nullptr))) return rc;
+    if ((rc = enqueue_corrector_rounds(h))) return rc;         // (profiling: their time is part of phase 3, "other")
     launch_update(h);
     HIP_TRY(h, hipGetLastError());
     if (all) HIP_TRY(h, hipEventRecord(ev[8], h->stream));
@@ -154,6 +213,7 @@ static int read_scalars(ipm_handle* h, bool* timed_out = nullptr) {
     unsigned* word = timeout_word(h);
     HIP_TRY(h, hipMemcpyAsync(h->h_sc, h->sc, sizeof(Scalars), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(&tmo, word, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    if (mcc_on(h)) HIP_TRY(h, hipMemcpyAsync(&h->mcc_host, mcc_ctl(h), sizeof(MccCtl), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (tmo) {
         if (h->stream2) HIP_TRY(h, hipStreamSynchronize(h->stream2));               // the bulk stream may still be draining
@@ -208,6 +268,11 @@ static int enqueue_snapshot(ipm_handle* h, int restore, hipStream_t st = nullptr
         const BndArgs b = bnd_args(h);
         double* sw = h->bnd_mem + 8 * (size_t)h->np;
         hipLaunchKernelGGL(snapshot_bounds_kernel, dim3(grid), dim3(256), 0, st ? st : h->stream, b.w, b.z, sw, sw + h->np, (int)h->np, restore);
+    }
+    if (mcc_on(h)) {                                           // the record of the corrector rounds (its tallies) <-> the copy behind it
+        MccCtl* c = mcc_ctl(h);
+        MccCtl* s = (MccCtl*)((double*)c + MCC_CTL_DOUBLES);
+        HIP_TRY(h, hipMemcpyAsync(restore ? c : s, restore ? s : c, sizeof(MccCtl), hipMemcpyDeviceToDevice, st ? st : h->stream));
     }
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
@@ -271,6 +336,23 @@ extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, do
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     eq_out(h, dx, h->eq_c, false); eq_out(h, dy, h->eq_r, false); eq_out(h, ds, h->eq_c, true);      // scaled handle: C dx', R dy', ds' / C
     fill_stats(h, stats, 0.0);
+    return IPM_OK;
+}
+
+// ------------------------------------------------------------------------------- centrality correctors
+extern "C" int ipm_set_centrality_correctors(ipm_handle* h, int32_t k) {
+    // (the range check reads nothing of the handle, so it comes first: both argument checks hold without a device, for any h)
+    if (k < 0 || k > IPM_MAX_CORRECTORS) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_centrality_correctors: k = %d outside 0 .. %d", (int)k, IPM_MAX_CORRECTORS);
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_centrality_correctors: NULL handle");
+    if (h->small) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_centrality_correctors: the handle runs the fused small-LP kernel (one workgroup holds the whole loop; factor and solve cost the same there)");
+    if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_centrality_correctors: the handle was created with IPM_FLAG_LOCKSTEP (the rounds have no batched twins)");
+    h->mcc_k = k;
+    return IPM_OK;
+}
+extern "C" int ipm_get_corrector_info(ipm_handle* h, int64_t out[4]) {
+    if (!h || !out) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_corrector_info: bad arguments");
+    const MccCtl& c = h->mcc_host;                              // the host copy the last ipm_solve / ipm_iterate read back
+    out[0] = h->mcc_k; out[1] = c.run; out[2] = c.acc; out[3] = c.iters;
     return IPM_OK;
 }
 
@@ -360,6 +442,7 @@ extern "C" int ipm_iterate(ipm_handle* h, int32_t n_steps, ipm_stats* stats) {
     int rc = check_ready(h, "ipm_iterate");
     if (rc) return rc;
     if (n_steps < 0) return fail(h, IPM_ERR_INVALID_ARG, "n_steps < 0");
+    if ((rc = mcc_check_path(h, "ipm_iterate"))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     h->predictor_valid = false;
     std::vector<hipEvent_t> evs;
@@ -387,6 +470,7 @@ extern "C" int ipm_iterate(ipm_handle* h, int32_t n_steps, ipm_stats* stats) {
     for (int attempt = 0;; ++attempt) {
         hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, h->stream, h->sc, 1e-8, 1e-8, 1e-8, h->opt.eta, 1 << 30, 1,
                            attempt == 0 ? reset_k : 0);
+        if ((rc = mcc_start(h, attempt == 0 && reset_k))) return rc;
         const bool guard_poll = may_poll(h) && n_steps > 0;
         if (guard_poll && (rc = enqueue_snapshot(h, 0))) return rc;
         HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
@@ -430,10 +514,12 @@ extern "C" int ipm_solve(ipm_handle* h, double tol_p, double tol_d, double tol_g
     int rc = check_ready(h, "ipm_solve");
     if (rc) return rc;
     if (max_iter < 0) return fail(h, IPM_ERR_INVALID_ARG, "max_iter < 0");
+    if ((rc = mcc_check_path(h, "ipm_solve"))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     h->predictor_valid = false; h->fresh_state = false;
     if (h->auto_reg) { h->auto_reg = 0; h->shift_rel = h->opt.regularize; }      // decided per solve
     hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, h->stream, h->sc, tol_p, tol_d, tol_gap, h->opt.eta, max_iter, 0, 1);
+    if ((rc = mcc_start(h, true))) return rc;
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     const int chunk = h->opt.check_every;
     const bool may_auto = h->opt.regularize == 0.0 && !(h->opt.flags & IPM_FLAG_NO_AUTO_REGULARIZE);

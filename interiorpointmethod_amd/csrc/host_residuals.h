@@ -3,12 +3,12 @@
 #pragma once
 static void launch_gemv_n(ipm_handle* h, const double* v, double sa, double sb, const double* add, double* out,
                           hipStream_t st = nullptr) {
-    if (h->sparse) launch_twin<LS_SPMV_CSR>(h, (unsigned)((h->mp + 15) / 16), {sparse_view(h), (int)h->mp, v, sa, sb, add, out, &h->sc->done}, st);
-    else launch_untwinned(h, gemv_n_kernel, dim3((unsigned)(h->mp / 4)), dim3(256), st, h->A, h->np, (int)h->mp, (int)h->np, v, sa, sb, add, out, &h->sc->done);
+    if (h->sparse) launch_twin<LS_SPMV_CSR>(h, (unsigned)((h->mp + 15) / 16), {sparse_view(h), (int)h->mp, v, sa, sb, add, out, solve_done(h)}, st);
+    else launch_untwinned(h, gemv_n_kernel, dim3((unsigned)(h->mp / 4)), dim3(256), st, h->A, h->np, (int)h->mp, (int)h->np, v, sa, sb, add, out, solve_done(h));
 }
 static void launch_gemv_t(ipm_handle* h, const double* u, hipStream_t st = nullptr) {
-    if (h->sparse) launch_twin<LS_SPMV_CSC_T>(h, (unsigned)((h->np + 15) / 16), {sparse_view(h), (int)h->np, u, h->atp, &h->sc->done}, st);
-    else launch_untwinned(h, gemv_t_kernel, dim3((unsigned)((h->np + 511) / 512), (unsigned)h->rc_chunks), dim3(256), st, h->A, h->np, h->rows_per_chunk, (int)h->np, u, h->atp, &h->sc->done);
+    if (h->sparse) launch_twin<LS_SPMV_CSC_T>(h, (unsigned)((h->np + 15) / 16), {sparse_view(h), (int)h->np, u, h->atp, solve_done(h)}, st);
+    else launch_untwinned(h, gemv_t_kernel, dim3((unsigned)((h->np + 511) / 512), (unsigned)h->rc_chunks), dim3(256), st, h->A, h->np, h->rows_per_chunk, (int)h->np, u, h->atp, solve_done(h));
 }
 // The same pass (dense A) over the row chunks [chunk0, chunk1) only: gemv_t_kernel on the sub-range of A, u and the partials, so it
 // writes exactly the partials the full launch writes for those chunks -- each chunk is one workgroup row's own sum, in the same
@@ -44,6 +44,20 @@ static void launch_scaling(ipm_handle* h) {      // (residual-stream iteration o
 static void launch_direction(ipm_handle* h, int corr) {
     if (h->bnd) launch_untwinned(h, direction_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), corr, bnd_args(h));
     else launch_twin<LS_DIRECTION>(h, (unsigned)h->vblk, {vec_args(h), corr});
+}
+// The three vector kernels of a centrality-corrector round (vector_ops.h: mcc_*).  No lockstep twins: ipm_set_centrality_correctors
+// refuses a lockstep handle, and a program recorded with rounds pending would be cut like any other untwinned launch.
+static void launch_mcc_target(ipm_handle* h, int first) {
+    if (h->bnd) launch_untwinned(h, mcc_target_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, first), bnd_args(h), mcc_bnd_args(h));
+    else launch_untwinned(h, mcc_target_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, first));
+}
+static void launch_mcc_direction(ipm_handle* h) {
+    if (h->bnd) launch_untwinned(h, mcc_direction_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, mcc_vec_args(h), mcc_args(h, 0), mcc_bnd_args(h));
+    else launch_untwinned(h, mcc_direction_kernel, dim3(h->vblk), dim3(VBLK), nullptr, mcc_vec_args(h), mcc_args(h, 0));
+}
+static void launch_mcc_accept(ipm_handle* h) {
+    if (h->bnd) launch_untwinned(h, mcc_accept_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, 0), bnd_args(h), mcc_bnd_args(h));
+    else launch_untwinned(h, mcc_accept_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, 0));
 }
 static void launch_mu_aff(ipm_handle* h) { launch_vec_step<LS_MU_AFF>(h, mu_aff_bounded_kernel); }
 static void launch_corrector_rhs(ipm_handle* h) { launch_vec_step<LS_CORR_RHS>(h, corrector_rhs_bounded_kernel); }

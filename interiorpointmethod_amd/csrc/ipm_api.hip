@@ -322,7 +322,7 @@ extern "C" int ipm_destroy(ipm_handle* h) {
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->h_sc) { std::lock_guard<std::mutex> lock(g_hsc_mutex); g_hsc_pool.push_back(h->h_sc); h->h_sc = nullptr; }
-    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
+    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->mcc_mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
         dev_free(h->device, h->stream, p);
     ff_release(h);
     free_sparse_factor(h);

@@ -141,23 +141,81 @@ __device__ __forceinline__ Centring centring(double sum, double mu, int n, const
 
 // corrector column, sm = sigma mu: r3c = x s + dxa dsa - sm ; q = r3c/x ; v = d (r_c - q)             main.py:150-152
 // Bounded, on U: r4c = w z + dwa dza - sm ; qz = r4c/w ; v = theta (r_c - q + (r4c - z r_u)/w)
+// Two steps, so that a centrality corrector (below) re-enters at the second with its own complementarity terms: the terms, then
+// q, qz, v from them into the arrays `a`, `bd` name.
+template <class Cols>
+__device__ __forceinline__ double corrector_r3(const Cols& a, int j, double xj, double sm) { return xj * a.s[j] + a.dxa[j] * a.dsa[j] - sm; }
+__device__ __forceinline__ double corrector_r4(const BndArgs& bd, int j, double wj, double zj, double sm) { return wj * zj + bd.dwa[j] * bd.dza[j] - sm; }
+template <class Cols>
+__device__ __forceinline__ void corrector_rhs_plain(const Cols& a, int j, double qj) { a.v[j] = a.d[j] * (a.rc[j] - qj); }
+template <class Cols>
+__device__ __forceinline__ void corrector_rhs_bounded(const Cols& a, const BndArgs& bd, int j, double xj, double wj, double zj, double uj, double qj, double r4c) {
+    bd.qz[j] = r4c / wj;
+    a.v[j] = a.d[j] * (a.rc[j] - qj + (r4c - zj * (xj + wj - uj)) / wj);
+}
 template <bool Bounded, class Cols>
 __device__ __forceinline__ void corrector_column(const Cols& a, const BndArgs& bd, int j, double sm) {
     const double xj = a.x[j];
-    const double r3c = xj * a.s[j] + a.dxa[j] * a.dsa[j] - sm;
+    const double r3c = corrector_r3(a, j, xj, sm);
     const double qj = r3c / xj;
     a.q[j] = qj;
     if constexpr (Bounded) {
         const double uj = bd.u[j];
         if (bnd_in(uj)) {
             const double wj = bd.w[j], zj = bd.z[j];
-            const double r4c = wj * zj + bd.dwa[j] * bd.dza[j] - sm;
-            bd.qz[j] = r4c / wj;
-            a.v[j] = a.d[j] * (a.rc[j] - qj + (r4c - zj * (xj + wj - uj)) / wj);
+            corrector_rhs_bounded(a, bd, j, xj, wj, zj, uj, qj, corrector_r4(bd, j, wj, zj, sm));
             return;
         }
     }
-    a.v[j] = a.d[j] * (a.rc[j] - qj);
+    corrector_rhs_plain(a, j, qj);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Gondzio's multiple centrality correctors (Comput. Optim. Appl. 6 (1996) 137-156): after Mehrotra's corrector the
+// factor is used again for up to K rounds.  A round aims the complementarity products of a trial point a little beyond the step
+// just found back into the box [beta_min, beta_max] sigma mu, solves for the direction with that target and keeps it when the
+// step lengths grow by gamma delta in sum.
+// The device-resident record of the rounds (the library's own allocation, beside the candidate vectors; the scalar record of the
+// solve is not touched).  ap, ad: the step lengths of the direction a round starts from, left by its target kernel for its accept
+// kernel.  rdone: the word the kernels of a round test in place of Scalars::done (done, or the chain of this iteration is dead: a
+// round was rejected); rdead: a round of this iteration was rejected.  Tallies of the solve (ipm_get_corrector_info): rounds that
+// did work, rounds accepted, iterations with an accepted round; hit: this iteration has one.
+struct MccCtl {
+    double ap, ad;
+    int rdone, rdead, run, acc, iters, hit;
+};
+constexpr double MCC_DELTA = 0.1, MCC_GAMMA = 0.1, MCC_BETA_MIN = 0.1, MCC_BETA_MAX = 10.0;
+__device__ __forceinline__ double mcc_trial_step(double alpha) { return fmin(1.0, alpha + MCC_DELTA); }
+// the correction t of one complementarity product v = (x + a~_p dx)(s + a~_d ds): the projection onto the box minus v, bounded below
+__device__ __forceinline__ double mcc_target(double v, double sm) {
+    const double t = fmin(fmax(v, MCC_BETA_MIN * sm), MCC_BETA_MAX * sm) - v;
+    return fmax(t, -MCC_BETA_MAX * sm);
+}
+// the candidate replaces the direction iff its step lengths gained gamma delta in sum; a NaN on either side rejects
+__device__ __forceinline__ bool mcc_accept(double ap, double ad, double ahp, double ahd) { return ahp + ahd >= ap + ad + MCC_GAMMA * MCC_DELTA; }
+// Column j of a round's right-hand side.  r3c (Bounded, on U: r4c): the complementarity terms of the direction the round starts from.
+// `a`, `bd` name the current direction (dx, ds, dw, dz); `c`, `cb` are the same views with the CANDIDATE's q, v (qz) in place, which
+// corrector_column's second step fills.  r3g (r4g) receive the candidate's terms r3c - t (r4c - t4; 0 outside U).
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void mcc_rhs_column(const Cols& a, const BndArgs& bd, const Cols& c, const BndArgs& cb, int j, double tp, double td,
+                                               double sm, double r3c, double r4c, double* r3g, double* r4g) {
+    const double xj = a.x[j];
+    const double r3 = r3c - mcc_target((xj + tp * a.dx[j]) * (a.s[j] + td * a.ds[j]), sm);
+    const double qj = r3 / xj;
+    r3g[j] = r3;
+    c.q[j] = qj;
+    if constexpr (Bounded) {
+        const double uj = bd.u[j];
+        if (bnd_in(uj)) {
+            const double wj = bd.w[j], zj = bd.z[j];
+            const double r4 = r4c - mcc_target((wj + tp * bd.dw[j]) * (zj + td * bd.dz[j]), sm);
+            r4g[j] = r4;
+            corrector_rhs_bounded(c, cb, j, xj, wj, zj, uj, qj, r4);
+            return;
+        }
+        r4g[j] = 0.0;
+    }
+    corrector_rhs_plain(c, j, qj);
 }
 
 // damped step from the reduced ratio-test minimum (main.py:604-626) and the column update x += a_p dx ; s += a_d ds

@@ -387,6 +387,108 @@ __global__ __launch_bounds__(VBLK) void update_kernel(VecArgs a) { update_kernel
 __global__ __launch_bounds__(VBLK) void update_bounded_kernel(VecArgs a, BndArgs bd) { update_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 
 // ---------------------------------------------------------------------------------------
+// Centrality correctors (iteration_rules.h: mcc_*): the three vector kernels of one round, enqueued K times between
+// the corrector's direction_kernel and update_kernel (host_iteration.h), never with K = 0.  Between the first two run the
+// products with A and the solve with this iteration's factor, which test MccCtl::rdone in place of Scalars::done.
+// `a`, `bd` are the handle's views; `c`, `cb` the same views with the candidate's q, v, dx, ds, dy (qz, dw, dz) in place.
+// ---------------------------------------------------------------------------------------
+struct MccArgs {
+    double *r3, *r3g, *r4, *r4g;   // complementarity terms of the current direction (valid once a round was accepted) and of the candidate
+    double* part;                  // [2][MAXPART]: the candidate's partial ratio-test minima (primal, dual)
+    MccCtl* ctl;                   // the record of the rounds
+    int first;                     // the iteration's first round
+};
+
+// target / right-hand side: alpha from the re-reduced minima as update_kernel takes it, the trial point, mcc_rhs_column.
+// One thread opens the round: rdone for the kernels behind this one (they are whole launches later, so the word is never read in
+// the launch that writes it; this kernel's own blocks decide from `done` and rdead, which earlier launches wrote), the step
+// lengths for accept_kernel, the tally.  The first round revives the chain (rdead = 0) and so never reads rdead.
+template <bool Bounded = false>
+__device__ __forceinline__ void mcc_target_kernel_body(VecArgs a, VecArgs c, MccArgs g, BndArgs bd = BndArgs{}, BndArgs cb = BndArgs{}) {
+    Scalars* sc = a.sc;
+    MccCtl* ctl = g.ctl;
+    const bool off = sc->done || (!g.first && ctl->rdead);
+    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+    if (lead) {
+        ctl->rdone = off ? 1 : 0;
+        if (g.first) { ctl->rdead = 0; ctl->hit = 0; }
+    }
+    if (off) return;
+    const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
+    const double eta = sc->eta;
+    const double ap = damped_step(eta, min_partials(a.part, P_MINP, a.nblk));
+    const double ad = damped_step(eta, min_partials(a.part, P_MIND, a.nblk));
+    const double tp = mcc_trial_step(ap), td = mcc_trial_step(ad);
+    const double sm = sc->sigma * sc->mu;                          // as corrector_rhs_kernel formed it
+    for (int j = gid; j < a.n; j += gsz) {
+        double r3c, r4c = 0.0;
+        if (g.first) {                                             // Mehrotra's terms, as corrector_column computed them
+            r3c = corrector_r3(a, j, a.x[j], sm);
+            if constexpr (Bounded) { if (bnd_in(bd.u[j])) r4c = corrector_r4(bd, j, bd.w[j], bd.z[j], sm); }
+        } else {
+            r3c = g.r3[j];
+            if constexpr (Bounded) r4c = g.r4[j];
+        }
+        mcc_rhs_column<Bounded>(a, bd, c, cb, j, tp, td, sm, r3c, r4c, g.r3g, g.r4g);
+    }
+    if (lead) { ctl->ap = ap; ctl->ad = ad; ctl->run += 1; }
+}
+__global__ __launch_bounds__(VBLK) void mcc_target_kernel(VecArgs a, VecArgs c, MccArgs g) { mcc_target_kernel_body(a, c, g); }
+__global__ __launch_bounds__(VBLK) void mcc_target_bounded_kernel(VecArgs a, VecArgs c, MccArgs g, BndArgs bd, BndArgs cb) { mcc_target_kernel_body<true>(a, c, g, bd, cb); }
+
+// candidate direction: direction_column on the candidate's arrays, its partial minima into slots of its own
+template <bool Bounded = false>
+__device__ __forceinline__ void mcc_direction_kernel_body(VecArgs c, MccArgs g, BndArgs cb = BndArgs{}) {
+    if (g.ctl->rdone) return;
+    __shared__ double red[VBLK];
+    const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
+    double mp_ = 1.0, md_ = 1.0;
+    for (int j = gid; j < c.n; j += gsz) {
+        const double xj = c.x[j], sj = c.s[j];
+        const double w = col_sum(c.atp, c.rc_chunks, c.np, j);
+        direction_column<Bounded>(c, cb, j, w, c.dx, c.ds, cb.dw, cb.dz, xj, sj, mp_, md_);
+    }
+    mp_ = block_min(mp_, red); md_ = block_min(md_, red);
+    if (threadIdx.x == 0) { g.part[blockIdx.x] = mp_; g.part[MAXPART + blockIdx.x] = md_; }
+}
+__global__ __launch_bounds__(VBLK) void mcc_direction_kernel(VecArgs c, MccArgs g) { mcc_direction_kernel_body(c, g); }
+__global__ __launch_bounds__(VBLK) void mcc_direction_bounded_kernel(VecArgs c, MccArgs g, BndArgs cb) { mcc_direction_kernel_body<true>(c, g, cb); }
+
+// accept: every block re-reduces the candidate's minima in the fixed order, holds them against the step lengths the target kernel
+// left (the minima of the current direction, re-reduced there: reading them here again would race with the blocks that already
+// replace them) and takes the same decision.  Accept: the block's columns of the candidate replace (dx, ds, dw, dz, q, qz, v) and the
+// complementarity terms, its rows dy, its slot the partial minima.  Reject: the chain is dead for the rest of the iteration.
+template <bool Bounded = false>
+__device__ __forceinline__ void mcc_accept_kernel_body(VecArgs a, VecArgs c, MccArgs g, BndArgs bd = BndArgs{}, BndArgs cb = BndArgs{}) {
+    MccCtl* ctl = g.ctl;
+    if (ctl->rdone) return;
+    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+    const double eta = a.sc->eta;
+    const double ahp = damped_step(eta, min_partials(g.part, 0, a.nblk));
+    const double ahd = damped_step(eta, min_partials(g.part, 1, a.nblk));
+    if (!mcc_accept(ctl->ap, ctl->ad, ahp, ahd)) {
+        if (lead) ctl->rdead = 1;
+        return;
+    }
+    const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
+    for (int j = gid; j < a.n; j += gsz) {
+        a.dx[j] = c.dx[j]; a.ds[j] = c.ds[j]; a.q[j] = c.q[j]; a.v[j] = c.v[j]; g.r3[j] = g.r3g[j];
+        if constexpr (Bounded) { bd.dw[j] = cb.dw[j]; bd.dz[j] = cb.dz[j]; bd.qz[j] = cb.qz[j]; g.r4[j] = g.r4g[j]; }
+    }
+    for (int i = gid; i < a.m; i += gsz) a.dy[i] = c.dy[i];
+    if (threadIdx.x == 0) {
+        a.part[P_MINP * MAXPART + blockIdx.x] = g.part[blockIdx.x];
+        a.part[P_MIND * MAXPART + blockIdx.x] = g.part[MAXPART + blockIdx.x];
+    }
+    if (lead) {
+        ctl->acc += 1;
+        if (!ctl->hit) { ctl->hit = 1; ctl->iters += 1; }
+    }
+}
+__global__ __launch_bounds__(VBLK) void mcc_accept_kernel(VecArgs a, VecArgs c, MccArgs g) { mcc_accept_kernel_body(a, c, g); }
+__global__ __launch_bounds__(VBLK) void mcc_accept_bounded_kernel(VecArgs a, VecArgs c, MccArgs g, BndArgs bd, BndArgs cb) { mcc_accept_kernel_body<true>(a, c, g, bd, cb); }
+
+// ---------------------------------------------------------------------------------------
 // Mehrotra's starting point on the device (ipm_init_state_mehrotra): the column work between the two solves with
 // A A^T and after them.  The rules are iteration_rules.h (start_*); the reductions are the two-level fixed-order ones of this file.
 // Entries beyond n (and rows beyond m) are never written: they keep the zeros ipm_init_state leaves there.

@@ -52,6 +52,20 @@ def check_scale(scale):
     return scale
 
 
+def check_correctors(k):
+    """THE check of the `correctors` keyword, before any device is touched: an integer 0 .. MAX_CORRECTORS."""
+    if isinstance(k, bool) or int(k) != k or not 0 <= int(k) <= _lib.MAX_CORRECTORS:
+        raise ValueError("correctors must be an integer 0 .. %d, not %r" % (_lib.MAX_CORRECTORS, k))
+    return int(k)
+
+
+def refuse_correctors(k, who):
+    """THE refusal of the batch front ends, which have no corrector rounds (lockstep twins, the one-workgroup small kernel): the
+    option is checked like anywhere else and K > 0 raises instead of being dropped."""
+    if check_correctors(k):
+        raise ValueError("correctors=%d: %s runs no centrality-corrector rounds; solve such LPs one at a time" % (k, who))
+
+
 def _gap_tol(tol, tol_gap):           # the gap tolerance of a solve: tol unless the caller gives one of its own
     return float(tol if tol_gap is None else tol_gap)
 
@@ -62,7 +76,7 @@ class IpmSolver:
     def __init__(self, A, b, c, device=0, eta=0.91, pivot_guard_eps=1e-30, pivot_guard_big=1e64,
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
                  auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
-                 infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES):
+                 infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0):
         """ub: native upper bounds 0 <= x <= ub (length n, +inf = none), checked on the host before any device
         is touched.  The normal matrix keeps order m; a bounded solver cannot join the lockstep batch.
         detect_infeasibility: the stop test also tests the iterate for a certificate of primal infeasibility (status 5) or of
@@ -71,8 +85,11 @@ class IpmSolver:
         scale="ruiz": ipm_equilibrate once A, b, c and the bounds are set -- power-of-two Ruiz row / column scaling with at most
         scale_passes passes.  The device then iterates on the scaled LP (stop test, history and statistics are the
         scaled problem's); states, directions and certificates enter and leave in the caller's units, exactly.  scaling() reports
-        the factors.  Off by default."""
+        the factors.  Off by default.
+        correctors: up to that many of Gondzio's centrality-corrector rounds per iteration re-use its factorization (set_correctors;
+        DESIGN.md 4-G).  0, the default, is the iteration without them, exactly."""
         self.scale = check_scale(scale)
+        correctors = check_correctors(correctors)
         if prepared is None:
             prepared = prepare(A, b, c, dense=dense, reorder=reorder, factor=factor, ub=ub)
         elif ub is not None:
@@ -163,6 +180,13 @@ class IpmSolver:
             self.scale_info = dict(passes=int(info[0]), row_spread_before=float(info[1]), row_spread_after=float(info[2]),
                                    col_spread_after=float(info[3]), ms=ms)
         self.stats = None
+        self.correctors = 0
+        if correctors:
+            try:
+                self.set_correctors(correctors)
+            except Exception:
+                self.close()
+                raise
 
     # -- plumbing
     def _check(self, code):
@@ -273,6 +297,20 @@ class IpmSolver:
         n = C.c_int32(0)
         self._check(self._lib.ipm_get_history(self._h, buf, _lib.HISTORY_CAPACITY, C.byref(n)))
         return [{k: getattr(buf[i], k) for k, _ in _lib.IterRecord._fields_} for i in range(n.value)]
+
+    def set_correctors(self, k):
+        """ipm_set_centrality_correctors: up to k (0 .. MAX_CORRECTORS) centrality-corrector rounds per iteration from the next
+        iteration on.  The library refuses (IpmError) a solver on the fused small path and a lockstep solver; both stay usable."""
+        k = check_correctors(k)
+        self._check(self._lib.ipm_set_centrality_correctors(self._h, k))
+        self.correctors = k
+
+    def corrector_info(self):
+        """ipm_get_corrector_info of the last solve() / iterate() sequence: dict with k, rounds (that did work), accepted (rounds)
+        and iterations (with at least one accepted round)."""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.ipm_get_corrector_info(self._h, out))
+        return dict(zip(("k", "rounds", "accepted", "iterations"), (int(v) for v in out)))
 
     def certificate(self):
         """The certificate of the last solve when it ended in status 5 (primal infeasible) or 6 (dual infeasible, i.e.
