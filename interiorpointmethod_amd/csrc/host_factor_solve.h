@@ -89,7 +89,7 @@ static int enqueue_group_inverses(ipm_handle* h, int g0 = 0, int g1 = -1, hipStr
     if (!st) st = h->stream;
     const int nG = g1 - g0;                               // groups [g0, g1)
     if (nG <= 0) return IPM_OK;
-    const int* done = &h->sc->done;
+    const int* done = factor_done(h);                     // (the inverses belong to the factor: whole or not at all, like it)
     launch_twin<LS_GROUP_DIAG_T>(h, 16u * (unsigned)(nG * GS), {h->invD, h->gXT, h->gX, g0 * GS, GS, done}, st);
     const int64_t gXs = GR * GR, gL = GR * (h->mp + 1), gSs = (GR / 2) * (GR / 2);   // group strides in X/XT, L, S
     double* gXT = h->gXT + g0 * gXs; double* gX = h->gX + g0 * gXs; double* gS = h->gS + g0 * gSs;

@@ -144,7 +144,9 @@ static int enqueue_iteration(ipm_handle* h, hipEvent_t* ev) {
         const int gstep = (nG >= 2 && (nG - 1) * h->gsz - 1 < rstep) ? (nG - 1) * h->gsz - 1 : -1;
         if (fused) { if ((rc = enqueue_form_factor(h, ev, rstep, gstep))) return rc; }
         else if ((rc = enqueue_factor(h, rstep, gstep))) return rc;
-        h->fdone = nullptr;
+        // the explicit inverses of the diagonal groups are part of the factor (ipm_normal_solve with reuse_factor substitutes with
+        // both): they test the latch as well, and so does the gate in front of them -- with `done` the last group's inverses of the
+        // iteration whose stop test fired stayed those of the iterate before, under the factor of the final one
         if (gstep >= 0) {
             // the last group's inverse (nine dependent launches, ~80 us) goes to the residual stream as well: the forward
             // sweep of the predictor over the earlier groups runs beside it and only its last step waits
@@ -155,17 +157,19 @@ static int enqueue_iteration(ipm_handle* h, hipEvent_t* ev) {
                 // (every worker's writes through the tile counters the chain acquired), and every kernel of a stream starts with an
                 // acquire.  The last group's inverse now starts 2 us after the launch ends, the main stream's sweep 11 us
                 // (profiles/r04_dense_iteration_timeline*.txt): 261.3 -> 262.4 it/s.
-                hipLaunchKernelGGL(ff_gate_kernel, dim3(1), dim3(64), 0, h->stream3, h->ff_potrfdone + (h->nblk - 1), 1u, timeout_word(h), &h->sc->done);
+                hipLaunchKernelGGL(ff_gate_kernel, dim3(1), dim3(64), 0, h->stream3, h->ff_potrfdone + (h->nblk - 1), 1u, timeout_word(h), factor_done(h));
             } else {
                 HIP_TRY(h, hipEventRecord(h->ev_grp, h->stream));
                 HIP_TRY(h, hipStreamWaitEvent(h->stream3, h->ev_grp, 0));
             }
             if ((rc = enqueue_group_inverses(h, nG - 1, nG, h->stream3))) return rc;
+            h->fdone = nullptr;
             HIP_TRY(h, hipEventRecord(h->ev_last, h->stream3));
             HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_res, 0));
             if ((rc = enqueue_predictor(h, nullptr, /*have_rhs=*/true, h->ev_last))) return rc;
         } else {
             if ((rc = enqueue_group_inverses(h, 0, nG, nullptr))) return rc;
+            h->fdone = nullptr;
             HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_res, 0));
             if ((rc = enqueue_predictor(h, nullptr, /*have_rhs=*/true))) return rc;
         }

@@ -40,8 +40,9 @@ struct Scalars {
     double obj_last_finite;      // last finite c^T x seen by the stop test (main.py:1227-1233 returns it on NaN)
     int done, status, k, max_iter, fixed, force, fixed_first;   // fixed_first: guarded pivots of the first factorization
     int done_f;                  // `done` as it stood when the iteration's formation began (scaling_kernel): what the formation and
-                                 // factorization kernels of the overlapped path test, so that a stop test that flips `done` while
-                                 // they are in flight (it runs on the residual stream) never leaves B half factored
+                                 // factorization kernels of the overlapped path test, and the group inverses behind them, so that a
+                                 // stop test that flips `done` while they are in flight (it runs on the residual stream) never leaves
+                                 // B half factored or the factor with the inverses of the iterate before
 };
 
 // per-iteration record (include/ipm_hip.h: ipm_iter_record), written by record_iteration into a ring

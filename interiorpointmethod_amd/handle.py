@@ -77,7 +77,11 @@ class IpmSolver:
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
                  auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
                  infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0):
-        """ub: native upper bounds 0 <= x <= ub (length n, +inf = none), checked on the host before any device
+        """check_every: solve() enqueues that many iterations at a time and reads the stop flag once per chunk (the launches behind a
+        satisfied stop test return at entry, so the result does not depend on it: DESIGN.md 4-A); a lockstep batch runs chunks of the
+        largest value among its members.  IPM_CHECK_EVERY in the environment, when set and not empty, OVERRIDES this argument for
+        every solver created while it is set.
+        ub: native upper bounds 0 <= x <= ub (length n, +inf = none), checked on the host before any device
         is touched.  The normal matrix keeps order m; a bounded solver cannot join the lockstep batch.
         detect_infeasibility: the stop test also tests the iterate for a certificate of primal infeasibility (status 5) or of
         unboundedness (status 6) with the tolerances infeasibility_tol = (eps_p, eps_d) (IPM_FLAG_DETECT_INFEASIBILITY,
