@@ -405,6 +405,32 @@ int ipm_set_centrality_correctors(ipm_handle* h, int32_t k);
 /* out = {k, rounds that did work, rounds accepted, iterations with at least one accepted round} of the last ipm_solve / ipm_iterate
  * sequence (the counts restart where the iteration count restarts). */
 int ipm_get_corrector_info(ipm_handle* h, int64_t out[4]);
+/* Iterative refinement of the normal-equations solves.  Every solve dy = B~^-1 t of the iteration (predictor,
+ * corrector, centrality-corrector rounds) and of ipm_normal_solve uses the FACTORED matrix B~: guarded pivots, the Tikhonov shift and
+ * the rounding of the Cholesky are in it.  With k > 0 up to k rounds follow each such solve on the device: r = t - A D^2 A^T dy from
+ * the handle's own passes over A, rho = ||r||_2, then dy += B~^-1 r with the same factor.  The rounds of a solve end when rho is 0
+ * or not finite, when rho did not halve against the round before (that correction stays), or when rho grew (that correction is
+ * undone and counted as a revert).  The correction of the last round goes unverified: no residual is taken behind it.  The
+ * decision lives on the device, the host does not synchronise, and the result does not depend on check_every.  D^2 is the handle's
+ * current scaling vector (theta with bounds; the d of ipm_normal_solve, or with reuse_factor the one the handle holds).
+ * ipm_init_state_mehrotra is not refined.  Off (k = 0) by default: the library then enqueues exactly what it enqueued before this call
+ * existed, also on a handle that ran with k > 0 earlier.  k = 0 .. IPM_MAX_REFINE.  IPM_ERR_INVALID_ARG, with the reason in
+ * ipm_last_error, for a NULL handle or k out of range (both checked first, no device is touched), and with k > 0 for a handle on the
+ * fused small path and for a handle created with IPM_FLAG_LOCKSTEP (k = 0 is accepted on every handle).  A handle that goes onto the small path after k > 0 was set is refused by
+ * ipm_solve / ipm_iterate / ipm_newton_direction / ipm_normal_solve until k is set to 0: the option is never dropped.  The vectors of
+ * the rounds are the library's own allocation, made on first use and kept; the workspace sizes do not change. */
+#define IPM_MAX_REFINE 4
+int ipm_set_refinement(ipm_handle* h, int32_t k);
+/* out = {k, solves refined, corrections applied, rounds ended because rho did not halve, reverts, rho_1/||t|| and the last kept
+ * rho/||t|| of the most recent solve, the largest rho_1/||t||} of the last ipm_solve / ipm_iterate sequence (the counts restart where the
+ * iteration count restarts), or of the last ipm_normal_solve or ipm_newton_direction call (each call's one solve: the counts restart
+ * with it). */
+int ipm_get_refinement_info(ipm_handle* h, double out[8]);
+/* Test hook: one of the m-vectors of the last refined solve WITH its padding, to host `out`.  *count = padded length (rows
+ * m .. *count - 1 are padding: zero); nothing is copied when out is NULL or capacity < *count.  which: 0 the kept right-hand side
+ * t, 1 the residual r, 2 the correction delta (IPM_ERR_STATE on a handle that never ran a round), 3 the handle's dy (corrector,
+ * ipm_normal_solve), 4 its predictor dy (tests/test_gpu_refine.py). */
+int ipm_debug_get_refine_vector(ipm_handle* h, int32_t which, double* out, int64_t capacity, int64_t* count);
 /* B = A diag(d) A^T (d on the host, length n); full symmetric m x m written to host B. */
 int ipm_form_normal_matrix(ipm_handle* h, const double* d, double* B, int64_t ldb);
 /* Cholesky factor of the handle's current normal matrix; lower triangle to host L. */

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .analysis import _upper_bounds
-from .handle import SCALE_PASSES, STATUS_NAMES, IpmSolver, check_correctors, check_scale, mehrotra_started, shift_allowed, wants_shift
+from .handle import SCALE_PASSES, STATUS_NAMES, IpmSolver, check_correctors, check_refine, check_scale, mehrotra_started, shift_allowed, wants_shift
 
 
 def _info(solver, cTlb=0.0):
@@ -44,6 +44,7 @@ def _solve_info(solver, history=False, certificate=False):
     info["serial_launches"] = fi["serial_launches"] if fi else 0
     info["factor_path"] = solver.factor
     info["correctors"] = solver.corrector_info()
+    info["refine"] = solver.refine_info()
     if solver.scale is not None:
         info["scale"] = dict(solver.scale_info)
         info["rp_unscaled"], info["rd_unscaled"] = unscaled_residuals(solver)
@@ -78,7 +79,7 @@ def _auto_regularize():          # the process-wide switch of the 5 % rule (hand
 
 def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
                     history=False, ub=None, detect_infeasibility=False, device_start=False, scale=None, scale_passes=SCALE_PASSES,
-                    correctors=0, **opts):
+                    correctors=0, refine=0, **opts):
     """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
     start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start(), or with
     device_start=True IpmSolver.init_state_mehrotra(): the same start computed on the device (no host copy of A, one
@@ -91,9 +92,12 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     scale="ruiz": the LP is equilibrated on the device first (IpmSolver); the statistics are then the SCALED problem's, and
     info["scale"], info["rp_unscaled"], info["rd_unscaled"] say what they mean in the caller's units (unscaled_residuals).
     correctors=K: up to K centrality-corrector rounds per iteration (IpmSolver.set_correctors; 0, the default: none);
-    info["correctors"] = IpmSolver.corrector_info().  An LP on the fused small path refuses K > 0 (IpmError)."""
+    info["correctors"] = IpmSolver.corrector_info().  An LP on the fused small path refuses K > 0 (IpmError).
+    refine=k: up to k rounds of iterative refinement behind every normal-equations solve (IpmSolver.set_refine; 0, the default:
+    none); info["refine"] = IpmSolver.refine_info().  An LP on the fused small path refuses k > 0 (IpmError)."""
     global _last_info
     correctors = check_correctors(correctors)
+    refine = check_refine(refine)
     if start not in ("reference", "mehrotra"):
         raise ValueError('start must be "reference" or "mehrotra"')
     if check_scale(scale) is not None:
@@ -111,7 +115,7 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     t0 = _time.perf_counter()
     if detect_infeasibility:
         opts = dict(opts, detect_infeasibility=True)
-    make = lambda **extra: IpmSolver(A, b, c, device=device, ub=ub, correctors=correctors, **dict(opts, **extra))          # noqa: E731
+    make = lambda **extra: IpmSolver(A, b, c, device=device, ub=ub, correctors=correctors, refine=refine, **dict(opts, **extra))          # noqa: E731
     with (mehrotra_started(make, opts.get("regularize"), _auto_regularize()) if on_device else make()) as sv:
         t1 = _time.perf_counter()
         if start == "mehrotra" and not on_device:
@@ -133,11 +137,11 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     return x, y, s, info
 
 
-def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, scale=None, scale_passes=SCALE_PASSES, correctors=0, **opts):
+def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, **opts):
     """min c^T x s.t. Ax=b, x>=0 (and x <= ub where ub is finite) by the Mehrotra predictor-corrector loop on the GPU
     -> (x, y, s)."""
     x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub, scale=scale,
-                                 scale_passes=scale_passes, correctors=correctors, **opts)
+                                 scale_passes=scale_passes, correctors=correctors, refine=refine, **opts)
     return x, y, s
 
 
@@ -150,12 +154,12 @@ def _verdict(info, value):
     return value
 
 
-def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False, scale=None, scale_passes=SCALE_PASSES, correctors=0):
+def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0):
     """Drop-in for main.py:760-815: start x=s=y=1, cap 5000, returns sum(x*c) - cTlb.  detect_infeasibility=True: +inf for an
-    LP detected infeasible, -inf for one detected unbounded.  scale, correctors: as solve_with_info (off by default)."""
+    LP detected infeasible, -inf for one detected unbounded.  scale, correctors, refine: as solve_with_info (off by default)."""
     _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=5000, y0=1.0, device=device,
                                     detect_infeasibility=detect_infeasibility, scale=scale, scale_passes=scale_passes,
-                                    correctors=correctors)
+                                    correctors=correctors, refine=refine)
     return _verdict(info, info["objective"] - float(cTlb))
 
 

@@ -142,6 +142,11 @@ struct ipm_handle {
     double* mcc_mem = nullptr;            // q v dx ds r3 r3g | qz dw dz r4 r4g (n-vectors) | dy (m-vector) | partial minima [2][MAXPART] | MccCtl | its roll-back copy
     MccCtl mcc_host = MccCtl{};           // host copy of the rounds' record, read back with the scalar record (read_scalars)
     const int* sdone = nullptr;
+    // iterative refinement of the normal-equations solves (ipm_set_refinement): up to ref_k rounds behind every solve
+    // of the iteration and of ipm_normal_solve.  ref_mem: own allocation made on first use (ref_ensure), see ref_views
+    int ref_k = 0;
+    double* ref_mem = nullptr;            // t r delta dy-copy (m-vectors) | atp-copy, A^T delta partials [rc_chunks][np] | partial sums [2][mp/16] | RefCtl | its roll-back copy
+    RefCtl ref_host = RefCtl{};           // host copy of the record, read back with the scalar record (read_scalars)
     // infeasibility detection (IPM_FLAG_DETECT_INFEASIBILITY): the Detect kernel instantiations run
     bool detect = false;
     double det_eps_p = 1e-8, det_eps_d = 1e-8;   // ipm_set_infeasibility_tol
@@ -416,6 +421,21 @@ static MccArgs mcc_args(ipm_handle* h, int first) {
     g.r3 = p + 4 * np; g.r3g = p + 5 * np; g.r4 = p + 9 * np; g.r4g = p + 10 * np;
     g.part = p + MCC_NVECS * np + (size_t)h->mp; g.ctl = mcc_ctl(h); g.first = first;
     return g;
+}
+
+// iterative refinement: views into ref_mem
+static const int REF_CTL_DOUBLES = 16;  // room of one RefCtl
+static_assert(sizeof(RefCtl) <= sizeof(double) * REF_CTL_DOUBLES, "RefCtl outgrew its slot");
+struct RefViews { double *t, *r, *delta, *dy_keep, *atp_keep, *atd, *part; RefCtl* ctl; };
+static size_t ref_na(const ipm_handle* h) { return (size_t)h->rc_chunks * h->np; }
+static size_t ref_doubles(const ipm_handle* h) { return 4 * (size_t)h->mp + 2 * ref_na(h) + 2 * (size_t)(h->mp / REF_ROWS) + 2 * REF_CTL_DOUBLES; }
+static RefViews ref_views(const ipm_handle* h) {
+    const size_t mp = (size_t)h->mp, na = ref_na(h);
+    double* p = h->ref_mem;
+    RefViews v;
+    v.t = p; v.r = p + mp; v.delta = p + 2 * mp; v.dy_keep = p + 3 * mp; v.atp_keep = p + 4 * mp; v.atd = v.atp_keep + na;
+    v.part = v.atd + na; v.ctl = (RefCtl*)(v.part + 2 * (mp / REF_ROWS));
+    return v;
 }
 
 static DetArgs det_args(const ipm_handle* h) { return DetArgs{h->det_eps_p, h->det_eps_d, h->det}; }

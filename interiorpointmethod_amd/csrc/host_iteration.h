@@ -1,6 +1,76 @@
 // host_iteration.h -- host side, unit 6: the launch sequence of one Mehrotra predictor-corrector iteration, the scalar read-back,
 // the roll-back / recovery after a poll time-out, and the loops built on them (ipm_newton_direction, ipm_iterate, ipm_solve).
 #pragma once
+// Iterative refinement of a solve (iteration_rules.h: refine_decide; refine_ops.h).  Nothing is enqueued with
+// ref_k = 0.  A solve that is refined keeps its right-hand side first (refine_keep, in front of the sweeps, which consume it), and
+// enqueue_refine goes behind its A^T dy pass: ref_k rounds of residual -> decide -> delta = B~^-1 r with the handle's own sweeps
+// -> A^T delta (the handle's own pass, into the feature's buffer) -> apply.  The sweeps and the pass test RefCtl::rdone, which the
+// decide kernel of the round wrote: once the rounds of a solve have ended, what is left of them are launches that return at entry,
+// and the host never looks.  `d` is the handle's current D^2 vector (theta on a bounded handle).  All launches are on the main
+// stream and untwinned (ipm_set_refinement refuses a lockstep handle; a program recorded with rounds pending would be cut).
+// h->atp: the apply kernel rewrites the partials in place, in front of their readers on this stream (direction_kernel and, for the
+// predictor, mu_aff / corrector_rhs); the next writer is ordered behind them as DESIGN 4-G says for the centrality correctors.
+static int ref_ensure(ipm_handle* h) {
+    if (h->ref_mem) return IPM_OK;
+    const size_t bytes = sizeof(double) * ref_doubles(h);
+    if (dev_malloc(h->device, h->stream, (void**)&h->ref_mem, bytes) != hipSuccess)
+        return fail(h, IPM_ERR_HIP, "iterative refinement: %lld doubles could not be allocated", (long long)ref_doubles(h));
+    HIP_TRY(h, hipMemsetAsync(h->ref_mem, 0, bytes, h->stream));      // (the padding rows of t, r, delta stay zero from here on)
+    return IPM_OK;
+}
+// start of a solve / of a sequence whose iteration count restarts: the tallies restart with it, as the centrality correctors'
+// do (mcc_start).  With k > 0 the record is made here, in front of the roll-back snapshot; with k = 0 nothing is enqueued.
+static bool ref_on(const ipm_handle* h) { return h->ref_k > 0 && h->ref_mem != nullptr; }
+static int ref_start(ipm_handle* h, bool reset) {
+    if (h->ref_k <= 0) { if (reset) h->ref_host = RefCtl{}; return IPM_OK; }
+    int rc = ref_ensure(h);
+    if (rc) return rc;
+    if (reset) HIP_TRY(h, hipMemsetAsync(ref_views(h).ctl, 0, sizeof(RefCtl), h->stream));
+    return IPM_OK;
+}
+// a handle that went onto the fused small path AFTER k > 0 was set: the solve entries refuse instead of dropping the option
+static int ref_check_path(ipm_handle* h, const char* who) {
+    if (h->small && h->ref_k > 0)
+        return fail(h, IPM_ERR_INVALID_ARG, "%s: %d refinement rounds are set but the handle runs the fused small-LP kernel, which has none (ipm_set_refinement(h, 0))", who, h->ref_k);
+    return IPM_OK;
+}
+static int refine_keep(ipm_handle* h, const double* t) {
+    if (h->ref_k <= 0) return IPM_OK;
+    int rc = ref_ensure(h);
+    if (rc) return rc;
+    launch_untwinned(h, refine_keep_kernel, dim3((unsigned)((h->mp + 255) / 256)), dim3(256), nullptr, t, ref_views(h).t, (int)h->mp, solve_done(h));
+    return IPM_OK;
+}
+// t: the kept right-hand side (refine_keep); dy: the result of the solve, whose A^T dy partials are in h->atp
+static int enqueue_refine(ipm_handle* h, const double* t, double* dy) {
+    if (h->ref_k <= 0) return IPM_OK;
+    int rc = ref_ensure(h);
+    if (rc) return rc;
+    const RefViews v = ref_views(h);
+    const int* outer = solve_done(h);                               // the word of the solve (Scalars::done, or a corrector round's)
+    struct Word { ipm_handle* h; const int* w; ~Word() { h->sdone = w; } } word{h, h->sdone};
+    const unsigned gres = (unsigned)(h->mp / REF_ROWS);
+    const unsigned gapp = (unsigned)std::min<int64_t>(((int64_t)ref_na(h) + VBLK - 1) / VBLK, 1024);
+    for (int j = 0; j < h->ref_k; ++j) {
+        const int first = j == 0;
+        if (h->sparse) launch_untwinned(h, refine_residual_csr_kernel, dim3(gres), dim3(256), nullptr, sparse_view(h), (int)h->mp, (int)h->np, (const double*)h->d,
+                                        (const double*)h->atp, h->rc_chunks, t, v.r, v.part, outer, (const RefCtl*)v.ctl, first);
+        else launch_untwinned(h, refine_residual_dense_kernel, dim3(gres), dim3(256), nullptr, (const double*)h->A, h->np, (int)h->m, (int)h->mp, (int)h->n, (int)h->np,
+                              (const double*)h->d, (const double*)h->atp, h->rc_chunks, t, v.r, v.part, outer, (const RefCtl*)v.ctl, first);
+        launch_untwinned(h, refine_decide_kernel, dim3(1), dim3(VBLK), nullptr, (const double*)v.part, (int)gres, v.ctl, outer, first);
+        h->sdone = &v.ctl->rdone;
+        if ((rc = enqueue_potrs(h, v.r, v.delta))) return rc;
+        if (h->sparse) launch_untwinned(h, spmv_csc_t_kernel, dim3((unsigned)((h->np + 15) / 16)), dim3(256), nullptr, sparse_view(h), (int)h->np, (const double*)v.delta, v.atd, solve_done(h));
+        else launch_untwinned(h, gemv_t_kernel, dim3((unsigned)((h->np + 511) / 512), (unsigned)h->rc_chunks), dim3(256), nullptr, (const double*)h->A, h->np, h->rows_per_chunk,
+                              (int)h->np, (const double*)v.delta, v.atd, solve_done(h));
+        h->sdone = word.w;
+        launch_untwinned(h, refine_apply_kernel, dim3(gapp), dim3(VBLK), nullptr, (const RefCtl*)v.ctl, (int)h->m, (int64_t)ref_na(h), (const double*)v.delta,
+                         (const double*)v.atd, dy, h->atp, v.dy_keep, v.atp_keep);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return IPM_OK;
+}
+
 // the tail the predictor (corr = 0) and the corrector (corr = 1) share: dy = B^{-1} t1, A^T dy, then the x and s parts of the direction
 // Streamed A^T dy (stream_at_on): the backward sweep makes dy final one 1024-row group at a time, last group first, and the
 // pass over A splits by row chunks without changing a bit (launch_gemv_t_rows), so the piece of every sweep event but the last runs
@@ -14,6 +84,8 @@
 // stream, and behind this iteration's last reader through the event it waits for (ev_mid / ev_fork, recorded on the main stream).
 static int enqueue_solve_direction(ipm_handle* h, hipEvent_t* ev, double* dy, int corr, hipEvent_t wait_last = nullptr) {
     if (ev) HIP_TRY(h, hipEventRecord(ev[0], h->stream));
+    int rrc = refine_keep(h, h->t1);
+    if (rrc) return rrc;
     std::vector<AtPiece> pieces;
     if (stream_at_on(h)) pieces = at_piece_schedule(h->mp, h->gsz, h->nblk, h->rc_chunks, h->rows_per_chunk);
     if (pieces.empty()) {
@@ -42,6 +114,7 @@ static int enqueue_solve_direction(ipm_handle* h, hipEvent_t* ev, double* dy, in
             HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_at, 0));
         }
     }
+    if ((rrc = enqueue_refine(h, ref_on(h) ? ref_views(h).t : nullptr, dy))) return rrc;      // (streamed pieces: behind the join)
     launch_direction(h, corr);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
@@ -104,8 +177,10 @@ static int enqueue_corrector_rounds(ipm_handle* h) {
         launch_mcc_target(h, r == 0);
         h->sdone = &mcc_ctl(h)->rdone;
         launch_gemv_n(h, c.v, -1.0, -1.0, h->rb, h->t1);
+        if ((rc = refine_keep(h, h->t1))) return rc;
         if ((rc = enqueue_potrs(h, h->t1, c.dy))) return rc;
         launch_gemv_t(h, c.dy);
+        if ((rc = enqueue_refine(h, ref_on(h) ? ref_views(h).t : nullptr, c.dy))) return rc;
         h->sdone = nullptr;
         launch_mcc_direction(h);
         launch_mcc_accept(h);
@@ -218,6 +293,7 @@ static int read_scalars(ipm_handle* h, bool* timed_out = nullptr) {
     HIP_TRY(h, hipMemcpyAsync(h->h_sc, h->sc, sizeof(Scalars), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(&tmo, word, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     if (mcc_on(h)) HIP_TRY(h, hipMemcpyAsync(&h->mcc_host, mcc_ctl(h), sizeof(MccCtl), hipMemcpyDeviceToHost, h->stream));
+    if (ref_on(h)) HIP_TRY(h, hipMemcpyAsync(&h->ref_host, ref_views(h).ctl, sizeof(RefCtl), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (tmo) {
         if (h->stream2) HIP_TRY(h, hipStreamSynchronize(h->stream2));               // the bulk stream may still be draining
@@ -278,6 +354,11 @@ static int enqueue_snapshot(ipm_handle* h, int restore, hipStream_t st = nullptr
         MccCtl* s = (MccCtl*)((double*)c + MCC_CTL_DOUBLES);
         HIP_TRY(h, hipMemcpyAsync(restore ? c : s, restore ? s : c, sizeof(MccCtl), hipMemcpyDeviceToDevice, st ? st : h->stream));
     }
+    if (ref_on(h)) {                                           // the record of the refinement rounds, likewise
+        RefCtl* c = ref_views(h).ctl;
+        RefCtl* s = (RefCtl*)((double*)c + REF_CTL_DOUBLES);
+        HIP_TRY(h, hipMemcpyAsync(restore ? c : s, restore ? s : c, sizeof(RefCtl), hipMemcpyDeviceToDevice, st ? st : h->stream));
+    }
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
@@ -306,10 +387,12 @@ static int check_ready(ipm_handle* h, const char* who) {
 extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, double* dy, double* ds, ipm_stats* stats) {
     int rc = check_ready(h, "ipm_newton_direction");
     if (rc) return rc;
+    if ((rc = ref_check_path(h, "ipm_newton_direction"))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     if (!corrector) {
         for (int attempt = 0;; ++attempt) {                 // second pass only after a recovered poll time-out
             hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, h->stream, h->sc, 1e-8, 1e-8, 1e-8, h->opt.eta, 1 << 30, 1, 0);
+            if ((rc = ref_start(h, true))) return rc;         // the tallies describe this call's solve
             if ((rc = enqueue_residuals(h))) return rc;
             if ((rc = enqueue_form(h, h->d))) return rc;
             if ((rc = enqueue_factor(h))) return rc;
@@ -328,6 +411,7 @@ extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, do
         if (ds) HIP_TRY(h, hipMemcpyAsync(ds, h->dsa, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     } else {
         if (!h->predictor_valid) return fail(h, IPM_ERR_STATE, "corrector requested without a predictor at this state");
+        if ((rc = ref_start(h, true))) return rc;
         if ((rc = enqueue_corrector(h, nullptr))) return rc;
         // alpha_p/alpha_d for stats without moving the iterate: recompute in a 1-thread kernel? they are
         // written by update_kernel only; expose the raw ratio minima through sigma/mu_aff and leave alpha to
@@ -357,6 +441,36 @@ extern "C" int ipm_get_corrector_info(ipm_handle* h, int64_t out[4]) {
     if (!h || !out) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_corrector_info: bad arguments");
     const MccCtl& c = h->mcc_host;                              // the host copy the last ipm_solve / ipm_iterate read back
     out[0] = h->mcc_k; out[1] = c.run; out[2] = c.acc; out[3] = c.iters;
+    return IPM_OK;
+}
+
+// ------------------------------------------------------------------------------- iterative refinement
+extern "C" int ipm_set_refinement(ipm_handle* h, int32_t k) {
+    if (k < 0 || k > IPM_MAX_REFINE) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_refinement: k = %d outside 0 .. %d", (int)k, IPM_MAX_REFINE);
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_refinement: NULL handle");
+    // (k = 0 is accepted on every handle: it is the way out for a handle that went onto the small path after k > 0 was set)
+    if (k > 0 && h->small) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_refinement: the handle runs the fused small-LP kernel (one workgroup holds the whole loop; it has no rounds)");
+    if (k > 0 && h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_refinement: the handle was created with IPM_FLAG_LOCKSTEP (the rounds have no batched twins)");
+    h->ref_k = k;
+    return IPM_OK;
+}
+extern "C" int ipm_debug_get_refine_vector(ipm_handle* h, int32_t which, double* out, int64_t capacity, int64_t* count) {
+    if (!h || !count || which < 0 || which > 4) return fail(h, IPM_ERR_INVALID_ARG, "ipm_debug_get_refine_vector: bad arguments");
+    *count = h->mp;
+    if (!out || capacity < h->mp) return IPM_OK;
+    if (which < 3 && !h->ref_mem) return fail(h, IPM_ERR_STATE, "ipm_debug_get_refine_vector: the handle never ran a refinement round");
+    const RefViews v = h->ref_mem ? ref_views(h) : RefViews{};
+    const double* src = which == 0 ? v.t : which == 1 ? v.r : which == 2 ? v.delta : which == 3 ? h->dy : h->dya;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpyAsync(out, src, sizeof(double) * h->mp, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return IPM_OK;
+}
+extern "C" int ipm_get_refinement_info(ipm_handle* h, double out[8]) {
+    if (!h || !out) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_refinement_info: bad arguments");
+    const RefCtl& c = h->ref_host;                              // the host copy the last call that read the scalar record took
+    out[0] = h->ref_k; out[1] = (double)c.solves; out[2] = (double)c.applied; out[3] = (double)c.half; out[4] = (double)c.reverts;
+    out[5] = c.first_rel; out[6] = c.last_rel; out[7] = c.max_rel;
     return IPM_OK;
 }
 
@@ -447,6 +561,7 @@ extern "C" int ipm_iterate(ipm_handle* h, int32_t n_steps, ipm_stats* stats) {
     if (rc) return rc;
     if (n_steps < 0) return fail(h, IPM_ERR_INVALID_ARG, "n_steps < 0");
     if ((rc = mcc_check_path(h, "ipm_iterate"))) return rc;
+    if ((rc = ref_check_path(h, "ipm_iterate"))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     h->predictor_valid = false;
     std::vector<hipEvent_t> evs;
@@ -475,6 +590,7 @@ extern "C" int ipm_iterate(ipm_handle* h, int32_t n_steps, ipm_stats* stats) {
         hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, h->stream, h->sc, 1e-8, 1e-8, 1e-8, h->opt.eta, 1 << 30, 1,
                            attempt == 0 ? reset_k : 0);
         if ((rc = mcc_start(h, attempt == 0 && reset_k))) return rc;
+        if ((rc = ref_start(h, attempt == 0 && reset_k))) return rc;
         const bool guard_poll = may_poll(h) && n_steps > 0;
         if (guard_poll && (rc = enqueue_snapshot(h, 0))) return rc;
         HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
@@ -519,11 +635,13 @@ extern "C" int ipm_solve(ipm_handle* h, double tol_p, double tol_d, double tol_g
     if (rc) return rc;
     if (max_iter < 0) return fail(h, IPM_ERR_INVALID_ARG, "max_iter < 0");
     if ((rc = mcc_check_path(h, "ipm_solve"))) return rc;
+    if ((rc = ref_check_path(h, "ipm_solve"))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     h->predictor_valid = false; h->fresh_state = false;
     if (h->auto_reg) { h->auto_reg = 0; h->shift_rel = h->opt.regularize; }      // decided per solve
     hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, h->stream, h->sc, tol_p, tol_d, tol_gap, h->opt.eta, max_iter, 0, 1);
     if ((rc = mcc_start(h, true))) return rc;
+    if ((rc = ref_start(h, true))) return rc;
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     const int chunk = h->opt.check_every;
     const bool may_auto = h->opt.regularize == 0.0 && !(h->opt.flags & IPM_FLAG_NO_AUTO_REGULARIZE);

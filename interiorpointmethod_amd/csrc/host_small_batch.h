@@ -53,6 +53,7 @@ static int small_batch_check_handles(const char* who, ipm_handle** hs, int32_t n
         if (!h) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d is NULL", who, i);
         if (!h->small) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d is not on the fused small-LP path (sparse A of at most %d rows; ipm_get_schedule out[9])", who, i, SMALL_MAX_M);
         if (h->mcc_k > 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d has %d centrality correctors set; the small-LP kernel runs no rounds", who, i, h->mcc_k);
+        if (h->ref_k > 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d has %d refinement rounds set; the small-LP kernel runs none", who, i, h->ref_k);
         if (h->device != hs[0]->device) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d lives on device %d, handle 0 on device %d", who, i, h->device, hs[0]->device);
     }
     {   // the same handle twice: two workgroups would race on one state

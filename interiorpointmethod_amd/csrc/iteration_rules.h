@@ -219,6 +219,45 @@ __device__ __forceinline__ void mcc_rhs_column(const Cols& a, const BndArgs& bd,
     corrector_rhs_plain(c, j, qj);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Iterative refinement of one normal-equations solve (ipm_set_refinement; restated in NumPy as tests/refine_oracle.py).
+// The solve gave dy = B~^-1 t with the FACTORED matrix B~ (guarded pivots, Tikhonov shift, rounding of the blocked Cholesky) and
+// a = A^T dy.  Up to k rounds correct it against the matrix-free operator A D^2 A^T.  Round j = 1 .. k:
+//   1. r = t - A (d o a), rho_j = ||r||_2 (fixed-order reduction, bitwise repeatable);
+//   2. rho_j is 0 or not finite: the rounds of this solve end;
+//   3. j > 1 and rho_j > rho_{j-1}: (dy, a) are restored from the copy taken before the previous correction, a revert is
+//      counted, the rounds end;
+//   4. j > 1 and rho_j > rho_{j-1} / 2: the rounds end, the previous correction stays;
+//   5. otherwise (dy, a) are copied aside, delta = B~^-1 r with the same factor and sweeps, dy += delta, a += A^T delta.
+// The correction of the LAST round is never measured: no residual follows it.
+// The decision of a round is this function, run by one thread (refine_decide_kernel) on the reduced sums of r^2 and t^2; it lives
+// in the device-side record, so no host synchronisation takes part.  rdone: the word the products with A and the substitutions
+// of a round test in place of Scalars::done (`outer_done`: the word the solve itself tests -- Scalars::done, or MccCtl::rdone inside
+// a centrality-corrector round); action: what the round's apply kernel does.  Tallies (ipm_get_refinement_info): solves whose
+// first round ran, corrections applied, rounds ended by rule 4, reverts, rho_1/||t|| and the last kept rho/||t|| of the most recent
+// solve, the largest rho_1/||t|| of the sequence.
+enum { REF_NONE = 0, REF_APPLY = 1, REF_RESTORE = 2 };
+struct RefCtl {
+    double rho_prev, first_rel, last_rel, max_rel;
+    long long solves, applied, half, reverts;
+    int rdone, action;
+};
+__device__ __forceinline__ void refine_decide(RefCtl* c, double r2, double t2, bool first, bool outer_done) {
+    c->action = REF_NONE;
+    if (first) {
+        c->rdone = outer_done ? 1 : 0;
+        if (outer_done) return;
+        c->solves += 1;
+    } else if (c->rdone) return;
+    const double rho = sqrt(r2), tn = sqrt(t2);
+    const double rel = rho > 0.0 ? rho / tn : rho;               // (rho = 0 with t = 0: 0, not 0/0)
+    if (first) { c->first_rel = rel; c->max_rel = fmax(c->max_rel, rel); }
+    if (!(rho > 0.0) || !(rho < 1.7976931348623157e308)) { c->last_rel = rel; c->rdone = 1; return; }                  // rule 2
+    if (!first && rho > c->rho_prev) { c->reverts += 1; c->action = REF_RESTORE; c->rdone = 1; return; }              // rule 3
+    if (!first && rho > 0.5 * c->rho_prev) { c->half += 1; c->last_rel = rel; c->rdone = 1; return; }                  // rule 4
+    c->applied += 1; c->rho_prev = rho; c->last_rel = rel; c->action = REF_APPLY;                                     // rule 5
+}
+
 // damped step from the reduced ratio-test minimum (main.py:604-626) and the column update x += a_p dx ; s += a_d ds
 // (Bounded: w += a_p dw ; z += a_d dz)  (main.py:694-696); y += a_d dy stays with the path, which knows where y lives
 __device__ __forceinline__ double damped_step(double eta, double ratio_min) { return fmin(1.0, eta * ratio_min); }

@@ -1,4 +1,5 @@
 """IpmSolver: one LP bound to one GPU through a libipm_hip handle.  PyTorch only owns the workspace and the stream; all arithmetic is HIP."""
+import collections
 import ctypes as C
 import os
 
@@ -66,6 +67,23 @@ def refuse_correctors(k, who):
         raise ValueError("correctors=%d: %s runs no centrality-corrector rounds; solve such LPs one at a time" % (k, who))
 
 
+def check_refine(k):
+    """THE check of the `refine` keyword, before any device is touched: an integer 0 .. MAX_REFINE."""
+    if isinstance(k, bool) or int(k) != k or not 0 <= int(k) <= _lib.MAX_REFINE:
+        raise ValueError("refine must be an integer 0 .. %d, not %r" % (_lib.MAX_REFINE, k))
+    return int(k)
+
+
+def refuse_refine(k, who):
+    """THE refusal of the batch front ends, which have no refinement rounds (lockstep twins, the one-workgroup small kernel): the
+    option is checked like anywhere else and k > 0 raises instead of being dropped."""
+    if check_refine(k):
+        raise ValueError("refine=%d: %s runs no refinement rounds; solve such LPs one at a time" % (k, who))
+
+
+RefineInfo = collections.namedtuple("RefineInfo", "k solves applied half_rule reverts first_rel last_rel max_first_rel")
+
+
 def _gap_tol(tol, tol_gap):           # the gap tolerance of a solve: tol unless the caller gives one of its own
     return float(tol if tol_gap is None else tol_gap)
 
@@ -76,7 +94,7 @@ class IpmSolver:
     def __init__(self, A, b, c, device=0, eta=0.91, pivot_guard_eps=1e-30, pivot_guard_big=1e64,
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
                  auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
-                 infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0):
+                 infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0):
         """check_every: solve() enqueues that many iterations at a time and reads the stop flag once per chunk (the launches behind a
         satisfied stop test return at entry, so the result does not depend on it: DESIGN.md 4-A); a lockstep batch runs chunks of the
         largest value among its members.  IPM_CHECK_EVERY in the environment, when set and not empty, OVERRIDES this argument for
@@ -91,9 +109,12 @@ class IpmSolver:
         scaled problem's); states, directions and certificates enter and leave in the caller's units, exactly.  scaling() reports
         the factors.  Off by default.
         correctors: up to that many of Gondzio's centrality-corrector rounds per iteration re-use its factorization (set_correctors;
-        DESIGN.md 4-G).  0, the default, is the iteration without them, exactly."""
+        DESIGN.md 4-G).  0, the default, is the iteration without them, exactly.
+        refine: up to that many rounds of iterative refinement behind every normal-equations solve, against the matrix-free
+        A D^2 A^T (set_refine).  0, the default, is the iteration without them, exactly."""
         self.scale = check_scale(scale)
         correctors = check_correctors(correctors)
+        refine = check_refine(refine)
         if prepared is None:
             prepared = prepare(A, b, c, dense=dense, reorder=reorder, factor=factor, ub=ub)
         elif ub is not None:
@@ -185,12 +206,15 @@ class IpmSolver:
                                    col_spread_after=float(info[3]), ms=ms)
         self.stats = None
         self.correctors = 0
-        if correctors:
-            try:
+        self.refine = 0
+        try:
+            if correctors:
                 self.set_correctors(correctors)
-            except Exception:
-                self.close()
-                raise
+            if refine:
+                self.set_refine(refine)
+        except Exception:
+            self.close()
+            raise
 
     # -- plumbing
     def _check(self, code):
@@ -315,6 +339,33 @@ class IpmSolver:
         out = (C.c_int64 * 4)()
         self._check(self._lib.ipm_get_corrector_info(self._h, out))
         return dict(zip(("k", "rounds", "accepted", "iterations"), (int(v) for v in out)))
+
+    def set_refine(self, k):
+        """ipm_set_refinement: up to k (0 .. MAX_REFINE) rounds of iterative refinement behind every normal-equations solve -- the
+        iteration's (predictor, corrector, centrality-corrector rounds) and normal_solve's; init_state_mehrotra is not refined.  The
+        library refuses (IpmError) a solver on the fused small path and a lockstep solver; both stay usable."""
+        k = check_refine(k)
+        self._check(self._lib.ipm_set_refinement(self._h, k))
+        self.refine = k
+
+    def refine_info(self):
+        """ipm_get_refinement_info of the last solve() / iterate() sequence (or normal_solve), in the order of the C array: a
+        RefineInfo tuple (k, solves refined, applied corrections, half_rule: rounds ended because the residual did not halve,
+        reverts, first_rel / last_rel: the residual norm over ||rhs|| of the most recent solve at its first round and the last one
+        kept, max_first_rel)."""
+        out = np.zeros(8)
+        self._check(self._lib.ipm_get_refinement_info(self._h, _dptr(out)))
+        return RefineInfo(*[int(v) for v in out[:5]], *[float(v) for v in out[5:]])
+
+    def debug_refine_vector(self, which):
+        """ipm_debug_get_refine_vector (test hook): an m-vector of the last refined solve WITH its padding rows, in the device's row
+        order -- which = "t", "r", "delta" (the kept right-hand side, the residual, the correction), "dy" or "dya"."""
+        idx = ("t", "r", "delta", "dy", "dya").index(which)
+        n = C.c_int64(0)
+        self._check(self._lib.ipm_debug_get_refine_vector(self._h, idx, None, 0, C.byref(n)))
+        out = np.empty(n.value)
+        self._check(self._lib.ipm_debug_get_refine_vector(self._h, idx, _dptr(out), n.value, C.byref(n)))
+        return out
 
     def certificate(self):
         """The certificate of the last solve when it ended in status 5 (primal infeasible) or 6 (dual infeasible, i.e.
