@@ -394,12 +394,12 @@ int ipm_normal_solve(ipm_handle* h, const double* d, const double* rhs, double* 
  * rejected round ends the rounds of its iteration.  Off (k = 0) by default: the handle then runs exactly the iteration it ran
  * without this call.  k = 0 .. IPM_MAX_CORRECTORS, taking effect with the next iteration of ipm_solve / ipm_iterate
  * (ipm_newton_direction keeps returning Mehrotra's two directions).  IPM_ERR_INVALID_ARG, with the reason in ipm_last_error, for a NULL
- * handle or k out of range (both checked first, no device is touched), for a handle on the fused small path (schedule word 9: one
- * workgroup holds the whole loop) and for a handle created with IPM_FLAG_LOCKSTEP (the rounds have no batched twins).  A handle that
- * ipm_set_A_csc puts on the small path AFTER k > 0 was set keeps k, and ipm_solve / ipm_iterate / ipm_solve_small_batch refuse it
- * (IPM_ERR_INVALID_ARG) until k is set to 0: the option is never dropped.  The candidate vectors are the library's own allocation,
- * made on first use and kept; the workspace sizes do not change.  With k = 0 the library enqueues exactly what it enqueued before
- * this call existed, also on a handle that ran with k > 0 earlier. */
+ * handle or k out of range (both checked first, no device is touched), and with k > 0 for a handle on the fused small path (schedule
+ * word 9: one workgroup holds the whole loop) and for a handle created with IPM_FLAG_LOCKSTEP (the rounds have no batched twins;
+ * k = 0 is accepted on every handle).  A handle that ipm_set_A_csc puts on the small path AFTER k > 0 was set keeps k, and ipm_solve /
+ * ipm_iterate / ipm_solve_small_batch refuse it (IPM_ERR_INVALID_ARG) until k is set to 0: the option is never dropped.  The
+ * candidate vectors are the library's own allocation, made on first use and kept; the workspace sizes do not change.  With k = 0 the
+ * library enqueues exactly what it enqueued before this call existed, also on a handle that ran with k > 0 earlier. */
 #define IPM_MAX_CORRECTORS 8
 int ipm_set_centrality_correctors(ipm_handle* h, int32_t k);
 /* out = {k, rounds that did work, rounds accepted, iterations with at least one accepted round} of the last ipm_solve / ipm_iterate

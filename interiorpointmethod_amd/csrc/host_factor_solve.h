@@ -379,43 +379,3 @@ static int enqueue_potrs(ipm_handle* h, double* r, double* out, hipEvent_t wait_
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
-
-// Mehrotra's starting point of a multi-kernel handle, enqueued on the handle's stream (ipm_init_state_mehrotra):
-// A A^T formed with d = 1, factored with the handle's guard and shift and the group inverses built as ipm_normal_solve(h, NULL, ...)
-// does, then  u = (A A^T)^-1 b, x = A^T u  and  y = (A A^T)^-1 (A c), s = c - A^T y  from the device copies of b and c, then the
-// shifts and the balance (vector_ops.h, start_*).  The guarded-pivot count of the factorization stays in sc->fixed.  Never part of a
-// recorded lockstep program (the handle joins its batch afterwards).
-static int enqueue_mehrotra_start(ipm_handle* h) {
-    int rc;
-    const unsigned gn = (unsigned)((h->n + 255) / 256);
-    hipLaunchKernelGGL(fill_kernel, dim3(gn), dim3(256), 0, h->stream, h->d, (int)h->n, 1.0);
-    if ((rc = enqueue_form(h, h->d))) return rc;
-    if ((rc = enqueue_factor(h))) return rc;
-    if ((rc = enqueue_group_inverses(h))) return rc;
-    const VecArgs va = vec_args(h);
-    const dim3 g(h->vblk), b(VBLK);
-    // x = A^T (A A^T)^-1 b   (the padding rows of b are zero, and stay zero through the solve)
-    HIP_TRY(h, hipMemcpyAsync(h->t1, h->b, sizeof(double) * h->mp, hipMemcpyDeviceToDevice, h->stream));
-    if ((rc = enqueue_potrs(h, h->t1, h->dy))) return rc;
-    launch_gemv_t(h, h->dy);
-    if (h->bnd) hipLaunchKernelGGL(start_primal_bounded_kernel, g, b, 0, h->stream, va, bnd_args(h));
-    else hipLaunchKernelGGL(start_primal_kernel, g, b, 0, h->stream, va);
-    // y = (A A^T)^-1 (A c), s = c - A^T y
-    launch_gemv_n(h, h->c, 1.0, 0.0, nullptr, h->t1);
-    if ((rc = enqueue_potrs(h, h->t1, h->dy))) return rc;
-    launch_gemv_t(h, h->dy);
-    if (h->bnd) {
-        const BndArgs bd = bnd_args(h);
-        hipLaunchKernelGGL(start_dual_bounded_kernel, g, b, 0, h->stream, va, bd);
-        hipLaunchKernelGGL(start_shift_bounded_kernel, g, b, 0, h->stream, va, bd);
-        hipLaunchKernelGGL(start_primal_correct_bounded_kernel, g, b, 0, h->stream, va, bd);
-        hipLaunchKernelGGL(start_dual_correct_bounded_kernel, g, b, 0, h->stream, va, bd);
-    } else {
-        hipLaunchKernelGGL(start_dual_kernel, g, b, 0, h->stream, va);
-        hipLaunchKernelGGL(start_shift_kernel, g, b, 0, h->stream, va);
-        hipLaunchKernelGGL(start_primal_correct_kernel, g, b, 0, h->stream, va);
-        hipLaunchKernelGGL(start_dual_correct_kernel, g, b, 0, h->stream, va);
-    }
-    HIP_TRY(h, hipGetLastError());
-    return IPM_OK;
-}

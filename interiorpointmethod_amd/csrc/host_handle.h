@@ -11,6 +11,26 @@ static const int MAX_DEVICES = 64;
 static std::atomic<int> g_live[MAX_DEVICES];
 static std::atomic<bool> g_attr_set[MAX_DEVICES];      // per-device function attributes (dynamic LDS of adat_sparse)
 
+// A round feature (centrality correctors, iterative refinement): k rounds set by the caller, device memory of its own made on first
+// use, and at the END of that memory a control record the kernels keep (tallies, the rounds' `done` word) with its roll-back copy
+// CTL_DOUBLES, the room of one record, behind it.  RoundsKind is what differs between the features besides where their vectors lie:
+// the words of the messages, the range of k and the size formula.  The operations are in host_iteration.h (rounds_*).
+struct ipm_handle;
+struct RoundsKind { const char *noun, *none, *small_why, *setter; int kmax; size_t (*doubles)(const ipm_handle*); };
+template <class Ctl, int CTL_DOUBLES> struct Rounds {
+    static_assert(sizeof(Ctl) <= sizeof(double) * CTL_DOUBLES, "the record outgrew its slot");
+    const RoundsKind* kind;
+    int k = 0;
+    double* mem = nullptr;
+    Ctl host = Ctl{};                     // host copy of the record, read back with the scalar record (read_scalars)
+    Ctl* ctl_copy(const ipm_handle* h) const { return (Ctl*)((double*)ctl(h) + CTL_DOUBLES); }
+    Ctl* ctl(const ipm_handle* h) const { return (Ctl*)(mem + kind->doubles(h) - 2 * CTL_DOUBLES); }
+};
+static const int MCC_CTL_DOUBLES = 8, REF_CTL_DOUBLES = 16;
+static size_t mcc_doubles(const ipm_handle* h), ref_doubles(const ipm_handle* h);      // (beside the views, below)
+static const RoundsKind MCC_KIND{"centrality correctors", "no rounds", "factor and solve cost the same there", "ipm_set_centrality_correctors", IPM_MAX_CORRECTORS, mcc_doubles};
+static const RoundsKind REF_KIND{"refinement rounds", "none", "it has no rounds", "ipm_set_refinement", IPM_MAX_REFINE, ref_doubles};
+
 struct ipm_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -135,18 +155,12 @@ struct ipm_handle {
     bool bnd = false;                     // a finite bound is set: the bounded kernel instantiations run
     int bnd_nU = 0;                       // |U|
     double* bnd_mem = nullptr;            // u | w | z | dwa | dza | dw | dz | qz | roll-back w | roll-back z
-    // centrality correctors (ipm_set_centrality_correctors): up to mcc_k rounds per iteration re-use its factor.
-    // mcc_mem: the candidate vectors, own allocation made on first use (mcc_ensure).  sdone: while the launches of a round are
-    // enqueued, the word its products with A and its substitutions test in place of Scalars::done (solve_done)
-    int mcc_k = 0;
-    double* mcc_mem = nullptr;            // q v dx ds r3 r3g | qz dw dz r4 r4g (n-vectors) | dy (m-vector) | partial minima [2][MAXPART] | MccCtl | its roll-back copy
-    MccCtl mcc_host = MccCtl{};           // host copy of the rounds' record, read back with the scalar record (read_scalars)
-    const int* sdone = nullptr;
-    // iterative refinement of the normal-equations solves (ipm_set_refinement): up to ref_k rounds behind every solve
-    // of the iteration and of ipm_normal_solve.  ref_mem: own allocation made on first use (ref_ensure), see ref_views
-    int ref_k = 0;
-    double* ref_mem = nullptr;            // t r delta dy-copy (m-vectors) | atp-copy, A^T delta partials [rc_chunks][np] | partial sums [2][mp/16] | RefCtl | its roll-back copy
-    RefCtl ref_host = RefCtl{};           // host copy of the record, read back with the scalar record (read_scalars)
+    // centrality correctors (ipm_set_centrality_correctors): up to mcc.k rounds per iteration re-use its factor
+    Rounds<MccCtl, MCC_CTL_DOUBLES> mcc{&MCC_KIND};   // mem: q v dx ds r3 r3g | qz dw dz r4 r4g (n-vectors) | dy (m-vector) | partial minima [2][MAXPART] | record | its copy
+    // iterative refinement of the normal-equations solves (ipm_set_refinement): up to ref.k rounds behind every solve
+    // of the iteration and of ipm_normal_solve
+    Rounds<RefCtl, REF_CTL_DOUBLES> ref{&REF_KIND};   // mem: t r delta dy-copy (m-vectors) | atp-copy, A^T delta partials [rc_chunks][np] | partial sums [2][mp/16] | record | its copy
+    const int* sdone = nullptr;           // the word the products with A and the substitutions test in place of Scalars::done (solve_done, SolveWord)
     // infeasibility detection (IPM_FLAG_DETECT_INFEASIBILITY): the Detect kernel instantiations run
     bool detect = false;
     double det_eps_p = 1e-8, det_eps_d = 1e-8;   // ipm_set_infeasibility_tol
@@ -228,6 +242,13 @@ static inline bool polls_device(const ipm_handle* h) { return wants_polling(h) &
 static inline unsigned* timeout_word(const ipm_handle* h) { return h->d_flags + 2 * (size_t)h->nblk; }      // time-out word of the device-side hand-offs
 static inline unsigned* at_progress_word(const ipm_handle* h) { return timeout_word(h) + 1; }               // progress word of the streamed A^T dy (d_flags has four spare words)
 static inline const int* solve_done(const ipm_handle* h) { return h->sdone ? h->sdone : &h->sc->done; }       // `done` word the products with A and the substitutions test
+// sets that word for a scope: the previous one comes back on every return path
+struct SolveWord {
+    ipm_handle* const h; const int* const prev;
+    SolveWord(ipm_handle* h_, const int* w) : h(h_), prev(h_->sdone) { h->sdone = w; }
+    ~SolveWord() { h->sdone = prev; }
+    SolveWord(const SolveWord&) = delete;
+};
 static inline const int* factor_done(const ipm_handle* h) { return h->fdone ? h->fdone : &h->sc->done; }    // `done` word formation / factorization test
 
 // Device memory the handle owns besides its workspace.  STREAM-ORDERED (hipMallocAsync / hipFreeAsync on the handle's
@@ -394,47 +415,42 @@ static BndArgs bnd_args(ipm_handle* h) {
     return b;
 }
 
-// centrality correctors: views into mcc_mem.  mcc_vec_args / mcc_bnd_args are the handle's views with the candidate's arrays in place.
+// centrality correctors: views into mcc.mem.  mcc_vec_args / mcc_bnd_args are the handle's views with the candidate's arrays in place.
 static const int MCC_NVECS = 11;
-static const int MCC_CTL_DOUBLES = 8;   // room of one MccCtl
-static_assert(sizeof(MccCtl) <= sizeof(double) * MCC_CTL_DOUBLES, "MccCtl outgrew its slot");
 static size_t mcc_doubles(const ipm_handle* h) { return (size_t)MCC_NVECS * h->np + (size_t)h->mp + 2 * MAXPART + 2 * MCC_CTL_DOUBLES; }
-static MccCtl* mcc_ctl(const ipm_handle* h) { return (MccCtl*)(h->mcc_mem + (size_t)MCC_NVECS * h->np + (size_t)h->mp + 2 * MAXPART); }
 static VecArgs mcc_vec_args(ipm_handle* h) {
     const size_t np = (size_t)h->np;
-    double* p = h->mcc_mem;
+    double* p = h->mcc.mem;
     VecArgs c = vec_args(h);
     c.q = p; c.v = p + np; c.dx = p + 2 * np; c.ds = p + 3 * np; c.dy = p + MCC_NVECS * np;
     return c;
 }
 static BndArgs mcc_bnd_args(ipm_handle* h) {
     const size_t np = (size_t)h->np;
-    double* p = h->mcc_mem;
+    double* p = h->mcc.mem;
     BndArgs b = bnd_args(h);
     b.qz = p + 6 * np; b.dw = p + 7 * np; b.dz = p + 8 * np;
     return b;
 }
 static MccArgs mcc_args(ipm_handle* h, int first) {
     const size_t np = (size_t)h->np;
-    double* p = h->mcc_mem;
+    double* p = h->mcc.mem;
     MccArgs g;
     g.r3 = p + 4 * np; g.r3g = p + 5 * np; g.r4 = p + 9 * np; g.r4g = p + 10 * np;
-    g.part = p + MCC_NVECS * np + (size_t)h->mp; g.ctl = mcc_ctl(h); g.first = first;
+    g.part = p + MCC_NVECS * np + (size_t)h->mp; g.ctl = h->mcc.ctl(h); g.first = first;
     return g;
 }
 
-// iterative refinement: views into ref_mem
-static const int REF_CTL_DOUBLES = 16;  // room of one RefCtl
-static_assert(sizeof(RefCtl) <= sizeof(double) * REF_CTL_DOUBLES, "RefCtl outgrew its slot");
+// iterative refinement: views into ref.mem
 struct RefViews { double *t, *r, *delta, *dy_keep, *atp_keep, *atd, *part; RefCtl* ctl; };
 static size_t ref_na(const ipm_handle* h) { return (size_t)h->rc_chunks * h->np; }
 static size_t ref_doubles(const ipm_handle* h) { return 4 * (size_t)h->mp + 2 * ref_na(h) + 2 * (size_t)(h->mp / REF_ROWS) + 2 * REF_CTL_DOUBLES; }
 static RefViews ref_views(const ipm_handle* h) {
     const size_t mp = (size_t)h->mp, na = ref_na(h);
-    double* p = h->ref_mem;
+    double* p = h->ref.mem;
     RefViews v;
     v.t = p; v.r = p + mp; v.delta = p + 2 * mp; v.dy_keep = p + 3 * mp; v.atp_keep = p + 4 * mp; v.atd = v.atp_keep + na;
-    v.part = v.atd + na; v.ctl = (RefCtl*)(v.part + 2 * (mp / REF_ROWS));
+    v.part = v.atd + na; v.ctl = h->ref.ctl(h);
     return v;
 }
 

@@ -1,98 +1,84 @@
 // host_iteration.h -- host side, unit 6: the launch sequence of one Mehrotra predictor-corrector iteration, the scalar read-back,
 // the roll-back / recovery after a poll time-out, and the loops built on them (ipm_newton_direction, ipm_iterate, ipm_solve).
 #pragma once
-// Iterative refinement of a solve (iteration_rules.h: refine_decide; refine_ops.h).  Nothing is enqueued with
-// ref_k = 0.  A solve that is refined keeps its right-hand side first (refine_keep, in front of the sweeps, which consume it), and
-// enqueue_refine goes behind its A^T dy pass: ref_k rounds of residual -> decide -> delta = B~^-1 r with the handle's own sweeps
-// -> A^T delta (the handle's own pass, into the feature's buffer) -> apply.  The sweeps and the pass test RefCtl::rdone, which the
-// decide kernel of the round wrote: once the rounds of a solve have ended, what is left of them are launches that return at entry,
-// and the host never looks.  `d` is the handle's current D^2 vector (theta on a bounded handle).  All launches are on the main
-// stream and untwinned (ipm_set_refinement refuses a lockstep handle; a program recorded with rounds pending would be cut).
-// h->atp: the apply kernel rewrites the partials in place, in front of their readers on this stream (direction_kernel and, for the
-// predictor, mu_aff / corrector_rhs); the next writer is ordered behind them as DESIGN 4-G says for the centrality correctors.
-static int ref_ensure(ipm_handle* h) {
-    if (h->ref_mem) return IPM_OK;
-    const size_t bytes = sizeof(double) * ref_doubles(h);
-    if (dev_malloc(h->device, h->stream, (void**)&h->ref_mem, bytes) != hipSuccess)
-        return fail(h, IPM_ERR_HIP, "iterative refinement: %lld doubles could not be allocated", (long long)ref_doubles(h));
-    HIP_TRY(h, hipMemsetAsync(h->ref_mem, 0, bytes, h->stream));      // (the padding rows of t, r, delta stay zero from here on)
+// The operations of a round feature (host_handle.h: Rounds), each stated once for the centrality correctors (h->mcc)
+// and the iterative refinement (h->ref, 4-I).  With k = 0 nothing is enqueued anywhere, also on a handle that ran rounds before.
+// The allocation, on first use, zeroed: products with A read the padding of the vectors in it, and the tallies start at zero.
+template <class R> static int rounds_ensure(ipm_handle* h, R& r) {
+    if (r.mem) return IPM_OK;
+    const size_t n = r.kind->doubles(h);
+    if (dev_malloc(h->device, h->stream, (void**)&r.mem, sizeof(double) * n) != hipSuccess)
+        return fail(h, IPM_ERR_HIP, "%s: %lld doubles could not be allocated", r.kind->noun, (long long)n);
+    HIP_TRY(h, hipMemsetAsync(r.mem, 0, sizeof(double) * n, h->stream));
     return IPM_OK;
 }
-// start of a solve / of a sequence whose iteration count restarts: the tallies restart with it, as the centrality correctors'
-// do (mcc_start).  With k > 0 the record is made here, in front of the roll-back snapshot; with k = 0 nothing is enqueued.
-static bool ref_on(const ipm_handle* h) { return h->ref_k > 0 && h->ref_mem != nullptr; }
-static int ref_start(ipm_handle* h, bool reset) {
-    if (h->ref_k <= 0) { if (reset) h->ref_host = RefCtl{}; return IPM_OK; }
-    int rc = ref_ensure(h);
+template <class R> static bool rounds_on(const R& r) { return r.k > 0 && r.mem != nullptr; }
+// start of a solve / of a sequence whose iteration count restarts (reset): the tallies restart with it.  With k > 0 the record is
+// made here, in front of the roll-back snapshot; with k = 0 the host copy of the tallies is cleared on the host.
+template <class R> static int rounds_start(ipm_handle* h, R& r, bool reset) {
+    if (r.k <= 0) { if (reset) r.host = {}; return IPM_OK; }
+    int rc = rounds_ensure(h, r);
     if (rc) return rc;
-    if (reset) HIP_TRY(h, hipMemsetAsync(ref_views(h).ctl, 0, sizeof(RefCtl), h->stream));
+    if (reset) HIP_TRY(h, hipMemsetAsync(r.ctl(h), 0, sizeof r.host, h->stream));
     return IPM_OK;
 }
-// a handle that went onto the fused small path AFTER k > 0 was set: the solve entries refuse instead of dropping the option
-static int ref_check_path(ipm_handle* h, const char* who) {
-    if (h->small && h->ref_k > 0)
-        return fail(h, IPM_ERR_INVALID_ARG, "%s: %d refinement rounds are set but the handle runs the fused small-LP kernel, which has none (ipm_set_refinement(h, 0))", who, h->ref_k);
+// A handle that went onto the fused small path AFTER k > 0 was set (ipm_set_A_csc decides the path): its loop runs in one workgroup
+// and has no rounds, so the solve entries refuse instead of dropping the option.
+template <class R> static int rounds_check_path(ipm_handle* h, const R& r, const char* who) {
+    if (h->small && r.k > 0)
+        return fail(h, IPM_ERR_INVALID_ARG, "%s: %d %s are set but the handle runs the fused small-LP kernel, which has %s (%s(h, 0))", who, r.k, r.kind->noun, r.kind->none, r.kind->setter);
     return IPM_OK;
 }
-static int refine_keep(ipm_handle* h, const double* t) {
-    if (h->ref_k <= 0) return IPM_OK;
-    int rc = ref_ensure(h);
-    if (rc) return rc;
-    launch_untwinned(h, refine_keep_kernel, dim3((unsigned)((h->mp + 255) / 256)), dim3(256), nullptr, t, ref_views(h).t, (int)h->mp, solve_done(h));
+// the record -> its host copy, beside the scalar record (read_scalars); the record <-> its roll-back copy (enqueue_snapshot)
+template <class R> static int rounds_read_back(ipm_handle* h, R& r) {
+    if (rounds_on(r)) HIP_TRY(h, hipMemcpyAsync(&r.host, r.ctl(h), sizeof r.host, hipMemcpyDeviceToHost, h->stream));
     return IPM_OK;
 }
-// t: the kept right-hand side (refine_keep); dy: the result of the solve, whose A^T dy partials are in h->atp
-static int enqueue_refine(ipm_handle* h, const double* t, double* dy) {
-    if (h->ref_k <= 0) return IPM_OK;
-    int rc = ref_ensure(h);
-    if (rc) return rc;
-    const RefViews v = ref_views(h);
-    const int* outer = solve_done(h);                               // the word of the solve (Scalars::done, or a corrector round's)
-    struct Word { ipm_handle* h; const int* w; ~Word() { h->sdone = w; } } word{h, h->sdone};
-    const unsigned gres = (unsigned)(h->mp / REF_ROWS);
-    const unsigned gapp = (unsigned)std::min<int64_t>(((int64_t)ref_na(h) + VBLK - 1) / VBLK, 1024);
-    for (int j = 0; j < h->ref_k; ++j) {
-        const int first = j == 0;
-        if (h->sparse) launch_untwinned(h, refine_residual_csr_kernel, dim3(gres), dim3(256), nullptr, sparse_view(h), (int)h->mp, (int)h->np, (const double*)h->d,
-                                        (const double*)h->atp, h->rc_chunks, t, v.r, v.part, outer, (const RefCtl*)v.ctl, first);
-        else launch_untwinned(h, refine_residual_dense_kernel, dim3(gres), dim3(256), nullptr, (const double*)h->A, h->np, (int)h->m, (int)h->mp, (int)h->n, (int)h->np,
-                              (const double*)h->d, (const double*)h->atp, h->rc_chunks, t, v.r, v.part, outer, (const RefCtl*)v.ctl, first);
-        launch_untwinned(h, refine_decide_kernel, dim3(1), dim3(VBLK), nullptr, (const double*)v.part, (int)gres, v.ctl, outer, first);
-        h->sdone = &v.ctl->rdone;
-        if ((rc = enqueue_potrs(h, v.r, v.delta))) return rc;
-        if (h->sparse) launch_untwinned(h, spmv_csc_t_kernel, dim3((unsigned)((h->np + 15) / 16)), dim3(256), nullptr, sparse_view(h), (int)h->np, (const double*)v.delta, v.atd, solve_done(h));
-        else launch_untwinned(h, gemv_t_kernel, dim3((unsigned)((h->np + 511) / 512), (unsigned)h->rc_chunks), dim3(256), nullptr, (const double*)h->A, h->np, h->rows_per_chunk,
-                              (int)h->np, (const double*)v.delta, v.atd, solve_done(h));
-        h->sdone = word.w;
-        launch_untwinned(h, refine_apply_kernel, dim3(gapp), dim3(VBLK), nullptr, (const RefCtl*)v.ctl, (int)h->m, (int64_t)ref_na(h), (const double*)v.delta,
-                         (const double*)v.atd, dy, h->atp, v.dy_keep, v.atp_keep);
-    }
-    HIP_TRY(h, hipGetLastError());
+template <class R> static int rounds_snapshot(ipm_handle* h, const R& r, int restore, hipStream_t st) {
+    if (rounds_on(r)) HIP_TRY(h, hipMemcpyAsync(restore ? r.ctl(h) : r.ctl_copy(h), restore ? r.ctl_copy(h) : r.ctl(h), sizeof r.host, hipMemcpyDeviceToDevice, st));
+    return IPM_OK;
+}
+// The setters' argument rules.  The range check reads nothing of the handle, so it comes first: both argument checks hold without a
+// device, for any h.  k = 0 is accepted on every handle: it is the way out for a handle that went onto the small path after k > 0.
+template <class R> static int rounds_set(ipm_handle* h, R ipm_handle::*which, const RoundsKind& kind, int32_t k) {
+    if (k < 0 || k > kind.kmax) return fail(h, IPM_ERR_INVALID_ARG, "%s: k = %d outside 0 .. %d", kind.setter, (int)k, kind.kmax);
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "%s: NULL handle", kind.setter);
+    if (k > 0 && h->small) return fail(h, IPM_ERR_INVALID_ARG, "%s: the handle runs the fused small-LP kernel (one workgroup holds the whole loop; %s)", kind.setter, kind.small_why);
+    if (k > 0 && h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "%s: the handle was created with IPM_FLAG_LOCKSTEP (the rounds have no batched twins)", kind.setter);
+    (h->*which).k = k;
     return IPM_OK;
 }
 
-// the tail the predictor (corr = 0) and the corrector (corr = 1) share: dy = B^{-1} t1, A^T dy, then the x and s parts of the direction
-// Streamed A^T dy (stream_at_on): the backward sweep makes dy final one 1024-row group at a time, last group first, and the
-// pass over A splits by row chunks without changing a bit (launch_gemv_t_rows), so the piece of every sweep event but the last runs
-// on the residual stream while the sweep goes on: a gate on the handle's progress word (the bounded spin of every device-side
-// wait; a time-out is rolled back like any other and poll_fallback drops the streaming for good), then the piece.  The main stream
-// runs the last event's piece itself and joins the residual stream with one event wait -- that event is recorded behind the last
-// streamed piece, which has normally ended by then.
+// One solve with the factored normal matrix, the one statement of it (predictor, corrector, a centrality-corrector round,
+// ipm_normal_solve, the two solves of Mehrotra's start, refinement's own correction solve):  out = B~^-1 rhs with the handle's
+// sweeps (rhs is consumed), then A^T out as partials into `atp` (null: no pass), then, for a `refine`d solve of a handle with
+// ref.k > 0, the refinement rounds -- which need rhs kept in front of the sweeps and the A^T pass behind them.
+// Hooks of the iteration: wait_last (enqueue_potrs), ev (two profiling events, around the sweeps) and stream_at.
+// Streamed A^T dy (stream_at where stream_at_on): the backward sweep makes dy final one 1024-row group
+// at a time, last group first, and the pass over A splits by row chunks without changing a bit (launch_gemv_t_rows), so the piece of
+// every sweep event but the last runs on the residual stream while the sweep goes on: a gate on the handle's progress word (the
+// bounded spin of every device-side wait; a time-out is rolled back like any other and poll_fallback drops the streaming for good),
+// then the piece.  The main stream runs the last event's piece itself and joins the residual stream with one event wait -- that
+// event is recorded behind the last streamed piece, which has normally ended by then.
 // h->atp: the corrector's pieces overwrite the predictor's partials, which mu_aff / corrector_rhs / the predictor's direction
 // kernel read -- all of them IN FRONT of the corrector's sweep on the main stream, and a piece runs only behind the gate that a
 // kernel of that sweep opens.  The next iteration's A^T y (residual stream) is enqueued behind these pieces on the same in-order
 // stream, and behind this iteration's last reader through the event it waits for (ev_mid / ev_fork, recorded on the main stream).
-static int enqueue_solve_direction(ipm_handle* h, hipEvent_t* ev, double* dy, int corr, hipEvent_t wait_last = nullptr) {
-    if (ev) HIP_TRY(h, hipEventRecord(ev[0], h->stream));
-    int rrc = refine_keep(h, h->t1);
-    if (rrc) return rrc;
+struct SolveHooks { hipEvent_t wait_last = nullptr; hipEvent_t* ev = nullptr; bool stream_at = false; };
+static int refine_keep(ipm_handle* h, const double* t);
+static int enqueue_refine(ipm_handle* h, double* dy);
+static int enqueue_normal_solve(ipm_handle* h, double* rhs, double* out, double* atp, bool refine, const SolveHooks& hooks = {}) {
+    int rc;
+    if (((refine && h->ref.k > 0) || hooks.stream_at) && atp != h->atp)             // (both read and write the handle's own partials)
+        return fail(h, IPM_ERR_INVALID_ARG, "enqueue_normal_solve: a refined or streamed solve takes h->atp");
+    if (hooks.ev) HIP_TRY(h, hipEventRecord(hooks.ev[0], h->stream));
+    if (refine && (rc = refine_keep(h, rhs))) return rc;
     std::vector<AtPiece> pieces;
-    if (stream_at_on(h)) pieces = at_piece_schedule(h->mp, h->gsz, h->nblk, h->rc_chunks, h->rows_per_chunk);
+    if (hooks.stream_at && stream_at_on(h)) pieces = at_piece_schedule(h->mp, h->gsz, h->nblk, h->rc_chunks, h->rows_per_chunk);
     if (pieces.empty()) {
-        int rc = enqueue_potrs(h, h->t1, dy, wait_last);
-        if (rc) return rc;
-        if (ev) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
-        launch_gemv_t(h, dy);
+        if ((rc = enqueue_potrs(h, rhs, out, hooks.wait_last))) return rc;
+        if (hooks.ev) HIP_TRY(h, hipEventRecord(hooks.ev[1], h->stream));
+        if (atp) launch_gemv_t(h, out, nullptr, atp);
     } else {
         bool streamed = false;
         SweepHook hook;
@@ -102,19 +88,65 @@ static int enqueue_solve_direction(ipm_handle* h, hipEvent_t* ev, double* dy, in
             const AtPiece& p = pieces[(size_t)e];
             if (p.chunk1 <= p.chunk0) return;
             hipLaunchKernelGGL(ff_gate_kernel, dim3(1), dim3(64), 0, h->stream3, hook.word, hook.base + (unsigned)e + 1u, timeout_word(h), &h->sc->done);
-            launch_gemv_t_rows(h, dy, p.chunk0, p.chunk1, h->stream3);
+            launch_gemv_t_rows(h, out, p.chunk0, p.chunk1, h->stream3);
             streamed = true;
         };
-        int rc = enqueue_potrs(h, h->t1, dy, wait_last, &hook);
-        if (rc) return rc;
-        if (ev) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
-        launch_gemv_t_rows(h, dy, pieces.back().chunk0, pieces.back().chunk1, h->stream);
+        if ((rc = enqueue_potrs(h, rhs, out, hooks.wait_last, &hook))) return rc;
+        if (hooks.ev) HIP_TRY(h, hipEventRecord(hooks.ev[1], h->stream));
+        launch_gemv_t_rows(h, out, pieces.back().chunk0, pieces.back().chunk1, h->stream);
         if (streamed) {
             HIP_TRY(h, hipEventRecord(h->ev_at, h->stream3));
             HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_at, 0));
         }
     }
-    if ((rrc = enqueue_refine(h, ref_on(h) ? ref_views(h).t : nullptr, dy))) return rrc;      // (streamed pieces: behind the join)
+    return refine ? enqueue_refine(h, out) : IPM_OK;              // (streamed pieces: behind the join)
+}
+
+// Iterative refinement of a solve (iteration_rules.h: refine_decide; refine_ops.h), the two halves that bracket it
+// inside enqueue_normal_solve: refine_keep copies the right-hand side in front of the sweeps, which consume it, and enqueue_refine
+// goes behind the A^T dy pass: ref.k rounds of residual -> decide -> delta = B~^-1 r, A^T delta (a solve of its own, unrefined,
+// into the feature's buffers) -> apply.  That solve tests RefCtl::rdone, which the decide kernel of the round wrote: once the
+// rounds of a solve have ended, what is left of them are launches that return at entry, and the host never looks.  The residual is
+// taken with the handle's current D^2 vector h->d (theta on a bounded handle).  All launches are on the main stream and untwinned
+// (ipm_set_refinement refuses a lockstep handle; a program recorded with rounds pending would be cut).
+// h->atp: the apply kernel rewrites the partials in place, in front of their readers on this stream (direction_kernel and, for the
+// predictor, mu_aff / corrector_rhs); the next writer is ordered behind them as said below for the centrality correctors.
+static int refine_keep(ipm_handle* h, const double* t) {
+    if (h->ref.k <= 0) return IPM_OK;
+    int rc = rounds_ensure(h, h->ref);
+    if (rc) return rc;
+    launch_untwinned(h, refine_keep_kernel, dim3((unsigned)((h->mp + 255) / 256)), dim3(256), nullptr, t, ref_views(h).t, (int)h->mp, solve_done(h));
+    return IPM_OK;
+}
+static int enqueue_refine(ipm_handle* h, double* dy) {               // dy: the result of the solve, whose A^T dy partials are in h->atp
+    if (h->ref.k <= 0) return IPM_OK;
+    int rc;
+    const RefViews v = ref_views(h);
+    const int* outer = solve_done(h);                               // the word of the solve (Scalars::done, or a corrector round's)
+    const unsigned gres = (unsigned)(h->mp / REF_ROWS);
+    const unsigned gapp = (unsigned)std::min<int64_t>(((int64_t)ref_na(h) + VBLK - 1) / VBLK, 1024);
+    for (int j = 0; j < h->ref.k; ++j) {
+        const int first = j == 0;
+        if (h->sparse) launch_untwinned(h, refine_residual_csr_kernel, dim3(gres), dim3(256), nullptr, sparse_view(h), (int)h->mp, (int)h->np, (const double*)h->d,
+                                        (const double*)h->atp, h->rc_chunks, (const double*)v.t, v.r, v.part, outer, (const RefCtl*)v.ctl, first);
+        else launch_untwinned(h, refine_residual_dense_kernel, dim3(gres), dim3(256), nullptr, (const double*)h->A, h->np, (int)h->m, (int)h->mp, (int)h->n, (int)h->np,
+                              (const double*)h->d, (const double*)h->atp, h->rc_chunks, (const double*)v.t, v.r, v.part, outer, (const RefCtl*)v.ctl, first);
+        launch_untwinned(h, refine_decide_kernel, dim3(1), dim3(VBLK), nullptr, (const double*)v.part, (int)gres, v.ctl, outer, first);
+        {
+            SolveWord word(h, &v.ctl->rdone);
+            if ((rc = enqueue_normal_solve(h, v.r, v.delta, v.atd, /*refine=*/false))) return rc;
+        }
+        launch_untwinned(h, refine_apply_kernel, dim3(gapp), dim3(VBLK), nullptr, (const RefCtl*)v.ctl, (int)h->m, (int64_t)ref_na(h), (const double*)v.delta,
+                         (const double*)v.atd, dy, h->atp, v.dy_keep, v.atp_keep);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return IPM_OK;
+}
+
+// the tail the predictor (corr = 0) and the corrector (corr = 1) share: dy = B^{-1} t1, A^T dy, then the x and s parts of the direction
+static int enqueue_solve_direction(ipm_handle* h, hipEvent_t* ev, double* dy, int corr, hipEvent_t wait_last = nullptr) {
+    int rc = enqueue_normal_solve(h, h->t1, dy, h->atp, /*refine=*/true, {wait_last, ev, /*stream_at=*/true});
+    if (rc) return rc;
     launch_direction(h, corr);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
@@ -130,58 +162,28 @@ static int enqueue_corrector(ipm_handle* h, hipEvent_t* ev) {
     return enqueue_solve_direction(h, ev, h->dy, 1);
 }
 
-// Centrality correctors: up to mcc_k rounds between the corrector and the update, each the corrector's pipeline
+// Centrality correctors: up to mcc.k rounds between the corrector and the update, each the corrector's pipeline
 // again with this iteration's factor -- target / right-hand side, rhs = -r_b - A v_g, dy_g = B^{-1} rhs, A^T dy_g, the candidate
-// direction, the accept decision.  Nothing is enqueued with mcc_k = 0.  The products with A and the substitutions test
-// MccCtl::rdone (solve_done), which the round's target kernel sets: after a rejected round the later rounds of the iteration are
-// launches that return at entry.  t1 / t2 are free here (the corrector's solve consumed them) and the candidate vectors are mcc_mem.
+// direction, the accept decision.  The products with A and the substitutions test MccCtl::rdone (SolveWord), which the round's
+// target kernel sets: after a rejected round the later rounds of the iteration are launches that return at entry.  t1 / t2 are
+// free here (the corrector's solve consumed them) and the candidate vectors are mcc.mem.
 // A^T dy_g is the UNSTREAMED pass on the main stream (streaming it behind the sweep is left out): it overwrites h->atp, whose last
 // reader of the Mehrotra corrector (direction_kernel) lies in front of it on this stream.  The next writer of h->atp is the next
 // iteration's A^T y on the residual stream; it waits for ev_mid (enqueue_residual_stream) or, on the fused path, ev_fork
 // (enqueue_form_factor), both recorded on the MAIN stream inside that iteration's factorization -- behind launch_update and so
 // behind every round's mcc_direction_kernel, the last reader of h->atp, in stream order.
-static int mcc_ensure(ipm_handle* h) {
-    if (h->mcc_mem) return IPM_OK;
-    const size_t bytes = sizeof(double) * mcc_doubles(h);
-    if (dev_malloc(h->device, h->stream, (void**)&h->mcc_mem, bytes) != hipSuccess)
-        return fail(h, IPM_ERR_HIP, "centrality correctors: %lld doubles could not be allocated", (long long)mcc_doubles(h));
-    HIP_TRY(h, hipMemsetAsync(h->mcc_mem, 0, bytes, h->stream));      // (the padding of v_g is read by the product with A: zeros)
-    return IPM_OK;
-}
-// start of a solve / of an iterate sequence whose iteration count restarts: the tallies restart with it (a handle that never ran a
-// round has no record and nothing is enqueued).  With K > 0 the record is made here, in front of the roll-back snapshot.
-// With K = 0 nothing is enqueued here, in read_scalars or in enqueue_snapshot, also on a handle that ran rounds before (mcc_on):
-// where the count restarts, the host copy of the tallies is cleared on the host.
-static bool mcc_on(const ipm_handle* h) { return h->mcc_k > 0 && h->mcc_mem != nullptr; }
-static int mcc_start(ipm_handle* h, bool reset) {
-    if (h->mcc_k <= 0) { if (reset) h->mcc_host = MccCtl{}; return IPM_OK; }
-    int rc = mcc_ensure(h);
-    if (rc) return rc;
-    if (reset) HIP_TRY(h, hipMemsetAsync(mcc_ctl(h), 0, sizeof(MccCtl), h->stream));
-    return IPM_OK;
-}
-// A handle that went onto the fused small path AFTER K > 0 was set (ipm_set_A_csc decides the path): its loop runs in one workgroup
-// and has no rounds, so the solve entries refuse instead of dropping the option.
-static int mcc_check_path(ipm_handle* h, const char* who) {
-    if (h->small && h->mcc_k > 0)
-        return fail(h, IPM_ERR_INVALID_ARG, "%s: %d centrality correctors are set but the handle runs the fused small-LP kernel, which has no rounds (ipm_set_centrality_correctors(h, 0))", who, h->mcc_k);
-    return IPM_OK;
-}
 static int enqueue_corrector_rounds(ipm_handle* h) {
-    if (h->mcc_k <= 0) return IPM_OK;
-    int rc = mcc_ensure(h);
+    if (h->mcc.k <= 0) return IPM_OK;
+    int rc = rounds_ensure(h, h->mcc);
     if (rc) return rc;
-    struct Word { ipm_handle* h; ~Word() { h->sdone = nullptr; } } word{h};
     const VecArgs c = mcc_vec_args(h);
-    for (int r = 0; r < h->mcc_k; ++r) {
+    for (int r = 0; r < h->mcc.k; ++r) {
         launch_mcc_target(h, r == 0);
-        h->sdone = &mcc_ctl(h)->rdone;
-        launch_gemv_n(h, c.v, -1.0, -1.0, h->rb, h->t1);
-        if ((rc = refine_keep(h, h->t1))) return rc;
-        if ((rc = enqueue_potrs(h, h->t1, c.dy))) return rc;
-        launch_gemv_t(h, c.dy);
-        if ((rc = enqueue_refine(h, ref_on(h) ? ref_views(h).t : nullptr, c.dy))) return rc;
-        h->sdone = nullptr;
+        {
+            SolveWord word(h, &h->mcc.ctl(h)->rdone);
+            launch_gemv_n(h, c.v, -1.0, -1.0, h->rb, h->t1);
+            if ((rc = enqueue_normal_solve(h, h->t1, c.dy, h->atp, /*refine=*/true))) return rc;
+        }
         launch_mcc_direction(h);
         launch_mcc_accept(h);
     }
@@ -292,8 +294,8 @@ static int read_scalars(ipm_handle* h, bool* timed_out = nullptr) {
     unsigned* word = timeout_word(h);
     HIP_TRY(h, hipMemcpyAsync(h->h_sc, h->sc, sizeof(Scalars), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(&tmo, word, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
-    if (mcc_on(h)) HIP_TRY(h, hipMemcpyAsync(&h->mcc_host, mcc_ctl(h), sizeof(MccCtl), hipMemcpyDeviceToHost, h->stream));
-    if (ref_on(h)) HIP_TRY(h, hipMemcpyAsync(&h->ref_host, ref_views(h).ctl, sizeof(RefCtl), hipMemcpyDeviceToHost, h->stream));
+    int rc;
+    if ((rc = rounds_read_back(h, h->mcc)) || (rc = rounds_read_back(h, h->ref))) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (tmo) {
         if (h->stream2) HIP_TRY(h, hipStreamSynchronize(h->stream2));               // the bulk stream may still be draining
@@ -349,16 +351,8 @@ static int enqueue_snapshot(ipm_handle* h, int restore, hipStream_t st = nullptr
         double* sw = h->bnd_mem + 8 * (size_t)h->np;
         hipLaunchKernelGGL(snapshot_bounds_kernel, dim3(grid), dim3(256), 0, st ? st : h->stream, b.w, b.z, sw, sw + h->np, (int)h->np, restore);
     }
-    if (mcc_on(h)) {                                           // the record of the corrector rounds (its tallies) <-> the copy behind it
-        MccCtl* c = mcc_ctl(h);
-        MccCtl* s = (MccCtl*)((double*)c + MCC_CTL_DOUBLES);
-        HIP_TRY(h, hipMemcpyAsync(restore ? c : s, restore ? s : c, sizeof(MccCtl), hipMemcpyDeviceToDevice, st ? st : h->stream));
-    }
-    if (ref_on(h)) {                                           // the record of the refinement rounds, likewise
-        RefCtl* c = ref_views(h).ctl;
-        RefCtl* s = (RefCtl*)((double*)c + REF_CTL_DOUBLES);
-        HIP_TRY(h, hipMemcpyAsync(restore ? c : s, restore ? s : c, sizeof(RefCtl), hipMemcpyDeviceToDevice, st ? st : h->stream));
-    }
+    int rc;                                                    // the records of the rounds (their tallies) <-> the copies behind them
+    if ((rc = rounds_snapshot(h, h->mcc, restore, st ? st : h->stream)) || (rc = rounds_snapshot(h, h->ref, restore, st ? st : h->stream))) return rc;
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
@@ -387,12 +381,12 @@ static int check_ready(ipm_handle* h, const char* who) {
 extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, double* dy, double* ds, ipm_stats* stats) {
     int rc = check_ready(h, "ipm_newton_direction");
     if (rc) return rc;
-    if ((rc = ref_check_path(h, "ipm_newton_direction"))) return rc;
+    if ((rc = rounds_check_path(h, h->ref, "ipm_newton_direction"))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     if (!corrector) {
         for (int attempt = 0;; ++attempt) {                 // second pass only after a recovered poll time-out
             hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, h->stream, h->sc, 1e-8, 1e-8, 1e-8, h->opt.eta, 1 << 30, 1, 0);
-            if ((rc = ref_start(h, true))) return rc;         // the tallies describe this call's solve
+            if ((rc = rounds_start(h, h->ref, true))) return rc;         // the tallies describe this call's solve
             if ((rc = enqueue_residuals(h))) return rc;
             if ((rc = enqueue_form(h, h->d))) return rc;
             if ((rc = enqueue_factor(h))) return rc;
@@ -411,7 +405,7 @@ extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, do
         if (ds) HIP_TRY(h, hipMemcpyAsync(ds, h->dsa, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     } else {
         if (!h->predictor_valid) return fail(h, IPM_ERR_STATE, "corrector requested without a predictor at this state");
-        if ((rc = ref_start(h, true))) return rc;
+        if ((rc = rounds_start(h, h->ref, true))) return rc;
         if ((rc = enqueue_corrector(h, nullptr))) return rc;
         // alpha_p/alpha_d for stats without moving the iterate: recompute in a 1-thread kernel? they are
         // written by update_kernel only; expose the raw ratio minima through sigma/mu_aff and leave alpha to
@@ -428,38 +422,22 @@ extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, do
 }
 
 // ------------------------------------------------------------------------------- centrality correctors
-extern "C" int ipm_set_centrality_correctors(ipm_handle* h, int32_t k) {
-    // (the range check reads nothing of the handle, so it comes first: both argument checks hold without a device, for any h)
-    if (k < 0 || k > IPM_MAX_CORRECTORS) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_centrality_correctors: k = %d outside 0 .. %d", (int)k, IPM_MAX_CORRECTORS);
-    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_centrality_correctors: NULL handle");
-    if (h->small) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_centrality_correctors: the handle runs the fused small-LP kernel (one workgroup holds the whole loop; factor and solve cost the same there)");
-    if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_centrality_correctors: the handle was created with IPM_FLAG_LOCKSTEP (the rounds have no batched twins)");
-    h->mcc_k = k;
-    return IPM_OK;
-}
+extern "C" int ipm_set_centrality_correctors(ipm_handle* h, int32_t k) { return rounds_set(h, &ipm_handle::mcc, MCC_KIND, k); }
 extern "C" int ipm_get_corrector_info(ipm_handle* h, int64_t out[4]) {
     if (!h || !out) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_corrector_info: bad arguments");
-    const MccCtl& c = h->mcc_host;                              // the host copy the last ipm_solve / ipm_iterate read back
-    out[0] = h->mcc_k; out[1] = c.run; out[2] = c.acc; out[3] = c.iters;
+    const MccCtl& c = h->mcc.host;                              // the host copy the last ipm_solve / ipm_iterate read back
+    out[0] = h->mcc.k; out[1] = c.run; out[2] = c.acc; out[3] = c.iters;
     return IPM_OK;
 }
 
 // ------------------------------------------------------------------------------- iterative refinement
-extern "C" int ipm_set_refinement(ipm_handle* h, int32_t k) {
-    if (k < 0 || k > IPM_MAX_REFINE) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_refinement: k = %d outside 0 .. %d", (int)k, IPM_MAX_REFINE);
-    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_refinement: NULL handle");
-    // (k = 0 is accepted on every handle: it is the way out for a handle that went onto the small path after k > 0 was set)
-    if (k > 0 && h->small) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_refinement: the handle runs the fused small-LP kernel (one workgroup holds the whole loop; it has no rounds)");
-    if (k > 0 && h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_refinement: the handle was created with IPM_FLAG_LOCKSTEP (the rounds have no batched twins)");
-    h->ref_k = k;
-    return IPM_OK;
-}
+extern "C" int ipm_set_refinement(ipm_handle* h, int32_t k) { return rounds_set(h, &ipm_handle::ref, REF_KIND, k); }
 extern "C" int ipm_debug_get_refine_vector(ipm_handle* h, int32_t which, double* out, int64_t capacity, int64_t* count) {
     if (!h || !count || which < 0 || which > 4) return fail(h, IPM_ERR_INVALID_ARG, "ipm_debug_get_refine_vector: bad arguments");
     *count = h->mp;
     if (!out || capacity < h->mp) return IPM_OK;
-    if (which < 3 && !h->ref_mem) return fail(h, IPM_ERR_STATE, "ipm_debug_get_refine_vector: the handle never ran a refinement round");
-    const RefViews v = h->ref_mem ? ref_views(h) : RefViews{};
+    if (which < 3 && !h->ref.mem) return fail(h, IPM_ERR_STATE, "ipm_debug_get_refine_vector: the handle never ran a refinement round");
+    const RefViews v = h->ref.mem ? ref_views(h) : RefViews{};
     const double* src = which == 0 ? v.t : which == 1 ? v.r : which == 2 ? v.delta : which == 3 ? h->dy : h->dya;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipMemcpyAsync(out, src, sizeof(double) * h->mp, hipMemcpyDeviceToHost, h->stream));
@@ -468,8 +446,8 @@ extern "C" int ipm_debug_get_refine_vector(ipm_handle* h, int32_t which, double*
 }
 extern "C" int ipm_get_refinement_info(ipm_handle* h, double out[8]) {
     if (!h || !out) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_refinement_info: bad arguments");
-    const RefCtl& c = h->ref_host;                              // the host copy the last call that read the scalar record took
-    out[0] = h->ref_k; out[1] = (double)c.solves; out[2] = (double)c.applied; out[3] = (double)c.half; out[4] = (double)c.reverts;
+    const RefCtl& c = h->ref.host;                              // the host copy the last call that read the scalar record took
+    out[0] = h->ref.k; out[1] = (double)c.solves; out[2] = (double)c.applied; out[3] = (double)c.half; out[4] = (double)c.reverts;
     out[5] = c.first_rel; out[6] = c.last_rel; out[7] = c.max_rel;
     return IPM_OK;
 }
@@ -526,6 +504,44 @@ static void launch_small_start(bool bounded, hipStream_t S, const SmallItem* one
     else { if (one) hipLaunchKernelGGL(small_start_bounded_kernel, g, b, 0, S, one->lp, one->bd); else hipLaunchKernelGGL(small_start_batch_bounded_kernel, g, b, 0, S, d_items); }
 }
 
+// Mehrotra's starting point of a multi-kernel handle, enqueued on the handle's stream (ipm_init_state_mehrotra):
+// A A^T formed with d = 1, factored with the handle's guard and shift and the group inverses built as ipm_normal_solve(h, NULL, ...)
+// does, then  u = (A A^T)^-1 b, x = A^T u  and  y = (A A^T)^-1 (A c), s = c - A^T y  from the device copies of b and c, then the
+// shifts and the balance (vector_ops.h, start_*).  The guarded-pivot count of the factorization stays in sc->fixed.  Never part of a
+// recorded lockstep program (the handle joins its batch afterwards).
+static int enqueue_mehrotra_start(ipm_handle* h) {
+    int rc;
+    const unsigned gn = (unsigned)((h->n + 255) / 256);
+    hipLaunchKernelGGL(fill_kernel, dim3(gn), dim3(256), 0, h->stream, h->d, (int)h->n, 1.0);
+    if ((rc = enqueue_form(h, h->d))) return rc;
+    if ((rc = enqueue_factor(h))) return rc;
+    if ((rc = enqueue_group_inverses(h))) return rc;
+    const VecArgs va = vec_args(h);
+    const dim3 g(h->vblk), b(VBLK);
+    // x = A^T (A A^T)^-1 b   (the padding rows of b are zero, and stay zero through the solve)
+    HIP_TRY(h, hipMemcpyAsync(h->t1, h->b, sizeof(double) * h->mp, hipMemcpyDeviceToDevice, h->stream));
+    if ((rc = enqueue_normal_solve(h, h->t1, h->dy, h->atp, /*refine=*/false))) return rc;
+    if (h->bnd) hipLaunchKernelGGL(start_primal_bounded_kernel, g, b, 0, h->stream, va, bnd_args(h));
+    else hipLaunchKernelGGL(start_primal_kernel, g, b, 0, h->stream, va);
+    // y = (A A^T)^-1 (A c), s = c - A^T y
+    launch_gemv_n(h, h->c, 1.0, 0.0, nullptr, h->t1);
+    if ((rc = enqueue_normal_solve(h, h->t1, h->dy, h->atp, /*refine=*/false))) return rc;
+    if (h->bnd) {
+        const BndArgs bd = bnd_args(h);
+        hipLaunchKernelGGL(start_dual_bounded_kernel, g, b, 0, h->stream, va, bd);
+        hipLaunchKernelGGL(start_shift_bounded_kernel, g, b, 0, h->stream, va, bd);
+        hipLaunchKernelGGL(start_primal_correct_bounded_kernel, g, b, 0, h->stream, va, bd);
+        hipLaunchKernelGGL(start_dual_correct_bounded_kernel, g, b, 0, h->stream, va, bd);
+    } else {
+        hipLaunchKernelGGL(start_dual_kernel, g, b, 0, h->stream, va);
+        hipLaunchKernelGGL(start_shift_kernel, g, b, 0, h->stream, va);
+        hipLaunchKernelGGL(start_primal_correct_kernel, g, b, 0, h->stream, va);
+        hipLaunchKernelGGL(start_dual_correct_kernel, g, b, 0, h->stream, va);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return IPM_OK;
+}
+
 // what every entry that sets a new iterate leaves in the handle (ipm_init_state, ipm_set_state)
 static void mark_fresh_state(ipm_handle* h) {
     h->haveState = true; h->predictor_valid = false; h->fresh_state = true;
@@ -560,8 +576,8 @@ extern "C" int ipm_iterate(ipm_handle* h, int32_t n_steps, ipm_stats* stats) {
     int rc = check_ready(h, "ipm_iterate");
     if (rc) return rc;
     if (n_steps < 0) return fail(h, IPM_ERR_INVALID_ARG, "n_steps < 0");
-    if ((rc = mcc_check_path(h, "ipm_iterate"))) return rc;
-    if ((rc = ref_check_path(h, "ipm_iterate"))) return rc;
+    if ((rc = rounds_check_path(h, h->mcc, "ipm_iterate"))) return rc;
+    if ((rc = rounds_check_path(h, h->ref, "ipm_iterate"))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     h->predictor_valid = false;
     std::vector<hipEvent_t> evs;
@@ -589,8 +605,8 @@ extern "C" int ipm_iterate(ipm_handle* h, int32_t n_steps, ipm_stats* stats) {
     for (int attempt = 0;; ++attempt) {
         hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, h->stream, h->sc, 1e-8, 1e-8, 1e-8, h->opt.eta, 1 << 30, 1,
                            attempt == 0 ? reset_k : 0);
-        if ((rc = mcc_start(h, attempt == 0 && reset_k))) return rc;
-        if ((rc = ref_start(h, attempt == 0 && reset_k))) return rc;
+        if ((rc = rounds_start(h, h->mcc, attempt == 0 && reset_k))) return rc;
+        if ((rc = rounds_start(h, h->ref, attempt == 0 && reset_k))) return rc;
         const bool guard_poll = may_poll(h) && n_steps > 0;
         if (guard_poll && (rc = enqueue_snapshot(h, 0))) return rc;
         HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
@@ -634,14 +650,14 @@ extern "C" int ipm_solve(ipm_handle* h, double tol_p, double tol_d, double tol_g
     int rc = check_ready(h, "ipm_solve");
     if (rc) return rc;
     if (max_iter < 0) return fail(h, IPM_ERR_INVALID_ARG, "max_iter < 0");
-    if ((rc = mcc_check_path(h, "ipm_solve"))) return rc;
-    if ((rc = ref_check_path(h, "ipm_solve"))) return rc;
+    if ((rc = rounds_check_path(h, h->mcc, "ipm_solve"))) return rc;
+    if ((rc = rounds_check_path(h, h->ref, "ipm_solve"))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     h->predictor_valid = false; h->fresh_state = false;
     if (h->auto_reg) { h->auto_reg = 0; h->shift_rel = h->opt.regularize; }      // decided per solve
     hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, h->stream, h->sc, tol_p, tol_d, tol_gap, h->opt.eta, max_iter, 0, 1);
-    if ((rc = mcc_start(h, true))) return rc;
-    if ((rc = ref_start(h, true))) return rc;
+    if ((rc = rounds_start(h, h->mcc, true))) return rc;
+    if ((rc = rounds_start(h, h->ref, true))) return rc;
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     const int chunk = h->opt.check_every;
     const bool may_auto = h->opt.regularize == 0.0 && !(h->opt.flags & IPM_FLAG_NO_AUTO_REGULARIZE);

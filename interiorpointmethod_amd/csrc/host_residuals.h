@@ -6,9 +6,11 @@ static void launch_gemv_n(ipm_handle* h, const double* v, double sa, double sb, 
     if (h->sparse) launch_twin<LS_SPMV_CSR>(h, (unsigned)((h->mp + 15) / 16), {sparse_view(h), (int)h->mp, v, sa, sb, add, out, solve_done(h)}, st);
     else launch_untwinned(h, gemv_n_kernel, dim3((unsigned)(h->mp / 4)), dim3(256), st, h->A, h->np, (int)h->mp, (int)h->np, v, sa, sb, add, out, solve_done(h));
 }
-static void launch_gemv_t(ipm_handle* h, const double* u, hipStream_t st = nullptr) {
-    if (h->sparse) launch_twin<LS_SPMV_CSC_T>(h, (unsigned)((h->np + 15) / 16), {sparse_view(h), (int)h->np, u, h->atp, solve_done(h)}, st);
-    else launch_untwinned(h, gemv_t_kernel, dim3((unsigned)((h->np + 511) / 512), (unsigned)h->rc_chunks), dim3(256), st, h->A, h->np, h->rows_per_chunk, (int)h->np, u, h->atp, solve_done(h));
+// A^T u as partials [rc_chunks][np], into `part` (the handle's own, h->atp, unless the caller names another buffer of that shape)
+static void launch_gemv_t(ipm_handle* h, const double* u, hipStream_t st = nullptr, double* part = nullptr) {
+    if (!part) part = h->atp;
+    if (h->sparse) launch_twin<LS_SPMV_CSC_T>(h, (unsigned)((h->np + 15) / 16), {sparse_view(h), (int)h->np, u, part, solve_done(h)}, st);
+    else launch_untwinned(h, gemv_t_kernel, dim3((unsigned)((h->np + 511) / 512), (unsigned)h->rc_chunks), dim3(256), st, h->A, h->np, h->rows_per_chunk, (int)h->np, u, part, solve_done(h));
 }
 // The same pass (dense A) over the row chunks [chunk0, chunk1) only: gemv_t_kernel on the sub-range of A, u and the partials, so it
 // writes exactly the partials the full launch writes for those chunks -- each chunk is one workgroup row's own sum, in the same
@@ -91,7 +93,7 @@ static int enqueue_residual_stream(ipm_handle* h, hipStream_t chain) {
 static bool overlap_residuals(const ipm_handle* h) {
     return h->stream3 != nullptr && h->profiling < 2;          // (created for dense handles from 16 blocks on, ipm_create)
 }
-// Is A^T dy streamed behind the backward sweeps (enqueue_solve_direction)?  Dense handles with a residual stream and grouped sweeps,
+// Is A^T dy streamed behind the backward sweeps (enqueue_normal_solve)?  Dense handles with a residual stream and grouped sweeps,
 // on the fused and the serial factor path alike.  Its pieces sit behind device-polled gates, so the rule of every other polled
 // hand-off holds: only while the handle polls and is alone on its device (polls_device; wants_polling is what may_poll takes the
 // roll-back snapshot by), never after a recovered time-out (poll_fallback), never while a lockstep program is being recorded.

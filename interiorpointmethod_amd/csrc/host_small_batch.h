@@ -43,6 +43,9 @@ static int small_batch_round(ipm_handle* h0, ipm_handle** hs, const std::vector<
     return IPM_OK;
 }
 
+template <class R> static int small_batch_check_rounds(const char* who, int i, const R& r) {      // a round feature with k > 0
+    return r.k > 0 ? fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d has %d %s set; the small-LP kernel runs %s", who, i, r.k, r.kind->noun, r.kind->none) : IPM_OK;
+}
 // the argument rules both batch entries share: n, the array, and per handle NULL / not on the small path / another device / twice
 static int small_batch_check_handles(const char* who, ipm_handle** hs, int32_t n) {
     if (n < 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: n = %d < 0", who, (int)n);
@@ -52,8 +55,8 @@ static int small_batch_check_handles(const char* who, ipm_handle** hs, int32_t n
         ipm_handle* h = hs[i];
         if (!h) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d is NULL", who, i);
         if (!h->small) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d is not on the fused small-LP path (sparse A of at most %d rows; ipm_get_schedule out[9])", who, i, SMALL_MAX_M);
-        if (h->mcc_k > 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d has %d centrality correctors set; the small-LP kernel runs no rounds", who, i, h->mcc_k);
-        if (h->ref_k > 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d has %d refinement rounds set; the small-LP kernel runs none", who, i, h->ref_k);
+        int rc;
+        if ((rc = small_batch_check_rounds(who, i, h->mcc)) || (rc = small_batch_check_rounds(who, i, h->ref))) return rc;
         if (h->device != hs[0]->device) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: handle %d lives on device %d, handle 0 on device %d", who, i, h->device, hs[0]->device);
     }
     {   // the same handle twice: two workgroups would race on one state

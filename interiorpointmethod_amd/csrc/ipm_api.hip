@@ -323,7 +323,7 @@ extern "C" int ipm_destroy(ipm_handle* h) {
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->h_sc) { std::lock_guard<std::mutex> lock(g_hsc_mutex); g_hsc_pool.push_back(h->h_sc); h->h_sc = nullptr; }
-    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->mcc_mem, (void*)h->ref_mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
+    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->mcc.mem, (void*)h->ref.mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
         dev_free(h->device, h->stream, p);
     ff_release(h);
     free_sparse_factor(h);
@@ -630,7 +630,7 @@ extern "C" int ipm_normal_solve(ipm_handle* h, const double* d, const double* rh
                                 int32_t* pivots_fixed) {
     if (!h || !rhs || !z) return fail(h, IPM_ERR_INVALID_ARG, "ipm_normal_solve: bad arguments");
     if (!h->haveA) return fail(h, IPM_ERR_STATE, "ipm_normal_solve: A not set");
-    int rc = ref_check_path(h, "ipm_normal_solve");
+    int rc = rounds_check_path(h, h->ref, "ipm_normal_solve");
     if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     for (int attempt = 0;; ++attempt) {                     // second pass only after a recovered poll time-out
@@ -647,13 +647,9 @@ extern "C" int ipm_normal_solve(ipm_handle* h, const double* d, const double* rh
         }
         HIP_TRY(h, hipMemsetAsync(h->t1, 0, sizeof(double) * h->mp, h->stream));
         HIP_TRY(h, hipMemcpyAsync(h->t1, rhs, sizeof(double) * h->m, hipMemcpyHostToDevice, h->stream));
-        if ((rc = ref_start(h, true))) return rc;
-        if ((rc = refine_keep(h, h->t1))) return rc;
-        if ((rc = enqueue_potrs(h, h->t1, h->dy))) return rc;
-        if (h->ref_k > 0) {                                    // refinement against A diag(h->d) A^T: the rounds need A^T z (h->atp is free here)
-            launch_gemv_t(h, h->dy);
-            if ((rc = enqueue_refine(h, ref_views(h).t, h->dy))) return rc;
-        }
+        if ((rc = rounds_start(h, h->ref, true))) return rc;
+        // refinement against A diag(h->d) A^T: only its rounds need A^T z (h->atp is free here)
+        if ((rc = enqueue_normal_solve(h, h->t1, h->dy, h->ref.k > 0 ? h->atp : nullptr, /*refine=*/true))) return rc;
         bool tmo = false;
         if ((rc = read_scalars(h, &tmo))) return rc;
         if (!tmo) break;

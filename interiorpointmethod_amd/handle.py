@@ -53,32 +53,34 @@ def check_scale(scale):
     return scale
 
 
-def check_correctors(k):
-    """THE check of the `correctors` keyword, before any device is touched: an integer 0 .. MAX_CORRECTORS."""
-    if isinstance(k, bool) or int(k) != k or not 0 <= int(k) <= _lib.MAX_CORRECTORS:
-        raise ValueError("correctors must be an integer 0 .. %d, not %r" % (_lib.MAX_CORRECTORS, k))
+# THE table of the round options: keyword -> (its maximum, the library's setter, what the batch front ends lack).  One check, one
+# refusal and one setter body (IpmSolver._set_rounds) are built on it.
+ROUND_OPTIONS = {
+    "correctors": (_lib.MAX_CORRECTORS, "ipm_set_centrality_correctors", "centrality-corrector rounds"),
+    "refine": (_lib.MAX_REFINE, "ipm_set_refinement", "refinement rounds"),
+}
+
+
+def check_rounds(name, k):
+    """THE check of a round option's keyword, before any device is touched: an integer 0 .. its maximum."""
+    kmax = ROUND_OPTIONS[name][0]
+    if isinstance(k, bool) or int(k) != k or not 0 <= int(k) <= kmax:
+        raise ValueError("%s must be an integer 0 .. %d, not %r" % (name, kmax, k))
     return int(k)
 
 
-def refuse_correctors(k, who):
-    """THE refusal of the batch front ends, which have no corrector rounds (lockstep twins, the one-workgroup small kernel): the
-    option is checked like anywhere else and K > 0 raises instead of being dropped."""
-    if check_correctors(k):
-        raise ValueError("correctors=%d: %s runs no centrality-corrector rounds; solve such LPs one at a time" % (k, who))
+def refuse_rounds(name, k, who):
+    """THE refusal of the batch front ends, which have no rounds (lockstep twins, the one-workgroup small kernel): the option is
+    checked like anywhere else and k > 0 raises instead of being dropped."""
+    if check_rounds(name, k):
+        raise ValueError("%s=%d: %s runs no %s; solve such LPs one at a time" % (name, k, who, ROUND_OPTIONS[name][2]))
 
 
-def check_refine(k):
-    """THE check of the `refine` keyword, before any device is touched: an integer 0 .. MAX_REFINE."""
-    if isinstance(k, bool) or int(k) != k or not 0 <= int(k) <= _lib.MAX_REFINE:
-        raise ValueError("refine must be an integer 0 .. %d, not %r" % (_lib.MAX_REFINE, k))
-    return int(k)
-
-
-def refuse_refine(k, who):
-    """THE refusal of the batch front ends, which have no refinement rounds (lockstep twins, the one-workgroup small kernel): the
-    option is checked like anywhere else and k > 0 raises instead of being dropped."""
-    if check_refine(k):
-        raise ValueError("refine=%d: %s runs no refinement rounds; solve such LPs one at a time" % (k, who))
+# the four names their importers use (api.py, batch.py, batches.py, the tests): one-line wrappers
+def check_correctors(k): return check_rounds("correctors", k)                 # noqa: E704
+def check_refine(k): return check_rounds("refine", k)                         # noqa: E704
+def refuse_correctors(k, who): return refuse_rounds("correctors", k, who)     # noqa: E704
+def refuse_refine(k, who): return refuse_rounds("refine", k, who)             # noqa: E704
 
 
 RefineInfo = collections.namedtuple("RefineInfo", "k solves applied half_rule reverts first_rel last_rel max_first_rel")
@@ -326,12 +328,15 @@ class IpmSolver:
         self._check(self._lib.ipm_get_history(self._h, buf, _lib.HISTORY_CAPACITY, C.byref(n)))
         return [{k: getattr(buf[i], k) for k, _ in _lib.IterRecord._fields_} for i in range(n.value)]
 
+    def _set_rounds(self, name, k):        # the one body of set_correctors / set_refine; self.<name> changes only if the library accepts
+        k = check_rounds(name, k)
+        self._check(getattr(self._lib, ROUND_OPTIONS[name][1])(self._h, k))
+        setattr(self, name, k)
+
     def set_correctors(self, k):
         """ipm_set_centrality_correctors: up to k (0 .. MAX_CORRECTORS) centrality-corrector rounds per iteration from the next
-        iteration on.  The library refuses (IpmError) a solver on the fused small path and a lockstep solver; both stay usable."""
-        k = check_correctors(k)
-        self._check(self._lib.ipm_set_centrality_correctors(self._h, k))
-        self.correctors = k
+        iteration on.  The library refuses k > 0 (IpmError) on a solver on the fused small path and on a lockstep solver; both stay usable."""
+        self._set_rounds("correctors", k)
 
     def corrector_info(self):
         """ipm_get_corrector_info of the last solve() / iterate() sequence: dict with k, rounds (that did work), accepted (rounds)
@@ -343,10 +348,8 @@ class IpmSolver:
     def set_refine(self, k):
         """ipm_set_refinement: up to k (0 .. MAX_REFINE) rounds of iterative refinement behind every normal-equations solve -- the
         iteration's (predictor, corrector, centrality-corrector rounds) and normal_solve's; init_state_mehrotra is not refined.  The
-        library refuses (IpmError) a solver on the fused small path and a lockstep solver; both stay usable."""
-        k = check_refine(k)
-        self._check(self._lib.ipm_set_refinement(self._h, k))
-        self.refine = k
+        library refuses k > 0 (IpmError) on a solver on the fused small path and on a lockstep solver; both stay usable."""
+        self._set_rounds("refine", k)
 
     def refine_info(self):
         """ipm_get_refinement_info of the last solve() / iterate() sequence (or normal_solve), in the order of the C array: a

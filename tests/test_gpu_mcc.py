@@ -24,8 +24,8 @@ K = 0 is the old code: a handle on which set_correctors(0) was called and an unt
 Repeatability and the overlapped path: dense 2048 x 2304 (16 blocks: residual stream, streamed A^T dy for Mehrotra's two solves) with
 K = 3 -- iterate(4) twice from the same state, and once more under IPM_STREAM_AT=0, all bit-identical.
 Residue: fresh handles on memory filled with 0x00, 0xFF and left alone give the same bytes with K = 3.
-Refusals: a small-path handle and a lockstep handle raise from set_correctors(1) and stay usable; the batch front ends raise
-ValueError.
+Refusals: a small-path handle and a lockstep handle raise from set_correctors(1), accept set_correctors(0) and stay usable; the
+batch front ends raise ValueError; a handle moved to the small path after K > 0 is refused by iterate / solve until K = 0.
 
 End to end (K = 2 at eta = 0.91 and 0.995, tests/golden/dense_syn_256x512.npz and GROW22 with native bounds from Mehrotra's start):
 status converged, the returned iterate passes the stop test recomputed in longdouble at the solve's tolerances, and the objective
@@ -39,6 +39,7 @@ E(k,i) = ||(y_k, z_k)|| rp_i + rd_k ||x_i||, hence c.x_1 - c.x_2 >= -(gap_2 + E(
     |c.x_1 - c.x_2| <= e3 + 2 e1 (1 + ||(b, u_U)||) max_k ||(y_k, z_k)|| + 2 e2 (1 + ||c||) max_i ||x_i||
 Iteration counts are printed (ITERS lines), not asserted.
 """
+import ctypes as C
 import os
 
 import numpy as np
@@ -205,8 +206,8 @@ def test_rounds_repeat_bitwise_on_the_overlapped_path(monkeypatch):
 # ---- the candidate vectors are written before they are read (the rule of tests/test_gpu_residue.py) ------------------------------
 @pytest.mark.parametrize("name,as_sparse", [("dense/130x257b", False), ("sparse/129x16385", True)])
 def test_rounds_do_not_depend_on_what_memory_held(name, as_sparse, monkeypatch):
-    """mcc_mem (11 n-vectors, dy_g, the candidate's partial minima) is the library's own allocation, cleared whole on first use
-    (mcc_ensure: the padding of v_g is read by the product with A).  Fresh handles with IPM_TEST_ALLOC_FILL = 0, 255 (NaN as doubles)
+    """mcc.mem (11 n-vectors, dy_g, the candidate's partial minima) is the library's own allocation, cleared whole on first use
+    (rounds_ensure: the padding of v_g is read by the product with A).  Fresh handles with IPM_TEST_ALLOC_FILL = 0, 255 (NaN as doubles)
     and unset give the same bytes after iterate(3) with K = 3, rejected rounds included, and the 255 run is finite."""
     case = M.get(name)
     out = []
@@ -233,6 +234,7 @@ def test_small_path_and_lockstep_handles_refuse_and_stay_usable():
         with pytest.raises(_lib.IpmError, match="small"):
             sv.set_correctors(1)
         assert sv.correctors == 0 and sv.corrector_info()["k"] == 0
+        sv.set_correctors(0)                                     # (k = 0 is accepted on every handle)
         sv.set_state(*small.state())
         assert sv.iterate(1)["iterations"] == 1
     with pytest.raises(_lib.IpmError, match="small"):
@@ -241,6 +243,7 @@ def test_small_path_and_lockstep_handles_refuse_and_stay_usable():
     with _solver(lock, as_sparse=True, lockstep=True, factor="dense") as sv:
         with pytest.raises(_lib.IpmError, match="LOCKSTEP"):
             sv.set_correctors(1)
+        sv.set_correctors(0)
         sv.set_state(*lock.state())
         assert ipm.lockstep_eligible(sv)
         with pytest.raises(ValueError, match="correctors"):
@@ -251,6 +254,33 @@ def test_small_path_and_lockstep_handles_refuse_and_stay_usable():
         ipm.solve_small_batch([(sparse.csc_matrix(small.A), small.b, small.c)], correctors=1)
     with pytest.raises(ValueError, match="correctors"):
         ipm.IpmSolver(lock.A, lock.b, lock.c, correctors=_lib.MAX_CORRECTORS + 1)
+
+
+def test_handle_moved_to_the_small_path_refuses_until_k_is_0():
+    """The mirror of the last block of test_gpu_refine.test_refusals, with its 128 x 600 pair (ipm_set_A_csc decides the path: 600 dense
+    columns of 128 rows are past the product-list cap of the one-workgroup kernel, the sparse matrix of the same shape is not): a
+    handle that went onto the small path after K > 0 is refused by the solve entries until set_correctors(0), which it accepts."""
+    rng = np.random.default_rng(3)
+    m, n = 128, 600
+    Ab = rng.standard_normal((m, n))
+    Ab[:, :m] += 4.0 * np.eye(m)
+    cols = np.arange(m, n)
+    Asm = sparse.csc_matrix((np.ones(m + 2 * cols.size), (np.concatenate([np.arange(m), cols % m, (7 * cols + 1) % m]),
+                                                          np.concatenate([np.arange(m), cols, cols]))), shape=(m, n))
+    Asm.sort_indices()
+    with ipm.IpmSolver(sparse.csc_matrix(Ab), Ab @ np.ones(n), np.ones(n), reorder=None, correctors=1) as sv:
+        assert sv.schedule()["fused_small"] == 0 and sv._perm is None
+        indptr, indices, data = Asm.indptr.astype(np.int32), Asm.indices.astype(np.int32), Asm.data.astype(np.float64)
+        sv._check(sv._lib.ipm_set_A_csc(sv._h, indptr.ctypes.data_as(C.POINTER(C.c_int32)), indices.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        data.ctypes.data_as(C.POINTER(C.c_double)), int(data.shape[0])))
+        assert sv.schedule()["fused_small"] == 1 and sv.corrector_info()["k"] == 1
+        sv.init_state(1.0)
+        for call in (lambda: sv.iterate(1), lambda: sv.solve(max_iter=2)):
+            with pytest.raises(_lib.IpmError, match="small"):
+                call()
+        sv.set_correctors(0)
+        assert sv.correctors == 0 and sv.corrector_info()["k"] == 0
+        assert sv.iterate(1)["iterations"] == 1
 
 
 # ---- end to end ------------------------------------------------------------------------------------------------------------

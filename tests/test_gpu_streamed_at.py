@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the streamed A^T dy (csrc/host_iteration.h: enqueue_solve_direction): the pass over A behind the
+"""GPU tests (-m gpu) of the streamed A^T dy (csrc/host_iteration.h: enqueue_normal_solve): the pass over A behind the
 predictor's and the corrector's backward sweep is cut into row-chunk pieces that run on the residual stream as the sweep makes
 their rows of dy final, released through a progress word that the sweep's own kernels store.  It is an overlap of work that stays
 the same, so the checker is the handle with the switch off (IPM_STREAM_AT=0: one pass behind the sweep) and the bound is EQUALITY,

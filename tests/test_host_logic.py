@@ -306,3 +306,22 @@ def test_bench_dump_outputs_float64_capped_and_seeded(tmp_path, monkeypatch):
     assert a1.size + b1.size <= 1000 and a1.size == 750 and b1.size == 250
     assert np.all(np.diff(a1) > 0) and np.all(np.isin(a1, big["a"]))          # positions sorted, values taken as they are
     assert np.array_equal(a1, np.load(tmp_path / "r2" / "a.npy")) and np.array_equal(b1, np.load(tmp_path / "r2" / "b.npy"))
+
+
+@pytest.mark.parametrize("name", ["correctors", "refine"])
+def test_round_option_table(name):
+    """handle.ROUND_OPTIONS: both round options take their check, their refusal and their wrappers from the one table."""
+    from interiorpointmethod_amd import handle
+    kmax = handle.ROUND_OPTIONS[name][0]
+    check, refuse = getattr(handle, "check_" + name), getattr(handle, "refuse_" + name)
+    for bad in (True, 1.5, -1, kmax + 1):
+        with pytest.raises(ValueError, match="^%s must be an integer 0 .. %d" % (name, kmax)):
+            check(bad)
+        with pytest.raises(ValueError, match="^%s must be an integer" % name):
+            refuse(bad, "the lockstep batch")
+    for ok in (0, kmax, float(kmax)):
+        assert check(ok) == ok and type(check(ok)) is int
+    for who in ("the lockstep batch", "the small-LP batch"):
+        assert refuse(0, who) is None
+        with pytest.raises(ValueError, match="^%s=%d: %s runs no .*rounds; solve such LPs one at a time$" % (name, kmax, who)):
+            refuse(kmax, who)

@@ -204,3 +204,17 @@ def test_entry_point_refuses_bad_arguments_without_a_device(built_lib):
         assert b"outside 0 .. 8" in lib.ipm_last_error(None)
     out = (C.c_int64 * 4)()
     assert lib.ipm_get_corrector_info(None, out) == err
+
+
+@pytest.mark.parametrize("setter,kmax", [("ipm_set_centrality_correctors", _lib.MAX_CORRECTORS), ("ipm_set_refinement", _lib.MAX_REFINE)])
+def test_both_round_setters_share_the_argument_rules_without_a_device(built_lib, setter, kmax):
+    """The one statement of the setters' argument rules (host_iteration.h, rounds_set): NULL and the range, in messages that name the
+    call; the range check comes first (it reads nothing of the handle)."""
+    lib = _lib.load()
+    call, err = getattr(lib, setter), -1                             # IPM_ERR_INVALID_ARG
+    for k in (0, 1, kmax):
+        assert call(None, k) == err
+        assert lib.ipm_last_error(None) == ("%s: NULL handle" % setter).encode()
+    for k in (-1, kmax + 1):
+        assert call(None, k) == err
+        assert lib.ipm_last_error(None) == ("%s: k = %d outside 0 .. %d" % (setter, k, kmax)).encode()
