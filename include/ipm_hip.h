@@ -431,9 +431,42 @@ int ipm_get_refinement_info(ipm_handle* h, double out[8]);
  * t, 1 the residual r, 2 the correction delta (IPM_ERR_STATE on a handle that never ran a round), 3 the handle's dy (corrector,
  * ipm_normal_solve), 4 its predictor dy (tests/test_gpu_refine.py). */
 int ipm_debug_get_refine_vector(ipm_handle* h, int32_t which, double* out, int64_t capacity, int64_t* count);
-/* B = A diag(d) A^T (d on the host, length n); full symmetric m x m written to host B. */
+/* Dense columns split out of the sparse factor.  A column of A with many entries puts a full clique into A A^T and
+ * the sparse factor fills up.  With the set DC of such columns named here (count <= IPM_MAX_DENSE_COLS distinct indices 0 .. n-1, in
+ * any order), the NEXT ipm_set_A_csc builds the symbolic analysis, the product list of the formation and the sparse factor from A
+ * without them, B_s = A_s D A_s^T = L L^T (pivot guard and Tikhonov shift apply to B_s as they do to B without a split), and every
+ * factorization is followed by V = A_DC diag(sqrt(d_DC)), W = L^-1 V (one batched walk of the panel tree) and the Cholesky factor R
+ * of S = I + W^T W; every solve B^-1 t then runs z = L^-1 t, z -= W S^-1 W^T z, L^-T z (Sherman-Morrison-Woodbury), for every caller
+ * of a solve: the iteration with its corrector, centrality-corrector and refinement rounds, ipm_normal_solve, ipm_init_state_mehrotra,
+ * bounded and infeasibility-detecting handles.  Products with A, residuals, A^T dy and the refinement residual keep the full A, which
+ * is what stabilises the split: the bare formulas lose every digit of a whole solve near the optimum, where the rows that only basic
+ * dense columns support leave B_s nearly singular.  So the library factors B_s + 1e-10 diag(V V^T) and runs at least two refinement
+ * rounds (ipm_set_refinement's, against the full A D A^T) behind every refined solve of a split handle; ipm_set_refinement(h, k < 2)
+ * on such a handle sets 2, and ipm_get_refinement_info reports it.  count = 0 clears the set (cols may be
+ * NULL): the next ipm_set_A_csc builds the handle exactly as without this call.  A set given after ipm_set_A_csc waits for the next one.
+ * IPM_ERR_INVALID_ARG, with the reason in ipm_last_error and the set the handle held kept, for: a NULL handle, count < 0 or
+ * count > IPM_MAX_DENSE_COLS, and with count > 0 a handle without IPM_FLAG_SPARSE_FACTOR (or without sparse_nnz), a handle of
+ * m <= 128 rows (the fused small path), a handle created with IPM_FLAG_LOCKSTEP, an index out of range or given twice.  A set whose
+ * removal leaves a row of A empty is refused by ipm_set_A_csc (IPM_ERR_INVALID_ARG; the handle keeps the A it had).  Buffers are the
+ * library's own allocation; the workspace sizes do not change.  Results are bitwise repeatable and do not depend on IPM_SP_MODE,
+ * IPM_SP_GRID or IPM_SP_FUSE_FWD. */
+#define IPM_MAX_DENSE_COLS 64
+int ipm_set_dense_columns(ipm_handle* h, int32_t count, const int32_t* cols);
+/* out[0] k, the dense columns of the split in place (0: none, and every other word is 0), [1] k padded to a multiple of 16, [2] row
+ * chunks of the Gram and correction kernels, [3] entries of L stored with the split, [4] the same without it when known (the library
+ * orders one of the two: 0; the Python host fills it in when it ordered both), [5] factorizations that built W and R, [6] corrections
+ * applied, both since ipm_set_A_csc, [7] 0. */
+int ipm_get_dense_split_info(ipm_handle* h, int64_t out[8]);
+/* Test hook of the split (IPM_ERR_STATE without one): which = 0 V, 1 W (m x k, column-major, the handle's row order), 2 R (k x k,
+ * row-major, zeros above the diagonal), 3 the column list (k values), as left by the last factorization; 4: L^-1 V computed again
+ * by this call, one column at a time with the stock forward sweep of the sparse factor (what W must equal bit for bit).  *count = the number of
+ * doubles; nothing is copied when out is NULL or capacity < *count (tests/test_gpu_dense_split.py). */
+int ipm_debug_get_dense_split(ipm_handle* h, int32_t which, double* out, int64_t capacity, int64_t* count);
+/* B = A diag(d) A^T (d on the host, length n); full symmetric m x m written to host B -- the FULL B also on a handle with a
+ * dense-column split. */
 int ipm_form_normal_matrix(ipm_handle* h, const double* d, double* B, int64_t ldb);
-/* Cholesky factor of the handle's current normal matrix; lower triangle to host L. */
+/* Cholesky factor of the handle's current normal matrix; lower triangle to host L.  On a handle with a dense-column split
+ * (ipm_set_dense_columns) this is the factor of B_s + 1e-10 diag(V V^T), B_s = A_s D A_s^T the matrix without the dense columns, not of B. */
 int ipm_get_factor(ipm_handle* h, double* L, int64_t ldl);
 /* Timing of the device phases of the last ipm_iterate call, milliseconds per iteration:
  * out[0]=form A D^2 A^T, out[1]=factor, out[2]=triangular solves, out[3]=everything else.

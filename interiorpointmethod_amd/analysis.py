@@ -133,6 +133,76 @@ def _factor_path(A, m, factor):
     return dense
 
 
+# THE selection rule of the dense-column split, stated once: a column is dense when it has more than
+# max(DENSE_COL_FRAC * m, DENSE_COL_FLOOR) entries.  Fixed by a host survey of the standard-form Netlib fixtures (tests/golden): with
+# 0.1 and 30 the rule takes 22 columns of FIT1P (m = 1026; nnz(A A^T) / m^2 0.37 -> 0.017 without them), 14 of SEBA (1029; 0.10 ->
+# 0.003) and 22 of ISRAEL (174; 0.74 -> 0.12), leaves no row of the three empty, and takes nothing from the files whose A A^T is
+# sparse already.  The floor keeps a small LP (0.1 m below 30) from calling its ordinary columns dense.
+DENSE_COL_FRAC = 0.1
+DENSE_COL_FLOOR = 30
+MAX_DENSE_COLS = _lib.MAX_DENSE_COLS
+
+
+def dense_columns(A, max_cols=MAX_DENSE_COLS, frac=DENSE_COL_FRAC, floor=DENSE_COL_FLOOR):
+    """The columns of sparse A to split out of the sparse factor (IpmSolver(dense_cols=...)) -> ascending int32 indices: those
+    with more than max(frac * m, floor) entries, the densest first (ties: the lower index) up to max_cols <= MAX_DENSE_COLS, and
+    never one whose removal, with the ones already taken, would leave a row of A without an entry.  Host only."""
+    if not 0 <= int(max_cols) <= MAX_DENSE_COLS:
+        raise ValueError("max_cols must be 0 .. %d, not %r" % (MAX_DENSE_COLS, max_cols))
+    if not _is_sparse(A):
+        return np.zeros(0, dtype=np.int32)
+    A = _sp.csc_matrix(A)
+    m = A.shape[0]
+    cnt = np.diff(A.indptr)
+    cand = np.flatnonzero(cnt > max(frac * m, floor))
+    cand = cand[np.lexsort((cand, -cnt[cand]))]
+    left = np.bincount(A.indices, minlength=m)          # entries a row keeps
+    out = []
+    for j in cand:
+        if len(out) >= int(max_cols):
+            break
+        rows = A.indices[A.indptr[j]:A.indptr[j + 1]]
+        if (left[rows] <= 1).any():
+            continue
+        left[rows] -= 1
+        out.append(int(j))
+    return np.asarray(sorted(out), dtype=np.int32)
+
+
+def check_dense_cols(dense_cols, n):
+    """THE host check of an explicit dense_cols sequence -> int32 array: distinct indices 0 .. n-1, at most MAX_DENSE_COLS."""
+    cols = np.asarray(dense_cols).reshape(-1)
+    if cols.size and not np.issubdtype(cols.dtype, np.integer):
+        raise ValueError("dense_cols must be None, \"auto\" or a sequence of column indices")
+    cols = cols.astype(np.int64)
+    if cols.size > MAX_DENSE_COLS:
+        raise ValueError("dense_cols: %d columns exceed the %d the split takes" % (cols.size, MAX_DENSE_COLS))
+    if cols.size and (cols.min() < 0 or cols.max() >= n):
+        raise ValueError("dense_cols: column index out of range 0 .. %d" % (n - 1))
+    if np.unique(cols).size != cols.size:
+        raise ValueError("dense_cols: duplicated column index")
+    return cols.astype(np.int32)
+
+
+def refuse_dense_cols(dense_cols, who):
+    """THE refusal of the front ends without a split (lockstep twins, the one-workgroup small kernel): the option raises, it is
+    never dropped."""
+    if dense_cols is not None:
+        raise ValueError("dense_cols=%r: %s has no dense-column split; solve such LPs one at a time" % (dense_cols, who))
+
+
+def without_columns(A, cols):
+    """Canonical CSC of A with the columns `cols` emptied (same shape): the matrix the sparse factor is built from under a split."""
+    A = _sp.csc_matrix(A)
+    keep = np.ones(A.shape[1], dtype=bool)
+    keep[cols] = False
+    cnt = np.diff(A.indptr)
+    entry = np.repeat(keep, cnt)
+    indptr = np.concatenate(([0], np.cumsum(np.where(keep, cnt, 0)))).astype(A.indptr.dtype)
+    As = _sp.csc_matrix((A.data[entry], A.indices[entry], indptr), shape=A.shape)
+    return As
+
+
 def path_flops(A, factor=None, want_info=False):
     """(path, Cholesky flops, flops of the four triangular sweeps) of one iteration AS THE DEVICE RUNS IT for this A under
     IpmSolver's factor rule: the sparse factor costs sum over columns of (entries of the column)^2 and 4 nnz(L); the
@@ -182,7 +252,7 @@ class Prepared:
     IpmSolver(..., prepared=P) takes it.  (Computing it AHEAD of the solves on helper threads in the batched mode was tried and
     is slower -- 14.55 -> 13.2 LPs/s on the 73-LP suite: the helpers' SciPy sections hold the interpreter lock the eight
     worker threads need between their library calls.)"""
-    __slots__ = ("host", "A", "b", "c", "m", "n", "factor", "order_info", "perm", "ub")
+    __slots__ = ("host", "A", "b", "c", "m", "n", "factor", "order_info", "perm", "ub", "dense_cols", "unsplit_info")
 
 
 def _upper_bounds(ub, n):
@@ -206,8 +276,44 @@ def _apply_row_order(A, b, perm):           # sparse A and b with device row i =
     return A, np.ascontiguousarray(b[perm])
 
 
-def prepare(A, b, c, dense=False, reorder="auto", factor=None, ub=None):
-    """Host-only part of IpmSolver.__init__ (no device is touched) -> Prepared.  ub: native upper bounds (see IpmSolver)."""
+def _split_factor_path(P, A, factor, dense_cols):
+    """The factor rule of prepare under dense_cols -> (path, perm, info); sets P.dense_cols (and P.unsplit_info, the ipm_order_rows
+    record of the unsplit A, where the host ordered both)."""
+    auto = isinstance(dense_cols, str)
+    if auto and dense_cols != "auto":
+        raise ValueError('dense_cols must be None, "auto" or a sequence of column indices, not %r' % (dense_cols,))
+    cols = None if auto else check_dense_cols(dense_cols, P.n)
+    if cols is not None and (not _is_sparse(A) or factor == "dense" or P.m <= FUSED_SMALL_MAX_ROWS):
+        if cols.size:
+            raise ValueError("dense_cols needs a sparse A of more than %d rows on the sparse factor" % FUSED_SMALL_MAX_ROWS)
+        P.dense_cols = cols          # the empty set: IpmSolver clears the handle's set explicitly (ipm_set_dense_columns(h, 0, NULL))
+        return _factor_path(A, P.m, factor)
+    if auto:
+        path = _factor_path(A, P.m, factor)
+        if path[0] == "sparse" or not _is_sparse(A) or factor == "dense" or P.m <= FUSED_SMALL_MAX_ROWS:
+            return path
+        cols = dense_columns(A)
+        if not cols.size:
+            return path
+        P.unsplit_info = path[2]
+    elif not cols.size:
+        P.dense_cols = cols
+        return _factor_path(A, P.m, factor)
+    split = _factor_path(without_columns(A, cols), P.m, factor)
+    if split[0] == "sparse":
+        P.dense_cols = cols
+        return split
+    if auto:
+        return path
+    raise ValueError("dense_cols: A without these columns does not go on the sparse factor (factor=%r)" % (factor,))
+
+
+def prepare(A, b, c, dense=False, reorder="auto", factor=None, ub=None, dense_cols=None):
+    """Host-only part of IpmSolver.__init__ (no device is touched) -> Prepared.  ub: native upper bounds (see IpmSolver).
+    dense_cols: None (default) no split; a sequence of column indices: those columns are split out of the sparse
+    factor, the factor rule and the row order see A without them, and the LP must end on the sparse factor (ValueError otherwise:
+    the option is never dropped); "auto": the split is taken only where the factor rule puts A on the dense path and A without
+    dense_columns(A) on the sparse factor.  P.dense_cols is the set in effect, or None (an empty array for an empty sequence)."""
     P = Prepared()
     if _is_sparse(A):
         A = _sp.csc_matrix(A, dtype=np.float64)
@@ -232,7 +338,11 @@ def prepare(A, b, c, dense=False, reorder="auto", factor=None, ub=None):
     factor = _factor_arg(factor)
     if factor not in ("auto", "dense", "sparse"):
         raise ValueError("factor must be 'auto', 'dense' or 'sparse'")
-    P.factor, P.perm, P.order_info = _factor_path(A, P.m, factor)
+    P.dense_cols, P.unsplit_info = None, None
+    if dense_cols is None:
+        P.factor, P.perm, P.order_info = _factor_path(A, P.m, factor)
+    else:
+        P.factor, P.perm, P.order_info = _split_factor_path(P, A, factor, dense_cols)
     if factor == "sparse" and P.perm is None and _is_sparse(A):
         raise ValueError("factor='sparse': A A^T is too dense for the sparse factor (ipm_order_rows)")
     if P.perm is None and _is_sparse(A) and reorder and (reorder == "rcm" or P.m >= REORDER_MIN_ROWS):

@@ -45,6 +45,7 @@ def _solve_info(solver, history=False, certificate=False):
     info["factor_path"] = solver.factor
     info["correctors"] = solver.corrector_info()
     info["refine"] = solver.refine_info()
+    info["dense_cols"] = solver.dense_split_info()          # None: no dense-column split ran
     if solver.scale is not None:
         info["scale"] = dict(solver.scale_info)
         info["rp_unscaled"], info["rd_unscaled"] = unscaled_residuals(solver)
@@ -79,7 +80,7 @@ def _auto_regularize():          # the process-wide switch of the 5 % rule (hand
 
 def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
                     history=False, ub=None, detect_infeasibility=False, device_start=False, scale=None, scale_passes=SCALE_PASSES,
-                    correctors=0, refine=0, **opts):
+                    correctors=0, refine=0, dense_cols=None, **opts):
     """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
     start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start(), or with
     device_start=True IpmSolver.init_state_mehrotra(): the same start computed on the device (no host copy of A, one
@@ -94,7 +95,9 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     correctors=K: up to K centrality-corrector rounds per iteration (IpmSolver.set_correctors; 0, the default: none);
     info["correctors"] = IpmSolver.corrector_info().  An LP on the fused small path refuses K > 0 (IpmError).
     refine=k: up to k rounds of iterative refinement behind every normal-equations solve (IpmSolver.set_refine; 0, the default:
-    none); info["refine"] = IpmSolver.refine_info().  An LP on the fused small path refuses k > 0 (IpmError)."""
+    none); info["refine"] = IpmSolver.refine_info().  An LP on the fused small path refuses k > 0 (IpmError).
+    dense_cols: None (default), "auto" or column indices: the dense-column split of the sparse factor (IpmSolver; DESIGN.md 4-D);
+    info["dense_cols"] = IpmSolver.dense_split_info() (None where no split ran)."""
     global _last_info
     correctors = check_correctors(correctors)
     refine = check_refine(refine)
@@ -102,6 +105,8 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
         raise ValueError('start must be "reference" or "mehrotra"')
     if check_scale(scale) is not None:
         opts = dict(opts, scale=scale, scale_passes=scale_passes)
+    if dense_cols is not None:
+        opts = dict(opts, dense_cols=dense_cols)
     ub = _upper_bounds(ub, np.asarray(c).reshape(-1).shape[0])
     on_device = start == "mehrotra" and device_start
     if start == "mehrotra" and not on_device and shift_allowed(opts.get("regularize"), _auto_regularize()):
@@ -137,11 +142,11 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     return x, y, s, info
 
 
-def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, **opts):
+def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, **opts):
     """min c^T x s.t. Ax=b, x>=0 (and x <= ub where ub is finite) by the Mehrotra predictor-corrector loop on the GPU
     -> (x, y, s)."""
     x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub, scale=scale,
-                                 scale_passes=scale_passes, correctors=correctors, refine=refine, **opts)
+                                 scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols, **opts)
     return x, y, s
 
 
@@ -154,12 +159,14 @@ def _verdict(info, value):
     return value
 
 
-def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0):
+def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0,
+                    dense_cols=None):
     """Drop-in for main.py:760-815: start x=s=y=1, cap 5000, returns sum(x*c) - cTlb.  detect_infeasibility=True: +inf for an
-    LP detected infeasible, -inf for one detected unbounded.  scale, correctors, refine: as solve_with_info (off by default)."""
+    LP detected infeasible, -inf for one detected unbounded.  scale, correctors, refine, dense_cols: as solve_with_info (off by
+    default)."""
     _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=5000, y0=1.0, device=device,
                                     detect_infeasibility=detect_infeasibility, scale=scale, scale_passes=scale_passes,
-                                    correctors=correctors, refine=refine)
+                                    correctors=correctors, refine=refine, dense_cols=dense_cols)
     return _verdict(info, info["objective"] - float(cTlb))
 
 

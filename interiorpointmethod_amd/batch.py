@@ -25,6 +25,7 @@ from . import _lib
 from .analysis import prepare
 from .api import _auto_regularize, _solve_info, solve_with_info
 from .batches import LockstepBatch, lockstep_eligible, small_batch_eligible, solve_small_batch_solvers
+from .analysis import refuse_dense_cols
 from .handle import SCALE_PASSES, IpmSolver, check_scale, mehrotra_started, refuse_correctors, refuse_refine
 
 # One record per LP.  The first nine fields are the statistics SURVEY.md 8e names; the rest make the library's hidden
@@ -95,18 +96,19 @@ def _guarded(solve_fn, problem, **kw):
 
 
 def solve_one(problem, device=0, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, concurrent=False, start="reference",
-              tol_gap=None, detect_infeasibility=False, device_start=False, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0):
+              tol_gap=None, detect_infeasibility=False, device_start=False, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0,
+              dense_cols=None):
     """Solve one LP (A, b, c) on `device` with the HIP path -> dict of statistics.  detect_infeasibility: the record's status
     may be 5 (primal infeasible) or 6 (dual infeasible, i.e. unbounded); DESIGN.md 4-C.  device_start: with start="mehrotra", the
     start is computed on the device (solve_with_info).  correctors: centrality-corrector rounds per iteration, refine: refinement
-    rounds per normal-equations solve (solve_with_info)."""
+    rounds per normal-equations solve, dense_cols: the dense-column split (solve_with_info)."""
     A, b, c = problem
     t0 = time.perf_counter()
     try:
         _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device,
                                         regularize=regularize, concurrent=concurrent, start=start, tol_gap=tol_gap,
                                         detect_infeasibility=detect_infeasibility, device_start=device_start, scale=scale,
-                                        scale_passes=scale_passes, correctors=correctors, refine=refine)
+                                        scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols)
         info = dict(info)
     except Exception as e:          # every failure becomes a record: the rank must still reach the all-gather
         _report_failure(A, e)
@@ -437,7 +439,8 @@ class _LockstepShard:
 
 
 def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, tol_gap=None,
-                         detect_infeasibility=False, small_batch=False, start="reference", scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, **_):
+                         detect_infeasibility=False, small_batch=False, start="reference", scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0,
+                         dense_cols=None, **_):
     """Solve problems[i] for i in ids on this rank's GPU with the LOCKSTEP BATCH -> (len(ids), NF) records.
 
     `workers` host threads prepare the LPs (host analysis, handle, upload), largest first.  An LP of more than 128 rows on the
@@ -461,9 +464,10 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
     a handle with different data, so the batches need nothing else.
 
     correctors > 0 raises ValueError: the centrality-corrector rounds have no batched twins (run_batch(lockstep=False) serves them);
-    refine > 0 likewise."""
+    refine > 0 likewise, and so does dense_cols (the split has no batched twins either)."""
     refuse_correctors(correctors, "the lockstep batch")
     refuse_refine(refine, "the lockstep batch")
+    refuse_dense_cols(dense_cols, "the lockstep batch")
     if start not in ("reference", "mehrotra"):
         raise ValueError('start must be "reference" or "mehrotra"')
     handle_kw = dict(device=device, regularize=regularize, concurrent=True, detect_infeasibility=detect_infeasibility)

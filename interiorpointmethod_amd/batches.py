@@ -6,6 +6,7 @@ import numpy as np
 from . import _lib
 from .analysis import FUSED_SMALL_MAX_ROWS, _sp, _upper_bounds
 from .api import _auto_regularize, _solve_info
+from .analysis import refuse_dense_cols
 from .handle import SCALE_PASSES, IpmSolver, _gap_tol, check_scale, refuse_correctors, refuse_refine, wants_shift
 
 
@@ -20,13 +21,14 @@ def _scatter_stats(solvers, stats):           # each solver takes its statistics
     return [sv.stats for sv in solvers]
 
 
-def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None, correctors=0, refine=0):
+def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None, correctors=0, refine=0, dense_cols=None):
     """ipm_solve_batch: solve the LPs of `solvers` (IpmSolver objects created with lockstep=True on one device, a state set) AT ONCE,
     iteration k of all of them in the same launches (csrc/lockstep.h) -> list of statistics dicts, one per solver.  Per-LP semantics
     and arithmetic are those of IpmSolver.solve on each of them alone (bit-identical iterates).  correctors > 0: ValueError (the rounds
     have no batched twins; a lockstep solver refuses set_correctors for the same reason); refine > 0 likewise."""
     refuse_correctors(correctors, "the lockstep batch")
     refuse_refine(refine, "the lockstep batch")
+    refuse_dense_cols(dense_cols, "the lockstep batch")          # (the split has no batched twins: ValueError, never dropped)
     hs, st = _handle_array(solvers)
     _lib.check(solvers[0]._h, _lib.load().ipm_solve_batch(hs, len(solvers), tol, tol, _gap_tol(tol, tol_gap), int(max_iter), st))
     return _scatter_stats(solvers, st)
@@ -95,7 +97,7 @@ def small_batch_eligible(solver):
     return bool(solver.schedule()["fused_small"])
 
 
-def solve_small_batch_solvers(solvers, tol=1e-8, max_iter=5000, tol_gap=None, stream=None, correctors=0, refine=0):
+def solve_small_batch_solvers(solvers, tol=1e-8, max_iter=5000, tol_gap=None, stream=None, correctors=0, refine=0, dense_cols=None):
     """ipm_solve_small_batch: solve the LPs of `solvers` (IpmSolver objects on the fused small-LP path, one device, a state set) in ONE
     launch per kernel variant, one workgroup per LP -> list of statistics dicts, one per solver (also in solver.stats).  Plain,
     bounded and detect_infeasibility solvers may be mixed.  Per-LP semantics and arithmetic are those of IpmSolver.solve on each of
@@ -105,6 +107,7 @@ def solve_small_batch_solvers(solvers, tol=1e-8, max_iter=5000, tol_gap=None, st
     correctors > 0 or refine > 0 (the one-workgroup kernel runs no centrality-corrector and no refinement rounds)."""
     refuse_correctors(correctors, "the small-LP batch")
     refuse_refine(refine, "the small-LP batch")
+    refuse_dense_cols(dense_cols, "the small-LP batch")          # (the one-workgroup kernel has no split: ValueError, never dropped)
     lib = _lib.load()
     solvers = list(solvers)
     if not solvers:
@@ -170,7 +173,7 @@ def _small_batch_host_check(problems, ub):
 
 
 def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, ub=None, detect_infeasibility=False,
-                      regularize=0.0, start="reference", scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0):
+                      regularize=0.0, start="reference", scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None):
     """Solve many small LPs at once -> list of (x, y, s, info), one per problem, each what solve_with_info returns for it alone.
 
     problems: list of (A, b, c) with at most 128 rows each; a dense A is converted to CSC.  ub: None or one entry per problem (None or
@@ -183,6 +186,7 @@ def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_g
     before any device is touched (solve_small_batch_solvers), and so for refine > 0."""
     refuse_correctors(correctors, "the small-LP batch")
     refuse_refine(refine, "the small-LP batch")
+    refuse_dense_cols(dense_cols, "the small-LP batch")          # (the one-workgroup kernel has no split: ValueError, never dropped)
     if start not in ("reference", "mehrotra"):
         raise ValueError('start must be "reference" or "mehrotra"')
     check_scale(scale)

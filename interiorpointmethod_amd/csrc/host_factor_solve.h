@@ -122,6 +122,34 @@ static int enqueue_group_inverses(ipm_handle* h, int g0 = 0, int g1 = -1, hipStr
     return IPM_OK;
 }
 
+// Dense-column split behind a factorization of B_s (dense_split.h): V from the handle's CSC copy of the dense columns
+// and the d the formation used (h->d at every call site), W = L^-1 V in ONE walk of the panel tree -- always the level form, one
+// launch per level whatever IPM_SP_MODE says: nothing spins, so the time-out machinery has nothing to cover -- then the Gram
+// partials and the Schur factor R.  k = 1: the walk runs sp_fwd_kernel itself on the split's update vectors.
+static int enqueue_dense_split_factor(ipm_handle* h) {
+    const DsSplit& s = h->dsp;
+    const int* done = h->spF.done;
+    hipLaunchKernelGGL(ds_scatter_kernel, dim3((unsigned)s.k), dim3(DS_THREADS), 0, h->stream, h->d_colptr, h->d_rowind, h->d_cval, h->d, s, done);
+    const int rm = std::max(16, h->sp_rmax);
+    SpFactor F = h->spF;
+    F.uvec = s.uvec;
+    sp_walk(h, /*by_level=*/true, /*leaves_first=*/true, [&](unsigned grid, const SpRec* recs, int count) {
+        if (s.k == 1) hipLaunchKernelGGL((sp_fwd_kernel<SPC_THREADS>), dim3(grid), dim3(SPC_THREADS), h->sp_lds_solve, h->stream, F, 0u, s.V, s.W, rm, recs, count);
+        else hipLaunchKernelGGL((ds_fwd_kernel<SPC_THREADS>), dim3(grid, (unsigned)s.k), dim3(SPC_THREADS), h->sp_lds_solve, h->stream, F, s, rm, recs, count);
+    });
+    hipLaunchKernelGGL(ds_gram_kernel, dim3((unsigned)s.nchunk), dim3(DS_THREADS), 0, h->stream, s, done);
+    hipLaunchKernelGGL(ds_schur_kernel, dim3(1), dim3(DS_THREADS), 0, h->stream, s, done);
+    ++h->ds_factorizations;
+    return IPM_OK;
+}
+// The correction of a solve between its sweeps: z -= W (R R^T)^-1 W^T z on z = L^-1 t.
+static void enqueue_dense_split_correction(ipm_handle* h, double* z) {
+    const DsSplit& s = h->dsp;
+    hipLaunchKernelGGL(ds_wtz_kernel, dim3((unsigned)s.nchunk), dim3(DS_THREADS), 0, h->stream, s, z, solve_done(h));
+    hipLaunchKernelGGL(ds_apply_kernel, dim3((unsigned)s.nchunk), dim3(DS_THREADS), 0, h->stream, s, z, solve_done(h));
+    ++h->ds_corrections;
+}
+
 // Multifrontal sparse Cholesky: one launch walks the elimination tree.
 // sp_fwd_rhs: right-hand side whose forward substitution rides on the factorization (z -> h->t2); the next enqueue_potrs of that
 // right-hand side then runs the backward sweep only (h->sp_fwd_fused).
@@ -134,6 +162,7 @@ static int enqueue_sparse_factor(ipm_handle* h, const double* sp_fwd_rhs) {
                            &h->sc->maxdiag, h->opt.pivot_guard_eps, h->opt.pivot_guard_big, h->shift_rel, &h->sc->fixed,
                            h->sp_lds_doubles, recs, count, sp_fwd_rhs, h->t2, h->sp_fv_off);
     });
+    if (h->ds_on) { if (int rc_ = enqueue_dense_split_factor(h)) return rc_; }
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
@@ -366,6 +395,7 @@ static int enqueue_potrs(ipm_handle* h, double* r, double* out, hipEvent_t wait_
         if (!fwd_done) sp_walk(h, by_level, /*leaves_first=*/true, [&](unsigned grid, const SpRec* recs, int count) {
             hipLaunchKernelGGL((sp_fwd_kernel<SPC_THREADS>), dim3(grid), dim3(SPC_THREADS), h->sp_lds_solve, h->stream, F, ep, r, h->t2, rm, recs, count);
         });
+        if (h->ds_on) enqueue_dense_split_correction(h, h->t2);      // (also behind a forward sweep that rode on the factorization)
         if (!by_level) ep = ++h->sp_epoch;                   // the level-mode sweeps share one epoch, task mode takes one per sweep
         sp_walk(h, by_level, /*leaves_first=*/false, [&](unsigned grid, const SpRec* recs, int count) {
             hipLaunchKernelGGL((sp_bwd_kernel<SPC_THREADS>), dim3(grid), dim3(SPC_THREADS), 0, h->stream, F, ep, h->t2, out, recs, count);

@@ -82,7 +82,7 @@ struct ipm_handle {
     int *sp_fptr = nullptr, *sp_fcol = nullptr;
     double* sp_fcoef = nullptr;
     long long* sp_diagpos = nullptr;
-    long long sp_nslot = 0, sp_nu = 0, sp_terms = 0;
+    long long sp_nslot = 0, sp_nu = 0, sp_terms = 0, sp_uvlen = 0;      // (sp_uvlen: doubles of the forward sweep's update vectors)
     int sp_height = 0, sp_rmax = 0, sp_grid = 1, sp_serial_launches = 0, sp_nvirtual = 0;
     size_t sp_lds_chol = 0, sp_lds_solve = 0;
     int sp_fv_off = 0;                    // doubles of sp_chol_kernel's dynamic LDS in front of the forward substitution's r-vector
@@ -94,6 +94,11 @@ struct ipm_handle {
     std::vector<int> sp_lvlptr;           // [levels + 1] into the level-ordered records
     SpRec* sp_rec_level = nullptr;
     unsigned sp_epoch = 0;
+    // dense columns split out of the sparse factor (ipm_set_dense_columns, dense_split.h)
+    std::vector<int> ds_cols;             // the set asked for, in the caller's order; ipm_set_A_csc builds the split from it
+    bool ds_on = false;                   // the sparse factor in place is that of A without those columns: W and R follow every factorization
+    DsSplit dsp;                          // device view (own allocations, freed with the sparse factor's)
+    long long ds_factorizations = 0, ds_corrections = 0;
     double shift_rel = 0.0;               // Tikhonov shift in effect (opt.regularize, or 1e-14 switched on by ipm_solve)
     int auto_reg = 0;                     // 1: the shift was switched on automatically
     unsigned* d_flags = nullptr;          // [2*nblk] hand-off flags + 1 timeout word + 1 progress word of the streamed A^T dy (own allocation)

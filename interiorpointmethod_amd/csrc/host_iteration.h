@@ -431,7 +431,10 @@ extern "C" int ipm_get_corrector_info(ipm_handle* h, int64_t out[4]) {
 }
 
 // ------------------------------------------------------------------------------- iterative refinement
-extern "C" int ipm_set_refinement(ipm_handle* h, int32_t k) { return rounds_set(h, &ipm_handle::ref, REF_KIND, k); }
+extern "C" int ipm_set_refinement(ipm_handle* h, int32_t k) {
+    if (h && h->ds_on && k >= 0 && k < DS_MIN_REFINE) k = DS_MIN_REFINE;      // a dense-column split keeps its own rounds
+    return rounds_set(h, &ipm_handle::ref, REF_KIND, k);
+}
 extern "C" int ipm_debug_get_refine_vector(ipm_handle* h, int32_t which, double* out, int64_t capacity, int64_t* count) {
     if (!h || !count || which < 0 || which > 4) return fail(h, IPM_ERR_INVALID_ARG, "ipm_debug_get_refine_vector: bad arguments");
     *count = h->mp;

@@ -6,6 +6,7 @@ static void free_sparse_factor(ipm_handle* h) {
     for (void* p : h->sp_allocs) dev_free(h->device, h->stream, p);
     h->sp_allocs.clear();
     h->spf = false;
+    h->ds_on = false;
 }
 
 template <class T>
@@ -48,8 +49,11 @@ static bool sym_cache_take(int m, int n, const std::vector<int>& cp, const std::
 
 // Symbolic analysis of A A^T in the given row order, task partition, product lists of the formation; everything the three
 // kernels of sparse_chol.h index with goes to the device once.  cp/ri/cv: canonical CSC of A; rp/ci/rv: its CSR.
+// diag_extra (dense-column split only): per row, further terms (column, coefficient) of its DIAGONAL entry, appended to the slot's list.
+typedef std::vector<std::vector<std::pair<int, double>>> SpDiagExtra;
 static int build_sparse_factor(ipm_handle* h, const std::vector<int>& cp, const std::vector<int>& ri, const std::vector<double>& cv,
-                               const std::vector<int>& rp, const std::vector<int>& ci, const std::vector<double>& rv) {
+                               const std::vector<int>& rp, const std::vector<int>& ci, const std::vector<double>& rv,
+                               const SpDiagExtra* diag_extra = nullptr) {
     free_sparse_factor(h);
     const int m = (int)h->m, n = (int)h->n;
     sym::Supernodes S;
@@ -149,6 +153,7 @@ static int build_sparse_factor(ipm_handle* h, const std::vector<int>& cp, const 
     {
         size_t terms = 0;
         for (int j = 0; j < n; ++j) { const size_t c = (size_t)(cp[j + 1] - cp[j]); terms += c * (c + 1) / 2; }
+        if (diag_extra) for (const auto& row : *diag_extra) terms += row.size();
         if (terms > ((size_t)1 << 30)) return fail(h, IPM_ERR_INVALID_ARG, "sparse factor: %zu products in A D^2 A^T (use the dense path)", terms);
         fcol.resize(terms); fcoef.resize(terms);
         std::vector<int> where((size_t)m, -1);
@@ -176,6 +181,13 @@ static int build_sparse_factor(ipm_handle* h, const std::vector<int>& cp, const 
                             const int64_t e = S.lptr[J] + (int64_t)a * w + b;
                             if (pass == 0) fptr[(size_t)e + 1]++;
                             else { const int t = nx[(size_t)e]++; fcol[(size_t)t] = j; fcoef[(size_t)t] = cv[q] * akj; }
+                        }
+                    }
+                    if (diag_extra) {                                            // (row k is row b of its own panel: own columns come first)
+                        const int64_t e = S.lptr[J] + (int64_t)b * w + b;
+                        for (const auto& term : (*diag_extra)[(size_t)k]) {
+                            if (pass == 0) fptr[(size_t)e + 1]++;
+                            else { const int t = nx[(size_t)e]++; fcol[(size_t)t] = term.first; fcoef[(size_t)t] = term.second; }
                         }
                     }
                 }
@@ -217,6 +229,7 @@ static int build_sparse_factor(ipm_handle* h, const std::vector<int>& cp, const 
     F.timeout = timeout_word(h);
     F.done = &h->sc->done;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->sp_uvlen = (long long)S.rows.size();
     h->sp_nslot = nslot; h->sp_nu = S.uptr[nsn]; h->sp_height = S.height; h->sp_rmax = S.rmax; h->sp_nvirtual = S.nvirtual;
     h->sp_lds_doubles = (int)std::max<int64_t>(std::max<int64_t>(16, S.panel_max), std::min<int64_t>((int64_t)S.rmax * S.rmax, SPC_FRONT));
     {   // LDS of the factorization kernel: the largest panel image with its padded row stride (sparse_chol.h: sp_chol_lds_need)
@@ -233,6 +246,7 @@ static int build_sparse_factor(ipm_handle* h, const std::vector<int>& cp, const 
         const int cap = 96 * 1024;
         if (h->sp_lds_solve > (size_t)cap || h->sp_lds_chol > (size_t)cap) return fail(h, IPM_ERR_INVALID_ARG, "sparse factor: a front of %d rows exceeds the LDS budget of the sweeps", S.rmax);
         HIP_TRY(h, hipFuncSetAttribute((const void*)sp_fwd_kernel<SPC_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+        HIP_TRY(h, hipFuncSetAttribute((const void*)ds_fwd_kernel<SPC_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
         HIP_TRY(h, hipFuncSetAttribute((const void*)sp_chol_kernel<SPC_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
     }
     {   // workgroups the chip holds at once: LDS- or wave-limited (32 waves per CU)
@@ -244,6 +258,98 @@ static int build_sparse_factor(ipm_handle* h, const std::vector<int>& cp, const 
     if (const char* e = getenv("IPM_SP_GRID")) h->sp_grid = std::max(1, std::min(ntask, atoi(e)));
     h->sp_epoch = 0; h->sp_serial = false;
     h->spf = true;
+    return IPM_OK;
+}
+
+// ------------------------------------------------------------------------------- dense columns (dense_split.h)
+// The buffers of the split behind a sparse factor that build_sparse_factor made from A WITHOUT the columns h->ds_cols: the handle's
+// own stream-ordered allocations, freed with the factor's (the workspace sizes do not change).
+static int build_dense_split(ipm_handle* h) {
+    DsSplit& s = h->dsp;
+    memset(&s, 0, sizeof s);
+    s.k = (int)h->ds_cols.size(); s.kp = (s.k + 15) / 16 * 16; s.m = (int)h->m;
+    s.rows = ds_chunk_rows(h->m); s.nchunk = (int)((h->m + s.rows - 1) / s.rows);
+    s.uvlen = h->sp_uvlen;
+    int rc;
+    int* d_cols = nullptr;
+    if ((rc = sp_upload(h, h->ds_cols, &d_cols))) return rc;
+    s.cols = d_cols;
+    if ((rc = sp_alloc_zero(h, (size_t)s.m * s.k, &s.V))) return rc;
+    if ((rc = sp_alloc_zero(h, (size_t)s.m * s.k, &s.W))) return rc;
+    if ((rc = sp_alloc_zero(h, (size_t)s.uvlen * s.k, &s.uvec))) return rc;
+    if ((rc = sp_alloc_zero(h, (size_t)s.nchunk * s.kp * s.kp, &s.gpart))) return rc;
+    if ((rc = sp_alloc_zero(h, (size_t)s.kp * s.kp, &s.R))) return rc;
+    if ((rc = sp_alloc_zero(h, (size_t)s.nchunk * s.kp, &s.upart))) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->ds_factorizations = 0; h->ds_corrections = 0;
+    h->ds_on = true;
+    return IPM_OK;
+}
+
+extern "C" int ipm_set_dense_columns(ipm_handle* h, int32_t count, const int32_t* cols) {
+    if (!h || count < 0 || (count > 0 && !cols)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_dense_columns: bad arguments");
+    if (count == 0) { h->ds_cols.clear(); return IPM_OK; }
+    if (count > IPM_MAX_DENSE_COLS) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_dense_columns: %d columns exceed IPM_MAX_DENSE_COLS = %d", (int)count, IPM_MAX_DENSE_COLS);
+    if (!h->sparse || !(h->opt.flags & IPM_FLAG_SPARSE_FACTOR)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_dense_columns: the handle has no sparse factor (IPM_FLAG_SPARSE_FACTOR on a sparse handle)");
+    if (h->m <= SMALL_MAX_M) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_dense_columns: a handle of m <= %d rows runs the fused small path, which has no split", SMALL_MAX_M);
+    if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_dense_columns: a lockstep handle has no split (its kernels have no batched twins)");
+    std::vector<char> seen((size_t)h->n, 0);
+    for (int32_t t = 0; t < count; ++t) {
+        if (cols[t] < 0 || cols[t] >= h->n) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_dense_columns: column index %d out of range", (int)cols[t]);
+        if (seen[(size_t)cols[t]]) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_dense_columns: column index %d is duplicated", (int)cols[t]);
+        seen[(size_t)cols[t]] = 1;
+    }
+    h->ds_cols.assign(cols, cols + count);
+    return IPM_OK;
+}
+
+extern "C" int ipm_get_dense_split_info(ipm_handle* h, int64_t out[8]) {
+    if (!h || !out) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_dense_split_info: bad arguments");
+    for (int t = 0; t < 8; ++t) out[t] = 0;
+    if (!h->ds_on) return IPM_OK;
+    out[0] = h->dsp.k; out[1] = h->dsp.kp; out[2] = h->dsp.nchunk; out[3] = h->sp_nslot;
+    out[5] = h->ds_factorizations; out[6] = h->ds_corrections;
+    return IPM_OK;
+}
+
+extern "C" int ipm_debug_get_dense_split(ipm_handle* h, int32_t which, double* out, int64_t capacity, int64_t* count) {
+    if (!h || !count || which < 0 || which > 4) return fail(h, IPM_ERR_INVALID_ARG, "ipm_debug_get_dense_split: bad arguments");
+    if (!h->ds_on) return fail(h, IPM_ERR_STATE, "ipm_debug_get_dense_split: the handle has no dense-column split");
+    const DsSplit& s = h->dsp;
+    const int64_t k = s.k;
+    *count = (which < 2 || which == 4) ? (int64_t)s.m * k : which == 2 ? k * k : k;
+    if (!out || capacity < *count) return IPM_OK;
+    if (which == 3) { for (int64_t t = 0; t < k; ++t) out[t] = (double)h->ds_cols[(size_t)t]; return IPM_OK; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (which == 4) {           // L^-1 V again, one column at a time with the stock sp_fwd_kernel (level form), into a buffer of its own
+        double* tmp = nullptr;
+        HIP_TRY(h, dev_malloc(h->device, h->stream, (void**)&tmp, sizeof(double) * (size_t)*count));
+        SpFactor F = h->spF;
+        F.uvec = s.uvec;        // (column 0's slice as scratch: the next factorization rewrites it)
+        F.done = nullptr;
+        const int rm = std::max(16, h->sp_rmax);
+        const size_t nlev = h->sp_lvlptr.empty() ? 0 : h->sp_lvlptr.size() - 1;
+        for (int64_t j = 0; j < k; ++j)
+            for (size_t l = 0; l < nlev; ++l) {
+                const int cnt = h->sp_lvlptr[l + 1] - h->sp_lvlptr[l];
+                hipLaunchKernelGGL((sp_fwd_kernel<SPC_THREADS>), dim3((unsigned)std::min(cnt, h->sp_grid)), dim3(SPC_THREADS), h->sp_lds_solve, h->stream, F, 0u,
+                                   s.V + j * s.m, tmp + j * s.m, rm, h->sp_rec_level + h->sp_lvlptr[l], cnt);
+            }
+        hipError_t e = hipMemcpyAsync(out, tmp, sizeof(double) * (size_t)*count, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        dev_free(h->device, h->stream, tmp);
+        if (e != hipSuccess) return fail(h, IPM_ERR_HIP, "ipm_debug_get_dense_split: %s", hipGetErrorString(e));
+        return IPM_OK;
+    }
+    if (which < 2) {
+        HIP_TRY(h, hipMemcpyAsync(out, which == 0 ? s.V : s.W, sizeof(double) * (size_t)*count, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return IPM_OK;
+    }
+    std::vector<double> R((size_t)s.kp * s.kp);
+    HIP_TRY(h, hipMemcpyAsync(R.data(), s.R, sizeof(double) * R.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int64_t i = 0; i < k; ++i) for (int64_t j = 0; j < k; ++j) out[i * k + j] = R[(size_t)(i * s.kp + j)];
     return IPM_OK;
 }
 
@@ -338,6 +444,16 @@ extern "C" int ipm_set_A_csc(ipm_handle* h, const int32_t* colptr, const int32_t
             cp[j + 1] = (int)ri.size();
         }
         const int64_t nz = (int64_t)ri.size();
+        const bool split = !h->ds_cols.empty() && (h->opt.flags & IPM_FLAG_SPARSE_FACTOR);      // (ipm_set_dense_columns refused m <= 128)
+        std::vector<char> is_dense;
+        if (split) {            // A without the dense columns must keep every row: B_s would be singular by structure
+            is_dense.assign((size_t)h->n, 0);
+            for (int j : h->ds_cols) is_dense[(size_t)j] = 1;
+            std::vector<int> left((size_t)h->m, 0);
+            for (int64_t j = 0; j < h->n; ++j) if (!is_dense[(size_t)j]) for (int q = cp[j]; q < cp[j + 1]; ++q) left[(size_t)ri[q]]++;
+            for (int64_t i = 0; i < h->m; ++i)
+                if (!left[(size_t)i]) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_A_csc: taking the dense columns out empties row %lld of A (ipm_set_dense_columns)", (long long)i);
+        }
         if (nz > h->nnz_cap) return fail(h, IPM_ERR_INVALID_ARG, "nnz %lld exceeds the handle's sparse_nnz %lld", (long long)nz, (long long)h->nnz_cap);
         if (int rc_ = eq_reset(h)) return rc_;               // a valid new A: the handle is unscaled again (host_equilibrate.h)
         std::vector<int> rp(h->m + 1, 0), ci((size_t)nz); std::vector<double> rv((size_t)nz);
@@ -458,7 +574,28 @@ extern "C" int ipm_set_A_csc(ipm_handle* h, const int32_t* colptr, const int32_t
             }
         }
         if ((h->opt.flags & IPM_FLAG_SPARSE_FACTOR) && !h->small) {      // (m <= 128: the fused single-workgroup kernel serves the LP)
-            int rc = build_sparse_factor(h, cp, ri, cv, rp, ci, rv);
+            int rc;
+            if (split) {
+                // A_s: the same n columns with the dense ones emptied, so that the product list indexes the full d; everything
+                // else (products with A, residuals, A^T dy, the refinement residual) keeps the full A uploaded above
+                // B_s also takes DS_DIAG_REL times the DIAGONAL of the dense columns' own term V V^T (dense_split.h): near the optimum
+                // the rows that only basic dense columns support would leave B_s with pivots the size of the vanishing d
+                std::vector<int> cps(cp.size(), 0), ris, rps(rp.size(), 0), cis; std::vector<double> cvs, rvs;
+                SpDiagExtra extra((size_t)h->m);
+                for (int64_t i = 0; i < h->m; ++i)
+                    for (int q = rp[i]; q < rp[i + 1]; ++q) if (is_dense[(size_t)ci[q]]) extra[(size_t)i].emplace_back(ci[q], DS_DIAG_REL * rv[q] * rv[q]);
+                for (int64_t j = 0; j < h->n; ++j) {
+                    if (!is_dense[(size_t)j]) for (int q = cp[j]; q < cp[j + 1]; ++q) { ris.push_back(ri[q]); cvs.push_back(cv[q]); }
+                    cps[(size_t)j + 1] = (int)ris.size();
+                }
+                for (int64_t i = 0; i < h->m; ++i) {
+                    for (int q = rp[i]; q < rp[i + 1]; ++q) if (!is_dense[(size_t)ci[q]]) { cis.push_back(ci[q]); rvs.push_back(rv[q]); }
+                    rps[(size_t)i + 1] = (int)cis.size();
+                }
+                rc = build_sparse_factor(h, cps, ris, cvs, rps, cis, rvs, &extra);
+                if (!rc) rc = build_dense_split(h);
+                if (!rc && h->ref.k < DS_MIN_REFINE) h->ref.k = DS_MIN_REFINE;      // the split's own refinement rounds
+            } else rc = build_sparse_factor(h, cp, ri, cv, rp, ci, rv);
             if (rc) { h->haveA = false; return rc; }
         }
         return IPM_OK;

@@ -30,6 +30,7 @@
 #include "small_lp.h"
 #include "sparse_chol.h"
 #include "sparse_symbolic.h"
+#include "dense_split.h"
 #include "vector_ops.h"
 #include "refine_ops.h"
 #include "form_factor.h"

@@ -189,7 +189,7 @@ def _ray_native(F, v):
 
 def new_interior_sparse(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None, tol=1e-20, device=0,
                         return_info=False, start="reference", bounds="fold", detect_infeasibility=False, scale=None, scale_passes=_solver.SCALE_PASSES,
-                        correctors=0, refine=0):
+                        correctors=0, refine=0, dense_cols=None):
     """Drop-in for main.py:1081-1245: convert to standard form, run the predictor-corrector loop on the GPU
     (e1 = e2 = tol, e3 = 1e-6, at most 999 iterations, x = y = s = 1), return the objective.
     bounds="fold" (default, the reference's way): every finite upper bound becomes a row and a slack column of A.
@@ -201,14 +201,16 @@ def new_interior_sparse(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, 
     x_original: the ray on the original variables (unbounded), and, for bounds="native", x and z over the get_Abc columns.
     scale="ruiz": the standard-form LP is equilibrated on the device first (solve_with_info; off by default).
     correctors=K: centrality-corrector rounds, as solve_with_info (0, the default: none).
-    refine=k: refinement rounds behind every normal-equations solve, as solve_with_info (0, the default: none)."""
+    refine=k: refinement rounds behind every normal-equations solve, as solve_with_info (0, the default: none).
+    dense_cols: the dense-column split on the standard-form LP that is solved ("auto", or indices into ITS columns), as
+    solve_with_info (None, the default: none)."""
     if bounds not in ("fold", "native"):
         raise ValueError('bounds must be "fold" or "native"')
     if bounds == "native":
         F = native_form(c, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=lb, ub=ub)
         x, _, _, info = _solver.solve_with_info(F.A, F.b, F.c, tol=tol, tol_gap=1e-6, max_iter=999, y0=1.0, device=device,
                                                 start=start, ub=F.u, detect_infeasibility=detect_infeasibility, scale=scale,
-                                                scale_passes=scale_passes, correctors=correctors, refine=refine)
+                                                scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols)
         info["fixed_removed"] = int(F.fixed.size)
         info["x"] = F.x_original(x)
         offset = F.offset
@@ -221,7 +223,7 @@ def new_interior_sparse(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, 
         _, _, _, info = _solver.solve_with_info(A, b, cs, tol=tol, tol_gap=1e-6, max_iter=999, y0=1.0, device=device,
                                                 start=start,            # start="mehrotra": optional, not the reference's
                                                 detect_infeasibility=detect_infeasibility, scale=scale, scale_passes=scale_passes,
-                                                correctors=correctors, refine=refine)
+                                                correctors=correctors, refine=refine, dense_cols=dense_cols)
         cert = info.get("certificate")
         if cert is not None:
             n0 = np.asarray(c).reshape(-1).shape[0]

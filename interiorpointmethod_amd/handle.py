@@ -96,7 +96,7 @@ class IpmSolver:
     def __init__(self, A, b, c, device=0, eta=0.91, pivot_guard_eps=1e-30, pivot_guard_big=1e64,
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
                  auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
-                 infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0):
+                 infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None):
         """check_every: solve() enqueues that many iterations at a time and reads the stop flag once per chunk (the launches behind a
         satisfied stop test return at entry, so the result does not depend on it: DESIGN.md 4-A); a lockstep batch runs chunks of the
         largest value among its members.  IPM_CHECK_EVERY in the environment, when set and not empty, OVERRIDES this argument for
@@ -113,14 +113,25 @@ class IpmSolver:
         correctors: up to that many of Gondzio's centrality-corrector rounds per iteration re-use its factorization (set_correctors;
         DESIGN.md 4-G).  0, the default, is the iteration without them, exactly.
         refine: up to that many rounds of iterative refinement behind every normal-equations solve, against the matrix-free
-        A D^2 A^T (set_refine).  0, the default, is the iteration without them, exactly."""
+        A D^2 A^T (set_refine).  0, the default, is the iteration without them, exactly.
+        dense_cols: None (default: no split), "auto" or a sequence of column indices -- the dense-column split of the sparse factor
+        (analysis.prepare, ipm_set_dense_columns; DESIGN.md 4-D).  self.dense_cols is the set in effect (None: none);
+        dense_split_info() reports it.  A lockstep solver refuses it (ValueError)."""
         self.scale = check_scale(scale)
         correctors = check_correctors(correctors)
         refine = check_refine(refine)
+        if lockstep and dense_cols is not None:
+            raise ValueError("dense_cols=%r: a lockstep solver has no dense-column split; solve such LPs one at a time" % (dense_cols,))
         if prepared is None:
-            prepared = prepare(A, b, c, dense=dense, reorder=reorder, factor=factor, ub=ub)
+            prepared = prepare(A, b, c, dense=dense, reorder=reorder, factor=factor, ub=ub, dense_cols=dense_cols)
         elif ub is not None:
             raise ValueError("pass ub to prepare() when a Prepared is given")
+        elif dense_cols is not None:
+            raise ValueError("pass dense_cols to prepare() when a Prepared is given")
+        self.dense_cols = getattr(prepared, "dense_cols", None)          # (an empty array: the handle's set is cleared explicitly, below)
+        self._unsplit_info = getattr(prepared, "unsplit_info", None)
+        if lockstep and self.dense_cols is not None and len(self.dense_cols):
+            raise ValueError("a lockstep solver has no dense-column split (the Prepared carries dense_cols); solve such LPs one at a time")
         lib = _lib.load()
         self._lib = lib
         self._h = None
@@ -172,6 +183,15 @@ class IpmSolver:
             indptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
             indices = np.ascontiguousarray(A.indices, dtype=np.int32)
             data = np.ascontiguousarray(A.data, dtype=np.float64)
+            if self.dense_cols is not None:
+                cols = np.ascontiguousarray(self.dense_cols, dtype=np.int32)
+                try:
+                    self._check(lib.ipm_set_dense_columns(h, int(cols.shape[0]), cols.ctypes.data_as(C.POINTER(C.c_int32))))
+                except Exception:
+                    self.close()
+                    raise
+                if not cols.shape[0]:
+                    self.dense_cols = None
             self._check(lib.ipm_set_A_csc(h, indptr.ctypes.data_as(C.POINTER(C.c_int32)),
                                           indices.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(data),
                                           int(data.shape[0])))
@@ -209,6 +229,8 @@ class IpmSolver:
         self.stats = None
         self.correctors = 0
         self.refine = 0
+        if self.dense_cols is not None:
+            self.refine = self.refine_info().k          # a split handle runs refinement rounds of its own
         try:
             if correctors:
                 self.set_correctors(correctors)
@@ -331,6 +353,8 @@ class IpmSolver:
     def _set_rounds(self, name, k):        # the one body of set_correctors / set_refine; self.<name> changes only if the library accepts
         k = check_rounds(name, k)
         self._check(getattr(self._lib, ROUND_OPTIONS[name][1])(self._h, k))
+        if name == "refine" and self.dense_cols is not None:
+            k = self.refine_info().k          # (a split handle keeps at least its own two rounds)
         setattr(self, name, k)
 
     def set_correctors(self, k):
@@ -400,6 +424,33 @@ class IpmSolver:
         keys = ("panels", "tasks", "height", "widest_front", "factor_entries", "update_entries", "product_terms",
                 "serial_launches")
         return dict(zip(keys, (int(v) for v in out)))
+
+    def dense_split_info(self):
+        """ipm_get_dense_split_info: dict with k (dense columns of the split in place), k_padded, row_chunks, factor_entries (of L
+        with the split), factor_entries_unsplit (ipm_order_rows' count for the unsplit A where prepare ordered both, else 0),
+        factorizations and corrections (since A was set); None for a solver without a split."""
+        out = (C.c_int64 * 8)()
+        self._check(self._lib.ipm_get_dense_split_info(self._h, out))
+        if not out[0]:
+            return None
+        d = dict(zip(("k", "k_padded", "row_chunks", "factor_entries", "factor_entries_unsplit", "factorizations", "corrections"),
+                     (int(v) for v in out)))
+        if self._unsplit_info:
+            d["factor_entries_unsplit"] = int(self._unsplit_info["nnz_factor"])
+        return d
+
+    def debug_dense_split(self, which):
+        """ipm_debug_get_dense_split (test hook): "V" or "W" as (m, k) arrays in the DEVICE's row order, "R" (k, k) lower
+        triangular, "cols" the column list, "W_stock" W recomputed column by column with the stock forward sweep."""
+        idx = ("V", "W", "R", "cols", "W_stock").index(which)
+        n = C.c_int64(0)
+        self._check(self._lib.ipm_debug_get_dense_split(self._h, idx, None, 0, C.byref(n)))
+        out = np.empty(n.value)
+        self._check(self._lib.ipm_debug_get_dense_split(self._h, idx, _dptr(out), n.value, C.byref(n)))
+        k = len(self.dense_cols)
+        if idx < 2 or idx == 4:
+            return out.reshape(k, self.m).T.copy()
+        return out.reshape(k, k) if idx == 2 else out.astype(np.int64)
 
     def set_profiling(self, level=2):
         """0 off, 1 time the A D^2 A^T kernel only, 2 all phases (True == 2 for old callers)."""
