@@ -220,6 +220,28 @@ int ipm_set_bounds(ipm_handle* h, const double* u);
 int ipm_set_bound_state(ipm_handle* h, const double* w, const double* z);
 int ipm_get_bound_state(ipm_handle* h, double* w, double* z);
 
+/* ---- separable convex QP: min c^T x + 1/2 x^T diag(g) x, g >= 0 -------- */
+/* g: host array of length n; the call needs only n, so it may come before ipm_set_A_*.  g == NULL (or all zeros) removes the term,
+ * and the handle then runs exactly the LP code.  NaN, Inf or negative entries: IPM_ERR_INVALID_INPUT, and the handle keeps what it
+ * held.  The normal matrix stays A Theta A^T with Theta = (S/X + Z/W + G)^-1, so every factorization path serves the handle: dense
+ * (the fused launch included), sparse on the envelope factor and with IPM_FLAG_SPARSE_FACTOR, bounded or not, with
+ * ipm_set_refinement and with a dense-column split.  The dual residual is A^T y + s - z - c - g o x, the objective in ipm_stats
+ * and the history is c^T x + 1/2 x^T diag(g) x, the stop test is unchanged, and the iteration takes ONE step length: alpha_p ==
+ * alpha_d and alpha_aff_p == alpha_aff_d (the minimum of the pair) in ipm_stats and the history.  The vector is allocated by the
+ * library on first use and freed by ipm_destroy; the workspace size does not change.  Invalidates a pending predictor.
+ * Never the fused small-LP path: ipm_set_A_csc does not choose it for a handle that holds a term, and a nonzero g on a handle
+ * already on that path is IPM_ERR_INVALID_ARG (set the term before A); clearing is always accepted.
+ * Refused with IPM_ERR_INVALID_ARG and a reason in ipm_last_error, never dropped: a nonzero g on an IPM_FLAG_LOCKSTEP handle (no
+ * batched twins), on an IPM_FLAG_DETECT_INFEASIBILITY handle (the tests are not restated for a QP) and on a handle with
+ * ipm_set_centrality_correctors(k > 0) (their accept rule compares step pairs); ipm_set_centrality_correctors(k > 0) refuses a
+ * handle that holds a term.  ipm_init_state_mehrotra runs on such a handle and IGNORES g (the LP's start).
+ * Scaled handle (ipm_equilibrate): g enters as g C^2 and leaves as g' / C^2, exact; an entry the factors push out of the normal
+ * fp64 range is IPM_ERR_INVALID_INPUT, here and in ipm_equilibrate, which rescales a g already set; ipm_set_A_* return it to the
+ * caller's units as they do u. */
+int ipm_set_quadratic(ipm_handle* h, const double* g);
+/* g (length n, the caller's units; zeros when no term is set) and the number of its positive entries; either may be NULL. */
+int ipm_get_quadratic(ipm_handle* h, double* g, int64_t* nonzeros);
+
 /* ---- equilibration: power-of-two Ruiz row / column scaling -------------- */
 /* Scale the handle's LP on the device to R A C, R b, C c, u / C with diagonal R, C whose entries are exact powers of two, so that
  * scaling and unscaling introduce no rounding at all.  Rule (csrc/equilibrate.h): simultaneous Ruiz passes on |A| in the infinity

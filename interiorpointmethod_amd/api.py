@@ -15,7 +15,8 @@ import numpy as np
 
 from . import _lib
 from .analysis import _upper_bounds
-from .handle import SCALE_PASSES, STATUS_NAMES, IpmSolver, check_correctors, check_refine, check_scale, mehrotra_started, shift_allowed, wants_shift
+from .handle import (SCALE_PASSES, STATUS_NAMES, IpmSolver, check_correctors, check_quadratic, check_refine, check_scale, mehrotra_started,
+                     refuse_quadratic, shift_allowed, wants_shift)
 
 
 def _info(solver, cTlb=0.0):
@@ -46,6 +47,7 @@ def _solve_info(solver, history=False, certificate=False):
     info["correctors"] = solver.corrector_info()
     info["refine"] = solver.refine_info()
     info["dense_cols"] = solver.dense_split_info()          # None: no dense-column split ran
+    info["quadratic"] = solver.quadratic_nonzeros()         # positive entries of the quadratic term's diagonal (0: an LP)
     if solver.scale is not None:
         info["scale"] = dict(solver.scale_info)
         info["rp_unscaled"], info["rd_unscaled"] = unscaled_residuals(solver)
@@ -53,7 +55,7 @@ def _solve_info(solver, history=False, certificate=False):
 
 
 def unscaled_residuals(solver):
-    """The reference's relative residuals ||A x - b|| / (1 + ||b||) and ||A^T y + s - z - c|| / (1 + ||c||) (main.py:170-171) of the
+    """The reference's relative residuals ||A x - b|| / (1 + ||b||) and ||A^T y + s - z - c (- g o x)|| / (1 + ||c||) (main.py:170-171) of the
     iterate the solver RETURNS, against the caller's own data: what the stop test of a scaled solve meant in the caller's units.
     Host arithmetic on the arrays the solver already holds."""
     A, b, c = solver._host
@@ -62,6 +64,8 @@ def unscaled_residuals(solver):
     rd = np.asarray(A.T @ y).reshape(-1) + s - c
     if solver.bounded:
         rd = rd - solver.get_bound_state()[1].reshape(-1)
+    if solver.quadratic_nonzeros():
+        rd = rd - solver.quadratic() * x
     rp = np.asarray(A @ x).reshape(-1) - b
     return float(np.linalg.norm(rp) / (1.0 + np.linalg.norm(b))), float(np.linalg.norm(rd) / (1.0 + np.linalg.norm(c)))
 
@@ -80,7 +84,7 @@ def _auto_regularize():          # the process-wide switch of the 5 % rule (hand
 
 def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
                     history=False, ub=None, detect_infeasibility=False, device_start=False, scale=None, scale_passes=SCALE_PASSES,
-                    correctors=0, refine=0, dense_cols=None, **opts):
+                    correctors=0, refine=0, dense_cols=None, quad=None, **opts):
     """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
     start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start(), or with
     device_start=True IpmSolver.init_state_mehrotra(): the same start computed on the device (no host copy of A, one
@@ -97,7 +101,10 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     refine=k: up to k rounds of iterative refinement behind every normal-equations solve (IpmSolver.set_refine; 0, the default:
     none); info["refine"] = IpmSolver.refine_info().  An LP on the fused small path refuses k > 0 (IpmError).
     dense_cols: None (default), "auto" or column indices: the dense-column split of the sparse factor (IpmSolver; DESIGN.md 4-D);
-    info["dense_cols"] = IpmSolver.dense_split_info() (None where no split ran)."""
+    info["dense_cols"] = IpmSolver.dense_split_info() (None where no split ran).
+    quad: None (default) or the diagonal g >= 0 of a separable quadratic term: min c.x + 1/2 x.diag(g) x (IpmSolver; DESIGN.md
+    4-Q); info["quadratic"] = its positive entries, info["objective"] includes the term.  Refused (ValueError) together with
+    detect_infeasibility and correctors > 0; start="mehrotra" ignores g."""
     global _last_info
     correctors = check_correctors(correctors)
     refine = check_refine(refine)
@@ -107,6 +114,12 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
         opts = dict(opts, scale=scale, scale_passes=scale_passes)
     if dense_cols is not None:
         opts = dict(opts, dense_cols=dense_cols)
+    quad = check_quadratic(quad, np.asarray(c).reshape(-1).shape[0])
+    if quad is not None:
+        if detect_infeasibility:
+            refuse_quadratic(quad, "detect_infeasibility=True", "the infeasibility tests are the LP's")
+        if correctors:
+            refuse_quadratic(quad, "correctors=%d" % correctors, "a quadratic solver takes one step length, the rounds compare step pairs")
     ub = _upper_bounds(ub, np.asarray(c).reshape(-1).shape[0])
     on_device = start == "mehrotra" and device_start
     if start == "mehrotra" and not on_device and shift_allowed(opts.get("regularize"), _auto_regularize()):
@@ -120,7 +133,7 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     t0 = _time.perf_counter()
     if detect_infeasibility:
         opts = dict(opts, detect_infeasibility=True)
-    make = lambda **extra: IpmSolver(A, b, c, device=device, ub=ub, correctors=correctors, refine=refine, **dict(opts, **extra))          # noqa: E731
+    make = lambda **extra: IpmSolver(A, b, c, device=device, ub=ub, correctors=correctors, refine=refine, quad=quad, **dict(opts, **extra))          # noqa: E731
     with (mehrotra_started(make, opts.get("regularize"), _auto_regularize()) if on_device else make()) as sv:
         t1 = _time.perf_counter()
         if start == "mehrotra" and not on_device:
@@ -142,11 +155,12 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     return x, y, s, info
 
 
-def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, **opts):
-    """min c^T x s.t. Ax=b, x>=0 (and x <= ub where ub is finite) by the Mehrotra predictor-corrector loop on the GPU
-    -> (x, y, s)."""
+def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None,
+          quad=None, **opts):
+    """min c^T x (+ 1/2 x^T diag(quad) x) s.t. Ax=b, x>=0 (and x <= ub where ub is finite) by the Mehrotra predictor-corrector loop
+    on the GPU -> (x, y, s)."""
     x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub, scale=scale,
-                                 scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols, **opts)
+                                 scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad, **opts)
     return x, y, s
 
 
@@ -160,13 +174,13 @@ def _verdict(info, value):
 
 
 def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0,
-                    dense_cols=None):
-    """Drop-in for main.py:760-815: start x=s=y=1, cap 5000, returns sum(x*c) - cTlb.  detect_infeasibility=True: +inf for an
+                    dense_cols=None, quad=None):
+    """Drop-in for main.py:760-815: start x=s=y=1, cap 5000, returns sum(x*c) - cTlb (with quad: the quadratic objective - cTlb).  detect_infeasibility=True: +inf for an
     LP detected infeasible, -inf for one detected unbounded.  scale, correctors, refine, dense_cols: as solve_with_info (off by
     default)."""
     _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=5000, y0=1.0, device=device,
                                     detect_infeasibility=detect_infeasibility, scale=scale, scale_passes=scale_passes,
-                                    correctors=correctors, refine=refine, dense_cols=dense_cols)
+                                    correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad)
     return _verdict(info, info["objective"] - float(cTlb))
 
 

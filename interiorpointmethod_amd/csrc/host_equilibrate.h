@@ -34,9 +34,17 @@ static void enqueue_bc_norms(ipm_handle* h) {
 
 // A new A has arrived and passed its validation (ipm_set_A_dense / ipm_set_A_csc call this just before they touch the device copy
 // of A, so a rejected A leaves the scaled handle as it was): the handle is unscaled again.  The bounds it holds go back to the
-// caller's units (exact); b and c must be set again.
+// caller's units (exact), and so does its quadratic term (g' = g C^2); b and c must be set again.
 static int eq_reset(ipm_handle* h) {
     if (!h->scaled) return IPM_OK;
+    if (h->quad) {
+        std::vector<double> g((size_t)h->n);
+        HIP_TRY(h, hipMemcpyAsync(g.data(), h->quad_g, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (size_t j = 0; j < g.size(); ++j) g[j] = g[j] / h->eq_c[j] / h->eq_c[j];
+        HIP_TRY(h, hipMemcpyAsync(h->quad_g, g.data(), sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
     if (h->bnd) {
         std::vector<double> u((size_t)h->n);
         HIP_TRY(h, hipMemcpyAsync(u.data(), h->bnd_mem, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
@@ -95,6 +103,7 @@ extern "C" int ipm_equilibrate(ipm_handle* h, int32_t max_passes, double info[4]
         hipLaunchKernelGGL(eq_vec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->c, ec, n, 1, 1, err_misc);
     }
     if (h->bnd) hipLaunchKernelGGL(eq_vec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->bnd_mem, ec, n, -1, 1, err_misc);
+    if (h->quad) hipLaunchKernelGGL(eq_vec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->quad_g, ec, n, 2, 1, err_misc);      // g <- g C^2
     HIP_TRY(h, hipGetLastError());
     std::vector<int> flags(2 * (size_t)cap + 8);
     double sp[6];
@@ -108,7 +117,7 @@ extern "C" int ipm_equilibrate(ipm_handle* h, int32_t max_passes, double info[4]
     if (info) { info[0] = passes; info[1] = eq_log2_spread(sp); info[2] = eq_log2_spread(sp + 2); info[3] = eq_log2_spread(sp + 4); }
     if (passes == 0) return IPM_OK;                      // cap 0, or the data sit at the fixed point already: nothing to rewrite
     if (f_err_max[passes] || f_err_misc)                 // (the maxima of launch `passes` are those of the final factors)
-        return fail(h, IPM_ERR_INVALID_INPUT, "ipm_equilibrate: a factor would push an entry of A, b, c or u out of the normal fp64 range; the handle stays unscaled");
+        return fail(h, IPM_ERR_INVALID_INPUT, "ipm_equilibrate: a factor would push an entry of A, b, c, u or g out of the normal fp64 range; the handle stays unscaled");
     // ---- rewrite A and every value table derived from it, once
     if (h->sparse) {
         hipLaunchKernelGGL(eq_sparse_apply_kernel, dim3((unsigned)((m + 15) / 16)), dim3(256), 0, h->stream, S.rowptr, S.colind, h->d_rval, m, er, ec);
@@ -128,6 +137,7 @@ extern "C" int ipm_equilibrate(ipm_handle* h, int32_t max_passes, double info[4]
         hipLaunchKernelGGL(eq_vec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->c, ec, n, 1, 0, err_misc);
     }
     if (h->bnd) hipLaunchKernelGGL(eq_vec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->bnd_mem, ec, n, -1, 0, err_misc);
+    if (h->quad) hipLaunchKernelGGL(eq_vec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->quad_g, ec, n, 2, 0, err_misc);
     if (h->haveBC) enqueue_bc_norms(h);
     HIP_TRY(h, hipGetLastError());
     std::vector<int> he((size_t)mp + np);

@@ -160,6 +160,11 @@ struct ipm_handle {
     bool bnd = false;                     // a finite bound is set: the bounded kernel instantiations run
     int bnd_nU = 0;                       // |U|
     double* bnd_mem = nullptr;            // u | w | z | dwa | dza | dw | dz | qz | roll-back w | roll-back z
+    // separable convex QP (ipm_set_quadratic): own allocation of one np-vector, made on first use
+    bool quad = false;                    // a positive entry is set: the Quad kernel instantiations run
+    int64_t quad_nnz = 0;                 // positive entries of g
+    double* quad_g = nullptr;             // g in the handle's units (g C^2 on a scaled handle), zero in the padding; constant during a
+                                          // solve, so the roll-back snapshot carries nothing of it
     // centrality correctors (ipm_set_centrality_correctors): up to mcc.k rounds per iteration re-use its factor
     Rounds<MccCtl, MCC_CTL_DOUBLES> mcc{&MCC_KIND};   // mem: q v dx ds r3 r3g | qz dw dz r4 r4g (n-vectors) | dy (m-vector) | partial minima [2][MAXPART] | record | its copy
     // iterative refinement of the normal-equations solves (ipm_set_refinement): up to ref.k rounds behind every solve

@@ -24,12 +24,21 @@ static void launch_gemv_t_rows(ipm_handle* h, const double* u, int chunk0, int c
 
 // The vector steps of the iteration, ONE launch function each: it holds the step's fork between the plain kernel and the detect
 // kernel (both have lockstep twins) and the bounded kernels (none: a bounded handle is never recorded, ls_eligible).
-template <LsType T> static void launch_vec_step(ipm_handle* h, void (*bounded)(VecArgs, BndArgs), hipStream_t st = nullptr) {
-    if (h->bnd) launch_untwinned(h, bounded, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
+// A handle with a quadratic term (ipm_set_quadratic) runs the Quad instantiation of the four steps that have one (quad, quad_bounded:
+// no twins either -- a lockstep handle is refused the term); every other step is the LP's.
+template <LsType T> static void launch_vec_step(ipm_handle* h, void (*bounded)(VecArgs, BndArgs), hipStream_t st = nullptr,
+                                                void (*quad)(VecArgs) = nullptr, void (*quad_bounded)(VecArgs, BndArgs) = nullptr) {
+    if (h->quad && quad) {
+        if (h->bnd) launch_untwinned(h, quad_bounded, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
+        else launch_untwinned(h, quad, dim3(h->vblk), dim3(VBLK), st, vec_args(h));
+    } else if (h->bnd) launch_untwinned(h, bounded, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
     else launch_twin<T>(h, (unsigned)h->vblk, {vec_args(h), 0}, st);
 }
 static void launch_prepare(ipm_handle* h, hipStream_t st) {
-    if (h->bnd && h->detect) launch_untwinned(h, prepare_bounded_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
+    const double* g = h->quad_g;
+    if (h->quad && h->bnd) launch_untwinned(h, prepare_bounded_quad_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g);      // (never with detect: refused)
+    else if (h->quad) launch_untwinned(h, prepare_quad_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g);
+    else if (h->bnd && h->detect) launch_untwinned(h, prepare_bounded_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
     else if (h->detect) launch_twin<LS_PREPARE_DETECT>(h, (unsigned)h->vblk, {vec_args(h), det_args(h)}, st);
     else launch_vec_step<LS_PREPARE>(h, prepare_bounded_kernel, st);
 }
@@ -40,7 +49,10 @@ static void launch_stop_test(ipm_handle* h, hipStream_t st) {
     else launch_twin<LS_STOP_TEST>(h, 1u, {vec_args(h), 0}, st);
 }
 static void launch_scaling(ipm_handle* h) {      // (residual-stream iteration only, which is never recorded: no twin, nothing to refuse)
-    if (h->bnd) hipLaunchKernelGGL(scaling_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), bnd_args(h));
+    const double* g = h->quad_g;
+    if (h->quad && h->bnd) hipLaunchKernelGGL(scaling_bounded_quad_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), bnd_args(h), g);
+    else if (h->quad) hipLaunchKernelGGL(scaling_quad_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), g);
+    else if (h->bnd) hipLaunchKernelGGL(scaling_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), bnd_args(h));
     else hipLaunchKernelGGL(scaling_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h));
 }
 static void launch_direction(ipm_handle* h, int corr) {
@@ -61,9 +73,9 @@ static void launch_mcc_accept(ipm_handle* h) {
     if (h->bnd) launch_untwinned(h, mcc_accept_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, 0), bnd_args(h), mcc_bnd_args(h));
     else launch_untwinned(h, mcc_accept_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, 0));
 }
-static void launch_mu_aff(ipm_handle* h) { launch_vec_step<LS_MU_AFF>(h, mu_aff_bounded_kernel); }
+static void launch_mu_aff(ipm_handle* h) { launch_vec_step<LS_MU_AFF>(h, mu_aff_bounded_kernel, nullptr, mu_aff_quad_kernel, mu_aff_bounded_quad_kernel); }
 static void launch_corrector_rhs(ipm_handle* h) { launch_vec_step<LS_CORR_RHS>(h, corrector_rhs_bounded_kernel); }
-static void launch_update(ipm_handle* h) { launch_vec_step<LS_UPDATE>(h, update_bounded_kernel); }
+static void launch_update(ipm_handle* h) { launch_vec_step<LS_UPDATE>(h, update_bounded_kernel, nullptr, update_quad_kernel, update_bounded_quad_kernel); }
 
 // r_b, r_c, d, predictor v, stop test (and, with IPM_FLAG_DETECT_INFEASIBILITY, the infeasibility tests): the one launch site of the
 // stop test of every multi-kernel path (dense, sparse envelope, sparse factor, fused formation + factorization, lockstep)

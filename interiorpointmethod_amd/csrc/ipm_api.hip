@@ -324,7 +324,7 @@ extern "C" int ipm_destroy(ipm_handle* h) {
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->h_sc) { std::lock_guard<std::mutex> lock(g_hsc_mutex); g_hsc_pool.push_back(h->h_sc); h->h_sc = nullptr; }
-    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->mcc.mem, (void*)h->ref.mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
+    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->quad_g, (void*)h->mcc.mem, (void*)h->ref.mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
         dev_free(h->device, h->stream, p);
     ff_release(h);
     free_sparse_factor(h);
@@ -439,6 +439,57 @@ extern "C" int ipm_set_bounds(ipm_handle* h, const double* u) {
     if (h->haveBC) hipLaunchKernelGGL(bnd_norm2_kernel, dim3(1), dim3(VBLK), 0, h->stream, h->b, (int)h->m, bd.u, (int)h->n, &h->sc->b_norm);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return IPM_OK;
+}
+
+// Separable convex QP: the diagonal g of the objective's quadratic term.  The vector is the library's own
+// allocation, made on first use and kept (clearing only switches the Quad kernels off); the workspace is not involved.  The whole
+// np-vector is written, so the padding is zero before any kernel reads it.
+extern "C" int ipm_set_quadratic(ipm_handle* h, const double* g) {
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: NULL handle");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int64_t nnz = 0;
+    if (g) {
+        for (int64_t j = 0; j < h->n; ++j) {
+            const double v = g[j];
+            if (!(v >= 0.0) || !(v < std::numeric_limits<double>::infinity()))
+                return fail(h, IPM_ERR_INVALID_INPUT, "ipm_set_quadratic: g[%lld] = %g (the diagonal must be finite and >= 0)", (long long)j, v);
+            if (v > 0.0) ++nnz;
+        }
+    }
+    if (nnz == 0) {                                            // NULL or all zeros: the LP code, exactly
+        h->quad = false; h->quad_nnz = 0; h->predictor_valid = false;
+        return IPM_OK;
+    }
+    if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle was created with IPM_FLAG_LOCKSTEP (the Quad kernels have no batched twins)");
+    if (h->detect) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the dual ray of a QP also needs g o x = 0; the tests are not restated)");
+    if (h->mcc.k > 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: %d centrality correctors are set (their accept rule compares step pairs, a quadratic handle takes one step; ipm_set_centrality_correctors(h, 0))", h->mcc.k);
+    if (h->small) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle runs the fused small-LP kernel, which has no quadratic term; set the term before A (ipm_set_A_csc then takes the multi-kernel path)");
+    const size_t np = (size_t)h->np;
+    std::vector<double> gg(np, 0.0);
+    std::copy(g, g + h->n, gg.begin());
+    if (h->scaled) {                                           // scaled handle: g C^2 (host_equilibrate.h), exact
+        for (int64_t j = 0; j < h->n; ++j) gg[(size_t)j] = gg[(size_t)j] * h->eq_c[(size_t)j] * h->eq_c[(size_t)j];
+        if (!eq_in_range(h, g, gg.data(), (size_t)h->n))
+            return fail(h, IPM_ERR_INVALID_INPUT, "ipm_set_quadratic: the handle's scaling would push an entry of g out of the normal fp64 range");
+    }
+    if (!h->quad_g && dev_malloc(h->device, h->stream, (void**)&h->quad_g, sizeof(double) * np) != hipSuccess)
+        return fail(h, IPM_ERR_HIP, "ipm_set_quadratic: %lld doubles could not be allocated", (long long)np);
+    HIP_TRY(h, hipMemcpyAsync(h->quad_g, gg.data(), sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->quad = true; h->quad_nnz = nnz; h->predictor_valid = false;
+    return IPM_OK;
+}
+
+extern "C" int ipm_get_quadratic(ipm_handle* h, double* g, int64_t* nonzeros) {
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_quadratic: NULL handle");
+    if (nonzeros) *nonzeros = h->quad ? h->quad_nnz : 0;
+    if (!g) return IPM_OK;
+    if (!h->quad) { std::fill(g, g + h->n, 0.0); return IPM_OK; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpyAsync(g, h->quad_g, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    eq_out(h, g, h->eq_c, true); eq_out(h, g, h->eq_c, true);      // scaled handle: g' / C^2
     return IPM_OK;
 }
 

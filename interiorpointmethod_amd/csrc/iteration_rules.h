@@ -8,7 +8,8 @@
 // The calling path owns where the vectors live, how it obtains (A^T dy)_j (passed in as a value), every reduction across threads
 // and the order of its additions.
 // `Cols` is VecArgs or SmallLP: a rule uses the column pointers both name alike (x, s, rc, d, v, q, dxa, dsa, dx, ds).
-// Bounded = native upper bounds (BndArgs), Detect = the infeasibility tests (DetArgs).
+// Bounded = native upper bounds (BndArgs), Detect = the infeasibility tests (DetArgs),
+// Quad = a diagonal quadratic term in the objective (quad_*).
 //
 // Two rules are NOT here yet and are still written out in both files, to be kept identical by hand: the predictor column
 // (prepare_kernel_body / residual_cols) and the stop decision (stop_test_kernel_body / the stop_test lambda).  Every shared
@@ -66,6 +67,22 @@ __device__ __forceinline__ double bnd_theta(double x, double s, double w, double
 // the number of complementarity pairs: mu = (x.s + w.z) / (n + |U|), and mu_aff alike
 template <bool Bounded>
 __device__ __forceinline__ double pair_count(int n, const BndArgs& bd) { return Bounded ? (double)(n + bd.nU) : (double)n; }
+
+// Separable convex QP (ipm_set_quadratic): min c.x + 1/2 x.diag(g) x with g >= 0 (g = 0 outside its support and in
+// the padding).  The Quad instantiations differ from the LP in four places, each stated here once:
+//   dual residual  r_c = A^T y + s - z - c - g o x                    (quad_rc: the term taken off the LP's r_c)
+//   scaling        d = x / (s + g x), on U: 1 / (s/x + z/w + g)       (scaling_kernel and prepare_kernel write it concurrently:
+//                                                                      one expression each)
+//   objective      sum_j (c_j + 1/2 g_j x_j) x_j                      (the P_CX partial; no new reduction)
+//   ONE step       alpha = min(alpha_p, alpha_d) wherever the iteration holds a (primal, dual) pair: with unequal steps the dual
+//                  residual would keep a term (alpha_d - alpha_p) g o dx that no later Newton step is aimed at
+// With that d and that r_c the predictor's v, direction_column, corrector_column, the right-hand side -r_b - A v and the recovery
+// keep the LP's formulas (eliminating ds = -(r_3 + s dx)/x from A^T dy + ds - dz - g o dx = -r_c only adds g to the diagonal).
+__device__ __forceinline__ double quad_rc(double rc_lp, double g, double x) { return rc_lp - g * x; }
+__device__ __forceinline__ double quad_theta(double x, double s, double g) { return x / (s + g * x); }
+__device__ __forceinline__ double quad_bnd_theta(double x, double s, double w, double z, double g) { return 1.0 / (s / x + z / w + g); }
+__device__ __forceinline__ double quad_objective(double c, double g, double x) { return (c + 0.5 * g * x) * x; }
+__device__ __forceinline__ double quad_step(double ap, double ad) { return fmin(ap, ad); }
 
 // Infeasibility tests of IPM_FLAG_DETECT_INFEASIBILITY, on the iterate of a stop test that said "continue":
 //   primal infeasible: beta = b.y - u_U.z_U > 0 and max_j (A^T y - z)_j+ <= eps_p beta   (certificate y / beta, z / beta)

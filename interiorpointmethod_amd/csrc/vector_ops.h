@@ -172,8 +172,9 @@ __device__ __forceinline__ double col_sum(const double* atp, int rc_chunks, int 
 // r_u^2 joins ||r_b||^2 and w z joins x.s
 // Detect (IPM_FLAG_DETECT_INFEASIBILITY): also the partials of the infeasibility tests (P_BY .. P_MXU) -- reads of what the
 // pass holds anyway (A^T y from col_sum, A x = r_b + b), no extra pass over A
-template <bool Bounded = false, bool Detect = false>
-__device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
+// Quad (ipm_set_quadratic; g: the np-vector of the diagonal): r_c, d and the objective by the quad_* rules, one more streamed vector
+template <bool Bounded = false, bool Detect = false, bool Quad = false>
+__device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, const double* g = nullptr) {
     __shared__ double red[VBLK];
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     double rc2 = 0.0, xs = 0.0, cx = 0.0, rb2 = 0.0;
@@ -185,9 +186,11 @@ __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx
             if (bnd_in(uj)) {
                 const double wj = bd.w[j], zj = bd.z[j];
                 const double atyj = col_sum(a.atp, a.rc_chunks, a.np, j);
-                const double rcj = atyj + sj - zj - a.c[j];
+                double rcj = atyj + sj - zj - a.c[j];
                 const double ruj = xj + wj - uj;
-                const double dj = bnd_theta(xj, sj, wj, zj);
+                double dj;
+                if constexpr (Quad) { const double gj = g[j]; rcj = quad_rc(rcj, gj, xj); dj = quad_bnd_theta(xj, sj, wj, zj, gj); cx += quad_objective(a.c[j], gj, xj); }
+                else dj = bnd_theta(xj, sj, wj, zj);
                 const double r3 = xj * sj, r4 = wj * zj;
                 a.rc[j] = rcj;
                 a.d[j] = dj;
@@ -197,7 +200,7 @@ __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx
                 rc2 += rcj * rcj;
                 xs += r3;
                 xs += r4;
-                cx += a.c[j] * xj;
+                if constexpr (!Quad) cx += a.c[j] * xj;
                 rb2 += ruj * ruj;
                 if constexpr (Detect) { uz += uj * zj; maty = fmax(maty, atyj - zj); mxu = fmax(mxu, xj); }
                 continue;
@@ -205,7 +208,9 @@ __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx
         }
         const double atyj = col_sum(a.atp, a.rc_chunks, a.np, j);
         double rcj = atyj + sj - a.c[j];
-        double dj = xj / sj;
+        double dj;
+        if constexpr (Quad) { const double gj = g[j]; rcj = quad_rc(rcj, gj, xj); dj = quad_theta(xj, sj, gj); cx += quad_objective(a.c[j], gj, xj); }
+        else dj = xj / sj;
         double r3 = xj * sj;
         a.rc[j] = rcj;
         a.d[j] = dj;
@@ -213,7 +218,7 @@ __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx
         a.v[j] = dj * (rcj - r3 / xj);
         rc2 += rcj * rcj;
         xs += r3;
-        cx += a.c[j] * xj;
+        if constexpr (!Quad) cx += a.c[j] * xj;
         if constexpr (Detect) maty = fmax(maty, atyj);
     }
     for (int i = gid; i < a.m; i += gsz) {
@@ -240,23 +245,32 @@ __global__ __launch_bounds__(VBLK) void prepare_kernel(VecArgs a) { prepare_kern
 __global__ __launch_bounds__(VBLK) void prepare_bounded_kernel(VecArgs a, BndArgs bd) { prepare_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 __global__ __launch_bounds__(VBLK) void prepare_detect_kernel(VecArgs a) { prepare_kernel_body<false, true>(a, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void prepare_bounded_detect_kernel(VecArgs a, BndArgs bd) { prepare_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd); }
+__global__ __launch_bounds__(VBLK) void prepare_quad_kernel(VecArgs a, const double* g) { prepare_kernel_body<false, false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, g); }
+__global__ __launch_bounds__(VBLK) void prepare_bounded_quad_kernel(VecArgs a, BndArgs bd, const double* g) { prepare_kernel_body<true, false, true>(a, blockIdx.x, gridDim.x, bd, g); }
 
 // d = x / s only (main.py:223): what the formation of A D^2 A^T needs; the full prepare_kernel follows on the residual
-// stream while the factorization runs (host_iteration.h, enqueue_iteration).  Bounded: d = theta on U.
-template <bool Bounded = false>
-__device__ __forceinline__ void scaling_kernel_body(VecArgs a, BndArgs bd = BndArgs{}) {
+// stream while the factorization runs (host_iteration.h, enqueue_iteration).  Bounded: d = theta on U.  Quad: the quad_* scalings.
+template <bool Bounded = false, bool Quad = false>
+__device__ __forceinline__ void scaling_kernel_body(VecArgs a, BndArgs bd = BndArgs{}, const double* g = nullptr) {
     if (blockIdx.x == 0 && threadIdx.x == 0) a.sc->done_f = a.sc->done;      // latch for this iteration's factorization
     if (a.sc->done) return;
     const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
     for (int j = gid; j < a.n; j += gsz) {
         if constexpr (Bounded) {
-            if (bnd_in(bd.u[j])) { a.d[j] = bnd_theta(a.x[j], a.s[j], bd.w[j], bd.z[j]); continue; }
+            if (bnd_in(bd.u[j])) {
+                if constexpr (Quad) a.d[j] = quad_bnd_theta(a.x[j], a.s[j], bd.w[j], bd.z[j], g[j]);
+                else a.d[j] = bnd_theta(a.x[j], a.s[j], bd.w[j], bd.z[j]);
+                continue;
+            }
         }
-        a.d[j] = a.x[j] / a.s[j];
+        if constexpr (Quad) a.d[j] = quad_theta(a.x[j], a.s[j], g[j]);
+        else a.d[j] = a.x[j] / a.s[j];
     }
 }
 __global__ __launch_bounds__(VBLK) void scaling_kernel(VecArgs a) { scaling_kernel_body(a); }
 __global__ __launch_bounds__(VBLK) void scaling_bounded_kernel(VecArgs a, BndArgs bd) { scaling_kernel_body<true>(a, bd); }
+__global__ __launch_bounds__(VBLK) void scaling_quad_kernel(VecArgs a, const double* g) { scaling_kernel_body<false, true>(a, BndArgs{}, g); }
+__global__ __launch_bounds__(VBLK) void scaling_bounded_quad_kernel(VecArgs a, BndArgs bd, const double* g) { scaling_kernel_body<true, true>(a, bd, g); }
 
 // stop test of check_optimality (main.py:162-173) -- one thread.
 // Bounded: ||r_b||^2 carries r_u^2 and the gap w.z (prepare_kernel), b_norm is ||(b, u_U)|| (ipm_set_bounds), mu divides by n + |U|.
@@ -334,14 +348,15 @@ __device__ __forceinline__ void direction_kernel_body(VecArgs a, int corr, const
 __global__ __launch_bounds__(VBLK) void direction_kernel(VecArgs a, int corr) { direction_kernel_body(a, corr, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void direction_bounded_kernel(VecArgs a, int corr, BndArgs bd) { direction_kernel_body<true>(a, corr, blockIdx.x, gridDim.x, bd); }
 
-// partial sums of mu_aff_column at the affine step lengths
-template <bool Bounded = false>
+// partial sums of mu_aff_column at the affine step lengths (Quad: at the one step quad_step makes of them, which the stats report)
+template <bool Bounded = false, bool Quad = false>
 __device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     if (a.sc->done) return;
     __shared__ double red[VBLK];
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
-    const double ap = min_partials(a.part, P_MINP_AFF, a.nblk);
-    const double ad = min_partials(a.part, P_MIND_AFF, a.nblk);
+    double ap = min_partials(a.part, P_MINP_AFF, a.nblk);
+    double ad = min_partials(a.part, P_MIND_AFF, a.nblk);
+    if constexpr (Quad) ap = ad = quad_step(ap, ad);
     double acc = 0.0;
     for (int j = gid; j < a.n; j += gsz) mu_aff_column<Bounded>(a, bd, j, ap, ad, acc);
     acc = block_sum(acc, red);
@@ -352,6 +367,8 @@ __device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_
 }
 __global__ __launch_bounds__(VBLK) void mu_aff_kernel(VecArgs a) { mu_aff_kernel_body(a, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void mu_aff_bounded_kernel(VecArgs a, BndArgs bd) { mu_aff_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
+__global__ __launch_bounds__(VBLK) void mu_aff_quad_kernel(VecArgs a) { mu_aff_kernel_body<false, true>(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(VBLK) void mu_aff_bounded_quad_kernel(VecArgs a, BndArgs bd) { mu_aff_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd); }
 
 // centring from the re-summed partials of mu_aff_kernel, then corrector_column
 template <bool Bounded = false>
@@ -367,14 +384,15 @@ __device__ __forceinline__ void corrector_rhs_kernel_body(VecArgs a, const unsig
 __global__ __launch_bounds__(VBLK) void corrector_rhs_kernel(VecArgs a) { corrector_rhs_kernel_body(a, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void corrector_rhs_bounded_kernel(VecArgs a, BndArgs bd) { corrector_rhs_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 
-// damped_step from the re-summed ratio-test minima, update_column, y += a_d dy, record_iteration
-template <bool Bounded = false>
+// damped_step from the re-summed ratio-test minima (Quad: quad_step of the pair), update_column, y += a_d dy, record_iteration
+template <bool Bounded = false, bool Quad = false>
 __device__ __forceinline__ void update_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
     if (a.sc->done) return;
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     const double eta = a.sc->eta;
-    const double ap = damped_step(eta, min_partials(a.part, P_MINP, a.nblk));
-    const double ad = damped_step(eta, min_partials(a.part, P_MIND, a.nblk));
+    double ap = damped_step(eta, min_partials(a.part, P_MINP, a.nblk));
+    double ad = damped_step(eta, min_partials(a.part, P_MIND, a.nblk));
+    if constexpr (Quad) ap = ad = quad_step(ap, ad);
     for (int j = gid; j < a.n; j += gsz) update_column<Bounded>(a, bd, j, ap, ad);
     for (int i = gid; i < a.m; i += gsz) a.y[i] += ad * a.dy[i];
     if (gid == 0) {
@@ -385,6 +403,8 @@ __device__ __forceinline__ void update_kernel_body(VecArgs a, const unsigned bx_
 }
 __global__ __launch_bounds__(VBLK) void update_kernel(VecArgs a) { update_kernel_body(a, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void update_bounded_kernel(VecArgs a, BndArgs bd) { update_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
+__global__ __launch_bounds__(VBLK) void update_quad_kernel(VecArgs a) { update_kernel_body<false, true>(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(VBLK) void update_bounded_quad_kernel(VecArgs a, BndArgs bd) { update_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd); }
 
 // ---------------------------------------------------------------------------------------
 // Centrality correctors (iteration_rules.h: mcc_*): the three vector kernels of one round, enqueued K times between

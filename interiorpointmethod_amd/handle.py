@@ -83,6 +83,26 @@ def refuse_correctors(k, who): return refuse_rounds("correctors", k, who)     # 
 def refuse_refine(k, who): return refuse_rounds("refine", k, who)             # noqa: E704
 
 
+def check_quadratic(quad, n):
+    """THE check of the `quad` keyword, before any device is touched: None (no term, the default) or n finite entries >= 0, the
+    diagonal g of the objective's quadratic term -> None (also for all zeros: the LP) or a fresh float64 array of length n."""
+    if quad is None:
+        return None
+    g = np.array(quad, dtype=np.float64).reshape(-1)
+    if g.shape[0] != n:
+        raise ValueError("quad has %d entries, the problem has %d columns" % (g.shape[0], n))
+    if not np.all(np.isfinite(g)) or np.any(g < 0):
+        raise ValueError("quad must be finite and >= 0 (the diagonal of a convex quadratic term)")
+    return g if np.any(g > 0) else None
+
+
+def refuse_quadratic(quad, who, why):
+    """THE refusal of what has no quadratic term (the batch front ends' options on IpmSolver: lockstep, detect_infeasibility,
+    correctors): a nonzero term raises instead of being dropped."""
+    if quad is not None and np.any(np.asarray(quad, dtype=np.float64) > 0):
+        raise ValueError("quad: %s takes no quadratic term (%s)" % (who, why))
+
+
 RefineInfo = collections.namedtuple("RefineInfo", "k solves applied half_rule reverts first_rel last_rel max_first_rel")
 
 
@@ -96,7 +116,7 @@ class IpmSolver:
     def __init__(self, A, b, c, device=0, eta=0.91, pivot_guard_eps=1e-30, pivot_guard_big=1e64,
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
                  auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
-                 infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None):
+                 infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, quad=None):
         """check_every: solve() enqueues that many iterations at a time and reads the stop flag once per chunk (the launches behind a
         satisfied stop test return at entry, so the result does not depend on it: DESIGN.md 4-A); a lockstep batch runs chunks of the
         largest value among its members.  IPM_CHECK_EVERY in the environment, when set and not empty, OVERRIDES this argument for
@@ -116,10 +136,21 @@ class IpmSolver:
         A D^2 A^T (set_refine).  0, the default, is the iteration without them, exactly.
         dense_cols: None (default: no split), "auto" or a sequence of column indices -- the dense-column split of the sparse factor
         (analysis.prepare, ipm_set_dense_columns; DESIGN.md 4-D).  self.dense_cols is the set in effect (None: none);
-        dense_split_info() reports it.  A lockstep solver refuses it (ValueError)."""
+        dense_split_info() reports it.  A lockstep solver refuses it (ValueError).
+        quad: None (default: the LP) or the diagonal g >= 0 (length n) of a separable convex quadratic term: the solver minimises
+        c.x + 1/2 x.diag(g) x (set_quadratic, ipm_set_quadratic), checked on the host before any device is touched.
+        The term is set before A, so a small sparse problem takes the multi-kernel path.  lockstep, detect_infeasibility and
+        correctors > 0 refuse a nonzero term (ValueError); mehrotra_start / init_state_mehrotra ignore it."""
         self.scale = check_scale(scale)
         correctors = check_correctors(correctors)
         refine = check_refine(refine)
+        quad = check_quadratic(quad, np.asarray(c).reshape(-1).shape[0] if prepared is None else prepared.n)
+        if lockstep:
+            refuse_quadratic(quad, "a lockstep solver", "the batch has no quadratic kernels; solve such problems one at a time")
+        if detect_infeasibility:
+            refuse_quadratic(quad, "detect_infeasibility=True", "the infeasibility tests are the LP's")
+        if correctors:
+            refuse_quadratic(quad, "correctors=%d" % correctors, "a quadratic solver takes one step length, the rounds compare step pairs")
         if lockstep and dense_cols is not None:
             raise ValueError("dense_cols=%r: a lockstep solver has no dense-column split; solve such LPs one at a time" % (dense_cols,))
         if prepared is None:
@@ -179,6 +210,12 @@ class IpmSolver:
         _lib.check(None, lib.ipm_create(int(device), self.m, self.n, C.byref(opts), ws_ptr,
                                         self.workspace_bytes if ws_ptr else 0, stream, C.byref(h)))
         self._h = h
+        if quad is not None:                 # before A: ipm_set_A_csc then never chooses the one-workgroup small path
+            try:
+                self._check(lib.ipm_set_quadratic(h, _dptr(quad)))
+            except Exception:
+                self.close()
+                raise
         if self.sparse:
             indptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
             indices = np.ascontiguousarray(A.indices, dtype=np.int32)
@@ -356,6 +393,26 @@ class IpmSolver:
         if name == "refine" and self.dense_cols is not None:
             k = self.refine_info().k          # (a split handle keeps at least its own two rounds)
         setattr(self, name, k)
+
+    def set_quadratic(self, g):
+        """ipm_set_quadratic: the diagonal g >= 0 (length n) of the objective's quadratic term from the next iteration on; None or
+        all zeros removes it, and the solver runs exactly the LP code again.  Checked on the host first (ValueError: length, NaN,
+        Inf, negative); the library refuses a nonzero term (IpmError) on a lockstep solver, with detect_infeasibility, with
+        correctors > 0 and on the fused small path.  Either way the solver keeps the term it held."""
+        g = check_quadratic(g, self.n)
+        self._check(self._lib.ipm_set_quadratic(self._h, None if g is None else _dptr(g)))
+
+    def quadratic(self):
+        """ipm_get_quadratic: the diagonal in the caller's units as a fresh array of length n (zeros without a term)."""
+        g = np.empty(self.n)
+        self._check(self._lib.ipm_get_quadratic(self._h, _dptr(g), None))
+        return g
+
+    def quadratic_nonzeros(self):
+        """The number of positive entries of the term the solver holds (0: the LP)."""
+        nz = C.c_int64(0)
+        self._check(self._lib.ipm_get_quadratic(self._h, None, C.byref(nz)))
+        return int(nz.value)
 
     def set_correctors(self, k):
         """ipm_set_centrality_correctors: up to k (0 .. MAX_CORRECTORS) centrality-corrector rounds per iteration from the next
