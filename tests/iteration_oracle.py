@@ -166,7 +166,8 @@ def _normal_matrix(A, theta):
 
 
 def cholesky(B):
-    """Lower Cholesky factor, left-looking column loop; every pivot must be positive (the cases are well conditioned)."""
+    """Lower Cholesky factor, left-looking column loop; every pivot must be positive (the cases here are well conditioned; those of
+    tests/late_cases.py are not, and stay where longdouble still finds every pivot positive)."""
     m = B.shape[0]
     L = np.zeros((m, m), dtype=LD)
     for j in range(m):
@@ -231,8 +232,16 @@ def ratio_test(v, dv, vb, dvb):
 # ---------------------------------------------------------------------------------------------------------------------------
 # one iteration
 # ---------------------------------------------------------------------------------------------------------------------------
-def _directions(case):
-    """Everything of the iteration that does not depend on eta (cached on the case)."""
+def direct_solver(A, theta):
+    """The normal-equations solve r -> (A Theta A^T)^-1 r of the oracle: the matrix formed and factored in longdouble."""
+    L = cholesky(_normal_matrix(A, theta))
+    return lambda r: cholesky_solve(L, r)
+
+
+def _directions(case, solver=None):
+    """Everything of the iteration that does not depend on eta (cached on the case, so the first call decides the solver).
+    solver: (A, theta) in longdouble -> the solve r -> (A Theta A^T)^-1 r; None: direct_solver.  tests/late_cases.py has a second
+    one, by refinement, for shapes whose longdouble formation would take minutes."""
     if case._dir is not None:
         return case._dir
     A = case.A.astype(LD)
@@ -248,13 +257,13 @@ def _directions(case):
     ru = np.where(U, x + w - u, LD(0))
     theta = x / s
     theta[U] = 1 / (s[U] / x[U] + z[U] / w[U])
-    L = cholesky(_normal_matrix(A, theta))
+    solve = (solver or direct_solver)(A, theta)
 
     def direction(r3, r4):
         t = rc - r3 / x
         t[U] += (r4[U] - z[U] * ru[U]) / w[U]
         v = theta * t
-        dy = cholesky_solve(L, -rb - A @ v)
+        dy = solve(-rb - A @ v)
         atdy = AT @ dy
         dx = theta * atdy + v
         ds = -(r3 + s * dx) / x
@@ -285,13 +294,13 @@ def _directions(case):
     return case._dir
 
 
-def iterate(case, eta=ETA):
+def iterate(case, eta=ETA, solver=None):
     """One Mehrotra predictor-corrector iteration from the case's state -> dict: the affine direction (dxa, dya, dsa, dwa, dza,
     atdya = A^T dya), the corrected one (dx, dy, ds, dw, dz, atdy), the next iterate (xn, yn, sn, wn, zn, atyn = A^T yn), the
     scalars (alpha_aff_p/d, alpha_p/d, mu, mu_aff, sigma, rp_norm = ||(r_b, r_u)||, rd_norm = ||r_c||, gap, objective = c.x, the last
     four at the STARTING iterate, as the device's history records them) and, per ratio test, every candidate ratio (cand_*), the
-    argmin (argmin_*: (part, column)) and the relative gap to the runner-up (sep_*).  All longdouble."""
-    d = _directions(case)
+    argmin (argmin_*: (part, column)) and the relative gap to the runner-up (sep_*).  All longdouble.  solver: see _directions."""
+    d = _directions(case, solver)
     eta = LD(eta)
     ap, ad = min(LD(1), eta * d["ratio_p"]), min(LD(1), eta * d["ratio_d"])
     aff, cor = d["aff"], d["cor"]
@@ -302,6 +311,16 @@ def iterate(case, eta=ETA):
                xn=d["x"] + ap * cor["dx"], yn=d["y"] + ad * cor["dy"], sn=d["s"] + ad * cor["ds"],
                wn=d["w"] + ap * cor["dw"], zn=d["z"] + ad * cor["dz"], atyn=d["aty"] + ad * cor["atdy"])
     return out
+
+
+# what a comparison of one iteration calls its quantities (tests/test_gpu_iteration_edges.check_iteration) -> the key of iterate()'s
+# result; a scalar is named as there, with the seam it was read at in front ("aff.mu", "cor.sigma", "hist.gap")
+VECTOR_KEYS = {"dxa": "dxa", "dsa": "dsa", "ATdya": "atdya", "dya": "dya", "dx": "dx", "ds": "ds", "ATdy": "atdy", "dy": "dy",
+               "x": "xn", "s": "sn", "ATy": "atyn", "y": "yn", "w": "wn", "z": "zn", "dw": "dw", "dz": "dz"}
+
+
+def oracle_key(quantity):
+    return VECTOR_KEYS.get(quantity) or quantity.split(".")[-1]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
