@@ -278,8 +278,13 @@ class Evaluated:
 def evaluate(name):
     """-> .case, .g, .o (the oracle's iteration), .solver (the RefinementSolver the oracle used, or None), .errs (three dicts, one per
     column order), .H, .spread, .dropped (set of cell names).  Computed once per process.  Read-only."""
+    return evaluate_case(get(name), quad_of(name))
+
+
+def evaluate_case(case, g=None):
+    """evaluate of a case that is not in CASES (tests/small_path_cases.py has one); not cached."""
     ev = Evaluated()
-    ev.case, ev.g = get(name), quad_of(name)
+    ev.case, ev.g = case, g
     ev.solver = RefinementSolver() if ev.case.m > REFINEMENT_ABOVE else None
     ev.o = QO.iterate(ev.case, ev.g) if ev.g is not None else IO.iterate(ev.case, solver=ev.solver)
     assert ev.case.m != ev.case.n
@@ -292,7 +297,10 @@ def evaluate(name):
 
 def bound(name):
     """cell name -> what the device may reach in that cell of the case: max(floor, MARGIN x H), +inf for a dropped cell."""
-    ev = evaluate(name)
+    return bound_of(evaluate(name))
+
+
+def bound_of(ev):
     return lambda cell: np.inf if cell in ev.dropped else max(floor(cell), MARGIN * ev.H[cell])
 
 

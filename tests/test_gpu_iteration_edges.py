@@ -247,13 +247,14 @@ DETECT = dict(detect_infeasibility=True, infeasibility_tol=(0.5, 0.5))
 ULP2 = 2.0 ** -51        # certificate_kernel multiplies by 1 / normalization: two roundings against the quotient
 
 
-def _check_certificate(cell, sv, case, st):
-    """Status, iteration count and the certificate of a solve that must have fired at k = 0, against the oracle's quantities."""
+def _check_certificate(cell, sv, case, st, k=0):
+    """Status, iteration count and the certificate of a solve that must have fired at k = 0, against the oracle's quantities.
+    (k > 0, tests/test_gpu_small_path_edges.py: fired at the stop test of iteration k, `case` holding the iterate of that moment.)"""
     q = IO.infeasibility(case)
     primal = cell.startswith("fire/primal")
     cert = sv.certificate()
-    assert st["status"] == (5 if primal else 6) and st["iterations"] == 0, (cell, st["status"], st["iterations"])
-    assert cert is not None and cert["k"] == 0 and cert["kind"] == ("primal_infeasible" if primal else "dual_infeasible")
+    assert st["status"] == (5 if primal else 6) and st["iterations"] == k, (cell, st["status"], st["iterations"])
+    assert cert is not None and cert["k"] == k and cert["kind"] == ("primal_infeasible" if primal else "dual_infeasible")
     nrm, viol = (q["beta"], q["vp"] / q["beta"]) if primal else (q["gamma"], q["vd"] / q["gamma"])
     _assert_all(cell, {"normalization": _srel(cert["normalization"], nrm), "violation": _srel(cert["violation"], viol)},
                 {"normalization": DETECT_TOL, "violation": DETECT_TOL})
