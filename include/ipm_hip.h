@@ -359,9 +359,10 @@ int ipm_get_history(ipm_handle* h, ipm_iter_record* out, int32_t capacity, int32
  * (shared device) instead of one launch per sweep.  (ABI 4: twelve words; ABI 3 had ten.) */
 int ipm_get_schedule(ipm_handle* h, int32_t out[12]);
 /* The same record for callers that know about words added since (additive: ipm_get_schedule keeps its twelve): the first
- * min(capacity, 13) words are written, *count (optional) receives the number.  out[12] = 1 while A^T dy of the predictor and
+ * min(capacity, 14) words are written, *count (optional) receives the number.  out[12] = 1 while A^T dy of the predictor and
  * the corrector is streamed behind the backward sweeps of the grouped solves (dense handles with a residual stream that poll the
- * device; IPM_STREAM_AT=0 and a recovered poll time-out switch it off). */
+ * device; IPM_STREAM_AT=0 and a recovered poll time-out switch it off).  out[13] = 128-row blocks per group of the grouped
+ * triangular solves (8, 4 or 2; floor(blocks / out[13]) groups have explicit inverses), 0 without them. */
 int ipm_get_schedule_words(ipm_handle* h, int32_t* out, int32_t capacity, int32_t* count);
 
 /* Fill-reducing order of the ROWS of an m x n sparse A (CSC, host) for the Cholesky of A D^2 A^T: minimum degree on
@@ -524,6 +525,12 @@ int ipm_get_phase_ms(ipm_handle* h, double out[4]);
 /* Test hook: inv(L_kk) of diagonal block k of the handle's current dense factor, 128 x 128 row-major (zeros above the diagonal), to
  * host `out`.  Rows of the block beyond the LP's row count are padding: the identity (tests/test_gpu_parity.py). */
 int ipm_debug_get_block_inverse(ipm_handle* h, int32_t k, double* out);
+/* Test hook: the explicit inverse of diagonal group g of the handle's current dense factor (grouped triangular solves: gsz blocks
+ * of 128 rows per group, floor(blocks / gsz) groups), whole, (128 gsz) x (128 gsz) row-major, to host `out`: which = 0 X_g =
+ * inv(L_gg) (zeros above the diagonal), which = 1 XT_g, its transpose.  IPM_ERR_STATE on a handle without group inverses.  The
+ * environment switch IPM_GINV_REF=1 (read by ipm_create) makes the handle assemble them with three launches of the generic GEMM
+ * kernel per level instead of two of their own engine: the same bits (tests/test_gpu_group_inverse.py). */
+int ipm_debug_get_group_inverse(ipm_handle* h, int32_t g, int32_t which, double* out);
 /* Diagnostic (environment IPM_FF_TRACE_ITEMS=1 at ipm_create; IPM_ERR_STATE otherwise): time line of the LAST fused formation +
  * factorization launch on the device-wide 100 MHz clock.  *count = words of the trace: 4 per work item {drawn, inputs ready,
  * done, worker} followed by 12 per 128-row block {potrf_diag: start, inputs ready, done, -; critical panel: same; critical

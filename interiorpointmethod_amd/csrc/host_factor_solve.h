@@ -78,8 +78,10 @@ static int enqueue_form(ipm_handle* h, const double* d, bool dense_image = false
 }
 
 // X_g, XT_g = inv of every 1024 x 1024 diagonal group of the factor and its transpose (trsv_grouped.h):
-// recursive doubling 128 -> 256 -> 512 -> 1024, three GEMMs per level batched over (pairs in a group,
-// groups).  After enqueue_factor, on the main stream.
+// recursive doubling 128 -> 256 -> 512 -> 1024, batched over (pairs in a group, groups): per level one launch for S and one
+// that produces X21 and XT12 together (ginv_gemm_f64.h).  The three-launch form on the generic kernel computes the same bits;
+// it is what a lockstep program records (its kernels have twins) and what IPM_GINV_REF=1 selects, the reference of
+// tests/test_gpu_group_inverse.py.  After enqueue_factor, on the main stream.
 static int enqueue_group_inverses(ipm_handle* h, int g0 = 0, int g1 = -1, hipStream_t st = nullptr) {
     if (sp_on(h)) return IPM_OK;
     if (!h->grouped_trsv) return IPM_OK;
@@ -94,15 +96,32 @@ static int enqueue_group_inverses(ipm_handle* h, int g0 = 0, int g1 = -1, hipStr
     const int64_t gXs = GR * GR, gL = GR * (h->mp + 1), gSs = (GR / 2) * (GR / 2);   // group strides in X/XT, L, S
     double* gXT = h->gXT + g0 * gXs; double* gX = h->gX + g0 * gXs; double* gS = h->gS + g0 * gSs;
     const double* Lg = h->B + g0 * gL;
+    const bool three_launches = h->ginv_ref || g_gemm_recorder;
     for (int hs = 128; hs < GR; hs *= 2) {
         const int np = (int)(GR / (2 * hs));              // pairs per group
-        GemmNT t = gemm_defaults();
-        t.done = done;
-        t.M = hs; t.N = hs; t.K = hs; t.batch = np; t.batch2 = nG;
         const int64_t pX = (int64_t)2 * hs * (GR + 1);                                 // pair strides in X, XT
         const int64_t pL = (int64_t)2 * hs * (h->mp + 1);
         const int64_t pS = (int64_t)hs * hs;
-        GemmNT a = t;                                     // S = XT11 * L21^T
+        if (!three_launches) {
+            GinvGemm a{};                                 // S = XT11 * L21^T
+            a.hs = hs; a.alpha = 1.0; a.done = done;
+            a.P = gXT; a.ldp = GR; a.sP = pX; a.sP2 = gXs;
+            a.Q = Lg + (int64_t)hs * h->mp; a.ldq = h->mp; a.sQ = pL; a.sQ2 = gL;
+            a.C = gS; a.ldc = hs; a.sC = pS; a.sC2 = gSs;
+            HIP_TRY(h, launch_ginv_gemm<false>(a, np, nG, st));
+            GinvGemm b{};                                 // X21 = -X22 * S^T and XT12 = -S * X22^T
+            b.hs = hs; b.alpha = -1.0; b.done = done;
+            b.P = gX + (int64_t)hs * GR + hs; b.ldp = GR; b.sP = pX; b.sP2 = gXs;
+            b.Q = gS; b.ldq = hs; b.sQ = pS; b.sQ2 = gSs;
+            b.C = gX + (int64_t)hs * GR; b.ldc = GR; b.sC = pX; b.sC2 = gXs;
+            b.CT = gXT + hs; b.ldct = GR; b.sCT = pX; b.sCT2 = gXs;
+            HIP_TRY(h, launch_ginv_gemm<true>(b, np, nG, st));
+            continue;
+        }
+        GemmNT t = gemm_defaults();
+        t.done = done;
+        t.M = hs; t.N = hs; t.K = hs; t.batch = np; t.batch2 = nG;
+        GemmNT a = t;                                    // S = XT11 * L21^T
         a.P = gXT; a.ldp = GR; a.sP = pX; a.sP2 = gXs;
         a.Q = Lg + (int64_t)hs * h->mp; a.ldq = h->mp; a.sQ = pL; a.sQ2 = gL;
         a.C = gS; a.ldc = hs; a.sC = pS; a.sC2 = gSs;

@@ -208,6 +208,17 @@ extern "C" int ipm_debug_get_block_inverse(ipm_handle* h, int32_t k, double* out
     return IPM_OK;
 }
 
+extern "C" int ipm_debug_get_group_inverse(ipm_handle* h, int32_t g, int32_t which, double* out) {
+    if (!h || !out || which < 0 || which > 1) return fail(h, IPM_ERR_INVALID_ARG, "ipm_debug_get_group_inverse: bad arguments");
+    if (!h->grouped_trsv || !h->gX || !h->gXT) return fail(h, IPM_ERR_STATE, "the handle holds no group inverses");
+    if (g < 0 || g >= h->nblk / h->gsz) return fail(h, IPM_ERR_INVALID_ARG, "ipm_debug_get_group_inverse: no such group");
+    const size_t GR = (size_t)h->gsz * 128;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpyAsync(out, (which ? h->gXT : h->gX) + (size_t)g * GR * GR, sizeof(double) * GR * GR, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return IPM_OK;
+}
+
 extern "C" int ipm_debug_ff_trace(ipm_handle* h, long long* out, int64_t capacity, int64_t* count, unsigned char* items, int32_t* nitems) {
     if (!h || !count) return fail(h, IPM_ERR_INVALID_ARG, "ipm_debug_ff_trace: bad arguments");
     if (!h->ff_trace || !h->ff_built) return fail(h, IPM_ERR_STATE, "no item trace (IPM_FF_TRACE_ITEMS=1 at ipm_create, fused path)");

@@ -124,6 +124,7 @@ struct ipm_handle {
     // IPM_FF_MAX_NBLK / IPM_FUSED_FACTOR=force|0 override.
     int ff_min_nblk = 16, ff_max_nblk = 72;
     bool ff_forced = false;
+    bool ginv_ref = false;                // IPM_GINV_REF=1: the group inverses as three launches of the generic kernel per level, the reference of tests/test_gpu_group_inverse.py
     bool ff_ref_engine = false;           // IPM_FF_REF_ENGINE=1: form_factor_roles_kernel (the engines' previous stage schedule), the reference of tests/test_gpu_ff_engines.py
     int ff_q = 4;                         // formation chunks per tile (IPM_FF_Q)
     int ff_workers = 0;                   // WORKER workgroups of the persistent launch (set by ff_build from the CU count, no switch)

@@ -26,6 +26,7 @@
 #include "potrf_f64.h"
 #include "sparse_ops.h"
 #include "trsv_grouped.h"
+#include "ginv_gemm_f64.h"
 #include "getrf_f64.h"
 #include "small_lp.h"
 #include "sparse_chol.h"
@@ -123,7 +124,8 @@ static void read_env_switches(ipm_handle* h) {
     if (const char* e = getenv("IPM_FF_MAX_NBLK")) h->ff_max_nblk = atoi(e);
     if (const char* e = getenv("IPM_FF_CHAIN_MODE")) h->ff_chain_mode0 = atoi(e) == 0;
     if (const char* e = getenv("IPM_FF_REF_ENGINE")) h->ff_ref_engine = atoi(e) != 0;
-    if (const char* e = getenv("IPM_FF_Q")) h->ff_q = std::max(1, std::min(16, atoi(e)));
+    if (const char* e = getenv("IPM_GINV_REF")) h->ginv_ref = atoi(e) != 0;
+    if (const char* e = getenv("IPM_FF_Q"))h->ff_q = std::max(1, std::min(16, atoi(e)));
     if (const char* e = getenv("IPM_STREAM_AT")) h->stream_at = atoi(e);
 }
 
@@ -612,7 +614,7 @@ extern "C" int ipm_get_history(ipm_handle* h, ipm_iter_record* out, int32_t capa
     return IPM_OK;
 }
 
-static const int SCHEDULE_WORDS = 13;
+static const int SCHEDULE_WORDS = 14;
 extern "C" int ipm_get_schedule_words(ipm_handle* h, int32_t* out, int32_t capacity, int32_t* count) {
     if (!h || !out || capacity < 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_schedule_words: bad arguments");
     const int live = live_on_device(h);
@@ -623,6 +625,7 @@ extern "C" int ipm_get_schedule_words(ipm_handle* h, int32_t* out, int32_t capac
     w[8] = h->timeouts_recovered; w[9] = h->small ? 1 : 0;
     w[10] = h->ff_last ? 1 : 0; w[11] = (h->spf && sp_level(h)) ? 1 : 0;
     w[12] = stream_at_on(h) ? 1 : 0;
+    w[13] = h->grouped_trsv ? h->gsz : 0;
     const int n = std::min<int>(capacity, SCHEDULE_WORDS);
     memcpy(out, w, sizeof(int32_t) * (size_t)n);
     if (count) *count = n;

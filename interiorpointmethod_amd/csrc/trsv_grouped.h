@@ -5,9 +5,12 @@
 // the factor's diagonal is regrouped into 1024 x 1024 lower-triangular blocks D_g whose explicit
 // inverses X_g = inv(D_g) are assembled right after the factorization from the 128-block inverses
 // the Cholesky already produced (batched MFMA GEMMs over all groups):
-// by recursive doubling (128 -> 256 -> 512 -> 1024), three batched NT GEMMs per level that keep both
-// X and XT = X^T current (the K-contiguous "NT" kernel needs one operand of each kind):
+// by recursive doubling (128 -> 256 -> 512 -> 1024), three batched NT products per level that keep both
+// X and XT = X^T current (a K-contiguous "NT" product needs one operand of each kind):
 //     S   = XT11 * L21^T ;   X21 = -X22 * S^T ;   XT12 = -S * X22^T        ( = inv([[L11,0],[L21,L22]]) )
+// in two launches per level: one for S, one that produces X21 and XT12 from the same operand fragments (ginv_gemm_f64.h;
+// the three launches of the generic kernel they replace compute the same bits and stay as the recorded lockstep program
+// and as the reference, IPM_GINV_REF=1).
 // A solve is then 4 group steps of dense GEMVs at HBM speed instead of 32 block steps:
 //     forward : z_g = X_g r_g ;  r_below -= L[below, g] z_g
 //     backward: w_g = XT_g z_g ;  z_left  -= L[g, left]^T w_g

@@ -466,10 +466,10 @@ class IpmSolver:
 
     def schedule(self):
         """How the handle runs its factorization (ipm_get_schedule): dict for tests and diagnostics."""
-        out = (C.c_int32 * 13)()
-        self._check(self._lib.ipm_get_schedule_words(self._h, out, 13, None))
+        out = (C.c_int32 * 14)()
+        self._check(self._lib.ipm_get_schedule_words(self._h, out, 14, None))
         keys = ("blocks", "group_steps", "grouped_trsv", "device_polling", "counter_steps", "event_steps", "envelope",
-                "live_handles", "timeouts_recovered", "fused_small", "fused_factor", "sparse_level_mode", "stream_at")
+                "live_handles", "timeouts_recovered", "fused_small", "fused_factor", "sparse_level_mode", "stream_at", "group_blocks")
         return dict(zip(keys, (int(v) for v in out)))
 
     def factor_info(self):
@@ -536,6 +536,15 @@ class IpmSolver:
         L = np.empty((self.m, self.m))
         self._check(self._lib.ipm_get_factor(self._h, _dptr(L), self.m))
         return L
+
+    def debug_group_inverse(self, g, which=0):
+        """ipm_debug_get_group_inverse (test hook): the explicit inverse of diagonal group g of the current dense factor, whole
+        (zero triangle included): which = 0 X_g = inv(L_gg), which = 1 XT_g, its transpose; schedule()["group_blocks"] blocks of
+        128 rows each way."""
+        rows = 128 * self.schedule()["group_blocks"]
+        out = np.empty((rows, rows))
+        self._check(self._lib.ipm_debug_get_group_inverse(self._h, int(g), int(which), _dptr(out)))
+        return out
 
     def normal_solve(self, rhs, d=None, reuse_factor=False):
         """z with (A diag(d) A^T) z = rhs on the device (d = None: ones); reuse_factor keeps the previous factor."""
