@@ -99,7 +99,16 @@ enum {
      * bit until it stops.  They certify what the infeasible-start iteration runs towards and do not guarantee detection: an LP
      * whose iterate overflows before its ray is clean still ends in IPM_STATUS_NAN.  Without the flag the kernels are
      * exactly those of a build without this feature.  A flagged handle may join the lockstep batch, next to unflagged ones. */
-    IPM_FLAG_DETECT_INFEASIBILITY = 32
+    IPM_FLAG_DETECT_INFEASIBILITY = 32,
+    /* A handle that qualifies for the fused small path (sparse A of at most 128 rows, a product list of at most 2^22 terms) keeps
+     * that path when it holds a quadratic term (ipm_set_quadratic): the whole loop of the QP runs in one launch of one workgroup
+     * (the Quad variants of the small kernel), and the handle may join ipm_solve_small_batch next to LP handles.
+     * Off by default: the small loop and the multi-kernel path sum in different orders, so their iterates agree to rounding, not bit
+     * for bit.  The flag alone changes nothing: a flagged handle without a term (never set, or cleared with NULL / all zeros) runs
+     * the LP kernels, bit for bit what an unflagged handle runs, and a handle that does not qualify for the small path ignores the
+     * flag.  It lifts no refusal: a term with IPM_FLAG_DETECT_INFEASIBILITY or IPM_FLAG_LOCKSTEP, centrality correctors, refinement
+     * rounds and dense columns on the small path are refused as without it. */
+    IPM_FLAG_SMALL_QUADRATIC = 64
 };
 
 typedef struct ipm_handle ipm_handle;
@@ -229,8 +238,10 @@ int ipm_get_bound_state(ipm_handle* h, double* w, double* z);
  * and the history is c^T x + 1/2 x^T diag(g) x, the stop test is unchanged, and the iteration takes ONE step length: alpha_p ==
  * alpha_d and alpha_aff_p == alpha_aff_d (the minimum of the pair) in ipm_stats and the history.  The vector is allocated by the
  * library on first use and freed by ipm_destroy; the workspace size does not change.  Invalidates a pending predictor.
- * Never the fused small-LP path: ipm_set_A_csc does not choose it for a handle that holds a term, and a nonzero g on a handle
- * already on that path is IPM_ERR_INVALID_ARG (set the term before A); clearing is always accepted.
+ * The fused small-LP path is off unless IPM_FLAG_SMALL_QUADRATIC: without the flag ipm_set_A_csc does not choose it for a handle
+ * that holds a term, and a nonzero g on a handle already on that path is IPM_ERR_INVALID_ARG (set the term before A); with the
+ * flag the handle keeps the path in either order of the two calls and runs the Quad variants of the small kernel while it holds a
+ * term.  Clearing is always accepted.
  * Refused with IPM_ERR_INVALID_ARG and a reason in ipm_last_error, never dropped: a nonzero g on an IPM_FLAG_LOCKSTEP handle (no
  * batched twins), on an IPM_FLAG_DETECT_INFEASIBILITY handle (the tests are not restated for a QP) and on a handle with
  * ipm_set_centrality_correctors(k > 0) (their accept rule compares step pairs); ipm_set_centrality_correctors(k > 0) refuses a
@@ -317,7 +328,8 @@ int ipm_batch_stats(ipm_batch* b, int32_t index, ipm_stats* stats);
  * sides, the AFIRO class of Netlib) fill the GPU's compute units where a loop of ipm_solve keeps one of them busy.  Every handle must be
  * served by that path (ipm_get_schedule out[9] == 1), live on the same device, have A, b, c and a state set and profiling off
  * (IPM_ERR_STATE otherwise); handles with upper bounds (ipm_set_bounds), with IPM_FLAG_DETECT_INFEASIBILITY and plain ones may be mixed
- * freely in one call.  IPM_ERR_INVALID_ARG, with the offending index in ipm_last_error(NULL), for a NULL handle, a handle that is not on
+ * freely in one call, and so may handles that hold a quadratic term on this path (IPM_FLAG_SMALL_QUADRATIC, bounded or not: six kernel
+ * variants in all).  IPM_ERR_INVALID_ARG, with the offending index in ipm_last_error(NULL), for a NULL handle, a handle that is not on
  * the small path, a handle on another device and the same handle twice (two workgroups would race on one state); n < 0 or handles ==
  * NULL with n > 0 likewise; n == 0 returns IPM_OK and touches no device.  stream: a hipStream_t ON THE HANDLES' DEVICE the launches go to
  * (the caller's to guarantee: a stream does not tell its device), NULL = the first handle's stream; the handles may own any streams -- the batch stream waits (stream events) for each distinct one before the launch,

@@ -48,6 +48,8 @@ def _solve_info(solver, history=False, certificate=False):
     info["refine"] = solver.refine_info()
     info["dense_cols"] = solver.dense_split_info()          # None: no dense-column split ran
     info["quadratic"] = solver.quadratic_nonzeros()         # positive entries of the quadratic term's diagonal (0: an LP)
+    # the path that served a quadratic term: "small" (the one-workgroup loop, quad_small=True) or "multi-kernel"; None for an LP
+    info["quadratic_path"] = None if not info["quadratic"] else "small" if solver.schedule()["fused_small"] else "multi-kernel"
     if solver.scale is not None:
         info["scale"] = dict(solver.scale_info)
         info["rp_unscaled"], info["rd_unscaled"] = unscaled_residuals(solver)
@@ -84,7 +86,7 @@ def _auto_regularize():          # the process-wide switch of the 5 % rule (hand
 
 def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
                     history=False, ub=None, detect_infeasibility=False, device_start=False, scale=None, scale_passes=SCALE_PASSES,
-                    correctors=0, refine=0, dense_cols=None, quad=None, **opts):
+                    correctors=0, refine=0, dense_cols=None, quad=None, quad_small=False, **opts):
     """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
     start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start(), or with
     device_start=True IpmSolver.init_state_mehrotra(): the same start computed on the device (no host copy of A, one
@@ -104,7 +106,9 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     info["dense_cols"] = IpmSolver.dense_split_info() (None where no split ran).
     quad: None (default) or the diagonal g >= 0 of a separable quadratic term: min c.x + 1/2 x.diag(g) x (IpmSolver; DESIGN.md
     4-Q); info["quadratic"] = its positive entries, info["objective"] includes the term.  Refused (ValueError) together with
-    detect_infeasibility and correctors > 0; start="mehrotra" ignores g."""
+    detect_infeasibility and correctors > 0; start="mehrotra" ignores g.
+    quad_small=True (off by default): a sparse problem of at most 128 rows keeps the fused small path with its term (IpmSolver,
+    IPM_FLAG_SMALL_QUADRATIC); info["quadratic_path"] says which path served the term: "small", "multi-kernel", or None for an LP."""
     global _last_info
     correctors = check_correctors(correctors)
     refine = check_refine(refine)
@@ -114,6 +118,8 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
         opts = dict(opts, scale=scale, scale_passes=scale_passes)
     if dense_cols is not None:
         opts = dict(opts, dense_cols=dense_cols)
+    if quad_small:
+        opts = dict(opts, quad_small=True)
     quad = check_quadratic(quad, np.asarray(c).reshape(-1).shape[0])
     if quad is not None:
         if detect_infeasibility:
@@ -156,11 +162,12 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
 
 
 def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None,
-          quad=None, **opts):
+          quad=None, quad_small=False, **opts):
     """min c^T x (+ 1/2 x^T diag(quad) x) s.t. Ax=b, x>=0 (and x <= ub where ub is finite) by the Mehrotra predictor-corrector loop
-    on the GPU -> (x, y, s)."""
+    on the GPU -> (x, y, s).  quad_small: as solve_with_info."""
     x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub, scale=scale,
-                                 scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad, **opts)
+                                 scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad,
+                                 quad_small=quad_small, **opts)
     return x, y, s
 
 

@@ -7,7 +7,7 @@ from . import _lib
 from .analysis import FUSED_SMALL_MAX_ROWS, _sp, _upper_bounds
 from .api import _auto_regularize, _solve_info
 from .analysis import refuse_dense_cols
-from .handle import SCALE_PASSES, IpmSolver, _gap_tol, check_scale, refuse_correctors, refuse_refine, wants_shift
+from .handle import SCALE_PASSES, IpmSolver, _gap_tol, check_quadratic, check_scale, refuse_correctors, refuse_refine, wants_shift
 
 
 def _handle_array(solvers):           # (the handles as a C array, a Stats array of the same length) for one batched library call
@@ -93,14 +93,16 @@ def lockstep_eligible(solver):
 
 def small_batch_eligible(solver):
     """Can this IpmSolver join solve_small_batch_solvers?  The library serves it with the fused single-workgroup kernel (sparse A of
-    at most 128 rows whose product list fits: ipm_get_schedule out[9] == 1).  Bounds and infeasibility detection do not matter."""
+    at most 128 rows whose product list fits: ipm_get_schedule out[9] == 1).  Bounds and infeasibility detection do not matter; a
+    solver with a quadratic term is on that path, and eligible, only when it was created with quad_small=True."""
     return bool(solver.schedule()["fused_small"])
 
 
 def solve_small_batch_solvers(solvers, tol=1e-8, max_iter=5000, tol_gap=None, stream=None, correctors=0, refine=0, dense_cols=None):
     """ipm_solve_small_batch: solve the LPs of `solvers` (IpmSolver objects on the fused small-LP path, one device, a state set) in ONE
     launch per kernel variant, one workgroup per LP -> list of statistics dicts, one per solver (also in solver.stats).  Plain,
-    bounded and detect_infeasibility solvers may be mixed.  Per-LP semantics and arithmetic are those of IpmSolver.solve on each of
+    bounded and detect_infeasibility solvers may be mixed, and so may solvers that hold a quadratic term on the small path
+    (IpmSolver(..., quad=g, quad_small=True), bounded or not: the two Quad variants of the kernel).  Per-LP semantics and arithmetic are those of IpmSolver.solve on each of
     them alone (bit-identical iterates); get_state / get_bound_state / history / certificate work afterwards as after solve().  The
     solvers stay alive: set_state / init_state and another call re-solve them.  stream: a torch.cuda.Stream for the launches
     (None: the first solver's stream).  ValueError, naming the index, for a solver that is not on the small path, and for
@@ -212,6 +214,74 @@ def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_g
                     solvers[i].init_state_mehrotra()
         solve_small_batch_solvers(solvers, tol=tol, max_iter=max_iter, tol_gap=tol_gap)
         return [sv.get_state() + (_solve_info(sv, certificate=detect_infeasibility),) for sv in solvers]
+    finally:
+        for sv in solvers:
+            sv.close()
+
+
+SMALL_TERM_LIMIT = 1 << 22            # ipm_set_A_csc: a product list of more terms leaves the small path (csrc/host_sparse_setup.h)
+
+
+def _small_qp_batch_host_check(problems, ub):
+    """Host part of solve_small_qp_batch (no device is touched): _small_batch_host_check plus the quadratic diagonals ->
+    list of (A as CSC, b, c, ub, g or None)."""
+    problems = list(problems)
+    for i, p in enumerate(problems):
+        if len(p) != 4:
+            raise ValueError("problem %d: expected (A, b, c, g), got %d entries" % (i, len(p)))
+    checked = _small_batch_host_check([(A, b, c) for A, b, c, _ in problems], ub)
+    out = []
+    for i, ((A, b, c, u), (_, _, _, g)) in enumerate(zip(checked, problems)):
+        try:
+            g = check_quadratic(g, A.shape[1])
+        except ValueError as e:
+            raise ValueError("problem %d: %s" % (i, e)) from e
+        cnt = np.diff(A.indptr).astype(np.int64)                # a column of c entries feeds c (c + 1) / 2 terms of the product list
+        terms = int((cnt * (cnt + 1) // 2).sum())
+        if terms > SMALL_TERM_LIMIT:
+            raise ValueError("problem %d: the product list of A D^2 A^T has %d terms, the fused small path takes at most %d"
+                             % (i, terms, SMALL_TERM_LIMIT))
+        out.append((A, b, c, u, g))
+    return out
+
+
+def solve_small_qp_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, ub=None, regularize=0.0, start="reference",
+                         scale=None, scale_passes=SCALE_PASSES):
+    """Solve many small separable convex QPs at once -> list of (x, y, s, info), one per problem, each what
+    solve_with_info(A, b, c, quad=g, quad_small=True) returns for it alone.
+
+    problems: list of (A, b, c, g) with at most 128 rows each: min c.x + 1/2 x.diag(g) x, A x = b, x >= 0 (x <= ub); a dense A is
+    converted to CSC.  g: the diagonal, length n, finite and >= 0; None or all zeros is an LP, and LPs may sit in the same list.
+    ub, y0, start, regularize, scale: as solve_small_batch (Mehrotra's start ignores g).  Built like solve_small_batch: the host
+    check before any device is touched, one IpmSolver(quad=g, quad_small=True) per problem, ONE ipm_solve_small_batch call (one
+    workgroup per problem, one grid per kernel variant present), read-back, close.  Every problem error is a ValueError naming the
+    problem's index: a bad shape, more than 128 rows, a negative or non-finite g, a product list too large for the path.  The
+    front end has no detect_infeasibility (the tests are the LP's), and correctors, refine and dense_cols are not parameters: the
+    one-workgroup loop runs none of them."""
+    if start not in ("reference", "mehrotra"):
+        raise ValueError('start must be "reference" or "mehrotra"')
+    check_scale(scale)
+    checked = _small_qp_batch_host_check(problems, ub)
+    make = lambda A, b, c, u, g, reg: IpmSolver(A, b, c, device=device, regularize=reg, ub=u, scale=scale, scale_passes=scale_passes,          # noqa: E731
+                                                quad=g, quad_small=True)
+    solvers = []
+    try:
+        for i, p in enumerate(checked):
+            sv = make(*p, regularize)
+            solvers.append(sv)
+            if not small_batch_eligible(sv):
+                raise ValueError("problem %d (%d x %d) is not served by the fused small path (its product list is too large)"
+                                 % (i, sv.m, sv.n))
+            if start == "reference":
+                sv.init_state(y0)
+        if start == "mehrotra":
+            for i, nfix in enumerate(init_small_batch_mehrotra(solvers)):
+                if wants_shift(nfix, solvers[i].m, regularize, _auto_regularize()):
+                    solvers[i].close()
+                    solvers[i] = make(*checked[i], 1e-14)
+                    solvers[i].init_state_mehrotra()
+        solve_small_batch_solvers(solvers, tol=tol, max_iter=max_iter, tol_gap=tol_gap)
+        return [sv.get_state() + (_solve_info(sv),) for sv in solvers]
     finally:
         for sv in solvers:
             sv.close()

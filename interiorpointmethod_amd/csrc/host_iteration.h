@@ -472,13 +472,15 @@ static SmallLP small_args(ipm_handle* h, int max_steps, int auto_reg) {
     return a;
 }
 
-static int small_variant(const ipm_handle* h) { return (h->bnd ? SMALL_BOUNDED : 0) | (h->detect ? SMALL_DETECT : 0); }
+// (a quadratic term never meets detect: ipm_set_quadratic refuses the pair, so 4 | 2 does not occur)
+static int small_variant(const ipm_handle* h) { return (h->bnd ? SMALL_BOUNDED : 0) | (h->detect ? SMALL_DETECT : 0) | (h->quad ? SMALL_QUAD : 0); }
 static SmallItem small_item(ipm_handle* h, int index, int max_steps, int auto_reg) {
     SmallItem it;
     memset(&it, 0, sizeof it);
     it.lp = small_args(h, max_steps, auto_reg);
     if (h->bnd) it.bd = bnd_args(h);
     it.dt = det_args(h);
+    it.g = h->quad ? h->quad_g : nullptr;
     it.eta = h->opt.eta;
     it.variant = small_variant(h);
     it.index = index;
@@ -491,7 +493,9 @@ static void launch_small(int v, hipStream_t S, const SmallItem* one, const Small
     if (v == SMALL_PLAIN) { if (one) hipLaunchKernelGGL(small_lp_kernel, g, b, 0, S, one->lp); else hipLaunchKernelGGL(small_lp_batch_kernel, g, b, 0, S, d_items); }
     else if (v == SMALL_BOUNDED) { if (one) hipLaunchKernelGGL(small_lp_bounded_kernel, g, b, 0, S, one->lp, one->bd); else hipLaunchKernelGGL(small_lp_batch_bounded_kernel, g, b, 0, S, d_items); }
     else if (v == SMALL_DETECT) { if (one) hipLaunchKernelGGL(small_lp_detect_kernel, g, b, 0, S, one->lp, one->dt); else hipLaunchKernelGGL(small_lp_batch_detect_kernel, g, b, 0, S, d_items); }
-    else { if (one) hipLaunchKernelGGL(small_lp_bounded_detect_kernel, g, b, 0, S, one->lp, one->bd, one->dt); else hipLaunchKernelGGL(small_lp_batch_bounded_detect_kernel, g, b, 0, S, d_items); }
+    else if (v == SMALL_BOUNDED_DETECT) { if (one) hipLaunchKernelGGL(small_lp_bounded_detect_kernel, g, b, 0, S, one->lp, one->bd, one->dt); else hipLaunchKernelGGL(small_lp_batch_bounded_detect_kernel, g, b, 0, S, d_items); }
+    else if (v == SMALL_QUAD) { if (one) hipLaunchKernelGGL(small_qp_kernel, g, b, 0, S, one->lp, one->g); else hipLaunchKernelGGL(small_lp_batch_quad_kernel, g, b, 0, S, d_items); }
+    else { if (one) hipLaunchKernelGGL(small_qp_bounded_kernel, g, b, 0, S, one->lp, one->bd, one->g); else hipLaunchKernelGGL(small_lp_batch_bounded_quad_kernel, g, b, 0, S, d_items); }
 }
 
 // whole loop of a small sparse LP in one launch of one workgroup (small_lp.h)

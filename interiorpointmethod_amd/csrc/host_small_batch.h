@@ -19,7 +19,7 @@ static int small_batch_round(ipm_handle* h0, ipm_handle** hs, const std::vector<
         return small_cost(hs[a]) > small_cost(hs[b]);
     });
     items.resize((size_t)cnt);
-    int count[SMALL_NVARIANTS] = {0, 0, 0, 0};
+    int count[SMALL_NVARIANTS] = {};
     for (int p = 0; p < cnt; ++p) {
         ipm_handle* h = hs[order[(size_t)p]];
         const bool may_auto = h->opt.regularize == 0.0 && !(h->opt.flags & IPM_FLAG_NO_AUTO_REGULARIZE);

@@ -466,7 +466,7 @@ extern "C" int ipm_set_quadratic(ipm_handle* h, const double* g) {
     if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle was created with IPM_FLAG_LOCKSTEP (the Quad kernels have no batched twins)");
     if (h->detect) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the dual ray of a QP also needs g o x = 0; the tests are not restated)");
     if (h->mcc.k > 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: %d centrality correctors are set (their accept rule compares step pairs, a quadratic handle takes one step; ipm_set_centrality_correctors(h, 0))", h->mcc.k);
-    if (h->small) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle runs the fused small-LP kernel, which has no quadratic term; set the term before A (ipm_set_A_csc then takes the multi-kernel path)");
+    if (h->small && !(h->opt.flags & IPM_FLAG_SMALL_QUADRATIC)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle runs the fused small-LP kernel, which has no quadratic term; set the term before A (ipm_set_A_csc then takes the multi-kernel path)");
     const size_t np = (size_t)h->np;
     std::vector<double> gg(np, 0.0);
     std::copy(g, g + h->n, gg.begin());

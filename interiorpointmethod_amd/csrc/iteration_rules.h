@@ -78,6 +78,8 @@ __device__ __forceinline__ double pair_count(int n, const BndArgs& bd) { return 
 //                  residual would keep a term (alpha_d - alpha_p) g o dx that no later Newton step is aimed at
 // With that d and that r_c the predictor's v, direction_column, corrector_column, the right-hand side -r_b - A v and the recovery
 // keep the LP's formulas (eliminating ds = -(r_3 + s dx)/x from A^T dy + ds - dz - g o dx = -r_c only adds g to the diagonal).
+// Both paths use them: the Quad kernels of vector_ops.h, and the Quad variants of the one-workgroup loop (small_lp.h,
+// IPM_FLAG_SMALL_QUADRATIC), whose residual_cols applies the first three and whose loop applies the step rule to both pairs.
 __device__ __forceinline__ double quad_rc(double rc_lp, double g, double x) { return rc_lp - g * x; }
 __device__ __forceinline__ double quad_theta(double x, double s, double g) { return x / (s + g * x); }
 __device__ __forceinline__ double quad_bnd_theta(double x, double s, double w, double z, double g) { return 1.0 / (s / x + z / w + g); }

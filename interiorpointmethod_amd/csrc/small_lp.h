@@ -18,6 +18,8 @@
 // mathematics, constants and stop test.  This file owns what this path does around the rules: A and the vectors
 // as placed above, (A^T y)_j as a CSC dot product with y in LDS, the normal equations, and the reductions.  Their summation orders
 // differ from the multi-kernel path's, so iterates agree to rounding, not bit for bit (tests compare both against the reference).
+// residual_cols is the hand-kept second copy of the predictor column (iteration_rules.h): its Quad branches are kept in step with
+// prepare_kernel_body<..., Quad> of vector_ops.h.
 // Below the loop: Mehrotra's starting point of such an LP in one launch (small_start_body), single and batched.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -76,8 +78,12 @@ __device__ __forceinline__ void block_reduce512(double (&v)[NV], double* red) {
 // the same reductions (r_u^2 into ||r_b||^2, w.z into x.s, the w / z ratios into the step minima); no extra LDS.
 // Detect = true: the infeasibility tests (detect_fire) in the stop test, from sums and maxima the residual passes
 // gather on the side (b.y, u_U.z_U, max (A^T y - z)_+, max |A x|, max x_U).
-template <bool Bounded, bool Detect = false>
-__device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt = DetArgs{}) {
+// Quad = true: a diagonal quadratic term g (the handle's quad_g; IPM_FLAG_SMALL_QUADRATIC): r_c, d and the objective
+// by the quad_* rules in residual_cols, and one step length (quad_step) wherever a (primal, dual) pair is held.  Everything else
+// -- the formation from d, the factorization, both matvecs, the direction, the corrector and the stop test -- is the LP's.
+template <bool Bounded, bool Detect = false, bool Quad = false>
+__device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt = DetArgs{}, const double* g = nullptr) {
+    static_assert(!(Quad && Detect), "the infeasibility tests are not restated for a quadratic term");
     __shared__ __attribute__((aligned(16))) double W[NB * WLD];
     __shared__ double dinv_s[NB];
     __shared__ double ys[NB], rbs[NB], t1s[NB], zs[NB], dys[NB];
@@ -115,7 +121,8 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
         }
         return rb2;
     };
-    // r_c, d, q, v and the partial sums of ||r_c||^2, x.s, c.x
+    // r_c, d, q, v and the partial sums of ||r_c||^2, x.s, c.x  (Quad: the same column as prepare_kernel_body<..., Quad> of
+    // vector_ops.h -- quad_rc, quad_theta / quad_bnd_theta, quad_objective; v keeps its formula with the new r_c and d)
     double ru2 = 0.0;                                   // bounded: this thread's share of ||r_u||^2 (residual_cols)
     double *DWp = nullptr, *DZp = nullptr;              // bounded: where direction() puts (dw, dz)
     auto residual_cols = [&](double& rc2, double& xs, double& cx) {
@@ -128,12 +135,14 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
                 // one straight-line update of the four sums for both kinds of column (with a `continue` per kind the
                 // accumulators were left in scratch memory)
                 const double uj = bd.u[j];
-                double rcj = w + sj - cj, dj = xj / sj, vj, r4 = 0.0, ru_j2 = 0.0;
+                double rcj = w + sj - cj, dj = xj / sj, vj, r4 = 0.0, ru_j2 = 0.0, gj = 0.0;
+                if constexpr (Quad) { gj = g[j]; rcj = quad_rc(rcj, gj, xj); dj = quad_theta(xj, sj, gj); }
                 const double r3 = xj * sj, qj = r3 / xj;
                 if (bnd_in(uj)) {
                     const double wj = bd.w[j], zj = bd.z[j];
                     const double ruj = xj + wj - uj;
                     rcj = w + sj - zj - cj; dj = bnd_theta(xj, sj, wj, zj); r4 = wj * zj; ru_j2 = ruj * ruj;
+                    if constexpr (Quad) { rcj = quad_rc(rcj, gj, xj); dj = quad_bnd_theta(xj, sj, wj, zj, gj); }
                     bd.qz[j] = r4 / wj;
                     vj = dj * (rcj - qj + (r4 - zj * ruj) / wj);
                     if constexpr (Detect) { duz += uj * zj; dmaty = fmax(dmaty, w - zj); dmxu = fmax(dmxu, xj); }
@@ -142,7 +151,11 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
                     if constexpr (Detect) dmaty = fmax(dmaty, w);
                 }
                 a.rc[j] = rcj; a.d[j] = dj; a.q[j] = qj; a.v[j] = vj;
-                rc2 += rcj * rcj; xs += r3; xs += r4; cx += cj * xj; ru2 += ru_j2;
+                rc2 += rcj * rcj; xs += r3; xs += r4; cx += Quad ? quad_objective(cj, gj, xj) : cj * xj; ru2 += ru_j2;
+            } else if constexpr (Quad) {
+                const double gj = g[j], rcj = quad_rc(w + sj - cj, gj, xj), dj = quad_theta(xj, sj, gj), r3 = xj * sj;
+                a.rc[j] = rcj; a.d[j] = dj; a.q[j] = r3 / xj; a.v[j] = dj * (rcj - r3 / xj);
+                rc2 += rcj * rcj; xs += r3; cx += quad_objective(cj, gj, xj);
             } else {
                 const double rcj = w + sj - cj, dj = xj / sj, r3 = xj * sj;
                 a.rc[j] = rcj; a.d[j] = dj; a.q[j] = r3 / xj; a.v[j] = dj * (rcj - r3 / xj);
@@ -282,7 +295,8 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
         if constexpr (Bounded) { DWp = bd.dwa; DZp = bd.dza; }
         direction(a.dxa, a.dsa, mn[0], mn[1]);
         block_reduce512<2, true>(mn, red);
-        const double aap = mn[0], aad = mn[1];
+        double aap = mn[0], aad = mn[1];
+        if constexpr (Quad) aap = aad = quad_step(aap, aad);                 // one step length
         double ma[1] = {0.0};
         for (int j = tid; j < n; j += PD_THREADS) mu_aff_column<Bounded>(a, bd, j, aap, aad, ma[0]);
         block_reduce512<1, false>(ma, red);
@@ -298,7 +312,8 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
         block_reduce512<2, true>(mc, red);
         // ---------------------------------------------------------------- damped step
         const double eta = sc->eta;
-        const double ap = damped_step(eta, mc[0]), ad = damped_step(eta, mc[1]);
+        double ap = damped_step(eta, mc[0]), ad = damped_step(eta, mc[1]);
+        if constexpr (Quad) ap = ad = quad_step(ap, ad);
         for (int j = tid; j < n; j += PD_THREADS) update_column<Bounded>(a, bd, j, ap, ad);
         if (tid < m) ys[tid] += ad * dys[tid];
         if (tid == 0) {
@@ -315,33 +330,38 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) { small
 __global__ __launch_bounds__(PD_THREADS) void small_lp_bounded_kernel(SmallLP a, BndArgs bd) { small_lp_body<true>(a, bd); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_detect_kernel(SmallLP a, DetArgs dt) { small_lp_body<false, true>(a, BndArgs{}, dt); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_bounded_detect_kernel(SmallLP a, BndArgs bd, DetArgs dt) { small_lp_body<true, true>(a, bd, dt); }
+__global__ __launch_bounds__(PD_THREADS) void small_qp_kernel(SmallLP a, const double* g) { small_lp_body<false, false, true>(a, BndArgs{}, DetArgs{}, g); }
+__global__ __launch_bounds__(PD_THREADS) void small_qp_bounded_kernel(SmallLP a, BndArgs bd, const double* g) { small_lp_body<true, false, true>(a, bd, DetArgs{}, g); }
 
 // ------------------------------------------------------------------------------- batch of small LPs (ipm_solve_small_batch)
 // One launch, one workgroup per LP: workgroup blockIdx.x reads item blockIdx.x of a table in device memory -- the arguments the
 // single-LP kernel gets in its kernel-argument segment -- and runs the SAME body on it.  The workgroups never talk to each other
 // (no atomics, no polling), so the dispatcher may run them in any order and in any number of rounds over the compute units; an LP's
-// arithmetic is that of its one-at-a-time launch, bit for bit.  The body keeps ~133 KB of static LDS per instantiation, so the four
-// variants stay four kernels: the host sorts the table by variant and launches one grid per variant present.
-enum { SMALL_PLAIN = 0, SMALL_BOUNDED = 1, SMALL_DETECT = 2, SMALL_BOUNDED_DETECT = 3, SMALL_NVARIANTS = 4 };
+// arithmetic is that of its one-at-a-time launch, bit for bit.  The body keeps ~133 KB of static LDS per instantiation, so the six
+// variants stay six kernels: the host sorts the table by variant and launches one grid per variant present.
+enum { SMALL_PLAIN = 0, SMALL_BOUNDED = 1, SMALL_DETECT = 2, SMALL_BOUNDED_DETECT = 3, SMALL_QUAD = 4, SMALL_BOUNDED_QUAD = 5, SMALL_NVARIANTS = 6 };
 struct SmallItem {
     SmallLP lp;
     BndArgs bd;
     DetArgs dt;
+    const double* g;                                     // the quadratic diagonal of a SMALL_*QUAD item (the handle's quad_g), else NULL
     double eta;                                          // the handle's step damping (small_batch_params_kernel)
     int variant;                                         // SMALL_*
     int index;                                           // position of the handle in the caller's array (the gathered record goes there)
 };
 
 // the index is the workgroup's own: the loads are wave-uniform and the item ends up in scalar registers like kernel arguments do
-template <bool Bounded, bool Detect>
+template <bool Bounded, bool Detect, bool Quad = false>
 __device__ __forceinline__ void small_lp_batch_body(const SmallItem* __restrict__ items) {
     const SmallItem it = items[blockIdx.x];
-    small_lp_body<Bounded, Detect>(it.lp, it.bd, it.dt);
+    small_lp_body<Bounded, Detect, Quad>(it.lp, it.bd, it.dt, it.g);
 }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, false>(items); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, false>(items); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, true>(items); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, true>(items); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_batch_quad_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, false, true>(items); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_quad_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, false, true>(items); }
 
 // start_solve(force = 0, reset = 1) for every item, as set_params_kernel does for one LP: one thread per item
 __global__ __launch_bounds__(256) void small_batch_params_kernel(const SmallItem* __restrict__ items, int n, double e1, double e2, double e3, int max_iter) {

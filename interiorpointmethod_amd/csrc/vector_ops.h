@@ -173,6 +173,7 @@ __device__ __forceinline__ double col_sum(const double* atp, int rc_chunks, int 
 // Detect (IPM_FLAG_DETECT_INFEASIBILITY): also the partials of the infeasibility tests (P_BY .. P_MXU) -- reads of what the
 // pass holds anyway (A^T y from col_sum, A x = r_b + b), no extra pass over A
 // Quad (ipm_set_quadratic; g: the np-vector of the diagonal): r_c, d and the objective by the quad_* rules, one more streamed vector
+// (residual_cols of small_lp.h is the hand-kept second copy of this column, its Quad branches included: keep the two in step)
 template <bool Bounded = false, bool Detect = false, bool Quad = false>
 __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, const double* g = nullptr) {
     __shared__ double red[VBLK];

@@ -116,7 +116,8 @@ class IpmSolver:
     def __init__(self, A, b, c, device=0, eta=0.91, pivot_guard_eps=1e-30, pivot_guard_big=1e64,
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
                  auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
-                 infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, quad=None):
+                 infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, quad=None,
+                 quad_small=False):
         """check_every: solve() enqueues that many iterations at a time and reads the stop flag once per chunk (the launches behind a
         satisfied stop test return at entry, so the result does not depend on it: DESIGN.md 4-A); a lockstep batch runs chunks of the
         largest value among its members.  IPM_CHECK_EVERY in the environment, when set and not empty, OVERRIDES this argument for
@@ -140,7 +141,11 @@ class IpmSolver:
         quad: None (default: the LP) or the diagonal g >= 0 (length n) of a separable convex quadratic term: the solver minimises
         c.x + 1/2 x.diag(g) x (set_quadratic, ipm_set_quadratic), checked on the host before any device is touched.
         The term is set before A, so a small sparse problem takes the multi-kernel path.  lockstep, detect_infeasibility and
-        correctors > 0 refuse a nonzero term (ValueError); mehrotra_start / init_state_mehrotra ignore it."""
+        correctors > 0 refuse a nonzero term (ValueError); mehrotra_start / init_state_mehrotra ignore it.
+        quad_small=True (IPM_FLAG_SMALL_QUADRATIC; off by default): a problem that qualifies for the fused small path (sparse A, at
+        most 128 rows) keeps it with a quadratic term -- the whole loop of the QP in one launch of one workgroup, and the solver may
+        join solve_small_batch_solvers; set_quadratic then also accepts a term after construction.  The flag alone changes nothing
+        (no term, or a problem that does not qualify: the solver an unflagged one is, bit for bit) and lifts no refusal."""
         self.scale = check_scale(scale)
         correctors = check_correctors(correctors)
         refine = check_refine(refine)
@@ -185,7 +190,9 @@ class IpmSolver:
                      ((_lib.FLAG_NO_DEVICE_POLLING | _lib.FLAG_SINGLE_STREAM) if concurrent else 0) | \
                      (0 if auto_regularize else _lib.FLAG_NO_AUTO_REGULARIZE) | \
                      (_lib.FLAG_SPARSE_FACTOR if self.factor == "sparse" else 0) | \
-                     (_lib.FLAG_DETECT_INFEASIBILITY if detect_infeasibility else 0)
+                     (_lib.FLAG_DETECT_INFEASIBILITY if detect_infeasibility else 0) | \
+                     (_lib.FLAG_SMALL_QUADRATIC if quad_small else 0)
+        self.quad_small = bool(quad_small)
         self.detect_infeasibility = bool(detect_infeasibility)
         nbytes = C.c_size_t(0)
         self.sparse = _is_sparse(A)
@@ -210,7 +217,7 @@ class IpmSolver:
         _lib.check(None, lib.ipm_create(int(device), self.m, self.n, C.byref(opts), ws_ptr,
                                         self.workspace_bytes if ws_ptr else 0, stream, C.byref(h)))
         self._h = h
-        if quad is not None:                 # before A: ipm_set_A_csc then never chooses the one-workgroup small path
+        if quad is not None:                 # before A: ipm_set_A_csc then chooses the one-workgroup small path only with quad_small
             try:
                 self._check(lib.ipm_set_quadratic(h, _dptr(quad)))
             except Exception:
@@ -398,7 +405,8 @@ class IpmSolver:
         """ipm_set_quadratic: the diagonal g >= 0 (length n) of the objective's quadratic term from the next iteration on; None or
         all zeros removes it, and the solver runs exactly the LP code again.  Checked on the host first (ValueError: length, NaN,
         Inf, negative); the library refuses a nonzero term (IpmError) on a lockstep solver, with detect_infeasibility, with
-        correctors > 0 and on the fused small path.  Either way the solver keeps the term it held."""
+        correctors > 0 and, unless the solver was created with quad_small=True, on the fused small path.  Either way the solver
+        keeps the term it held."""
         g = check_quadratic(g, self.n)
         self._check(self._lib.ipm_set_quadratic(self._h, None if g is None else _dptr(g)))
 
