@@ -313,7 +313,11 @@ int ipm_solve_batch(ipm_handle** handles, int32_t n, double tol_p, double tol_d,
  * running) and the caller learns which ones finished after every step (and can tear them down while the batch runs on).
  * ipm_batch_add: the handle (requirements as above) starts its solve from its current state, *index = its position in the batch.
  * ipm_batch_step: opt.check_every iterations of every active handle in lockstep; the indices of the handles that finished in this
- * step go to finished[0 .. *n_finished), *n_active = handles still running (0: nothing left to do).  ipm_batch_stats: the statistics
+ * step go to finished[0 .. *n_finished), *n_active = handles still running (0: nothing left to do).  `cap` is the capacity of
+ * `finished`: every finished handle is reported exactly once, and the indices that do not fit stay queued in the batch -- the
+ * following calls return them first, at most `cap` per call and oldest first, before or next to the handles that finish in those
+ * calls, also when *n_active has reached 0 (such a call launches nothing).  A caller with cap < the number of handles therefore
+ * calls until *n_active == 0 AND *n_finished == 0.  ipm_batch_stats: the statistics
  * of a finished handle.  A batch owns one stream; it is not thread-safe; the handles stay owned by the caller and must outlive their
  * part in the batch (destroy a handle only after ipm_batch_step reported it finished, or after ipm_batch_destroy). */
 typedef struct ipm_batch ipm_batch;
@@ -555,6 +559,12 @@ int ipm_debug_ff_trace(ipm_handle* h, long long* out, int64_t capacity, int64_t*
  * position} in step order.  Returns the number of steps, -1 on bad arguments / too small a capacity. */
 int ipm_debug_ls_merge(int32_t n, const int32_t* off, const int32_t* types_flat, int32_t max_group, int32_t aligned,
                        int32_t* out_steps, int32_t cap_steps, int32_t* out_members);
+/* Test hook (host only, launches nothing): the merged schedule that the last ipm_batch_step of `b` launched, four words per step
+ * in launch order: {kernel type (LsType of csrc/lockstep.h), members (handles served by the launch, at most 64), blocks (the packed
+ * 1-D grid: the sum of the members' own grids), lds (dynamic LDS bytes: the largest among the members)}.  *count = the number of
+ * steps (0 before the first step); IPM_ERR_INVALID_ARG, with *count set, when capacity (in words) < 4 * steps
+ * (tests/test_gpu_lockstep_wide.py). */
+int ipm_debug_batch_schedule(ipm_batch* b, int32_t* out, int32_t capacity, int32_t* count);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@ EXPORTS = [
     "ipm_iterate", "ipm_solve", "ipm_solve_batch", "ipm_solve_small_batch", "ipm_init_small_batch_mehrotra", "ipm_batch_create", "ipm_batch_destroy", "ipm_batch_last_error", "ipm_batch_add", "ipm_batch_step", "ipm_batch_stats", "ipm_get_history", "ipm_set_centrality_correctors", "ipm_get_corrector_info", "ipm_set_refinement", "ipm_get_refinement_info", "ipm_debug_get_refine_vector", "ipm_set_infeasibility_tol", "ipm_get_certificate", "ipm_get_schedule", "ipm_get_schedule_words", "ipm_debug_at_pieces", "ipm_debug_chol_plan", "ipm_order_rows", "ipm_get_factor_info", "ipm_solve_linear", "ipm_lu_solve", "ipm_lu_factor", "ipm_normal_solve", "ipm_form_normal_matrix", "ipm_get_factor",
     "ipm_set_dense_columns", "ipm_get_dense_split_info", "ipm_debug_get_dense_split",
     "ipm_set_profiling", "ipm_get_phase_ms", "ipm_debug_get_stamps", "ipm_debug_ff_schedule", "ipm_debug_ff_trace", "ipm_debug_get_block_inverse", "ipm_debug_get_group_inverse", "ipm_debug_ls_merge",
+    "ipm_debug_batch_schedule",
 ]
 
 IPM_OK = 0
@@ -179,6 +180,7 @@ def load():
     lib.ipm_debug_get_group_inverse.argtypes = [vp, i32, i32, pd]
     lib.ipm_debug_ff_trace.argtypes = [vp, C.POINTER(C.c_longlong), i64, C.POINTER(i64), C.POINTER(C.c_ubyte), C.POINTER(i32)]
     lib.ipm_debug_ls_merge.argtypes = [i32, C.POINTER(i32), C.POINTER(i32), i32, i32, C.POINTER(i32), i32, C.POINTER(i32)]
+    lib.ipm_debug_batch_schedule.argtypes = [vp, C.POINTER(i32), i32, C.POINTER(i32)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("ipm_default_options", "ipm_last_error", "ipm_batch_last_error"):

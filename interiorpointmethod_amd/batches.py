@@ -73,6 +73,19 @@ class LockstepBatch:
         _scatter_stats(out, stats)
         return out
 
+    def schedule(self):
+        """ipm_debug_batch_schedule (test hook, host only): the merged schedule the last step() launched -> list of dicts, one per
+        launch in order: type (LsType of csrc/lockstep.h), members (LPs served by the launch), blocks (the packed grid: the sum of
+        the members' own grids) and lds (dynamic LDS bytes).  Empty before the first step."""
+        n = C.c_int32(0)
+        code = self._lib.ipm_debug_batch_schedule(self._b, None, 0, C.byref(n))
+        if n.value == 0:
+            self._check(code)
+            return []
+        out = (C.c_int32 * (4 * n.value))()
+        self._check(self._lib.ipm_debug_batch_schedule(self._b, out, 4 * n.value, C.byref(n)))
+        return [dict(zip(("type", "members", "blocks", "lds"), (int(v) for v in out[4 * k:4 * k + 4]))) for k in range(n.value)]
+
     def close(self):
         if self._b:
             self._lib.ipm_batch_destroy(self._b)

@@ -84,6 +84,7 @@ struct ipm_batch {
     std::vector<std::vector<LsLaunch>> prog;
     std::vector<char> first, finished;
     std::vector<int> active;
+    std::vector<int> unreported;                       // finished, not yet handed to the caller (ipm_batch_step: cap was too small), oldest first
     std::vector<LsStep> steps;
     std::vector<LsRec> recs;
     LsRec* d_recs = nullptr;
@@ -166,11 +167,18 @@ extern "C" int ipm_batch_add(ipm_batch* b, ipm_handle* h, double tol_p, double t
 
 // One chunk (check_every iterations) of every active handle in lockstep, then the stop flags are read: the indices of the
 // handles that finished in this chunk go to finished[0 .. *n_finished) (capacity cap), *n_active = handles still running.
+// EVERY finished handle is reported exactly once: those that did not fit into `cap` stay queued (b->unreported) and lead the
+// list of the following calls, at most `cap` per call, also when nothing is active any more.
+static void ls_report_finished(ipm_batch* b, int32_t* finished, int32_t cap, int32_t* n_finished) {
+    size_t k = 0;
+    while (k < b->unreported.size() && *n_finished < cap) finished[(*n_finished)++] = b->unreported[k++];
+    b->unreported.erase(b->unreported.begin(), b->unreported.begin() + (long)k);
+}
 extern "C" int ipm_batch_step(ipm_batch* b, int32_t* finished, int32_t cap, int32_t* n_finished, int32_t* n_active) {
     if (!b || !n_finished || (cap > 0 && !finished)) return bfail(b, IPM_ERR_INVALID_ARG, "ipm_batch_step: bad arguments");
     *n_finished = 0;
     if (n_active) *n_active = (int32_t)b->active.size();
-    if (b->active.empty()) return IPM_OK;
+    if (b->active.empty()) { ls_report_finished(b, finished, cap, n_finished); return IPM_OK; }
     B_TRY(b, hipSetDevice(b->device));
     hipStream_t S = b->S;
     const auto t_in = std::chrono::steady_clock::now();
@@ -244,13 +252,27 @@ extern "C" int ipm_batch_step(ipm_batch* b, int32_t* finished, int32_t cap, int3
         b->first[(size_t)i] = 0;
         if (h->h_sc->done) {
             b->dirty = true; b->finished[(size_t)i] = 1;
-            if (*n_finished < cap) finished[(*n_finished)++] = i;
+            b->unreported.push_back(i);
             continue;
         }
         keep.push_back(i);
     }
     b->active.swap(keep);
+    ls_report_finished(b, finished, cap, n_finished);
     if (n_active) *n_active = (int32_t)b->active.size();
+    return IPM_OK;
+}
+// Test hook (host only, nothing is launched): the merged schedule the last ipm_batch_step launched, {type, members, blocks, lds}
+// per step, copied from b->steps.  *count = steps; IPM_ERR_INVALID_ARG (with *count set) when capacity < 4 * steps.
+extern "C" int ipm_debug_batch_schedule(ipm_batch* b, int32_t* out, int32_t capacity, int32_t* count) {
+    if (!b || !count || (capacity > 0 && !out) || capacity < 0) return bfail(b, IPM_ERR_INVALID_ARG, "ipm_debug_batch_schedule: bad arguments");
+    *count = (int32_t)b->steps.size();
+    if ((int64_t)capacity < 4 * (int64_t)b->steps.size())
+        return bfail(b, IPM_ERR_INVALID_ARG, "ipm_debug_batch_schedule: capacity %d < 4 x %zu steps", (int)capacity, b->steps.size());
+    for (size_t s = 0; s < b->steps.size(); ++s) {
+        const LsStep& st = b->steps[s];
+        out[4 * s] = st.type; out[4 * s + 1] = (int32_t)st.count; out[4 * s + 2] = (int32_t)st.blocks; out[4 * s + 3] = (int32_t)st.lds;
+    }
     return IPM_OK;
 }
 extern "C" int ipm_batch_stats(ipm_batch* b, int32_t index, ipm_stats* stats) {
