@@ -58,10 +58,11 @@ class Problem:
         self.c_norm = IO.norm(self.c) if T is LD else np.sqrt(self.c @ self.c)      # (LD: iteration_oracle's own summation)
 
 
-def newton(P, x, y, s, w, z, eta, one_step=True, tol=None):
+def newton(P, x, y, s, w, z, eta, one_step=True, tol=None, theta_shift=0.0):
     """One iteration from (x, y, s, w, z) -> dict (the keys of iteration_oracle.iterate, plus the residual vectors rb, rc, ru and the
     corrector's complementarity terms r3c, r4c).  tol: the stop test runs first, and a converged state returns only the scalars of the
-    state with converged=True."""
+    state with converged=True.  theta_shift: a deliberately WRONG rule, theta from s + theta_shift (the "safe division" x / (s + 1e-14));
+    the host files use it to show that their bounds see such a change.  0.0 leaves every bit as it is."""
     T, A, AT, U, g = P.T, P.A, P.AT, P.U, P.g
     n = P.n
     N = T(n + P.nU)
@@ -75,8 +76,9 @@ def newton(P, x, y, s, w, z, eta, one_step=True, tol=None):
     if tol is not None and out["rp_norm"] <= tol * (1 + P.b_norm) and out["rd_norm"] <= tol * (1 + P.c_norm) and gap <= tol:
         out["converged"] = True
         return out
-    theta = x / (s + g * x)
-    theta[U] = 1 / (s[U] / x[U] + z[U] / w[U] + g[U])
+    st = s + T(theta_shift)
+    theta = x / (st + g * x)
+    theta[U] = 1 / (st[U] / x[U] + z[U] / w[U] + g[U])
     solve = _factor(A, theta, T)
 
     def direction(r3, r4):
@@ -118,11 +120,12 @@ def newton(P, x, y, s, w, z, eta, one_step=True, tol=None):
     return out
 
 
-def iterate(case, g, eta=IO.ETA, one_step=True, T=LD):
-    """One iteration from the case's state with the diagonal g: T = LD the oracle, T = np.float64 the host restatement."""
+def iterate(case, g, eta=IO.ETA, one_step=True, T=LD, theta_shift=0.0):
+    """One iteration from the case's state with the diagonal g: T = LD the oracle, T = np.float64 the host restatement.
+    theta_shift: see newton."""
     P = Problem(case.A, case.b, case.c, g, case.u, T)
     x, y, s, w, z = (np.asarray(v, dtype=T) for v in (case.x, case.y, case.s, case.w, case.z))
-    return newton(P, x, y, s, w, z, eta, one_step)
+    return newton(P, x, y, s, w, z, eta, one_step, theta_shift=theta_shift)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -85,8 +85,8 @@ def _recorder(name):
     return measure, seen
 
 
-def _report(cell, name, seen):
-    ev = LC.evaluate(name)
+def _report(cell, name, seen, ev=None):
+    ev = ev or LC.evaluate(name)
     for k in sorted(seen):
         print("LATE %s %s error %.3e H %.3e floor %.1e over %.3f%s" % (cell, k, seen[k], ev.H[k], LC.floor(k),
               seen[k] / max(ev.H[k], LC.floor(k) / LC.MARGIN), " DROPPED (host spread %.1f)" % ev.spread[k] if k in ev.dropped else ""))
@@ -102,13 +102,14 @@ def _exact(cell, sv, case, st, h):
     assert st["pivots_fixed"] == 0 and h["pivots_fixed"] == 0, (cell, st["pivots_fixed"], h["pivots_fixed"])
 
 
-def check_late(cell, name, sv):
-    ev = LC.evaluate(name)
+def check_late(cell, name, sv, ev=None):
+    """ev: the evaluated case where it is not one of late_cases.CASES (tests/test_gpu_late_large.py)."""
+    ev = ev or LC.evaluate(name)
     measure, seen = _recorder(name)
     try:
-        o, st, h = check_iteration(cell, sv, ev.case, o=ev.o, measure=measure, bound=LC.bound(name))
+        o, st, h = check_iteration(cell, sv, ev.case, o=ev.o, measure=measure, bound=LC.bound_of(ev))
     finally:
-        _report(cell, name, seen)
+        _report(cell, name, seen, ev)
     _exact(cell, sv, ev.case, st, h)
     return st, h
 
@@ -192,18 +193,21 @@ def test_small_path_and_its_multi_kernel_twin(fused, monkeypatch):
 
 
 # ---- lockstep twins --------------------------------------------------------------------------------------------------------
-def test_lockstep_pair():
-    cases = [LC.get(nm) for nm in LC.LOCK]
+def check_lockstep(names, evaluate, group_blocks):
+    """solve_lockstep(max_iter=1) of the named cases as one batch, every LP against its oracle.  evaluate: name -> the evaluated case;
+    group_blocks: per case, what schedule() must report (0: block steps)."""
+    evs = [evaluate(nm) for nm in names]
+    cases = [ev.case for ev in evs]
     svs = [_solver(case, as_sparse=True, lockstep=True, factor="dense") for case in cases]
     try:
-        for sv, case in zip(svs, cases):
+        for sv, case, gb in zip(svs, cases, group_blocks):
             sch = sv.schedule()
             assert ipm.lockstep_eligible(sv) and sch["fused_small"] == 0 and sv.factor == "dense" and not sv.bounded
-            assert sch["blocks"] == (case.m + 127) // 128 and sch["grouped_trsv"] == (0 if case.m > 256 else 1), sch      # 3 blocks: block steps
+            assert sch["blocks"] == (case.m + 127) // 128 and sch["grouped_trsv"] == (1 if gb else 0) and sch["group_blocks"] == gb, sch
             sv.set_state(*case.state())
         stats = ipm.solve_lockstep(svs, tol=1e-30, max_iter=1)
-        for name, sv, case, st in zip(LC.LOCK, svs, cases, stats):
-            ev = LC.evaluate(name)
+        for name, sv, ev, st in zip(names, svs, evs, stats):
+            case = ev.case
             assert st["iterations"] == 1 and st["status"] == _lib.STATUS_MAX_ITER, (name, st)
             hist = sv.history()
             assert len(hist) == 1 and hist[0]["k"] == 0
@@ -215,13 +219,18 @@ def test_lockstep_pair():
             e = {}
             for q, v in got.items():
                 e.update(LC.measure(q, v, ev.o))
-            _report(name, name, e)
-            bound = LC.bound(name)
+            _report(name, name, e, ev)
+            bound = LC.bound_of(ev)
             _assert_all(name, e, {k: bound(k) for k in e})
             _exact(name, sv, case, st, h)
+            assert sv.schedule()["timeouts_recovered"] == 0
     finally:
         for sv in svs:
             sv.close()
+
+
+def test_lockstep_pair():
+    check_lockstep(LC.LOCK, LC.evaluate, [0, 2])                # 257 rows: 3 blocks, block steps; 130 rows: one 256-row group
 
 
 # ---- the QP ----------------------------------------------------------------------------------------------------------------
