@@ -253,6 +253,35 @@ int ipm_set_quadratic(ipm_handle* h, const double* g);
 /* g (length n, the caller's units; zeros when no term is set) and the number of its positive entries; either may be NULL. */
 int ipm_get_quadratic(ipm_handle* h, double* g, int64_t* nonzeros);
 
+/* ---- free columns with curvature: what Q = diag(g) + F F^T needs -------- */
+/* idx: `count` distinct column indices 0 .. n-1; count == 0 or idx == NULL clears the set, and the handle then runs exactly the
+ * code it ran before.  A free column j carries no sign constraint: no s_j (stored and returned as exactly 0), no bound, no
+ * complementarity pair; it needs g_j > 0 (ipm_set_quadratic), and its scaling is the constant 1 / g_j, so the normal matrix stays
+ * A Theta A^T and every factorization path serves the handle: dense (the fused launch included), sparse on the envelope factor and
+ * with IPM_FLAG_SPARSE_FACTOR, bounded or not (bounds on the OTHER columns), with ipm_set_refinement, with ipm_equilibrate (the
+ * marks are scale-free) and with a dense-column split.  mu, mu_aff and sigma count n - count (+ |U|) pairs; the ratio tests skip the
+ * free columns; their dual residual (A^T y - c - g o x)_j counts in rd_norm.  The call needs only n and may come before or after
+ * ipm_set_A_*, ipm_set_quadratic and ipm_set_bounds.  With the reformulation t = F^T x (rows [F^T -I], t free, g_t = 1) a handle
+ * solves min c^T x + 1/2 x^T (diag(g) + F F^T) x.
+ * State: ipm_init_state writes x = 1 and s = 0 on the free columns; ipm_set_state stores s = 0 there whatever is passed (x may
+ * have any sign or be 0); ipm_get_state returns 0.  Setting or changing the set on a handle that holds a state zeroes s on the new
+ * free columns.  After CLEARING the set the former free columns still hold s = 0, which the barrier iteration cannot start from:
+ * set a state anew (ipm_init_state / ipm_set_state) before the next iteration.
+ * Refused with IPM_ERR_INVALID_ARG and a reason in ipm_last_error, in either order of the calls involved, never dropped: an index
+ * out of range or given twice; a column with g_j = 0 (here when the term is set, by ipm_set_quadratic when the set came first,
+ * and by ipm_iterate / ipm_solve / ipm_newton_direction when no term ever came); ipm_set_quadratic clearing the term or zeroing g_j
+ * on a free column; a finite u_j on a free column (here, or by ipm_set_bounds); every column free (no pair left: mu would be 0/0);
+ * an IPM_FLAG_LOCKSTEP or IPM_FLAG_DETECT_INFEASIBILITY handle; a handle on the fused small path, IPM_FLAG_SMALL_QUADRATIC
+ * included (set the columns before A: ipm_set_A_csc then takes the multi-kernel path); ipm_init_state_mehrotra on a handle with
+ * free columns (its least-squares start is not restated for them).  Centrality correctors are refused as for every quadratic
+ * handle.  The marks are np bytes allocated by the library on first use and freed by ipm_destroy.  Invalidates a pending predictor. */
+int ipm_set_free_columns(ipm_handle* h, const int32_t* idx, int32_t count);
+/* The set in the caller's order: *count receives its size, idx (capacity cap; may be NULL with cap == 0) the first cap indices. */
+int ipm_get_free_columns(ipm_handle* h, int32_t* idx, int32_t cap, int32_t* count);
+/* Test hook: a column vector of the iteration as the device holds it after the last ipm_newton_direction / ipm_iterate, n entries
+ * in the HANDLE's units (a scaled handle's are not unscaled): which = 0 r_c, 1 d (the diagonal of Theta), 2 v, 3 q. */
+int ipm_debug_get_column_vector(ipm_handle* h, int32_t which, double* out);
+
 /* ---- equilibration: power-of-two Ruiz row / column scaling -------------- */
 /* Scale the handle's LP on the device to R A C, R b, C c, u / C with diagonal R, C whose entries are exact powers of two, so that
  * scaling and unscaling introduce no rounding at all.  Rule (csrc/equilibrate.h): simultaneous Ruiz passes on |A| in the infinity

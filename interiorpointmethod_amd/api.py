@@ -15,8 +15,8 @@ import numpy as np
 
 from . import _lib
 from .analysis import _upper_bounds
-from .handle import (SCALE_PASSES, STATUS_NAMES, IpmSolver, check_correctors, check_quadratic, check_refine, check_scale, mehrotra_started,
-                     refuse_quadratic, shift_allowed, wants_shift)
+from .handle import (SCALE_PASSES, STATUS_NAMES, IpmSolver, check_correctors, check_free, check_quadratic, check_refine, check_scale, mehrotra_started,
+                     refuse_free, refuse_quadratic, shift_allowed, wants_shift)
 
 
 def _info(solver, cTlb=0.0):
@@ -50,6 +50,7 @@ def _solve_info(solver, history=False, certificate=False):
     info["quadratic"] = solver.quadratic_nonzeros()         # positive entries of the quadratic term's diagonal (0: an LP)
     # the path that served a quadratic term: "small" (the one-workgroup loop, quad_small=True) or "multi-kernel"; None for an LP
     info["quadratic_path"] = None if not info["quadratic"] else "small" if solver.schedule()["fused_small"] else "multi-kernel"
+    info["free"] = solver._n_free                           # free columns (0: none); the count the handle keeps, no library call
     if solver.scale is not None:
         info["scale"] = dict(solver.scale_info)
         info["rp_unscaled"], info["rd_unscaled"] = unscaled_residuals(solver)
@@ -86,7 +87,7 @@ def _auto_regularize():          # the process-wide switch of the 5 % rule (hand
 
 def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
                     history=False, ub=None, detect_infeasibility=False, device_start=False, scale=None, scale_passes=SCALE_PASSES,
-                    correctors=0, refine=0, dense_cols=None, quad=None, quad_small=False, **opts):
+                    correctors=0, refine=0, dense_cols=None, quad=None, quad_small=False, free=None, **opts):
     """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
     start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start(), or with
     device_start=True IpmSolver.init_state_mehrotra(): the same start computed on the device (no host copy of A, one
@@ -108,7 +109,10 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     4-Q); info["quadratic"] = its positive entries, info["objective"] includes the term.  Refused (ValueError) together with
     detect_infeasibility and correctors > 0; start="mehrotra" ignores g.
     quad_small=True (off by default): a sparse problem of at most 128 rows keeps the fused small path with its term (IpmSolver,
-    IPM_FLAG_SMALL_QUADRATIC); info["quadratic_path"] says which path served the term: "small", "multi-kernel", or None for an LP."""
+    IPM_FLAG_SMALL_QUADRATIC); info["quadratic_path"] says which path served the term: "small", "multi-kernel", or None for an LP.
+    free: None (default), column indices or a boolean mask: the free columns (IpmSolver) -- quad > 0 there, no bound,
+    no sign constraint; info["free"] = their count.  Checked on the host before any device is touched (ValueError naming the
+    column); refused (ValueError) together with detect_infeasibility, correctors > 0 and start="mehrotra"."""
     global _last_info
     correctors = check_correctors(correctors)
     refine = check_refine(refine)
@@ -127,6 +131,13 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
         if correctors:
             refuse_quadratic(quad, "correctors=%d" % correctors, "a quadratic solver takes one step length, the rounds compare step pairs")
     ub = _upper_bounds(ub, np.asarray(c).reshape(-1).shape[0])
+    free = check_free(free, np.asarray(c).reshape(-1).shape[0], quad, ub)
+    if detect_infeasibility:
+        refuse_free(free, "detect_infeasibility=True", "the infeasibility tests are the LP's")
+    if correctors:
+        refuse_free(free, "correctors=%d" % correctors, "a quadratic solver takes one step length, the rounds compare step pairs")
+    if start == "mehrotra":
+        refuse_free(free, 'start="mehrotra"', "the least-squares start is not restated for free columns")
     on_device = start == "mehrotra" and device_start
     if start == "mehrotra" and not on_device and shift_allowed(opts.get("regularize"), _auto_regularize()):
         # the least-squares start factors A A^T: guarded pivots there are dependent rows of A (handle.wants_shift: the 5 % rule).
@@ -139,7 +150,7 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     t0 = _time.perf_counter()
     if detect_infeasibility:
         opts = dict(opts, detect_infeasibility=True)
-    make = lambda **extra: IpmSolver(A, b, c, device=device, ub=ub, correctors=correctors, refine=refine, quad=quad, **dict(opts, **extra))          # noqa: E731
+    make = lambda **extra: IpmSolver(A, b, c, device=device, ub=ub, correctors=correctors, refine=refine, quad=quad, free=free, **dict(opts, **extra))          # noqa: E731
     with (mehrotra_started(make, opts.get("regularize"), _auto_regularize()) if on_device else make()) as sv:
         t1 = _time.perf_counter()
         if start == "mehrotra" and not on_device:
@@ -162,12 +173,12 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
 
 
 def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None,
-          quad=None, quad_small=False, **opts):
+          quad=None, quad_small=False, free=None, **opts):
     """min c^T x (+ 1/2 x^T diag(quad) x) s.t. Ax=b, x>=0 (and x <= ub where ub is finite) by the Mehrotra predictor-corrector loop
-    on the GPU -> (x, y, s).  quad_small: as solve_with_info."""
+    on the GPU -> (x, y, s).  quad_small, free (columns without the sign constraint): as solve_with_info."""
     x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub, scale=scale,
                                  scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad,
-                                 quad_small=quad_small, **opts)
+                                 quad_small=quad_small, free=free, **opts)
     return x, y, s
 
 
@@ -181,13 +192,13 @@ def _verdict(info, value):
 
 
 def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0,
-                    dense_cols=None, quad=None):
+                    dense_cols=None, quad=None, free=None):
     """Drop-in for main.py:760-815: start x=s=y=1, cap 5000, returns sum(x*c) - cTlb (with quad: the quadratic objective - cTlb).  detect_infeasibility=True: +inf for an
     LP detected infeasible, -inf for one detected unbounded.  scale, correctors, refine, dense_cols: as solve_with_info (off by
-    default)."""
+    default); free likewise (free columns of a quadratic problem)."""
     _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=5000, y0=1.0, device=device,
                                     detect_infeasibility=detect_infeasibility, scale=scale, scale_passes=scale_passes,
-                                    correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad)
+                                    correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad, free=free)
     return _verdict(info, info["objective"] - float(cTlb))
 
 

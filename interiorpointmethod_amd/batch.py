@@ -26,7 +26,7 @@ from .analysis import prepare
 from .api import _auto_regularize, _solve_info, solve_with_info
 from .batches import LockstepBatch, lockstep_eligible, small_batch_eligible, solve_small_batch_solvers
 from .analysis import refuse_dense_cols
-from .handle import SCALE_PASSES, IpmSolver, check_scale, mehrotra_started, refuse_correctors, refuse_refine
+from .handle import SCALE_PASSES, IpmSolver, check_scale, mehrotra_started, refuse_correctors, refuse_free, refuse_refine
 
 # One record per LP.  The first nine fields are the statistics SURVEY.md 8e names; the rest make the library's hidden
 # recoveries and the host-side phases of a solve visible in the gathered table: `timeouts_recovered` = device hand-off
@@ -440,7 +440,7 @@ class _LockstepShard:
 
 def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, tol_gap=None,
                          detect_infeasibility=False, small_batch=False, start="reference", scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0,
-                         dense_cols=None, **_):
+                         dense_cols=None, free=None, **_):
     """Solve problems[i] for i in ids on this rank's GPU with the LOCKSTEP BATCH -> (len(ids), NF) records.
 
     `workers` host threads prepare the LPs (host analysis, handle, upload), largest first.  An LP of more than 128 rows on the
@@ -464,7 +464,8 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
     a handle with different data, so the batches need nothing else.
 
     correctors > 0 raises ValueError: the centrality-corrector rounds have no batched twins (run_batch(lockstep=False) serves them);
-    refine > 0 likewise, and so does dense_cols (the split has no batched twins either)."""
+    refine > 0 likewise, and so does dense_cols (the split has no batched twins either), and so does free (free columns)."""
+    refuse_free(free, "the lockstep batch", "the Free kernels have no batched twins; solve such problems one at a time")
     refuse_correctors(correctors, "the lockstep batch")
     refuse_refine(refine, "the lockstep batch")
     refuse_dense_cols(dense_cols, "the lockstep batch")
@@ -584,7 +585,7 @@ def lockstep_wanted(problems, world=1, workers=8, mode="auto"):
 
 
 def run_batch(problems, costs=None, device=0, dist=None, gather_device=None, solve_fn=solve_one, workers=1,
-              schedule="static", store=None, collective_at_world_one=False, lockstep=False, **kw):
+              schedule="static", store=None, collective_at_world_one=False, lockstep=False, free=None, **kw):
     """Shard `problems` (list of (A, b, c)) over the ranks of `dist`, solve, gather statistics.
 
     schedule="static": deterministic LPT partition on the predicted cost, no scheduling traffic at all.
@@ -593,7 +594,9 @@ def run_batch(problems, costs=None, device=0, dist=None, gather_device=None, sol
     ONE all-gather of the statistics records.  Returns (records sorted by id, this rank's wall seconds).  Without an
     initialised process group this is the single-GPU loop; so it is with a group of ONE rank, unless
     collective_at_world_one asks for the distributed code path anyway (store counter, device tensors through
-    dist.all_gather): that is how the RCCL branch is exercised on a one-GPU box (tests/test_gpu_parity.py)."""
+    dist.all_gather): that is how the RCCL branch is exercised on a one-GPU box (tests/test_gpu_parity.py).
+    free (free columns of a quadratic problem) raises ValueError: a batch's problems are (A, b, c) triples, LPs."""
+    refuse_free(free, "run_batch", "its problems are LPs; solve such problems one at a time")
     global _CALLS
     _CALLS += 1
     live = dist is not None and dist.is_initialized()

@@ -7,7 +7,7 @@ from . import _lib
 from .analysis import FUSED_SMALL_MAX_ROWS, _sp, _upper_bounds
 from .api import _auto_regularize, _solve_info
 from .analysis import refuse_dense_cols
-from .handle import SCALE_PASSES, IpmSolver, _gap_tol, check_quadratic, check_scale, refuse_correctors, refuse_refine, wants_shift
+from .handle import SCALE_PASSES, IpmSolver, _gap_tol, check_quadratic, check_scale, refuse_correctors, refuse_free, refuse_refine, wants_shift
 
 
 def _handle_array(solvers):           # (the handles as a C array, a Stats array of the same length) for one batched library call
@@ -21,11 +21,12 @@ def _scatter_stats(solvers, stats):           # each solver takes its statistics
     return [sv.stats for sv in solvers]
 
 
-def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None, correctors=0, refine=0, dense_cols=None):
+def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None, correctors=0, refine=0, dense_cols=None, free=None):
     """ipm_solve_batch: solve the LPs of `solvers` (IpmSolver objects created with lockstep=True on one device, a state set) AT ONCE,
     iteration k of all of them in the same launches (csrc/lockstep.h) -> list of statistics dicts, one per solver.  Per-LP semantics
     and arithmetic are those of IpmSolver.solve on each of them alone (bit-identical iterates).  correctors > 0: ValueError (the rounds
-    have no batched twins; a lockstep solver refuses set_correctors for the same reason); refine > 0 likewise."""
+    have no batched twins; a lockstep solver refuses set_correctors for the same reason); refine > 0 likewise, and free columns."""
+    refuse_free(free, "the lockstep batch", "the Free kernels have no batched twins; solve such problems one at a time")
     refuse_correctors(correctors, "the lockstep batch")
     refuse_refine(refine, "the lockstep batch")
     refuse_dense_cols(dense_cols, "the lockstep batch")          # (the split has no batched twins: ValueError, never dropped)
@@ -188,7 +189,7 @@ def _small_batch_host_check(problems, ub):
 
 
 def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, ub=None, detect_infeasibility=False,
-                      regularize=0.0, start="reference", scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None):
+                      regularize=0.0, start="reference", scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, free=None):
     """Solve many small LPs at once -> list of (x, y, s, info), one per problem, each what solve_with_info returns for it alone.
 
     problems: list of (A, b, c) with at most 128 rows each; a dense A is converted to CSC.  ub: None or one entry per problem (None or
@@ -198,7 +199,8 @@ def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_g
     of handle.wants_shift gets its handle again with regularize=1e-14 and its own start).  An LP the library does not put on the
     small path (more than 128 rows, or a product list of A D^2 A^T beyond its cap) raises ValueError naming its index before anything
     is launched.  scale="ruiz": every LP is equilibrated on the device first (IpmSolver; off by default).  correctors > 0: ValueError
-    before any device is touched (solve_small_batch_solvers), and so for refine > 0."""
+    before any device is touched (solve_small_batch_solvers), and so for refine > 0 and for free columns (free=)."""
+    refuse_free(free, "the small-LP batch", "the one-workgroup kernel has no free columns; solve such problems one at a time")
     refuse_correctors(correctors, "the small-LP batch")
     refuse_refine(refine, "the small-LP batch")
     refuse_dense_cols(dense_cols, "the small-LP batch")          # (the one-workgroup kernel has no split: ValueError, never dropped)
@@ -270,7 +272,8 @@ def solve_small_qp_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, to
     workgroup per problem, one grid per kernel variant present), read-back, close.  Every problem error is a ValueError naming the
     problem's index: a bad shape, more than 128 rows, a negative or non-finite g, a product list too large for the path.  The
     front end has no detect_infeasibility (the tests are the LP's), and correctors, refine and dense_cols are not parameters: the
-    one-workgroup loop runs none of them."""
+    one-workgroup loop runs none of them, and no free columns either (free is not a parameter, so Python itself
+    refuses the keyword)."""
     if start not in ("reference", "mehrotra"):
         raise ValueError('start must be "reference" or "mehrotra"')
     check_scale(scale)

@@ -166,6 +166,14 @@ struct ipm_handle {
     int64_t quad_nnz = 0;                 // positive entries of g
     double* quad_g = nullptr;             // g in the handle's units (g C^2 on a scaled handle), zero in the padding; constant during a
                                           // solve, so the roll-back snapshot carries nothing of it
+    std::vector<char> quad_pos;           // host: g_j > 0 (empty without a term), what the free-column checks read
+    std::vector<char> bnd_finite;         // host: u_j finite (empty without a finite bound), for the same checks
+    // free columns with curvature (ipm_set_free_columns): own allocation of np bytes, made on first use
+    bool free_on = false;                 // the set is not empty: the Free kernel instantiations run
+    std::vector<int> free_cols;           // the set, in the caller's order
+    std::vector<char> free_host;          // host: column j is free (empty without a set), what ipm_set_bounds reads
+    unsigned char* free_mark = nullptr;   // 1 on the free columns, 0 elsewhere and in the padding (written whole); scale-free and
+                                          // constant during a solve, so neither the equilibration nor the roll-back snapshot touch it
     // centrality correctors (ipm_set_centrality_correctors): up to mcc.k rounds per iteration re-use its factor
     Rounds<MccCtl, MCC_CTL_DOUBLES> mcc{&MCC_KIND};   // mem: q v dx ds r3 r3g | qz dw dz r4 r4g (n-vectors) | dy (m-vector) | partial minima [2][MAXPART] | record | its copy
     // iterative refinement of the normal-equations solves (ipm_set_refinement): up to ref.k rounds behind every solve
@@ -425,6 +433,8 @@ static BndArgs bnd_args(ipm_handle* h) {
     b.qz = p + 7 * np; b.nU = h->bnd_nU;
     return b;
 }
+
+static FreeArgs free_args(const ipm_handle* h) { return FreeArgs{h->free_mark, (int)h->free_cols.size()}; }
 
 // centrality correctors: views into mcc.mem.  mcc_vec_args / mcc_bnd_args are the handle's views with the candidate's arrays in place.
 static const int MCC_NVECS = 11;

@@ -374,6 +374,8 @@ static void fill_stats(ipm_handle* h, ipm_stats* st, double ms) {
 static int check_ready(ipm_handle* h, const char* who) {
     if (!h) return fail(h, IPM_ERR_INVALID_ARG, "%s: NULL handle", who);
     if (!h->haveA || !h->haveBC || !h->haveState) return fail(h, IPM_ERR_STATE, "%s: A, (b,c) and a state must be set first", who);
+    if (h->free_on && !h->quad)          // (a set given before the term is checked against it by ipm_set_quadratic; none ever came)
+        return fail(h, IPM_ERR_INVALID_ARG, "%s: column %d is a free column (ipm_set_free_columns) without a quadratic term: a free column needs g > 0 (ipm_set_quadratic)", who, h->free_cols[0]);
     return IPM_OK;
 }
 
@@ -563,6 +565,7 @@ extern "C" int ipm_init_state_mehrotra(ipm_handle* h, int32_t* pivots_fixed) {
     if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_init_state_mehrotra: NULL handle");
     if (!h->haveA) return fail(h, IPM_ERR_STATE, "ipm_init_state_mehrotra: A not set");
     if (!h->haveBC) return fail(h, IPM_ERR_STATE, "ipm_init_state_mehrotra: (b, c) not set");
+    if (h->free_on) return fail(h, IPM_ERR_INVALID_ARG, "ipm_init_state_mehrotra: the handle has free columns (ipm_set_free_columns): the least-squares start is not restated for them; use ipm_init_state");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
     for (int attempt = 0;; ++attempt) {                     // second pass only after a recovered poll time-out

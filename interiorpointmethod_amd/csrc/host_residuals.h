@@ -34,15 +34,27 @@ template <LsType T> static void launch_vec_step(ipm_handle* h, void (*bounded)(V
     } else if (h->bnd) launch_untwinned(h, bounded, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
     else launch_twin<T>(h, (unsigned)h->vblk, {vec_args(h), 0}, st);
 }
+// A handle with free columns (ipm_set_free_columns; it holds a quadratic term, and is neither a lockstep nor a detect handle: the
+// setter and check_ready see to that) runs the Free instantiation of all seven steps.  An empty set enqueues what it always did.
+static bool free_step(ipm_handle* h, void (*plain)(VecArgs, FreeArgs), void (*bounded)(VecArgs, BndArgs, FreeArgs), hipStream_t st = nullptr, unsigned grid = 0) {
+    if (!h->free_on) return false;
+    const dim3 g(grid ? grid : (unsigned)h->vblk), b(grid ? 64 : VBLK);
+    if (h->bnd) launch_untwinned(h, bounded, g, b, st, vec_args(h), bnd_args(h), free_args(h));
+    else launch_untwinned(h, plain, g, b, st, vec_args(h), free_args(h));
+    return true;
+}
 static void launch_prepare(ipm_handle* h, hipStream_t st) {
     const double* g = h->quad_g;
-    if (h->quad && h->bnd) launch_untwinned(h, prepare_bounded_quad_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g);      // (never with detect: refused)
+    if (h->free_on && h->bnd) launch_untwinned(h, prepare_bounded_free_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g, free_args(h));
+    else if (h->free_on) launch_untwinned(h, prepare_free_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g, free_args(h));
+    else if (h->quad && h->bnd) launch_untwinned(h, prepare_bounded_quad_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g);      // (never with detect: refused)
     else if (h->quad) launch_untwinned(h, prepare_quad_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g);
     else if (h->bnd && h->detect) launch_untwinned(h, prepare_bounded_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
     else if (h->detect) launch_twin<LS_PREPARE_DETECT>(h, (unsigned)h->vblk, {vec_args(h), det_args(h)}, st);
     else launch_vec_step<LS_PREPARE>(h, prepare_bounded_kernel, st);
 }
 static void launch_stop_test(ipm_handle* h, hipStream_t st) {
+    if (free_step(h, stop_test_free_kernel, stop_test_bounded_free_kernel, st, 1u)) return;
     if (h->bnd && h->detect) launch_untwinned(h, stop_test_bounded_detect_kernel, dim3(1), dim3(64), st, vec_args(h), bnd_args(h), det_args(h));
     else if (h->bnd) launch_untwinned(h, stop_test_bounded_kernel, dim3(1), dim3(64), st, vec_args(h), bnd_args(h));
     else if (h->detect) launch_twin<LS_STOP_TEST_DETECT>(h, 1u, {vec_args(h), det_args(h)}, st);
@@ -50,13 +62,17 @@ static void launch_stop_test(ipm_handle* h, hipStream_t st) {
 }
 static void launch_scaling(ipm_handle* h) {      // (residual-stream iteration only, which is never recorded: no twin, nothing to refuse)
     const double* g = h->quad_g;
-    if (h->quad && h->bnd) hipLaunchKernelGGL(scaling_bounded_quad_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), bnd_args(h), g);
+    if (h->free_on && h->bnd) hipLaunchKernelGGL(scaling_bounded_free_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), bnd_args(h), g, free_args(h));
+    else if (h->free_on) hipLaunchKernelGGL(scaling_free_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), g, free_args(h));
+    else if (h->quad && h->bnd) hipLaunchKernelGGL(scaling_bounded_quad_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), bnd_args(h), g);
     else if (h->quad) hipLaunchKernelGGL(scaling_quad_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), g);
     else if (h->bnd) hipLaunchKernelGGL(scaling_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), bnd_args(h));
     else hipLaunchKernelGGL(scaling_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h));
 }
 static void launch_direction(ipm_handle* h, int corr) {
-    if (h->bnd) launch_untwinned(h, direction_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), corr, bnd_args(h));
+    if (h->free_on && h->bnd) launch_untwinned(h, direction_bounded_free_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), corr, bnd_args(h), free_args(h));
+    else if (h->free_on) launch_untwinned(h, direction_free_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), corr, free_args(h));
+    else if (h->bnd) launch_untwinned(h, direction_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), corr, bnd_args(h));
     else launch_twin<LS_DIRECTION>(h, (unsigned)h->vblk, {vec_args(h), corr});
 }
 // The three vector kernels of a centrality-corrector round (vector_ops.h: mcc_*).  No lockstep twins: ipm_set_centrality_correctors
@@ -73,9 +89,9 @@ static void launch_mcc_accept(ipm_handle* h) {
     if (h->bnd) launch_untwinned(h, mcc_accept_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, 0), bnd_args(h), mcc_bnd_args(h));
     else launch_untwinned(h, mcc_accept_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, 0));
 }
-static void launch_mu_aff(ipm_handle* h) { launch_vec_step<LS_MU_AFF>(h, mu_aff_bounded_kernel, nullptr, mu_aff_quad_kernel, mu_aff_bounded_quad_kernel); }
-static void launch_corrector_rhs(ipm_handle* h) { launch_vec_step<LS_CORR_RHS>(h, corrector_rhs_bounded_kernel); }
-static void launch_update(ipm_handle* h) { launch_vec_step<LS_UPDATE>(h, update_bounded_kernel, nullptr, update_quad_kernel, update_bounded_quad_kernel); }
+static void launch_mu_aff(ipm_handle* h) { if (!free_step(h, mu_aff_free_kernel, mu_aff_bounded_free_kernel)) launch_vec_step<LS_MU_AFF>(h, mu_aff_bounded_kernel, nullptr, mu_aff_quad_kernel, mu_aff_bounded_quad_kernel); }
+static void launch_corrector_rhs(ipm_handle* h) { if (!free_step(h, corrector_rhs_free_kernel, corrector_rhs_bounded_free_kernel)) launch_vec_step<LS_CORR_RHS>(h, corrector_rhs_bounded_kernel); }
+static void launch_update(ipm_handle* h) { if (!free_step(h, update_free_kernel, update_bounded_free_kernel)) launch_vec_step<LS_UPDATE>(h, update_bounded_kernel, nullptr, update_quad_kernel, update_bounded_quad_kernel); }
 
 // r_b, r_c, d, predictor v, stop test (and, with IPM_FLAG_DETECT_INFEASIBILITY, the infeasibility tests): the one launch site of the
 // stop test of every multi-kernel path (dense, sparse envelope, sparse factor, fused formation + factorization, lockstep)

@@ -326,7 +326,7 @@ extern "C" int ipm_destroy(ipm_handle* h) {
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->h_sc) { std::lock_guard<std::mutex> lock(g_hsc_mutex); g_hsc_pool.push_back(h->h_sc); h->h_sc = nullptr; }
-    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->quad_g, (void*)h->mcc.mem, (void*)h->ref.mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
+    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->quad_g, (void*)h->free_mark, (void*)h->mcc.mem, (void*)h->ref.mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
         dev_free(h->device, h->stream, p);
     ff_release(h);
     free_sparse_factor(h);
@@ -378,6 +378,15 @@ extern "C" int ipm_set_bc(ipm_handle* h, const double* b, const double* c) {
     return IPM_OK;
 }
 
+// free columns (ipm_set_free_columns) hold no s: every seam that writes a state zeroes it there
+static int enqueue_free_zero_s(ipm_handle* h) {
+    if (!h->free_on) return IPM_OK;
+    hipLaunchKernelGGL(free_zero_s_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, (const unsigned char*)h->free_mark, h->s, (int)h->n);
+    HIP_TRY(h, hipGetLastError());
+    return IPM_OK;
+}
+static bool free_is(const ipm_handle* h, int64_t j) { return h->free_on && h->free_host[(size_t)j] != 0; }
+
 extern "C" int ipm_set_state(ipm_handle* h, const double* x, const double* y, const double* s) {
     if (!h || !x || !y || !s) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_state: bad arguments");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -386,6 +395,7 @@ extern "C" int ipm_set_state(ipm_handle* h, const double* x, const double* y, co
     HIP_TRY(h, hipMemcpyAsync(h->x, x, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->y, y, sizeof(double) * h->m, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->s, s, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
+    if (int rc_ = enqueue_free_zero_s(h)) return rc_;              // free columns: s = 0, whatever was passed
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     mark_fresh_state(h);
     return IPM_OK;
@@ -412,12 +422,16 @@ extern "C" int ipm_set_bounds(ipm_handle* h, const double* u) {
         for (int64_t j = 0; j < h->n; ++j) {
             const double v = u[j];
             if (!(v >= 0.0)) return fail(h, IPM_ERR_INVALID_INPUT, "ipm_set_bounds: u[%lld] = %g (bounds must be >= 0, +inf for none)", (long long)j, v);
-            if (v < std::numeric_limits<double>::infinity()) ++nU;
+            if (v < std::numeric_limits<double>::infinity()) {
+                if (free_is(h, j))
+                    return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_bounds: u[%lld] = %g is finite, but column %lld is a free column (ipm_set_free_columns): it takes no bound", (long long)j, v, (long long)j);
+                ++nU;
+            }
         }
     }
     h->predictor_valid = false;
     if (nU == 0) {                                             // NULL or all +inf: the unbounded code, exactly
-        h->bnd = false; h->bnd_nU = 0;
+        h->bnd = false; h->bnd_nU = 0; h->bnd_finite.clear();
         if (h->haveBC) hipLaunchKernelGGL(norm2_kernel, dim3(1), dim3(VBLK), 0, h->stream, h->b, (int)h->m, &h->sc->b_norm);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -436,6 +450,8 @@ extern "C" int ipm_set_bounds(ipm_handle* h, const double* u) {
         return fail(h, IPM_ERR_INVALID_INPUT, "ipm_set_bounds: the handle's scaling would push a bound out of the normal fp64 range");
     HIP_TRY(h, hipMemcpyAsync(h->bnd_mem, uu.data(), sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
     h->bnd = true; h->bnd_nU = nU;
+    h->bnd_finite.assign((size_t)h->n, 0);
+    for (int64_t j = 0; j < h->n; ++j) h->bnd_finite[(size_t)j] = u[j] < std::numeric_limits<double>::infinity();
     const BndArgs bd = bnd_args(h);
     hipLaunchKernelGGL(bnd_fill_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, h->stream, bd.u, bd.w, bd.z, (int)np, 1.0, 0);
     if (h->haveBC) hipLaunchKernelGGL(bnd_norm2_kernel, dim3(1), dim3(VBLK), 0, h->stream, h->b, (int)h->m, bd.u, (int)h->n, &h->sc->b_norm);
@@ -459,8 +475,11 @@ extern "C" int ipm_set_quadratic(ipm_handle* h, const double* g) {
             if (v > 0.0) ++nnz;
         }
     }
+    for (int c : h->free_cols)                                 // a free column keeps its curvature: 1 / g_j is its scaling
+        if (!g || !(g[c] > 0.0))
+            return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: g[%d] = %g, but column %d is a free column (ipm_set_free_columns) and needs g > 0; clear the free set first", c, g ? g[c] : 0.0, c);
     if (nnz == 0) {                                            // NULL or all zeros: the LP code, exactly
-        h->quad = false; h->quad_nnz = 0; h->predictor_valid = false;
+        h->quad = false; h->quad_nnz = 0; h->predictor_valid = false; h->quad_pos.clear();
         return IPM_OK;
     }
     if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle was created with IPM_FLAG_LOCKSTEP (the Quad kernels have no batched twins)");
@@ -480,6 +499,8 @@ extern "C" int ipm_set_quadratic(ipm_handle* h, const double* g) {
     HIP_TRY(h, hipMemcpyAsync(h->quad_g, gg.data(), sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->quad = true; h->quad_nnz = nnz; h->predictor_valid = false;
+    h->quad_pos.assign((size_t)h->n, 0);
+    for (int64_t j = 0; j < h->n; ++j) h->quad_pos[(size_t)j] = g[j] > 0.0;
     return IPM_OK;
 }
 
@@ -492,6 +513,60 @@ extern "C" int ipm_get_quadratic(ipm_handle* h, double* g, int64_t* nonzeros) {
     HIP_TRY(h, hipMemcpyAsync(g, h->quad_g, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     eq_out(h, g, h->eq_c, true); eq_out(h, g, h->eq_c, true);      // scaled handle: g' / C^2
+    return IPM_OK;
+}
+
+// Free columns with curvature.  The marks are the library's own allocation of np bytes, made on first use and kept
+// (clearing only switches the Free kernels off); the whole vector is written, so the padding is zero before any kernel reads it.
+extern "C" int ipm_set_free_columns(ipm_handle* h, const int32_t* idx, int32_t count) {
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: NULL handle");
+    if (count < 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: count = %d", (int)count);
+    if (count == 0 || !idx) {                                  // cleared: the Quad (or LP) code, exactly
+        h->free_cols.clear(); h->free_host.clear(); h->free_on = false; h->predictor_valid = false;
+        return IPM_OK;
+    }
+    if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle was created with IPM_FLAG_LOCKSTEP (the Free kernels have no batched twins)");
+    if (h->detect) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the tests are the LP's and are not restated)");
+    if (h->small) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle runs the fused small kernel, which has no free columns; set them before A (ipm_set_A_csc then takes the multi-kernel path)");
+    std::vector<char> seen((size_t)h->n, 0);
+    for (int32_t t = 0; t < count; ++t) {
+        const int32_t j = idx[t];
+        if (j < 0 || j >= h->n) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: column index %d out of range", (int)j);
+        if (seen[(size_t)j]) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: column index %d is duplicated", (int)j);
+        seen[(size_t)j] = 1;
+        if (h->quad && !h->quad_pos[(size_t)j]) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: column %d has g = 0: a free column needs curvature (ipm_set_quadratic)", (int)j);
+        if (h->bnd && h->bnd_finite[(size_t)j]) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: column %d has a finite upper bound (ipm_set_bounds): a free column takes none", (int)j);
+    }
+    if ((int64_t)count >= h->n) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: all %d columns free leaves no complementarity pair (mu would be 0/0)", (int)count);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t np = (size_t)h->np;
+    if (!h->free_mark && dev_malloc(h->device, h->stream, (void**)&h->free_mark, np) != hipSuccess)
+        return fail(h, IPM_ERR_HIP, "ipm_set_free_columns: %lld bytes could not be allocated", (long long)np);
+    std::vector<unsigned char> mk(np, 0);
+    for (int32_t t = 0; t < count; ++t) mk[(size_t)idx[t]] = 1;
+    HIP_TRY(h, hipMemcpyAsync(h->free_mark, mk.data(), np, hipMemcpyHostToDevice, h->stream));
+    h->free_cols.assign(idx, idx + count); h->free_host.swap(seen); h->free_on = true; h->predictor_valid = false;
+    if (int rc_ = enqueue_free_zero_s(h)) return rc_;              // a state the handle holds loses s on the new free columns
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return IPM_OK;
+}
+
+extern "C" int ipm_get_free_columns(ipm_handle* h, int32_t* idx, int32_t cap, int32_t* count) {
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_free_columns: NULL handle");
+    if (cap < 0 || (cap > 0 && !idx)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_free_columns: bad arguments");
+    const int32_t k = (int32_t)h->free_cols.size();
+    if (count) *count = k;
+    for (int32_t t = 0; t < k && t < cap; ++t) idx[t] = h->free_cols[(size_t)t];
+    return IPM_OK;
+}
+
+// test hook: a column vector of the iteration as the device holds it (the handle's units: no unscaling), n entries
+extern "C" int ipm_debug_get_column_vector(ipm_handle* h, int32_t which, double* out) {
+    if (!h || !out || which < 0 || which > 3) return fail(h, IPM_ERR_INVALID_ARG, "ipm_debug_get_column_vector: bad arguments");
+    const double* src[4] = {h->rc, h->d, h->v, h->q};
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpyAsync(out, src[which], sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return IPM_OK;
 }
 
@@ -533,7 +608,7 @@ static int enqueue_init_state(ipm_handle* h, double y0) {
         hipLaunchKernelGGL(bnd_fill_kernel, dim3(gn), dim3(256), 0, h->stream, bd.u, bd.w, bd.z, (int)h->n, 1.0, 0);
     }
     HIP_TRY(h, hipGetLastError());
-    return IPM_OK;
+    return enqueue_free_zero_s(h);                                  // free columns: x = 1 like every column, s = 0
 }
 
 extern "C" int ipm_init_state(ipm_handle* h, double y0) {

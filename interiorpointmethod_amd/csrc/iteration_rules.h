@@ -86,6 +86,50 @@ __device__ __forceinline__ double quad_bnd_theta(double x, double s, double w, d
 __device__ __forceinline__ double quad_objective(double c, double g, double x) { return (c + 0.5 * g * x) * x; }
 __device__ __forceinline__ double quad_step(double ap, double ad) { return fmin(ap, ad); }
 
+// Free columns with curvature (ipm_set_free_columns): column j of a Quad handle with g_j > 0 that carries no sign
+// constraint -- no s_j (stored as exactly 0), no bound (u_j = +inf), no complementarity pair.  What factor-model QPs need:
+// Q = diag(g) + F F^T becomes t = F^T x with free t and 1/2 t.t in the diagonal.  The Free instantiations differ from the Quad
+// ones in the rows below, each stated here once; the mark is an np-vector of bytes of the library's own (1 = free, 0 elsewhere and
+// in the padding; constant during a solve), one more coalesced stream and no index gather:
+//   dual residual  r_c = (A^T y)_j - c_j - g_j x_j                    (free_rc: quad_rc with s_j = 0)
+//   scaling        d = 1 / g_j                                        (free_theta: finite, constant, exact; never x / (s + g x),
+//                                                                      which is 0/0 at x_j = 0; scaling_kernel and prepare_kernel
+//                                                                      write it concurrently: one expression)
+//   predictor      q = 0, v = d r_c                                   (free_rhs_column; the corrector's column alike: no sigma mu)
+//   objective      (c_j + 1/2 g_j x_j) x_j                            (quad_objective, unchanged)
+//   recovery       dx = d w + v, ds = 0 (dw = dz = 0)                 (free_direction_column)
+//   ratio tests    no contribution to minp or mind
+//   mu, mu_aff, sigma: no term; the pair count is n - n_free (+ |U|)  (free_pair_count) in the stop test and the centring
+//   update         x += alpha dx; s stays 0                           (free_update_column)
+//   stop test      r_c of a free column counts in ||r_c||; it adds nothing to the gap
+// Eliminating dx_j = (A^T dy + r_c)_j / g_j from row j of the Newton system, A^T dy - g dx = -r_c, puts 1/g_j on the diagonal of
+// Theta: formation, every factorization path, the sweeps, refinement and the dense-column split read only d and serve it unchanged.
+// The one step length of quad_step applies as to every quadratic handle.  A handle keeps at least one pair (n - n_free + |U| >= 1).
+struct FreeArgs {
+    const unsigned char* mark;     // [np] 1 on the free columns
+    int nfree;
+};
+__device__ __forceinline__ bool free_in(const FreeArgs& fr, int j) { return fr.mark[j] != 0; }
+__device__ __forceinline__ double free_rc(double aty, double c, double g, double x) { return quad_rc(aty - c, g, x); }
+__device__ __forceinline__ double free_theta(double g) { return 1.0 / g; }
+template <bool Bounded>
+__device__ __forceinline__ double free_pair_count(int n, const BndArgs& bd, const FreeArgs& fr) { return pair_count<Bounded>(n - fr.nfree, bd); }
+// q = 0, v = d r_c: the column of the predictor's and of the corrector's right-hand side (Bounded: qz = 0, the column is outside U)
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void free_rhs_column(const Cols& a, const BndArgs& bd, int j, double dj, double rcj) {
+    a.q[j] = 0.0;
+    a.v[j] = dj * rcj;
+    if constexpr (Bounded) bd.qz[j] = 0.0;
+}
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void free_direction_column(const Cols& a, int j, double w, double* DX, double* DS, double* DW, double* DZ) {
+    DX[j] = a.d[j] * w + a.v[j];
+    DS[j] = 0.0;
+    if constexpr (Bounded) { DW[j] = 0.0; DZ[j] = 0.0; }
+}
+template <class Cols>
+__device__ __forceinline__ void free_update_column(const Cols& a, int j, double ap) { a.x[j] += ap * a.dx[j]; }
+
 // Infeasibility tests of IPM_FLAG_DETECT_INFEASIBILITY, on the iterate of a stop test that said "continue":
 //   primal infeasible: beta = b.y - u_U.z_U > 0 and max_j (A^T y - z)_j+ <= eps_p beta   (certificate y / beta, z / beta)
 //   dual infeasible:   gamma = -c.x > 0 and max(||A x||_inf, max x_U) <= eps_d gamma      (certificate x / gamma)

@@ -174,14 +174,31 @@ __device__ __forceinline__ double col_sum(const double* atp, int rc_chunks, int 
 // pass holds anyway (A^T y from col_sum, A x = r_b + b), no extra pass over A
 // Quad (ipm_set_quadratic; g: the np-vector of the diagonal): r_c, d and the objective by the quad_* rules, one more streamed vector
 // (residual_cols of small_lp.h is the hand-kept second copy of this column, its Quad branches included: keep the two in step)
-template <bool Bounded = false, bool Detect = false, bool Quad = false>
-__device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, const double* g = nullptr) {
+// Free (ipm_set_free_columns; fr: the byte marks and their count): a marked column by the free_* rules -- r_c without s, d = 1 / g,
+// q = 0, v = d r_c, nothing into x.s -- one more streamed vector of bytes
+template <bool Bounded = false, bool Detect = false, bool Quad = false, bool Free = false>
+__device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, const double* g = nullptr,
+                                                    FreeArgs fr = FreeArgs{}) {
+    static_assert(!Free || (Quad && !Detect), "a free column needs curvature: Free is only meaningful with Quad");
     __shared__ double red[VBLK];
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     double rc2 = 0.0, xs = 0.0, cx = 0.0, rb2 = 0.0;
     double by = 0.0, uz = 0.0, maty = 0.0, max_ = 0.0, mxu = 0.0;      // Detect only
     for (int j = gid; j < a.n; j += gsz) {
         double xj = a.x[j], sj = a.s[j];
+        if constexpr (Free) {
+            if (free_in(fr, j)) {
+                const double gj = g[j];
+                const double rcj = free_rc(col_sum(a.atp, a.rc_chunks, a.np, j), a.c[j], gj, xj);
+                const double dj = free_theta(gj);
+                a.rc[j] = rcj;
+                a.d[j] = dj;
+                free_rhs_column<Bounded>(a, bd, j, dj, rcj);
+                rc2 += rcj * rcj;
+                cx += quad_objective(a.c[j], gj, xj);
+                continue;
+            }
+        }
         if constexpr (Bounded) {
             const double uj = bd.u[j];
             if (bnd_in(uj)) {
@@ -248,15 +265,22 @@ __global__ __launch_bounds__(VBLK) void prepare_detect_kernel(VecArgs a) { prepa
 __global__ __launch_bounds__(VBLK) void prepare_bounded_detect_kernel(VecArgs a, BndArgs bd) { prepare_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd); }
 __global__ __launch_bounds__(VBLK) void prepare_quad_kernel(VecArgs a, const double* g) { prepare_kernel_body<false, false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, g); }
 __global__ __launch_bounds__(VBLK) void prepare_bounded_quad_kernel(VecArgs a, BndArgs bd, const double* g) { prepare_kernel_body<true, false, true>(a, blockIdx.x, gridDim.x, bd, g); }
+__global__ __launch_bounds__(VBLK) void prepare_free_kernel(VecArgs a, const double* g, FreeArgs fr) { prepare_kernel_body<false, false, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, g, fr); }
+__global__ __launch_bounds__(VBLK) void prepare_bounded_free_kernel(VecArgs a, BndArgs bd, const double* g, FreeArgs fr) { prepare_kernel_body<true, false, true, true>(a, blockIdx.x, gridDim.x, bd, g, fr); }
 
 // d = x / s only (main.py:223): what the formation of A D^2 A^T needs; the full prepare_kernel follows on the residual
 // stream while the factorization runs (host_iteration.h, enqueue_iteration).  Bounded: d = theta on U.  Quad: the quad_* scalings.
-template <bool Bounded = false, bool Quad = false>
-__device__ __forceinline__ void scaling_kernel_body(VecArgs a, BndArgs bd = BndArgs{}, const double* g = nullptr) {
+// Free: d = free_theta on the marked columns.
+template <bool Bounded = false, bool Quad = false, bool Free = false>
+__device__ __forceinline__ void scaling_kernel_body(VecArgs a, BndArgs bd = BndArgs{}, const double* g = nullptr, FreeArgs fr = FreeArgs{}) {
+    static_assert(!Free || Quad, "a free column needs curvature: Free is only meaningful with Quad");
     if (blockIdx.x == 0 && threadIdx.x == 0) a.sc->done_f = a.sc->done;      // latch for this iteration's factorization
     if (a.sc->done) return;
     const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
     for (int j = gid; j < a.n; j += gsz) {
+        if constexpr (Free) {
+            if (free_in(fr, j)) { a.d[j] = free_theta(g[j]); continue; }
+        }
         if constexpr (Bounded) {
             if (bnd_in(bd.u[j])) {
                 if constexpr (Quad) a.d[j] = quad_bnd_theta(a.x[j], a.s[j], bd.w[j], bd.z[j], g[j]);
@@ -272,12 +296,17 @@ __global__ __launch_bounds__(VBLK) void scaling_kernel(VecArgs a) { scaling_kern
 __global__ __launch_bounds__(VBLK) void scaling_bounded_kernel(VecArgs a, BndArgs bd) { scaling_kernel_body<true>(a, bd); }
 __global__ __launch_bounds__(VBLK) void scaling_quad_kernel(VecArgs a, const double* g) { scaling_kernel_body<false, true>(a, BndArgs{}, g); }
 __global__ __launch_bounds__(VBLK) void scaling_bounded_quad_kernel(VecArgs a, BndArgs bd, const double* g) { scaling_kernel_body<true, true>(a, bd, g); }
+__global__ __launch_bounds__(VBLK) void scaling_free_kernel(VecArgs a, const double* g, FreeArgs fr) { scaling_kernel_body<false, true, true>(a, BndArgs{}, g, fr); }
+__global__ __launch_bounds__(VBLK) void scaling_bounded_free_kernel(VecArgs a, BndArgs bd, const double* g, FreeArgs fr) { scaling_kernel_body<true, true, true>(a, bd, g, fr); }
 
 // stop test of check_optimality (main.py:162-173) -- one thread.
 // Bounded: ||r_b||^2 carries r_u^2 and the gap w.z (prepare_kernel), b_norm is ||(b, u_U)|| (ipm_set_bounds), mu divides by n + |U|.
 // Detect: the infeasibility tests (detect_fire) where the convergence test says "continue", before the iteration cap.
-template <bool Bounded = false, bool Detect = false>
-__device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, DetArgs dt = DetArgs{}) {
+// Free: mu divides by free_pair_count (the free columns put nothing into the gap; their r_c is in ||r_c||).
+template <bool Bounded = false, bool Detect = false, bool Free = false>
+__device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, DetArgs dt = DetArgs{},
+                                                      FreeArgs fr = FreeArgs{}) {
+    static_assert(!Free || !Detect, "the infeasibility tests are the LP's");
     if (threadIdx.x != 0 || bx_ != 0) return;
     Scalars* sc = a.sc;
     if (sc->done) return;
@@ -288,7 +317,8 @@ __device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned 
     const double obj = sum_partials(a.part, P_CX, a.nblk);
     sc->obj = obj;
     if (fabs(obj) < 1.7e308) sc->obj_last_finite = obj;          // false for NaN and Inf
-    if constexpr (Bounded) sc->mu = gap / (double)(a.n + bd.nU);
+    if constexpr (Free) sc->mu = gap / free_pair_count<Bounded>(a.n, bd, fr);
+    else if constexpr (Bounded) sc->mu = gap / (double)(a.n + bd.nU);
     else sc->mu = gap / (double)a.n;
     bool cont = (sc->e1 * (1.0 + sc->b_norm) < rb) || (sc->e2 * (1.0 + sc->c_norm) < rc) || (sc->e3 < gap);
     if (sc->force) return;
@@ -309,6 +339,8 @@ __global__ void stop_test_kernel(VecArgs a) { stop_test_kernel_body(a, blockIdx.
 __global__ void stop_test_bounded_kernel(VecArgs a, BndArgs bd) { stop_test_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 __global__ void stop_test_detect_kernel(VecArgs a, DetArgs dt) { stop_test_kernel_body<false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, dt); }
 __global__ void stop_test_bounded_detect_kernel(VecArgs a, BndArgs bd, DetArgs dt) { stop_test_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd, dt); }
+__global__ void stop_test_free_kernel(VecArgs a, FreeArgs fr) { stop_test_kernel_body<false, false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, DetArgs{}, fr); }
+__global__ void stop_test_bounded_free_kernel(VecArgs a, BndArgs bd, FreeArgs fr) { stop_test_kernel_body<true, false, true>(a, blockIdx.x, gridDim.x, bd, DetArgs{}, fr); }
 
 // The certificate of a detection (ipm_get_certificate): kind 5 -> (y / beta, z / beta), kind 6 -> x / gamma; the other parts 0.
 // out = [x (n) | y (m) | z (n)]; z = nullptr without bounds.
@@ -327,8 +359,9 @@ __global__ __launch_bounds__(256) void certificate_kernel(const double* x, const
 
 // direction_column + ratio test.  corr == 0: (dxa, dsa[, dwa, dza]) from dya with the predictor's q;
 // corr == 1: (dx, ds[, dw, dz]) from dy with the corrector's q.
-template <bool Bounded = false>
-__device__ __forceinline__ void direction_kernel_body(VecArgs a, int corr, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
+// Free: free_direction_column on the marked columns, which take no part in the ratio tests.
+template <bool Bounded = false, bool Free = false>
+__device__ __forceinline__ void direction_kernel_body(VecArgs a, int corr, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, FreeArgs fr = FreeArgs{}) {
     if (a.sc->done) return;
     __shared__ double red[VBLK];
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
@@ -338,6 +371,9 @@ __device__ __forceinline__ void direction_kernel_body(VecArgs a, int corr, const
     for (int j = gid; j < a.n; j += gsz) {
         const double xj = a.x[j], sj = a.s[j];
         const double w = col_sum(a.atp, a.rc_chunks, a.np, j);
+        if constexpr (Free) {
+            if (free_in(fr, j)) { free_direction_column<Bounded>(a, j, w, DX, DS, corr ? bd.dw : bd.dwa, corr ? bd.dz : bd.dza); continue; }
+        }
         direction_column<Bounded>(a, bd, j, w, DX, DS, corr ? bd.dw : bd.dwa, corr ? bd.dz : bd.dza, xj, sj, mp_, md_);
     }
     mp_ = block_min(mp_, red); md_ = block_min(md_, red);
@@ -348,10 +384,14 @@ __device__ __forceinline__ void direction_kernel_body(VecArgs a, int corr, const
 }
 __global__ __launch_bounds__(VBLK) void direction_kernel(VecArgs a, int corr) { direction_kernel_body(a, corr, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void direction_bounded_kernel(VecArgs a, int corr, BndArgs bd) { direction_kernel_body<true>(a, corr, blockIdx.x, gridDim.x, bd); }
+__global__ __launch_bounds__(VBLK) void direction_free_kernel(VecArgs a, int corr, FreeArgs fr) { direction_kernel_body<false, true>(a, corr, blockIdx.x, gridDim.x, BndArgs{}, fr); }
+__global__ __launch_bounds__(VBLK) void direction_bounded_free_kernel(VecArgs a, int corr, BndArgs bd, FreeArgs fr) { direction_kernel_body<true, true>(a, corr, blockIdx.x, gridDim.x, bd, fr); }
 
 // partial sums of mu_aff_column at the affine step lengths (Quad: at the one step quad_step makes of them, which the stats report)
-template <bool Bounded = false, bool Quad = false>
-__device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
+// Free: no term of a marked column.
+template <bool Bounded = false, bool Quad = false, bool Free = false>
+__device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, FreeArgs fr = FreeArgs{}) {
+    static_assert(!Free || Quad, "a free column needs curvature: Free is only meaningful with Quad");
     if (a.sc->done) return;
     __shared__ double red[VBLK];
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
@@ -359,7 +399,12 @@ __device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_
     double ad = min_partials(a.part, P_MIND_AFF, a.nblk);
     if constexpr (Quad) ap = ad = quad_step(ap, ad);
     double acc = 0.0;
-    for (int j = gid; j < a.n; j += gsz) mu_aff_column<Bounded>(a, bd, j, ap, ad, acc);
+    for (int j = gid; j < a.n; j += gsz) {
+        if constexpr (Free) {
+            if (free_in(fr, j)) continue;
+        }
+        mu_aff_column<Bounded>(a, bd, j, ap, ad, acc);
+    }
     acc = block_sum(acc, red);
     if (threadIdx.x == 0) {
         a.part[P_MUAFF * MAXPART + bx_] = acc;
@@ -370,31 +415,48 @@ __global__ __launch_bounds__(VBLK) void mu_aff_kernel(VecArgs a) { mu_aff_kernel
 __global__ __launch_bounds__(VBLK) void mu_aff_bounded_kernel(VecArgs a, BndArgs bd) { mu_aff_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 __global__ __launch_bounds__(VBLK) void mu_aff_quad_kernel(VecArgs a) { mu_aff_kernel_body<false, true>(a, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void mu_aff_bounded_quad_kernel(VecArgs a, BndArgs bd) { mu_aff_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd); }
+__global__ __launch_bounds__(VBLK) void mu_aff_free_kernel(VecArgs a, FreeArgs fr) { mu_aff_kernel_body<false, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, fr); }
+__global__ __launch_bounds__(VBLK) void mu_aff_bounded_free_kernel(VecArgs a, BndArgs bd, FreeArgs fr) { mu_aff_kernel_body<true, true, true>(a, blockIdx.x, gridDim.x, bd, fr); }
 
 // centring from the re-summed partials of mu_aff_kernel, then corrector_column
-template <bool Bounded = false>
-__device__ __forceinline__ void corrector_rhs_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
+// Free: the centring over free_pair_count pairs (centring with n - n_free columns), free_rhs_column on the marked columns.
+template <bool Bounded = false, bool Free = false>
+__device__ __forceinline__ void corrector_rhs_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, FreeArgs fr = FreeArgs{}) {
     if (a.sc->done) return;
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     const double mu = a.sc->mu;
-    const Centring ct = centring<Bounded>(sum_partials(a.part, P_MUAFF, a.nblk), mu, a.n, bd);
+    const Centring ct = centring<Bounded>(sum_partials(a.part, P_MUAFF, a.nblk), mu, Free ? a.n - fr.nfree : a.n, bd);
     const double sm = ct.sigma * mu;
-    for (int j = gid; j < a.n; j += gsz) corrector_column<Bounded>(a, bd, j, sm);
+    for (int j = gid; j < a.n; j += gsz) {
+        if constexpr (Free) {
+            if (free_in(fr, j)) { free_rhs_column<Bounded>(a, bd, j, a.d[j], a.rc[j]); continue; }
+        }
+        corrector_column<Bounded>(a, bd, j, sm);
+    }
     if (gid == 0) { a.sc->mu_aff = ct.mu_aff; a.sc->sigma = ct.sigma; }
 }
 __global__ __launch_bounds__(VBLK) void corrector_rhs_kernel(VecArgs a) { corrector_rhs_kernel_body(a, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void corrector_rhs_bounded_kernel(VecArgs a, BndArgs bd) { corrector_rhs_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
+__global__ __launch_bounds__(VBLK) void corrector_rhs_free_kernel(VecArgs a, FreeArgs fr) { corrector_rhs_kernel_body<false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, fr); }
+__global__ __launch_bounds__(VBLK) void corrector_rhs_bounded_free_kernel(VecArgs a, BndArgs bd, FreeArgs fr) { corrector_rhs_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd, fr); }
 
 // damped_step from the re-summed ratio-test minima (Quad: quad_step of the pair), update_column, y += a_d dy, record_iteration
-template <bool Bounded = false, bool Quad = false>
-__device__ __forceinline__ void update_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}) {
+// Free: free_update_column on the marked columns (s stays 0).
+template <bool Bounded = false, bool Quad = false, bool Free = false>
+__device__ __forceinline__ void update_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, FreeArgs fr = FreeArgs{}) {
+    static_assert(!Free || Quad, "a free column needs curvature: Free is only meaningful with Quad");
     if (a.sc->done) return;
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     const double eta = a.sc->eta;
     double ap = damped_step(eta, min_partials(a.part, P_MINP, a.nblk));
     double ad = damped_step(eta, min_partials(a.part, P_MIND, a.nblk));
     if constexpr (Quad) ap = ad = quad_step(ap, ad);
-    for (int j = gid; j < a.n; j += gsz) update_column<Bounded>(a, bd, j, ap, ad);
+    for (int j = gid; j < a.n; j += gsz) {
+        if constexpr (Free) {
+            if (free_in(fr, j)) { free_update_column(a, j, ap); continue; }
+        }
+        update_column<Bounded>(a, bd, j, ap, ad);
+    }
     for (int i = gid; i < a.m; i += gsz) a.y[i] += ad * a.dy[i];
     if (gid == 0) {
         Scalars* sc = a.sc;
@@ -406,6 +468,8 @@ __global__ __launch_bounds__(VBLK) void update_kernel(VecArgs a) { update_kernel
 __global__ __launch_bounds__(VBLK) void update_bounded_kernel(VecArgs a, BndArgs bd) { update_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 __global__ __launch_bounds__(VBLK) void update_quad_kernel(VecArgs a) { update_kernel_body<false, true>(a, blockIdx.x, gridDim.x); }
 __global__ __launch_bounds__(VBLK) void update_bounded_quad_kernel(VecArgs a, BndArgs bd) { update_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd); }
+__global__ __launch_bounds__(VBLK) void update_free_kernel(VecArgs a, FreeArgs fr) { update_kernel_body<false, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, fr); }
+__global__ __launch_bounds__(VBLK) void update_bounded_free_kernel(VecArgs a, BndArgs bd, FreeArgs fr) { update_kernel_body<true, true, true>(a, blockIdx.x, gridDim.x, bd, fr); }
 
 // ---------------------------------------------------------------------------------------
 // Centrality correctors (iteration_rules.h: mcc_*): the three vector kernels of one round, enqueued K times between
@@ -630,6 +694,12 @@ __global__ void bnd_fill_kernel(const double* u, double* w, double* z, int n, do
     if (j >= n) return;
     if (!bnd_in(u[j])) { w[j] = 0.0; z[j] = 0.0; }
     else if (!mask_only) { w[j] = value; z[j] = value; }
+}
+
+// s = 0 on the free columns (every seam that writes a state: ipm_init_state, ipm_set_state, ipm_set_free_columns)
+__global__ void free_zero_s_kernel(const unsigned char* mark, double* s, int n) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n && mark[j]) s[j] = 0.0;
 }
 
 }  // namespace ipm

@@ -103,6 +103,65 @@ def refuse_quadratic(quad, who, why):
         raise ValueError("quad: %s takes no quadratic term (%s)" % (who, why))
 
 
+def check_free(free, n, quad=None, ub=None, term_known=True):
+    """THE check of the `free` keyword, before any device is touched: None (no free column, the default), a sequence of distinct
+    column indices 0 .. n-1 or a boolean mask of length n -> None (also for an empty set) or a fresh int32 array, ascending for a
+    mask and in the caller's order otherwise.  A free column carries no sign constraint and no bound and needs curvature: with
+    term_known, quad (the diagonal as check_quadratic returns it, None: no term) must be positive there, and ub (None: no bounds)
+    +inf; and one column at least must keep its complementarity pair.  Every violation is a ValueError naming the column."""
+    if free is None:
+        return None
+    f = np.asarray(free)
+    if f.dtype == np.bool_:
+        if f.reshape(-1).shape[0] != n:
+            raise ValueError("free: the mask has %d entries, the problem has %d columns" % (f.reshape(-1).shape[0], n))
+        idx = np.flatnonzero(f.reshape(-1))
+    else:
+        f = f.reshape(-1)
+        if f.shape[0] and not np.issubdtype(f.dtype, np.integer):
+            if not np.issubdtype(f.dtype, np.floating) or not np.all(np.isfinite(f)) or np.any(f != np.floor(f)):
+                raise ValueError("free must be column indices or a boolean mask, not %r" % (free,))
+        idx = f.astype(np.int64)
+    if not idx.shape[0]:
+        return None
+    seen = set()
+    for j in idx.tolist():
+        if not 0 <= j < n:
+            raise ValueError("free: column index %d out of range (the problem has %d columns)" % (j, n))
+        if j in seen:
+            raise ValueError("free: column index %d is given twice" % j)
+        seen.add(j)
+    if term_known:
+        for j in idx.tolist():
+            if quad is None or not quad[j] > 0:
+                raise ValueError("free: column %d has no quadratic term (quad[%d] = %s): a free column needs curvature, g > 0" % (j, j, "none" if quad is None else repr(float(quad[j]))))
+    if ub is not None:
+        u = np.asarray(ub, dtype=np.float64).reshape(-1)
+        if u.shape[0] != n:
+            raise ValueError("ub has %d entries, the problem has %d columns" % (u.shape[0], n))
+        for j in idx.tolist():
+            if np.isfinite(u[j]):
+                raise ValueError("free: column %d has the finite upper bound %r: a free column takes none" % (j, float(u[j])))
+    if idx.shape[0] >= n:
+        raise ValueError("free: all %d columns free leaves no complementarity pair (mu would be 0/0)" % n)
+    return np.ascontiguousarray(idx, dtype=np.int32)
+
+
+def _free_count(free):
+    """The number of columns a `free` argument names: None 0, a boolean mask its True entries, else its length."""
+    if free is None:
+        return 0
+    f = np.asarray(free)
+    return int(f.sum()) if f.dtype == np.bool_ else int(f.size)
+
+
+def refuse_free(free, who, why):
+    """THE refusal of what has no free columns (the batch front ends, and lockstep / detect_infeasibility / correctors on IpmSolver):
+    a non-empty set raises instead of being dropped."""
+    if _free_count(free):
+        raise ValueError("free: %s takes no free columns (%s)" % (who, why))
+
+
 RefineInfo = collections.namedtuple("RefineInfo", "k solves applied half_rule reverts first_rel last_rel max_first_rel")
 
 
@@ -117,7 +176,7 @@ class IpmSolver:
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
                  auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
                  infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, quad=None,
-                 quad_small=False):
+                 quad_small=False, free=None):
         """check_every: solve() enqueues that many iterations at a time and reads the stop flag once per chunk (the launches behind a
         satisfied stop test return at entry, so the result does not depend on it: DESIGN.md 4-A); a lockstep batch runs chunks of the
         largest value among its members.  IPM_CHECK_EVERY in the environment, when set and not empty, OVERRIDES this argument for
@@ -145,11 +204,23 @@ class IpmSolver:
         quad_small=True (IPM_FLAG_SMALL_QUADRATIC; off by default): a problem that qualifies for the fused small path (sparse A, at
         most 128 rows) keeps it with a quadratic term -- the whole loop of the QP in one launch of one workgroup, and the solver may
         join solve_small_batch_solvers; set_quadratic then also accepts a term after construction.  The flag alone changes nothing
-        (no term, or a problem that does not qualify: the solver an unflagged one is, bit for bit) and lifts no refusal."""
+        (no term, or a problem that does not qualify: the solver an unflagged one is, bit for bit) and lifts no refusal.
+        free: None (default), a sequence of column indices or a boolean mask: the free columns (set_free, ipm_set_free_columns;
+        DESIGN.md 4-U) -- columns with quad > 0 and no upper bound that carry no sign constraint, what the factor form of
+        Q = diag(g) + F F^T needs (factor_qp.solve_factor_qp builds it).  Checked on the host before any device is touched
+        (check_free: ValueError naming the column) and set before A, so a small sparse problem takes the multi-kernel path.
+        lockstep, detect_infeasibility and correctors > 0 refuse a non-empty set (ValueError); so does init_state_mehrotra
+        (IpmError).  s is 0 on a free column in every state that goes in or comes out."""
         self.scale = check_scale(scale)
         correctors = check_correctors(correctors)
         refine = check_refine(refine)
         quad = check_quadratic(quad, np.asarray(c).reshape(-1).shape[0] if prepared is None else prepared.n)
+        n_cols = np.asarray(c).reshape(-1).shape[0] if prepared is None else prepared.n
+        free = check_free(free, n_cols, quad, ub if prepared is None else getattr(prepared, "ub", None))
+        if lockstep:
+            refuse_free(free, "a lockstep solver", "the batch has no Free kernels; solve such problems one at a time")
+        if detect_infeasibility:
+            refuse_free(free, "detect_infeasibility=True", "the infeasibility tests are the LP's")
         if lockstep:
             refuse_quadratic(quad, "a lockstep solver", "the batch has no quadratic kernels; solve such problems one at a time")
         if detect_infeasibility:
@@ -220,6 +291,13 @@ class IpmSolver:
         if quad is not None:                 # before A: ipm_set_A_csc then chooses the one-workgroup small path only with quad_small
             try:
                 self._check(lib.ipm_set_quadratic(h, _dptr(quad)))
+            except Exception:
+                self.close()
+                raise
+        self._n_free = 0                     # the size of the set the library holds (info["free"] reads it without a library call)
+        if free is not None:                 # before A too: a handle with free columns never takes the one-workgroup small path
+            try:
+                self._set_free_checked(free)
             except Exception:
                 self.close()
                 raise
@@ -409,6 +487,36 @@ class IpmSolver:
         keeps the term it held."""
         g = check_quadratic(g, self.n)
         self._check(self._lib.ipm_set_quadratic(self._h, None if g is None else _dptr(g)))
+
+    def _set_free_checked(self, idx):
+        self._check(self._lib.ipm_set_free_columns(self._h, None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   0 if idx is None else int(idx.shape[0])))
+        self._n_free = 0 if idx is None else int(idx.shape[0])
+
+    def set_free(self, free):
+        """ipm_set_free_columns: the free columns (indices or a boolean mask) from the next iteration on; None or an empty set
+        clears them, and the solver runs exactly the code it ran without.  The indices are checked on the host first (ValueError:
+        range, duplicates, every column free); the library decides what depends on the handle's other data (IpmError: a column
+        without curvature or with a finite bound, a lockstep or detect_infeasibility solver, the fused small path).  A state the
+        solver holds gets s = 0 on the new free columns; after CLEARING, set a state anew (init_state / set_state) before iterating:
+        the former free columns still hold s = 0."""
+        self._set_free_checked(check_free(free, self.n, term_known=False))
+
+    def free_columns(self):
+        """ipm_get_free_columns: the set in the order it was given, as a fresh int32 array (empty: none)."""
+        k = C.c_int32(0)
+        self._check(self._lib.ipm_get_free_columns(self._h, None, 0, C.byref(k)))
+        out = np.zeros(k.value, dtype=np.int32)
+        if k.value:
+            self._check(self._lib.ipm_get_free_columns(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), k.value, C.byref(k)))
+        return out
+
+    def debug_column_vector(self, which):
+        """ipm_debug_get_column_vector (test hook): "rc", "d", "v" or "q" of the last newton_direction / iterate as the device holds
+        it, length n, in the handle's units."""
+        out = np.empty(self.n)
+        self._check(self._lib.ipm_debug_get_column_vector(self._h, ("rc", "d", "v", "q").index(which), _dptr(out)))
+        return out
 
     def quadratic(self):
         """ipm_get_quadratic: the diagonal in the caller's units as a fresh array of length n (zeros without a term)."""

@@ -62,6 +62,40 @@ def separable_qp(m, n, seed, bounded=False, mixed=False):
     return A, A @ x, c, g, u, x, y
 
 
+def factor_qp(m, n, k, seed, bounded=False):
+    """Factor-model QP with a KNOWN optimum: min c.x + 1/2 x.(diag(g) + F F^T) x, A x = b, 0 <= x (<= u)
+    -> (A (m, n) dense, b, c, g, F (n, k), u (None unless bounded; +inf = no bound), x_star, y_star), vectors 1-D.
+
+    Built as separable_qp builds its own: A ~ N(0, 1); a column is active with probability 0.75 (x* ~ U(0.5, 2), s* = 0), otherwise
+    x* = 0, s* ~ U(0.5, 2); bounded: half the columns get u = x* + U(0.5, 2) and a tenth of the bounded active ones sit AT their
+    bound (u = x*, z* ~ U(0.5, 2)); g ~ U(0.1, 2); F ~ N(0, 1) / sqrt(n); y* ~ N(0, 1); c = A^T y* + s* - z* - g o x* - F (F^T x*),
+    b = A x*.  The same assertion: at least 1.25 m columns strictly between their bounds.  PCG64(seed)."""
+    rng = np.random.default_rng(seed)
+    A = rng.standard_normal((m, n))
+    active = rng.random(n) < 0.75
+    x = np.where(active, rng.uniform(0.5, 2.0, n), 0.0)
+    s = np.where(active, 0.0, rng.uniform(0.5, 2.0, n))
+    z = np.zeros(n)
+    u = None
+    between = active.copy()
+    if bounded:
+        u = np.full(n, np.inf)
+        has_u = rng.random(n) < 0.5
+        u[has_u] = x[has_u] + rng.uniform(0.5, 2.0, int(has_u.sum()))
+        at = has_u & active & (rng.random(n) < 0.1)
+        u[at] = x[at]
+        z[at] = rng.uniform(0.5, 2.0, int(at.sum()))
+        between &= ~at
+    g = rng.uniform(0.1, 2.0, n)
+    F = rng.standard_normal((n, k)) / np.sqrt(n)
+    y = rng.standard_normal(m)
+    if int(between.sum()) < 1.25 * m:
+        raise AssertionError("factor_qp(%d, %d, %d, seed=%d): %d columns strictly between their bounds, fewer than 1.25 m"
+                             % (m, n, k, seed, int(between.sum())))
+    c = A.T @ y + s - z - g * x - F @ (F.T @ x)
+    return A, A @ x, c, g, F, u, x, y
+
+
 def block_angular_lp(m, block, k, seed=0, link_fill=0.5):
     """Block-angular LP with k linking columns: A = [block-diagonal sparse part | k linking columns | identity], m rows
     in blocks of `block` consecutive rows -> (A as scipy CSC, b (m, 1), c (n, 1), the indices of the linking columns).
