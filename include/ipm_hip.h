@@ -86,7 +86,10 @@ enum {
     IPM_FLAG_SPARSE_FACTOR = 8,
     /* The handle is created for ipm_solve_batch (the LOCKSTEP batch: iteration k of several LPs in the same launches): implies
      * IPM_FLAG_SINGLE_STREAM | IPM_FLAG_NO_DEVICE_POLLING and block-step triangular solves, so that every launch of its iteration has
-     * a batched twin.  Such a handle still works with every other entry point (ipm_solve included: same arithmetic, one LP). */
+     * a batched twin.  Such a handle still works with every other entry point (ipm_solve included: same arithmetic, one LP).
+     * Who may join a batch: a handle with IPM_FLAG_DETECT_INFEASIBILITY, and -- only with IPM_FLAG_LOCKSTEP_BOUNDS -- one with finite
+     * upper bounds.  Refused on such a handle whatever else is set: a quadratic term, free columns, centrality correctors, refinement
+     * rounds, dense columns (none has batched twins). */
     IPM_FLAG_LOCKSTEP = 16,
     /* Detect infeasible and unbounded LPs.  At every stop test whose convergence test says "continue" (never
      * under ipm_iterate) the iterate (x, y, s, w, z) is tested, with beta = b^T y - u_U^T z_U and gamma = -c^T x:
@@ -108,7 +111,15 @@ enum {
      * the LP kernels, bit for bit what an unflagged handle runs, and a handle that does not qualify for the small path ignores the
      * flag.  It lifts no refusal: a term with IPM_FLAG_DETECT_INFEASIBILITY or IPM_FLAG_LOCKSTEP, centrality correctors, refinement
      * rounds and dense columns on the small path are refused as without it. */
-    IPM_FLAG_SMALL_QUADRATIC = 64
+    IPM_FLAG_SMALL_QUADRATIC = 64,
+    /* Bit 7 (value 128).  With IPM_FLAG_LOCKSTEP (ipm_create refuses it alone): a handle that holds finite upper bounds
+     * (ipm_set_bounds) may join the lockstep batch -- ipm_batch_add and ipm_solve_batch accept it, next to unbounded and detecting
+     * handles.  Its eight bounded vector steps run as batched kernels of their own types (csrc/lockstep.h: LsBndType), each the body of
+     * the single-LP bounded kernel, so a joined bounded handle computes what ipm_solve computes on it alone, bit for bit, (w, z), the
+     * history and the roll-back of the automatic Tikhonov restart included.  An opt-in: without the flag a bounded lockstep handle is
+     * refused by the batch as before.  The flag alone changes nothing: a flagged handle without a finite bound is an ordinary lockstep
+     * handle, bit for bit.  It lifts no other refusal of IPM_FLAG_LOCKSTEP. */
+    IPM_FLAG_LOCKSTEP_BOUNDS = IPM_FLAG_SMALL_QUADRATIC << 1
 };
 
 typedef struct ipm_handle ipm_handle;
@@ -222,8 +233,9 @@ int ipm_init_state_mehrotra(ipm_handle* h, int32_t* pivots_fixed);
  * handle then runs exactly the unbounded code.  NaN or negative entries: IPM_ERR_INVALID_INPUT.  The bounded set U
  * gets an upper slack w (x + w = u) and its dual z inside the Newton system: the normal matrix keeps order m
  * (DESIGN.md 4-B).  Sets w = z = 1 on U.  The bound vectors are allocated by the library on first use and freed by
- * ipm_destroy; the workspace size does not change.  Invalidates a pending predictor.  A handle with bounds cannot
- * join the lockstep batch (ipm_batch_add / ipm_solve_batch: IPM_ERR_INVALID_ARG). */
+ * ipm_destroy; the workspace size does not change.  Invalidates a pending predictor.  A handle with bounds joins
+ * the lockstep batch only when it was created with IPM_FLAG_LOCKSTEP_BOUNDS (then with the arithmetic of ipm_solve on it alone,
+ * (w, z) included); without that flag ipm_batch_add / ipm_solve_batch refuse it with IPM_ERR_INVALID_ARG. */
 int ipm_set_bounds(ipm_handle* h, const double* u);
 /* (w, z): host arrays of length n; entries outside U are ignored on set and read back as 0.  IPM_ERR_STATE without bounds. */
 int ipm_set_bound_state(ipm_handle* h, const double* w, const double* z);
@@ -334,9 +346,10 @@ int ipm_solve(ipm_handle* h, double tol_p, double tol_d, double tol_gap, int32_t
 /* The LOCKSTEP BATCH of the batched-LP mode (the driver loop of script.py:147-173 over independent LPs, on one GPU): ipm_solve for n
  * handles AT ONCE, iteration k of all of them in the same launches (csrc/lockstep.h).  Every handle must have been created with
  * IPM_FLAG_LOCKSTEP on the same device, hold a sparse A of more than 128 rows on the dense-tile factor (not IPM_FLAG_SPARSE_FACTOR)
- * and have A, b, c and a state set.  Same arguments and per-handle semantics as ipm_solve (stop test, iteration cap, automatic
+ * and have A, b, c and a state set.  Handles with IPM_FLAG_DETECT_INFEASIBILITY, handles with finite upper bounds (ipm_set_bounds;
+ * only with IPM_FLAG_LOCKSTEP_BOUNDS, IPM_ERR_INVALID_ARG without) and plain ones may be mixed freely.  Same arguments and per-handle semantics as ipm_solve (stop test, iteration cap, automatic
  * Tikhonov shift); stats[i] (may be NULL) describes handle i, with solve_ms the device time of the whole batch.  The arithmetic
- * of a handle is exactly that of ipm_solve on it alone: bit-identical iterates.  Launched on the first handle's stream. */
+ * of a handle is exactly that of ipm_solve on it alone: bit-identical iterates, for a bounded handle (w, z) included.  Launched on the first handle's stream. */
 int ipm_solve_batch(ipm_handle** handles, int32_t n, double tol_p, double tol_d, double tol_gap, int32_t max_iter, ipm_stats* stats);
 /* The same batch, incrementally: handles may JOIN between two steps (a host thread finishes an LP's set-up while the batch is already
  * running) and the caller learns which ones finished after every step (and can tear them down while the batch runs on).
@@ -589,7 +602,7 @@ int ipm_debug_ff_trace(ipm_handle* h, long long* out, int64_t capacity, int64_t*
 int ipm_debug_ls_merge(int32_t n, const int32_t* off, const int32_t* types_flat, int32_t max_group, int32_t aligned,
                        int32_t* out_steps, int32_t cap_steps, int32_t* out_members);
 /* Test hook (host only, launches nothing): the merged schedule that the last ipm_batch_step of `b` launched, four words per step
- * in launch order: {kernel type (LsType of csrc/lockstep.h), members (handles served by the launch, at most 64), blocks (the packed
+ * in launch order: {kernel type (LsType or, for a bounded step, LsBndType of csrc/lockstep.h), members (handles served by the launch, at most 64), blocks (the packed
  * 1-D grid: the sum of the members' own grids), lds (dynamic LDS bytes: the largest among the members)}.  *count = the number of
  * steps (0 before the first step); IPM_ERR_INVALID_ARG, with *count set, when capacity (in words) < 4 * steps
  * (tests/test_gpu_lockstep_wide.py). */

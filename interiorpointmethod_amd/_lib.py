@@ -34,6 +34,7 @@ FLAG_SPARSE_FACTOR = 8          # include/ipm_hip.h: IPM_FLAG_SPARSE_FACTOR
 FLAG_LOCKSTEP = 16              # include/ipm_hip.h: IPM_FLAG_LOCKSTEP
 FLAG_DETECT_INFEASIBILITY = 32  # include/ipm_hip.h: IPM_FLAG_DETECT_INFEASIBILITY
 FLAG_SMALL_QUADRATIC = 64       # include/ipm_hip.h: IPM_FLAG_SMALL_QUADRATIC
+FLAG_LOCKSTEP_BOUNDS = 128      # include/ipm_hip.h: IPM_FLAG_LOCKSTEP_BOUNDS
 ERR_WORKSPACE = -4
 ABI_VERSION = 4
 HISTORY_CAPACITY = 1024         # IPM_HISTORY_CAPACITY

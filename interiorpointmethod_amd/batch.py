@@ -22,7 +22,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import _lib
-from .analysis import prepare
+from .analysis import _upper_bounds, prepare
 from .api import _auto_regularize, _solve_info, solve_with_info
 from .batches import LockstepBatch, lockstep_eligible, small_batch_eligible, solve_small_batch_solvers
 from .analysis import refuse_dense_cols
@@ -41,12 +41,28 @@ STATUS_INVALID_INPUT = -6.0          # IPM_ERR_INVALID_INPUT surfaced as a statu
 STATUS_ERROR = -99.0
 
 
-def predicted_cost(m, n, nnz_col_sq=None, iters_est=40):
-    """Predicted solve time (arbitrary units) for the LPT partition.  Measured on MI355X (profiles/r01_netlib_*.json):
+def unpack_problem(problem):
+    """THE tuple rule of the batched-LP mode, stated once: a problem is (A, b, c) or (A, b, c, ub) -> (A, b, c, u).  ub: None or the
+    native upper bounds 0 <= x <= ub, length n, +inf = none; u is what analysis._upper_bounds makes of it on the
+    host -- float64, or None when no entry is finite, so a triple and a 4-tuple without a finite bound are the same problem.
+    ValueError for any other tuple length, a wrong length of ub, NaN or negative entries: before any device is touched."""
+    if len(problem) == 3:
+        (A, b, c), ub = problem, None
+    elif len(problem) == 4:
+        A, b, c, ub = problem
+    else:
+        raise ValueError("a problem is (A, b, c) or (A, b, c, ub), got %d entries" % len(problem))
+    return A, b, c, _upper_bounds(ub, A.shape[1])
+
+
+def predicted_cost(m, n=None, nnz_col_sq=None, iters_est=40):
+    """predicted_cost(m, n) or predicted_cost(problem), a problem being what unpack_problem takes.  Predicted solve time (arbitrary units) for the LPT partition.  Measured on MI355X (profiles/r01_netlib_*.json):
     one iteration costs about 0.1 ms + 0.11 ms per 128-row block of the normal matrix from m = 27 to m = 16675 -- the
     blocked Cholesky is a latency chain, not a flop count -- so the model is linear in the block count.  (The cubic
     flop model this replaces put 11.2 s of a 12.5 s suite on one of two ranks.)  The iteration count is not
     predictable (14 ... the cap) and is taken as equal."""
+    if n is None:
+        m, n = unpack_problem(m)[0].shape
     nblk = (int(m) + 127) // 128
     return iters_est * (0.1 + 0.11 * nblk)
 
@@ -98,14 +114,14 @@ def _guarded(solve_fn, problem, **kw):
 def solve_one(problem, device=0, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, concurrent=False, start="reference",
               tol_gap=None, detect_infeasibility=False, device_start=False, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0,
               dense_cols=None):
-    """Solve one LP (A, b, c) on `device` with the HIP path -> dict of statistics.  detect_infeasibility: the record's status
+    """Solve one LP, (A, b, c) or (A, b, c, ub) (unpack_problem), on `device` with the HIP path -> dict of statistics.  detect_infeasibility: the record's status
     may be 5 (primal infeasible) or 6 (dual infeasible, i.e. unbounded); DESIGN.md 4-C.  device_start: with start="mehrotra", the
     start is computed on the device (solve_with_info).  correctors: centrality-corrector rounds per iteration, refine: refinement
     rounds per normal-equations solve, dense_cols: the dense-column split (solve_with_info)."""
-    A, b, c = problem
+    A, b, c, ub = unpack_problem(problem)
     t0 = time.perf_counter()
     try:
-        _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device,
+        _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub,
                                         regularize=regularize, concurrent=concurrent, start=start, tol_gap=tol_gap,
                                         detect_infeasibility=detect_infeasibility, device_start=device_start, scale=scale,
                                         scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols)
@@ -144,7 +160,11 @@ def solve_shard(problems, ids, device=0, solve_fn=solve_one, workers=1, **kw):
     four; with the two-stream look-ahead of a lone solve two LPs already collide (2 x DEGEN3: 1.3x the time of one, 3 x:
     2.4x), with one stream per handle four overlap almost perfectly (4 x: 1.15x; tools/concurrency_probe.py) although
     each solve alone is 10-25 % slower without the look-ahead.  Results do not depend on the interleaving (every handle
-    is independent and deterministic, and both schedules perform the same arithmetic)."""
+    is independent and deterministic, and both schedules perform the same arithmetic).  With solve_one a problem is (A, b, c) or
+    (A, b, c, ub): a bad ub raises ValueError here, before any device is touched (unpack_problem)."""
+    if solve_fn is solve_one:
+        for i in ids:
+            unpack_problem(problems[i])
     rec = np.zeros((len(ids), NF), dtype=np.float64)
     free_streams = queue.Queue()        # the rank's worker streams, the same ones in every call (see _lockstep_streams)
     for st in _lockstep_streams(device, max(1, workers)):
@@ -220,6 +240,7 @@ class _LockstepShard:
 
     def __init__(self, problems, ids, device, workers, small_batch, y0, stop_kw, handle_kw, start="reference"):
         self.problems, self.ids, self.device, self.workers, self.small_batch, self.y0 = problems, ids, device, workers, small_batch, y0
+        self.lp = {i: unpack_problem(problems[i]) for i in ids}      # (A, b, c, u) of every LP: a bad ub raises here, before any device work
         self.start = start                  # "reference": init_state(y0); "mehrotra": the device start, on the set-up thread's stream
         self.stop_kw = stop_kw              # tol, max_iter, tol_gap: of every solve of the shard
         self.handle_kw = handle_kw          # device, regularize, concurrent=True, detect_infeasibility: of every handle of the shard
@@ -239,7 +260,7 @@ class _LockstepShard:
 
     # -- classification of the LPs
     def _rows_of(self, i):
-        return self.problems[i][0].shape[0]
+        return self.lp[i][0].shape[0]
 
     def _wants_lockstep(self, i):
         return 128 < self._rows_of(i) <= LOCKSTEP_MAX_ROWS
@@ -302,8 +323,8 @@ class _LockstepShard:
         return sv
 
     def _small_setup(self, problem, device=0, row=None, i=None, prepared=None, t0=None):
-        # the handle _classic() would create for this LP; False: the library does not put it on the small path
-        A, b, c = problem
+        # the handle _classic() would create for this LP (its bounds travel in `prepared`); False: the library does not put it on the small path
+        A, b, c, _ = unpack_problem(problem)
         sv = self._started(A, b, c, prepared)
         try:
             if not small_batch_eligible(sv):
@@ -318,16 +339,18 @@ class _LockstepShard:
 
     def _setup(self, row_i):
         row, i = row_i
-        A, b, c = self.problems[i]
+        A, b, c, u = self.lp[i]
         ready = self.ready[self._cls_of(i)]
         t0 = time.perf_counter()
         sv, handed = None, False
         try:
             # host analysis ONCE: row order, factor path.  Up to LOCKSTEP_DENSE_ROWS rows the dense-tile factor even where a lone solve
             # would take the sparse one: inside a batch an LP whose program is shorter than the class leader's adds no launches
-            prepared = prepare(A, b, c, factor=("dense" if self._wants_lockstep(i) and A.shape[0] <= LOCKSTEP_DENSE_ROWS else None))
+            # (the bounds travel in `prepared` from here on: to the batch handle, the small-batch handle and the one-at-a-time runners)
+            prepared = prepare(A, b, c, factor=("dense" if self._wants_lockstep(i) and A.shape[0] <= LOCKSTEP_DENSE_ROWS else None), ub=u)
             if self._wants_lockstep(i) and prepared.factor != "sparse":
-                sv = self._started(A, b, c, prepared, lockstep=True)      # (the start runs on the handle's own stream, before it joins)
+                # (the start runs on the handle's own stream, before it joins; an LP with a finite bound opts into the bounded twins)
+                sv = self._started(A, b, c, prepared, lockstep=True, **(dict(lockstep_bounds=True) if u is not None else {}))
                 if lockstep_eligible(sv):
                     ready.put((row, i, sv, time.perf_counter() - t0))
                     handed = True
@@ -352,7 +375,7 @@ class _LockstepShard:
 
     # -- the one-at-a-time runners: the LPs no batch serves
     def _classic(self, problem, device=0, prepared=None):
-        A, b, c = problem
+        A, b, c, _ = unpack_problem(problem)        # (ub: in `prepared`, which solve_with_info hands to the handle)
         _, _, _, info = solve_with_info(A, b, c, y0=self.y0, prepared=prepared, start=self.start, device_start=True, **self.stop_kw, **self.handle_kw)
         return dict(info)
 
@@ -444,7 +467,8 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
     """Solve problems[i] for i in ids on this rank's GPU with the LOCKSTEP BATCH -> (len(ids), NF) records.
 
     `workers` host threads prepare the LPs (host analysis, handle, upload), largest first.  An LP of more than 128 rows on the
-    dense-tile factor JOINS the running batch of its size class as soon as its handle is ready (ipm_batch_add between two steps):
+    dense-tile factor JOINS the running batch of its size class as soon as its handle is ready (ipm_batch_add between two steps;
+    a problem is (A, b, c) or (A, b, c, ub), unpack_problem, and an LP with a finite bound joins like any other: lockstep_bounds=True):
     iteration k of all LPs of a class in the same launches (csrc/lockstep.h), so that the rank's chains of launches are those of
     the longest LP of each class instead of eight chains that share four hardware queues.  The LPs a batch cannot serve -- up to
     128 rows (fused single-workgroup kernel), the sparse multifrontal factor above LOCKSTEP_DENSE_ROWS rows -- are solved one after
@@ -580,13 +604,14 @@ def lockstep_wanted(problems, world=1, workers=8, mode="auto"):
     if workers <= 1:
         return False
     if mode == "auto":
-        return sum(1 for p in problems if p[0].shape[0] > 128) >= LOCKSTEP_MIN_LPS * max(1, world)
+        return sum(1 for p in problems if unpack_problem(p)[0].shape[0] > 128) >= LOCKSTEP_MIN_LPS * max(1, world)
     return True
 
 
 def run_batch(problems, costs=None, device=0, dist=None, gather_device=None, solve_fn=solve_one, workers=1,
               schedule="static", store=None, collective_at_world_one=False, lockstep=False, free=None, **kw):
-    """Shard `problems` (list of (A, b, c)) over the ranks of `dist`, solve, gather statistics.
+    """Shard `problems` (list of (A, b, c) or (A, b, c, ub): unpack_problem; ub = native upper bounds, checked on the host before any
+    device work when solve_fn is solve_one) over the ranks of `dist`, solve, gather statistics.
 
     schedule="static": deterministic LPT partition on the predicted cost, no scheduling traffic at all.
     schedule="dynamic" (N > 1): the ranks pull LPs, most expensive first, from a counter on `store` (a
@@ -597,6 +622,9 @@ def run_batch(problems, costs=None, device=0, dist=None, gather_device=None, sol
     dist.all_gather): that is how the RCCL branch is exercised on a one-GPU box (tests/test_gpu_parity.py).
     free (free columns of a quadratic problem) raises ValueError: a batch's problems are (A, b, c) triples, LPs."""
     refuse_free(free, "run_batch", "its problems are LPs; solve such problems one at a time")
+    if solve_fn is solve_one:
+        for p in problems:
+            unpack_problem(p)
     global _CALLS
     _CALLS += 1
     live = dist is not None and dist.is_initialized()

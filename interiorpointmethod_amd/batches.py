@@ -24,7 +24,9 @@ def _scatter_stats(solvers, stats):           # each solver takes its statistics
 def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None, correctors=0, refine=0, dense_cols=None, free=None):
     """ipm_solve_batch: solve the LPs of `solvers` (IpmSolver objects created with lockstep=True on one device, a state set) AT ONCE,
     iteration k of all of them in the same launches (csrc/lockstep.h) -> list of statistics dicts, one per solver.  Per-LP semantics
-    and arithmetic are those of IpmSolver.solve on each of them alone (bit-identical iterates).  correctors > 0: ValueError (the rounds
+    and arithmetic are those of IpmSolver.solve on each of them alone (bit-identical iterates).  Bounded solvers (ub=) join when they
+    were created with lockstep_bounds=True, next to unbounded ones, (w, z) bit-identical too; without it the library refuses them
+    (IpmError).  correctors > 0: ValueError (the rounds
     have no batched twins; a lockstep solver refuses set_correctors for the same reason); refine > 0 likewise, and free columns."""
     refuse_free(free, "the lockstep batch", "the Free kernels have no batched twins; solve such problems one at a time")
     refuse_correctors(correctors, "the lockstep batch")
@@ -38,7 +40,7 @@ def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None, correctors=0,
 class LockstepBatch:
     """ipm_batch_*: the lockstep batch, incrementally.  add(solver) lets an IpmSolver (lockstep=True, a state set) JOIN between two
     steps; step() runs opt.check_every iterations of every active LP in the same launches and returns the solvers that finished,
-    each with its statistics in solver.stats.  The solvers stay owned by the caller (close them after they are reported finished)."""
+    each with its statistics in solver.stats.  A bounded solver joins only with lockstep_bounds=True (IpmError otherwise).  The solvers stay owned by the caller (close them after they are reported finished)."""
 
     def __init__(self, device=0, tol=1e-8, max_iter=5000, tol_gap=None, stream=None):
         """stream: a torch.cuda.Stream the batch's launches go to (the caller keeps it alive); None: a stream of the batch's own."""
@@ -76,7 +78,7 @@ class LockstepBatch:
 
     def schedule(self):
         """ipm_debug_batch_schedule (test hook, host only): the merged schedule the last step() launched -> list of dicts, one per
-        launch in order: type (LsType of csrc/lockstep.h), members (LPs served by the launch), blocks (the packed grid: the sum of
+        launch in order: type (LsType, or LsBndType for a bounded step, of csrc/lockstep.h), members (LPs served by the launch), blocks (the packed grid: the sum of
         the members' own grids) and lds (dynamic LDS bytes).  Empty before the first step."""
         n = C.c_int32(0)
         code = self._lib.ipm_debug_batch_schedule(self._b, None, 0, C.byref(n))
@@ -101,8 +103,9 @@ class LockstepBatch:
 
 def lockstep_eligible(solver):
     """Can this IpmSolver join solve_lockstep?  Sparse A on the dense-tile factor, more than 128 rows (the small LPs have their fused
-    single-workgroup kernel, the sparse-factor LPs their tree sweeps).  A solver with upper bounds has no lockstep twin."""
-    return bool(solver.sparse and solver.factor != "sparse" and not solver.bounded and not solver.schedule()["fused_small"])
+    single-workgroup kernel, the sparse-factor LPs their tree sweeps).  A solver with upper bounds only when it was created with
+    lockstep_bounds=True (the opt-in to the batch's bounded kernels)."""
+    return bool(solver.sparse and solver.factor != "sparse" and (not solver.bounded or solver.lockstep_bounds) and not solver.schedule()["fused_small"])
 
 
 def small_batch_eligible(solver):

@@ -210,13 +210,13 @@ struct ipm_handle {
 struct LsLaunch { int type; LsRec rec; };
 // A launch site of the iteration names its kernel type and fills ONE argument struct (lockstep.h: LsTwin<T>): the launch is recorded
 // while a program is being recorded (record_twin: also the GEMM launchers' way in, ls_gemm_hook), else the single-LP kernel runs.
-template <LsType T> static void record_twin(ipm_handle* h, unsigned gridx, const LsArgs<T>& a, unsigned lds = 0) {
+template <int T> static void record_twin(ipm_handle* h, unsigned gridx, const LsArgs<T>& a, unsigned lds = 0) {
     LsLaunch L{};
     L.type = T; L.rec.gridx = gridx; L.rec.lds = lds;
     memcpy(L.rec.args, &a, sizeof a);
     h->ls_rec->push_back(L);
 }
-template <LsType T> static void launch_twin(ipm_handle* h, unsigned grid, const LsArgs<T>& a, hipStream_t st = nullptr, unsigned lds = 0) {
+template <int T> static void launch_twin(ipm_handle* h, unsigned grid, const LsArgs<T>& a, hipStream_t st = nullptr, unsigned lds = 0) {
     if (h->ls_rec) record_twin<T>(h, grid, a, lds);
     else LsTwin<T>::single(a, grid, lds, st ? st : h->stream);
 }

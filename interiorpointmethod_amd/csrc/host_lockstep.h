@@ -3,7 +3,7 @@
 #pragma once
 // ------------------------------------------------------------------------------- lockstep batch (lockstep.h)
 // the GEMM launchers' way into a recording: the type is the one whose declared tile shape (lockstep.h) is the launcher's instantiation
-template <LsType... T> static bool ls_record_gemm(ipm_handle* h, int bm, int bn, int bk, int wm, int wn, const GemmNT& g, unsigned grid) {
+template <int... T> static bool ls_record_gemm(ipm_handle* h, int bm, int bn, int bk, int wm, int wn, const GemmNT& g, unsigned grid) {
     return ((LsTwin<T>::is(bm, bn, bk, wm, wn) && (record_twin<T>(h, grid, g), true)) || ...);
 }
 static void ls_gemm_hook(void* ctx, int bm, int bn, int bk, int wm, int wn, const GemmNT& g, int grid) {
@@ -15,8 +15,10 @@ static void ls_gemm_hook(void* ctx, int bm, int bn, int bk, int wm, int wn, cons
         ok = !g.wait_on && !g.signal && ls_record_gemm<LS_CHOL_UPDATE, LS_GEMM_32_128_32, LS_GEMM_64_64_16, LS_GEMM_64_128_16, LS_GEMM_128_128_16, LS_GEMM_32_32_32>(h, bm, bn, bk, wm, wn, g, (unsigned)grid);
     if (!ok) h->ls_cut = true;                               // not recordable: ls_record_program reports it
 }
+// (a handle with finite upper bounds only with IPM_FLAG_LOCKSTEP_BOUNDS, the opt-in to the bounded twins)
+static bool ls_bounds_ok(const ipm_handle* h) { return !h->bnd || (h->opt.flags & IPM_FLAG_LOCKSTEP_BOUNDS); }
 static bool ls_eligible(const ipm_handle* h) {
-    return h->lockstep && !h->bnd && h->sparse && !h->small && !h->spf && h->lookahead == 0 && h->stream2 == nullptr && h->B && h->invD &&
+    return h->lockstep && ls_bounds_ok(h) && h->sparse && !h->small && !h->spf && h->lookahead == 0 && h->stream2 == nullptr && h->B && h->invD &&
            h->haveA && h->haveBC && h->haveState;
 }
 // the launch sequence of ONE iteration of the handle, recorded (nothing is launched)
@@ -144,7 +146,7 @@ extern "C" const char* ipm_batch_last_error(const ipm_batch* b) { return b ? b->
 extern "C" int ipm_batch_add(ipm_batch* b, ipm_handle* h, double tol_p, double tol_d, double tol_gap, int32_t max_iter, int32_t* index) {
     if (!b || !h || max_iter < 0) return bfail(b, IPM_ERR_INVALID_ARG, "ipm_batch_add: bad arguments");
     if (h->device != b->device) return bfail(b, IPM_ERR_INVALID_ARG, "ipm_batch_add: the handle lives on device %d, the batch on %d", h->device, b->device);
-    if (h->bnd) return bfail(b, IPM_ERR_INVALID_ARG, "ipm_batch_add: a handle with upper bounds (ipm_set_bounds) has no lockstep twin");
+    if (!ls_bounds_ok(h)) return bfail(b, IPM_ERR_INVALID_ARG, "ipm_batch_add: a handle with upper bounds (ipm_set_bounds) has no lockstep twin");
     if (!ls_eligible(h)) return bfail(b, IPM_ERR_STATE, "ipm_batch_add: not a lockstep handle (IPM_FLAG_LOCKSTEP, sparse A, more than 128 rows, dense-tile factor, A / b / c / state set)");
     B_TRY(b, hipSetDevice(b->device));
     if (h->stream != b->S) B_TRY(b, hipStreamSynchronize(h->stream));      // everything the handle did on its own stream is complete
@@ -198,17 +200,17 @@ extern "C" int ipm_batch_step(ipm_batch* b, int32_t* finished, int32_t cap, int3
         b->dirty = false;
         b->t_merge += secs(t_in); b->n_merge++;
         if (getenv("IPM_LS_DEBUG")) {
-            size_t longest = 0; int cnt[LS_NTYPES] = {0};
+            size_t longest = 0; int cnt[LS_NTYPES_ALL] = {0};
             for (int i : b->active) longest = std::max(longest, b->prog[(size_t)i].size());
             for (const LsStep& st : b->steps) cnt[st.type]++;
             fprintf(stderr, "[lockstep] %zu LPs active, longest program %zu launches, merged schedule %zu steps (%zu records); steps by type:", b->active.size(), longest, b->steps.size(), b->recs.size());
-            for (int t = 0; t < LS_NTYPES; ++t) if (cnt[t]) fprintf(stderr, " %d:%d", t, cnt[t]);
+            for (int t = 0; t < LS_NTYPES_ALL; ++t) if (cnt[t]) fprintf(stderr, " %d:%d", t, cnt[t]);
             fprintf(stderr, "\n");
         }
     }
     const auto t_mid = std::chrono::steady_clock::now();
     static const bool ls_prof = getenv("IPM_LS_PROF") != nullptr;      // diagnostic: a synchronisation after every launch, wall time per kernel type
-    static double tot[LS_NTYPES]; static long cnt[LS_NTYPES]; static long calls = 0;
+    static double tot[LS_NTYPES_ALL]; static long cnt[LS_NTYPES_ALL]; static long calls = 0;
     for (int c = 0; c < b->chunk; ++c)
         for (const LsStep& st : b->steps) {
             const auto t0 = ls_prof ? std::chrono::steady_clock::now() : t_mid;
@@ -219,9 +221,9 @@ extern "C" int ipm_batch_step(ipm_batch* b, int32_t* finished, int32_t cap, int3
         }
     if (ls_prof && ++calls % 25 == 0) {
         fprintf(stderr, "[lockstep prof] %zu active, %zu steps; us per launch (launches) by type:", b->active.size(), b->steps.size());
-        for (int t = 0; t < LS_NTYPES; ++t) if (cnt[t]) fprintf(stderr, " %d:%.1f(%ld)", t, 1e6 * tot[t] / cnt[t], cnt[t]);
+        for (int t = 0; t < LS_NTYPES_ALL; ++t) if (cnt[t]) fprintf(stderr, " %d:%.1f(%ld)", t, 1e6 * tot[t] / cnt[t], cnt[t]);
         fprintf(stderr, "\n");
-        for (int t = 0; t < LS_NTYPES; ++t) { tot[t] = 0; cnt[t] = 0; }
+        for (int t = 0; t < LS_NTYPES_ALL; ++t) { tot[t] = 0; cnt[t] = 0; }
     }
     for (int i : b->active) B_TRY(b, hipMemcpyAsync(b->hs[(size_t)i]->h_sc, b->hs[(size_t)i]->sc, sizeof(Scalars), hipMemcpyDeviceToHost, S));
     b->t_enqueue += secs(t_mid); b->n_launch += (long)b->chunk * (long)b->steps.size();
@@ -290,7 +292,7 @@ extern "C" int ipm_solve_batch(ipm_handle** hs, int32_t n, double tol_p, double 
     if (!hs || n <= 0 || max_iter < 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_batch: bad arguments");
     for (int i = 0; i < n; ++i) if (!hs[i]) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_batch: NULL handle");
     for (int i = 0; i < n; ++i)
-        if (hs[i]->bnd) return fail(hs[i], IPM_ERR_INVALID_ARG, "ipm_solve_batch: handle %d has upper bounds (ipm_set_bounds): no lockstep twin", i);
+        if (!ls_bounds_ok(hs[i])) return fail(hs[i], IPM_ERR_INVALID_ARG, "ipm_solve_batch: handle %d has upper bounds (ipm_set_bounds): no lockstep twin", i);
     ipm_batch* b = nullptr;
     int rc = ipm_batch_create(hs[0]->device, nullptr, &b);
     if (rc) return rc;

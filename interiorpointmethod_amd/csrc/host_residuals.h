@@ -22,16 +22,17 @@ static void launch_gemv_t_rows(ipm_handle* h, const double* u, int chunk0, int c
                        h->A + r0 * h->np, h->np, h->rows_per_chunk, (int)h->np, u + r0, h->atp + (int64_t)chunk0 * h->np, &h->sc->done);
 }
 
-// The vector steps of the iteration, ONE launch function each: it holds the step's fork between the plain kernel and the detect
-// kernel (both have lockstep twins) and the bounded kernels (none: a bounded handle is never recorded, ls_eligible).
+// The vector steps of the iteration, ONE launch function each: it holds the step's fork between the plain kernel, the detect
+// kernel and their bounded forms.  All four have lockstep twins (T: the plain type, TB: its bounded twin, whose `single` is the
+// *_bounded_kernel -- outside a recording a bounded handle enqueues what it always did; whether one may be recorded is ls_eligible's).
 // A handle with a quadratic term (ipm_set_quadratic) runs the Quad instantiation of the four steps that have one (quad, quad_bounded:
-// no twins either -- a lockstep handle is refused the term); every other step is the LP's.
-template <LsType T> static void launch_vec_step(ipm_handle* h, void (*bounded)(VecArgs, BndArgs), hipStream_t st = nullptr,
-                                                void (*quad)(VecArgs) = nullptr, void (*quad_bounded)(VecArgs, BndArgs) = nullptr) {
+// no twins -- a lockstep handle is refused the term); every other step is the LP's.
+template <int T, int TB> static void launch_vec_step(ipm_handle* h, hipStream_t st = nullptr,
+                                                     void (*quad)(VecArgs) = nullptr, void (*quad_bounded)(VecArgs, BndArgs) = nullptr) {
     if (h->quad && quad) {
         if (h->bnd) launch_untwinned(h, quad_bounded, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
         else launch_untwinned(h, quad, dim3(h->vblk), dim3(VBLK), st, vec_args(h));
-    } else if (h->bnd) launch_untwinned(h, bounded, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
+    } else if (h->bnd) launch_twin<TB>(h, (unsigned)h->vblk, {vec_args(h), 0, bnd_args(h)}, st);
     else launch_twin<T>(h, (unsigned)h->vblk, {vec_args(h), 0}, st);
 }
 // A handle with free columns (ipm_set_free_columns; it holds a quadratic term, and is neither a lockstep nor a detect handle: the
@@ -49,14 +50,14 @@ static void launch_prepare(ipm_handle* h, hipStream_t st) {
     else if (h->free_on) launch_untwinned(h, prepare_free_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g, free_args(h));
     else if (h->quad && h->bnd) launch_untwinned(h, prepare_bounded_quad_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g);      // (never with detect: refused)
     else if (h->quad) launch_untwinned(h, prepare_quad_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g);
-    else if (h->bnd && h->detect) launch_untwinned(h, prepare_bounded_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
+    else if (h->bnd && h->detect) launch_twin<LS_PREPARE_DETECT_BND>(h, (unsigned)h->vblk, {vec_args(h), bnd_args(h), det_args(h)}, st);
     else if (h->detect) launch_twin<LS_PREPARE_DETECT>(h, (unsigned)h->vblk, {vec_args(h), det_args(h)}, st);
-    else launch_vec_step<LS_PREPARE>(h, prepare_bounded_kernel, st);
+    else launch_vec_step<LS_PREPARE, LS_PREPARE_BND>(h, st);
 }
 static void launch_stop_test(ipm_handle* h, hipStream_t st) {
     if (free_step(h, stop_test_free_kernel, stop_test_bounded_free_kernel, st, 1u)) return;
-    if (h->bnd && h->detect) launch_untwinned(h, stop_test_bounded_detect_kernel, dim3(1), dim3(64), st, vec_args(h), bnd_args(h), det_args(h));
-    else if (h->bnd) launch_untwinned(h, stop_test_bounded_kernel, dim3(1), dim3(64), st, vec_args(h), bnd_args(h));
+    if (h->bnd && h->detect) launch_twin<LS_STOP_TEST_DETECT_BND>(h, 1u, {vec_args(h), bnd_args(h), det_args(h)}, st);
+    else if (h->bnd) launch_twin<LS_STOP_TEST_BND>(h, 1u, {vec_args(h), 0, bnd_args(h)}, st);
     else if (h->detect) launch_twin<LS_STOP_TEST_DETECT>(h, 1u, {vec_args(h), det_args(h)}, st);
     else launch_twin<LS_STOP_TEST>(h, 1u, {vec_args(h), 0}, st);
 }
@@ -72,7 +73,7 @@ static void launch_scaling(ipm_handle* h) {      // (residual-stream iteration o
 static void launch_direction(ipm_handle* h, int corr) {
     if (h->free_on && h->bnd) launch_untwinned(h, direction_bounded_free_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), corr, bnd_args(h), free_args(h));
     else if (h->free_on) launch_untwinned(h, direction_free_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), corr, free_args(h));
-    else if (h->bnd) launch_untwinned(h, direction_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), corr, bnd_args(h));
+    else if (h->bnd) launch_twin<LS_DIRECTION_BND>(h, (unsigned)h->vblk, {vec_args(h), corr, bnd_args(h)});
     else launch_twin<LS_DIRECTION>(h, (unsigned)h->vblk, {vec_args(h), corr});
 }
 // The three vector kernels of a centrality-corrector round (vector_ops.h: mcc_*).  No lockstep twins: ipm_set_centrality_correctors
@@ -89,9 +90,9 @@ static void launch_mcc_accept(ipm_handle* h) {
     if (h->bnd) launch_untwinned(h, mcc_accept_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, 0), bnd_args(h), mcc_bnd_args(h));
     else launch_untwinned(h, mcc_accept_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, 0));
 }
-static void launch_mu_aff(ipm_handle* h) { if (!free_step(h, mu_aff_free_kernel, mu_aff_bounded_free_kernel)) launch_vec_step<LS_MU_AFF>(h, mu_aff_bounded_kernel, nullptr, mu_aff_quad_kernel, mu_aff_bounded_quad_kernel); }
-static void launch_corrector_rhs(ipm_handle* h) { if (!free_step(h, corrector_rhs_free_kernel, corrector_rhs_bounded_free_kernel)) launch_vec_step<LS_CORR_RHS>(h, corrector_rhs_bounded_kernel); }
-static void launch_update(ipm_handle* h) { if (!free_step(h, update_free_kernel, update_bounded_free_kernel)) launch_vec_step<LS_UPDATE>(h, update_bounded_kernel, nullptr, update_quad_kernel, update_bounded_quad_kernel); }
+static void launch_mu_aff(ipm_handle* h) { if (!free_step(h, mu_aff_free_kernel, mu_aff_bounded_free_kernel)) launch_vec_step<LS_MU_AFF, LS_MU_AFF_BND>(h, nullptr, mu_aff_quad_kernel, mu_aff_bounded_quad_kernel); }
+static void launch_corrector_rhs(ipm_handle* h) { if (!free_step(h, corrector_rhs_free_kernel, corrector_rhs_bounded_free_kernel)) launch_vec_step<LS_CORR_RHS, LS_CORR_RHS_BND>(h); }
+static void launch_update(ipm_handle* h) { if (!free_step(h, update_free_kernel, update_bounded_free_kernel)) launch_vec_step<LS_UPDATE, LS_UPDATE_BND>(h, nullptr, update_quad_kernel, update_bounded_quad_kernel); }
 
 // r_b, r_c, d, predictor v, stop test (and, with IPM_FLAG_DETECT_INFEASIBILITY, the infeasibility tests): the one launch site of the
 // stop test of every multi-kernel path (dense, sparse envelope, sparse factor, fused formation + factorization, lockstep)

@@ -152,6 +152,9 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, IPM_ERR_NO_DEVICE, "no HIP device visible");
     if (device < 0 || device >= ndev) return fail(nullptr, IPM_ERR_INVALID_ARG, "device %d out of range (%d visible)", device, ndev);
+    static_assert(IPM_FLAG_LOCKSTEP_BOUNDS == 128, "the bit the Python host states (_lib.FLAG_LOCKSTEP_BOUNDS)");
+    if (opts && (opts->flags & IPM_FLAG_LOCKSTEP_BOUNDS) && !(opts->flags & IPM_FLAG_LOCKSTEP))
+        return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_create: IPM_FLAG_LOCKSTEP_BOUNDS without IPM_FLAG_LOCKSTEP (it opts a lockstep handle into the bounded twins, nothing else)");
     ipm_handle* h = new ipm_handle();
     h->device = device;
     if (opts) h->opt = *opts; else ipm_default_options(&h->opt);

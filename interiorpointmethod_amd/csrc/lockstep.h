@@ -36,6 +36,14 @@ enum LsType {
     LS_PREPARE_DETECT, LS_STOP_TEST_DETECT, LS_NTYPES
 };
 
+// The bounded twins (IPM_FLAG_LOCKSTEP_BOUNDS): the eight bounded vector steps of the single-stream iteration, types of their own so
+// that the wrappers above them and every single-LP kernel compile to what they compiled to before.  Their ids continue LsType's --
+// which is why LsTwin, ls_kernel, record_twin and launch_twin are keyed on int: a value past LS_NTYPES is no LsType.
+enum LsBndType {
+    LS_PREPARE_BND = LS_NTYPES, LS_PREPARE_DETECT_BND, LS_STOP_TEST_BND, LS_STOP_TEST_DETECT_BND, LS_DIRECTION_BND, LS_MU_AFF_BND, LS_CORR_RHS_BND,
+    LS_UPDATE_BND, LS_NTYPES_ALL
+};
+
 constexpr int LS_ARG_BYTES = 304;
 constexpr int LS_MAX_GROUP = 64;              // LPs per launch: the block -> LP look-up is one wave-wide load + ballot
 struct LsRec {                                // one LP's share of one global step
@@ -49,6 +57,8 @@ struct LsRec {                                // one LP's share of one global st
 
 struct LsVecA { VecArgs a; int corr; };
 struct LsVecDet { VecArgs a; DetArgs dt; };             // the infeasibility tests of a handle with IPM_FLAG_DETECT_INFEASIBILITY
+struct LsVecBnd { VecArgs a; int corr; BndArgs bd; };   // a handle with native upper bounds (ipm_set_bounds) ...
+struct LsVecBndDet { VecArgs a; BndArgs bd; DetArgs dt; };   // ... and with the infeasibility tests
 struct LsSpmv { SparseA A; int mp; const double* v; double sa, sb; const double* add; double* out; const int* done; };
 struct LsSpmvT { SparseA A; int np; const double* u; double* w; const int* done; };
 struct LsZero { double* p; int64_t n; const int* done; };
@@ -73,8 +83,8 @@ struct LsMaxdiag { const double* B; int64_t ld; int n; double* out; const int* d
 // launch of the single-LP kernel from that struct with the field list the wrapper passes to X_kernel_body.  launch_twin<T> (host
 // side) records the struct or calls `single`; ls_launch takes wrapper and block dimension from here.  The GEMM types state `is`
 // instead -- the launcher instantiation they record: launch_gemm_nt / launch_chol_update hand their struct to ls_gemm_hook.
-template <LsType T> struct LsTwin;
-template <LsType T> using LsArgs = typename LsTwin<T>::Args;
+template <int T> struct LsTwin;
+template <int T> using LsArgs = typename LsTwin<T>::Args;
 template <class A, unsigned THREADS> struct LsTwinOf {
     static_assert(sizeof(A) <= LS_ARG_BYTES && std::is_trivially_copyable<A>::value, "LsRec::args");
     using Args = A;
@@ -86,7 +96,7 @@ template <class A, unsigned THREADS> struct LsTwinOf {
     static void single(const Args& p, unsigned grid, unsigned lds, hipStream_t st) { hipLaunchKernelGGL(KERNEL, dim3(grid), block(), lds, st, __VA_ARGS__); }
 // head of the wrapper kernel of type T (optional: the second argument of __launch_bounds__), bound to the type for ls_launch
 using LsKernel = void (*)(const LsRec*, unsigned);
-template <LsType T> inline constexpr LsKernel ls_kernel = nullptr;
+template <int T> inline constexpr LsKernel ls_kernel = nullptr;
 #define LS_KERNEL(T, NAME, ...)                                                                                         \
     __global__ __launch_bounds__(LsTwin<T>::threads, ##__VA_ARGS__) void NAME(const LsRec* recs, const unsigned count); \
     template <> inline constexpr LsKernel ls_kernel<T> = NAME;                                                          \
@@ -158,6 +168,23 @@ template <> struct LsTwin<LS_CORR_RHS> : LsTwinOf<LsVecA, VBLK> { LS_SINGLE(corr
 LS_KERNEL(LS_CORR_RHS, ls_corr_rhs) { LS_ENTER(LsArgs<LS_CORR_RHS>); corrector_rhs_kernel_body(p.a, bx, r_.gridx); }
 template <> struct LsTwin<LS_UPDATE> : LsTwinOf<LsVecA, VBLK> { LS_SINGLE(update_kernel, p.a) };
 LS_KERNEL(LS_UPDATE, ls_update) { LS_ENTER(LsArgs<LS_UPDATE>); update_kernel_body(p.a, bx, r_.gridx); }
+// the bounded twins: the Bounded instantiation of the same bodies, `single` = the *_bounded*_kernel of vector_ops.h
+template <> struct LsTwin<LS_PREPARE_BND> : LsTwinOf<LsVecBnd, VBLK> { LS_SINGLE(prepare_bounded_kernel, p.a, p.bd) };
+LS_KERNEL(LS_PREPARE_BND, ls_prepare_bnd) { LS_ENTER(LsArgs<LS_PREPARE_BND>); prepare_kernel_body<true>(p.a, bx, r_.gridx, p.bd); }
+template <> struct LsTwin<LS_PREPARE_DETECT_BND> : LsTwinOf<LsVecBndDet, VBLK> { LS_SINGLE(prepare_bounded_detect_kernel, p.a, p.bd) };
+LS_KERNEL(LS_PREPARE_DETECT_BND, ls_prepare_detect_bnd) { LS_ENTER(LsArgs<LS_PREPARE_DETECT_BND>); prepare_kernel_body<true, true>(p.a, bx, r_.gridx, p.bd); }
+template <> struct LsTwin<LS_STOP_TEST_BND> : LsTwinOf<LsVecBnd, 64> { LS_SINGLE(stop_test_bounded_kernel, p.a, p.bd) };
+LS_KERNEL(LS_STOP_TEST_BND, ls_stop_test_bnd) { LS_ENTER(LsArgs<LS_STOP_TEST_BND>); stop_test_kernel_body<true>(p.a, bx, r_.gridx, p.bd); }
+template <> struct LsTwin<LS_STOP_TEST_DETECT_BND> : LsTwinOf<LsVecBndDet, 64> { LS_SINGLE(stop_test_bounded_detect_kernel, p.a, p.bd, p.dt) };
+LS_KERNEL(LS_STOP_TEST_DETECT_BND, ls_stop_test_detect_bnd) { LS_ENTER(LsArgs<LS_STOP_TEST_DETECT_BND>); stop_test_kernel_body<true, true>(p.a, bx, r_.gridx, p.bd, p.dt); }
+template <> struct LsTwin<LS_DIRECTION_BND> : LsTwinOf<LsVecBnd, VBLK> { LS_SINGLE(direction_bounded_kernel, p.a, p.corr, p.bd) };
+LS_KERNEL(LS_DIRECTION_BND, ls_direction_bnd) { LS_ENTER(LsArgs<LS_DIRECTION_BND>); direction_kernel_body<true>(p.a, p.corr, bx, r_.gridx, p.bd); }
+template <> struct LsTwin<LS_MU_AFF_BND> : LsTwinOf<LsVecBnd, VBLK> { LS_SINGLE(mu_aff_bounded_kernel, p.a, p.bd) };
+LS_KERNEL(LS_MU_AFF_BND, ls_mu_aff_bnd) { LS_ENTER(LsArgs<LS_MU_AFF_BND>); mu_aff_kernel_body<true>(p.a, bx, r_.gridx, p.bd); }
+template <> struct LsTwin<LS_CORR_RHS_BND> : LsTwinOf<LsVecBnd, VBLK> { LS_SINGLE(corrector_rhs_bounded_kernel, p.a, p.bd) };
+LS_KERNEL(LS_CORR_RHS_BND, ls_corr_rhs_bnd) { LS_ENTER(LsArgs<LS_CORR_RHS_BND>); corrector_rhs_kernel_body<true>(p.a, bx, r_.gridx, p.bd); }
+template <> struct LsTwin<LS_UPDATE_BND> : LsTwinOf<LsVecBnd, VBLK> { LS_SINGLE(update_bounded_kernel, p.a, p.bd) };
+LS_KERNEL(LS_UPDATE_BND, ls_update_bnd) { LS_ENTER(LsArgs<LS_UPDATE_BND>); update_kernel_body<true>(p.a, bx, r_.gridx, p.bd); }
 
 template <> struct LsTwin<LS_GEMV_N> : LsTwinOf<LsGemvN, 256> { LS_SINGLE(gemv_n_kernel, p.A, p.lda, p.mp, p.np, p.v, p.sa, p.sb, p.add, p.out, p.done) };
 LS_KERNEL(LS_GEMV_N, ls_gemv_n) { LS_ENTER(LsArgs<LS_GEMV_N>); gemv_n_kernel_body(p.A, p.lda, p.mp, p.np, p.v, p.sa, p.sb, p.add, p.out, p.done, bx, r_.gridx); }
@@ -191,13 +218,13 @@ LS_KERNEL(LS_GEMM_32_32_32_BATCHED, ls_gemm_32_batched, 2) {
 
 // launch one global step: `count` (<= LS_MAX_GROUP) LPs, `blocks` = the sum of their grids, `lds` = the largest dynamic LDS among them
 template <int... T> inline hipError_t ls_launch_in(std::integer_sequence<int, T...>, int type, const LsRec* d_recs, unsigned count, unsigned blocks, unsigned lds, hipStream_t st) {
-    static const struct { LsKernel kernel; dim3 block; } step[] = {{ls_kernel<(LsType)T>, LsTwin<(LsType)T>::block()}...};
-    if (type < 0 || type >= LS_NTYPES) return hipErrorInvalidValue;
+    static const struct { LsKernel kernel; dim3 block; } step[] = {{ls_kernel<T>, LsTwin<T>::block()}...};
+    if (type < 0 || type >= LS_NTYPES_ALL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(step[type].kernel, dim3(blocks), step[type].block, lds, st, d_recs, count);
     return hipGetLastError();
 }
 inline hipError_t ls_launch(int type, const LsRec* d_recs, unsigned count, unsigned blocks, unsigned lds, hipStream_t st) {
-    return ls_launch_in(std::make_integer_sequence<int, LS_NTYPES>{}, type, d_recs, count, blocks, lds, st);
+    return ls_launch_in(std::make_integer_sequence<int, LS_NTYPES_ALL>{}, type, d_recs, count, blocks, lds, st);
 }
 
 }  // namespace ipm

@@ -8,6 +8,7 @@ Same names and argument meaning as the reference (payakorn/InteriorPointMethod):
     add_bound_into_matrix(A, b, c, bound)                 -> (A, b, c, (None, None), constant)   main.py:968-1060
     new_interior_sparse(c, Aeq, beq, Aineq, bineq, lb, ub, tol)  -> objective        main.py:1081-1245
     native_form(c, Aeq, beq, Aineq, bineq, lb, ub)        -> NativeForm   (bounds="native": 0 <= x <= u in the Newton system)
+    native_problem(c, Aeq, beq, Aineq, bineq, lb, ub)     -> ((A, b, c, u), NativeForm)   (one problem of batch.run_batch)
     create_problem_from_mps_matlab(name)                  -> (c, Aineq, bineq, Aeq, beq, lb, ub)  sparse_interior.py:290-314
 
 The conversion is host-side data plumbing (scipy.sparse / numpy); the solve is libipm_hip's loop with the
@@ -178,6 +179,14 @@ def native_form(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None)
     F.offset = float(cs @ lb0)
     F.keep, F.fixed, F.lb0, F.n = keep, fixed, lb0, n
     return F
+
+
+def native_problem(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None):
+    """native_form's arguments -> ((A, b, c, u), NativeForm): the general-form problem as ONE problem of the batched-LP mode
+    (batch.run_batch and its front ends take (A, b, c, ub) tuples), and the form whose `offset` maps a record's objective back:
+    original objective = record objective + NativeForm.offset."""
+    F = native_form(c, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=lb, ub=ub)
+    return (F.A, F.b, F.c, F.u), F
 
 
 def _ray_native(F, v):

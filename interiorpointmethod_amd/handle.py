@@ -176,13 +176,16 @@ class IpmSolver:
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
                  auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
                  infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, quad=None,
-                 quad_small=False, free=None):
+                 quad_small=False, free=None, lockstep_bounds=False):
         """check_every: solve() enqueues that many iterations at a time and reads the stop flag once per chunk (the launches behind a
         satisfied stop test return at entry, so the result does not depend on it: DESIGN.md 4-A); a lockstep batch runs chunks of the
         largest value among its members.  IPM_CHECK_EVERY in the environment, when set and not empty, OVERRIDES this argument for
         every solver created while it is set.
         ub: native upper bounds 0 <= x <= ub (length n, +inf = none), checked on the host before any device
-        is touched.  The normal matrix keeps order m; a bounded solver cannot join the lockstep batch.
+        is touched.  The normal matrix keeps order m; a bounded solver joins the lockstep batch only with lockstep_bounds=True.
+        lockstep_bounds=True (IPM_FLAG_LOCKSTEP_BOUNDS; off by default, ValueError without lockstep=True): a lockstep solver with a
+        finite bound may join solve_lockstep / LockstepBatch, bit-identical to its own solve(), (w, z) included.  The
+        flag alone changes nothing (ub None or all +inf: the lockstep solver an unflagged one is) and lifts no other refusal.
         detect_infeasibility: the stop test also tests the iterate for a certificate of primal infeasibility (status 5) or of
         unboundedness (status 6) with the tolerances infeasibility_tol = (eps_p, eps_d) (IPM_FLAG_DETECT_INFEASIBILITY,
         DESIGN.md 4-C); certificate() returns it.  Off by default: the solve is then exactly the reference's loop.
@@ -212,6 +215,8 @@ class IpmSolver:
         lockstep, detect_infeasibility and correctors > 0 refuse a non-empty set (ValueError); so does init_state_mehrotra
         (IpmError).  s is 0 on a free column in every state that goes in or comes out."""
         self.scale = check_scale(scale)
+        if lockstep_bounds and not lockstep:
+            raise ValueError("lockstep_bounds=True needs lockstep=True: it opts a lockstep solver into the batch's bounded kernels")
         correctors = check_correctors(correctors)
         refine = check_refine(refine)
         quad = check_quadratic(quad, np.asarray(c).reshape(-1).shape[0] if prepared is None else prepared.n)
@@ -262,8 +267,10 @@ class IpmSolver:
                      (0 if auto_regularize else _lib.FLAG_NO_AUTO_REGULARIZE) | \
                      (_lib.FLAG_SPARSE_FACTOR if self.factor == "sparse" else 0) | \
                      (_lib.FLAG_DETECT_INFEASIBILITY if detect_infeasibility else 0) | \
-                     (_lib.FLAG_SMALL_QUADRATIC if quad_small else 0)
+                     (_lib.FLAG_SMALL_QUADRATIC if quad_small else 0) | \
+                     (_lib.FLAG_LOCKSTEP_BOUNDS if lockstep_bounds else 0)
         self.quad_small = bool(quad_small)
+        self.lockstep_bounds = bool(lockstep_bounds)
         self.detect_infeasibility = bool(detect_infeasibility)
         nbytes = C.c_size_t(0)
         self.sparse = _is_sparse(A)
