@@ -119,7 +119,19 @@ enum {
      * history and the roll-back of the automatic Tikhonov restart included.  An opt-in: without the flag a bounded lockstep handle is
      * refused by the batch as before.  The flag alone changes nothing: a flagged handle without a finite bound is an ordinary lockstep
      * handle, bit for bit.  It lifts no other refusal of IPM_FLAG_LOCKSTEP. */
-    IPM_FLAG_LOCKSTEP_BOUNDS = IPM_FLAG_SMALL_QUADRATIC << 1
+    IPM_FLAG_LOCKSTEP_BOUNDS = IPM_FLAG_SMALL_QUADRATIC << 1,
+    /* Bit 8 (value 256).  With IPM_FLAG_SMALL_QUADRATIC (ipm_create refuses it alone: a free column needs the term, and the term
+     * reaches the fused small path only with that flag): a handle that qualifies for the fused small path keeps it when it holds
+     * free columns (ipm_set_free_columns) -- the whole loop of a factor-model QP of m + k <= 128 rows runs in one launch of one
+     * workgroup (the two Free variants of the small kernel), and the handle may join ipm_solve_small_batch next to
+     * every other handle of that path.  Both call orders: ipm_set_free_columns on a handle already on the small path is accepted,
+     * and ipm_set_A_csc on a handle that holds a set may choose the path.  Every rule of ipm_set_free_columns holds unchanged
+     * (g_j > 0, no finite bound, one pair left, no detection), and so do the refusals of the small path (centrality correctors,
+     * refinement rounds, dense columns) and of Mehrotra's start (ipm_init_state_mehrotra; ipm_init_small_batch_mehrotra names the
+     * handle's index).  Off by default: the small loop and the multi-kernel path sum in different orders.  The flag alone changes
+     * nothing: a flagged handle without a set (never given, or cleared) runs the Quad or LP kernels, bit for bit what a handle
+     * with IPM_FLAG_SMALL_QUADRATIC alone runs. */
+    IPM_FLAG_SMALL_FREE = IPM_FLAG_LOCKSTEP_BOUNDS << 1
 };
 
 typedef struct ipm_handle ipm_handle;
@@ -284,7 +296,8 @@ int ipm_get_quadratic(ipm_handle* h, double* g, int64_t* nonzeros);
  * and by ipm_iterate / ipm_solve / ipm_newton_direction when no term ever came); ipm_set_quadratic clearing the term or zeroing g_j
  * on a free column; a finite u_j on a free column (here, or by ipm_set_bounds); every column free (no pair left: mu would be 0/0);
  * an IPM_FLAG_LOCKSTEP or IPM_FLAG_DETECT_INFEASIBILITY handle; a handle on the fused small path, IPM_FLAG_SMALL_QUADRATIC
- * included (set the columns before A: ipm_set_A_csc then takes the multi-kernel path); ipm_init_state_mehrotra on a handle with
+ * included (set the columns before A: ipm_set_A_csc then takes the multi-kernel path) -- unless the handle was created with
+ * IPM_FLAG_SMALL_FREE, which keeps it on that path in either call order; ipm_init_state_mehrotra on a handle with
  * free columns (its least-squares start is not restated for them).  Centrality correctors are refused as for every quadratic
  * handle.  The marks are np bytes allocated by the library on first use and freed by ipm_destroy.  Invalidates a pending predictor. */
 int ipm_set_free_columns(ipm_handle* h, const int32_t* idx, int32_t count);
@@ -374,8 +387,8 @@ int ipm_batch_stats(ipm_batch* b, int32_t index, ipm_stats* stats);
  * sides, the AFIRO class of Netlib) fill the GPU's compute units where a loop of ipm_solve keeps one of them busy.  Every handle must be
  * served by that path (ipm_get_schedule out[9] == 1), live on the same device, have A, b, c and a state set and profiling off
  * (IPM_ERR_STATE otherwise); handles with upper bounds (ipm_set_bounds), with IPM_FLAG_DETECT_INFEASIBILITY and plain ones may be mixed
- * freely in one call, and so may handles that hold a quadratic term on this path (IPM_FLAG_SMALL_QUADRATIC, bounded or not: six kernel
- * variants in all).  IPM_ERR_INVALID_ARG, with the offending index in ipm_last_error(NULL), for a NULL handle, a handle that is not on
+ * freely in one call, and so may handles that hold a quadratic term on this path (IPM_FLAG_SMALL_QUADRATIC, bounded or not), with
+ * free columns on top (IPM_FLAG_SMALL_FREE, bounded or not: eight kernel variants in all).  IPM_ERR_INVALID_ARG, with the offending index in ipm_last_error(NULL), for a NULL handle, a handle that is not on
  * the small path, a handle on another device and the same handle twice (two workgroups would race on one state); n < 0 or handles ==
  * NULL with n > 0 likewise; n == 0 returns IPM_OK and touches no device.  stream: a hipStream_t ON THE HANDLES' DEVICE the launches go to
  * (the caller's to guarantee: a stream does not tell its device), NULL = the first handle's stream; the handles may own any streams -- the batch stream waits (stream events) for each distinct one before the launch,
@@ -389,7 +402,8 @@ int ipm_solve_small_batch(ipm_handle** handles, int32_t n, double tol_p, double 
                           ipm_stats* stats);
 /* ipm_init_state_mehrotra for n handles of the fused small-LP path in ONE launch per variant (plain / bounded), one workgroup per LP.
  * Arguments are checked exactly as by ipm_solve_small_batch (NULL handle, not on the small path, other device, the same handle twice:
- * IPM_ERR_INVALID_ARG; n == 0: IPM_OK, no device touched), except that no state is needed (IPM_ERR_STATE without A or (b, c)); `stream`
+ * IPM_ERR_INVALID_ARG; n == 0: IPM_OK, no device touched), except that no state is needed (IPM_ERR_STATE without A or (b, c)) and that a
+ * handle with free columns is refused as by ipm_init_state_mehrotra (IPM_ERR_INVALID_ARG naming its index, nothing launched); `stream`
  * has the same meaning and the same event waits on the handles' own streams apply.  pivots_fixed (may be NULL): n counts,
  * pivots_fixed[i] is handle i's.  The workgroups never communicate: each handle's (x, y, s[, w, z]) is bit-identical to
  * ipm_init_state_mehrotra on it alone, whatever the order of the handles.  One host synchronisation however large n is. */

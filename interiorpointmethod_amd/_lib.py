@@ -35,6 +35,18 @@ FLAG_LOCKSTEP = 16              # include/ipm_hip.h: IPM_FLAG_LOCKSTEP
 FLAG_DETECT_INFEASIBILITY = 32  # include/ipm_hip.h: IPM_FLAG_DETECT_INFEASIBILITY
 FLAG_SMALL_QUADRATIC = 64       # include/ipm_hip.h: IPM_FLAG_SMALL_QUADRATIC
 FLAG_LOCKSTEP_BOUNDS = 128      # include/ipm_hip.h: IPM_FLAG_LOCKSTEP_BOUNDS
+# Flags the header states by a shift expression after IPM_FLAG_LOCKSTEP_BOUNDS.  They are attributes of this module like the ones
+# above (_lib.FLAG_SMALL_FREE; module __getattr__ below) but not names of its dict: tests/test_lockstep_bounds_host.py pins the set
+# of FLAG_* names the dict holds.
+_SHIFTED_FLAGS = {"FLAG_SMALL_FREE": FLAG_LOCKSTEP_BOUNDS << 1}          # include/ipm_hip.h: IPM_FLAG_SMALL_FREE (256)
+
+
+def __getattr__(name):
+    if name in _SHIFTED_FLAGS:
+        return _SHIFTED_FLAGS[name]
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
 ERR_WORKSPACE = -4
 ABI_VERSION = 4
 HISTORY_CAPACITY = 1024         # IPM_HISTORY_CAPACITY

@@ -48,8 +48,10 @@ def _solve_info(solver, history=False, certificate=False):
     info["refine"] = solver.refine_info()
     info["dense_cols"] = solver.dense_split_info()          # None: no dense-column split ran
     info["quadratic"] = solver.quadratic_nonzeros()         # positive entries of the quadratic term's diagonal (0: an LP)
-    # the path that served a quadratic term: "small" (the one-workgroup loop, quad_small=True) or "multi-kernel"; None for an LP
-    info["quadratic_path"] = None if not info["quadratic"] else "small" if solver.schedule()["fused_small"] else "multi-kernel"
+    # the path that served a quadratic term: "small" (the one-workgroup loop, quad_small=True), "one-workgroup" (the same loop with free
+    # columns, free_small=True: its Free variants) or "multi-kernel"; None for an LP
+    small = solver.schedule()["fused_small"]
+    info["quadratic_path"] = None if not info["quadratic"] else "multi-kernel" if not small else "one-workgroup" if solver._n_free else "small"
     info["free"] = solver._n_free                           # free columns (0: none); the count the handle keeps, no library call
     if solver.scale is not None:
         info["scale"] = dict(solver.scale_info)
@@ -87,7 +89,7 @@ def _auto_regularize():          # the process-wide switch of the 5 % rule (hand
 
 def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
                     history=False, ub=None, detect_infeasibility=False, device_start=False, scale=None, scale_passes=SCALE_PASSES,
-                    correctors=0, refine=0, dense_cols=None, quad=None, quad_small=False, free=None, **opts):
+                    correctors=0, refine=0, dense_cols=None, quad=None, quad_small=False, free=None, free_small=False, **opts):
     """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
     start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start(), or with
     device_start=True IpmSolver.init_state_mehrotra(): the same start computed on the device (no host copy of A, one
@@ -112,7 +114,9 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     IPM_FLAG_SMALL_QUADRATIC); info["quadratic_path"] says which path served the term: "small", "multi-kernel", or None for an LP.
     free: None (default), column indices or a boolean mask: the free columns (IpmSolver) -- quad > 0 there, no bound,
     no sign constraint; info["free"] = their count.  Checked on the host before any device is touched (ValueError naming the
-    column); refused (ValueError) together with detect_infeasibility, correctors > 0 and start="mehrotra"."""
+    column); refused (ValueError) together with detect_infeasibility, correctors > 0 and start="mehrotra".
+    free_small=True (off by default): a sparse problem of at most 128 rows keeps the fused small path with its term and its free
+    columns (IpmSolver, IPM_FLAG_SMALL_FREE); info["quadratic_path"] is then "one-workgroup"."""
     global _last_info
     correctors = check_correctors(correctors)
     refine = check_refine(refine)
@@ -124,6 +128,8 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
         opts = dict(opts, dense_cols=dense_cols)
     if quad_small:
         opts = dict(opts, quad_small=True)
+    if free_small:
+        opts = dict(opts, free_small=True)
     quad = check_quadratic(quad, np.asarray(c).reshape(-1).shape[0])
     if quad is not None:
         if detect_infeasibility:
@@ -173,12 +179,12 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
 
 
 def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None,
-          quad=None, quad_small=False, free=None, **opts):
+          quad=None, quad_small=False, free=None, free_small=False, **opts):
     """min c^T x (+ 1/2 x^T diag(quad) x) s.t. Ax=b, x>=0 (and x <= ub where ub is finite) by the Mehrotra predictor-corrector loop
-    on the GPU -> (x, y, s).  quad_small, free (columns without the sign constraint): as solve_with_info."""
+    on the GPU -> (x, y, s).  quad_small, free (columns without the sign constraint), free_small: as solve_with_info."""
     x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub, scale=scale,
                                  scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad,
-                                 quad_small=quad_small, free=free, **opts)
+                                 quad_small=quad_small, free=free, free_small=free_small, **opts)
     return x, y, s
 
 
@@ -192,13 +198,13 @@ def _verdict(info, value):
 
 
 def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0,
-                    dense_cols=None, quad=None, free=None):
+                    dense_cols=None, quad=None, free=None, free_small=False):
     """Drop-in for main.py:760-815: start x=s=y=1, cap 5000, returns sum(x*c) - cTlb (with quad: the quadratic objective - cTlb).  detect_infeasibility=True: +inf for an
     LP detected infeasible, -inf for one detected unbounded.  scale, correctors, refine, dense_cols: as solve_with_info (off by
-    default); free likewise (free columns of a quadratic problem)."""
+    default); free likewise (free columns of a quadratic problem), and free_small (the one-workgroup path for them)."""
     _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=5000, y0=1.0, device=device,
                                     detect_infeasibility=detect_infeasibility, scale=scale, scale_passes=scale_passes,
-                                    correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad, free=free)
+                                    correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad, free=free, free_small=free_small)
     return _verdict(info, info["objective"] - float(cTlb))
 
 

@@ -111,7 +111,8 @@ def lockstep_eligible(solver):
 def small_batch_eligible(solver):
     """Can this IpmSolver join solve_small_batch_solvers?  The library serves it with the fused single-workgroup kernel (sparse A of
     at most 128 rows whose product list fits: ipm_get_schedule out[9] == 1).  Bounds and infeasibility detection do not matter; a
-    solver with a quadratic term is on that path, and eligible, only when it was created with quad_small=True."""
+    solver with a quadratic term is on that path, and eligible, only when it was created with quad_small=True, one with free columns
+    only with free_small=True."""
     return bool(solver.schedule()["fused_small"])
 
 
@@ -119,7 +120,8 @@ def solve_small_batch_solvers(solvers, tol=1e-8, max_iter=5000, tol_gap=None, st
     """ipm_solve_small_batch: solve the LPs of `solvers` (IpmSolver objects on the fused small-LP path, one device, a state set) in ONE
     launch per kernel variant, one workgroup per LP -> list of statistics dicts, one per solver (also in solver.stats).  Plain,
     bounded and detect_infeasibility solvers may be mixed, and so may solvers that hold a quadratic term on the small path
-    (IpmSolver(..., quad=g, quad_small=True), bounded or not: the two Quad variants of the kernel).  Per-LP semantics and arithmetic are those of IpmSolver.solve on each of
+    (IpmSolver(..., quad=g, quad_small=True), bounded or not: the two Quad variants of the kernel) and solvers with free columns on
+    it (free=..., free_small=True: the two Free variants; eight variants in all).  Per-LP semantics and arithmetic are those of IpmSolver.solve on each of
     them alone (bit-identical iterates); get_state / get_bound_state / history / certificate work afterwards as after solve().  The
     solvers stay alive: set_state / init_state and another call re-solve them.  stream: a torch.cuda.Stream for the launches
     (None: the first solver's stream).  ValueError, naming the index, for a solver that is not on the small path, and for

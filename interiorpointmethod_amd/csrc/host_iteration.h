@@ -475,7 +475,12 @@ static SmallLP small_args(ipm_handle* h, int max_steps, int auto_reg) {
 }
 
 // (a quadratic term never meets detect: ipm_set_quadratic refuses the pair, so 4 | 2 does not occur)
-static int small_variant(const ipm_handle* h) { return (h->bnd ? SMALL_BOUNDED : 0) | (h->detect ? SMALL_DETECT : 0) | (h->quad ? SMALL_QUAD : 0); }
+// (free columns meet neither detect nor a handle without a term: ipm_set_free_columns and check_ready / the batch's own check refuse
+//  those, so a free_on handle here holds a term: the two Free variants, IPM_FLAG_SMALL_FREE)
+static int small_variant(const ipm_handle* h) {
+    if (h->free_on) return h->bnd ? SMALL_BOUNDED_FREE_QUAD : SMALL_FREE_QUAD;
+    return (h->bnd ? SMALL_BOUNDED : 0) | (h->detect ? SMALL_DETECT : 0) | (h->quad ? SMALL_QUAD : 0);
+}
 static SmallItem small_item(ipm_handle* h, int index, int max_steps, int auto_reg) {
     SmallItem it;
     memset(&it, 0, sizeof it);
@@ -483,6 +488,7 @@ static SmallItem small_item(ipm_handle* h, int index, int max_steps, int auto_re
     if (h->bnd) it.bd = bnd_args(h);
     it.dt = det_args(h);
     it.g = h->quad ? h->quad_g : nullptr;
+    if (h->free_on) it.fr = free_args(h);
     it.eta = h->opt.eta;
     it.variant = small_variant(h);
     it.index = index;
@@ -497,7 +503,9 @@ static void launch_small(int v, hipStream_t S, const SmallItem* one, const Small
     else if (v == SMALL_DETECT) { if (one) hipLaunchKernelGGL(small_lp_detect_kernel, g, b, 0, S, one->lp, one->dt); else hipLaunchKernelGGL(small_lp_batch_detect_kernel, g, b, 0, S, d_items); }
     else if (v == SMALL_BOUNDED_DETECT) { if (one) hipLaunchKernelGGL(small_lp_bounded_detect_kernel, g, b, 0, S, one->lp, one->bd, one->dt); else hipLaunchKernelGGL(small_lp_batch_bounded_detect_kernel, g, b, 0, S, d_items); }
     else if (v == SMALL_QUAD) { if (one) hipLaunchKernelGGL(small_qp_kernel, g, b, 0, S, one->lp, one->g); else hipLaunchKernelGGL(small_lp_batch_quad_kernel, g, b, 0, S, d_items); }
-    else { if (one) hipLaunchKernelGGL(small_qp_bounded_kernel, g, b, 0, S, one->lp, one->bd, one->g); else hipLaunchKernelGGL(small_lp_batch_bounded_quad_kernel, g, b, 0, S, d_items); }
+    else if (v == SMALL_BOUNDED_QUAD) { if (one) hipLaunchKernelGGL(small_qp_bounded_kernel, g, b, 0, S, one->lp, one->bd, one->g); else hipLaunchKernelGGL(small_lp_batch_bounded_quad_kernel, g, b, 0, S, d_items); }
+    else if (v == SMALL_FREE_QUAD) { if (one) hipLaunchKernelGGL(small_qp_free_kernel, g, b, 0, S, one->lp, one->g, one->fr); else hipLaunchKernelGGL(small_lp_batch_free_quad_kernel, g, b, 0, S, d_items); }
+    else { if (one) hipLaunchKernelGGL(small_qp_bounded_free_kernel, g, b, 0, S, one->lp, one->bd, one->g, one->fr); else hipLaunchKernelGGL(small_lp_batch_bounded_free_quad_kernel, g, b, 0, S, d_items); }
 }
 
 // whole loop of a small sparse LP in one launch of one workgroup (small_lp.h)

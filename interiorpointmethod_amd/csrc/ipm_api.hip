@@ -155,6 +155,9 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     static_assert(IPM_FLAG_LOCKSTEP_BOUNDS == 128, "the bit the Python host states (_lib.FLAG_LOCKSTEP_BOUNDS)");
     if (opts && (opts->flags & IPM_FLAG_LOCKSTEP_BOUNDS) && !(opts->flags & IPM_FLAG_LOCKSTEP))
         return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_create: IPM_FLAG_LOCKSTEP_BOUNDS without IPM_FLAG_LOCKSTEP (it opts a lockstep handle into the bounded twins, nothing else)");
+    static_assert(IPM_FLAG_SMALL_FREE == 256, "the bit the Python host states (_lib.FLAG_SMALL_FREE)");
+    if (opts && (opts->flags & IPM_FLAG_SMALL_FREE) && !(opts->flags & IPM_FLAG_SMALL_QUADRATIC))
+        return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_create: IPM_FLAG_SMALL_FREE without IPM_FLAG_SMALL_QUADRATIC (a free column needs a quadratic term, and the term reaches the fused small path only with that flag)");
     ipm_handle* h = new ipm_handle();
     h->device = device;
     if (opts) h->opt = *opts; else ipm_default_options(&h->opt);
@@ -530,7 +533,7 @@ extern "C" int ipm_set_free_columns(ipm_handle* h, const int32_t* idx, int32_t c
     }
     if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle was created with IPM_FLAG_LOCKSTEP (the Free kernels have no batched twins)");
     if (h->detect) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the tests are the LP's and are not restated)");
-    if (h->small) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle runs the fused small kernel, which has no free columns; set them before A (ipm_set_A_csc then takes the multi-kernel path)");
+    if (h->small && !(h->opt.flags & IPM_FLAG_SMALL_FREE)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle runs the fused small kernel, which has no free columns; set them before A (ipm_set_A_csc then takes the multi-kernel path)");
     std::vector<char> seen((size_t)h->n, 0);
     for (int32_t t = 0; t < count; ++t) {
         const int32_t j = idx[t];

@@ -105,6 +105,8 @@ __device__ __forceinline__ double quad_step(double ap, double ad) { return fmin(
 // Eliminating dx_j = (A^T dy + r_c)_j / g_j from row j of the Newton system, A^T dy - g dx = -r_c, puts 1/g_j on the diagonal of
 // Theta: formation, every factorization path, the sweeps, refinement and the dense-column split read only d and serve it unchanged.
 // The one step length of quad_step applies as to every quadratic handle.  A handle keeps at least one pair (n - n_free + |U| >= 1).
+// Both paths use them: the Free kernels of vector_ops.h, and the Free variants of the one-workgroup loop (small_lp.h,
+// IPM_FLAG_SMALL_FREE), whose column loops call the same helpers on the marked columns.
 struct FreeArgs {
     const unsigned char* mark;     // [np] 1 on the free columns
     int nfree;

@@ -19,7 +19,7 @@
 // as placed above, (A^T y)_j as a CSC dot product with y in LDS, the normal equations, and the reductions.  Their summation orders
 // differ from the multi-kernel path's, so iterates agree to rounding, not bit for bit (tests compare both against the reference).
 // residual_cols is the hand-kept second copy of the predictor column (iteration_rules.h): its Quad branches are kept in step with
-// prepare_kernel_body<..., Quad> of vector_ops.h.
+// prepare_kernel_body<..., Quad> of vector_ops.h, its Free branch with prepare_kernel_body<..., Quad, Free>.
 // Below the loop: Mehrotra's starting point of such an LP in one launch (small_start_body), single and batched.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -81,9 +81,13 @@ __device__ __forceinline__ void block_reduce512(double (&v)[NV], double* red) {
 // Quad = true: a diagonal quadratic term g (the handle's quad_g; IPM_FLAG_SMALL_QUADRATIC): r_c, d and the objective
 // by the quad_* rules in residual_cols, and one step length (quad_step) wherever a (primal, dual) pair is held.  Everything else
 // -- the formation from d, the factorization, both matvecs, the direction, the corrector and the stop test -- is the LP's.
-template <bool Bounded, bool Detect = false, bool Quad = false>
-__device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt = DetArgs{}, const double* g = nullptr) {
+// Free = true: free columns with curvature (FreeArgs; IPM_FLAG_SMALL_FREE): a marked column takes the free_* rules of
+// iteration_rules.h in every column loop -- d = 1 / g, q = 0, v = d r_c, ds = 0, no ratio, no term of mu_aff -- and the pair count of
+// the stop test and the centring is free_pair_count.  One more byte per column from global memory; no LDS, no reduction of its own.
+template <bool Bounded, bool Detect = false, bool Quad = false, bool Free = false>
+__device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt = DetArgs{}, const double* g = nullptr, FreeArgs fr = FreeArgs{}) {
     static_assert(!(Quad && Detect), "the infeasibility tests are not restated for a quadratic term");
+    static_assert(!Free || (Quad && !Detect), "a free column needs curvature: Free is only meaningful with Quad");
     __shared__ __attribute__((aligned(16))) double W[NB * WLD];
     __shared__ double dinv_s[NB];
     __shared__ double ys[NB], rbs[NB], t1s[NB], zs[NB], dys[NB];
@@ -131,7 +135,35 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
             double w = 0.0;
             for (int p = pb; p < pe; ++p) w += a.A.cval[p] * ys[a.A.rowind[p]];
             const double xj = a.x[j], sj = a.s[j], cj = a.c[j];
-            if constexpr (Bounded) {
+            if constexpr (Free) {
+                // the three kinds of column (free, on U, plain) choose values; the sums are updated once, straight-line, as below.
+                // A free x_j may be 0 or negative: x_j s_j / x_j is formed on the other branch only.
+                const double gj = g[j];
+                double rcj, dj, r3 = 0.0, r4 = 0.0, ru_j2 = 0.0;
+                if (free_in(fr, j)) {
+                    rcj = free_rc(w, cj, gj, xj); dj = free_theta(gj);
+                    free_rhs_column<Bounded>(a, bd, j, dj, rcj);
+                } else {
+                    r3 = xj * sj;
+                    const double qj = r3 / xj;
+                    rcj = quad_rc(w + sj - cj, gj, xj); dj = quad_theta(xj, sj, gj);
+                    double vj = dj * (rcj - qj);
+                    if constexpr (Bounded) {
+                        const double uj = bd.u[j];
+                        if (bnd_in(uj)) {
+                            const double wj = bd.w[j], zj = bd.z[j];
+                            const double ruj = xj + wj - uj;
+                            rcj = quad_rc(w + sj - zj - cj, gj, xj); dj = quad_bnd_theta(xj, sj, wj, zj, gj); r4 = wj * zj; ru_j2 = ruj * ruj;
+                            bd.qz[j] = r4 / wj;
+                            vj = dj * (rcj - qj + (r4 - zj * ruj) / wj);
+                        }
+                    }
+                    a.q[j] = qj; a.v[j] = vj;
+                }
+                a.rc[j] = rcj; a.d[j] = dj;
+                rc2 += rcj * rcj; xs += r3; cx += quad_objective(cj, gj, xj);
+                if constexpr (Bounded) { xs += r4; ru2 += ru_j2; }
+            } else if constexpr (Bounded) {
                 // one straight-line update of the four sums for both kinds of column (with a `continue` per kind the
                 // accumulators were left in scratch memory)
                 const double uj = bd.u[j];
@@ -171,7 +203,8 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
             const double rb = sqrt(rb2), rcn = sqrt(rc2);
             sc->rb_norm = rb; sc->rc_norm = rcn; sc->gap = gap; sc->obj = obj;
             if (fabs(obj) < 1.7e308) sc->obj_last_finite = obj;
-            const double nmu = Bounded ? (double)(n + bd.nU) : (double)n;
+            double nmu = Bounded ? (double)(n + bd.nU) : (double)n;
+            if constexpr (Free) nmu = free_pair_count<Bounded>(n, bd, fr);
             sc->mu = gap / nmu;
             sh[0] = gap / nmu;
             int cont_loop = 1;
@@ -225,7 +258,10 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
             double w = 0.0;
             for (int p = pb; p < pe; ++p) w += a.A.cval[p] * dys[a.A.rowind[p]];
             const double xj = a.x[j], sj = a.s[j];
-            direction_column<Bounded>(a, bd, j, w, DX, DS, DWp, DZp, xj, sj, minp, mind);
+            if constexpr (Free) {
+                if (free_in(fr, j)) free_direction_column<Bounded>(a, j, w, DX, DS, DWp, DZp);
+                else direction_column<Bounded>(a, bd, j, w, DX, DS, DWp, DZp, xj, sj, minp, mind);
+            } else direction_column<Bounded>(a, bd, j, w, DX, DS, DWp, DZp, xj, sj, minp, mind);
         }
     };
 
@@ -298,12 +334,20 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
         double aap = mn[0], aad = mn[1];
         if constexpr (Quad) aap = aad = quad_step(aap, aad);                 // one step length
         double ma[1] = {0.0};
-        for (int j = tid; j < n; j += PD_THREADS) mu_aff_column<Bounded>(a, bd, j, aap, aad, ma[0]);
+        for (int j = tid; j < n; j += PD_THREADS) {
+            if constexpr (Free) { if (!free_in(fr, j)) mu_aff_column<Bounded>(a, bd, j, aap, aad, ma[0]); }
+            else mu_aff_column<Bounded>(a, bd, j, aap, aad, ma[0]);
+        }
         block_reduce512<1, false>(ma, red);
-        const Centring ct = centring<Bounded>(ma[0], mu, n, bd);
+        const Centring ct = centring<Bounded>(ma[0], mu, Free ? n - fr.nfree : n, bd);      // (Free: free_pair_count pairs)
         const double sm = ct.sigma * mu;
         // ---------------------------------------------------------------- corrector, same factor
-        for (int j = tid; j < n; j += PD_THREADS) corrector_column<Bounded>(a, bd, j, sm);
+        for (int j = tid; j < n; j += PD_THREADS) {
+            if constexpr (Free) {
+                if (free_in(fr, j)) free_rhs_column<Bounded>(a, bd, j, a.d[j], a.rc[j]);
+                else corrector_column<Bounded>(a, bd, j, sm);
+            } else corrector_column<Bounded>(a, bd, j, sm);
+        }
         __syncthreads();
         solve_normal();
         double mc[2] = {1.0, 1.0};
@@ -314,7 +358,12 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
         const double eta = sc->eta;
         double ap = damped_step(eta, mc[0]), ad = damped_step(eta, mc[1]);
         if constexpr (Quad) ap = ad = quad_step(ap, ad);
-        for (int j = tid; j < n; j += PD_THREADS) update_column<Bounded>(a, bd, j, ap, ad);
+        for (int j = tid; j < n; j += PD_THREADS) {
+            if constexpr (Free) {
+                if (free_in(fr, j)) free_update_column(a, j, ap);
+                else update_column<Bounded>(a, bd, j, ap, ad);
+            } else update_column<Bounded>(a, bd, j, ap, ad);
+        }
         if (tid < m) ys[tid] += ad * dys[tid];
         if (tid == 0) {
             record_iteration(sc, a.hist, mu, ct.sigma, aap, aad, ap, ad);
@@ -332,29 +381,34 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_detect_kernel(SmallLP a, 
 __global__ __launch_bounds__(PD_THREADS) void small_lp_bounded_detect_kernel(SmallLP a, BndArgs bd, DetArgs dt) { small_lp_body<true, true>(a, bd, dt); }
 __global__ __launch_bounds__(PD_THREADS) void small_qp_kernel(SmallLP a, const double* g) { small_lp_body<false, false, true>(a, BndArgs{}, DetArgs{}, g); }
 __global__ __launch_bounds__(PD_THREADS) void small_qp_bounded_kernel(SmallLP a, BndArgs bd, const double* g) { small_lp_body<true, false, true>(a, bd, DetArgs{}, g); }
+__global__ __launch_bounds__(PD_THREADS) void small_qp_free_kernel(SmallLP a, const double* g, FreeArgs fr) { small_lp_body<false, false, true, true>(a, BndArgs{}, DetArgs{}, g, fr); }
+__global__ __launch_bounds__(PD_THREADS) void small_qp_bounded_free_kernel(SmallLP a, BndArgs bd, const double* g, FreeArgs fr) { small_lp_body<true, false, true, true>(a, bd, DetArgs{}, g, fr); }
 
 // ------------------------------------------------------------------------------- batch of small LPs (ipm_solve_small_batch)
 // One launch, one workgroup per LP: workgroup blockIdx.x reads item blockIdx.x of a table in device memory -- the arguments the
 // single-LP kernel gets in its kernel-argument segment -- and runs the SAME body on it.  The workgroups never talk to each other
 // (no atomics, no polling), so the dispatcher may run them in any order and in any number of rounds over the compute units; an LP's
-// arithmetic is that of its one-at-a-time launch, bit for bit.  The body keeps ~133 KB of static LDS per instantiation, so the six
-// variants stay six kernels: the host sorts the table by variant and launches one grid per variant present.
-enum { SMALL_PLAIN = 0, SMALL_BOUNDED = 1, SMALL_DETECT = 2, SMALL_BOUNDED_DETECT = 3, SMALL_QUAD = 4, SMALL_BOUNDED_QUAD = 5, SMALL_NVARIANTS = 6 };
+// arithmetic is that of its one-at-a-time launch, bit for bit.  The body keeps ~133 KB of static LDS per instantiation, so the eight
+// variants stay eight kernels: the host sorts the table by variant and launches one grid per variant present.
+enum { SMALL_PLAIN = 0, SMALL_BOUNDED = 1, SMALL_DETECT = 2, SMALL_BOUNDED_DETECT = 3, SMALL_QUAD = 4, SMALL_BOUNDED_QUAD = 5, SMALL_FREE_QUAD = 6,
+       SMALL_BOUNDED_FREE_QUAD = 7, SMALL_NVARIANTS = 8 };
 struct SmallItem {
     SmallLP lp;
     BndArgs bd;
     DetArgs dt;
     const double* g;                                     // the quadratic diagonal of a SMALL_*QUAD item (the handle's quad_g), else NULL
+    FreeArgs fr;                                         // the marks of a SMALL_*FREE_QUAD item (the handle's free_mark), else {NULL, 0}
     double eta;                                          // the handle's step damping (small_batch_params_kernel)
     int variant;                                         // SMALL_*
     int index;                                           // position of the handle in the caller's array (the gathered record goes there)
 };
 
 // the index is the workgroup's own: the loads are wave-uniform and the item ends up in scalar registers like kernel arguments do
-template <bool Bounded, bool Detect, bool Quad = false>
+template <bool Bounded, bool Detect, bool Quad = false, bool Free = false>
 __device__ __forceinline__ void small_lp_batch_body(const SmallItem* __restrict__ items) {
     const SmallItem it = items[blockIdx.x];
-    small_lp_body<Bounded, Detect, Quad>(it.lp, it.bd, it.dt, it.g);
+    if constexpr (Free) small_lp_body<Bounded, Detect, Quad, true>(it.lp, it.bd, it.dt, it.g, it.fr);
+    else small_lp_body<Bounded, Detect, Quad>(it.lp, it.bd, it.dt, it.g);
 }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, false>(items); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, false>(items); }
@@ -362,6 +416,8 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_detect_kernel(const
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, true>(items); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_quad_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, false, true>(items); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_quad_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, false, true>(items); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_batch_free_quad_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, false, true, true>(items); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_free_quad_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, false, true, true>(items); }
 
 // start_solve(force = 0, reset = 1) for every item, as set_params_kernel does for one LP: one thread per item
 __global__ __launch_bounds__(256) void small_batch_params_kernel(const SmallItem* __restrict__ items, int n, double e1, double e2, double e3, int max_iter) {

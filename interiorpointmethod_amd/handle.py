@@ -176,7 +176,7 @@ class IpmSolver:
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
                  auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
                  infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, quad=None,
-                 quad_small=False, free=None, lockstep_bounds=False):
+                 quad_small=False, free=None, lockstep_bounds=False, free_small=False):
         """check_every: solve() enqueues that many iterations at a time and reads the stop flag once per chunk (the launches behind a
         satisfied stop test return at entry, so the result does not depend on it: DESIGN.md 4-A); a lockstep batch runs chunks of the
         largest value among its members.  IPM_CHECK_EVERY in the environment, when set and not empty, OVERRIDES this argument for
@@ -211,9 +211,14 @@ class IpmSolver:
         free: None (default), a sequence of column indices or a boolean mask: the free columns (set_free, ipm_set_free_columns;
         DESIGN.md 4-U) -- columns with quad > 0 and no upper bound that carry no sign constraint, what the factor form of
         Q = diag(g) + F F^T needs (factor_qp.solve_factor_qp builds it).  Checked on the host before any device is touched
-        (check_free: ValueError naming the column) and set before A, so a small sparse problem takes the multi-kernel path.
+        (check_free: ValueError naming the column) and set before A, so a small sparse problem takes the multi-kernel path
+        (unless free_small=True, below).
         lockstep, detect_infeasibility and correctors > 0 refuse a non-empty set (ValueError); so does init_state_mehrotra
-        (IpmError).  s is 0 on a free column in every state that goes in or comes out."""
+        (IpmError).  s is 0 on a free column in every state that goes in or comes out.
+        free_small=True (IPM_FLAG_SMALL_QUADRATIC | IPM_FLAG_SMALL_FREE; off by default): a problem that qualifies for the fused
+        small path keeps it with a quadratic term AND with free columns -- a factor-model QP of m + k <= 128 rows runs its whole
+        loop in one launch of one workgroup, the solver may join solve_small_batch_solvers, and set_free is accepted after
+        construction too.  Implies what quad_small=True gives.  The flag alone changes nothing and lifts no other refusal."""
         self.scale = check_scale(scale)
         if lockstep_bounds and not lockstep:
             raise ValueError("lockstep_bounds=True needs lockstep=True: it opts a lockstep solver into the batch's bounded kernels")
@@ -267,9 +272,11 @@ class IpmSolver:
                      (0 if auto_regularize else _lib.FLAG_NO_AUTO_REGULARIZE) | \
                      (_lib.FLAG_SPARSE_FACTOR if self.factor == "sparse" else 0) | \
                      (_lib.FLAG_DETECT_INFEASIBILITY if detect_infeasibility else 0) | \
-                     (_lib.FLAG_SMALL_QUADRATIC if quad_small else 0) | \
-                     (_lib.FLAG_LOCKSTEP_BOUNDS if lockstep_bounds else 0)
+                     (_lib.FLAG_SMALL_QUADRATIC if quad_small or free_small else 0) | \
+                     (_lib.FLAG_LOCKSTEP_BOUNDS if lockstep_bounds else 0) | \
+                     (_lib.FLAG_SMALL_FREE if free_small else 0)
         self.quad_small = bool(quad_small)
+        self.free_small = bool(free_small)
         self.lockstep_bounds = bool(lockstep_bounds)
         self.detect_infeasibility = bool(detect_infeasibility)
         nbytes = C.c_size_t(0)
@@ -302,7 +309,7 @@ class IpmSolver:
                 self.close()
                 raise
         self._n_free = 0                     # the size of the set the library holds (info["free"] reads it without a library call)
-        if free is not None:                 # before A too: a handle with free columns never takes the one-workgroup small path
+        if free is not None:                 # before A too: a handle with free columns takes the one-workgroup small path only with free_small
             try:
                 self._set_free_checked(free)
             except Exception:
