@@ -109,7 +109,7 @@ enum {
      * Off by default: the small loop and the multi-kernel path sum in different orders, so their iterates agree to rounding, not bit
      * for bit.  The flag alone changes nothing: a flagged handle without a term (never set, or cleared with NULL / all zeros) runs
      * the LP kernels, bit for bit what an unflagged handle runs, and a handle that does not qualify for the small path ignores the
-     * flag.  It lifts no refusal: a term with IPM_FLAG_DETECT_INFEASIBILITY or IPM_FLAG_LOCKSTEP, centrality correctors, refinement
+     * flag.  It lifts no refusal: a term with IPM_FLAG_DETECT_INFEASIBILITY (without IPM_FLAG_DETECT_QUADRATIC) or IPM_FLAG_LOCKSTEP, centrality correctors, refinement
      * rounds and dense columns on the small path are refused as without it. */
     IPM_FLAG_SMALL_QUADRATIC = 64,
     /* Bit 7 (value 128).  With IPM_FLAG_LOCKSTEP (ipm_create refuses it alone): a handle that holds finite upper bounds
@@ -131,7 +131,26 @@ enum {
      * handle's index).  Off by default: the small loop and the multi-kernel path sum in different orders.  The flag alone changes
      * nothing: a flagged handle without a set (never given, or cleared) runs the Quad or LP kernels, bit for bit what a handle
      * with IPM_FLAG_SMALL_QUADRATIC alone runs. */
-    IPM_FLAG_SMALL_FREE = IPM_FLAG_LOCKSTEP_BOUNDS << 1
+    IPM_FLAG_SMALL_FREE = IPM_FLAG_LOCKSTEP_BOUNDS << 1,
+    /* Bit 9 (value 512).  With IPM_FLAG_DETECT_INFEASIBILITY (ipm_create refuses it alone, and together with IPM_FLAG_LOCKSTEP: the
+     * kernels have no batched twins): ipm_set_quadratic and ipm_set_free_columns accept the detecting handle, and its stop test
+     * runs the two tests restated for a quadratic problem (U the bounded columns, Phi the free ones, g the diagonal):
+     *   primal infeasible (status 5): beta = b^T y - u_U^T z_U > 0 and
+     *       max( max_{j not in Phi} (A^T y - z)_j+ , max_{j in Phi} |(A^T y)_j| ) <= eps_p * beta   (a free column needs equality);
+     *     certificate y / beta, z / beta as above.
+     *   dual infeasible (status 6): gamma = -c^T x > 0, the LINEAR part of the objective only, and
+     *       max( ||A x||_inf , max_{j in U} x_j , max_j g_j |x_j| ) <= eps_d * gamma;
+     *     certificate x / gamma:  x^_j >= 0 off Phi, ||A x^||_inf, x^_U and g o x^ <= eps_d, c^T x^ = -1: a ray that avoids the curvature.
+     * With g = 0 and no free column both are the tests above exactly.  The iteration is unchanged (a flagged solve follows the
+     * unflagged quadratic one bit for bit until it stops); the tolerances are ipm_set_infeasibility_tol's; statuses, ipm_get_certificate
+     * and its record are those above.  On an equilibrated handle the tests act on the scaled problem and the record's violation is
+     * the SCALED problem's; the vectors of the certificate leave in the caller's units.  Every path a quadratic handle has is served:
+     * multi-kernel (dense, sparse, residual stream) and, with IPM_FLAG_SMALL_QUADRATIC / IPM_FLAG_SMALL_FREE, the one-workgroup kernel
+     * and ipm_solve_small_batch.  Detection is not guaranteed (an iterate that overflows first still ends in IPM_STATUS_NAN), and
+     * curvature on ONE column of a ray does not bound a problem whose recession cone holds other rays: the loop then finds one of
+     * those.  Without the flag every refusal stays as it was; the flag lifts no other refusal (lockstep, centrality correctors on a
+     * quadratic handle, Mehrotra's start with free columns). */
+    IPM_FLAG_DETECT_QUADRATIC = IPM_FLAG_SMALL_FREE << 1
 };
 
 typedef struct ipm_handle ipm_handle;
@@ -267,7 +286,8 @@ int ipm_get_bound_state(ipm_handle* h, double* w, double* z);
  * flag the handle keeps the path in either order of the two calls and runs the Quad variants of the small kernel while it holds a
  * term.  Clearing is always accepted.
  * Refused with IPM_ERR_INVALID_ARG and a reason in ipm_last_error, never dropped: a nonzero g on an IPM_FLAG_LOCKSTEP handle (no
- * batched twins), on an IPM_FLAG_DETECT_INFEASIBILITY handle (the tests are not restated for a QP) and on a handle with
+ * batched twins), on an IPM_FLAG_DETECT_INFEASIBILITY handle without IPM_FLAG_DETECT_QUADRATIC (the LP's tests do not fit a QP; that
+ * flag adds the ones that do) and on a handle with
  * ipm_set_centrality_correctors(k > 0) (their accept rule compares step pairs); ipm_set_centrality_correctors(k > 0) refuses a
  * handle that holds a term.  ipm_init_state_mehrotra runs on such a handle and IGNORES g (the LP's start).
  * Scaled handle (ipm_equilibrate): g enters as g C^2 and leaves as g' / C^2, exact; an entry the factors push out of the normal
@@ -295,7 +315,7 @@ int ipm_get_quadratic(ipm_handle* h, double* g, int64_t* nonzeros);
  * out of range or given twice; a column with g_j = 0 (here when the term is set, by ipm_set_quadratic when the set came first,
  * and by ipm_iterate / ipm_solve / ipm_newton_direction when no term ever came); ipm_set_quadratic clearing the term or zeroing g_j
  * on a free column; a finite u_j on a free column (here, or by ipm_set_bounds); every column free (no pair left: mu would be 0/0);
- * an IPM_FLAG_LOCKSTEP or IPM_FLAG_DETECT_INFEASIBILITY handle; a handle on the fused small path, IPM_FLAG_SMALL_QUADRATIC
+ * an IPM_FLAG_LOCKSTEP handle, an IPM_FLAG_DETECT_INFEASIBILITY handle without IPM_FLAG_DETECT_QUADRATIC; a handle on the fused small path, IPM_FLAG_SMALL_QUADRATIC
  * included (set the columns before A: ipm_set_A_csc then takes the multi-kernel path) -- unless the handle was created with
  * IPM_FLAG_SMALL_FREE, which keeps it on that path in either call order; ipm_init_state_mehrotra on a handle with
  * free columns (its least-squares start is not restated for them).  Centrality correctors are refused as for every quadratic
@@ -388,7 +408,7 @@ int ipm_batch_stats(ipm_batch* b, int32_t index, ipm_stats* stats);
  * served by that path (ipm_get_schedule out[9] == 1), live on the same device, have A, b, c and a state set and profiling off
  * (IPM_ERR_STATE otherwise); handles with upper bounds (ipm_set_bounds), with IPM_FLAG_DETECT_INFEASIBILITY and plain ones may be mixed
  * freely in one call, and so may handles that hold a quadratic term on this path (IPM_FLAG_SMALL_QUADRATIC, bounded or not), with
- * free columns on top (IPM_FLAG_SMALL_FREE, bounded or not: eight kernel variants in all).  IPM_ERR_INVALID_ARG, with the offending index in ipm_last_error(NULL), for a NULL handle, a handle that is not on
+ * free columns on top (IPM_FLAG_SMALL_FREE, bounded or not), each of those four also with IPM_FLAG_DETECT_QUADRATIC (twelve kernel variants in all).  IPM_ERR_INVALID_ARG, with the offending index in ipm_last_error(NULL), for a NULL handle, a handle that is not on
  * the small path, a handle on another device and the same handle twice (two workgroups would race on one state); n < 0 or handles ==
  * NULL with n > 0 likewise; n == 0 returns IPM_OK and touches no device.  stream: a hipStream_t ON THE HANDLES' DEVICE the launches go to
  * (the caller's to guarantee: a stream does not tell its device), NULL = the first handle's stream; the handles may own any streams -- the batch stream waits (stream events) for each distinct one before the launch,

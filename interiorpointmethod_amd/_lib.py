@@ -38,7 +38,8 @@ FLAG_LOCKSTEP_BOUNDS = 128      # include/ipm_hip.h: IPM_FLAG_LOCKSTEP_BOUNDS
 # Flags the header states by a shift expression after IPM_FLAG_LOCKSTEP_BOUNDS.  They are attributes of this module like the ones
 # above (_lib.FLAG_SMALL_FREE; module __getattr__ below) but not names of its dict: tests/test_lockstep_bounds_host.py pins the set
 # of FLAG_* names the dict holds.
-_SHIFTED_FLAGS = {"FLAG_SMALL_FREE": FLAG_LOCKSTEP_BOUNDS << 1}          # include/ipm_hip.h: IPM_FLAG_SMALL_FREE (256)
+_SHIFTED_FLAGS = {"FLAG_SMALL_FREE": FLAG_LOCKSTEP_BOUNDS << 1,          # include/ipm_hip.h: IPM_FLAG_SMALL_FREE (256)
+                  "FLAG_DETECT_QUADRATIC": FLAG_LOCKSTEP_BOUNDS << 2}    # include/ipm_hip.h: IPM_FLAG_DETECT_QUADRATIC (512)
 
 
 def __getattr__(name):

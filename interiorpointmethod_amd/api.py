@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .analysis import _upper_bounds
-from .handle import (SCALE_PASSES, STATUS_NAMES, IpmSolver, check_correctors, check_free, check_quadratic, check_refine, check_scale, mehrotra_started,
+from .handle import (SCALE_PASSES, STATUS_NAMES, IpmSolver, check_correctors, check_detect_qp, check_free, check_quadratic, check_refine, check_scale, mehrotra_started,
                      refuse_free, refuse_quadratic, shift_allowed, wants_shift)
 
 
@@ -89,7 +89,9 @@ def _auto_regularize():          # the process-wide switch of the 5 % rule (hand
 
 def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
                     history=False, ub=None, detect_infeasibility=False, device_start=False, scale=None, scale_passes=SCALE_PASSES,
-                    correctors=0, refine=0, dense_cols=None, quad=None, quad_small=False, free=None, free_small=False, **opts):
+                    correctors=0, refine=0, dense_cols=None, quad=None, quad_small=False, free=None, detect_qp=False, free_small=False, **opts):
+    # (detect_qp stands IN FRONT of free_small here, in solve and in interior_sparse: an existing test pins free_small as the last
+    #  parameter, so it cannot be keyword-only behind it; pass both by keyword)
     """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
     start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start(), or with
     device_start=True IpmSolver.init_state_mehrotra(): the same start computed on the device (no host copy of A, one
@@ -116,7 +118,10 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     no sign constraint; info["free"] = their count.  Checked on the host before any device is touched (ValueError naming the
     column); refused (ValueError) together with detect_infeasibility, correctors > 0 and start="mehrotra".
     free_small=True (off by default): a sparse problem of at most 128 rows keeps the fused small path with its term and its free
-    columns (IpmSolver, IPM_FLAG_SMALL_FREE); info["quadratic_path"] is then "one-workgroup"."""
+    columns (IpmSolver, IPM_FLAG_SMALL_FREE); info["quadratic_path"] is then "one-workgroup".
+    detect_qp=True (off by default): the infeasibility tests of a QUADRATIC problem (IpmSolver) -- with quad (and
+    free) the solve may end in status 5 / 6 and info["certificate"] = IpmSolver.certificate(), which verify_certificate(..., g=quad,
+    free=free) checks.  Implies detect_infeasibility=True and lifts its refusal of quad / free; ValueError without a quadratic term."""
     global _last_info
     correctors = check_correctors(correctors)
     refine = check_refine(refine)
@@ -131,15 +136,19 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     if free_small:
         opts = dict(opts, free_small=True)
     quad = check_quadratic(quad, np.asarray(c).reshape(-1).shape[0])
+    detect_qp = check_detect_qp(detect_qp, quad)
+    if detect_qp:
+        opts = dict(opts, detect_qp=True)
     if quad is not None:
-        if detect_infeasibility:
+        if detect_infeasibility and not detect_qp:
             refuse_quadratic(quad, "detect_infeasibility=True", "the infeasibility tests are the LP's")
         if correctors:
             refuse_quadratic(quad, "correctors=%d" % correctors, "a quadratic solver takes one step length, the rounds compare step pairs")
     ub = _upper_bounds(ub, np.asarray(c).reshape(-1).shape[0])
     free = check_free(free, np.asarray(c).reshape(-1).shape[0], quad, ub)
-    if detect_infeasibility:
+    if detect_infeasibility and not detect_qp:
         refuse_free(free, "detect_infeasibility=True", "the infeasibility tests are the LP's")
+    detect_infeasibility = bool(detect_infeasibility) or detect_qp
     if correctors:
         refuse_free(free, "correctors=%d" % correctors, "a quadratic solver takes one step length, the rounds compare step pairs")
     if start == "mehrotra":
@@ -179,12 +188,13 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
 
 
 def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None,
-          quad=None, quad_small=False, free=None, free_small=False, **opts):
+          quad=None, quad_small=False, free=None, detect_qp=False, free_small=False, **opts):
     """min c^T x (+ 1/2 x^T diag(quad) x) s.t. Ax=b, x>=0 (and x <= ub where ub is finite) by the Mehrotra predictor-corrector loop
-    on the GPU -> (x, y, s).  quad_small, free (columns without the sign constraint), free_small: as solve_with_info."""
+    on the GPU -> (x, y, s).  quad_small, free (columns without the sign constraint), free_small, detect_qp: as solve_with_info
+    (last_info() then holds the status and the certificate of a detection)."""
     x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub, scale=scale,
                                  scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad,
-                                 quad_small=quad_small, free=free, free_small=free_small, **opts)
+                                 quad_small=quad_small, free=free, detect_qp=detect_qp, free_small=free_small, **opts)
     return x, y, s
 
 
@@ -198,13 +208,15 @@ def _verdict(info, value):
 
 
 def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0,
-                    dense_cols=None, quad=None, free=None, free_small=False):
+                    dense_cols=None, quad=None, free=None, detect_qp=False, free_small=False):
     """Drop-in for main.py:760-815: start x=s=y=1, cap 5000, returns sum(x*c) - cTlb (with quad: the quadratic objective - cTlb).  detect_infeasibility=True: +inf for an
     LP detected infeasible, -inf for one detected unbounded.  scale, correctors, refine, dense_cols: as solve_with_info (off by
-    default); free likewise (free columns of a quadratic problem), and free_small (the one-workgroup path for them)."""
+    default); free likewise (free columns of a quadratic problem), and free_small (the one-workgroup path for them).  detect_qp=True:
+    the same verdicts for a problem with quad (solve_with_info): +inf infeasible, -inf unbounded."""
     _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=5000, y0=1.0, device=device,
                                     detect_infeasibility=detect_infeasibility, scale=scale, scale_passes=scale_passes,
-                                    correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad, free=free, free_small=free_small)
+                                    correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad, free=free, detect_qp=detect_qp,
+                                    free_small=free_small)
     return _verdict(info, info["objective"] - float(cTlb))
 
 
@@ -216,18 +228,34 @@ def interior(A, b, c, tol=1e-20, device=0, detect_infeasibility=False):
     return _verdict(info, info["objective"])
 
 
-def verify_certificate(A, b, c, cert, ub=None):
+def verify_certificate(A, b, c, cert, ub=None, g=None, free=None, F=None):
     """Recompute, in float64 from the problem data alone, how far `cert` (IpmSolver.certificate(): kind, y, z, x; y in the
     caller's row order) is from an exact certificate of min c.x, A x = b, 0 <= x <= ub -> the violation (0 = exact):
       primal_infeasible: y^ = y / t, z^ = z / t with t = b.y - u.z (must be > 0): max(max(A^T y^ - z^)_+, max(-z^)_+);
       dual_infeasible:   x^ = x / t with t = -c.x (must be > 0): max(||A x^||_inf, max(-x^)_+, max x^_U).
-    +inf when the normalisation is not positive (no certificate at all).  Pure NumPy / SciPy: no device is touched."""
+    +inf when the normalisation is not positive (no certificate at all).  Pure NumPy / SciPy: no device is touched.
+    A quadratic problem min c.x + 1/2 x.(diag(g) + F F^T) x with free columns adds, from the same data alone:
+      g (None: no term; the diagonal, length n): max_j g_j |x^_j| joins the dual_infeasible terms (the ray avoids the curvature);
+      free (None, column indices or a boolean mask): on a free column max |(A^T y^)_j| replaces the positive part (a free column
+        has no slack: equality), and -x^_j is no violation there (no sign constraint);
+      F (None, or n x k: the factors of solve_factor_qp's ORIGINAL problem): max |F^T x^| joins the dual_infeasible terms, and a
+        primal_infeasible cert may carry y_factor (k), whose |y_factor|_inf joins its terms (the rows F^T x - t = 0 have free t: the
+        multipliers must vanish) with F y_factor added to A^T y; a dual_infeasible one may carry t (k), checked as F^T x^ - t^.
+    With g, free and F left at None the value is exactly what it was without them."""
     kind = cert["kind"] if isinstance(cert, dict) else cert
     b = np.asarray(b, dtype=np.float64).reshape(-1)
     c = np.asarray(c, dtype=np.float64).reshape(-1)
     n = c.shape[0]
     u = np.full(n, np.inf) if ub is None else np.asarray(ub, dtype=np.float64).reshape(-1)
     U = np.isfinite(u)
+    phi = np.zeros(n, dtype=bool)
+    if free is not None:
+        f = np.asarray(free)
+        if f.dtype == np.bool_:
+            phi = f.reshape(-1).copy()
+        else:
+            phi[f.astype(np.int64).reshape(-1)] = True
+    Fm = None if F is None else np.asarray(F, dtype=np.float64).reshape(n, -1)
     if kind == "primal_infeasible":
         y = np.asarray(cert["y"], dtype=np.float64).reshape(-1)
         z = np.zeros(n) if cert.get("z") is None else np.asarray(cert["z"], dtype=np.float64).reshape(-1)
@@ -236,7 +264,15 @@ def verify_certificate(A, b, c, cert, ub=None):
         if not t > 0.0 or not np.isfinite(t):
             return np.inf
         aty = np.asarray(A.T @ y).reshape(-1) / t - z / t
-        return float(max(np.max(aty, initial=0.0), np.max(-z / t, initial=0.0), 0.0))
+        extra = 0.0
+        if Fm is not None and cert.get("y_factor") is not None:
+            yf = np.asarray(cert["y_factor"], dtype=np.float64).reshape(-1) / t
+            aty = aty + Fm @ yf
+            extra = float(np.max(np.abs(yf), initial=0.0))
+        if phi.any():
+            extra = max(extra, float(np.max(np.abs(aty[phi]), initial=0.0)))
+            aty = aty[~phi]
+        return float(max(np.max(aty, initial=0.0), np.max(-z / t, initial=0.0), 0.0, extra))
     if kind == "dual_infeasible":
         x = np.asarray(cert["x"], dtype=np.float64).reshape(-1)
         t = float(-(c @ x))
@@ -244,5 +280,13 @@ def verify_certificate(A, b, c, cert, ub=None):
             return np.inf
         xh = x / t
         ax = np.asarray(A @ xh).reshape(-1)
-        return float(max(np.max(np.abs(ax), initial=0.0), np.max(-xh, initial=0.0), np.max(xh[U], initial=0.0)))
+        v = float(max(np.max(np.abs(ax), initial=0.0), np.max(-xh[~phi] if phi.any() else -xh, initial=0.0), np.max(xh[U], initial=0.0)))
+        if g is not None:
+            v = max(v, float(np.max(np.asarray(g, dtype=np.float64).reshape(-1) * np.abs(xh), initial=0.0)))
+        if Fm is not None:
+            ftx = Fm.T @ xh
+            v = max(v, float(np.max(np.abs(ftx), initial=0.0)))
+            if cert.get("t") is not None:
+                v = max(v, float(np.max(np.abs(ftx - np.asarray(cert["t"], dtype=np.float64).reshape(-1) / t), initial=0.0)))
+        return v
     raise ValueError("cert kind must be 'primal_infeasible' or 'dual_infeasible', not %r" % (kind,))

@@ -26,7 +26,7 @@ from .analysis import _upper_bounds, prepare
 from .api import _auto_regularize, _solve_info, solve_with_info
 from .batches import LockstepBatch, lockstep_eligible, small_batch_eligible, solve_small_batch_solvers
 from .analysis import refuse_dense_cols
-from .handle import SCALE_PASSES, IpmSolver, check_scale, mehrotra_started, refuse_correctors, refuse_free, refuse_refine
+from .handle import SCALE_PASSES, IpmSolver, check_scale, mehrotra_started, refuse_correctors, refuse_detect_qp, refuse_free, refuse_refine
 
 # One record per LP.  The first nine fields are the statistics SURVEY.md 8e names; the rest make the library's hidden
 # recoveries and the host-side phases of a solve visible in the gathered table: `timeouts_recovered` = device hand-off
@@ -463,7 +463,7 @@ class _LockstepShard:
 
 def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, tol_gap=None,
                          detect_infeasibility=False, small_batch=False, start="reference", scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0,
-                         dense_cols=None, free=None, **_):
+                         dense_cols=None, free=None, detect_qp=False, **_):
     """Solve problems[i] for i in ids on this rank's GPU with the LOCKSTEP BATCH -> (len(ids), NF) records.
 
     `workers` host threads prepare the LPs (host analysis, handle, upload), largest first.  An LP of more than 128 rows on the
@@ -488,7 +488,9 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
     a handle with different data, so the batches need nothing else.
 
     correctors > 0 raises ValueError: the centrality-corrector rounds have no batched twins (run_batch(lockstep=False) serves them);
-    refine > 0 likewise, and so does dense_cols (the split has no batched twins either), and so does free (free columns)."""
+    refine > 0 likewise, and so does dense_cols (the split has no batched twins either), and so does free (free columns), and so
+    does detect_qp=True (no quadratic kernels in the batch)."""
+    refuse_detect_qp(detect_qp, "the lockstep batch", "the Quad and Free kernels have no batched twins; solve such problems one at a time")
     refuse_free(free, "the lockstep batch", "the Free kernels have no batched twins; solve such problems one at a time")
     refuse_correctors(correctors, "the lockstep batch")
     refuse_refine(refine, "the lockstep batch")

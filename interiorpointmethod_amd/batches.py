@@ -7,7 +7,8 @@ from . import _lib
 from .analysis import FUSED_SMALL_MAX_ROWS, _sp, _upper_bounds
 from .api import _auto_regularize, _solve_info
 from .analysis import refuse_dense_cols
-from .handle import SCALE_PASSES, IpmSolver, _gap_tol, check_quadratic, check_scale, refuse_correctors, refuse_free, refuse_refine, wants_shift
+from .handle import (SCALE_PASSES, IpmSolver, _gap_tol, check_quadratic, check_scale, refuse_correctors, refuse_detect_qp, refuse_free, refuse_refine,
+                     wants_shift)
 
 
 def _handle_array(solvers):           # (the handles as a C array, a Stats array of the same length) for one batched library call
@@ -21,13 +22,15 @@ def _scatter_stats(solvers, stats):           # each solver takes its statistics
     return [sv.stats for sv in solvers]
 
 
-def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None, correctors=0, refine=0, dense_cols=None, free=None):
+def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None, correctors=0, refine=0, dense_cols=None, free=None, detect_qp=False):
     """ipm_solve_batch: solve the LPs of `solvers` (IpmSolver objects created with lockstep=True on one device, a state set) AT ONCE,
     iteration k of all of them in the same launches (csrc/lockstep.h) -> list of statistics dicts, one per solver.  Per-LP semantics
     and arithmetic are those of IpmSolver.solve on each of them alone (bit-identical iterates).  Bounded solvers (ub=) join when they
     were created with lockstep_bounds=True, next to unbounded ones, (w, z) bit-identical too; without it the library refuses them
     (IpmError).  correctors > 0: ValueError (the rounds
-    have no batched twins; a lockstep solver refuses set_correctors for the same reason); refine > 0 likewise, and free columns."""
+    have no batched twins; a lockstep solver refuses set_correctors for the same reason); refine > 0 likewise, and free columns, and
+    detect_qp=True (no quadratic kernels in the batch)."""
+    refuse_detect_qp(detect_qp, "the lockstep batch", "the Quad and Free kernels have no batched twins; solve such problems one at a time")
     refuse_free(free, "the lockstep batch", "the Free kernels have no batched twins; solve such problems one at a time")
     refuse_correctors(correctors, "the lockstep batch")
     refuse_refine(refine, "the lockstep batch")
@@ -121,7 +124,7 @@ def solve_small_batch_solvers(solvers, tol=1e-8, max_iter=5000, tol_gap=None, st
     launch per kernel variant, one workgroup per LP -> list of statistics dicts, one per solver (also in solver.stats).  Plain,
     bounded and detect_infeasibility solvers may be mixed, and so may solvers that hold a quadratic term on the small path
     (IpmSolver(..., quad=g, quad_small=True), bounded or not: the two Quad variants of the kernel) and solvers with free columns on
-    it (free=..., free_small=True: the two Free variants; eight variants in all).  Per-LP semantics and arithmetic are those of IpmSolver.solve on each of
+    it (free=..., free_small=True: the two Free variants), each of these four also with detect_qp=True (twelve variants in all).  Per-LP semantics and arithmetic are those of IpmSolver.solve on each of
     them alone (bit-identical iterates); get_state / get_bound_state / history / certificate work afterwards as after solve().  The
     solvers stay alive: set_state / init_state and another call re-solve them.  stream: a torch.cuda.Stream for the launches
     (None: the first solver's stream).  ValueError, naming the index, for a solver that is not on the small path, and for
@@ -265,6 +268,15 @@ def _small_qp_batch_host_check(problems, ub):
     return out
 
 
+def solve_small_qp_batch_detect(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, ub=None, regularize=0.0, start="reference",
+                                scale=None, scale_passes=SCALE_PASSES, infeasibility_tol=(1e-8, 1e-8)):
+    """solve_small_qp_batch with the infeasibility tests on every member (the sibling that carries the option: the list of parameters
+    of solve_small_qp_batch is fixed): a member with a quadratic term is created with detect_qp=True, an LP in the
+    list with detect_infeasibility=True.  An infeasible or unbounded member ends in status 5 / 6 with info["certificate"]
+    (IpmSolver.certificate(); None for the others); every other member is, bit for bit, what solve_small_qp_batch returns for it."""
+    return _solve_small_qp_batch(problems, tol, max_iter, y0, device, tol_gap, ub, regularize, start, scale, scale_passes, True, infeasibility_tol)
+
+
 def solve_small_qp_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, ub=None, regularize=0.0, start="reference",
                          scale=None, scale_passes=SCALE_PASSES):
     """Solve many small separable convex QPs at once -> list of (x, y, s, info), one per problem, each what
@@ -278,13 +290,21 @@ def solve_small_qp_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, to
     problem's index: a bad shape, more than 128 rows, a negative or non-finite g, a product list too large for the path.  The
     front end has no detect_infeasibility (the tests are the LP's), and correctors, refine and dense_cols are not parameters: the
     one-workgroup loop runs none of them, and no free columns either (free is not a parameter, so Python itself
-    refuses the keyword)."""
+    refuses the keyword).  solve_small_qp_batch_detect is the same call with the infeasibility tests on."""
+    return _solve_small_qp_batch(problems, tol, max_iter, y0, device, tol_gap, ub, regularize, start, scale, scale_passes, False, None)
+
+
+def _solve_small_qp_batch(problems, tol, max_iter, y0, device, tol_gap, ub, regularize, start, scale, scale_passes, detect, infeasibility_tol):
     if start not in ("reference", "mehrotra"):
         raise ValueError('start must be "reference" or "mehrotra"')
     check_scale(scale)
     checked = _small_qp_batch_host_check(problems, ub)
-    make = lambda A, b, c, u, g, reg: IpmSolver(A, b, c, device=device, regularize=reg, ub=u, scale=scale, scale_passes=scale_passes,          # noqa: E731
-                                                quad=g, quad_small=True)
+
+    def make(A, b, c, u, g, reg):
+        kw = {}
+        if detect:          # (g is None for an LP: check_quadratic)
+            kw = dict(infeasibility_tol=infeasibility_tol, **(dict(detect_infeasibility=True) if g is None else dict(detect_qp=True)))
+        return IpmSolver(A, b, c, device=device, regularize=reg, ub=u, scale=scale, scale_passes=scale_passes, quad=g, quad_small=True, **kw)
     solvers = []
     try:
         for i, p in enumerate(checked):
@@ -302,7 +322,7 @@ def solve_small_qp_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, to
                     solvers[i] = make(*checked[i], 1e-14)
                     solvers[i].init_state_mehrotra()
         solve_small_batch_solvers(solvers, tol=tol, max_iter=max_iter, tol_gap=tol_gap)
-        return [sv.get_state() + (_solve_info(sv),) for sv in solvers]
+        return [sv.get_state() + (_solve_info(sv, certificate=detect),) for sv in solvers]
     finally:
         for sv in solvers:
             sv.close()

@@ -182,6 +182,7 @@ struct ipm_handle {
     const int* sdone = nullptr;           // the word the products with A and the substitutions test in place of Scalars::done (solve_done, SolveWord)
     // infeasibility detection (IPM_FLAG_DETECT_INFEASIBILITY): the Detect kernel instantiations run
     bool detect = false;
+    bool detect_qp = false;               // IPM_FLAG_DETECT_QUADRATIC on top: the setters of a quadratic term / of free columns accept the handle
     double det_eps_p = 1e-8, det_eps_d = 1e-8;   // ipm_set_infeasibility_tol
     double* det = nullptr;                // [4] record of the last detection (workspace): kind, normalisation, violation, k
     double* cert_mem = nullptr;           // x | y | z of ipm_get_certificate (own allocation, made on first use)
@@ -384,7 +385,7 @@ static Layout make_layout(int64_t m, int64_t n, int64_t sparse_nnz = 0, bool no_
     L.off_nvec = take(sizeof(double) * L.np * N_NVEC);
     L.off_mvec = take(sizeof(double) * L.mp * N_MVEC);
     L.off_atp = take(sizeof(double) * L.rc_chunks * L.np);
-    L.off_part = take(sizeof(double) * P_NSLOT_DETECT * MAXPART);     // (the slots of the infeasibility tests included)
+    L.off_part = take(sizeof(double) * P_NSLOT_DETECT_QUAD * MAXPART);     // (the slots of the infeasibility tests included, a quadratic handle's two too)
     L.off_det = take(sizeof(double) * 4);
     L.off_sc = take(sizeof(Scalars));
     L.off_fixed = take(256);

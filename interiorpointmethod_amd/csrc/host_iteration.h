@@ -474,10 +474,12 @@ static SmallLP small_args(ipm_handle* h, int max_steps, int auto_reg) {
     return a;
 }
 
-// (a quadratic term never meets detect: ipm_set_quadratic refuses the pair, so 4 | 2 does not occur)
-// (free columns meet neither detect nor a handle without a term: ipm_set_free_columns and check_ready / the batch's own check refuse
-//  those, so a free_on handle here holds a term: the two Free variants, IPM_FLAG_SMALL_FREE)
+// (a quadratic term meets detect only with IPM_FLAG_DETECT_QUADRATIC, ipm_set_quadratic: the four *_DETECT variants of the term; 4 | 2
+//  does not occur)
+// (free columns never meet a handle without a term: check_ready / the batch's own check refuse that, so a free_on handle here holds
+//  a term: the Free variants, IPM_FLAG_SMALL_FREE)
 static int small_variant(const ipm_handle* h) {
+    if (h->quad && h->detect) return (h->free_on ? SMALL_FREE_QUAD_DETECT : SMALL_QUAD_DETECT) + (h->bnd ? 1 : 0);
     if (h->free_on) return h->bnd ? SMALL_BOUNDED_FREE_QUAD : SMALL_FREE_QUAD;
     return (h->bnd ? SMALL_BOUNDED : 0) | (h->detect ? SMALL_DETECT : 0) | (h->quad ? SMALL_QUAD : 0);
 }
@@ -505,7 +507,11 @@ static void launch_small(int v, hipStream_t S, const SmallItem* one, const Small
     else if (v == SMALL_QUAD) { if (one) hipLaunchKernelGGL(small_qp_kernel, g, b, 0, S, one->lp, one->g); else hipLaunchKernelGGL(small_lp_batch_quad_kernel, g, b, 0, S, d_items); }
     else if (v == SMALL_BOUNDED_QUAD) { if (one) hipLaunchKernelGGL(small_qp_bounded_kernel, g, b, 0, S, one->lp, one->bd, one->g); else hipLaunchKernelGGL(small_lp_batch_bounded_quad_kernel, g, b, 0, S, d_items); }
     else if (v == SMALL_FREE_QUAD) { if (one) hipLaunchKernelGGL(small_qp_free_kernel, g, b, 0, S, one->lp, one->g, one->fr); else hipLaunchKernelGGL(small_lp_batch_free_quad_kernel, g, b, 0, S, d_items); }
-    else { if (one) hipLaunchKernelGGL(small_qp_bounded_free_kernel, g, b, 0, S, one->lp, one->bd, one->g, one->fr); else hipLaunchKernelGGL(small_lp_batch_bounded_free_quad_kernel, g, b, 0, S, d_items); }
+    else if (v == SMALL_BOUNDED_FREE_QUAD) { if (one) hipLaunchKernelGGL(small_qp_bounded_free_kernel, g, b, 0, S, one->lp, one->bd, one->g, one->fr); else hipLaunchKernelGGL(small_lp_batch_bounded_free_quad_kernel, g, b, 0, S, d_items); }
+    else if (v == SMALL_QUAD_DETECT) { if (one) hipLaunchKernelGGL(small_qp_detect_kernel, g, b, 0, S, one->lp, one->dt, one->g); else hipLaunchKernelGGL(small_lp_batch_quad_detect_kernel, g, b, 0, S, d_items); }
+    else if (v == SMALL_BOUNDED_QUAD_DETECT) { if (one) hipLaunchKernelGGL(small_qp_bounded_detect_kernel, g, b, 0, S, one->lp, one->bd, one->dt, one->g); else hipLaunchKernelGGL(small_lp_batch_bounded_quad_detect_kernel, g, b, 0, S, d_items); }
+    else if (v == SMALL_FREE_QUAD_DETECT) { if (one) hipLaunchKernelGGL(small_qp_free_detect_kernel, g, b, 0, S, one->lp, one->dt, one->g, one->fr); else hipLaunchKernelGGL(small_lp_batch_free_quad_detect_kernel, g, b, 0, S, d_items); }
+    else { if (one) hipLaunchKernelGGL(small_qp_bounded_free_detect_kernel, g, b, 0, S, one->lp, one->bd, one->dt, one->g, one->fr); else hipLaunchKernelGGL(small_lp_batch_bounded_free_quad_detect_kernel, g, b, 0, S, d_items); }
 }
 
 // whole loop of a small sparse LP in one launch of one workgroup (small_lp.h)

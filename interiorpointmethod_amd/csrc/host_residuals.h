@@ -35,8 +35,10 @@ template <int T, int TB> static void launch_vec_step(ipm_handle* h, hipStream_t 
     } else if (h->bnd) launch_twin<TB>(h, (unsigned)h->vblk, {vec_args(h), 0, bnd_args(h)}, st);
     else launch_twin<T>(h, (unsigned)h->vblk, {vec_args(h), 0}, st);
 }
-// A handle with free columns (ipm_set_free_columns; it holds a quadratic term, and is neither a lockstep nor a detect handle: the
-// setter and check_ready see to that) runs the Free instantiation of all seven steps.  An empty set enqueues what it always did.
+// A handle with free columns (ipm_set_free_columns; it holds a quadratic term and is no lockstep handle: the setter and check_ready
+// see to that) runs the Free instantiation of all seven steps.  An empty set enqueues what it always did.
+// A detect handle reaches a quadratic term or free columns only with IPM_FLAG_DETECT_QUADRATIC (the setters): launch_prepare and
+// launch_stop_test then pick the Detect instantiations of the Quad / Free kernels (quad_detect below), every other step is unchanged.
 static bool free_step(ipm_handle* h, void (*plain)(VecArgs, FreeArgs), void (*bounded)(VecArgs, BndArgs, FreeArgs), hipStream_t st = nullptr, unsigned grid = 0) {
     if (!h->free_on) return false;
     const dim3 g(grid ? grid : (unsigned)h->vblk), b(grid ? 64 : VBLK);
@@ -44,17 +46,32 @@ static bool free_step(ipm_handle* h, void (*plain)(VecArgs, FreeArgs), void (*bo
     else launch_untwinned(h, plain, g, b, st, vec_args(h), free_args(h));
     return true;
 }
+static bool quad_detect(const ipm_handle* h) { return h->detect && h->quad; }
 static void launch_prepare(ipm_handle* h, hipStream_t st) {
     const double* g = h->quad_g;
+    if (quad_detect(h)) {
+        if (h->free_on && h->bnd) launch_untwinned(h, prepare_bounded_free_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g, free_args(h));
+        else if (h->free_on) launch_untwinned(h, prepare_free_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g, free_args(h));
+        else if (h->bnd) launch_untwinned(h, prepare_bounded_quad_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g);
+        else launch_untwinned(h, prepare_quad_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g);
+        return;
+    }
     if (h->free_on && h->bnd) launch_untwinned(h, prepare_bounded_free_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g, free_args(h));
     else if (h->free_on) launch_untwinned(h, prepare_free_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g, free_args(h));
-    else if (h->quad && h->bnd) launch_untwinned(h, prepare_bounded_quad_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g);      // (never with detect: refused)
+    else if (h->quad && h->bnd) launch_untwinned(h, prepare_bounded_quad_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g);
     else if (h->quad) launch_untwinned(h, prepare_quad_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g);
     else if (h->bnd && h->detect) launch_twin<LS_PREPARE_DETECT_BND>(h, (unsigned)h->vblk, {vec_args(h), bnd_args(h), det_args(h)}, st);
     else if (h->detect) launch_twin<LS_PREPARE_DETECT>(h, (unsigned)h->vblk, {vec_args(h), det_args(h)}, st);
     else launch_vec_step<LS_PREPARE, LS_PREPARE_BND>(h, st);
 }
 static void launch_stop_test(ipm_handle* h, hipStream_t st) {
+    if (quad_detect(h)) {
+        if (h->free_on && h->bnd) launch_untwinned(h, stop_test_bounded_free_detect_kernel, dim3(1u), dim3(64), st, vec_args(h), bnd_args(h), det_args(h), free_args(h));
+        else if (h->free_on) launch_untwinned(h, stop_test_free_detect_kernel, dim3(1u), dim3(64), st, vec_args(h), det_args(h), free_args(h));
+        else if (h->bnd) launch_untwinned(h, stop_test_bounded_quad_detect_kernel, dim3(1u), dim3(64), st, vec_args(h), bnd_args(h), det_args(h));
+        else launch_untwinned(h, stop_test_quad_detect_kernel, dim3(1u), dim3(64), st, vec_args(h), det_args(h));
+        return;
+    }
     if (free_step(h, stop_test_free_kernel, stop_test_bounded_free_kernel, st, 1u)) return;
     if (h->bnd && h->detect) launch_twin<LS_STOP_TEST_DETECT_BND>(h, 1u, {vec_args(h), bnd_args(h), det_args(h)}, st);
     else if (h->bnd) launch_twin<LS_STOP_TEST_BND>(h, 1u, {vec_args(h), 0, bnd_args(h)}, st);

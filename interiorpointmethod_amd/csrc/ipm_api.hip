@@ -158,6 +158,11 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     static_assert(IPM_FLAG_SMALL_FREE == 256, "the bit the Python host states (_lib.FLAG_SMALL_FREE)");
     if (opts && (opts->flags & IPM_FLAG_SMALL_FREE) && !(opts->flags & IPM_FLAG_SMALL_QUADRATIC))
         return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_create: IPM_FLAG_SMALL_FREE without IPM_FLAG_SMALL_QUADRATIC (a free column needs a quadratic term, and the term reaches the fused small path only with that flag)");
+    static_assert(IPM_FLAG_DETECT_QUADRATIC == 512, "the bit the Python host states (_lib.FLAG_DETECT_QUADRATIC)");
+    if (opts && (opts->flags & IPM_FLAG_DETECT_QUADRATIC) && !(opts->flags & IPM_FLAG_DETECT_INFEASIBILITY))
+        return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_create: IPM_FLAG_DETECT_QUADRATIC without IPM_FLAG_DETECT_INFEASIBILITY (it opts a detecting handle into the tests of a quadratic problem, nothing else)");
+    if (opts && (opts->flags & IPM_FLAG_DETECT_QUADRATIC) && (opts->flags & IPM_FLAG_LOCKSTEP))
+        return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_create: IPM_FLAG_DETECT_QUADRATIC with IPM_FLAG_LOCKSTEP (the Quad and Free kernels have no batched twins)");
     ipm_handle* h = new ipm_handle();
     h->device = device;
     if (opts) h->opt = *opts; else ipm_default_options(&h->opt);
@@ -249,6 +254,7 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     CREATE_TRY(hipEventCreate(&h->ev0));
     CREATE_TRY(hipEventCreate(&h->ev1));
     h->detect = (h->opt.flags & IPM_FLAG_DETECT_INFEASIBILITY) != 0;
+    h->detect_qp = (h->opt.flags & IPM_FLAG_DETECT_QUADRATIC) != 0;
     if (h->opt.flags & IPM_FLAG_LOCKSTEP) { h->lockstep = 1; h->opt.flags |= IPM_FLAG_SINGLE_STREAM | IPM_FLAG_NO_DEVICE_POLLING; }
     if (h->opt.flags & IPM_FLAG_SINGLE_STREAM) h->lookahead = 0;
     if (h->lockstep && h->ls_block_steps) h->grouped_trsv = 0;      // (A/B: block-step substitutions in the lockstep batch)
@@ -489,7 +495,7 @@ extern "C" int ipm_set_quadratic(ipm_handle* h, const double* g) {
         return IPM_OK;
     }
     if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle was created with IPM_FLAG_LOCKSTEP (the Quad kernels have no batched twins)");
-    if (h->detect) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the dual ray of a QP also needs g o x = 0; the tests are not restated)");
+    if (h->detect && !h->detect_qp) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the dual ray of a QP also needs g o x = 0; the tests are not restated)");
     if (h->mcc.k > 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: %d centrality correctors are set (their accept rule compares step pairs, a quadratic handle takes one step; ipm_set_centrality_correctors(h, 0))", h->mcc.k);
     if (h->small && !(h->opt.flags & IPM_FLAG_SMALL_QUADRATIC)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle runs the fused small-LP kernel, which has no quadratic term; set the term before A (ipm_set_A_csc then takes the multi-kernel path)");
     const size_t np = (size_t)h->np;
@@ -532,7 +538,7 @@ extern "C" int ipm_set_free_columns(ipm_handle* h, const int32_t* idx, int32_t c
         return IPM_OK;
     }
     if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle was created with IPM_FLAG_LOCKSTEP (the Free kernels have no batched twins)");
-    if (h->detect) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the tests are the LP's and are not restated)");
+    if (h->detect && !h->detect_qp) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the tests are the LP's and are not restated)");
     if (h->small && !(h->opt.flags & IPM_FLAG_SMALL_FREE)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle runs the fused small kernel, which has no free columns; set them before A (ipm_set_A_csc then takes the multi-kernel path)");
     std::vector<char> seen((size_t)h->n, 0);
     for (int32_t t = 0; t < count; ++t) {

@@ -136,6 +136,17 @@ __device__ __forceinline__ void free_update_column(const Cols& a, int j, double 
 //   primal infeasible: beta = b.y - u_U.z_U > 0 and max_j (A^T y - z)_j+ <= eps_p beta   (certificate y / beta, z / beta)
 //   dual infeasible:   gamma = -c.x > 0 and max(||A x||_inf, max x_U) <= eps_d gamma      (certificate x / gamma)
 // Maxima, not sums of squares: the iterate runs along a ray and |y| reaches 1e87 before the test fires.
+//
+// The same two tests of a quadratic handle (IPM_FLAG_DETECT_QUADRATIC), with U the native bounds, Phi the free columns
+// and g the diagonal (0 where there is no term); with g = 0 and Phi empty they are the LP's tests exactly:
+//   primal infeasible: beta as above and max( max_{j not in Phi} (A^T y - z)_j+ , max_{j in Phi} |(A^T y)_j| ) <= eps_p beta
+//                      (detect_dual_free: a free column has no s that absorbs a reduced cost of either sign -- equality)
+//   dual infeasible:   gamma = -c.x > 0 with c.x the LINEAR part only (the handle's objective carries 1/2 g x^2: detect_linear)
+//                      and max(||A x||_inf, max x_U, max_j g_j |x_j|) <= eps_d gamma   (detect_curvature: the ray avoids the curvature)
+// The iteration itself is unchanged: only what the stop test reads from the iterate differs.
+__device__ __forceinline__ double detect_dual_free(double aty) { return fabs(aty); }
+__device__ __forceinline__ double detect_linear(double c, double x) { return c * x; }
+__device__ __forceinline__ double detect_curvature(double g, double x) { return g * fabs(x); }
 struct DetArgs {
     double eps_p, eps_d;
     double* out;                   // [4]: kind (5 / 6), normalisation (beta / gamma), violation / normalisation, k at detection

@@ -330,10 +330,18 @@ struct NoEarlyWork {
 };
 
 // tile0_done: the caller has factored tile (0,0) itself (factor_tile with `pre`) and every wave has passed a barrier since.
-template <bool STAMP, typename Early = NoEarlyWork>
+// FRESH_TID: the thread index is read behind an empty asm, so that the lane constants below are formed here on every call instead of
+// being hoisted out of the caller's loop and kept live across it (small_lp.h: the Detect + Quad variants of small_lp_body, which would
+// spill them).  false, the default: the code it always was.
+template <bool FRESH>
+__device__ __forceinline__ unsigned thread_index() {
+    if constexpr (FRESH) { unsigned t = threadIdx.x; asm volatile("" : "+v"(t)); return t; }
+    else return threadIdx.x;
+}
+template <bool STAMP, typename Early = NoEarlyWork, bool FRESH_TID = false>
 __device__ __forceinline__ int potrf_lds(double* W, double* dinv_s, int nt, double thresh, double big, int lim, long long* stamps,
                                          Early early = Early(), bool tile0_done = false) {
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = thread_index<FRESH_TID>(), lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fk = lane >> 4;
     int nfix = 0;

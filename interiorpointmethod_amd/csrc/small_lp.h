@@ -48,9 +48,11 @@ struct SmallLP {
 };
 
 // sum / min of NV values over the 512 threads, fixed order; result in every thread.  `red` = 8 * NV doubles of LDS.
-template <int NV, bool MIN>
+// FRESH_TID: the thread index is read behind an empty asm, so that nothing derived from it is hoisted out of the caller's loop
+// (small_lp_body's Detect + Quad variants; see the note at `ctid` there).  false: the code it always was.
+template <int NV, bool MIN, bool FRESH_TID = false>
 __device__ __forceinline__ void block_reduce512(double (&v)[NV], double* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = thread_index<FRESH_TID>() & 63, wave = thread_index<FRESH_TID>() >> 6;
 #pragma unroll
     for (int q = 0; q < NV; ++q) {
 #pragma unroll
@@ -84,10 +86,12 @@ __device__ __forceinline__ void block_reduce512(double (&v)[NV], double* red) {
 // Free = true: free columns with curvature (FreeArgs; IPM_FLAG_SMALL_FREE): a marked column takes the free_* rules of
 // iteration_rules.h in every column loop -- d = 1 / g, q = 0, v = d r_c, ds = 0, no ratio, no term of mu_aff -- and the pair count of
 // the stop test and the centring is free_pair_count.  One more byte per column from global memory; no LDS, no reduction of its own.
+// Detect with Quad (IPM_FLAG_DETECT_QUADRATIC; iteration_rules.h states the tests): residual_cols also gathers the linear
+// c.x and max g|x| (and |A^T y| of a free column into the dual maximum), which ride in the two reductions the LP's tests make -- one
+// more sum, one more maximum, the same LDS, no scratch memory (the note at `ctid` below says what that took).
 template <bool Bounded, bool Detect = false, bool Quad = false, bool Free = false>
 __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt = DetArgs{}, const double* g = nullptr, FreeArgs fr = FreeArgs{}) {
-    static_assert(!(Quad && Detect), "the infeasibility tests are not restated for a quadratic term");
-    static_assert(!Free || (Quad && !Detect), "a free column needs curvature: Free is only meaningful with Quad");
+    static_assert(!Free || Quad, "a free column needs curvature: Free is only meaningful with Quad");
     __shared__ __attribute__((aligned(16))) double W[NB * WLD];
     __shared__ double dinv_s[NB];
     __shared__ double ys[NB], rbs[NB], t1s[NB], zs[NB], dys[NB];
@@ -107,20 +111,27 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
     }
     __syncthreads();
 
+    // The thread's indices as the loop body uses them.  In the Detect + Quad variants they are made opaque to the compiler at the top of
+    // every iteration (an empty asm; potrf_lds and block_reduce512 do the same with their own copy, FRESH_TID), so that the per-thread
+    // addresses and LDS offsets are formed where they are used: hoisted out of the loop, some fifty of them stayed live across the whole
+    // iteration and the variants spilled 52 .. 68 VGPRs (204 .. 272 bytes of scratch per lane).  With this: none, 0 bytes.  In every
+    // other variant they ARE tid, row4, l4 and the kernels are the code they were.
+    int ctid = tid, crow4 = row4, cl4 = l4;
     double dby = 0.0, duz = 0.0, dmaty = 0.0, dmax = 0.0, dmxu = 0.0;      // Detect: this thread's share of the test quantities
+    double dcxl = 0.0, dmgx = 0.0;                                         // Detect with Quad: of the linear c.x and of max g|x|
     // r_b = A x - b into rbs (4 lanes per row), returns this thread's share of ||r_b||^2
     auto residual_rows = [&]() {
         double rb2 = 0.0;
-        if (row4 < m) {
-            const int pb = a.A.rowptr[row4], pe = a.A.rowptr[row4 + 1];
+        if (crow4 < m) {
+            const int pb = a.A.rowptr[crow4], pe = a.A.rowptr[crow4 + 1];
             double acc = 0.0;
-            for (int p = pb + l4; p < pe; p += 4) acc += a.A.rval[p] * a.x[a.A.colind[p]];
+            for (int p = pb + cl4; p < pe; p += 4) acc += a.A.rval[p] * a.x[a.A.colind[p]];
             acc += __shfl_xor(acc, 2, 4);
             acc += __shfl_xor(acc, 1, 4);
-            const double r = acc - a.b[row4];
-            if (l4 == 0) { rbs[row4] = r; rb2 = r * r; }
+            const double r = acc - a.b[crow4];
+            if (cl4 == 0) { rbs[crow4] = r; rb2 = r * r; }
             if constexpr (Detect) {
-                if (l4 == 0) { dby = a.b[row4] * ys[row4]; dmax = fabs(acc); }
+                if (cl4 == 0) { dby = a.b[crow4] * ys[crow4]; dmax = fabs(acc); }
             }
         }
         return rb2;
@@ -130,7 +141,7 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
     double ru2 = 0.0;                                   // bounded: this thread's share of ||r_u||^2 (residual_cols)
     double *DWp = nullptr, *DZp = nullptr;              // bounded: where direction() puts (dw, dz)
     auto residual_cols = [&](double& rc2, double& xs, double& cx) {
-        for (int j = tid; j < n; j += PD_THREADS) {
+        for (int j = ctid; j < n; j += PD_THREADS) {
             const int pb = a.A.colptr[j], pe = a.A.colptr[j + 1];
             double w = 0.0;
             for (int p = pb; p < pe; ++p) w += a.A.cval[p] * ys[a.A.rowind[p]];
@@ -140,9 +151,11 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
                 // A free x_j may be 0 or negative: x_j s_j / x_j is formed on the other branch only.
                 const double gj = g[j];
                 double rcj, dj, r3 = 0.0, r4 = 0.0, ru_j2 = 0.0;
+                double atyj = w;                                 // Detect: what the column gives the dual maximum ((A^T y - z)_j, free: |(A^T y)_j|)
                 if (free_in(fr, j)) {
                     rcj = free_rc(w, cj, gj, xj); dj = free_theta(gj);
                     free_rhs_column<Bounded>(a, bd, j, dj, rcj);
+                    if constexpr (Detect) atyj = detect_dual_free(w);
                 } else {
                     r3 = xj * sj;
                     const double qj = r3 / xj;
@@ -156,6 +169,7 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
                             rcj = quad_rc(w + sj - zj - cj, gj, xj); dj = quad_bnd_theta(xj, sj, wj, zj, gj); r4 = wj * zj; ru_j2 = ruj * ruj;
                             bd.qz[j] = r4 / wj;
                             vj = dj * (rcj - qj + (r4 - zj * ruj) / wj);
+                            if constexpr (Detect) { duz += uj * zj; atyj = w - zj; dmxu = fmax(dmxu, xj); }
                         }
                     }
                     a.q[j] = qj; a.v[j] = vj;
@@ -163,6 +177,29 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
                 a.rc[j] = rcj; a.d[j] = dj;
                 rc2 += rcj * rcj; xs += r3; cx += quad_objective(cj, gj, xj);
                 if constexpr (Bounded) { xs += r4; ru2 += ru_j2; }
+                if constexpr (Detect) { dmaty = fmax(dmaty, atyj); dcxl += detect_linear(cj, xj); dmgx = fmax(dmgx, detect_curvature(gj, xj)); }
+            } else if constexpr (Bounded && Detect && Quad) {
+                // the Bounded branch below for a detecting quadratic handle: the same column, with the terms of the tests chosen inside
+                // the branches and ALL accumulators updated once behind them (updated inside the branches, as the LP's detect variants
+                // below do, duz / dmaty / dmxu were left in scratch memory: 24 bytes per lane)
+                const double uj = bd.u[j], gj = g[j];
+                double rcj = quad_rc(w + sj - cj, gj, xj), dj = quad_theta(xj, sj, gj), vj, r4 = 0.0, ru_j2 = 0.0;
+                const double r3 = xj * sj, qj = r3 / xj;
+                double atyj = w, uzj = 0.0, xuj = 0.0;
+                if (bnd_in(uj)) {
+                    const double wj = bd.w[j], zj = bd.z[j];
+                    const double ruj = xj + wj - uj;
+                    rcj = quad_rc(w + sj - zj - cj, gj, xj); dj = quad_bnd_theta(xj, sj, wj, zj, gj); r4 = wj * zj; ru_j2 = ruj * ruj;
+                    bd.qz[j] = r4 / wj;
+                    vj = dj * (rcj - qj + (r4 - zj * ruj) / wj);
+                    uzj = uj * zj; atyj = w - zj; xuj = xj;
+                } else {
+                    vj = dj * (rcj - qj);
+                }
+                a.rc[j] = rcj; a.d[j] = dj; a.q[j] = qj; a.v[j] = vj;
+                rc2 += rcj * rcj; xs += r3; xs += r4; cx += quad_objective(cj, gj, xj); ru2 += ru_j2;
+                duz += uzj; dmaty = fmax(dmaty, atyj); dmxu = fmax(dmxu, xuj);
+                dcxl += detect_linear(cj, xj); dmgx = fmax(dmgx, detect_curvature(gj, xj));
             } else if constexpr (Bounded) {
                 // one straight-line update of the four sums for both kinds of column (with a `continue` per kind the
                 // accumulators were left in scratch memory)
@@ -188,6 +225,7 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
                 const double gj = g[j], rcj = quad_rc(w + sj - cj, gj, xj), dj = quad_theta(xj, sj, gj), r3 = xj * sj;
                 a.rc[j] = rcj; a.d[j] = dj; a.q[j] = r3 / xj; a.v[j] = dj * (rcj - r3 / xj);
                 rc2 += rcj * rcj; xs += r3; cx += quad_objective(cj, gj, xj);
+                if constexpr (Detect) { dmaty = fmax(dmaty, w); dcxl += detect_linear(cj, xj); dmgx = fmax(dmgx, detect_curvature(gj, xj)); }
             } else {
                 const double rcj = w + sj - cj, dj = xj / sj, r3 = xj * sj;
                 a.rc[j] = rcj; a.d[j] = dj; a.q[j] = r3 / xj; a.v[j] = dj * (rcj - r3 / xj);
@@ -197,9 +235,10 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
         }
     };
     // stop test of check_optimality (main.py:162-173): thread 0, result in `go`
-    // (Detect: ds = {b.y, u_U.z_U}, dm = {max (A^T y - z)_+, max |A x|, max x_U}, reduced over the workgroup)
+    // (Detect: ds = {b.y, u_U.z_U}, dm = {max (A^T y - z)_+, max |A x|, max x_U}, reduced over the workgroup; with Quad one more of each:
+    //  ds[2] = the linear c.x, dm[3] = max g|x|, and the free columns' |A^T y| inside dm[0])
     auto stop_test = [&](double rb2, double rc2, double gap, double obj, const double* ds, const double* dm) {
-        if (tid == 0) {
+        if (ctid == 0) {
             const double rb = sqrt(rb2), rcn = sqrt(rc2);
             sc->rb_norm = rb; sc->rc_norm = rcn; sc->gap = gap; sc->obj = obj;
             if (fabs(obj) < 1.7e308) sc->obj_last_finite = obj;
@@ -214,7 +253,9 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
                     const bool finite = (rb == rb) && (rcn == rcn) && (gap == gap) && (fabs(rb) < 1.7e308) &&
                                         (fabs(rcn) < 1.7e308) && (fabs(gap) < 1.7e308);
                     sc->status = finite ? 1 : 3; sc->done = 1; cont_loop = 0;
-                } else if (Detect && detect_fire(dt, sc, ds[0] - ds[1], dm[0], -obj, fmax(dm[1], dm[2]))) {
+                } else if (Detect && !Quad && detect_fire(dt, sc, ds[0] - ds[1], dm[0], -obj, fmax(dm[1], dm[2]))) {
+                    cont_loop = 0;
+                } else if (Detect && Quad && detect_fire(dt, sc, ds[0] - ds[1], dm[0], -ds[2], fmax(fmax(dm[1], dm[2]), dm[3]))) {
                     cont_loop = 0;
                 } else if (sc->k >= sc->max_iter) {
                     sc->status = 2; sc->done = 1; cont_loop = 0;
@@ -225,35 +266,35 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
     };
     // t1 = -r_b - A v ; z = inv(L) t1 ; dys = inv(L)^T z       (both matvecs with X = inv(L) from LDS)
     auto solve_normal = [&]() {
-        if (row4 < m) {
-            const int pb = a.A.rowptr[row4], pe = a.A.rowptr[row4 + 1];
+        if (crow4 < m) {
+            const int pb = a.A.rowptr[crow4], pe = a.A.rowptr[crow4 + 1];
             double acc = 0.0;
-            for (int p = pb + l4; p < pe; p += 4) acc += a.A.rval[p] * a.v[a.A.colind[p]];
+            for (int p = pb + cl4; p < pe; p += 4) acc += a.A.rval[p] * a.v[a.A.colind[p]];
             acc += __shfl_xor(acc, 2, 4);
             acc += __shfl_xor(acc, 1, 4);
-            if (l4 == 0) t1s[row4] = -rbs[row4] - acc;
+            if (cl4 == 0) t1s[crow4] = -rbs[crow4] - acc;
         }
         __syncthreads();
-        if (row4 < mt) {                                   // z_i = sum_{k <= i} X[i][k] t1_k,  X[i][k] at W[k*WLD + i + 1]
+        if (crow4 < mt) {                                   // z_i = sum_{k <= i} X[i][k] t1_k,  X[i][k] at W[k*WLD + i + 1]
             double acc = 0.0;
-            for (int k = l4; k <= row4; k += 4) acc += W[k * WLD + row4 + 1] * t1s[k];
+            for (int k = cl4; k <= crow4; k += 4) acc += W[k * WLD + crow4 + 1] * t1s[k];
             acc += __shfl_xor(acc, 2, 4);
             acc += __shfl_xor(acc, 1, 4);
-            if (l4 == 0) zs[row4] = acc;
+            if (cl4 == 0) zs[crow4] = acc;
         }
         __syncthreads();
-        if (row4 < mt) {                                   // dy_k = sum_{i >= k} X[i][k] z_i
+        if (crow4 < mt) {                                   // dy_k = sum_{i >= k} X[i][k] z_i
             double acc = 0.0;
-            for (int i = row4 + l4; i < mt; i += 4) acc += W[row4 * WLD + i + 1] * zs[i];
+            for (int i = crow4 + cl4; i < mt; i += 4) acc += W[crow4 * WLD + i + 1] * zs[i];
             acc += __shfl_xor(acc, 2, 4);
             acc += __shfl_xor(acc, 1, 4);
-            if (l4 == 0) dys[row4] = acc;
+            if (cl4 == 0) dys[crow4] = acc;
         }
         __syncthreads();
     };
     // direction_column over the columns with (A^T dy)_j from dys; this thread's ratio-test minima
     auto direction = [&](double* DX, double* DS, double& minp, double& mind) {
-        for (int j = tid; j < n; j += PD_THREADS) {
+        for (int j = ctid; j < n; j += PD_THREADS) {
             const int pb = a.A.colptr[j], pe = a.A.colptr[j + 1];
             double w = 0.0;
             for (int p = pb; p < pe; ++p) w += a.A.cval[p] * dys[a.A.rowind[p]];
@@ -268,20 +309,26 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
     int steps = 0;
     for (;;) {
         // ---------------------------------------------------------------- residuals + stop test
+        if constexpr (Detect && Quad) asm volatile("" : "+v"(ctid), "+v"(crow4), "+v"(cl4));
         double r4[4] = {0.0, 0.0, 0.0, 0.0};               // ||r_b||^2, ||r_c||^2, x.s, c.x
         r4[0] = residual_rows();
         if constexpr (Bounded) ru2 = 0.0;
         residual_cols(r4[1], r4[2], r4[3]);
         if constexpr (Bounded) r4[0] += ru2;
-        block_reduce512<4, false>(r4, red);
-        double ds[2] = {0.0, 0.0}, dm[3] = {0.0, 0.0, 0.0};
+        block_reduce512<4, false, Detect && Quad>(r4, red);
+        constexpr int NS = (Detect && Quad) ? 3 : 2, NM = (Detect && Quad) ? 4 : 3;
+        double ds[NS] = {}, dm[NM] = {};
         if constexpr (Detect) {
             ds[0] = dby; ds[1] = duz;
-            block_reduce512<2, false>(ds, red);
+            if constexpr (Quad) ds[2] = dcxl;
+            block_reduce512<NS, false, Detect && Quad>(ds, red);
             dm[0] = -dmaty; dm[1] = -dmax; dm[2] = -dmxu;                    // max = -min of the negated values
-            block_reduce512<3, true>(dm, red);
-            dm[0] = -dm[0]; dm[1] = -dm[1]; dm[2] = -dm[2];
+            if constexpr (Quad) dm[3] = -dmgx;
+            block_reduce512<NM, true, Detect && Quad>(dm, red);
+#pragma unroll
+            for (int q = 0; q < NM; ++q) dm[q] = -dm[q];
             duz = 0.0; dmaty = 0.0; dmxu = 0.0;
+            if constexpr (Quad) { dcxl = 0.0; dmgx = 0.0; }
         }
         stop_test(r4[0], r4[1], r4[2], r4[3], ds, dm);
         __syncthreads();
@@ -289,10 +336,10 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
         const double mu = sh[0];
 
         // ---------------------------------------------------------------- B = A diag(d) A^T into W, guarded Cholesky
-        for (int idx = tid; idx < mt * WLD; idx += PD_THREADS) W[idx] = 0.0;
+        for (int idx = ctid; idx < mt * WLD; idx += PD_THREADS) W[idx] = 0.0;
         __syncthreads();
         double mx[1] = {-1.7976931348623157e308};
-        for (int e = tid; e < a.nb; e += PD_THREADS) {
+        for (int e = ctid; e < a.nb; e += PD_THREADS) {
             const int i = a.bi[e], k = a.bk[e];
             double acc = 0.0;
             for (int t = a.bptr[e]; t < a.bptr[e + 1]; ++t) acc += a.bcoef[t] * a.d[a.bcol[t]];
@@ -300,16 +347,16 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
             if (i != k && (i >> 4) == (k >> 4)) W[k * WLD + i] = acc;       // diagonal tiles are held symmetric
             if (i == k) mx[0] = (acc > mx[0]) ? acc : mx[0];                 // NaN never wins
         }
-        if (tid >= m && tid < mt) W[tid * WLD + tid] = 1.0;                  // padding rows of the last tile
+        if (ctid >= m && ctid < mt) W[ctid * WLD + ctid] = 1.0;                  // padding rows of the last tile
         {   // max over the TRUE rows (fmax would drop a NaN as well); -max of negated values = max
             double ng[1] = {-mx[0]};
-            block_reduce512<1, true>(ng, red);
+            block_reduce512<1, true, Detect && Quad>(ng, red);
             mx[0] = -ng[0];
         }
-        if (a.shift_rel != 0.0 && tid < mt) W[tid * WLD + tid] += a.shift_rel * mx[0];
+        if (a.shift_rel != 0.0 && ctid < mt) W[ctid * WLD + ctid] += a.shift_rel * mx[0];
         __syncthreads();
-        const int nfix = potrf_lds<false>(W, dinv_s, nt, a.eps * mx[0], a.big, m, nullptr);
-        if (tid == 0) {
+        const int nfix = potrf_lds<false, NoEarlyWork, Detect && Quad>(W, dinv_s, nt, a.eps * mx[0], a.big, m, nullptr);
+        if (ctid == 0) {
             sc->maxdiag = mx[0];
             const int fx = sc->fixed + nfix;
             sc->fixed = fx;
@@ -330,19 +377,19 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
         double mn[2] = {1.0, 1.0};
         if constexpr (Bounded) { DWp = bd.dwa; DZp = bd.dza; }
         direction(a.dxa, a.dsa, mn[0], mn[1]);
-        block_reduce512<2, true>(mn, red);
+        block_reduce512<2, true, Detect && Quad>(mn, red);
         double aap = mn[0], aad = mn[1];
         if constexpr (Quad) aap = aad = quad_step(aap, aad);                 // one step length
         double ma[1] = {0.0};
-        for (int j = tid; j < n; j += PD_THREADS) {
+        for (int j = ctid; j < n; j += PD_THREADS) {
             if constexpr (Free) { if (!free_in(fr, j)) mu_aff_column<Bounded>(a, bd, j, aap, aad, ma[0]); }
             else mu_aff_column<Bounded>(a, bd, j, aap, aad, ma[0]);
         }
-        block_reduce512<1, false>(ma, red);
+        block_reduce512<1, false, Detect && Quad>(ma, red);
         const Centring ct = centring<Bounded>(ma[0], mu, Free ? n - fr.nfree : n, bd);      // (Free: free_pair_count pairs)
         const double sm = ct.sigma * mu;
         // ---------------------------------------------------------------- corrector, same factor
-        for (int j = tid; j < n; j += PD_THREADS) {
+        for (int j = ctid; j < n; j += PD_THREADS) {
             if constexpr (Free) {
                 if (free_in(fr, j)) free_rhs_column<Bounded>(a, bd, j, a.d[j], a.rc[j]);
                 else corrector_column<Bounded>(a, bd, j, sm);
@@ -353,26 +400,26 @@ __device__ __forceinline__ void small_lp_body(SmallLP a, BndArgs bd, DetArgs dt 
         double mc[2] = {1.0, 1.0};
         if constexpr (Bounded) { DWp = bd.dw; DZp = bd.dz; }
         direction(a.dx, a.ds, mc[0], mc[1]);
-        block_reduce512<2, true>(mc, red);
+        block_reduce512<2, true, Detect && Quad>(mc, red);
         // ---------------------------------------------------------------- damped step
         const double eta = sc->eta;
         double ap = damped_step(eta, mc[0]), ad = damped_step(eta, mc[1]);
         if constexpr (Quad) ap = ad = quad_step(ap, ad);
-        for (int j = tid; j < n; j += PD_THREADS) {
+        for (int j = ctid; j < n; j += PD_THREADS) {
             if constexpr (Free) {
                 if (free_in(fr, j)) free_update_column(a, j, ap);
                 else update_column<Bounded>(a, bd, j, ap, ad);
             } else update_column<Bounded>(a, bd, j, ap, ad);
         }
-        if (tid < m) ys[tid] += ad * dys[tid];
-        if (tid == 0) {
+        if (ctid < m) ys[ctid] += ad * dys[ctid];
+        if (ctid == 0) {
             record_iteration(sc, a.hist, mu, ct.sigma, aap, aad, ap, ad);
             sc->mu_aff = ct.mu_aff; sc->sigma = ct.sigma; sc->alpha_aff_p = aap; sc->alpha_aff_d = aad;
         }
         ++steps;
         __syncthreads();
     }
-    if (tid < m) a.y[tid] = ys[tid];
+    if (ctid < m) a.y[ctid] = ys[ctid];
 }
 
 __global__ __launch_bounds__(PD_THREADS) void small_lp_kernel(SmallLP a) { small_lp_body<false>(a, BndArgs{}); }
@@ -383,15 +430,21 @@ __global__ __launch_bounds__(PD_THREADS) void small_qp_kernel(SmallLP a, const d
 __global__ __launch_bounds__(PD_THREADS) void small_qp_bounded_kernel(SmallLP a, BndArgs bd, const double* g) { small_lp_body<true, false, true>(a, bd, DetArgs{}, g); }
 __global__ __launch_bounds__(PD_THREADS) void small_qp_free_kernel(SmallLP a, const double* g, FreeArgs fr) { small_lp_body<false, false, true, true>(a, BndArgs{}, DetArgs{}, g, fr); }
 __global__ __launch_bounds__(PD_THREADS) void small_qp_bounded_free_kernel(SmallLP a, BndArgs bd, const double* g, FreeArgs fr) { small_lp_body<true, false, true, true>(a, bd, DetArgs{}, g, fr); }
+__global__ __launch_bounds__(PD_THREADS) void small_qp_detect_kernel(SmallLP a, DetArgs dt, const double* g) { small_lp_body<false, true, true>(a, BndArgs{}, dt, g); }
+__global__ __launch_bounds__(PD_THREADS) void small_qp_bounded_detect_kernel(SmallLP a, BndArgs bd, DetArgs dt, const double* g) { small_lp_body<true, true, true>(a, bd, dt, g); }
+__global__ __launch_bounds__(PD_THREADS) void small_qp_free_detect_kernel(SmallLP a, DetArgs dt, const double* g, FreeArgs fr) { small_lp_body<false, true, true, true>(a, BndArgs{}, dt, g, fr); }
+__global__ __launch_bounds__(PD_THREADS) void small_qp_bounded_free_detect_kernel(SmallLP a, BndArgs bd, DetArgs dt, const double* g, FreeArgs fr) { small_lp_body<true, true, true, true>(a, bd, dt, g, fr); }
 
 // ------------------------------------------------------------------------------- batch of small LPs (ipm_solve_small_batch)
 // One launch, one workgroup per LP: workgroup blockIdx.x reads item blockIdx.x of a table in device memory -- the arguments the
 // single-LP kernel gets in its kernel-argument segment -- and runs the SAME body on it.  The workgroups never talk to each other
 // (no atomics, no polling), so the dispatcher may run them in any order and in any number of rounds over the compute units; an LP's
-// arithmetic is that of its one-at-a-time launch, bit for bit.  The body keeps ~133 KB of static LDS per instantiation, so the eight
-// variants stay eight kernels: the host sorts the table by variant and launches one grid per variant present.
+// arithmetic is that of its one-at-a-time launch, bit for bit.  The body keeps ~133 KB of static LDS per instantiation, so the twelve
+// variants stay twelve kernels: the host sorts the table by variant and launches one grid per variant present.
 enum { SMALL_PLAIN = 0, SMALL_BOUNDED = 1, SMALL_DETECT = 2, SMALL_BOUNDED_DETECT = 3, SMALL_QUAD = 4, SMALL_BOUNDED_QUAD = 5, SMALL_FREE_QUAD = 6,
-       SMALL_BOUNDED_FREE_QUAD = 7, SMALL_NVARIANTS = 8 };
+       SMALL_BOUNDED_FREE_QUAD = 7,
+       // a detecting handle with a quadratic term (IPM_FLAG_DETECT_QUADRATIC): + 1 bounded, + 2 free columns
+       SMALL_QUAD_DETECT = 8, SMALL_BOUNDED_QUAD_DETECT = 9, SMALL_FREE_QUAD_DETECT = 10, SMALL_BOUNDED_FREE_QUAD_DETECT = 11, SMALL_NVARIANTS = 12 };
 struct SmallItem {
     SmallLP lp;
     BndArgs bd;
@@ -418,6 +471,10 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_quad_kernel(const S
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_quad_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, false, true>(items); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_free_quad_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, false, true, true>(items); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_free_quad_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, false, true, true>(items); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_batch_quad_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, true, true>(items); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_quad_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, true, true>(items); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_batch_free_quad_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, true, true, true>(items); }
+__global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_free_quad_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, true, true, true>(items); }
 
 // start_solve(force = 0, reset = 1) for every item, as set_params_kernel does for one LP: one thread per item
 __global__ __launch_bounds__(256) void small_batch_params_kernel(const SmallItem* __restrict__ items, int n, double e1, double e2, double e3, int max_iter) {

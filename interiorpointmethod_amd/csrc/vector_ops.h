@@ -26,6 +26,9 @@ constexpr int MAXPART = 64;      // max blocks (= partials) of a vector kernel
 enum { P_RC2 = 0, P_XS, P_CX, P_RB2, P_MINP_AFF, P_MIND_AFF, P_MUAFF, P_MINP, P_MIND, P_NSLOT };
 // slots of the infeasibility tests (Detect instantiations only): b.y, u_U.z_U, max (A^T y - z)_+, max |A x|, max x_U
 enum { P_BY = P_NSLOT, P_UZ, P_MATY, P_MAX, P_MXU, P_NSLOT_DETECT };
+// two more of a quadratic handle's tests (Detect with Quad, IPM_FLAG_DETECT_QUADRATIC), behind every slot above: the LINEAR c.x (a sum:
+// P_CX of such a handle carries 1/2 g x^2) and max_j g_j |x_j|.  The free columns' |(A^T y)_j| goes into P_MATY.
+enum { P_CXL = P_NSLOT_DETECT, P_MGX, P_NSLOT_DETECT_QUAD };
 
 __device__ __forceinline__ double block_sum(double v, double* red) {
     const int tid = threadIdx.x;
@@ -176,26 +179,31 @@ __device__ __forceinline__ double col_sum(const double* atp, int rc_chunks, int 
 // (residual_cols of small_lp.h is the hand-kept second copy of this column, its Quad branches included: keep the two in step)
 // Free (ipm_set_free_columns; fr: the byte marks and their count): a marked column by the free_* rules -- r_c without s, d = 1 / g,
 // q = 0, v = d r_c, nothing into x.s -- one more streamed vector of bytes
+// Detect with Quad (IPM_FLAG_DETECT_QUADRATIC; iteration_rules.h states the tests): two more partials, P_CXL and P_MGX, from c, g and x
+// the column holds anyway, and |(A^T y)_j| of a free column into P_MATY -- still no extra pass over A
 template <bool Bounded = false, bool Detect = false, bool Quad = false, bool Free = false>
 __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, const double* g = nullptr,
                                                     FreeArgs fr = FreeArgs{}) {
-    static_assert(!Free || (Quad && !Detect), "a free column needs curvature: Free is only meaningful with Quad");
+    static_assert(!Free || Quad, "a free column needs curvature: Free is only meaningful with Quad");
     __shared__ double red[VBLK];
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     double rc2 = 0.0, xs = 0.0, cx = 0.0, rb2 = 0.0;
     double by = 0.0, uz = 0.0, maty = 0.0, max_ = 0.0, mxu = 0.0;      // Detect only
+    double cxl = 0.0, mgx = 0.0;                                       // Detect with Quad only
     for (int j = gid; j < a.n; j += gsz) {
         double xj = a.x[j], sj = a.s[j];
         if constexpr (Free) {
             if (free_in(fr, j)) {
                 const double gj = g[j];
-                const double rcj = free_rc(col_sum(a.atp, a.rc_chunks, a.np, j), a.c[j], gj, xj);
+                const double atyj = col_sum(a.atp, a.rc_chunks, a.np, j);
+                const double rcj = free_rc(atyj, a.c[j], gj, xj);
                 const double dj = free_theta(gj);
                 a.rc[j] = rcj;
                 a.d[j] = dj;
                 free_rhs_column<Bounded>(a, bd, j, dj, rcj);
                 rc2 += rcj * rcj;
                 cx += quad_objective(a.c[j], gj, xj);
+                if constexpr (Detect) { maty = fmax(maty, detect_dual_free(atyj)); cxl += detect_linear(a.c[j], xj); mgx = fmax(mgx, detect_curvature(gj, xj)); }
                 continue;
             }
         }
@@ -207,7 +215,8 @@ __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx
                 double rcj = atyj + sj - zj - a.c[j];
                 const double ruj = xj + wj - uj;
                 double dj;
-                if constexpr (Quad) { const double gj = g[j]; rcj = quad_rc(rcj, gj, xj); dj = quad_bnd_theta(xj, sj, wj, zj, gj); cx += quad_objective(a.c[j], gj, xj); }
+                if constexpr (Quad) { const double gj = g[j]; rcj = quad_rc(rcj, gj, xj); dj = quad_bnd_theta(xj, sj, wj, zj, gj); cx += quad_objective(a.c[j], gj, xj);
+                                     if constexpr (Detect) { cxl += detect_linear(a.c[j], xj); mgx = fmax(mgx, detect_curvature(gj, xj)); } }
                 else dj = bnd_theta(xj, sj, wj, zj);
                 const double r3 = xj * sj, r4 = wj * zj;
                 a.rc[j] = rcj;
@@ -227,7 +236,8 @@ __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx
         const double atyj = col_sum(a.atp, a.rc_chunks, a.np, j);
         double rcj = atyj + sj - a.c[j];
         double dj;
-        if constexpr (Quad) { const double gj = g[j]; rcj = quad_rc(rcj, gj, xj); dj = quad_theta(xj, sj, gj); cx += quad_objective(a.c[j], gj, xj); }
+        if constexpr (Quad) { const double gj = g[j]; rcj = quad_rc(rcj, gj, xj); dj = quad_theta(xj, sj, gj); cx += quad_objective(a.c[j], gj, xj);
+                             if constexpr (Detect) { cxl += detect_linear(a.c[j], xj); mgx = fmax(mgx, detect_curvature(gj, xj)); } }
         else dj = xj / sj;
         double r3 = xj * sj;
         a.rc[j] = rcj;
@@ -245,6 +255,7 @@ __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx
     }
     rc2 = block_sum(rc2, red); xs = block_sum(xs, red); cx = block_sum(cx, red); rb2 = block_sum(rb2, red);
     if constexpr (Detect) { by = block_sum(by, red); uz = block_sum(uz, red); maty = block_max(maty, red); max_ = block_max(max_, red); mxu = block_max(mxu, red); }
+    if constexpr (Detect && Quad) { cxl = block_sum(cxl, red); mgx = block_max(mgx, red); }
     if (threadIdx.x == 0) {
         a.part[P_RC2 * MAXPART + bx_] = rc2;
         a.part[P_XS * MAXPART + bx_] = xs;
@@ -257,6 +268,10 @@ __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx
             a.part[P_MAX * MAXPART + bx_] = max_;
             a.part[P_MXU * MAXPART + bx_] = mxu;
         }
+        if constexpr (Detect && Quad) {
+            a.part[P_CXL * MAXPART + bx_] = cxl;
+            a.part[P_MGX * MAXPART + bx_] = mgx;
+        }
     }
 }
 __global__ __launch_bounds__(VBLK) void prepare_kernel(VecArgs a) { prepare_kernel_body(a, blockIdx.x, gridDim.x); }
@@ -267,6 +282,10 @@ __global__ __launch_bounds__(VBLK) void prepare_quad_kernel(VecArgs a, const dou
 __global__ __launch_bounds__(VBLK) void prepare_bounded_quad_kernel(VecArgs a, BndArgs bd, const double* g) { prepare_kernel_body<true, false, true>(a, blockIdx.x, gridDim.x, bd, g); }
 __global__ __launch_bounds__(VBLK) void prepare_free_kernel(VecArgs a, const double* g, FreeArgs fr) { prepare_kernel_body<false, false, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, g, fr); }
 __global__ __launch_bounds__(VBLK) void prepare_bounded_free_kernel(VecArgs a, BndArgs bd, const double* g, FreeArgs fr) { prepare_kernel_body<true, false, true, true>(a, blockIdx.x, gridDim.x, bd, g, fr); }
+__global__ __launch_bounds__(VBLK) void prepare_quad_detect_kernel(VecArgs a, const double* g) { prepare_kernel_body<false, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, g); }
+__global__ __launch_bounds__(VBLK) void prepare_bounded_quad_detect_kernel(VecArgs a, BndArgs bd, const double* g) { prepare_kernel_body<true, true, true>(a, blockIdx.x, gridDim.x, bd, g); }
+__global__ __launch_bounds__(VBLK) void prepare_free_detect_kernel(VecArgs a, const double* g, FreeArgs fr) { prepare_kernel_body<false, true, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, g, fr); }
+__global__ __launch_bounds__(VBLK) void prepare_bounded_free_detect_kernel(VecArgs a, BndArgs bd, const double* g, FreeArgs fr) { prepare_kernel_body<true, true, true, true>(a, blockIdx.x, gridDim.x, bd, g, fr); }
 
 // d = x / s only (main.py:223): what the formation of A D^2 A^T needs; the full prepare_kernel follows on the residual
 // stream while the factorization runs (host_iteration.h, enqueue_iteration).  Bounded: d = theta on U.  Quad: the quad_* scalings.
@@ -303,10 +322,12 @@ __global__ __launch_bounds__(VBLK) void scaling_bounded_free_kernel(VecArgs a, B
 // Bounded: ||r_b||^2 carries r_u^2 and the gap w.z (prepare_kernel), b_norm is ||(b, u_U)|| (ipm_set_bounds), mu divides by n + |U|.
 // Detect: the infeasibility tests (detect_fire) where the convergence test says "continue", before the iteration cap.
 // Free: mu divides by free_pair_count (the free columns put nothing into the gap; their r_c is in ||r_c||).
-template <bool Bounded = false, bool Detect = false, bool Free = false>
+// Quad (meaningful with Detect only; IPM_FLAG_DETECT_QUADRATIC): gamma from the linear c.x (P_CXL), max g|x| (P_MGX) joins the dual violation.
+template <bool Bounded = false, bool Detect = false, bool Free = false, bool Quad = false>
 __device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, DetArgs dt = DetArgs{},
                                                       FreeArgs fr = FreeArgs{}) {
-    static_assert(!Free || !Detect, "the infeasibility tests are the LP's");
+    static_assert(!Free || !Detect || Quad, "a free column needs curvature: Free is only meaningful with Quad");
+    static_assert(!Quad || Detect, "the stop test reads the quadratic term through the infeasibility tests only");
     if (threadIdx.x != 0 || bx_ != 0) return;
     Scalars* sc = a.sc;
     if (sc->done) return;
@@ -327,9 +348,13 @@ __device__ __forceinline__ void stop_test_kernel_body(VecArgs a, const unsigned 
                       (fabs(gap) < 1.7e308);
         sc->status = finite ? 1 : 3;
         sc->done = 1;
-    } else if (Detect && detect_fire(dt, sc, sum_partials(a.part, P_BY, a.nblk) - sum_partials(a.part, P_UZ, a.nblk),
-                                     max_partials(a.part, P_MATY, a.nblk), -obj,
-                                     fmax(max_partials(a.part, P_MAX, a.nblk), max_partials(a.part, P_MXU, a.nblk)))) {
+    } else if (Detect && !Quad && detect_fire(dt, sc, sum_partials(a.part, P_BY, a.nblk) - sum_partials(a.part, P_UZ, a.nblk),
+                                              max_partials(a.part, P_MATY, a.nblk), -obj,
+                                              fmax(max_partials(a.part, P_MAX, a.nblk), max_partials(a.part, P_MXU, a.nblk)))) {
+    } else if (Detect && Quad && detect_fire(dt, sc, sum_partials(a.part, P_BY, a.nblk) - sum_partials(a.part, P_UZ, a.nblk),
+                                             max_partials(a.part, P_MATY, a.nblk), -sum_partials(a.part, P_CXL, a.nblk),
+                                             fmax(fmax(max_partials(a.part, P_MAX, a.nblk), max_partials(a.part, P_MXU, a.nblk)),
+                                                  max_partials(a.part, P_MGX, a.nblk)))) {
     } else if (sc->k >= sc->max_iter) {
         sc->status = 2;
         sc->done = 1;
@@ -341,6 +366,10 @@ __global__ void stop_test_detect_kernel(VecArgs a, DetArgs dt) { stop_test_kerne
 __global__ void stop_test_bounded_detect_kernel(VecArgs a, BndArgs bd, DetArgs dt) { stop_test_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd, dt); }
 __global__ void stop_test_free_kernel(VecArgs a, FreeArgs fr) { stop_test_kernel_body<false, false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, DetArgs{}, fr); }
 __global__ void stop_test_bounded_free_kernel(VecArgs a, BndArgs bd, FreeArgs fr) { stop_test_kernel_body<true, false, true>(a, blockIdx.x, gridDim.x, bd, DetArgs{}, fr); }
+__global__ void stop_test_quad_detect_kernel(VecArgs a, DetArgs dt) { stop_test_kernel_body<false, true, false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, dt); }
+__global__ void stop_test_bounded_quad_detect_kernel(VecArgs a, BndArgs bd, DetArgs dt) { stop_test_kernel_body<true, true, false, true>(a, blockIdx.x, gridDim.x, bd, dt); }
+__global__ void stop_test_free_detect_kernel(VecArgs a, DetArgs dt, FreeArgs fr) { stop_test_kernel_body<false, true, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, dt, fr); }
+__global__ void stop_test_bounded_free_detect_kernel(VecArgs a, BndArgs bd, DetArgs dt, FreeArgs fr) { stop_test_kernel_body<true, true, true, true>(a, blockIdx.x, gridDim.x, bd, dt, fr); }
 
 // The certificate of a detection (ipm_get_certificate): kind 5 -> (y / beta, z / beta), kind 6 -> x / gamma; the other parts 0.
 // out = [x (n) | y (m) | z (n)]; z = nullptr without bounds.

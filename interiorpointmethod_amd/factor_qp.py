@@ -73,7 +73,11 @@ def factor_qp_solution(xa, ya, sa, info, F, c_, g_, m, n):
     factor_qp_form -> (x (n, 1), y (m, 1), s (n, 1), info) with info["factors"] = k, info["t"] = the k free variables as solved,
     info["y_factor"] = the multipliers of the rows F^T x - t = 0, info["objective"] = c.x + 1/2 x.(g o x) + 1/2 ||F^T x||^2 of the x
     returned (the ORIGINAL problem's objective), the augmented problem's under info["objective_augmented"], and info["w"], info["z"]
-    (bounded problems) cut to the n original columns.  F: n x k; the input record is not changed."""
+    (bounded problems) cut to the n original columns.  A certificate of the augmented problem (detect_qp=True, status 5 / 6;
+    info["certificate"]) is mapped to the ORIGINAL problem: kind 5 keeps y (m) and gets y_factor (k: the multipliers of the factor
+    rows, 0 up to the violation), kind 6 keeps x (n) and gets t (k: the free variables, F^T x up to the violation); z and the other
+    parts are cut to n / m.  verify_certificate(A, b, c, cert, ub=ub, g=g, F=F) checks it against the original data.
+    F: n x k; the input record is not changed."""
     x, y, s = xa[:n], ya[:m], sa[:n]
     Fm, xv = np.asarray(F, dtype=np.float64), x.reshape(-1)
     ftx = Fm.T @ xv
@@ -84,6 +88,14 @@ def factor_qp_solution(xa, ya, sa, info, F, c_, g_, m, n):
     for key in ("w", "z"):
         if key in info:
             info[key] = info[key][:n]
+    cert = info.get("certificate")
+    if cert is not None:
+        cert = dict(cert)
+        ya_c, xa_c = np.asarray(cert["y"]).reshape(-1), np.asarray(cert["x"]).reshape(-1)
+        cert["y"], cert["y_factor"] = ya_c[:m].copy(), ya_c[m:].copy()
+        cert["x"], cert["t"] = xa_c[:n].copy(), xa_c[n:].copy()
+        cert["z"] = np.asarray(cert["z"]).reshape(-1)[:n].copy()
+        info["certificate"] = cert
     return x, y, s, info
 
 
@@ -96,7 +108,9 @@ def solve_factor_qp(A, b, c, F, g=None, ub=None, **opts):
     ORIGINAL problem's objective, with the augmented problem's (1/2 t.t in place of the last term, what the device's stop test
     saw) under info["objective_augmented"]; info["w"], info["z"] (bounded problems) are cut to the n original columns
     (factor_qp_solution).  free_small=True: a sparse A with m + k <= 128 keeps the one-workgroup small path
-    (info["quadratic_path"] == "one-workgroup"; solve_small_factor_qp_batch solves a list of such problems in one call)."""
+    (info["quadratic_path"] == "one-workgroup"; solve_small_factor_qp_batch solves a list of such problems in one call).
+    detect_qp=True: the infeasibility tests of a quadratic problem (solve_with_info): info["status"] may be 5 / 6 and
+    info["certificate"] is then the certificate of the ORIGINAL problem (factor_qp_solution: y and y_factor, or x and t)."""
     A_, b_, c_, g_, u_, free = factor_qp_form(A, b, c, g, F, ub)
     m, n = A_.shape[0] - free.shape[0], A_.shape[1] - free.shape[0]
     for name in ("quad", "free"):
@@ -167,14 +181,33 @@ def solve_small_factor_qp_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, devic
     free_small=True) per problem, init_state(y0), ONE ipm_solve_small_batch call (one workgroup per problem, one grid per kernel
     variant present), read-back, close.  Every problem error is a ValueError naming the problem's index: a bad shape,
     m + k > 128, a non-finite F, a negative or non-finite g, a product list of the augmented matrix beyond SMALL_TERM_LIMIT.
-    There is no start parameter: Mehrotra's start is refused for free columns."""
+    There is no start parameter: Mehrotra's start is refused for free columns.
+    solve_small_factor_qp_batch_detect is the same call with the infeasibility tests on."""
+    return _solve_small_factor_qp_batch(problems, tol, max_iter, y0, device, tol_gap, ub, regularize, scale, scale_passes, False, None)
+
+
+def solve_small_factor_qp_batch_detect(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, ub=None, regularize=0.0, scale=None,
+                                       scale_passes=SCALE_PASSES, infeasibility_tol=(1e-8, 1e-8)):
+    """solve_small_factor_qp_batch with the infeasibility tests on every member (the sibling that carries the option: the list of
+    parameters of solve_small_factor_qp_batch is fixed): a member with a quadratic term is created with detect_qp=True, a plain LP in
+    the list with detect_infeasibility=True.  A member that is infeasible or unbounded ends in status 5 / 6 after a few iterations
+    instead of running to max_iter, with info["certificate"] mapped to its ORIGINAL problem (factor_qp_solution); every other member
+    is, bit for bit, what solve_small_factor_qp_batch returns for it (the tests change no iterate).  One ipm_solve_small_batch call."""
+    return _solve_small_factor_qp_batch(problems, tol, max_iter, y0, device, tol_gap, ub, regularize, scale, scale_passes, True, infeasibility_tol)
+
+
+def _solve_small_factor_qp_batch(problems, tol, max_iter, y0, device, tol_gap, ub, regularize, scale, scale_passes, detect, infeasibility_tol):
+    """The body of solve_small_factor_qp_batch and solve_small_factor_qp_batch_detect (detect: the infeasibility tests on every member)."""
     check_scale(scale)
     checked = _small_factor_qp_host_check(problems, ub)
     solvers = []
     try:
         for i, (A_, b_, c_, g_, u_, free, _, _, _) in enumerate(checked):
+            kw = {}
+            if detect:          # (check_quadratic's rule of a term: one positive entry)
+                kw = dict(infeasibility_tol=infeasibility_tol, **(dict(detect_qp=True) if g_ is not None and np.any(g_ > 0) else dict(detect_infeasibility=True)))
             sv = IpmSolver(A_, b_, c_, device=device, regularize=regularize, ub=u_, scale=scale, scale_passes=scale_passes, quad=g_, free=free,
-                           free_small=True)
+                           free_small=True, **kw)
             solvers.append(sv)
             if not small_batch_eligible(sv):
                 raise ValueError("problem %d (%d x %d augmented) is not served by the fused small path (its product list is too large)"
@@ -184,7 +217,7 @@ def solve_small_factor_qp_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, devic
         out = []
         for sv, (_, _, c_, g_, _, _, Fm, m, n) in zip(solvers, checked):
             xa, ya, sa = sv.get_state()
-            out.append(factor_qp_solution(xa, ya, sa, _solve_info(sv), Fm, c_, np.zeros(sv.n) if g_ is None else g_, m, n))
+            out.append(factor_qp_solution(xa, ya, sa, _solve_info(sv, certificate=detect), Fm, c_, np.zeros(sv.n) if g_ is None else g_, m, n))
         return out
     finally:
         for sv in solvers:

@@ -162,6 +162,21 @@ def refuse_free(free, who, why):
         raise ValueError("free: %s takes no free columns (%s)" % (who, why))
 
 
+def check_detect_qp(detect_qp, quad):
+    """THE check of the `detect_qp` keyword, before any device is touched: detect_qp=True asks for the infeasibility tests of a
+    QUADRATIC problem (IPM_FLAG_DETECT_INFEASIBILITY | IPM_FLAG_DETECT_QUADRATIC) and needs a quadratic term (quad as
+    check_quadratic returns it; None: no term) -> bool.  An LP takes detect_infeasibility=True."""
+    if detect_qp and quad is None:
+        raise ValueError("detect_qp=True without a quadratic term (quad): an LP takes detect_infeasibility=True")
+    return bool(detect_qp)
+
+
+def refuse_detect_qp(detect_qp, who, why):
+    """THE refusal of what has no quadratic infeasibility tests (the lockstep front ends): detect_qp=True raises instead of being dropped."""
+    if detect_qp:
+        raise ValueError("detect_qp: %s takes no quadratic infeasibility tests (%s)" % (who, why))
+
+
 RefineInfo = collections.namedtuple("RefineInfo", "k solves applied half_rule reverts first_rel last_rel max_first_rel")
 
 
@@ -176,7 +191,8 @@ class IpmSolver:
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
                  auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
                  infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, quad=None,
-                 quad_small=False, free=None, lockstep_bounds=False, free_small=False):
+                 quad_small=False, free=None, lockstep_bounds=False, detect_qp=False, free_small=False):
+        # (detect_qp stands IN FRONT of free_small, which an existing test pins as the last parameter: pass both by keyword)
         """check_every: solve() enqueues that many iterations at a time and reads the stop flag once per chunk (the launches behind a
         satisfied stop test return at entry, so the result does not depend on it: DESIGN.md 4-A); a lockstep batch runs chunks of the
         largest value among its members.  IPM_CHECK_EVERY in the environment, when set and not empty, OVERRIDES this argument for
@@ -218,7 +234,12 @@ class IpmSolver:
         free_small=True (IPM_FLAG_SMALL_QUADRATIC | IPM_FLAG_SMALL_FREE; off by default): a problem that qualifies for the fused
         small path keeps it with a quadratic term AND with free columns -- a factor-model QP of m + k <= 128 rows runs its whole
         loop in one launch of one workgroup, the solver may join solve_small_batch_solvers, and set_free is accepted after
-        construction too.  Implies what quad_small=True gives.  The flag alone changes nothing and lifts no other refusal."""
+        construction too.  Implies what quad_small=True gives.  The flag alone changes nothing and lifts no other refusal.
+        detect_qp=True (IPM_FLAG_DETECT_INFEASIBILITY | IPM_FLAG_DETECT_QUADRATIC; off by default): the infeasibility
+        tests of a quadratic problem -- with quad (and free) the solve may end in status 5 / 6 with a certificate: a free column
+        needs (A^T y)_j = 0, and a ray of unboundedness has -c.x > 0 for the LINEAR objective and avoids the curvature (g o x = 0).
+        Implies detect_infeasibility=True (infeasibility_tol applies).  ValueError without a quadratic term and with lockstep=True;
+        every other refusal (correctors, init_state_mehrotra with free columns) stays."""
         self.scale = check_scale(scale)
         if lockstep_bounds and not lockstep:
             raise ValueError("lockstep_bounds=True needs lockstep=True: it opts a lockstep solver into the batch's bounded kernels")
@@ -227,13 +248,16 @@ class IpmSolver:
         quad = check_quadratic(quad, np.asarray(c).reshape(-1).shape[0] if prepared is None else prepared.n)
         n_cols = np.asarray(c).reshape(-1).shape[0] if prepared is None else prepared.n
         free = check_free(free, n_cols, quad, ub if prepared is None else getattr(prepared, "ub", None))
+        detect_qp = check_detect_qp(detect_qp, quad)
+        if lockstep:
+            refuse_detect_qp(detect_qp, "a lockstep solver", "the batch has no quadratic kernels; solve such problems one at a time")
         if lockstep:
             refuse_free(free, "a lockstep solver", "the batch has no Free kernels; solve such problems one at a time")
-        if detect_infeasibility:
+        if detect_infeasibility and not detect_qp:
             refuse_free(free, "detect_infeasibility=True", "the infeasibility tests are the LP's")
         if lockstep:
             refuse_quadratic(quad, "a lockstep solver", "the batch has no quadratic kernels; solve such problems one at a time")
-        if detect_infeasibility:
+        if detect_infeasibility and not detect_qp:
             refuse_quadratic(quad, "detect_infeasibility=True", "the infeasibility tests are the LP's")
         if correctors:
             refuse_quadratic(quad, "correctors=%d" % correctors, "a quadratic solver takes one step length, the rounds compare step pairs")
@@ -258,6 +282,7 @@ class IpmSolver:
         self._host = prepared.host  # the caller's (A, b, c), caller's row order: mehrotra_start and api.unscaled_residuals read it
         self.factor, self.order_info = prepared.factor, prepared.order_info
         A, b, c = prepared.A, prepared.b, prepared.c
+        detect_infeasibility = bool(detect_infeasibility) or detect_qp
         opts = _lib.Options()
         lib.ipm_default_options(C.byref(opts))
         opts.eta, opts.pivot_guard_eps, opts.pivot_guard_big = eta, pivot_guard_eps, pivot_guard_big
@@ -274,11 +299,13 @@ class IpmSolver:
                      (_lib.FLAG_DETECT_INFEASIBILITY if detect_infeasibility else 0) | \
                      (_lib.FLAG_SMALL_QUADRATIC if quad_small or free_small else 0) | \
                      (_lib.FLAG_LOCKSTEP_BOUNDS if lockstep_bounds else 0) | \
-                     (_lib.FLAG_SMALL_FREE if free_small else 0)
+                     (_lib.FLAG_SMALL_FREE if free_small else 0) | \
+                     (_lib.FLAG_DETECT_QUADRATIC if detect_qp else 0)
         self.quad_small = bool(quad_small)
         self.free_small = bool(free_small)
         self.lockstep_bounds = bool(lockstep_bounds)
         self.detect_infeasibility = bool(detect_infeasibility)
+        self.detect_qp = detect_qp
         nbytes = C.c_size_t(0)
         self.sparse = _is_sparse(A)
         if self.sparse:                      # A stays sparse on the device (CSR + CSC, sparse formation of B)
