@@ -611,6 +611,19 @@ int ipm_debug_at_pieces(int32_t nblk, int32_t layout[4], int32_t* pieces, int32_
 #define IPM_CHOL_STEP_WORDS 15
 int ipm_debug_chol_plan(int32_t nblk, int64_t m, const int32_t knobs[6], const int32_t* env_last, int32_t totals[5], int32_t* steps,
                         int32_t capacity);
+/* Host only: the kernel that serves a problem class at a step, read from the library's variant tables (csrc/vector_ops.h,
+ * csrc/small_lp.h; the class: bounded = ipm_set_bounds, detect = IPM_FLAG_DETECT_INFEASIBILITY, quad = ipm_set_quadratic, free_cols =
+ * ipm_set_free_columns).  name_out (capacity bytes) receives the row's name: the kernel, or for a step that has a lockstep twin at
+ * that class the twin's type (LS_*), whose id goes to *twin_type_out (-1: no twin).  For the IPM_STEP_SMALL* steps *twin_type_out is
+ * the row's id instead: the variant (SMALL_*) or, for the two start steps, 0 plain / 1 bounded.  IPM_ERR_INVALID_ARG for free columns
+ * without a quadratic term, which is no class. */
+enum {
+    IPM_STEP_PREPARE = 0, IPM_STEP_STOP_TEST, IPM_STEP_SCALING, IPM_STEP_DIRECTION, IPM_STEP_MU_AFF, IPM_STEP_CORRECTOR_RHS, IPM_STEP_UPDATE,
+    IPM_STEP_SMALL, IPM_STEP_SMALL_BATCH, IPM_STEP_SMALL_START, IPM_STEP_SMALL_START_BATCH,
+    IPM_STEP_START_PRIMAL, IPM_STEP_START_DUAL, IPM_STEP_START_SHIFT, IPM_STEP_START_PRIMAL_CORRECT, IPM_STEP_START_DUAL_CORRECT, IPM_STEP_COUNT
+};
+int ipm_debug_step_kernel(int32_t step, int32_t bounded, int32_t detect, int32_t quad, int32_t free_cols, char* name_out, int32_t capacity,
+                          int32_t* twin_type_out);
 int ipm_debug_ff_schedule(int32_t nblk, int32_t q, int32_t workers, unsigned char* items, int32_t capacity, int32_t* count,
                           int32_t* tile_items, double sim_us[2]);
 int ipm_get_phase_ms(ipm_handle* h, double out[4]);

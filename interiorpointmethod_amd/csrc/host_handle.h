@@ -477,3 +477,29 @@ static RefViews ref_views(const ipm_handle* h) {
 }
 
 static DetArgs det_args(const ipm_handle* h) { return DetArgs{h->det_eps_p, h->det_eps_d, h->det}; }
+
+// ------------------------------------------------------------------------------- the handle's problem class and its arguments
+// The ONE place that reads the four class switches of a handle in order to choose a kernel (vector_ops.h: StepVariant and the
+// variant tables; the legality rule free => quad is variant_legal, which check_ready and the small batch's own check enforce before
+// a launch).  Every other reader of these fields keeps data in step with them: the setters, equilibration, the roll-back copies
+// of (w, z), the refusals.
+static StepVariant step_variant(const ipm_handle* h) { return StepVariant{h->bnd, h->detect, h->quad, h->free_on}; }
+// ... and the guard in front of every table look-up (the iteration's and the small path's entries call it before their first launch):
+// a handle whose class is not legal has no row, and an entry point that forgot check_ready gets an error, not a null row.
+static int check_class(ipm_handle* h, const char* who) {
+    return variant_legal(variant_bits(step_variant(h))) ? IPM_OK : fail(h, IPM_ERR_STATE, "%s: free columns without a quadratic term: no kernel serves that class", who);
+}
+
+// A handle at a step, as a source of kernel arguments (vector_ops.h: Pick): each argument group by its type, int = the step's corr.
+struct StepSrc { ipm_handle* h; int corr; };
+template <> struct Pick<VecArgs, StepSrc> { static VecArgs of(const StepSrc& s) { return vec_args(s.h); } };
+template <> struct Pick<BndArgs, StepSrc> { static BndArgs of(const StepSrc& s) { return bnd_args(s.h); } };
+template <> struct Pick<DetArgs, StepSrc> { static DetArgs of(const StepSrc& s) { return det_args(s.h); } };
+template <> struct Pick<const double*, StepSrc> { static const double* of(const StepSrc& s) { return s.h->quad_g; } };
+template <> struct Pick<FreeArgs, StepSrc> { static FreeArgs of(const StepSrc& s) { return free_args(s.h); } };
+template <> struct Pick<int, StepSrc> { static int of(const StepSrc& s) { return s.corr; } };
+// ... and the argument structs of the vector steps' lockstep twins (lockstep.h)
+inline LsVecA::LsVecA(ipm_handle* h, int corr_) : a(vec_args(h)), corr(corr_) {}
+inline LsVecDet::LsVecDet(ipm_handle* h, int) : a(vec_args(h)), dt(det_args(h)) {}
+inline LsVecBnd::LsVecBnd(ipm_handle* h, int corr_) : a(vec_args(h)), corr(corr_), bd(bnd_args(h)) {}
+inline LsVecBndDet::LsVecBndDet(ipm_handle* h, int) : a(vec_args(h)), bd(bnd_args(h)), dt(det_args(h)) {}

@@ -197,6 +197,7 @@ static const int EV_PER_IT = 9;
 
 static int enqueue_iteration(ipm_handle* h, hipEvent_t* ev) {
     int rc;
+    if ((rc = check_class(h, "enqueue_iteration"))) return rc;
     const bool all = ev && h->profiling >= 2;            // each event record costs the stream ~6 us: level 1 keeps two
     if (overlap_residuals(h)) {
         // d = x/s -> formation -> factorization, with the residuals, the stop test and the predictor rhs on the residual
@@ -474,15 +475,10 @@ static SmallLP small_args(ipm_handle* h, int max_steps, int auto_reg) {
     return a;
 }
 
-// (a quadratic term meets detect only with IPM_FLAG_DETECT_QUADRATIC, ipm_set_quadratic: the four *_DETECT variants of the term; 4 | 2
-//  does not occur)
-// (free columns never meet a handle without a term: check_ready / the batch's own check refuse that, so a free_on handle here holds
-//  a term: the Free variants, IPM_FLAG_SMALL_FREE)
-static int small_variant(const ipm_handle* h) {
-    if (h->quad && h->detect) return (h->free_on ? SMALL_FREE_QUAD_DETECT : SMALL_QUAD_DETECT) + (h->bnd ? 1 : 0);
-    if (h->free_on) return h->bnd ? SMALL_BOUNDED_FREE_QUAD : SMALL_FREE_QUAD;
-    return (h->bnd ? SMALL_BOUNDED : 0) | (h->detect ? SMALL_DETECT : 0) | (h->quad ? SMALL_QUAD : 0);
-}
+// The SMALL_* id of the handle's class: the row of the variant table (small_lp.h: SMALL_ROWS) whose switches are the handle's.
+// (A quadratic term meets detect only with IPM_FLAG_DETECT_QUADRATIC, and free columns never meet a handle without a term:
+//  check_ready / the batch's own check refuse that, so every handle that gets here has a row.)
+static int small_variant(const ipm_handle* h) { return small_row_of(SMALL_ROWS, variant_bits(step_variant(h))); }
 static SmallItem small_item(ipm_handle* h, int index, int max_steps, int auto_reg) {
     SmallItem it;
     memset(&it, 0, sizeof it);
@@ -496,39 +492,21 @@ static SmallItem small_item(ipm_handle* h, int index, int max_steps, int auto_re
     it.index = index;
     return it;
 }
-// The variant -> kernel table of the fused small-LP path, once: `one` (a host item) launches the single-LP kernel of variant v on
-// it, otherwise the batch kernel of variant v runs `grid` workgroups on the device table d_items.
-static void launch_small(int v, hipStream_t S, const SmallItem* one, const SmallItem* d_items, unsigned grid) {
-    const dim3 g(one ? 1u : grid), b(PD_THREADS);
-    if (v == SMALL_PLAIN) { if (one) hipLaunchKernelGGL(small_lp_kernel, g, b, 0, S, one->lp); else hipLaunchKernelGGL(small_lp_batch_kernel, g, b, 0, S, d_items); }
-    else if (v == SMALL_BOUNDED) { if (one) hipLaunchKernelGGL(small_lp_bounded_kernel, g, b, 0, S, one->lp, one->bd); else hipLaunchKernelGGL(small_lp_batch_bounded_kernel, g, b, 0, S, d_items); }
-    else if (v == SMALL_DETECT) { if (one) hipLaunchKernelGGL(small_lp_detect_kernel, g, b, 0, S, one->lp, one->dt); else hipLaunchKernelGGL(small_lp_batch_detect_kernel, g, b, 0, S, d_items); }
-    else if (v == SMALL_BOUNDED_DETECT) { if (one) hipLaunchKernelGGL(small_lp_bounded_detect_kernel, g, b, 0, S, one->lp, one->bd, one->dt); else hipLaunchKernelGGL(small_lp_batch_bounded_detect_kernel, g, b, 0, S, d_items); }
-    else if (v == SMALL_QUAD) { if (one) hipLaunchKernelGGL(small_qp_kernel, g, b, 0, S, one->lp, one->g); else hipLaunchKernelGGL(small_lp_batch_quad_kernel, g, b, 0, S, d_items); }
-    else if (v == SMALL_BOUNDED_QUAD) { if (one) hipLaunchKernelGGL(small_qp_bounded_kernel, g, b, 0, S, one->lp, one->bd, one->g); else hipLaunchKernelGGL(small_lp_batch_bounded_quad_kernel, g, b, 0, S, d_items); }
-    else if (v == SMALL_FREE_QUAD) { if (one) hipLaunchKernelGGL(small_qp_free_kernel, g, b, 0, S, one->lp, one->g, one->fr); else hipLaunchKernelGGL(small_lp_batch_free_quad_kernel, g, b, 0, S, d_items); }
-    else if (v == SMALL_BOUNDED_FREE_QUAD) { if (one) hipLaunchKernelGGL(small_qp_bounded_free_kernel, g, b, 0, S, one->lp, one->bd, one->g, one->fr); else hipLaunchKernelGGL(small_lp_batch_bounded_free_quad_kernel, g, b, 0, S, d_items); }
-    else if (v == SMALL_QUAD_DETECT) { if (one) hipLaunchKernelGGL(small_qp_detect_kernel, g, b, 0, S, one->lp, one->dt, one->g); else hipLaunchKernelGGL(small_lp_batch_quad_detect_kernel, g, b, 0, S, d_items); }
-    else if (v == SMALL_BOUNDED_QUAD_DETECT) { if (one) hipLaunchKernelGGL(small_qp_bounded_detect_kernel, g, b, 0, S, one->lp, one->bd, one->dt, one->g); else hipLaunchKernelGGL(small_lp_batch_bounded_quad_detect_kernel, g, b, 0, S, d_items); }
-    else if (v == SMALL_FREE_QUAD_DETECT) { if (one) hipLaunchKernelGGL(small_qp_free_detect_kernel, g, b, 0, S, one->lp, one->dt, one->g, one->fr); else hipLaunchKernelGGL(small_lp_batch_free_quad_detect_kernel, g, b, 0, S, d_items); }
-    else { if (one) hipLaunchKernelGGL(small_qp_bounded_free_detect_kernel, g, b, 0, S, one->lp, one->bd, one->dt, one->g, one->fr); else hipLaunchKernelGGL(small_lp_batch_bounded_free_quad_detect_kernel, g, b, 0, S, d_items); }
+// A row of a variant table of the fused small-LP path (small_lp.h: SMALL_ROWS by SMALL_* id, SMALL_START_ROWS by bounded): `one`
+// (a host item) launches the row's single-LP kernel on it, its arguments bound by type; otherwise the row's batch kernel runs
+// `grid` workgroups on the device table d_items.
+static void launch_small(const SmallRow& row, hipStream_t S, const SmallItem* one, const SmallItem* d_items, unsigned grid) {
+    if (one) row.one(S, *one);
+    else hipLaunchKernelGGL(row.batch, dim3(grid), dim3(PD_THREADS), 0, S, d_items);
 }
 
 // whole loop of a small sparse LP in one launch of one workgroup (small_lp.h)
 static int enqueue_small(ipm_handle* h, int max_steps, int auto_reg) {
+    if (int rc_ = check_class(h, "enqueue_small")) return rc_;
     const SmallItem it = small_item(h, 0, max_steps, auto_reg);
-    launch_small(it.variant, h->stream, &it, nullptr, 1);
+    launch_small(SMALL_ROWS[it.variant], h->stream, &it, nullptr, 1);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
-}
-
-// The kernels of Mehrotra's start on the fused small-LP path (small_lp.h, small_start_body): the single-LP kernel on a host item, or
-// `grid` workgroups of the batch kernel on the device table d_items.  The start has two variants only (the tests of a Detect handle
-// play no part in it).
-static void launch_small_start(bool bounded, hipStream_t S, const SmallItem* one, const SmallItem* d_items, unsigned grid) {
-    const dim3 g(one ? 1u : grid), b(PD_THREADS);
-    if (!bounded) { if (one) hipLaunchKernelGGL(small_start_kernel, g, b, 0, S, one->lp); else hipLaunchKernelGGL(small_start_batch_kernel, g, b, 0, S, d_items); }
-    else { if (one) hipLaunchKernelGGL(small_start_bounded_kernel, g, b, 0, S, one->lp, one->bd); else hipLaunchKernelGGL(small_start_batch_bounded_kernel, g, b, 0, S, d_items); }
 }
 
 // Mehrotra's starting point of a multi-kernel handle, enqueued on the handle's stream (ipm_init_state_mehrotra):
@@ -543,28 +521,14 @@ static int enqueue_mehrotra_start(ipm_handle* h) {
     if ((rc = enqueue_form(h, h->d))) return rc;
     if ((rc = enqueue_factor(h))) return rc;
     if ((rc = enqueue_group_inverses(h))) return rc;
-    const VecArgs va = vec_args(h);
-    const dim3 g(h->vblk), b(VBLK);
     // x = A^T (A A^T)^-1 b   (the padding rows of b are zero, and stay zero through the solve)
     HIP_TRY(h, hipMemcpyAsync(h->t1, h->b, sizeof(double) * h->mp, hipMemcpyDeviceToDevice, h->stream));
     if ((rc = enqueue_normal_solve(h, h->t1, h->dy, h->atp, /*refine=*/false))) return rc;
-    if (h->bnd) hipLaunchKernelGGL(start_primal_bounded_kernel, g, b, 0, h->stream, va, bnd_args(h));
-    else hipLaunchKernelGGL(start_primal_kernel, g, b, 0, h->stream, va);
+    launch_step(STEP_START_PRIMAL, h);
     // y = (A A^T)^-1 (A c), s = c - A^T y
     launch_gemv_n(h, h->c, 1.0, 0.0, nullptr, h->t1);
     if ((rc = enqueue_normal_solve(h, h->t1, h->dy, h->atp, /*refine=*/false))) return rc;
-    if (h->bnd) {
-        const BndArgs bd = bnd_args(h);
-        hipLaunchKernelGGL(start_dual_bounded_kernel, g, b, 0, h->stream, va, bd);
-        hipLaunchKernelGGL(start_shift_bounded_kernel, g, b, 0, h->stream, va, bd);
-        hipLaunchKernelGGL(start_primal_correct_bounded_kernel, g, b, 0, h->stream, va, bd);
-        hipLaunchKernelGGL(start_dual_correct_bounded_kernel, g, b, 0, h->stream, va, bd);
-    } else {
-        hipLaunchKernelGGL(start_dual_kernel, g, b, 0, h->stream, va);
-        hipLaunchKernelGGL(start_shift_kernel, g, b, 0, h->stream, va);
-        hipLaunchKernelGGL(start_primal_correct_kernel, g, b, 0, h->stream, va);
-        hipLaunchKernelGGL(start_dual_correct_kernel, g, b, 0, h->stream, va);
-    }
+    for (const StepTable* t : {&STEP_START_DUAL, &STEP_START_SHIFT, &STEP_START_PRIMAL_CORRECT, &STEP_START_DUAL_CORRECT}) launch_step(*t, h);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
@@ -586,7 +550,7 @@ extern "C" int ipm_init_state_mehrotra(ipm_handle* h, int32_t* pivots_fixed) {
         hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, h->stream, h->sc, 1e-8, 1e-8, 1e-8, h->opt.eta, 1 << 30, 1, 1);
         if (h->small) {
             const SmallItem it = small_item(h, 0, 0, 0);
-            launch_small_start(h->bnd, h->stream, &it, nullptr, 1);
+            launch_small(SMALL_START_ROWS[step_variant(h).bounded], h->stream, &it, nullptr, 1);
             HIP_TRY(h, hipGetLastError());
         } else if ((rc = enqueue_mehrotra_start(h))) return rc;
         bool tmo = false;

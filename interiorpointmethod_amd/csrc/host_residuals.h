@@ -1,5 +1,6 @@
-// host_residuals.h -- host side, unit 3: the products with A and the residual / stop-test launches.  Ahead of the factorization
-// units because the factorization enqueues them on the residual stream under its chain-bound tail.
+// host_residuals.h -- host side, unit 3: the products with A, the launch tables of the vector steps (one per step, expanded from the
+// variant lists next to the kernels: a launch is a look-up by the handle's class) and the residual / stop-test launches.  Ahead of
+// the factorization units because the factorization enqueues them on the residual stream under its chain-bound tail.
 #pragma once
 static void launch_gemv_n(ipm_handle* h, const double* v, double sa, double sb, const double* add, double* out,
                           hipStream_t st = nullptr) {
@@ -22,79 +23,70 @@ static void launch_gemv_t_rows(ipm_handle* h, const double* u, int chunk0, int c
                        h->A + r0 * h->np, h->np, h->rows_per_chunk, (int)h->np, u + r0, h->atp + (int64_t)chunk0 * h->np, &h->sc->done);
 }
 
-// The vector steps of the iteration, ONE launch function each: it holds the step's fork between the plain kernel, the detect
-// kernel and their bounded forms.  All four have lockstep twins (T: the plain type, TB: its bounded twin, whose `single` is the
-// *_bounded_kernel -- outside a recording a bounded handle enqueues what it always did; whether one may be recorded is ls_eligible's).
-// A handle with a quadratic term (ipm_set_quadratic) runs the Quad instantiation of the four steps that have one (quad, quad_bounded:
-// no twins -- a lockstep handle is refused the term); every other step is the LP's.
-template <int T, int TB> static void launch_vec_step(ipm_handle* h, hipStream_t st = nullptr,
-                                                     void (*quad)(VecArgs) = nullptr, void (*quad_bounded)(VecArgs, BndArgs) = nullptr) {
-    if (h->quad && quad) {
-        if (h->bnd) launch_untwinned(h, quad_bounded, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h));
-        else launch_untwinned(h, quad, dim3(h->vblk), dim3(VBLK), st, vec_args(h));
-    } else if (h->bnd) launch_twin<TB>(h, (unsigned)h->vblk, {vec_args(h), 0, bnd_args(h)}, st);
-    else launch_twin<T>(h, (unsigned)h->vblk, {vec_args(h), 0}, st);
+// The vector steps of the iteration: one TABLE per step, expanded here from the list below the step's kernels (vector_ops.h:
+// X_VARIANTS, X_FLAGS), and one look-up per launch.  A row is a lockstep twin type -- launched or recorded by launch_twin<T>, its
+// argument struct built from (h, corr) -- or a kernel without a twin, its arguments bound by type (StepSrc): through launch_untwinned,
+// which cuts a recording, or launched directly where the step is never recorded (scaling, the start).  No kernel and no argument
+// list of a class variant is named in the host units; a new variant is one row per step it changes.
+struct StepRow {
+    unsigned serves;                       // the set of classes (bits masked with the step's flags) the row serves
+    const char* name;                      // the kernel, or the twin type
+    int twin;                              // LsType / LsBndType of a twin row, else -1
+    void (*launch)(ipm_handle* h, int corr, unsigned grid, unsigned threads, hipStream_t st);
+};
+template <int T> static void row_twin(ipm_handle* h, int corr, unsigned grid, unsigned, hipStream_t st) { launch_twin<T>(h, grid, LsArgs<T>(h, corr), st); }
+template <class... P> static void launch_untwinned_bound(ipm_handle* h, void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t st, const StepSrc& s) {
+    launch_untwinned(h, kernel, grid, block, st, Pick<P, StepSrc>::of(s)...);
 }
-// A handle with free columns (ipm_set_free_columns; it holds a quadratic term and is no lockstep handle: the setter and check_ready
-// see to that) runs the Free instantiation of all seven steps.  An empty set enqueues what it always did.
-// A detect handle reaches a quadratic term or free columns only with IPM_FLAG_DETECT_QUADRATIC (the setters): launch_prepare and
-// launch_stop_test then pick the Detect instantiations of the Quad / Free kernels (quad_detect below), every other step is unchanged.
-static bool free_step(ipm_handle* h, void (*plain)(VecArgs, FreeArgs), void (*bounded)(VecArgs, BndArgs, FreeArgs), hipStream_t st = nullptr, unsigned grid = 0) {
-    if (!h->free_on) return false;
-    const dim3 g(grid ? grid : (unsigned)h->vblk), b(grid ? 64 : VBLK);
-    if (h->bnd) launch_untwinned(h, bounded, g, b, st, vec_args(h), bnd_args(h), free_args(h));
-    else launch_untwinned(h, plain, g, b, st, vec_args(h), free_args(h));
+template <auto K> static void row_untwinned(ipm_handle* h, int corr, unsigned grid, unsigned threads, hipStream_t st) { launch_untwinned_bound(h, K, dim3(grid), dim3(threads), st, StepSrc{h, corr}); }
+template <auto K> static void row_direct(ipm_handle* h, int corr, unsigned grid, unsigned threads, hipStream_t st) { launch_bound(K, dim3(grid), dim3(threads), st ? st : h->stream, StepSrc{h, corr}); }
+struct StepTable { const StepRow* rows; int n; unsigned flags; };
+// the row that serves a class (null: none -- only for a class that is not legal)
+constexpr const StepRow* step_row(const StepTable& t, unsigned bits) {
+    for (int i = 0; i < t.n; ++i) if (t.rows[i].serves & V_AT(bits & t.flags)) return &t.rows[i];
+    return nullptr;
+}
+constexpr bool step_table_ok(const StepTable& t) {          // every legal class is served by exactly one row
+    for (unsigned c = 0; c <= V_ALL; ++c) {
+        int n = 0;
+        for (int i = 0; i < t.n; ++i) n += (t.rows[i].serves >> (c & t.flags)) & 1u;
+        if (variant_legal(c) && n != 1) return false;
+    }
     return true;
 }
-static bool quad_detect(const ipm_handle* h) { return h->detect && h->quad; }
-static void launch_prepare(ipm_handle* h, hipStream_t st) {
-    const double* g = h->quad_g;
-    if (quad_detect(h)) {
-        if (h->free_on && h->bnd) launch_untwinned(h, prepare_bounded_free_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g, free_args(h));
-        else if (h->free_on) launch_untwinned(h, prepare_free_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g, free_args(h));
-        else if (h->bnd) launch_untwinned(h, prepare_bounded_quad_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g);
-        else launch_untwinned(h, prepare_quad_detect_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g);
-        return;
-    }
-    if (h->free_on && h->bnd) launch_untwinned(h, prepare_bounded_free_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g, free_args(h));
-    else if (h->free_on) launch_untwinned(h, prepare_free_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g, free_args(h));
-    else if (h->quad && h->bnd) launch_untwinned(h, prepare_bounded_quad_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), bnd_args(h), g);
-    else if (h->quad) launch_untwinned(h, prepare_quad_kernel, dim3(h->vblk), dim3(VBLK), st, vec_args(h), g);
-    else if (h->bnd && h->detect) launch_twin<LS_PREPARE_DETECT_BND>(h, (unsigned)h->vblk, {vec_args(h), bnd_args(h), det_args(h)}, st);
-    else if (h->detect) launch_twin<LS_PREPARE_DETECT>(h, (unsigned)h->vblk, {vec_args(h), det_args(h)}, st);
-    else launch_vec_step<LS_PREPARE, LS_PREPARE_BND>(h, st);
+#define ROW_TWIN(SERVES, T) {SERVES, #T, T, row_twin<T>},
+#define ROW_UNTWINNED(SERVES, K) {SERVES, #K, -1, row_untwinned<K>},
+#define ROW_DIRECT(SERVES, K) {SERVES, #K, -1, row_direct<K>},
+#define STEP_TABLE(NAME, VARIANTS, FLAGS, ROW_U)                                              \
+    static constexpr StepRow NAME##_ROWS[] = {VARIANTS(ROW_U, ROW_TWIN)};                     \
+    static constexpr StepTable NAME = {NAME##_ROWS, (int)(sizeof NAME##_ROWS / sizeof(StepRow)), FLAGS}; \
+    static_assert(step_table_ok(NAME), #NAME ": a legal class without a row, or with two")
+STEP_TABLE(STEP_PREPARE, PREPARE_VARIANTS, PREPARE_FLAGS, ROW_UNTWINNED);
+STEP_TABLE(STEP_STOP_TEST, STOP_TEST_VARIANTS, STOP_TEST_FLAGS, ROW_UNTWINNED);
+STEP_TABLE(STEP_SCALING, SCALING_VARIANTS, SCALING_FLAGS, ROW_DIRECT);
+STEP_TABLE(STEP_DIRECTION, DIRECTION_VARIANTS, DIRECTION_FLAGS, ROW_UNTWINNED);
+STEP_TABLE(STEP_MU_AFF, MU_AFF_VARIANTS, MU_AFF_FLAGS, ROW_UNTWINNED);
+STEP_TABLE(STEP_CORRECTOR_RHS, CORRECTOR_RHS_VARIANTS, CORRECTOR_RHS_FLAGS, ROW_UNTWINNED);
+STEP_TABLE(STEP_UPDATE, UPDATE_VARIANTS, UPDATE_FLAGS, ROW_UNTWINNED);
+STEP_TABLE(STEP_START_PRIMAL, START_PRIMAL_VARIANTS, START_FLAGS, ROW_DIRECT);
+STEP_TABLE(STEP_START_DUAL, START_DUAL_VARIANTS, START_FLAGS, ROW_DIRECT);
+STEP_TABLE(STEP_START_SHIFT, START_SHIFT_VARIANTS, START_FLAGS, ROW_DIRECT);
+STEP_TABLE(STEP_START_PRIMAL_CORRECT, START_PRIMAL_CORRECT_VARIANTS, START_FLAGS, ROW_DIRECT);
+STEP_TABLE(STEP_START_DUAL_CORRECT, START_DUAL_CORRECT_VARIANTS, START_FLAGS, ROW_DIRECT);
+// the launch of a step on a handle: the vector steps run h->vblk blocks of VBLK threads, the stop test one block of 64
+static void launch_step(const StepTable& t, ipm_handle* h, hipStream_t st = nullptr, int corr = 0, unsigned grid = 0, unsigned threads = VBLK) {
+    step_row(t, variant_bits(step_variant(h)))->launch(h, corr, grid ? grid : (unsigned)h->vblk, threads, st);
 }
-static void launch_stop_test(ipm_handle* h, hipStream_t st) {
-    if (quad_detect(h)) {
-        if (h->free_on && h->bnd) launch_untwinned(h, stop_test_bounded_free_detect_kernel, dim3(1u), dim3(64), st, vec_args(h), bnd_args(h), det_args(h), free_args(h));
-        else if (h->free_on) launch_untwinned(h, stop_test_free_detect_kernel, dim3(1u), dim3(64), st, vec_args(h), det_args(h), free_args(h));
-        else if (h->bnd) launch_untwinned(h, stop_test_bounded_quad_detect_kernel, dim3(1u), dim3(64), st, vec_args(h), bnd_args(h), det_args(h));
-        else launch_untwinned(h, stop_test_quad_detect_kernel, dim3(1u), dim3(64), st, vec_args(h), det_args(h));
-        return;
-    }
-    if (free_step(h, stop_test_free_kernel, stop_test_bounded_free_kernel, st, 1u)) return;
-    if (h->bnd && h->detect) launch_twin<LS_STOP_TEST_DETECT_BND>(h, 1u, {vec_args(h), bnd_args(h), det_args(h)}, st);
-    else if (h->bnd) launch_twin<LS_STOP_TEST_BND>(h, 1u, {vec_args(h), 0, bnd_args(h)}, st);
-    else if (h->detect) launch_twin<LS_STOP_TEST_DETECT>(h, 1u, {vec_args(h), det_args(h)}, st);
-    else launch_twin<LS_STOP_TEST>(h, 1u, {vec_args(h), 0}, st);
-}
-static void launch_scaling(ipm_handle* h) {      // (residual-stream iteration only, which is never recorded: no twin, nothing to refuse)
-    const double* g = h->quad_g;
-    if (h->free_on && h->bnd) hipLaunchKernelGGL(scaling_bounded_free_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), bnd_args(h), g, free_args(h));
-    else if (h->free_on) hipLaunchKernelGGL(scaling_free_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), g, free_args(h));
-    else if (h->quad && h->bnd) hipLaunchKernelGGL(scaling_bounded_quad_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), bnd_args(h), g);
-    else if (h->quad) hipLaunchKernelGGL(scaling_quad_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), g);
-    else if (h->bnd) hipLaunchKernelGGL(scaling_bounded_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h), bnd_args(h));
-    else hipLaunchKernelGGL(scaling_kernel, dim3(h->vblk), dim3(VBLK), 0, h->stream, vec_args(h));
-}
-static void launch_direction(ipm_handle* h, int corr) {
-    if (h->free_on && h->bnd) launch_untwinned(h, direction_bounded_free_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), corr, bnd_args(h), free_args(h));
-    else if (h->free_on) launch_untwinned(h, direction_free_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), corr, free_args(h));
-    else if (h->bnd) launch_twin<LS_DIRECTION_BND>(h, (unsigned)h->vblk, {vec_args(h), corr, bnd_args(h)});
-    else launch_twin<LS_DIRECTION>(h, (unsigned)h->vblk, {vec_args(h), corr});
-}
+static void launch_prepare(ipm_handle* h, hipStream_t st) { launch_step(STEP_PREPARE, h, st); }
+static void launch_stop_test(ipm_handle* h, hipStream_t st) { launch_step(STEP_STOP_TEST, h, st, 0, 1u, 64u); }
+static void launch_scaling(ipm_handle* h) { launch_step(STEP_SCALING, h); }
+static void launch_direction(ipm_handle* h, int corr) { launch_step(STEP_DIRECTION, h, nullptr, corr); }
+static void launch_mu_aff(ipm_handle* h) { launch_step(STEP_MU_AFF, h); }
+static void launch_corrector_rhs(ipm_handle* h) { launch_step(STEP_CORRECTOR_RHS, h); }
+static void launch_update(ipm_handle* h) { launch_step(STEP_UPDATE, h); }
 // The three vector kernels of a centrality-corrector round (vector_ops.h: mcc_*).  No lockstep twins: ipm_set_centrality_correctors
-// refuses a lockstep handle, and a program recorded with rounds pending would be cut like any other untwinned launch.
+// refuses a lockstep handle, and a program recorded with rounds pending would be cut like any other untwinned launch.  They take two
+// VecArgs and two BndArgs views, so a type does not identify the argument: their plain / bounded forks are written out.
 static void launch_mcc_target(ipm_handle* h, int first) {
     if (h->bnd) launch_untwinned(h, mcc_target_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, first), bnd_args(h), mcc_bnd_args(h));
     else launch_untwinned(h, mcc_target_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, first));
@@ -107,13 +99,11 @@ static void launch_mcc_accept(ipm_handle* h) {
     if (h->bnd) launch_untwinned(h, mcc_accept_bounded_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, 0), bnd_args(h), mcc_bnd_args(h));
     else launch_untwinned(h, mcc_accept_kernel, dim3(h->vblk), dim3(VBLK), nullptr, vec_args(h), mcc_vec_args(h), mcc_args(h, 0));
 }
-static void launch_mu_aff(ipm_handle* h) { if (!free_step(h, mu_aff_free_kernel, mu_aff_bounded_free_kernel)) launch_vec_step<LS_MU_AFF, LS_MU_AFF_BND>(h, nullptr, mu_aff_quad_kernel, mu_aff_bounded_quad_kernel); }
-static void launch_corrector_rhs(ipm_handle* h) { if (!free_step(h, corrector_rhs_free_kernel, corrector_rhs_bounded_free_kernel)) launch_vec_step<LS_CORR_RHS, LS_CORR_RHS_BND>(h); }
-static void launch_update(ipm_handle* h) { if (!free_step(h, update_free_kernel, update_bounded_free_kernel)) launch_vec_step<LS_UPDATE, LS_UPDATE_BND>(h, nullptr, update_quad_kernel, update_bounded_quad_kernel); }
 
 // r_b, r_c, d, predictor v, stop test (and, with IPM_FLAG_DETECT_INFEASIBILITY, the infeasibility tests): the one launch site of the
 // stop test of every multi-kernel path (dense, sparse envelope, sparse factor, fused formation + factorization, lockstep)
 static int enqueue_residuals(ipm_handle* h, hipStream_t st = nullptr) {
+    if (int rc_ = check_class(h, "enqueue_residuals")) return rc_;
     launch_gemv_n(h, h->x, 1.0, -1.0, h->b, h->rb, st);             // r_b = A x - b
     launch_gemv_t(h, h->y, st);                                     // A^T y (partials)
     launch_prepare(h, st);

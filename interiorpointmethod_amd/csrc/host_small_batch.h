@@ -22,6 +22,7 @@ static int small_batch_round(ipm_handle* h0, ipm_handle** hs, const std::vector<
     int count[SMALL_NVARIANTS] = {};
     for (int p = 0; p < cnt; ++p) {
         ipm_handle* h = hs[order[(size_t)p]];
+        if (int rc_ = check_class(h, "ipm_solve_small_batch")) return rc_;
         const bool may_auto = h->opt.regularize == 0.0 && !(h->opt.flags & IPM_FLAG_NO_AUTO_REGULARIZE);
         items[(size_t)p] = small_item(h, p, 1 << 30, first && may_auto ? 1 : 0);
         count[items[(size_t)p].variant]++;
@@ -32,7 +33,7 @@ static int small_batch_round(ipm_handle* h0, ipm_handle** hs, const std::vector<
     int off = 0;
     for (int v = 0; v < SMALL_NVARIANTS; ++v) {
         if (!count[v]) continue;
-        launch_small(v, S, nullptr, d_items + off, (unsigned)count[v]);
+        launch_small(SMALL_ROWS[v], S, nullptr, d_items + off, (unsigned)count[v]);
         off += count[v];
     }
     hipLaunchKernelGGL(small_batch_gather_kernel, dim3(g256), dim3(256), 0, S, d_items, cnt, d_sc);
@@ -151,20 +152,21 @@ extern "C" int ipm_init_small_batch_mehrotra(ipm_handle** hs, int32_t n, void* s
     std::vector<int> order((size_t)n);
     for (int i = 0; i < n; ++i) order[(size_t)i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) {      // plain first, inside a variant the long LPs first (small_cost)
-        if (hs[a]->bnd != hs[b]->bnd) return !hs[a]->bnd;
+        const bool ba = step_variant(hs[a]).bounded, bb = step_variant(hs[b]).bounded;
+        if (ba != bb) return !ba;
         return small_cost(hs[a]) > small_cost(hs[b]);
     });
     std::vector<SmallItem> items((size_t)n);
     int nplain = 0;
     for (int p = 0; p < n; ++p) {
         items[(size_t)p] = small_item(hs[order[(size_t)p]], p, 0, 0);
-        if (!hs[order[(size_t)p]]->bnd) ++nplain;
+        if (!step_variant(hs[order[(size_t)p]]).bounded) ++nplain;
     }
     HIP_TRY(h0, hipMemcpyAsync(mem.items, items.data(), sizeof(SmallItem) * (size_t)n, hipMemcpyHostToDevice, S));
     const unsigned g256 = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(small_batch_params_kernel, dim3(g256), dim3(256), 0, S, mem.items, (int)n, 1e-8, 1e-8, 1e-8, 1 << 30);
-    if (nplain) launch_small_start(false, S, nullptr, mem.items, (unsigned)nplain);
-    if (n - nplain) launch_small_start(true, S, nullptr, mem.items + nplain, (unsigned)(n - nplain));
+    if (nplain) launch_small(SMALL_START_ROWS[0], S, nullptr, mem.items, (unsigned)nplain);
+    if (n - nplain) launch_small(SMALL_START_ROWS[1], S, nullptr, mem.items + nplain, (unsigned)(n - nplain));
     hipLaunchKernelGGL(small_batch_gather_kernel, dim3(g256), dim3(256), 0, S, mem.items, (int)n, mem.sc);
     HIP_TRY(h0, hipGetLastError());
     std::vector<Scalars> host_sc((size_t)n);

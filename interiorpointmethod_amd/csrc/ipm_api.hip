@@ -748,6 +748,31 @@ extern "C" int ipm_debug_chol_plan(int32_t nblk, int64_t m, const int32_t knobs[
     return IPM_OK;
 }
 
+// The variant tables, read back (host only; tests/test_step_dispatch_host.py): the row that serves a class at a step.
+extern "C" int ipm_debug_step_kernel(int32_t step, int32_t bounded, int32_t detect, int32_t quad, int32_t free_cols, char* name_out, int32_t capacity,
+                                     int32_t* twin_type_out) {
+    static const StepTable* const steps[] = {&STEP_PREPARE, &STEP_STOP_TEST, &STEP_SCALING, &STEP_DIRECTION, &STEP_MU_AFF, &STEP_CORRECTOR_RHS, &STEP_UPDATE};
+    static const StepTable* const starts[] = {&STEP_START_PRIMAL, &STEP_START_DUAL, &STEP_START_SHIFT, &STEP_START_PRIMAL_CORRECT, &STEP_START_DUAL_CORRECT};
+    static_assert(sizeof steps / sizeof *steps == IPM_STEP_SMALL && IPM_STEP_START_PRIMAL + sizeof starts / sizeof *starts == IPM_STEP_COUNT, "the step ids of ipm_hip.h");
+    const unsigned bits = variant_bits(StepVariant{bounded != 0, detect != 0, quad != 0, free_cols != 0});
+    if (step < 0 || step >= IPM_STEP_COUNT || capacity < 0 || (capacity > 0 && !name_out)) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_debug_step_kernel: bad arguments");
+    if (!variant_legal(bits)) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_debug_step_kernel: free columns without a quadratic term are no class (a free column needs g > 0)");
+    const char* name;
+    int id;
+    if (step >= IPM_STEP_SMALL && step < IPM_STEP_START_PRIMAL) {          // the one-workgroup path: the row's id is its SMALL_* value / bounded
+        const bool start = step >= IPM_STEP_SMALL_START, batch = step == IPM_STEP_SMALL_BATCH || step == IPM_STEP_SMALL_START_BATCH;
+        id = start ? small_row_of(SMALL_START_ROWS, bits & V_B) : small_row_of(SMALL_ROWS, bits);
+        const SmallRow& row = start ? SMALL_START_ROWS[id] : SMALL_ROWS[id];
+        name = batch ? row.batch_name : row.name;
+    } else {
+        const StepRow* row = step_row(step < IPM_STEP_SMALL ? *steps[step] : *starts[step - IPM_STEP_START_PRIMAL], bits);
+        name = row->name; id = row->twin;
+    }
+    if (capacity > 0) snprintf(name_out, (size_t)capacity, "%s", name);
+    if (twin_type_out) *twin_type_out = id;
+    return IPM_OK;
+}
+
 // ------------------------------------------------------------------------------- kernel-level entry points
 extern "C" int ipm_form_normal_matrix(ipm_handle* h, const double* d, double* B, int64_t ldb) {
     if (!h || !d || !B || ldb < h->m) return fail(h, IPM_ERR_INVALID_ARG, "ipm_form_normal_matrix: bad arguments");

@@ -27,6 +27,8 @@
 #include "trsv_grouped.h"
 #include "vector_ops.h"
 
+struct ipm_handle;      // (include/ipm_hip.h; defined in host_handle.h)
+
 namespace ipm {
 
 enum LsType {
@@ -55,10 +57,11 @@ struct LsRec {                                // one LP's share of one global st
     alignas(8) unsigned char args[LS_ARG_BYTES];
 };
 
-struct LsVecA { VecArgs a; int corr; };
-struct LsVecDet { VecArgs a; DetArgs dt; };             // the infeasibility tests of a handle with IPM_FLAG_DETECT_INFEASIBILITY
-struct LsVecBnd { VecArgs a; int corr; BndArgs bd; };   // a handle with native upper bounds (ipm_set_bounds) ...
-struct LsVecBndDet { VecArgs a; BndArgs bd; DetArgs dt; };   // ... and with the infeasibility tests
+// (the four of the vector steps are filled from a handle at a step, corr = the direction step's: the constructors, host_handle.h)
+struct LsVecA { VecArgs a; int corr; LsVecA(ipm_handle* h, int corr); };
+struct LsVecDet { VecArgs a; DetArgs dt; LsVecDet(ipm_handle* h, int corr); };             // the infeasibility tests of a handle with IPM_FLAG_DETECT_INFEASIBILITY
+struct LsVecBnd { VecArgs a; int corr; BndArgs bd; LsVecBnd(ipm_handle* h, int corr); };   // a handle with native upper bounds (ipm_set_bounds) ...
+struct LsVecBndDet { VecArgs a; BndArgs bd; DetArgs dt; LsVecBndDet(ipm_handle* h, int corr); };   // ... and with the infeasibility tests
 struct LsSpmv { SparseA A; int mp; const double* v; double sa, sb; const double* add; double* out; const int* done; };
 struct LsSpmvT { SparseA A; int np; const double* u; double* w; const int* done; };
 struct LsZero { double* p; int64_t n; const int* done; };

@@ -476,6 +476,48 @@ __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_quad_detect
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_free_quad_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<false, true, true, true>(items); }
 __global__ __launch_bounds__(PD_THREADS) void small_lp_batch_bounded_free_quad_detect_kernel(const SmallItem* __restrict__ items) { small_lp_batch_body<true, true, true, true>(items); }
 
+// The variant table of the one-workgroup path (host side; vector_ops.h says how a class is written): row SMALL_x serves the class
+// `flags` with the single-LP kernel `one`, launched on a host item with its arguments bound by type, and the batch kernel `batch` on
+// a device table of items.  The ids keep their values: a batch launches one grid per variant in id order.
+template <> struct Pick<SmallLP, SmallItem> { static SmallLP of(const SmallItem& it) { return it.lp; } };
+template <> struct Pick<BndArgs, SmallItem> { static BndArgs of(const SmallItem& it) { return it.bd; } };
+template <> struct Pick<DetArgs, SmallItem> { static DetArgs of(const SmallItem& it) { return it.dt; } };
+template <> struct Pick<const double*, SmallItem> { static const double* of(const SmallItem& it) { return it.g; } };
+template <> struct Pick<FreeArgs, SmallItem> { static FreeArgs of(const SmallItem& it) { return it.fr; } };
+struct SmallRow {
+    int id; unsigned flags; const char *name, *batch_name;
+    void (*one)(hipStream_t, const SmallItem&); void (*batch)(const SmallItem*);
+};
+template <auto K> static void small_one(hipStream_t st, const SmallItem& it) { launch_bound(K, dim3(1), dim3(PD_THREADS), st, it); }
+#define SMALL_ROW(ID, FLAGS, ONE, BATCH) {ID, FLAGS, #ONE, #BATCH, small_one<ONE>, BATCH}
+constexpr SmallRow SMALL_ROWS[] = {
+    SMALL_ROW(SMALL_PLAIN, 0, small_lp_kernel, small_lp_batch_kernel),
+    SMALL_ROW(SMALL_BOUNDED, V_B, small_lp_bounded_kernel, small_lp_batch_bounded_kernel),
+    SMALL_ROW(SMALL_DETECT, V_D, small_lp_detect_kernel, small_lp_batch_detect_kernel),
+    SMALL_ROW(SMALL_BOUNDED_DETECT, V_B | V_D, small_lp_bounded_detect_kernel, small_lp_batch_bounded_detect_kernel),
+    SMALL_ROW(SMALL_QUAD, V_Q, small_qp_kernel, small_lp_batch_quad_kernel),
+    SMALL_ROW(SMALL_BOUNDED_QUAD, V_B | V_Q, small_qp_bounded_kernel, small_lp_batch_bounded_quad_kernel),
+    SMALL_ROW(SMALL_FREE_QUAD, V_Q | V_F, small_qp_free_kernel, small_lp_batch_free_quad_kernel),
+    SMALL_ROW(SMALL_BOUNDED_FREE_QUAD, V_B | V_Q | V_F, small_qp_bounded_free_kernel, small_lp_batch_bounded_free_quad_kernel),
+    SMALL_ROW(SMALL_QUAD_DETECT, V_D | V_Q, small_qp_detect_kernel, small_lp_batch_quad_detect_kernel),
+    SMALL_ROW(SMALL_BOUNDED_QUAD_DETECT, V_B | V_D | V_Q, small_qp_bounded_detect_kernel, small_lp_batch_bounded_quad_detect_kernel),
+    SMALL_ROW(SMALL_FREE_QUAD_DETECT, V_D | V_Q | V_F, small_qp_free_detect_kernel, small_lp_batch_free_quad_detect_kernel),
+    SMALL_ROW(SMALL_BOUNDED_FREE_QUAD_DETECT, V_B | V_D | V_Q | V_F, small_qp_bounded_free_detect_kernel, small_lp_batch_bounded_free_quad_detect_kernel),
+};
+// the row of a class (its index in `rows` is its id), -1 for none
+template <int N> constexpr int small_row_of(const SmallRow (&rows)[N], unsigned bits) {
+    for (int i = 0; i < N; ++i) if (rows[i].flags == bits) return i;
+    return -1;
+}
+// every row sits at its id, and every legal class has its row (flags are distinct: N legal classes, N rows)
+template <int N> constexpr bool small_rows_ok(const SmallRow (&rows)[N], unsigned mask, int legal) {
+    for (int i = 0; i < N; ++i) if (rows[i].id != i || !variant_legal(rows[i].flags) || (rows[i].flags & ~mask)) return false;
+    int n = 0;
+    for (unsigned c = 0; c <= mask; ++c) if ((c & ~mask) == 0 && variant_legal(c) && small_row_of(rows, c) >= 0) ++n;
+    return n == N && N == legal;
+}
+static_assert(small_rows_ok(SMALL_ROWS, V_ALL, SMALL_NVARIANTS), "SMALL_ROWS: one row per legal class, each at its SMALL_* id");
+
 // start_solve(force = 0, reset = 1) for every item, as set_params_kernel does for one LP: one thread per item
 __global__ __launch_bounds__(256) void small_batch_params_kernel(const SmallItem* __restrict__ items, int n, double e1, double e2, double e3, int max_iter) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -593,6 +635,12 @@ __global__ __launch_bounds__(PD_THREADS) void small_start_kernel(SmallLP a) { sm
 __global__ __launch_bounds__(PD_THREADS) void small_start_bounded_kernel(SmallLP a, BndArgs bd) { small_start_body<true>(a, bd); }
 __global__ __launch_bounds__(PD_THREADS) void small_start_batch_kernel(const SmallItem* __restrict__ items) { const SmallItem it = items[blockIdx.x]; small_start_body<false>(it.lp, it.bd); }
 __global__ __launch_bounds__(PD_THREADS) void small_start_batch_bounded_kernel(const SmallItem* __restrict__ items) { const SmallItem it = items[blockIdx.x]; small_start_body<true>(it.lp, it.bd); }
+// the start tells plain (row 0) from bounded (row 1) only: the tests of a Detect handle and the term play no part in it
+constexpr SmallRow SMALL_START_ROWS[] = {
+    SMALL_ROW(0, 0, small_start_kernel, small_start_batch_kernel),
+    SMALL_ROW(1, V_B, small_start_bounded_kernel, small_start_batch_bounded_kernel),
+};
+static_assert(small_rows_ok(SMALL_START_ROWS, V_B, 2), "SMALL_START_ROWS: plain, bounded");
 
 // every item's scalar record into ONE contiguous array (slot = the item's index): the host reads all statistics with one copy
 __global__ __launch_bounds__(256) void small_batch_gather_kernel(const SmallItem* __restrict__ items, int n, Scalars* __restrict__ out) {

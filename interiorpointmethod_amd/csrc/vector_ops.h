@@ -153,6 +153,32 @@ struct VecArgs {
     IterRec* hist;                 // [HIST_CAP] ring of per-iteration records
 };
 
+// ------------------------------------------------------------------------------- class variants (host side)
+// A handle's problem class is four switches, and every step of the iteration has one kernel per class it tells apart.  Which kernel
+// serves which class is stated ONCE per step, in a table directly below the step's __global__ wrappers (here and in small_lp.h):
+//     #define X_VARIANTS(U, T)  U(classes, kernel) ... T(classes, lockstep twin type) ...
+// a row names its kernel once, says which classes it serves (V_AT(switches), or-ed where it serves several), and is either an untwinned
+// kernel (U) or a lockstep twin type (T: lockstep.h, LsTwin<T>, which names the single-LP kernel).  X_FLAGS are the switches the step
+// tells apart; the look-up masks the others off.  The host expands the lists into its launch tables (host_residuals.h), where a
+// static_assert holds every table to "each legal class is served by exactly one row"; ipm_debug_step_kernel reads them back.
+struct StepVariant {
+    bool bounded, detect, quad, free;      // ipm_set_bounds, IPM_FLAG_DETECT_INFEASIBILITY, ipm_set_quadratic, ipm_set_free_columns
+};
+enum : unsigned { V_B = 1, V_D = 2, V_Q = 4, V_F = 8, V_ALL = 15 };
+constexpr unsigned variant_bits(StepVariant v) { return (v.bounded ? V_B : 0u) | (v.detect ? V_D : 0u) | (v.quad ? V_Q : 0u) | (v.free ? V_F : 0u); }
+// THE legality rule of a class: a free column needs curvature, so free implies quad (check_ready and the small batch's own check
+// refuse a handle in the other state before anything is launched)
+constexpr bool variant_legal(unsigned bits) { return !(bits & V_F) || (bits & V_Q); }
+#define V_AT(bits) (1u << (bits))         // the one class with exactly these switches (after the step's mask), as a set
+
+// A kernel's arguments, bound by its parameter TYPES: Pick<P, Src>::of(src) is the argument of type P that a source of arguments
+// holds (a handle at a step: host_handle.h, StepSrc; an item of the one-workgroup path: small_lp.h, SmallItem).  Each class-variant
+// kernel's parameter list says which argument groups it takes, so no call site writes one out.
+template <class P, class Src> struct Pick;
+template <class Src, class... P> static void launch_bound(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t st, const Src& src) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, Pick<P, Src>::of(src)...);
+}
+
 // sum over the row chunks of the GEMV-T partials, in chunk order (fixed order: bitwise reproducible).  Eight loads are in
 // flight at a time: a plain loop waits for every load before it issues the next one (32 chunks = 32 L2 latencies, 13 us of
 // direction_kernel's 13 us at n = 8192).
@@ -286,6 +312,20 @@ __global__ __launch_bounds__(VBLK) void prepare_quad_detect_kernel(VecArgs a, co
 __global__ __launch_bounds__(VBLK) void prepare_bounded_quad_detect_kernel(VecArgs a, BndArgs bd, const double* g) { prepare_kernel_body<true, true, true>(a, blockIdx.x, gridDim.x, bd, g); }
 __global__ __launch_bounds__(VBLK) void prepare_free_detect_kernel(VecArgs a, const double* g, FreeArgs fr) { prepare_kernel_body<false, true, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, g, fr); }
 __global__ __launch_bounds__(VBLK) void prepare_bounded_free_detect_kernel(VecArgs a, BndArgs bd, const double* g, FreeArgs fr) { prepare_kernel_body<true, true, true, true>(a, blockIdx.x, gridDim.x, bd, g, fr); }
+constexpr unsigned PREPARE_FLAGS = V_ALL;
+#define PREPARE_VARIANTS(U, T)                                                    \
+    T(V_AT(0), LS_PREPARE)                                                        \
+    T(V_AT(V_B), LS_PREPARE_BND)                                                  \
+    T(V_AT(V_D), LS_PREPARE_DETECT)                                               \
+    T(V_AT(V_B | V_D), LS_PREPARE_DETECT_BND)                                     \
+    U(V_AT(V_Q), prepare_quad_kernel)                                             \
+    U(V_AT(V_B | V_Q), prepare_bounded_quad_kernel)                               \
+    U(V_AT(V_Q | V_F), prepare_free_kernel)                                       \
+    U(V_AT(V_B | V_Q | V_F), prepare_bounded_free_kernel)                         \
+    U(V_AT(V_D | V_Q), prepare_quad_detect_kernel)                                \
+    U(V_AT(V_B | V_D | V_Q), prepare_bounded_quad_detect_kernel)                  \
+    U(V_AT(V_D | V_Q | V_F), prepare_free_detect_kernel)                          \
+    U(V_AT(V_B | V_D | V_Q | V_F), prepare_bounded_free_detect_kernel)
 
 // d = x / s only (main.py:223): what the formation of A D^2 A^T needs; the full prepare_kernel follows on the residual
 // stream while the factorization runs (host_iteration.h, enqueue_iteration).  Bounded: d = theta on U.  Quad: the quad_* scalings.
@@ -317,6 +357,14 @@ __global__ __launch_bounds__(VBLK) void scaling_quad_kernel(VecArgs a, const dou
 __global__ __launch_bounds__(VBLK) void scaling_bounded_quad_kernel(VecArgs a, BndArgs bd, const double* g) { scaling_kernel_body<true, true>(a, bd, g); }
 __global__ __launch_bounds__(VBLK) void scaling_free_kernel(VecArgs a, const double* g, FreeArgs fr) { scaling_kernel_body<false, true, true>(a, BndArgs{}, g, fr); }
 __global__ __launch_bounds__(VBLK) void scaling_bounded_free_kernel(VecArgs a, BndArgs bd, const double* g, FreeArgs fr) { scaling_kernel_body<true, true, true>(a, bd, g, fr); }
+constexpr unsigned SCALING_FLAGS = V_B | V_Q | V_F;      // (residual-stream iteration only, which is never recorded: launched directly)
+#define SCALING_VARIANTS(U, T)                                                    \
+    U(V_AT(0), scaling_kernel)                                                    \
+    U(V_AT(V_B), scaling_bounded_kernel)                                          \
+    U(V_AT(V_Q), scaling_quad_kernel)                                             \
+    U(V_AT(V_B | V_Q), scaling_bounded_quad_kernel)                               \
+    U(V_AT(V_Q | V_F), scaling_free_kernel)                                       \
+    U(V_AT(V_B | V_Q | V_F), scaling_bounded_free_kernel)
 
 // stop test of check_optimality (main.py:162-173) -- one thread.
 // Bounded: ||r_b||^2 carries r_u^2 and the gap w.z (prepare_kernel), b_norm is ||(b, u_U)|| (ipm_set_bounds), mu divides by n + |U|.
@@ -370,6 +418,19 @@ __global__ void stop_test_quad_detect_kernel(VecArgs a, DetArgs dt) { stop_test_
 __global__ void stop_test_bounded_quad_detect_kernel(VecArgs a, BndArgs bd, DetArgs dt) { stop_test_kernel_body<true, true, false, true>(a, blockIdx.x, gridDim.x, bd, dt); }
 __global__ void stop_test_free_detect_kernel(VecArgs a, DetArgs dt, FreeArgs fr) { stop_test_kernel_body<false, true, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, dt, fr); }
 __global__ void stop_test_bounded_free_detect_kernel(VecArgs a, BndArgs bd, DetArgs dt, FreeArgs fr) { stop_test_kernel_body<true, true, true, true>(a, blockIdx.x, gridDim.x, bd, dt, fr); }
+// (the term alone changes nothing the stop test reads: without Detect a quadratic handle takes the LP's rows)
+constexpr unsigned STOP_TEST_FLAGS = V_ALL;
+#define STOP_TEST_VARIANTS(U, T)                                                  \
+    T(V_AT(0) | V_AT(V_Q), LS_STOP_TEST)                                          \
+    T(V_AT(V_B) | V_AT(V_B | V_Q), LS_STOP_TEST_BND)                              \
+    T(V_AT(V_D), LS_STOP_TEST_DETECT)                                             \
+    T(V_AT(V_B | V_D), LS_STOP_TEST_DETECT_BND)                                   \
+    U(V_AT(V_Q | V_F), stop_test_free_kernel)                                     \
+    U(V_AT(V_B | V_Q | V_F), stop_test_bounded_free_kernel)                       \
+    U(V_AT(V_D | V_Q), stop_test_quad_detect_kernel)                              \
+    U(V_AT(V_B | V_D | V_Q), stop_test_bounded_quad_detect_kernel)                \
+    U(V_AT(V_D | V_Q | V_F), stop_test_free_detect_kernel)                        \
+    U(V_AT(V_B | V_D | V_Q | V_F), stop_test_bounded_free_detect_kernel)
 
 // The certificate of a detection (ipm_get_certificate): kind 5 -> (y / beta, z / beta), kind 6 -> x / gamma; the other parts 0.
 // out = [x (n) | y (m) | z (n)]; z = nullptr without bounds.
@@ -415,6 +476,12 @@ __global__ __launch_bounds__(VBLK) void direction_kernel(VecArgs a, int corr) { 
 __global__ __launch_bounds__(VBLK) void direction_bounded_kernel(VecArgs a, int corr, BndArgs bd) { direction_kernel_body<true>(a, corr, blockIdx.x, gridDim.x, bd); }
 __global__ __launch_bounds__(VBLK) void direction_free_kernel(VecArgs a, int corr, FreeArgs fr) { direction_kernel_body<false, true>(a, corr, blockIdx.x, gridDim.x, BndArgs{}, fr); }
 __global__ __launch_bounds__(VBLK) void direction_bounded_free_kernel(VecArgs a, int corr, BndArgs bd, FreeArgs fr) { direction_kernel_body<true, true>(a, corr, blockIdx.x, gridDim.x, bd, fr); }
+constexpr unsigned DIRECTION_FLAGS = V_B | V_F;
+#define DIRECTION_VARIANTS(U, T)                                                  \
+    T(V_AT(0), LS_DIRECTION)                                                      \
+    T(V_AT(V_B), LS_DIRECTION_BND)                                                \
+    U(V_AT(V_F), direction_free_kernel)                                           \
+    U(V_AT(V_B | V_F), direction_bounded_free_kernel)
 
 // partial sums of mu_aff_column at the affine step lengths (Quad: at the one step quad_step makes of them, which the stats report)
 // Free: no term of a marked column.
@@ -446,6 +513,14 @@ __global__ __launch_bounds__(VBLK) void mu_aff_quad_kernel(VecArgs a) { mu_aff_k
 __global__ __launch_bounds__(VBLK) void mu_aff_bounded_quad_kernel(VecArgs a, BndArgs bd) { mu_aff_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd); }
 __global__ __launch_bounds__(VBLK) void mu_aff_free_kernel(VecArgs a, FreeArgs fr) { mu_aff_kernel_body<false, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, fr); }
 __global__ __launch_bounds__(VBLK) void mu_aff_bounded_free_kernel(VecArgs a, BndArgs bd, FreeArgs fr) { mu_aff_kernel_body<true, true, true>(a, blockIdx.x, gridDim.x, bd, fr); }
+constexpr unsigned MU_AFF_FLAGS = V_B | V_Q | V_F;
+#define MU_AFF_VARIANTS(U, T)                                                     \
+    T(V_AT(0), LS_MU_AFF)                                                         \
+    T(V_AT(V_B), LS_MU_AFF_BND)                                                   \
+    U(V_AT(V_Q), mu_aff_quad_kernel)                                              \
+    U(V_AT(V_B | V_Q), mu_aff_bounded_quad_kernel)                                \
+    U(V_AT(V_Q | V_F), mu_aff_free_kernel)                                        \
+    U(V_AT(V_B | V_Q | V_F), mu_aff_bounded_free_kernel)
 
 // centring from the re-summed partials of mu_aff_kernel, then corrector_column
 // Free: the centring over free_pair_count pairs (centring with n - n_free columns), free_rhs_column on the marked columns.
@@ -468,6 +543,12 @@ __global__ __launch_bounds__(VBLK) void corrector_rhs_kernel(VecArgs a) { correc
 __global__ __launch_bounds__(VBLK) void corrector_rhs_bounded_kernel(VecArgs a, BndArgs bd) { corrector_rhs_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 __global__ __launch_bounds__(VBLK) void corrector_rhs_free_kernel(VecArgs a, FreeArgs fr) { corrector_rhs_kernel_body<false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, fr); }
 __global__ __launch_bounds__(VBLK) void corrector_rhs_bounded_free_kernel(VecArgs a, BndArgs bd, FreeArgs fr) { corrector_rhs_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd, fr); }
+constexpr unsigned CORRECTOR_RHS_FLAGS = V_B | V_F;
+#define CORRECTOR_RHS_VARIANTS(U, T)                                              \
+    T(V_AT(0), LS_CORR_RHS)                                                       \
+    T(V_AT(V_B), LS_CORR_RHS_BND)                                                 \
+    U(V_AT(V_F), corrector_rhs_free_kernel)                                       \
+    U(V_AT(V_B | V_F), corrector_rhs_bounded_free_kernel)
 
 // damped_step from the re-summed ratio-test minima (Quad: quad_step of the pair), update_column, y += a_d dy, record_iteration
 // Free: free_update_column on the marked columns (s stays 0).
@@ -499,6 +580,14 @@ __global__ __launch_bounds__(VBLK) void update_quad_kernel(VecArgs a) { update_k
 __global__ __launch_bounds__(VBLK) void update_bounded_quad_kernel(VecArgs a, BndArgs bd) { update_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd); }
 __global__ __launch_bounds__(VBLK) void update_free_kernel(VecArgs a, FreeArgs fr) { update_kernel_body<false, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, fr); }
 __global__ __launch_bounds__(VBLK) void update_bounded_free_kernel(VecArgs a, BndArgs bd, FreeArgs fr) { update_kernel_body<true, true, true>(a, blockIdx.x, gridDim.x, bd, fr); }
+constexpr unsigned UPDATE_FLAGS = V_B | V_Q | V_F;
+#define UPDATE_VARIANTS(U, T)                                                     \
+    T(V_AT(0), LS_UPDATE)                                                         \
+    T(V_AT(V_B), LS_UPDATE_BND)                                                   \
+    U(V_AT(V_Q), update_quad_kernel)                                              \
+    U(V_AT(V_B | V_Q), update_bounded_quad_kernel)                                \
+    U(V_AT(V_Q | V_F), update_free_kernel)                                        \
+    U(V_AT(V_B | V_Q | V_F), update_bounded_free_kernel)
 
 // ---------------------------------------------------------------------------------------
 // Centrality correctors (iteration_rules.h: mcc_*): the three vector kernels of one round, enqueued K times between
@@ -691,6 +780,13 @@ __device__ __forceinline__ void start_dual_correct_kernel_body(VecArgs a, BndArg
 }
 __global__ __launch_bounds__(VBLK) void start_dual_correct_kernel(VecArgs a) { start_dual_correct_kernel_body<false>(a); }
 __global__ __launch_bounds__(VBLK) void start_dual_correct_bounded_kernel(VecArgs a, BndArgs bd) { start_dual_correct_kernel_body<true>(a, bd); }
+// The five steps of the start tell plain from bounded only (launched directly: the start is never part of a recorded program).
+constexpr unsigned START_FLAGS = V_B;
+#define START_PRIMAL_VARIANTS(U, T) U(V_AT(0), start_primal_kernel) U(V_AT(V_B), start_primal_bounded_kernel)
+#define START_DUAL_VARIANTS(U, T) U(V_AT(0), start_dual_kernel) U(V_AT(V_B), start_dual_bounded_kernel)
+#define START_SHIFT_VARIANTS(U, T) U(V_AT(0), start_shift_kernel) U(V_AT(V_B), start_shift_bounded_kernel)
+#define START_PRIMAL_CORRECT_VARIANTS(U, T) U(V_AT(0), start_primal_correct_kernel) U(V_AT(V_B), start_primal_correct_bounded_kernel)
+#define START_DUAL_CORRECT_VARIANTS(U, T) U(V_AT(0), start_dual_correct_kernel) U(V_AT(V_B), start_dual_correct_bounded_kernel)
 
 // out[i] = value for i < n (fill)
 __global__ void fill_kernel(double* out, int n, double value) {
