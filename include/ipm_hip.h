@@ -323,6 +323,33 @@ int ipm_get_quadratic(ipm_handle* h, double* g, int64_t* nonzeros);
 int ipm_set_free_columns(ipm_handle* h, const int32_t* idx, int32_t count);
 /* The set in the caller's order: *count receives its size, idx (capacity cap; may be NULL with cap == 0) the first cap indices. */
 int ipm_get_free_columns(ipm_handle* h, int32_t* idx, int32_t cap, int32_t* count);
+
+/* ---- LP free columns: free variables of a linear program, served natively -------- */
+/* idx: `count` distinct column indices 0 .. n-1; count == 0 or idx == NULL clears the set, and the handle then enqueues exactly
+ * what it enqueued before.  An LP free column j carries no sign constraint and no quadratic term: no s_j (stored and returned as
+ * exactly 0), no bound, no complementarity pair.  Its curvature is borrowed: proximal-point primal regularisation of the free block
+ * only (Altman and Gondzio 1999) -- at every iteration the free block of the objective carries 1/2 rho |x - x^k|^2 centred at the
+ * iterate, whose gradient there is zero, so the residuals, the objective and the stop test are the true LP's, and only the Newton
+ * matrix sees rho, as Theta_j = 1 / rho on the column.  rho is one positive finite number per handle, applied in the units of the
+ * problem the handle iterates on (the scaled problem on an equilibrated handle); rho <= 0 selects IPM_FREE_LP_RHO_DEFAULT, a rho
+ * that is not finite is IPM_ERR_INVALID_ARG.  The iteration keeps the LP's two step lengths; mu, mu_aff and sigma count
+ * n - count (+ |U|) pairs; the ratio tests skip the columns; their dual residual (A^T y - c)_j counts in rd_norm.
+ * Served: bounds on the other columns, dense A (the fused launch and the residual stream included), the envelope factor and
+ * IPM_FLAG_SPARSE_FACTOR, ipm_set_refinement, ipm_equilibrate, the dense-column split, check_every / run-ahead,
+ * ipm_newton_direction, and ipm_init_state_mehrotra (x_j the least-squares value, unshifted and uncorrected; s_j = 0; no term in
+ * any minimum or sum of the start).
+ * State: as for ipm_set_free_columns (x = 1, s = 0 from ipm_init_state; s stored and returned as 0; setting the set zeroes s there;
+ * after clearing, set a state anew).
+ * Refused with IPM_ERR_INVALID_ARG and a reason in ipm_last_error, in either order of the calls involved, never dropped: an index
+ * out of range or given twice; a finite u_j on a marked column (here, or by ipm_set_bounds); every column free; a handle with a
+ * quadratic term or an ipm_set_free_columns set (and those two setters on a handle with this set); an IPM_FLAG_LOCKSTEP handle;
+ * an IPM_FLAG_DETECT_INFEASIBILITY handle; centrality correctors k > 0 (here, or by ipm_set_centrality_correctors); a handle
+ * already on the fused small path (set the columns before A: ipm_set_A_csc then takes the multi-kernel path).
+ * The marks are np bytes allocated by the library on first use and freed by ipm_destroy.  Invalidates a pending predictor. */
+#define IPM_FREE_LP_RHO_DEFAULT 1e-8
+int ipm_set_free_lp_columns(ipm_handle* h, const int32_t* idx, int32_t count, double rho);
+/* The set in the caller's order and its rho (either pointer may be NULL): *count receives the size, idx the first cap indices. */
+int ipm_get_free_lp_columns(ipm_handle* h, int32_t* idx, int32_t cap, int32_t* count, double* rho);
 /* Test hook: a column vector of the iteration as the device holds it after the last ipm_newton_direction / ipm_iterate, n entries
  * in the HANDLE's units (a scaled handle's are not unscaled): which = 0 r_c, 1 d (the diagonal of Theta), 2 v, 3 q. */
 int ipm_debug_get_column_vector(ipm_handle* h, int32_t which, double* out);
@@ -624,6 +651,11 @@ enum {
 };
 int ipm_debug_step_kernel(int32_t step, int32_t bounded, int32_t detect, int32_t quad, int32_t free_cols, char* name_out, int32_t capacity,
                           int32_t* twin_type_out);
+/* The same with the fifth switch, free_lp = ipm_set_free_lp_columns: legal only without detect, quad and free_cols, and served by the
+ * multi-kernel steps only (IPM_ERR_INVALID_ARG otherwise, the IPM_STEP_SMALL* steps included).  With free_lp = 0 it answers as
+ * ipm_debug_step_kernel does. */
+int ipm_debug_step_kernel_ex(int32_t step, int32_t bounded, int32_t detect, int32_t quad, int32_t free_cols, int32_t free_lp, char* name_out,
+                             int32_t capacity, int32_t* twin_type_out);
 int ipm_debug_ff_schedule(int32_t nblk, int32_t q, int32_t workers, unsigned char* items, int32_t capacity, int32_t* count,
                           int32_t* tile_items, double sim_us[2]);
 int ipm_get_phase_ms(ipm_handle* h, double out[4]);

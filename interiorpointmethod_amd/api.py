@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .analysis import _upper_bounds
-from .handle import (SCALE_PASSES, STATUS_NAMES, IpmSolver, check_correctors, check_detect_qp, check_free, check_quadratic, check_refine, check_scale, mehrotra_started,
+from .handle import (SCALE_PASSES, STATUS_NAMES, IpmSolver, check_correctors, check_detect_qp, check_free, check_free_lp, check_free_rho, check_quadratic, check_refine, check_scale, mehrotra_started,
                      refuse_free, refuse_quadratic, shift_allowed, wants_shift)
 
 
@@ -53,6 +53,7 @@ def _solve_info(solver, history=False, certificate=False):
     small = solver.schedule()["fused_small"]
     info["quadratic_path"] = None if not info["quadratic"] else "multi-kernel" if not small else "one-workgroup" if solver._n_free else "small"
     info["free"] = solver._n_free                           # free columns (0: none); the count the handle keeps, no library call
+    info["free_lp"] = solver._n_free_lp                     # LP free columns (0: none), likewise
     if solver.scale is not None:
         info["scale"] = dict(solver.scale_info)
         info["rp_unscaled"], info["rd_unscaled"] = unscaled_residuals(solver)
@@ -89,8 +90,8 @@ def _auto_regularize():          # the process-wide switch of the 5 % rule (hand
 
 def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, start="reference",
                     history=False, ub=None, detect_infeasibility=False, device_start=False, scale=None, scale_passes=SCALE_PASSES,
-                    correctors=0, refine=0, dense_cols=None, quad=None, quad_small=False, free=None, detect_qp=False, free_small=False, **opts):
-    # (detect_qp stands IN FRONT of free_small here, in solve and in interior_sparse: an existing test pins free_small as the last
+                    correctors=0, refine=0, dense_cols=None, quad=None, quad_small=False, free=None, detect_qp=False, free_lp=None, free_rho=None, free_small=False, **opts):
+    # (detect_qp, free_lp and free_rho stand IN FRONT of free_small here, in solve and in interior_sparse: an existing test pins free_small as the last
     #  parameter, so it cannot be keyword-only behind it; pass both by keyword)
     """solve() plus the statistics record (iterations, status, objective, rp, rd, gap, ...).
     start="reference": x = s = 1, y = y0 as the reference does; start="mehrotra": IpmSolver.mehrotra_start(), or with
@@ -121,7 +122,11 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     columns (IpmSolver, IPM_FLAG_SMALL_FREE); info["quadratic_path"] is then "one-workgroup".
     detect_qp=True (off by default): the infeasibility tests of a QUADRATIC problem (IpmSolver) -- with quad (and
     free) the solve may end in status 5 / 6 and info["certificate"] = IpmSolver.certificate(), which verify_certificate(..., g=quad,
-    free=free) checks.  Implies detect_infeasibility=True and lifts its refusal of quad / free; ValueError without a quadratic term."""
+    free=free) checks.  Implies detect_infeasibility=True and lifts its refusal of quad / free; ValueError without a quadratic term.
+    free_lp: None (default), column indices or a boolean mask: the LP free columns (IpmSolver) -- free variables of
+    an LP, served natively by proximal-point regularisation of the free block with the weight free_rho (None: the library's
+    default); info["free_lp"] = their count.  Checked on the host before any device is touched (ValueError naming the column);
+    refused (ValueError) together with quad, free, detect_infeasibility and correctors > 0.  Both starts serve the set."""
     global _last_info
     correctors = check_correctors(correctors)
     refine = check_refine(refine)
@@ -148,6 +153,9 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     free = check_free(free, np.asarray(c).reshape(-1).shape[0], quad, ub)
     if detect_infeasibility and not detect_qp:
         refuse_free(free, "detect_infeasibility=True", "the infeasibility tests are the LP's")
+    if check_free_lp(free_lp, np.asarray(c).reshape(-1).shape[0], ub, quad, free) is not None:
+        check_free_rho(free_rho)
+        opts = dict(opts, free_lp=free_lp, free_rho=free_rho)          # (IpmSolver refuses detect_infeasibility and correctors with it)
     detect_infeasibility = bool(detect_infeasibility) or detect_qp
     if correctors:
         refuse_free(free, "correctors=%d" % correctors, "a quadratic solver takes one step length, the rounds compare step pairs")
@@ -188,13 +196,13 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
 
 
 def solve(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, ub=None, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None,
-          quad=None, quad_small=False, free=None, detect_qp=False, free_small=False, **opts):
+          quad=None, quad_small=False, free=None, detect_qp=False, free_lp=None, free_rho=None, free_small=False, **opts):
     """min c^T x (+ 1/2 x^T diag(quad) x) s.t. Ax=b, x>=0 (and x <= ub where ub is finite) by the Mehrotra predictor-corrector loop
-    on the GPU -> (x, y, s).  quad_small, free (columns without the sign constraint), free_small, detect_qp: as solve_with_info
+    on the GPU -> (x, y, s).  quad_small, free (columns without the sign constraint), free_small, detect_qp, free_lp / free_rho (free variables of an LP): as solve_with_info
     (last_info() then holds the status and the certificate of a detection)."""
     x, y, s, _ = solve_with_info(A, b, c, tol=tol, max_iter=max_iter, y0=y0, device=device, ub=ub, scale=scale,
                                  scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad,
-                                 quad_small=quad_small, free=free, detect_qp=detect_qp, free_small=free_small, **opts)
+                                 quad_small=quad_small, free=free, detect_qp=detect_qp, free_lp=free_lp, free_rho=free_rho, free_small=free_small, **opts)
     return x, y, s
 
 
@@ -208,15 +216,16 @@ def _verdict(info, value):
 
 
 def interior_sparse(A, b, c, cTlb=0.0, tol=1e-20, device=0, detect_infeasibility=False, scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0,
-                    dense_cols=None, quad=None, free=None, detect_qp=False, free_small=False):
+                    dense_cols=None, quad=None, free=None, detect_qp=False, free_lp=None, free_rho=None, free_small=False):
     """Drop-in for main.py:760-815: start x=s=y=1, cap 5000, returns sum(x*c) - cTlb (with quad: the quadratic objective - cTlb).  detect_infeasibility=True: +inf for an
     LP detected infeasible, -inf for one detected unbounded.  scale, correctors, refine, dense_cols: as solve_with_info (off by
     default); free likewise (free columns of a quadratic problem), and free_small (the one-workgroup path for them).  detect_qp=True:
-    the same verdicts for a problem with quad (solve_with_info): +inf infeasible, -inf unbounded."""
+    the same verdicts for a problem with quad (solve_with_info): +inf infeasible, -inf unbounded.  free_lp / free_rho: the free
+    variables of an LP and their proximal weight, as solve_with_info."""
     _, _, _, info = solve_with_info(A, b, c, tol=tol, max_iter=5000, y0=1.0, device=device,
                                     detect_infeasibility=detect_infeasibility, scale=scale, scale_passes=scale_passes,
                                     correctors=correctors, refine=refine, dense_cols=dense_cols, quad=quad, free=free, detect_qp=detect_qp,
-                                    free_small=free_small)
+                                    free_lp=free_lp, free_rho=free_rho, free_small=free_small)
     return _verdict(info, info["objective"] - float(cTlb))
 
 

@@ -26,7 +26,7 @@ from .analysis import _upper_bounds, prepare
 from .api import _auto_regularize, _solve_info, solve_with_info
 from .batches import LockstepBatch, lockstep_eligible, small_batch_eligible, solve_small_batch_solvers
 from .analysis import refuse_dense_cols
-from .handle import SCALE_PASSES, IpmSolver, check_scale, mehrotra_started, refuse_correctors, refuse_detect_qp, refuse_free, refuse_refine
+from .handle import SCALE_PASSES, IpmSolver, check_scale, mehrotra_started, refuse_correctors, refuse_detect_qp, refuse_free, refuse_free_lp, refuse_refine
 
 # One record per LP.  The first nine fields are the statistics SURVEY.md 8e names; the rest make the library's hidden
 # recoveries and the host-side phases of a solve visible in the gathered table: `timeouts_recovered` = device hand-off
@@ -463,7 +463,7 @@ class _LockstepShard:
 
 def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=5000, y0=1.0, regularize=0.0, tol_gap=None,
                          detect_infeasibility=False, small_batch=False, start="reference", scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0,
-                         dense_cols=None, free=None, detect_qp=False, **_):
+                         dense_cols=None, free=None, detect_qp=False, free_lp=None, **_):
     """Solve problems[i] for i in ids on this rank's GPU with the LOCKSTEP BATCH -> (len(ids), NF) records.
 
     `workers` host threads prepare the LPs (host analysis, handle, upload), largest first.  An LP of more than 128 rows on the
@@ -492,6 +492,7 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
     does detect_qp=True (no quadratic kernels in the batch)."""
     refuse_detect_qp(detect_qp, "the lockstep batch", "the Quad and Free kernels have no batched twins; solve such problems one at a time")
     refuse_free(free, "the lockstep batch", "the Free kernels have no batched twins; solve such problems one at a time")
+    refuse_free_lp(free_lp, "the lockstep batch", "the free_lp kernels have no batched twins; solve such problems one at a time")
     refuse_correctors(correctors, "the lockstep batch")
     refuse_refine(refine, "the lockstep batch")
     refuse_dense_cols(dense_cols, "the lockstep batch")
@@ -611,7 +612,7 @@ def lockstep_wanted(problems, world=1, workers=8, mode="auto"):
 
 
 def run_batch(problems, costs=None, device=0, dist=None, gather_device=None, solve_fn=solve_one, workers=1,
-              schedule="static", store=None, collective_at_world_one=False, lockstep=False, free=None, **kw):
+              schedule="static", store=None, collective_at_world_one=False, lockstep=False, free=None, free_lp=None, **kw):
     """Shard `problems` (list of (A, b, c) or (A, b, c, ub): unpack_problem; ub = native upper bounds, checked on the host before any
     device work when solve_fn is solve_one) over the ranks of `dist`, solve, gather statistics.
 
@@ -624,6 +625,7 @@ def run_batch(problems, costs=None, device=0, dist=None, gather_device=None, sol
     dist.all_gather): that is how the RCCL branch is exercised on a one-GPU box (tests/test_gpu_parity.py).
     free (free columns of a quadratic problem) raises ValueError: a batch's problems are (A, b, c) triples, LPs."""
     refuse_free(free, "run_batch", "its problems are LPs; solve such problems one at a time")
+    refuse_free_lp(free_lp, "run_batch", "its problems are (A, b, c, ub) tuples with no slot for free columns; solve such problems one at a time")
     if solve_fn is solve_one:
         for p in problems:
             unpack_problem(p)

@@ -7,7 +7,7 @@ from . import _lib
 from .analysis import FUSED_SMALL_MAX_ROWS, _sp, _upper_bounds
 from .api import _auto_regularize, _solve_info
 from .analysis import refuse_dense_cols
-from .handle import (SCALE_PASSES, IpmSolver, _gap_tol, check_quadratic, check_scale, refuse_correctors, refuse_detect_qp, refuse_free, refuse_refine,
+from .handle import (SCALE_PASSES, IpmSolver, _gap_tol, check_quadratic, check_scale, refuse_correctors, refuse_detect_qp, refuse_free, refuse_free_lp, refuse_refine,
                      wants_shift)
 
 
@@ -22,7 +22,7 @@ def _scatter_stats(solvers, stats):           # each solver takes its statistics
     return [sv.stats for sv in solvers]
 
 
-def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None, correctors=0, refine=0, dense_cols=None, free=None, detect_qp=False):
+def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None, correctors=0, refine=0, dense_cols=None, free=None, detect_qp=False, free_lp=None):
     """ipm_solve_batch: solve the LPs of `solvers` (IpmSolver objects created with lockstep=True on one device, a state set) AT ONCE,
     iteration k of all of them in the same launches (csrc/lockstep.h) -> list of statistics dicts, one per solver.  Per-LP semantics
     and arithmetic are those of IpmSolver.solve on each of them alone (bit-identical iterates).  Bounded solvers (ub=) join when they
@@ -32,6 +32,7 @@ def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None, correctors=0,
     detect_qp=True (no quadratic kernels in the batch)."""
     refuse_detect_qp(detect_qp, "the lockstep batch", "the Quad and Free kernels have no batched twins; solve such problems one at a time")
     refuse_free(free, "the lockstep batch", "the Free kernels have no batched twins; solve such problems one at a time")
+    refuse_free_lp(free_lp, "the lockstep batch", "the free_lp kernels have no batched twins; solve such problems one at a time")
     refuse_correctors(correctors, "the lockstep batch")
     refuse_refine(refine, "the lockstep batch")
     refuse_dense_cols(dense_cols, "the lockstep batch")          # (the split has no batched twins: ValueError, never dropped)
@@ -197,7 +198,7 @@ def _small_batch_host_check(problems, ub):
 
 
 def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=None, ub=None, detect_infeasibility=False,
-                      regularize=0.0, start="reference", scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, free=None):
+                      regularize=0.0, start="reference", scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, free=None, free_lp=None):
     """Solve many small LPs at once -> list of (x, y, s, info), one per problem, each what solve_with_info returns for it alone.
 
     problems: list of (A, b, c) with at most 128 rows each; a dense A is converted to CSC.  ub: None or one entry per problem (None or
@@ -209,6 +210,7 @@ def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_g
     is launched.  scale="ruiz": every LP is equilibrated on the device first (IpmSolver; off by default).  correctors > 0: ValueError
     before any device is touched (solve_small_batch_solvers), and so for refine > 0 and for free columns (free=)."""
     refuse_free(free, "the small-LP batch", "the one-workgroup kernel has no free columns; solve such problems one at a time")
+    refuse_free_lp(free_lp, "the small-LP batch", "the one-workgroup kernel has no LP free columns; solve such problems one at a time")
     refuse_correctors(correctors, "the small-LP batch")
     refuse_refine(refine, "the small-LP batch")
     refuse_dense_cols(dense_cols, "the small-LP batch")          # (the one-workgroup kernel has no split: ValueError, never dropped)

@@ -174,6 +174,13 @@ struct ipm_handle {
     std::vector<char> free_host;          // host: column j is free (empty without a set), what ipm_set_bounds reads
     unsigned char* free_mark = nullptr;   // 1 on the free columns, 0 elsewhere and in the padding (written whole); scale-free and
                                           // constant during a solve, so neither the equilibration nor the roll-back snapshot touch it
+    // LP free columns (ipm_set_free_lp_columns): own allocation of np bytes, made on first use; never together with
+    // a quadratic term or the set above
+    bool free_lp_on = false;              // the set is not empty: the free_lp kernel instantiations run
+    std::vector<int> free_lp_cols;        // the set, in the caller's order
+    std::vector<char> free_lp_host;       // host: column j is in the set (empty without a set), what ipm_set_bounds reads
+    unsigned char* free_lp_mark = nullptr;   // as free_mark
+    double free_lp_rho = 1e-8;            // the proximal weight, in the handle's units (IPM_FREE_LP_RHO_DEFAULT)
     // centrality correctors (ipm_set_centrality_correctors): up to mcc.k rounds per iteration re-use its factor
     Rounds<MccCtl, MCC_CTL_DOUBLES> mcc{&MCC_KIND};   // mem: q v dx ds r3 r3g | qz dw dz r4 r4g (n-vectors) | dy (m-vector) | partial minima [2][MAXPART] | record | its copy
     // iterative refinement of the normal-equations solves (ipm_set_refinement): up to ref.k rounds behind every solve
@@ -436,6 +443,7 @@ static BndArgs bnd_args(ipm_handle* h) {
 }
 
 static FreeArgs free_args(const ipm_handle* h) { return FreeArgs{h->free_mark, (int)h->free_cols.size()}; }
+static FreeLpArgs free_lp_args(const ipm_handle* h) { return FreeLpArgs{FreeArgs{h->free_lp_mark, (int)h->free_lp_cols.size()}, h->free_lp_rho}; }
 
 // centrality correctors: views into mcc.mem.  mcc_vec_args / mcc_bnd_args are the handle's views with the candidate's arrays in place.
 static const int MCC_NVECS = 11;
@@ -479,15 +487,18 @@ static RefViews ref_views(const ipm_handle* h) {
 static DetArgs det_args(const ipm_handle* h) { return DetArgs{h->det_eps_p, h->det_eps_d, h->det}; }
 
 // ------------------------------------------------------------------------------- the handle's problem class and its arguments
-// The ONE place that reads the four class switches of a handle in order to choose a kernel (vector_ops.h: StepVariant and the
+// The ONE place that reads the five class switches of a handle in order to choose a kernel (vector_ops.h: StepVariant and the
 // variant tables; the legality rule free => quad is variant_legal, which check_ready and the small batch's own check enforce before
 // a launch).  Every other reader of these fields keeps data in step with them: the setters, equilibration, the roll-back copies
 // of (w, z), the refusals.
-static StepVariant step_variant(const ipm_handle* h) { return StepVariant{h->bnd, h->detect, h->quad, h->free_on}; }
+static StepVariant step_variant(const ipm_handle* h) { return StepVariant{h->bnd, h->detect, h->quad, h->free_on, h->free_lp_on}; }
 // ... and the guard in front of every table look-up (the iteration's and the small path's entries call it before their first launch):
 // a handle whose class is not legal has no row, and an entry point that forgot check_ready gets an error, not a null row.
 static int check_class(ipm_handle* h, const char* who) {
-    return variant_legal(variant_bits(step_variant(h))) ? IPM_OK : fail(h, IPM_ERR_STATE, "%s: free columns without a quadratic term: no kernel serves that class", who);
+    const unsigned bits = variant_bits(step_variant(h));
+    if (variant_legal(bits)) return IPM_OK;
+    if (bits & V_L) return fail(h, IPM_ERR_STATE, "%s: LP free columns beside a quadratic term, free columns with curvature or the infeasibility tests: no kernel serves that class", who);
+    return fail(h, IPM_ERR_STATE, "%s: free columns without a quadratic term: no kernel serves that class", who);
 }
 
 // A handle at a step, as a source of kernel arguments (vector_ops.h: Pick): each argument group by its type, int = the step's corr.
@@ -497,6 +508,7 @@ template <> struct Pick<BndArgs, StepSrc> { static BndArgs of(const StepSrc& s) 
 template <> struct Pick<DetArgs, StepSrc> { static DetArgs of(const StepSrc& s) { return det_args(s.h); } };
 template <> struct Pick<const double*, StepSrc> { static const double* of(const StepSrc& s) { return s.h->quad_g; } };
 template <> struct Pick<FreeArgs, StepSrc> { static FreeArgs of(const StepSrc& s) { return free_args(s.h); } };
+template <> struct Pick<FreeLpArgs, StepSrc> { static FreeLpArgs of(const StepSrc& s) { return free_lp_args(s.h); } };
 template <> struct Pick<int, StepSrc> { static int of(const StepSrc& s) { return s.corr; } };
 // ... and the argument structs of the vector steps' lockstep twins (lockstep.h)
 inline LsVecA::LsVecA(ipm_handle* h, int corr_) : a(vec_args(h)), corr(corr_) {}

@@ -428,6 +428,8 @@ extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, do
 extern "C" int ipm_set_centrality_correctors(ipm_handle* h, int32_t k) {
     if (h && h->quad && k > 0 && k <= MCC_KIND.kmax)           // (behind the range check, which reads nothing of the handle)
         return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_centrality_correctors: the handle holds a quadratic term (ipm_set_quadratic): it takes one step length, and the rounds' accept rule compares step pairs");
+    if (h && h->free_lp_on && k > 0 && k <= MCC_KIND.kmax)
+        return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_centrality_correctors: the handle holds LP free columns (ipm_set_free_lp_columns): the rounds' kernels are not restated for them");
     return rounds_set(h, &ipm_handle::mcc, MCC_KIND, k);
 }
 extern "C" int ipm_get_corrector_info(ipm_handle* h, int64_t out[4]) {

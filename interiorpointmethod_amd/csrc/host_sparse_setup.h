@@ -500,7 +500,7 @@ extern "C" int ipm_set_A_csc(ipm_handle* h, const int32_t* colptr, const int32_t
             // (a handle that holds a quadratic term takes it only with IPM_FLAG_SMALL_QUADRATIC: the Quad variants of the loop,
             //  ipm_set_quadratic; one that holds free columns only with IPM_FLAG_SMALL_FREE on top: the Free variants, ipm_set_free_columns)
             const bool want_small = h->fused_small && h->m <= SMALL_MAX_M && terms <= ((size_t)1 << 22) && (!h->quad || (h->opt.flags & IPM_FLAG_SMALL_QUADRATIC)) &&
-                                    (!h->free_on || (h->opt.flags & IPM_FLAG_SMALL_FREE));
+                                    (!h->free_on || (h->opt.flags & IPM_FLAG_SMALL_FREE)) && !h->free_lp_on;      // (an LP free set: the multi-kernel path)
             // (measured, ms per iteration list / row-owner: SHELL (8 blocks) 0.778 / 0.810, DEGEN3 (12) 1.13 / 1.12, PILOT87 (30)
             //  2.44 / 2.38: the zero fill of B eats the gain from 16 blocks on)
             const bool want_list = h->list_form_opt && h->m > SMALL_MAX_M && h->mp <= 1536 && terms <= ((size_t)1 << 24);

@@ -338,7 +338,7 @@ extern "C" int ipm_destroy(ipm_handle* h) {
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->h_sc) { std::lock_guard<std::mutex> lock(g_hsc_mutex); g_hsc_pool.push_back(h->h_sc); h->h_sc = nullptr; }
-    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->quad_g, (void*)h->free_mark, (void*)h->mcc.mem, (void*)h->ref.mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
+    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->quad_g, (void*)h->free_mark, (void*)h->free_lp_mark, (void*)h->mcc.mem, (void*)h->ref.mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
         dev_free(h->device, h->stream, p);
     ff_release(h);
     free_sparse_factor(h);
@@ -392,12 +392,14 @@ extern "C" int ipm_set_bc(ipm_handle* h, const double* b, const double* c) {
 
 // free columns (ipm_set_free_columns) hold no s: every seam that writes a state zeroes it there
 static int enqueue_free_zero_s(ipm_handle* h) {
-    if (!h->free_on) return IPM_OK;
-    hipLaunchKernelGGL(free_zero_s_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, (const unsigned char*)h->free_mark, h->s, (int)h->n);
+    if (!h->free_on && !h->free_lp_on) return IPM_OK;            // (never both: the setters refuse the pair)
+    hipLaunchKernelGGL(free_zero_s_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream,
+                       (const unsigned char*)(h->free_on ? h->free_mark : h->free_lp_mark), h->s, (int)h->n);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
 static bool free_is(const ipm_handle* h, int64_t j) { return h->free_on && h->free_host[(size_t)j] != 0; }
+static bool free_lp_is(const ipm_handle* h, int64_t j) { return h->free_lp_on && h->free_lp_host[(size_t)j] != 0; }
 
 extern "C" int ipm_set_state(ipm_handle* h, const double* x, const double* y, const double* s) {
     if (!h || !x || !y || !s) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_state: bad arguments");
@@ -437,6 +439,8 @@ extern "C" int ipm_set_bounds(ipm_handle* h, const double* u) {
             if (v < std::numeric_limits<double>::infinity()) {
                 if (free_is(h, j))
                     return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_bounds: u[%lld] = %g is finite, but column %lld is a free column (ipm_set_free_columns): it takes no bound", (long long)j, v, (long long)j);
+                if (free_lp_is(h, j))
+                    return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_bounds: u[%lld] = %g is finite, but column %lld is an LP free column (ipm_set_free_lp_columns): it takes no bound", (long long)j, v, (long long)j);
                 ++nU;
             }
         }
@@ -494,6 +498,7 @@ extern "C" int ipm_set_quadratic(ipm_handle* h, const double* g) {
         h->quad = false; h->quad_nnz = 0; h->predictor_valid = false; h->quad_pos.clear();
         return IPM_OK;
     }
+    if (h->free_lp_on) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle holds LP free columns (ipm_set_free_lp_columns): they live on a handle without a quadratic term; clear that set first");
     if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle was created with IPM_FLAG_LOCKSTEP (the Quad kernels have no batched twins)");
     if (h->detect && !h->detect_qp) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the dual ray of a QP also needs g o x = 0; the tests are not restated)");
     if (h->mcc.k > 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: %d centrality correctors are set (their accept rule compares step pairs, a quadratic handle takes one step; ipm_set_centrality_correctors(h, 0))", h->mcc.k);
@@ -537,6 +542,7 @@ extern "C" int ipm_set_free_columns(ipm_handle* h, const int32_t* idx, int32_t c
         h->free_cols.clear(); h->free_host.clear(); h->free_on = false; h->predictor_valid = false;
         return IPM_OK;
     }
+    if (h->free_lp_on) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle holds LP free columns (ipm_set_free_lp_columns): the two sets do not share a handle; clear that set first");
     if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle was created with IPM_FLAG_LOCKSTEP (the Free kernels have no batched twins)");
     if (h->detect && !h->detect_qp) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the tests are the LP's and are not restated)");
     if (h->small && !(h->opt.flags & IPM_FLAG_SMALL_FREE)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle runs the fused small kernel, which has no free columns; set them before A (ipm_set_A_csc then takes the multi-kernel path)");
@@ -569,6 +575,56 @@ extern "C" int ipm_get_free_columns(ipm_handle* h, int32_t* idx, int32_t cap, in
     const int32_t k = (int32_t)h->free_cols.size();
     if (count) *count = k;
     for (int32_t t = 0; t < k && t < cap; ++t) idx[t] = h->free_cols[(size_t)t];
+    return IPM_OK;
+}
+
+// LP free columns: columns without a quadratic term and without a sign constraint, served by proximal-point
+// regularisation of the free block (iteration_rules.h: free_lp_*).  The marks are the library's own allocation of np bytes, made on
+// first use and kept (clearing only switches the free_lp kernels off); the whole vector is written.
+extern "C" int ipm_set_free_lp_columns(ipm_handle* h, const int32_t* idx, int32_t count, double rho) {
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: NULL handle");
+    if (count < 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: count = %d", (int)count);
+    if (count == 0 || !idx) {                                  // cleared: the LP code, exactly
+        h->free_lp_cols.clear(); h->free_lp_host.clear(); h->free_lp_on = false; h->predictor_valid = false;
+        return IPM_OK;
+    }
+    if (!std::isfinite(rho)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: rho = %g is not finite", rho);
+    if (!(rho > 0.0)) rho = IPM_FREE_LP_RHO_DEFAULT;
+    if (h->quad) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: the handle holds a quadratic term (ipm_set_quadratic): LP free columns live on a handle without one (a free column with g > 0 is ipm_set_free_columns)");
+    if (h->free_on) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: the handle holds free columns with curvature (ipm_set_free_columns): the two sets do not share a handle");
+    if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: the handle was created with IPM_FLAG_LOCKSTEP (the free_lp kernels have no batched twins)");
+    if (h->detect) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the tests are not restated for LP free columns)");
+    if (h->mcc.k > 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: %d centrality correctors are set (their kernels are not restated for LP free columns; ipm_set_centrality_correctors(h, 0))", h->mcc.k);
+    if (h->small) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: the handle runs the fused small kernel, which has no LP free columns; set them before A (ipm_set_A_csc then takes the multi-kernel path)");
+    std::vector<char> seen((size_t)h->n, 0);
+    for (int32_t t = 0; t < count; ++t) {
+        const int32_t j = idx[t];
+        if (j < 0 || j >= h->n) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: column index %d out of range", (int)j);
+        if (seen[(size_t)j]) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: column index %d is duplicated", (int)j);
+        seen[(size_t)j] = 1;
+        if (h->bnd && h->bnd_finite[(size_t)j]) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: column %d has a finite upper bound (ipm_set_bounds): a free column takes none", (int)j);
+    }
+    if ((int64_t)count >= h->n) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: all %d columns free leaves no complementarity pair (mu would be 0/0)", (int)count);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t np = (size_t)h->np;
+    if (!h->free_lp_mark && dev_malloc(h->device, h->stream, (void**)&h->free_lp_mark, np) != hipSuccess)
+        return fail(h, IPM_ERR_HIP, "ipm_set_free_lp_columns: %lld bytes could not be allocated", (long long)np);
+    std::vector<unsigned char> mk(np, 0);
+    for (int32_t t = 0; t < count; ++t) mk[(size_t)idx[t]] = 1;
+    HIP_TRY(h, hipMemcpyAsync(h->free_lp_mark, mk.data(), np, hipMemcpyHostToDevice, h->stream));
+    h->free_lp_cols.assign(idx, idx + count); h->free_lp_host.swap(seen); h->free_lp_on = true; h->free_lp_rho = rho; h->predictor_valid = false;
+    if (int rc_ = enqueue_free_zero_s(h)) return rc_;              // a state the handle holds loses s on the new free columns
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return IPM_OK;
+}
+
+extern "C" int ipm_get_free_lp_columns(ipm_handle* h, int32_t* idx, int32_t cap, int32_t* count, double* rho) {
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_free_lp_columns: NULL handle");
+    if (cap < 0 || (cap > 0 && !idx)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_free_lp_columns: bad arguments");
+    const int32_t k = (int32_t)h->free_lp_cols.size();
+    if (count) *count = k;
+    if (rho) *rho = h->free_lp_rho;
+    for (int32_t t = 0; t < k && t < cap; ++t) idx[t] = h->free_lp_cols[(size_t)t];
     return IPM_OK;
 }
 
@@ -748,15 +804,25 @@ extern "C" int ipm_debug_chol_plan(int32_t nblk, int64_t m, const int32_t knobs[
     return IPM_OK;
 }
 
-// The variant tables, read back (host only; tests/test_step_dispatch_host.py): the row that serves a class at a step.
+// The variant tables, read back (host only; tests/test_step_dispatch_host.py, tests/test_free_lp_host.py): the row that serves a
+// class at a step.  ipm_debug_step_kernel is the four-switch entry, ipm_debug_step_kernel_ex adds the fifth (LP free columns).
+static int debug_step_kernel(const char* who, int32_t step, unsigned bits, char* name_out, int32_t capacity, int32_t* twin_type_out);
 extern "C" int ipm_debug_step_kernel(int32_t step, int32_t bounded, int32_t detect, int32_t quad, int32_t free_cols, char* name_out, int32_t capacity,
                                      int32_t* twin_type_out) {
+    return debug_step_kernel("ipm_debug_step_kernel", step, variant_bits(StepVariant{bounded != 0, detect != 0, quad != 0, free_cols != 0}), name_out, capacity, twin_type_out);
+}
+extern "C" int ipm_debug_step_kernel_ex(int32_t step, int32_t bounded, int32_t detect, int32_t quad, int32_t free_cols, int32_t free_lp, char* name_out,
+                                        int32_t capacity, int32_t* twin_type_out) {
+    return debug_step_kernel("ipm_debug_step_kernel_ex", step, variant_bits(StepVariant{bounded != 0, detect != 0, quad != 0, free_cols != 0, free_lp != 0}), name_out, capacity, twin_type_out);
+}
+static int debug_step_kernel(const char* who, int32_t step, unsigned bits, char* name_out, int32_t capacity, int32_t* twin_type_out) {
     static const StepTable* const steps[] = {&STEP_PREPARE, &STEP_STOP_TEST, &STEP_SCALING, &STEP_DIRECTION, &STEP_MU_AFF, &STEP_CORRECTOR_RHS, &STEP_UPDATE};
     static const StepTable* const starts[] = {&STEP_START_PRIMAL, &STEP_START_DUAL, &STEP_START_SHIFT, &STEP_START_PRIMAL_CORRECT, &STEP_START_DUAL_CORRECT};
     static_assert(sizeof steps / sizeof *steps == IPM_STEP_SMALL && IPM_STEP_START_PRIMAL + sizeof starts / sizeof *starts == IPM_STEP_COUNT, "the step ids of ipm_hip.h");
-    const unsigned bits = variant_bits(StepVariant{bounded != 0, detect != 0, quad != 0, free_cols != 0});
-    if (step < 0 || step >= IPM_STEP_COUNT || capacity < 0 || (capacity > 0 && !name_out)) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_debug_step_kernel: bad arguments");
-    if (!variant_legal(bits)) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_debug_step_kernel: free columns without a quadratic term are no class (a free column needs g > 0)");
+    if (step < 0 || step >= IPM_STEP_COUNT || capacity < 0 || (capacity > 0 && !name_out)) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: bad arguments", who);
+    if (!variant_legal(bits & ~V_L)) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: free columns without a quadratic term are no class (a free column needs g > 0)", who);
+    if (!variant_legal(bits)) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: LP free columns beside a quadratic term, free columns with curvature or the infeasibility tests are no class", who);
+    if ((bits & V_L) && step >= IPM_STEP_SMALL && step < IPM_STEP_START_PRIMAL) return fail(nullptr, IPM_ERR_INVALID_ARG, "%s: the one-workgroup path serves no LP free columns", who);
     const char* name;
     int id;
     if (step >= IPM_STEP_SMALL && step < IPM_STEP_START_PRIMAL) {          // the one-workgroup path: the row's id is its SMALL_* value / bounded

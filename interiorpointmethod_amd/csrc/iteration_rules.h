@@ -132,6 +132,31 @@ __device__ __forceinline__ void free_direction_column(const Cols& a, int j, doub
 template <class Cols>
 __device__ __forceinline__ void free_update_column(const Cols& a, int j, double ap) { a.x[j] += ap * a.dx[j]; }
 
+// LP free columns (ipm_set_free_lp_columns): column j of an LP handle -- no quadratic term anywhere -- that carries no
+// sign constraint.  It has no curvature of its own, so the Newton matrix borrows one: proximal-point primal regularisation of the
+// free block only (Altman and Gondzio, Optim. Methods Softw. 11 (1999) 275-302).  At iteration k the free block of the objective
+// carries 1/2 rho |x_Phi - x_Phi^k|^2, centred AT the iterate: its gradient there is zero, so r_c, the objective and the stop test
+// are the true LP's; only the matrix sees rho, as Theta_j = 1 / rho.  Nothing is subtracted anywhere.  The rows that differ from
+// an LP column, each stated once; the byte marks are FreeArgs, rho is the handle's one scalar (in the handle's units):
+//   dual residual  r_c = (A^T y)_j - c_j                              (free_lp_rc: no s, no g x)
+//   scaling        d = 1 / rho                                        (free_lp_theta: scaling_kernel and prepare_kernel write it
+//                                                                      concurrently: one expression)
+//   predictor      q = 0, v = d r_c                                   (free_rhs_column as it is; the corrector's column alike)
+//   objective      c_j x_j
+//   recovery       dx = d w + v, ds = 0 (dw = dz = 0)                 (free_direction_column as it is)
+//   ratio tests, mu, mu_aff, sigma: no term; free_pair_count pairs
+//   step lengths   the LP's two, alpha_p and alpha_d (never quad_step); x += alpha_p dx, s stays 0 (free_update_column)
+//   stop test      r_c of the column counts in ||r_c||; nothing into the gap
+// Row j of the Newton system is A^T dy - rho dx = -r_c: an inexact Newton step whose dual residual on the column after a step of
+// length alpha_d is (1 - alpha_d) r_c + alpha_d rho dx_j, which vanishes with dx.
+// The start (start_free_lp_*): x_j is the least-squares value, unshifted and uncorrected; s_j = 0; no term in a minimum or a sum.
+struct FreeLpArgs {
+    FreeArgs cols;                 // the marks and their count
+    double rho;
+};
+__device__ __forceinline__ double free_lp_rc(double aty, double c) { return aty - c; }
+__device__ __forceinline__ double free_lp_theta(double rho) { return 1.0 / rho; }
+
 // Infeasibility tests of IPM_FLAG_DETECT_INFEASIBILITY, on the iterate of a stop test that said "continue":
 //   primal infeasible: beta = b.y - u_U.z_U > 0 and max_j (A^T y - z)_j+ <= eps_p beta   (certificate y / beta, z / beta)
 //   dual infeasible:   gamma = -c.x > 0 and max(||A x||_inf, max x_U) <= eps_d gamma      (certificate x / gamma)
@@ -420,6 +445,25 @@ __device__ __forceinline__ void start_reference_column(const Cols& a, const BndA
         const double o = bnd_in(bd.u[j]) ? 1.0 : 0.0;
         bd.w[j] = o; bd.z[j] = o;
     }
+}
+
+// The same five steps on an LP free column (FreeLpArgs above): the least-squares x as computed, s = 0 (w = z = 0: the column is
+// outside U), and no term in any minimum or sum -- so the shift and both corrections pass it by.  On degenerate data the reference's
+// start as ipm_init_state leaves it on such a handle: x = 1, s = 0.
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void start_free_lp_primal_column(const Cols& a, const BndArgs& bd, int j, double xj) {
+    a.x[j] = xj;
+    if constexpr (Bounded) bd.w[j] = 0.0;
+}
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void start_free_lp_dual_column(const Cols& a, const BndArgs& bd, int j) {
+    a.s[j] = 0.0;
+    if constexpr (Bounded) bd.z[j] = 0.0;
+}
+template <bool Bounded, class Cols>
+__device__ __forceinline__ void start_free_lp_reference_column(const Cols& a, const BndArgs& bd, int j) {
+    a.x[j] = 1.0; a.s[j] = 0.0;
+    if constexpr (Bounded) { bd.w[j] = 0.0; bd.z[j] = 0.0; }
 }
 
 // end of an iteration -- one thread: the IterRec of iteration k into the ring, the step lengths, k += 1.  mu, sigma and the affine

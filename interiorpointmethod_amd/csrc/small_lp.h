@@ -516,7 +516,8 @@ template <int N> constexpr bool small_rows_ok(const SmallRow (&rows)[N], unsigne
     for (unsigned c = 0; c <= mask; ++c) if ((c & ~mask) == 0 && variant_legal(c) && small_row_of(rows, c) >= 0) ++n;
     return n == N && N == legal;
 }
-static_assert(small_rows_ok(SMALL_ROWS, V_ALL, SMALL_NVARIANTS), "SMALL_ROWS: one row per legal class, each at its SMALL_* id");
+// (the one-workgroup path serves no LP free set, V_L: ipm_set_free_lp_columns keeps such a handle on the multi-kernel path)
+static_assert(small_rows_ok(SMALL_ROWS, V_ALL & ~V_L, SMALL_NVARIANTS), "SMALL_ROWS: one row per legal class, each at its SMALL_* id");
 
 // start_solve(force = 0, reset = 1) for every item, as set_params_kernel does for one LP: one thread per item
 __global__ __launch_bounds__(256) void small_batch_params_kernel(const SmallItem* __restrict__ items, int n, double e1, double e2, double e3, int max_iter) {

@@ -154,7 +154,7 @@ struct VecArgs {
 };
 
 // ------------------------------------------------------------------------------- class variants (host side)
-// A handle's problem class is four switches, and every step of the iteration has one kernel per class it tells apart.  Which kernel
+// A handle's problem class is five switches, and every step of the iteration has one kernel per class it tells apart.  Which kernel
 // serves which class is stated ONCE per step, in a table directly below the step's __global__ wrappers (here and in small_lp.h):
 //     #define X_VARIANTS(U, T)  U(classes, kernel) ... T(classes, lockstep twin type) ...
 // a row names its kernel once, says which classes it serves (V_AT(switches), or-ed where it serves several), and is either an untwinned
@@ -163,12 +163,17 @@ struct VecArgs {
 // static_assert holds every table to "each legal class is served by exactly one row"; ipm_debug_step_kernel reads them back.
 struct StepVariant {
     bool bounded, detect, quad, free;      // ipm_set_bounds, IPM_FLAG_DETECT_INFEASIBILITY, ipm_set_quadratic, ipm_set_free_columns
+    bool free_lp = false;                  // ipm_set_free_lp_columns (the fifth switch, V_L)
 };
-enum : unsigned { V_B = 1, V_D = 2, V_Q = 4, V_F = 8, V_ALL = 15 };
-constexpr unsigned variant_bits(StepVariant v) { return (v.bounded ? V_B : 0u) | (v.detect ? V_D : 0u) | (v.quad ? V_Q : 0u) | (v.free ? V_F : 0u); }
+enum : unsigned { V_B = 1, V_D = 2, V_Q = 4, V_F = 8, V_L = 16, V_ALL = 31 };
+constexpr unsigned variant_bits(StepVariant v) {
+    return (v.bounded ? V_B : 0u) | (v.detect ? V_D : 0u) | (v.quad ? V_Q : 0u) | (v.free ? V_F : 0u) | (v.free_lp ? V_L : 0u);
+}
 // THE legality rule of a class: a free column needs curvature, so free implies quad (check_ready and the small batch's own check
-// refuse a handle in the other state before anything is launched)
-constexpr bool variant_legal(unsigned bits) { return !(bits & V_F) || (bits & V_Q); }
+// refuse a handle in the other state before anything is launched); an LP free column borrows its curvature from the proximal term
+// and lives on a plain or bounded LP handle only -- no quadratic term, no free columns with curvature, no infeasibility tests
+// (the setters refuse every such pair in both orders of the calls)
+constexpr bool variant_legal(unsigned bits) { return (!(bits & V_F) || (bits & V_Q)) && (!(bits & V_L) || !(bits & (V_D | V_Q | V_F))); }
 #define V_AT(bits) (1u << (bits))         // the one class with exactly these switches (after the step's mask), as a set
 
 // A kernel's arguments, bound by its parameter TYPES: Pick<P, Src>::of(src) is the argument of type P that a source of arguments
@@ -207,10 +212,13 @@ __device__ __forceinline__ double col_sum(const double* atp, int rc_chunks, int 
 // q = 0, v = d r_c, nothing into x.s -- one more streamed vector of bytes
 // Detect with Quad (IPM_FLAG_DETECT_QUADRATIC; iteration_rules.h states the tests): two more partials, P_CXL and P_MGX, from c, g and x
 // the column holds anyway, and |(A^T y)_j| of a free column into P_MATY -- still no extra pass over A
-template <bool Bounded = false, bool Detect = false, bool Quad = false, bool Free = false>
+// FreeLp (ipm_set_free_lp_columns; fr: the marks, rho: the handle's proximal weight): a marked column by the free_lp_* rules -- r_c
+// without s, d = 1 / rho, q = 0, v = d r_c, c x into the objective, nothing into x.s
+template <bool Bounded = false, bool Detect = false, bool Quad = false, bool Free = false, bool FreeLp = false>
 __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, const double* g = nullptr,
-                                                    FreeArgs fr = FreeArgs{}) {
+                                                    FreeArgs fr = FreeArgs{}, double rho = 0.0) {
     static_assert(!Free || Quad, "a free column needs curvature: Free is only meaningful with Quad");
+    static_assert(!FreeLp || (!Detect && !Quad && !Free), "an LP free column lives on a plain or bounded LP handle");
     __shared__ double red[VBLK];
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     double rc2 = 0.0, xs = 0.0, cx = 0.0, rb2 = 0.0;
@@ -218,6 +226,18 @@ __device__ __forceinline__ void prepare_kernel_body(VecArgs a, const unsigned bx
     double cxl = 0.0, mgx = 0.0;                                       // Detect with Quad only
     for (int j = gid; j < a.n; j += gsz) {
         double xj = a.x[j], sj = a.s[j];
+        if constexpr (FreeLp) {
+            if (free_in(fr, j)) {
+                const double rcj = free_lp_rc(col_sum(a.atp, a.rc_chunks, a.np, j), a.c[j]);
+                const double dj = free_lp_theta(rho);
+                a.rc[j] = rcj;
+                a.d[j] = dj;
+                free_rhs_column<Bounded>(a, bd, j, dj, rcj);
+                rc2 += rcj * rcj;
+                cx += a.c[j] * xj;
+                continue;
+            }
+        }
         if constexpr (Free) {
             if (free_in(fr, j)) {
                 const double gj = g[j];
@@ -312,6 +332,8 @@ __global__ __launch_bounds__(VBLK) void prepare_quad_detect_kernel(VecArgs a, co
 __global__ __launch_bounds__(VBLK) void prepare_bounded_quad_detect_kernel(VecArgs a, BndArgs bd, const double* g) { prepare_kernel_body<true, true, true>(a, blockIdx.x, gridDim.x, bd, g); }
 __global__ __launch_bounds__(VBLK) void prepare_free_detect_kernel(VecArgs a, const double* g, FreeArgs fr) { prepare_kernel_body<false, true, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, g, fr); }
 __global__ __launch_bounds__(VBLK) void prepare_bounded_free_detect_kernel(VecArgs a, BndArgs bd, const double* g, FreeArgs fr) { prepare_kernel_body<true, true, true, true>(a, blockIdx.x, gridDim.x, bd, g, fr); }
+__global__ __launch_bounds__(VBLK) void prepare_free_lp_kernel(VecArgs a, FreeLpArgs fl) { prepare_kernel_body<false, false, false, false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, nullptr, fl.cols, fl.rho); }
+__global__ __launch_bounds__(VBLK) void prepare_bounded_free_lp_kernel(VecArgs a, BndArgs bd, FreeLpArgs fl) { prepare_kernel_body<true, false, false, false, true>(a, blockIdx.x, gridDim.x, bd, nullptr, fl.cols, fl.rho); }
 constexpr unsigned PREPARE_FLAGS = V_ALL;
 #define PREPARE_VARIANTS(U, T)                                                    \
     T(V_AT(0), LS_PREPARE)                                                        \
@@ -325,18 +347,24 @@ constexpr unsigned PREPARE_FLAGS = V_ALL;
     U(V_AT(V_D | V_Q), prepare_quad_detect_kernel)                                \
     U(V_AT(V_B | V_D | V_Q), prepare_bounded_quad_detect_kernel)                  \
     U(V_AT(V_D | V_Q | V_F), prepare_free_detect_kernel)                          \
-    U(V_AT(V_B | V_D | V_Q | V_F), prepare_bounded_free_detect_kernel)
+    U(V_AT(V_B | V_D | V_Q | V_F), prepare_bounded_free_detect_kernel)            \
+    U(V_AT(V_L), prepare_free_lp_kernel)                                          \
+    U(V_AT(V_B | V_L), prepare_bounded_free_lp_kernel)
 
 // d = x / s only (main.py:223): what the formation of A D^2 A^T needs; the full prepare_kernel follows on the residual
 // stream while the factorization runs (host_iteration.h, enqueue_iteration).  Bounded: d = theta on U.  Quad: the quad_* scalings.
-// Free: d = free_theta on the marked columns.
-template <bool Bounded = false, bool Quad = false, bool Free = false>
-__device__ __forceinline__ void scaling_kernel_body(VecArgs a, BndArgs bd = BndArgs{}, const double* g = nullptr, FreeArgs fr = FreeArgs{}) {
+// Free: d = free_theta on the marked columns.  FreeLp: d = free_lp_theta there.
+template <bool Bounded = false, bool Quad = false, bool Free = false, bool FreeLp = false>
+__device__ __forceinline__ void scaling_kernel_body(VecArgs a, BndArgs bd = BndArgs{}, const double* g = nullptr, FreeArgs fr = FreeArgs{}, double rho = 0.0) {
     static_assert(!Free || Quad, "a free column needs curvature: Free is only meaningful with Quad");
+    static_assert(!FreeLp || (!Quad && !Free), "an LP free column lives on a plain or bounded LP handle");
     if (blockIdx.x == 0 && threadIdx.x == 0) a.sc->done_f = a.sc->done;      // latch for this iteration's factorization
     if (a.sc->done) return;
     const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
     for (int j = gid; j < a.n; j += gsz) {
+        if constexpr (FreeLp) {
+            if (free_in(fr, j)) { a.d[j] = free_lp_theta(rho); continue; }
+        }
         if constexpr (Free) {
             if (free_in(fr, j)) { a.d[j] = free_theta(g[j]); continue; }
         }
@@ -357,14 +385,18 @@ __global__ __launch_bounds__(VBLK) void scaling_quad_kernel(VecArgs a, const dou
 __global__ __launch_bounds__(VBLK) void scaling_bounded_quad_kernel(VecArgs a, BndArgs bd, const double* g) { scaling_kernel_body<true, true>(a, bd, g); }
 __global__ __launch_bounds__(VBLK) void scaling_free_kernel(VecArgs a, const double* g, FreeArgs fr) { scaling_kernel_body<false, true, true>(a, BndArgs{}, g, fr); }
 __global__ __launch_bounds__(VBLK) void scaling_bounded_free_kernel(VecArgs a, BndArgs bd, const double* g, FreeArgs fr) { scaling_kernel_body<true, true, true>(a, bd, g, fr); }
-constexpr unsigned SCALING_FLAGS = V_B | V_Q | V_F;      // (residual-stream iteration only, which is never recorded: launched directly)
+__global__ __launch_bounds__(VBLK) void scaling_free_lp_kernel(VecArgs a, FreeLpArgs fl) { scaling_kernel_body<false, false, false, true>(a, BndArgs{}, nullptr, fl.cols, fl.rho); }
+__global__ __launch_bounds__(VBLK) void scaling_bounded_free_lp_kernel(VecArgs a, BndArgs bd, FreeLpArgs fl) { scaling_kernel_body<true, false, false, true>(a, bd, nullptr, fl.cols, fl.rho); }
+constexpr unsigned SCALING_FLAGS = V_B | V_Q | V_F | V_L;      // (residual-stream iteration only, which is never recorded: launched directly)
 #define SCALING_VARIANTS(U, T)                                                    \
     U(V_AT(0), scaling_kernel)                                                    \
     U(V_AT(V_B), scaling_bounded_kernel)                                          \
     U(V_AT(V_Q), scaling_quad_kernel)                                             \
     U(V_AT(V_B | V_Q), scaling_bounded_quad_kernel)                               \
     U(V_AT(V_Q | V_F), scaling_free_kernel)                                       \
-    U(V_AT(V_B | V_Q | V_F), scaling_bounded_free_kernel)
+    U(V_AT(V_B | V_Q | V_F), scaling_bounded_free_kernel)                         \
+    U(V_AT(V_L), scaling_free_lp_kernel)                                          \
+    U(V_AT(V_B | V_L), scaling_bounded_free_lp_kernel)
 
 // stop test of check_optimality (main.py:162-173) -- one thread.
 // Bounded: ||r_b||^2 carries r_u^2 and the gap w.z (prepare_kernel), b_norm is ||(b, u_U)|| (ipm_set_bounds), mu divides by n + |U|.
@@ -418,6 +450,9 @@ __global__ void stop_test_quad_detect_kernel(VecArgs a, DetArgs dt) { stop_test_
 __global__ void stop_test_bounded_quad_detect_kernel(VecArgs a, BndArgs bd, DetArgs dt) { stop_test_kernel_body<true, true, false, true>(a, blockIdx.x, gridDim.x, bd, dt); }
 __global__ void stop_test_free_detect_kernel(VecArgs a, DetArgs dt, FreeArgs fr) { stop_test_kernel_body<false, true, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, dt, fr); }
 __global__ void stop_test_bounded_free_detect_kernel(VecArgs a, BndArgs bd, DetArgs dt, FreeArgs fr) { stop_test_kernel_body<true, true, true, true>(a, blockIdx.x, gridDim.x, bd, dt, fr); }
+// (an LP free column changes the pair count and nothing else the stop test reads: the Free body, from the LP free set's marks)
+__global__ void stop_test_free_lp_kernel(VecArgs a, FreeLpArgs fl) { stop_test_kernel_body<false, false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, DetArgs{}, fl.cols); }
+__global__ void stop_test_bounded_free_lp_kernel(VecArgs a, BndArgs bd, FreeLpArgs fl) { stop_test_kernel_body<true, false, true>(a, blockIdx.x, gridDim.x, bd, DetArgs{}, fl.cols); }
 // (the term alone changes nothing the stop test reads: without Detect a quadratic handle takes the LP's rows)
 constexpr unsigned STOP_TEST_FLAGS = V_ALL;
 #define STOP_TEST_VARIANTS(U, T)                                                  \
@@ -430,7 +465,9 @@ constexpr unsigned STOP_TEST_FLAGS = V_ALL;
     U(V_AT(V_D | V_Q), stop_test_quad_detect_kernel)                              \
     U(V_AT(V_B | V_D | V_Q), stop_test_bounded_quad_detect_kernel)                \
     U(V_AT(V_D | V_Q | V_F), stop_test_free_detect_kernel)                        \
-    U(V_AT(V_B | V_D | V_Q | V_F), stop_test_bounded_free_detect_kernel)
+    U(V_AT(V_B | V_D | V_Q | V_F), stop_test_bounded_free_detect_kernel)          \
+    U(V_AT(V_L), stop_test_free_lp_kernel)                                        \
+    U(V_AT(V_B | V_L), stop_test_bounded_free_lp_kernel)
 
 // The certificate of a detection (ipm_get_certificate): kind 5 -> (y / beta, z / beta), kind 6 -> x / gamma; the other parts 0.
 // out = [x (n) | y (m) | z (n)]; z = nullptr without bounds.
@@ -476,18 +513,24 @@ __global__ __launch_bounds__(VBLK) void direction_kernel(VecArgs a, int corr) { 
 __global__ __launch_bounds__(VBLK) void direction_bounded_kernel(VecArgs a, int corr, BndArgs bd) { direction_kernel_body<true>(a, corr, blockIdx.x, gridDim.x, bd); }
 __global__ __launch_bounds__(VBLK) void direction_free_kernel(VecArgs a, int corr, FreeArgs fr) { direction_kernel_body<false, true>(a, corr, blockIdx.x, gridDim.x, BndArgs{}, fr); }
 __global__ __launch_bounds__(VBLK) void direction_bounded_free_kernel(VecArgs a, int corr, BndArgs bd, FreeArgs fr) { direction_kernel_body<true, true>(a, corr, blockIdx.x, gridDim.x, bd, fr); }
-constexpr unsigned DIRECTION_FLAGS = V_B | V_F;
+// (an LP free column's recovery is free_direction_column too: the Free body, from the LP free set's marks)
+__global__ __launch_bounds__(VBLK) void direction_free_lp_kernel(VecArgs a, int corr, FreeLpArgs fl) { direction_kernel_body<false, true>(a, corr, blockIdx.x, gridDim.x, BndArgs{}, fl.cols); }
+__global__ __launch_bounds__(VBLK) void direction_bounded_free_lp_kernel(VecArgs a, int corr, BndArgs bd, FreeLpArgs fl) { direction_kernel_body<true, true>(a, corr, blockIdx.x, gridDim.x, bd, fl.cols); }
+constexpr unsigned DIRECTION_FLAGS = V_B | V_F | V_L;
 #define DIRECTION_VARIANTS(U, T)                                                  \
     T(V_AT(0), LS_DIRECTION)                                                      \
     T(V_AT(V_B), LS_DIRECTION_BND)                                                \
     U(V_AT(V_F), direction_free_kernel)                                           \
-    U(V_AT(V_B | V_F), direction_bounded_free_kernel)
+    U(V_AT(V_B | V_F), direction_bounded_free_kernel)                             \
+    U(V_AT(V_L), direction_free_lp_kernel)                                        \
+    U(V_AT(V_B | V_L), direction_bounded_free_lp_kernel)
 
 // partial sums of mu_aff_column at the affine step lengths (Quad: at the one step quad_step makes of them, which the stats report)
-// Free: no term of a marked column.
-template <bool Bounded = false, bool Quad = false, bool Free = false>
+// Free: no term of a marked column.  (An LP free column: Free without Quad -- the LP's two affine step lengths.)
+template <bool Bounded = false, bool Quad = false, bool Free = false, bool FreeLp = false>
 __device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, FreeArgs fr = FreeArgs{}) {
     static_assert(!Free || Quad, "a free column needs curvature: Free is only meaningful with Quad");
+    static_assert(!FreeLp || (!Quad && !Free), "an LP free column lives on a plain or bounded LP handle");
     if (a.sc->done) return;
     __shared__ double red[VBLK];
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
@@ -496,7 +539,7 @@ __device__ __forceinline__ void mu_aff_kernel_body(VecArgs a, const unsigned bx_
     if constexpr (Quad) ap = ad = quad_step(ap, ad);
     double acc = 0.0;
     for (int j = gid; j < a.n; j += gsz) {
-        if constexpr (Free) {
+        if constexpr (Free || FreeLp) {
             if (free_in(fr, j)) continue;
         }
         mu_aff_column<Bounded>(a, bd, j, ap, ad, acc);
@@ -513,14 +556,18 @@ __global__ __launch_bounds__(VBLK) void mu_aff_quad_kernel(VecArgs a) { mu_aff_k
 __global__ __launch_bounds__(VBLK) void mu_aff_bounded_quad_kernel(VecArgs a, BndArgs bd) { mu_aff_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd); }
 __global__ __launch_bounds__(VBLK) void mu_aff_free_kernel(VecArgs a, FreeArgs fr) { mu_aff_kernel_body<false, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, fr); }
 __global__ __launch_bounds__(VBLK) void mu_aff_bounded_free_kernel(VecArgs a, BndArgs bd, FreeArgs fr) { mu_aff_kernel_body<true, true, true>(a, blockIdx.x, gridDim.x, bd, fr); }
-constexpr unsigned MU_AFF_FLAGS = V_B | V_Q | V_F;
+__global__ __launch_bounds__(VBLK) void mu_aff_free_lp_kernel(VecArgs a, FreeLpArgs fl) { mu_aff_kernel_body<false, false, false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, fl.cols); }
+__global__ __launch_bounds__(VBLK) void mu_aff_bounded_free_lp_kernel(VecArgs a, BndArgs bd, FreeLpArgs fl) { mu_aff_kernel_body<true, false, false, true>(a, blockIdx.x, gridDim.x, bd, fl.cols); }
+constexpr unsigned MU_AFF_FLAGS = V_B | V_Q | V_F | V_L;
 #define MU_AFF_VARIANTS(U, T)                                                     \
     T(V_AT(0), LS_MU_AFF)                                                         \
     T(V_AT(V_B), LS_MU_AFF_BND)                                                   \
     U(V_AT(V_Q), mu_aff_quad_kernel)                                              \
     U(V_AT(V_B | V_Q), mu_aff_bounded_quad_kernel)                                \
     U(V_AT(V_Q | V_F), mu_aff_free_kernel)                                        \
-    U(V_AT(V_B | V_Q | V_F), mu_aff_bounded_free_kernel)
+    U(V_AT(V_B | V_Q | V_F), mu_aff_bounded_free_kernel)                          \
+    U(V_AT(V_L), mu_aff_free_lp_kernel)                                           \
+    U(V_AT(V_B | V_L), mu_aff_bounded_free_lp_kernel)
 
 // centring from the re-summed partials of mu_aff_kernel, then corrector_column
 // Free: the centring over free_pair_count pairs (centring with n - n_free columns), free_rhs_column on the marked columns.
@@ -543,18 +590,24 @@ __global__ __launch_bounds__(VBLK) void corrector_rhs_kernel(VecArgs a) { correc
 __global__ __launch_bounds__(VBLK) void corrector_rhs_bounded_kernel(VecArgs a, BndArgs bd) { corrector_rhs_kernel_body<true>(a, blockIdx.x, gridDim.x, bd); }
 __global__ __launch_bounds__(VBLK) void corrector_rhs_free_kernel(VecArgs a, FreeArgs fr) { corrector_rhs_kernel_body<false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, fr); }
 __global__ __launch_bounds__(VBLK) void corrector_rhs_bounded_free_kernel(VecArgs a, BndArgs bd, FreeArgs fr) { corrector_rhs_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd, fr); }
-constexpr unsigned CORRECTOR_RHS_FLAGS = V_B | V_F;
+// (an LP free column's corrector column is free_rhs_column over free_pair_count pairs too: the Free body, from the LP free set's marks)
+__global__ __launch_bounds__(VBLK) void corrector_rhs_free_lp_kernel(VecArgs a, FreeLpArgs fl) { corrector_rhs_kernel_body<false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, fl.cols); }
+__global__ __launch_bounds__(VBLK) void corrector_rhs_bounded_free_lp_kernel(VecArgs a, BndArgs bd, FreeLpArgs fl) { corrector_rhs_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd, fl.cols); }
+constexpr unsigned CORRECTOR_RHS_FLAGS = V_B | V_F | V_L;
 #define CORRECTOR_RHS_VARIANTS(U, T)                                              \
     T(V_AT(0), LS_CORR_RHS)                                                       \
     T(V_AT(V_B), LS_CORR_RHS_BND)                                                 \
     U(V_AT(V_F), corrector_rhs_free_kernel)                                       \
-    U(V_AT(V_B | V_F), corrector_rhs_bounded_free_kernel)
+    U(V_AT(V_B | V_F), corrector_rhs_bounded_free_kernel)                         \
+    U(V_AT(V_L), corrector_rhs_free_lp_kernel)                                    \
+    U(V_AT(V_B | V_L), corrector_rhs_bounded_free_lp_kernel)
 
 // damped_step from the re-summed ratio-test minima (Quad: quad_step of the pair), update_column, y += a_d dy, record_iteration
-// Free: free_update_column on the marked columns (s stays 0).
-template <bool Bounded = false, bool Quad = false, bool Free = false>
+// Free: free_update_column on the marked columns (s stays 0).  FreeLp: the same with the LP's own alpha_p (no quad_step).
+template <bool Bounded = false, bool Quad = false, bool Free = false, bool FreeLp = false>
 __device__ __forceinline__ void update_kernel_body(VecArgs a, const unsigned bx_, const unsigned gx_, BndArgs bd = BndArgs{}, FreeArgs fr = FreeArgs{}) {
     static_assert(!Free || Quad, "a free column needs curvature: Free is only meaningful with Quad");
+    static_assert(!FreeLp || (!Quad && !Free), "an LP free column lives on a plain or bounded LP handle");
     if (a.sc->done) return;
     const int gid = bx_ * VBLK + threadIdx.x, gsz = gx_ * VBLK;
     const double eta = a.sc->eta;
@@ -562,7 +615,7 @@ __device__ __forceinline__ void update_kernel_body(VecArgs a, const unsigned bx_
     double ad = damped_step(eta, min_partials(a.part, P_MIND, a.nblk));
     if constexpr (Quad) ap = ad = quad_step(ap, ad);
     for (int j = gid; j < a.n; j += gsz) {
-        if constexpr (Free) {
+        if constexpr (Free || FreeLp) {
             if (free_in(fr, j)) { free_update_column(a, j, ap); continue; }
         }
         update_column<Bounded>(a, bd, j, ap, ad);
@@ -580,14 +633,18 @@ __global__ __launch_bounds__(VBLK) void update_quad_kernel(VecArgs a) { update_k
 __global__ __launch_bounds__(VBLK) void update_bounded_quad_kernel(VecArgs a, BndArgs bd) { update_kernel_body<true, true>(a, blockIdx.x, gridDim.x, bd); }
 __global__ __launch_bounds__(VBLK) void update_free_kernel(VecArgs a, FreeArgs fr) { update_kernel_body<false, true, true>(a, blockIdx.x, gridDim.x, BndArgs{}, fr); }
 __global__ __launch_bounds__(VBLK) void update_bounded_free_kernel(VecArgs a, BndArgs bd, FreeArgs fr) { update_kernel_body<true, true, true>(a, blockIdx.x, gridDim.x, bd, fr); }
-constexpr unsigned UPDATE_FLAGS = V_B | V_Q | V_F;
+__global__ __launch_bounds__(VBLK) void update_free_lp_kernel(VecArgs a, FreeLpArgs fl) { update_kernel_body<false, false, false, true>(a, blockIdx.x, gridDim.x, BndArgs{}, fl.cols); }
+__global__ __launch_bounds__(VBLK) void update_bounded_free_lp_kernel(VecArgs a, BndArgs bd, FreeLpArgs fl) { update_kernel_body<true, false, false, true>(a, blockIdx.x, gridDim.x, bd, fl.cols); }
+constexpr unsigned UPDATE_FLAGS = V_B | V_Q | V_F | V_L;
 #define UPDATE_VARIANTS(U, T)                                                     \
     T(V_AT(0), LS_UPDATE)                                                         \
     T(V_AT(V_B), LS_UPDATE_BND)                                                   \
     U(V_AT(V_Q), update_quad_kernel)                                              \
     U(V_AT(V_B | V_Q), update_bounded_quad_kernel)                                \
     U(V_AT(V_Q | V_F), update_free_kernel)                                        \
-    U(V_AT(V_B | V_Q | V_F), update_bounded_free_kernel)
+    U(V_AT(V_B | V_Q | V_F), update_bounded_free_kernel)                          \
+    U(V_AT(V_L), update_free_lp_kernel)                                           \
+    U(V_AT(V_B | V_L), update_bounded_free_lp_kernel)
 
 // ---------------------------------------------------------------------------------------
 // Centrality correctors (iteration_rules.h: mcc_*): the three vector kernels of one round, enqueued K times between
@@ -710,13 +767,21 @@ __device__ __forceinline__ StartSums start_sums(const double* part, int nblk) {
 
 // finishes the A^T partials in col_sum's order.  Dual = false: x = A^T u (Bounded: w = u - x on U) and the partial minima of (x, w_U);
 // Dual = true: r = c - A^T y, s = r (Bounded, on U: s = max(r, 0), z = max(-r, 0)), the partial minima of (s, z_U), and y = dy
-template <bool Bounded, bool Dual>
-__device__ __forceinline__ void start_ls_kernel_body(VecArgs a, BndArgs bd = BndArgs{}) {
+// FreeLp: a marked column by the start_free_lp_* rules (no term in the minimum)
+template <bool Bounded, bool Dual, bool FreeLp = false>
+__device__ __forceinline__ void start_ls_kernel_body(VecArgs a, BndArgs bd = BndArgs{}, FreeArgs fr = FreeArgs{}) {
     __shared__ double red[VBLK];
     const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
     double mn = __builtin_inf();
     for (int j = gid; j < a.n; j += gsz) {
         const double t = col_sum(a.atp, a.rc_chunks, a.np, j);
+        if constexpr (FreeLp) {
+            if (free_in(fr, j)) {
+                if constexpr (Dual) start_free_lp_dual_column<Bounded>(a, bd, j);
+                else start_free_lp_primal_column<Bounded>(a, bd, j, t);
+                continue;
+            }
+        }
         if constexpr (Dual) start_dual_column<Bounded>(a, bd, j, a.c[j] - t, mn);
         else start_primal_column<Bounded>(a, bd, j, t, mn);
     }
@@ -728,16 +793,25 @@ __global__ __launch_bounds__(VBLK) void start_primal_kernel(VecArgs a) { start_l
 __global__ __launch_bounds__(VBLK) void start_primal_bounded_kernel(VecArgs a, BndArgs bd) { start_ls_kernel_body<true, false>(a, bd); }
 __global__ __launch_bounds__(VBLK) void start_dual_kernel(VecArgs a) { start_ls_kernel_body<false, true>(a); }
 __global__ __launch_bounds__(VBLK) void start_dual_bounded_kernel(VecArgs a, BndArgs bd) { start_ls_kernel_body<true, true>(a, bd); }
+__global__ __launch_bounds__(VBLK) void start_primal_free_lp_kernel(VecArgs a, FreeLpArgs fl) { start_ls_kernel_body<false, false, true>(a, BndArgs{}, fl.cols); }
+__global__ __launch_bounds__(VBLK) void start_primal_bounded_free_lp_kernel(VecArgs a, BndArgs bd, FreeLpArgs fl) { start_ls_kernel_body<true, false, true>(a, bd, fl.cols); }
+__global__ __launch_bounds__(VBLK) void start_dual_free_lp_kernel(VecArgs a, FreeLpArgs fl) { start_ls_kernel_body<false, true, true>(a, BndArgs{}, fl.cols); }
+__global__ __launch_bounds__(VBLK) void start_dual_bounded_free_lp_kernel(VecArgs a, BndArgs bd, FreeLpArgs fl) { start_ls_kernel_body<true, true, true>(a, bd, fl.cols); }
 
 // scalar phase 1: the shifts from the re-reduced minima, applied; partial sums of x.s + w.z, sum s + sum z_U, sum x + sum w_U
-template <bool Bounded>
-__device__ __forceinline__ void start_shift_kernel_body(VecArgs a, BndArgs bd = BndArgs{}) {
+template <bool Bounded, bool FreeLp = false>
+__device__ __forceinline__ void start_shift_kernel_body(VecArgs a, BndArgs bd = BndArgs{}, FreeArgs fr = FreeArgs{}) {
     __shared__ double red[VBLK];
     const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
     const double dp = start_shift(start_min_partials(a.part, PS_MIN_P, a.nblk));
     const double dd = start_shift(start_min_partials(a.part, PS_MIN_D, a.nblk));
     double xs = 0.0, ss = 0.0, sx = 0.0;
-    for (int j = gid; j < a.n; j += gsz) start_shift_column<Bounded>(a, bd, j, dp, dd, xs, ss, sx);
+    for (int j = gid; j < a.n; j += gsz) {
+        if constexpr (FreeLp) {
+            if (free_in(fr, j)) continue;
+        }
+        start_shift_column<Bounded>(a, bd, j, dp, dd, xs, ss, sx);
+    }
     xs = block_sum(xs, red); ss = block_sum(ss, red); sx = block_sum(sx, red);
     if (threadIdx.x == 0) {
         a.part[PS_XS * MAXPART + blockIdx.x] = xs;
@@ -747,46 +821,73 @@ __device__ __forceinline__ void start_shift_kernel_body(VecArgs a, BndArgs bd = 
 }
 __global__ __launch_bounds__(VBLK) void start_shift_kernel(VecArgs a) { start_shift_kernel_body<false>(a); }
 __global__ __launch_bounds__(VBLK) void start_shift_bounded_kernel(VecArgs a, BndArgs bd) { start_shift_kernel_body<true>(a, bd); }
+__global__ __launch_bounds__(VBLK) void start_shift_free_lp_kernel(VecArgs a, FreeLpArgs fl) { start_shift_kernel_body<false, true>(a, BndArgs{}, fl.cols); }
+__global__ __launch_bounds__(VBLK) void start_shift_bounded_free_lp_kernel(VecArgs a, BndArgs bd, FreeLpArgs fl) { start_shift_kernel_body<true, true>(a, bd, fl.cols); }
 
 // scalar phase 2: degenerate data -> the reference's start (x = s = 1, y = 1, w = z = 1 on U) and nothing else; otherwise the
 // primal correction x += xs / ss and the partial sums of sum x + sum w_U after it
-template <bool Bounded>
-__device__ __forceinline__ void start_primal_correct_kernel_body(VecArgs a, BndArgs bd = BndArgs{}) {
+template <bool Bounded, bool FreeLp = false>
+__device__ __forceinline__ void start_primal_correct_kernel_body(VecArgs a, BndArgs bd = BndArgs{}, FreeArgs fr = FreeArgs{}) {
     __shared__ double red[VBLK];
     const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
     const StartSums t = start_sums(a.part, a.nblk);
     if (start_degenerate(t.xs, t.ss, t.sx)) {                     // (the same decision in every thread of every block: all leave)
-        for (int j = gid; j < a.n; j += gsz) start_reference_column<Bounded>(a, bd, j);
+        for (int j = gid; j < a.n; j += gsz) {
+            if constexpr (FreeLp) {
+                if (free_in(fr, j)) { start_free_lp_reference_column<Bounded>(a, bd, j); continue; }
+            }
+            start_reference_column<Bounded>(a, bd, j);
+        }
         for (int i = gid; i < a.m; i += gsz) a.y[i] = 1.0;
         return;
     }
     const double pc = t.xs / t.ss;
     double sx = 0.0;
-    for (int j = gid; j < a.n; j += gsz) start_primal_correct_column<Bounded>(a, bd, j, pc, sx);
+    for (int j = gid; j < a.n; j += gsz) {
+        if constexpr (FreeLp) {
+            if (free_in(fr, j)) continue;
+        }
+        start_primal_correct_column<Bounded>(a, bd, j, pc, sx);
+    }
     sx = block_sum(sx, red);
     if (threadIdx.x == 0) a.part[PS_SX2 * MAXPART + blockIdx.x] = sx;
 }
 __global__ __launch_bounds__(VBLK) void start_primal_correct_kernel(VecArgs a) { start_primal_correct_kernel_body<false>(a); }
 __global__ __launch_bounds__(VBLK) void start_primal_correct_bounded_kernel(VecArgs a, BndArgs bd) { start_primal_correct_kernel_body<true>(a, bd); }
+__global__ __launch_bounds__(VBLK) void start_primal_correct_free_lp_kernel(VecArgs a, FreeLpArgs fl) { start_primal_correct_kernel_body<false, true>(a, BndArgs{}, fl.cols); }
+__global__ __launch_bounds__(VBLK) void start_primal_correct_bounded_free_lp_kernel(VecArgs a, BndArgs bd, FreeLpArgs fl) { start_primal_correct_kernel_body<true, true>(a, bd, fl.cols); }
 
 // scalar phase 3: the dual correction s += xs / (sum x + sum w_U); nothing on degenerate data (phase 2 wrote the reference's start)
-template <bool Bounded>
-__device__ __forceinline__ void start_dual_correct_kernel_body(VecArgs a, BndArgs bd = BndArgs{}) {
+template <bool Bounded, bool FreeLp = false>
+__device__ __forceinline__ void start_dual_correct_kernel_body(VecArgs a, BndArgs bd = BndArgs{}, FreeArgs fr = FreeArgs{}) {
     const int gid = blockIdx.x * VBLK + threadIdx.x, gsz = gridDim.x * VBLK;
     const StartSums t = start_sums(a.part, a.nblk);
     if (start_degenerate(t.xs, t.ss, t.sx)) return;
     const double dc = t.xs / sum_partials(a.part, PS_SX2, a.nblk);
-    for (int j = gid; j < a.n; j += gsz) start_dual_correct_column<Bounded>(a, bd, j, dc);
+    for (int j = gid; j < a.n; j += gsz) {
+        if constexpr (FreeLp) {
+            if (free_in(fr, j)) continue;
+        }
+        start_dual_correct_column<Bounded>(a, bd, j, dc);
+    }
 }
 __global__ __launch_bounds__(VBLK) void start_dual_correct_kernel(VecArgs a) { start_dual_correct_kernel_body<false>(a); }
 __global__ __launch_bounds__(VBLK) void start_dual_correct_bounded_kernel(VecArgs a, BndArgs bd) { start_dual_correct_kernel_body<true>(a, bd); }
-// The five steps of the start tell plain from bounded only (launched directly: the start is never part of a recorded program).
-constexpr unsigned START_FLAGS = V_B;
-#define START_PRIMAL_VARIANTS(U, T) U(V_AT(0), start_primal_kernel) U(V_AT(V_B), start_primal_bounded_kernel)
-#define START_DUAL_VARIANTS(U, T) U(V_AT(0), start_dual_kernel) U(V_AT(V_B), start_dual_bounded_kernel)
-#define START_SHIFT_VARIANTS(U, T) U(V_AT(0), start_shift_kernel) U(V_AT(V_B), start_shift_bounded_kernel)
-#define START_PRIMAL_CORRECT_VARIANTS(U, T) U(V_AT(0), start_primal_correct_kernel) U(V_AT(V_B), start_primal_correct_bounded_kernel)
-#define START_DUAL_CORRECT_VARIANTS(U, T) U(V_AT(0), start_dual_correct_kernel) U(V_AT(V_B), start_dual_correct_bounded_kernel)
+__global__ __launch_bounds__(VBLK) void start_dual_correct_free_lp_kernel(VecArgs a, FreeLpArgs fl) { start_dual_correct_kernel_body<false, true>(a, BndArgs{}, fl.cols); }
+__global__ __launch_bounds__(VBLK) void start_dual_correct_bounded_free_lp_kernel(VecArgs a, BndArgs bd, FreeLpArgs fl) { start_dual_correct_kernel_body<true, true>(a, bd, fl.cols); }
+// The five steps of the start tell plain from bounded, and an LP free set from none (launched directly: the start is never part of
+// a recorded program).
+constexpr unsigned START_FLAGS = V_B | V_L;
+#define START_PRIMAL_VARIANTS(U, T) U(V_AT(0), start_primal_kernel) U(V_AT(V_B), start_primal_bounded_kernel) \
+    U(V_AT(V_L), start_primal_free_lp_kernel) U(V_AT(V_B | V_L), start_primal_bounded_free_lp_kernel)
+#define START_DUAL_VARIANTS(U, T) U(V_AT(0), start_dual_kernel) U(V_AT(V_B), start_dual_bounded_kernel) \
+    U(V_AT(V_L), start_dual_free_lp_kernel) U(V_AT(V_B | V_L), start_dual_bounded_free_lp_kernel)
+#define START_SHIFT_VARIANTS(U, T) U(V_AT(0), start_shift_kernel) U(V_AT(V_B), start_shift_bounded_kernel) \
+    U(V_AT(V_L), start_shift_free_lp_kernel) U(V_AT(V_B | V_L), start_shift_bounded_free_lp_kernel)
+#define START_PRIMAL_CORRECT_VARIANTS(U, T) U(V_AT(0), start_primal_correct_kernel) U(V_AT(V_B), start_primal_correct_bounded_kernel) \
+    U(V_AT(V_L), start_primal_correct_free_lp_kernel) U(V_AT(V_B | V_L), start_primal_correct_bounded_free_lp_kernel)
+#define START_DUAL_CORRECT_VARIANTS(U, T) U(V_AT(0), start_dual_correct_kernel) U(V_AT(V_B), start_dual_correct_bounded_kernel) \
+    U(V_AT(V_L), start_dual_correct_free_lp_kernel) U(V_AT(V_B | V_L), start_dual_correct_bounded_free_lp_kernel)
 
 // out[i] = value for i < n (fill)
 __global__ void fill_kernel(double* out, int n, double value) {
@@ -821,7 +922,8 @@ __global__ void bnd_fill_kernel(const double* u, double* w, double* z, int n, do
     else if (!mask_only) { w[j] = value; z[j] = value; }
 }
 
-// s = 0 on the free columns (every seam that writes a state: ipm_init_state, ipm_set_state, ipm_set_free_columns)
+// s = 0 on the free columns (every seam that writes a state: ipm_init_state, ipm_set_state, ipm_set_free_columns; the LP free set of
+// ipm_set_free_lp_columns alike, from its own marks)
 __global__ void free_zero_s_kernel(const unsigned char* mark, double* s, int n) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n && mark[j]) s[j] = 0.0;

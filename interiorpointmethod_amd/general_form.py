@@ -7,7 +7,8 @@ Same names and argument meaning as the reference (payakorn/InteriorPointMethod):
     get_Abc(c, Aeq, beq, Aineq, bineq, lb, ub, options)   -> (A, b, c, bound)        main.py:818-965
     add_bound_into_matrix(A, b, c, bound)                 -> (A, b, c, (None, None), constant)   main.py:968-1060
     new_interior_sparse(c, Aeq, beq, Aineq, bineq, lb, ub, tol)  -> objective        main.py:1081-1245
-    native_form(c, Aeq, beq, Aineq, bineq, lb, ub)        -> NativeForm   (bounds="native": 0 <= x <= u in the Newton system)
+    native_form(c, Aeq, beq, Aineq, bineq, lb, ub)        -> NativeForm   (bounds="native": 0 <= x <= u in the Newton system;
+                                                                           free="native": free variables stay free columns)
     native_problem(c, Aeq, beq, Aineq, bineq, lb, ub)     -> ((A, b, c, u), NativeForm)   (one problem of batch.run_batch)
     create_problem_from_mps_matlab(name)                  -> (c, Aineq, bineq, Aeq, beq, lb, ub)  sparse_interior.py:290-314
 
@@ -141,19 +142,27 @@ class NativeForm:
     original objective = c^T x' + offset.  A is get_Abc's matrix (inequality slacks appended) without the columns of the
     fixed variables (lb == ub), b is shifted by the finite lower bounds (x = x' + lb), u = ub - lb (+inf where there is no
     upper bound, and for the slack columns).  keep: get_Abc columns that remain; fixed: those removed; lb0: lower bounds
-    of every get_Abc column; n: number of original variables."""
-    __slots__ = ("A", "b", "c", "u", "offset", "keep", "fixed", "lb0", "n")
+    of every get_Abc column; n: number of original variables.
+    With native_form(free="native"): free = the columns of A (positions in `keep` order) that are free variables (lb = -inf,
+    ub = +inf), kept unshifted -- what IpmSolver(free_lp=...) takes; sign = +1 per get_Abc column, -1 where a variable with
+    lb = -inf and a finite ub was substituted by x = ub - x' (its lb0 entry then holds ub, its column of A and its cost are negated,
+    and it is an ordinary barrier column).  Without the option free is empty and sign all ones."""
+    __slots__ = ("A", "b", "c", "u", "offset", "keep", "fixed", "lb0", "n", "free", "sign")
 
     def x_original(self, xn):
         """x' of the native problem -> x of the original variables (length n)."""
         x = self.lb0.copy()
-        x[self.keep] += np.asarray(xn, dtype=np.float64).reshape(-1)
+        x[self.keep] += self.sign[self.keep] * np.asarray(xn, dtype=np.float64).reshape(-1)
         return x[:self.n]
 
 
-def native_form(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None):
-    """General form -> NativeForm (host only).  ValueError for ub < lb or a -inf lower bound (free variables are not
-    supported)."""
+def native_form(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None, free="error"):
+    """General form -> NativeForm (host only).  ValueError for ub < lb, and with free="error" (the default) for a -inf lower
+    bound (free variables are not supported).  free="native": a variable with lb = -inf and ub = +inf stays an unshifted column,
+    reported in NativeForm.free (the LP free columns of IpmSolver(free_lp=...)); one with lb = -inf and a finite ub is
+    substituted by x = ub - x' and becomes a barrier column (NativeForm.sign)."""
+    if free not in ("error", "native"):
+        raise ValueError('free must be "error" or "native"')
     c0 = _vec(c)
     n = c0.shape[0]
     lb = np.zeros((n, 1)) if lb is None else _vec(lb, "lb", n)
@@ -162,43 +171,56 @@ def native_form(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None)
         raise ValueError("lb / ub have NaN entries")
     if (ub < lb).any():
         raise ValueError("ub < lb for %d variables (infeasible bounds)" % int((ub < lb).sum()))
-    if not np.all(lb > -np.inf):
+    if free == "error" and not np.all(lb > -np.inf):
         raise ValueError("there are -inf in lower bound (free variables are not supported)")
     A0, b0, cs, _ = get_Abc(c0, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=None, ub=None)
     A0 = sparse.csc_matrix(A0, dtype=np.float64)
     N = A0.shape[1]
-    lb0 = np.zeros(N); lb0[:n] = lb.ravel()
-    u0 = np.full(N, np.inf); u0[:n] = (ub - lb).ravel()
     cs = np.asarray(cs, dtype=np.float64).ravel()
+    noLb = np.isneginf(lb.ravel())
+    isfree = noLb & np.isposinf(ub.ravel())          # stays free, unshifted
+    flip = noLb & ~isfree                            # (-inf, ub]: x = ub - x'
+    sign = np.ones(N)
+    lb0 = np.zeros(N); lb0[:n] = np.where(isfree, 0.0, np.where(flip, ub.ravel(), lb.ravel()))
+    u0 = np.full(N, np.inf); u0[:n] = np.where(noLb, np.inf, (ub - lb).ravel())
     b = np.asarray(b0, dtype=np.float64).ravel() - np.asarray(A0 @ lb0).ravel()
+    if flip.any():                                   # (behind the shift of b, which takes a_j ub with the original column)
+        sign[:n][flip] = -1.0
+        A0 = sparse.csc_matrix(A0 @ sparse.diags(sign))
     fixed = np.nonzero(u0 == 0.0)[0]
     keep = np.nonzero(u0 != 0.0)[0]
     F = NativeForm()
     F.A = sparse.csc_matrix(A0[:, keep])
-    F.b, F.c, F.u = b.reshape(-1, 1), cs[keep].reshape(-1, 1), u0[keep]
+    F.b, F.c, F.u = b.reshape(-1, 1), (sign * cs)[keep].reshape(-1, 1), u0[keep]
     F.offset = float(cs @ lb0)
     F.keep, F.fixed, F.lb0, F.n = keep, fixed, lb0, n
+    isfree0 = np.zeros(N, dtype=bool); isfree0[:n] = isfree
+    F.free, F.sign = np.flatnonzero(isfree0[keep]).astype(np.int32), sign
     return F
 
 
-def native_problem(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None):
+def native_problem(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None, free="error"):
     """native_form's arguments -> ((A, b, c, u), NativeForm): the general-form problem as ONE problem of the batched-LP mode
     (batch.run_batch and its front ends take (A, b, c, ub) tuples), and the form whose `offset` maps a record's objective back:
-    original objective = record objective + NativeForm.offset."""
-    F = native_form(c, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=lb, ub=ub)
+    original objective = record objective + NativeForm.offset.  free: as native_form; a problem that then has free columns is a
+    ValueError -- the batch tuples have no slot for them."""
+    F = native_form(c, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=lb, ub=ub, free=free)
+    if F.free.size:
+        raise ValueError("native_problem: the problem has %d free variables (first: column %d); a batch problem is an (A, b, c, ub) tuple with no slot for free columns -- solve it with new_interior_sparse(bounds=\"native\", free=\"native\")" % (F.free.size, int(F.keep[F.free[0]])))
     return (F.A, F.b, F.c, F.u), F
 
 
-def _ray_native(F, v):
-    """A vector over the columns of a NativeForm -> over the get_Abc columns (0 at the removed fixed columns); no lb shift."""
+def _ray_native(F, v, primal=False):
+    """A vector over the columns of a NativeForm -> over the get_Abc columns (0 at the removed fixed columns); no lb shift.
+    primal: a direction in x, which changes sign on the substituted columns (NativeForm.sign)."""
     out = np.zeros(F.lb0.shape[0])
     out[F.keep] = np.asarray(v, dtype=np.float64).reshape(-1)
-    return out
+    return out * F.sign if primal else out
 
 
 def new_interior_sparse(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, ub=None, tol=1e-20, device=0,
                         return_info=False, start="reference", bounds="fold", detect_infeasibility=False, scale=None, scale_passes=_solver.SCALE_PASSES,
-                        correctors=0, refine=0, dense_cols=None):
+                        correctors=0, refine=0, dense_cols=None, free="error", free_rho=None):
     """Drop-in for main.py:1081-1245: convert to standard form, run the predictor-corrector loop on the GPU
     (e1 = e2 = tol, e3 = 1e-6, at most 999 iterations, x = y = s = 1), return the objective.
     bounds="fold" (default, the reference's way): every finite upper bound becomes a row and a slack column of A.
@@ -212,20 +234,29 @@ def new_interior_sparse(c, Aeq=None, beq=None, Aineq=None, bineq=None, lb=None, 
     correctors=K: centrality-corrector rounds, as solve_with_info (0, the default: none).
     refine=k: refinement rounds behind every normal-equations solve, as solve_with_info (0, the default: none).
     dense_cols: the dense-column split on the standard-form LP that is solved ("auto", or indices into ITS columns), as
-    solve_with_info (None, the default: none)."""
+    solve_with_info (None, the default: none).
+    free="native" (with bounds="native" only; "error", the default, keeps the ValueError for a -inf lower bound): free variables
+    are served natively -- native_form(free="native") keeps them as LP free columns (solve_with_info(free_lp=..., free_rho=...);
+    DESIGN.md 4-W) and substitutes x = ub - x' for a variable with only an upper bound; info["free_lp"] = their count, info["x"]
+    the original variables."""
     if bounds not in ("fold", "native"):
         raise ValueError('bounds must be "fold" or "native"')
+    if free not in ("error", "native"):
+        raise ValueError('free must be "error" or "native"')
+    if free == "native" and bounds == "fold":
+        raise ValueError('free="native" needs bounds="native": the folded standard form has no free columns (its lower-bound shift needs a finite lb)')
     if bounds == "native":
-        F = native_form(c, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=lb, ub=ub)
+        F = native_form(c, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=lb, ub=ub, free=free)
         x, _, _, info = _solver.solve_with_info(F.A, F.b, F.c, tol=tol, tol_gap=1e-6, max_iter=999, y0=1.0, device=device,
                                                 start=start, ub=F.u, detect_infeasibility=detect_infeasibility, scale=scale,
-                                                scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols)
+                                                scale_passes=scale_passes, correctors=correctors, refine=refine, dense_cols=dense_cols,
+                                                **(dict(free_lp=F.free, free_rho=free_rho) if F.free.size else {}))
         info["fixed_removed"] = int(F.fixed.size)
         info["x"] = F.x_original(x)
         offset = F.offset
         cert = info.get("certificate")
         if cert is not None:
-            cert["x"], cert["z"] = _ray_native(F, cert["x"]), _ray_native(F, cert["z"])
+            cert["x"], cert["z"] = _ray_native(F, cert["x"], primal=True), _ray_native(F, cert["z"])
             cert["x_original"] = cert["x"][:F.n].copy()
     else:
         A, b, cs, offset = standard_form(c, Aeq=Aeq, beq=beq, Aineq=Aineq, bineq=bineq, lb=lb, ub=ub)

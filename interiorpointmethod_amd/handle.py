@@ -162,6 +162,43 @@ def refuse_free(free, who, why):
         raise ValueError("free: %s takes no free columns (%s)" % (who, why))
 
 
+def check_free_rho(free_rho):
+    """THE check of the `free_rho` keyword: None or a value <= 0 -> 0.0 (the library's default, IPM_FREE_LP_RHO_DEFAULT), a positive
+    finite number -> that float; NaN and Inf are a ValueError."""
+    if free_rho is None:
+        return 0.0
+    rho = float(free_rho)
+    if not np.isfinite(rho):
+        raise ValueError("free_rho = %r is not finite (one positive finite number per solver; None or <= 0: the default %g)" % (free_rho, _lib.FREE_LP_RHO_DEFAULT))
+    return rho if rho > 0 else 0.0
+
+
+def check_free_lp(free_lp, n, ub=None, quad=None, free=None):
+    """THE check of the `free_lp` keyword, before any device is touched: None (no LP free column, the default), a sequence of distinct
+    column indices 0 .. n-1 or a boolean mask of length n -> None (also for an empty set) or a fresh int32 array, as check_free
+    returns it.  An LP free column carries no sign constraint, no bound and no quadratic term: ub (None: no bounds) must be +inf
+    there, the problem must have no quadratic term (quad) and no free columns with curvature (free), and one column at least must
+    keep its complementarity pair.  Every violation is a ValueError naming the column."""
+    try:
+        idx = check_free(free_lp, n, None, ub, term_known=False)
+    except ValueError as e:
+        raise ValueError(str(e).replace("free:", "free_lp:", 1).replace("free must", "free_lp must", 1)) from None
+    if idx is None:
+        return None
+    if quad is not None and np.any(np.asarray(quad, dtype=np.float64) > 0):
+        raise ValueError("free_lp: column %d is an LP free column, but the problem has a quadratic term (quad): a free column with curvature is `free`" % int(idx[0]))
+    if _free_count(free):
+        raise ValueError("free_lp: column %d is an LP free column, but the problem has free columns with curvature (free): the two sets do not share a solver" % int(idx[0]))
+    return idx
+
+
+def refuse_free_lp(free_lp, who, why):
+    """THE refusal of what has no LP free columns (the batch front ends, and lockstep / detect_infeasibility / correctors on
+    IpmSolver): a non-empty set raises instead of being dropped."""
+    if _free_count(free_lp):
+        raise ValueError("free_lp: %s takes no LP free columns (%s)" % (who, why))
+
+
 def check_detect_qp(detect_qp, quad):
     """THE check of the `detect_qp` keyword, before any device is touched: detect_qp=True asks for the infeasibility tests of a
     QUADRATIC problem (IPM_FLAG_DETECT_INFEASIBILITY | IPM_FLAG_DETECT_QUADRATIC) and needs a quadratic term (quad as
@@ -191,8 +228,8 @@ class IpmSolver:
                  check_every=4, use_torch=True, dense=False, regularize=0.0, reorder="auto", concurrent=False,
                  auto_regularize=True, factor=None, prepared=None, lockstep=False, ub=None, detect_infeasibility=False,
                  infeasibility_tol=(1e-8, 1e-8), scale=None, scale_passes=SCALE_PASSES, correctors=0, refine=0, dense_cols=None, quad=None,
-                 quad_small=False, free=None, lockstep_bounds=False, detect_qp=False, free_small=False):
-        # (detect_qp stands IN FRONT of free_small, which an existing test pins as the last parameter: pass both by keyword)
+                 quad_small=False, free=None, lockstep_bounds=False, detect_qp=False, free_lp=None, free_rho=None, free_small=False):
+        # (detect_qp, free_lp and free_rho stand IN FRONT of free_small, which an existing test pins as the last parameter: pass them by keyword)
         """check_every: solve() enqueues that many iterations at a time and reads the stop flag once per chunk (the launches behind a
         satisfied stop test return at entry, so the result does not depend on it: DESIGN.md 4-A); a lockstep batch runs chunks of the
         largest value among its members.  IPM_CHECK_EVERY in the environment, when set and not empty, OVERRIDES this argument for
@@ -239,7 +276,14 @@ class IpmSolver:
         tests of a quadratic problem -- with quad (and free) the solve may end in status 5 / 6 with a certificate: a free column
         needs (A^T y)_j = 0, and a ray of unboundedness has -c.x > 0 for the LINEAR objective and avoids the curvature (g o x = 0).
         Implies detect_infeasibility=True (infeasibility_tol applies).  ValueError without a quadratic term and with lockstep=True;
-        every other refusal (correctors, init_state_mehrotra with free columns) stays."""
+        every other refusal (correctors, init_state_mehrotra with free columns) stays.
+        free_lp: None (default), a sequence of column indices or a boolean mask: the LP free columns (set_free_lp,
+        ipm_set_free_lp_columns) -- columns of an LP without a sign constraint, served by proximal-point
+        regularisation of the free block with the weight free_rho (None or <= 0: the library's default 1e-8; in the units of the
+        problem the device iterates on).  Checked on the host before any device is touched (check_free_lp: ValueError naming the
+        column) and set before A, so a small sparse problem takes the multi-kernel path.  quad, free, lockstep,
+        detect_infeasibility and correctors > 0 refuse a non-empty set (ValueError).  s is 0 on such a column in every state;
+        mehrotra_start / init_state_mehrotra serve the set."""
         self.scale = check_scale(scale)
         if lockstep_bounds and not lockstep:
             raise ValueError("lockstep_bounds=True needs lockstep=True: it opts a lockstep solver into the batch's bounded kernels")
@@ -249,6 +293,14 @@ class IpmSolver:
         n_cols = np.asarray(c).reshape(-1).shape[0] if prepared is None else prepared.n
         free = check_free(free, n_cols, quad, ub if prepared is None else getattr(prepared, "ub", None))
         detect_qp = check_detect_qp(detect_qp, quad)
+        free_lp = check_free_lp(free_lp, n_cols, ub if prepared is None else getattr(prepared, "ub", None), quad, free)
+        free_rho = check_free_rho(free_rho)
+        if lockstep:
+            refuse_free_lp(free_lp, "a lockstep solver", "the batch has no free_lp kernels; solve such problems one at a time")
+        if detect_infeasibility:
+            refuse_free_lp(free_lp, "detect_infeasibility=True", "the infeasibility tests are not restated for LP free columns")
+        if correctors:
+            refuse_free_lp(free_lp, "correctors=%d" % correctors, "the rounds' kernels are not restated for LP free columns")
         if lockstep:
             refuse_detect_qp(detect_qp, "a lockstep solver", "the batch has no quadratic kernels; solve such problems one at a time")
         if lockstep:
@@ -339,6 +391,14 @@ class IpmSolver:
         if free is not None:                 # before A too: a handle with free columns takes the one-workgroup small path only with free_small
             try:
                 self._set_free_checked(free)
+            except Exception:
+                self.close()
+                raise
+        self._n_free_lp = 0                  # the size of the LP free set the library holds (info["free_lp"])
+        self._free_lp_idx = None             # ... and the set itself, for mehrotra_start
+        if free_lp is not None:              # before A too: ipm_set_A_csc then takes the multi-kernel path
+            try:
+                self._set_free_lp_checked(free_lp, free_rho)
             except Exception:
                 self.close()
                 raise
@@ -552,6 +612,29 @@ class IpmSolver:
             self._check(self._lib.ipm_get_free_columns(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), k.value, C.byref(k)))
         return out
 
+    def _set_free_lp_checked(self, idx, rho):
+        self._check(self._lib.ipm_set_free_lp_columns(self._h, None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      0 if idx is None else int(idx.shape[0]), float(rho)))
+        self._n_free_lp = 0 if idx is None else int(idx.shape[0])
+        self._free_lp_idx = None if idx is None else idx.copy()
+
+    def set_free_lp(self, free_lp, free_rho=None):
+        """ipm_set_free_lp_columns: the LP free columns (indices or a boolean mask) and their proximal weight from the next iteration
+        on; None or an empty set clears them, and the solver enqueues exactly what it enqueued without.  The indices and free_rho
+        are checked on the host first (ValueError); the library decides what depends on the handle's other data (IpmError: a finite
+        bound, a quadratic term, free columns with curvature, a lockstep or detect_infeasibility solver, correctors, the fused small
+        path).  A state the solver holds gets s = 0 on the new free columns; after CLEARING, set a state anew before iterating."""
+        self._set_free_lp_checked(check_free_lp(free_lp, self.n), check_free_rho(free_rho))
+
+    def free_lp_columns(self):
+        """ipm_get_free_lp_columns: (the set in the order it was given as a fresh int32 array, rho in the handle's units)."""
+        k, rho = C.c_int32(0), C.c_double(0.0)
+        self._check(self._lib.ipm_get_free_lp_columns(self._h, None, 0, C.byref(k), C.byref(rho)))
+        out = np.zeros(k.value, dtype=np.int32)
+        if k.value:
+            self._check(self._lib.ipm_get_free_lp_columns(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), k.value, C.byref(k), C.byref(rho)))
+        return out, rho.value
+
     def debug_column_vector(self, which):
         """ipm_debug_get_column_vector (test hook): "rc", "d", "v" or "q" of the last newton_direction / iterate as the device holds
         it, length n, in the handle's units."""
@@ -745,6 +828,8 @@ class IpmSolver:
         y = self.normal_solve(A @ c, reuse_factor=True)
         s = c - A.T @ y
         x = np.asarray(x).ravel(); s = np.asarray(s).ravel()
+        if self._n_free_lp:
+            return self._mehrotra_start_free_lp(x, np.asarray(y).ravel(), s, ub)
         if self.bounded:
             return self._mehrotra_start_bounded(x, np.asarray(y).ravel(), s, ub)
         x = x + max(-1.5 * x.min(), 0.0)
@@ -780,6 +865,38 @@ class IpmSolver:
         sx = float(x.sum() + w[U].sum())                 # (after the primal correction, as in the unbounded recipe)
         s = s + xs / sx; z[U] += xs / sx
         return x, y, s, w, z
+
+    def _mehrotra_start_free_lp(self, x, y, r, ub):
+        """The recipe with LP free columns Phi (plain -> (x, y, s), bounded -> (x, y, s, w, z)): on Phi x is the least-squares value,
+        unshifted and uncorrected, and s = 0; Phi puts nothing into a minimum or a sum, so the shifts and the balance are those of
+        the barrier columns alone -- the arithmetic, in the order of the device start (start_free_lp_* of iteration_rules.h)."""
+        F = np.zeros(self.n, dtype=bool)
+        F[self._free_lp_idx] = True
+        Bc = ~F
+        U = np.isfinite(ub) if self.bounded else np.zeros(self.n, dtype=bool)
+        w = np.zeros(self.n); z = np.zeros(self.n)
+        s = r.copy()
+        if self.bounded:
+            w[U] = ub[U] - x[U]
+            s[U] = np.maximum(r[U], 0.0)
+            z[U] = np.maximum(-r[U], 0.0)
+        s[F] = 0.0
+        x = x.copy()
+        dp = max(-1.5 * min(x[Bc].min(), w[U].min() if U.any() else np.inf), 0.0)
+        dd = max(-1.5 * min(s[Bc].min(), z[U].min() if U.any() else np.inf), 0.0)
+        x[Bc] += dp; w[U] += dp
+        s[Bc] += dd; z[U] += dd
+        xs = 0.5 * float(x[Bc] @ s[Bc] + w[U] @ z[U])
+        sx, ss = float(x[Bc].sum() + w[U].sum()), float(s[Bc].sum() + z[U].sum())
+        if not (np.isfinite(xs) and ss > 0 and sx > 0 and xs > 0):          # degenerate data: the reference's start of such a handle
+            x, s = np.ones(self.n), np.ones(self.n)
+            s[F] = 0.0
+            w[U], z[U] = 1.0, 1.0
+            return (x, np.ones(self.m), s, w, z) if self.bounded else (x, np.ones(self.m), s)
+        x[Bc] += xs / ss; w[U] += xs / ss
+        sx = float(x[Bc].sum() + w[U].sum())
+        s[Bc] += xs / sx; z[U] += xs / sx
+        return (x, y, s, w, z) if self.bounded else (x, y, s)
 
     def solve_linear(self, B, rhs):
         """B z = rhs for the CALLER's dense SPD matrix (main.py:176-182): the row order this handle keeps its own A in

@@ -10,7 +10,7 @@
 from .analysis import (FUSED_SMALL_MAX_ROWS, REORDER_MIN_ROWS, SPARSE_FACTOR_MIN_ROWS, Prepared, _col, _tile_envelope_work,  # noqa: F401
                        _upper_bounds, _worth_ordering, dense_tile_ms, envelope_row_order, factor_flops, path_flops, prefer_sparse_factor,
                        prepare, sparse_factor_order)
-from .handle import SCALE_PASSES, STATUS_NAMES, IpmSolver, _dptr, check_free, check_scale, mehrotra_started, shift_allowed, wants_shift  # noqa: F401
+from .handle import SCALE_PASSES, STATUS_NAMES, IpmSolver, _dptr, check_free, check_free_lp, check_free_rho, check_scale, mehrotra_started, shift_allowed, wants_shift  # noqa: F401
 from .api import _info, _verdict, interior, interior_sparse, last_info, solve, solve_with_info, unscaled_residuals, verify_certificate  # noqa: F401
 from .batches import (LockstepBatch, _small_batch_host_check, _small_qp_batch_host_check, init_small_batch_mehrotra, lockstep_eligible,  # noqa: F401
                       small_batch_eligible, solve_lockstep, solve_small_batch, solve_small_batch_solvers, solve_small_qp_batch, solve_small_qp_batch_detect)

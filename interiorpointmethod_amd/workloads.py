@@ -135,3 +135,53 @@ def block_angular_lp(m, block, k, seed=0, link_fill=0.5):
     y0 = rng.standard_normal((m, 1))
     s0 = rng.uniform(0.5, 1.5, (n, 1))
     return A, A @ x0, A.T @ y0 + s0, link
+
+
+def free_lp(m, n, n_free, seed, bounded=False, dependent=False):
+    """LP with free variables and a KNOWN optimum: min c.x, A x = b, x_j >= 0 (<= u_j) for j outside Phi, x_Phi free
+    -> (A (m, n) dense, b, c, free (the sorted indices of Phi, int32), u (None unless bounded; +inf = no bound), x_star, y_star,
+    s_star), vectors 1-D.
+
+    A ~ N(0, 1); Phi = n_free columns drawn without replacement.  The free columns are basic: x* ~ +-U(0.5, 2) of either sign,
+    s* = 0.  Of the barrier columns m - n_free are basic (x* ~ U(0.5, 2), s* = 0) and the rest are nonbasic (x* = 0,
+    s* ~ U(0.5, 2)): strictly complementary, and the m basic columns of a Gaussian A are independent, so (x*, y*, s*) is the
+    unique optimum.  bounded: half the barrier columns get u = x* + U(0.5, 2), and a tenth of the bounded NONBASIC ones sit AT
+    their bound instead: x* = u ~ U(0.5, 2), s* = 0, z* ~ U(0.5, 2).  y* ~ N(0, 1), c = A^T y* + s* - z*, b = A x*.
+    dependent=True (n_free >= 4): the last free column becomes a copy of the first and the one before it twice the second, so x*_Phi
+    is not unique (the objective and A x = b still are); m - n_free + 2 barrier columns are basic then.  PCG64(seed)."""
+    if not 1 <= n_free < n or m < 1:
+        raise ValueError("free_lp needs m >= 1 and 1 <= n_free < n")
+    if dependent and n_free < 4:
+        raise ValueError("free_lp(dependent=True) needs n_free >= 4")
+    n_basic = m - n_free + (2 if dependent else 0)
+    if n_basic < 0 or n_basic > n - n_free:
+        raise ValueError("free_lp: m - n_free basic barrier columns do not fit (m = %d, n = %d, n_free = %d)" % (m, n, n_free))
+    rng = np.random.default_rng(seed)
+    A = rng.standard_normal((m, n))
+    free = np.sort(rng.choice(n, n_free, replace=False))
+    if dependent:
+        A[:, free[-1]] = A[:, free[0]]
+        A[:, free[-2]] = 2.0 * A[:, free[1]]
+    barrier = np.setdiff1d(np.arange(n), free)
+    basic = rng.choice(barrier, n_basic, replace=False)
+    x = np.zeros(n)
+    s = np.zeros(n)
+    z = np.zeros(n)
+    x[free] = rng.uniform(0.5, 2.0, n_free) * rng.choice([-1.0, 1.0], n_free)
+    x[basic] = rng.uniform(0.5, 2.0, n_basic)
+    nonbasic = np.setdiff1d(barrier, basic)
+    s[nonbasic] = rng.uniform(0.5, 2.0, nonbasic.size)
+    u = None
+    if bounded:
+        u = np.full(n, np.inf)
+        has_u = barrier[rng.random(barrier.size) < 0.5]
+        u[has_u] = x[has_u] + rng.uniform(0.5, 2.0, has_u.size)
+        at = np.intersect1d(has_u, nonbasic)
+        at = at[rng.random(at.size) < 0.1]
+        x[at] = rng.uniform(0.5, 2.0, at.size)
+        u[at] = x[at]
+        s[at] = 0.0
+        z[at] = rng.uniform(0.5, 2.0, at.size)
+    y = rng.standard_normal(m)
+    c = A.T @ y + s - z
+    return A, A @ x, c, free.astype(np.int32), u, x, y, s
