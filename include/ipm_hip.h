@@ -656,6 +656,18 @@ int ipm_debug_step_kernel(int32_t step, int32_t bounded, int32_t detect, int32_t
  * ipm_debug_step_kernel does. */
 int ipm_debug_step_kernel_ex(int32_t step, int32_t bounded, int32_t detect, int32_t quad, int32_t free_cols, int32_t free_lp, char* name_out,
                              int32_t capacity, int32_t* twin_type_out);
+/* Host only: the library's option-compatibility table (csrc/host_compat.h), read back.  The features a handle can hold;
+ * the last two are option flags that only LIFT an exclusion, and IPM_FEATURE_MEHROTRA_START is an operation (ipm_init_state_mehrotra /
+ * ipm_init_small_batch_mehrotra), never held. */
+enum {
+    IPM_FEATURE_BOUNDS = 0, IPM_FEATURE_QUADRATIC, IPM_FEATURE_FREE, IPM_FEATURE_FREE_LP, IPM_FEATURE_DETECT, IPM_FEATURE_DETECT_QP,
+    IPM_FEATURE_CORRECTORS, IPM_FEATURE_REFINEMENT, IPM_FEATURE_DENSE_SPLIT, IPM_FEATURE_LOCKSTEP, IPM_FEATURE_LOCKSTEP_BOUNDS,
+    IPM_FEATURE_SMALL_PATH, IPM_FEATURE_MEHROTRA_START, IPM_FEATURE_SMALL_QUADRATIC_FLAG, IPM_FEATURE_SMALL_FREE_FLAG, IPM_FEATURE_COUNT
+};
+/* Is switching feature a ON refused on a handle that holds feature b?  *excluded = 1 / 0; *lifted_by = the feature whose presence on
+ * the handle removes the exclusion, -1 for none (also when *excluded = 0).  Either pointer may be NULL.  A row is symmetric unless the
+ * table declares it one-directional.  IPM_ERR_INVALID_ARG for an id outside 0 .. IPM_FEATURE_COUNT - 1. */
+int ipm_debug_compat(int32_t a, int32_t b, int32_t* excluded, int32_t* lifted_by);
 int ipm_debug_ff_schedule(int32_t nblk, int32_t q, int32_t workers, unsigned char* items, int32_t capacity, int32_t* count,
                           int32_t* tile_items, double sim_us[2]);
 int ipm_get_phase_ms(ipm_handle* h, double out[4]);

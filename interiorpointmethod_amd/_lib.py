@@ -18,7 +18,7 @@ EXPORTS = [
     "ipm_abi_version", "ipm_device_count", "ipm_default_options", "ipm_workspace_bytes", "ipm_workspace_bytes_csc", "ipm_workspace_bytes_opts",
     "ipm_create", "ipm_destroy", "ipm_last_error", "ipm_set_A_dense", "ipm_set_A_csc",
     "ipm_set_bc", "ipm_set_state", "ipm_get_state", "ipm_init_state", "ipm_init_state_mehrotra", "ipm_set_bounds", "ipm_set_bound_state", "ipm_get_bound_state", "ipm_set_quadratic", "ipm_get_quadratic", "ipm_set_free_columns", "ipm_get_free_columns", "ipm_set_free_lp_columns", "ipm_get_free_lp_columns", "ipm_debug_get_column_vector", "ipm_equilibrate", "ipm_get_scaling", "ipm_newton_direction",
-    "ipm_iterate", "ipm_solve", "ipm_solve_batch", "ipm_solve_small_batch", "ipm_init_small_batch_mehrotra", "ipm_batch_create", "ipm_batch_destroy", "ipm_batch_last_error", "ipm_batch_add", "ipm_batch_step", "ipm_batch_stats", "ipm_get_history", "ipm_set_centrality_correctors", "ipm_get_corrector_info", "ipm_set_refinement", "ipm_get_refinement_info", "ipm_debug_get_refine_vector", "ipm_set_infeasibility_tol", "ipm_get_certificate", "ipm_get_schedule", "ipm_get_schedule_words", "ipm_debug_at_pieces", "ipm_debug_chol_plan", "ipm_debug_step_kernel", "ipm_debug_step_kernel_ex", "ipm_order_rows", "ipm_get_factor_info", "ipm_solve_linear", "ipm_lu_solve", "ipm_lu_factor", "ipm_normal_solve", "ipm_form_normal_matrix", "ipm_get_factor",
+    "ipm_iterate", "ipm_solve", "ipm_solve_batch", "ipm_solve_small_batch", "ipm_init_small_batch_mehrotra", "ipm_batch_create", "ipm_batch_destroy", "ipm_batch_last_error", "ipm_batch_add", "ipm_batch_step", "ipm_batch_stats", "ipm_get_history", "ipm_set_centrality_correctors", "ipm_get_corrector_info", "ipm_set_refinement", "ipm_get_refinement_info", "ipm_debug_get_refine_vector", "ipm_set_infeasibility_tol", "ipm_get_certificate", "ipm_get_schedule", "ipm_get_schedule_words", "ipm_debug_at_pieces", "ipm_debug_chol_plan", "ipm_debug_step_kernel", "ipm_debug_step_kernel_ex", "ipm_debug_compat", "ipm_order_rows", "ipm_get_factor_info", "ipm_solve_linear", "ipm_lu_solve", "ipm_lu_factor", "ipm_normal_solve", "ipm_form_normal_matrix", "ipm_get_factor",
     "ipm_set_dense_columns", "ipm_get_dense_split_info", "ipm_debug_get_dense_split",
     "ipm_set_profiling", "ipm_get_phase_ms", "ipm_debug_get_stamps", "ipm_debug_ff_schedule", "ipm_debug_ff_trace", "ipm_debug_get_block_inverse", "ipm_debug_get_group_inverse", "ipm_debug_ls_merge",
     "ipm_debug_batch_schedule",
@@ -55,6 +55,9 @@ MAX_CORRECTORS = 8              # include/ipm_hip.h: IPM_MAX_CORRECTORS
 MAX_REFINE = 4                  # include/ipm_hip.h: IPM_MAX_REFINE
 MAX_DENSE_COLS = 64             # include/ipm_hip.h: IPM_MAX_DENSE_COLS
 FREE_LP_RHO_DEFAULT = 1e-8      # include/ipm_hip.h: IPM_FREE_LP_RHO_DEFAULT
+# include/ipm_hip.h: IPM_FEATURE_*, by id (ipm_debug_compat; the `pair` of a row of options.ROWS names two of them)
+FEATURES = ("bounds", "quad", "free", "free_lp", "detect", "detect_qp", "correctors", "refinement", "dense_split", "lockstep", "lockstep_bounds",
+            "small_path", "mehrotra_start", "small_quadratic_flag", "small_free_flag")
 ERR_INVALID_INPUT = -6
 ERR_SINGULAR = -7               # include/ipm_hip.h: IPM_ERR_SINGULAR (ipm_lu_solve / ipm_lu_factor, info > 0)
 
@@ -181,6 +184,7 @@ def load():
     lib.ipm_debug_chol_plan.argtypes = [i32, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32]
     lib.ipm_debug_step_kernel.argtypes = [i32, i32, i32, i32, i32, C.c_char_p, i32, C.POINTER(i32)]
     lib.ipm_debug_step_kernel_ex.argtypes = [i32, i32, i32, i32, i32, i32, C.c_char_p, i32, C.POINTER(i32)]
+    lib.ipm_debug_compat.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
     lib.ipm_set_infeasibility_tol.argtypes = [vp, dbl, dbl]
     lib.ipm_get_certificate.argtypes = [vp, pd, pd, pd, pd]
     lib.ipm_order_rows.argtypes = [i64, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), pd]

@@ -5,6 +5,7 @@ import os
 import numpy as np
 
 from . import _lib
+from .options import refuse_dense_cols          # noqa: F401  (its importers find it here as before)
 
 try:  # scipy is optional on the host side (dense inputs work without it)
     from scipy import sparse as _sp
@@ -182,13 +183,6 @@ def check_dense_cols(dense_cols, n):
     if np.unique(cols).size != cols.size:
         raise ValueError("dense_cols: duplicated column index")
     return cols.astype(np.int32)
-
-
-def refuse_dense_cols(dense_cols, who):
-    """THE refusal of the front ends without a split (lockstep twins, the one-workgroup small kernel): the option raises, it is
-    never dropped."""
-    if dense_cols is not None:
-        raise ValueError("dense_cols=%r: %s has no dense-column split; solve such LPs one at a time" % (dense_cols, who))
 
 
 def without_columns(A, cols):

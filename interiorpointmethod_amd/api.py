@@ -15,8 +15,8 @@ import numpy as np
 
 from . import _lib
 from .analysis import _upper_bounds
-from .handle import (SCALE_PASSES, STATUS_NAMES, IpmSolver, check_correctors, check_detect_qp, check_free, check_free_lp, check_free_rho, check_quadratic, check_refine, check_scale, mehrotra_started,
-                     refuse_free, refuse_quadratic, shift_allowed, wants_shift)
+from .handle import SCALE_PASSES, STATUS_NAMES, IpmSolver, mehrotra_started, shift_allowed, wants_shift
+from .options import check_free_rho, check_options
 
 
 def _info(solver, cTlb=0.0):
@@ -128,11 +128,14 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
     default); info["free_lp"] = their count.  Checked on the host before any device is touched (ValueError naming the column);
     refused (ValueError) together with quad, free, detect_infeasibility and correctors > 0.  Both starts serve the set."""
     global _last_info
-    correctors = check_correctors(correctors)
-    refine = check_refine(refine)
     if start not in ("reference", "mehrotra"):
         raise ValueError('start must be "reference" or "mehrotra"')
-    if check_scale(scale) is not None:
+    n_cols = np.asarray(c).reshape(-1).shape[0]
+    ub = _upper_bounds(ub, n_cols)
+    v = check_options("solve_with_info", n_cols, scale=scale, correctors=correctors, refine=refine, quad=quad, free=free, detect_qp=detect_qp, free_lp=free_lp,
+                      detect_infeasibility=detect_infeasibility, start=start, ub=ub, dense_cols=dense_cols, lockstep=opts.get("lockstep", False))
+    correctors, refine, quad, free, detect_qp = (v[k] for k in ("correctors", "refine", "quad", "free", "detect_qp"))
+    if scale is not None:
         opts = dict(opts, scale=scale, scale_passes=scale_passes)
     if dense_cols is not None:
         opts = dict(opts, dense_cols=dense_cols)
@@ -140,27 +143,12 @@ def solve_with_info(A, b, c, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_gap=
         opts = dict(opts, quad_small=True)
     if free_small:
         opts = dict(opts, free_small=True)
-    quad = check_quadratic(quad, np.asarray(c).reshape(-1).shape[0])
-    detect_qp = check_detect_qp(detect_qp, quad)
     if detect_qp:
         opts = dict(opts, detect_qp=True)
-    if quad is not None:
-        if detect_infeasibility and not detect_qp:
-            refuse_quadratic(quad, "detect_infeasibility=True", "the infeasibility tests are the LP's")
-        if correctors:
-            refuse_quadratic(quad, "correctors=%d" % correctors, "a quadratic solver takes one step length, the rounds compare step pairs")
-    ub = _upper_bounds(ub, np.asarray(c).reshape(-1).shape[0])
-    free = check_free(free, np.asarray(c).reshape(-1).shape[0], quad, ub)
-    if detect_infeasibility and not detect_qp:
-        refuse_free(free, "detect_infeasibility=True", "the infeasibility tests are the LP's")
-    if check_free_lp(free_lp, np.asarray(c).reshape(-1).shape[0], ub, quad, free) is not None:
-        check_free_rho(free_rho)
-        opts = dict(opts, free_lp=free_lp, free_rho=free_rho)          # (IpmSolver refuses detect_infeasibility and correctors with it)
+    if v["free_lp"] is not None:
+        check_free_rho(free_rho)                                  # (read only beside a set, as before)
+        opts = dict(opts, free_lp=free_lp, free_rho=free_rho)
     detect_infeasibility = bool(detect_infeasibility) or detect_qp
-    if correctors:
-        refuse_free(free, "correctors=%d" % correctors, "a quadratic solver takes one step length, the rounds compare step pairs")
-    if start == "mehrotra":
-        refuse_free(free, 'start="mehrotra"', "the least-squares start is not restated for free columns")
     on_device = start == "mehrotra" and device_start
     if start == "mehrotra" and not on_device and shift_allowed(opts.get("regularize"), _auto_regularize()):
         # the least-squares start factors A A^T: guarded pivots there are dependent rows of A (handle.wants_shift: the 5 % rule).

@@ -25,8 +25,8 @@ from . import _lib
 from .analysis import _upper_bounds, prepare
 from .api import _auto_regularize, _solve_info, solve_with_info
 from .batches import LockstepBatch, lockstep_eligible, small_batch_eligible, solve_small_batch_solvers
-from .analysis import refuse_dense_cols
-from .handle import SCALE_PASSES, IpmSolver, check_scale, mehrotra_started, refuse_correctors, refuse_detect_qp, refuse_free, refuse_free_lp, refuse_refine
+from .handle import SCALE_PASSES, IpmSolver, mehrotra_started
+from .options import check_options
 
 # One record per LP.  The first nine fields are the statistics SURVEY.md 8e names; the rest make the library's hidden
 # recoveries and the host-side phases of a solve visible in the gathered table: `timeouts_recovered` = device hand-off
@@ -490,16 +490,11 @@ def solve_shard_lockstep(problems, ids, device=0, workers=8, tol=1e-8, max_iter=
     correctors > 0 raises ValueError: the centrality-corrector rounds have no batched twins (run_batch(lockstep=False) serves them);
     refine > 0 likewise, and so does dense_cols (the split has no batched twins either), and so does free (free columns), and so
     does detect_qp=True (no quadratic kernels in the batch)."""
-    refuse_detect_qp(detect_qp, "the lockstep batch", "the Quad and Free kernels have no batched twins; solve such problems one at a time")
-    refuse_free(free, "the lockstep batch", "the Free kernels have no batched twins; solve such problems one at a time")
-    refuse_free_lp(free_lp, "the lockstep batch", "the free_lp kernels have no batched twins; solve such problems one at a time")
-    refuse_correctors(correctors, "the lockstep batch")
-    refuse_refine(refine, "the lockstep batch")
-    refuse_dense_cols(dense_cols, "the lockstep batch")
+    check_options("the lockstep batch", detect_qp=detect_qp, free=free, free_lp=free_lp, correctors=correctors, refine=refine, dense_cols=dense_cols, scale=scale)
     if start not in ("reference", "mehrotra"):
         raise ValueError('start must be "reference" or "mehrotra"')
     handle_kw = dict(device=device, regularize=regularize, concurrent=True, detect_infeasibility=detect_infeasibility)
-    if check_scale(scale) is not None:
+    if scale is not None:
         handle_kw.update(scale=scale, scale_passes=scale_passes)
     return _LockstepShard(problems, ids, device, workers, small_batch, y0, dict(tol=tol, max_iter=max_iter, tol_gap=tol_gap),
                           handle_kw, start=start).run()
@@ -624,8 +619,7 @@ def run_batch(problems, costs=None, device=0, dist=None, gather_device=None, sol
     collective_at_world_one asks for the distributed code path anyway (store counter, device tensors through
     dist.all_gather): that is how the RCCL branch is exercised on a one-GPU box (tests/test_gpu_parity.py).
     free (free columns of a quadratic problem) raises ValueError: a batch's problems are (A, b, c) triples, LPs."""
-    refuse_free(free, "run_batch", "its problems are LPs; solve such problems one at a time")
-    refuse_free_lp(free_lp, "run_batch", "its problems are (A, b, c, ub) tuples with no slot for free columns; solve such problems one at a time")
+    check_options("run_batch", free=free, free_lp=free_lp)
     if solve_fn is solve_one:
         for p in problems:
             unpack_problem(p)

@@ -6,9 +6,8 @@ import numpy as np
 from . import _lib
 from .analysis import FUSED_SMALL_MAX_ROWS, _sp, _upper_bounds
 from .api import _auto_regularize, _solve_info
-from .analysis import refuse_dense_cols
-from .handle import (SCALE_PASSES, IpmSolver, _gap_tol, check_quadratic, check_scale, refuse_correctors, refuse_detect_qp, refuse_free, refuse_free_lp, refuse_refine,
-                     wants_shift)
+from .handle import SCALE_PASSES, IpmSolver, _gap_tol, wants_shift
+from .options import check_options, check_quadratic, check_scale
 
 
 def _handle_array(solvers):           # (the handles as a C array, a Stats array of the same length) for one batched library call
@@ -30,12 +29,7 @@ def solve_lockstep(solvers, tol=1e-8, max_iter=5000, tol_gap=None, correctors=0,
     (IpmError).  correctors > 0: ValueError (the rounds
     have no batched twins; a lockstep solver refuses set_correctors for the same reason); refine > 0 likewise, and free columns, and
     detect_qp=True (no quadratic kernels in the batch)."""
-    refuse_detect_qp(detect_qp, "the lockstep batch", "the Quad and Free kernels have no batched twins; solve such problems one at a time")
-    refuse_free(free, "the lockstep batch", "the Free kernels have no batched twins; solve such problems one at a time")
-    refuse_free_lp(free_lp, "the lockstep batch", "the free_lp kernels have no batched twins; solve such problems one at a time")
-    refuse_correctors(correctors, "the lockstep batch")
-    refuse_refine(refine, "the lockstep batch")
-    refuse_dense_cols(dense_cols, "the lockstep batch")          # (the split has no batched twins: ValueError, never dropped)
+    check_options("the lockstep batch", detect_qp=detect_qp, free=free, free_lp=free_lp, correctors=correctors, refine=refine, dense_cols=dense_cols)          # (ValueError, never dropped)
     hs, st = _handle_array(solvers)
     _lib.check(solvers[0]._h, _lib.load().ipm_solve_batch(hs, len(solvers), tol, tol, _gap_tol(tol, tol_gap), int(max_iter), st))
     return _scatter_stats(solvers, st)
@@ -130,9 +124,7 @@ def solve_small_batch_solvers(solvers, tol=1e-8, max_iter=5000, tol_gap=None, st
     solvers stay alive: set_state / init_state and another call re-solve them.  stream: a torch.cuda.Stream for the launches
     (None: the first solver's stream).  ValueError, naming the index, for a solver that is not on the small path, and for
     correctors > 0 or refine > 0 (the one-workgroup kernel runs no centrality-corrector and no refinement rounds)."""
-    refuse_correctors(correctors, "the small-LP batch")
-    refuse_refine(refine, "the small-LP batch")
-    refuse_dense_cols(dense_cols, "the small-LP batch")          # (the one-workgroup kernel has no split: ValueError, never dropped)
+    check_options("the small-LP batch", correctors=correctors, refine=refine, dense_cols=dense_cols)          # (ValueError, never dropped)
     lib = _lib.load()
     solvers = list(solvers)
     if not solvers:
@@ -209,11 +201,7 @@ def solve_small_batch(problems, tol=1e-8, max_iter=5000, y0=1.0, device=0, tol_g
     small path (more than 128 rows, or a product list of A D^2 A^T beyond its cap) raises ValueError naming its index before anything
     is launched.  scale="ruiz": every LP is equilibrated on the device first (IpmSolver; off by default).  correctors > 0: ValueError
     before any device is touched (solve_small_batch_solvers), and so for refine > 0 and for free columns (free=)."""
-    refuse_free(free, "the small-LP batch", "the one-workgroup kernel has no free columns; solve such problems one at a time")
-    refuse_free_lp(free_lp, "the small-LP batch", "the one-workgroup kernel has no LP free columns; solve such problems one at a time")
-    refuse_correctors(correctors, "the small-LP batch")
-    refuse_refine(refine, "the small-LP batch")
-    refuse_dense_cols(dense_cols, "the small-LP batch")          # (the one-workgroup kernel has no split: ValueError, never dropped)
+    check_options("the small-LP batch", free=free, free_lp=free_lp, correctors=correctors, refine=refine, dense_cols=dense_cols)
     if start not in ("reference", "mehrotra"):
         raise ValueError('start must be "reference" or "mehrotra"')
     check_scale(scale)

@@ -16,7 +16,7 @@ static std::atomic<bool> g_attr_set[MAX_DEVICES];      // per-device function at
 // CTL_DOUBLES, the room of one record, behind it.  RoundsKind is what differs between the features besides where their vectors lie:
 // the words of the messages, the range of k and the size formula.  The operations are in host_iteration.h (rounds_*).
 struct ipm_handle;
-struct RoundsKind { const char *noun, *none, *small_why, *setter; int kmax; size_t (*doubles)(const ipm_handle*); };
+struct RoundsKind { const char *noun, *none, *setter; int feature, kmax; size_t (*doubles)(const ipm_handle*); };      // (feature: its IPM_FEATURE_* of host_compat.h)
 template <class Ctl, int CTL_DOUBLES> struct Rounds {
     static_assert(sizeof(Ctl) <= sizeof(double) * CTL_DOUBLES, "the record outgrew its slot");
     const RoundsKind* kind;
@@ -28,8 +28,18 @@ template <class Ctl, int CTL_DOUBLES> struct Rounds {
 };
 static const int MCC_CTL_DOUBLES = 8, REF_CTL_DOUBLES = 16;
 static size_t mcc_doubles(const ipm_handle* h), ref_doubles(const ipm_handle* h);      // (beside the views, below)
-static const RoundsKind MCC_KIND{"centrality correctors", "no rounds", "factor and solve cost the same there", "ipm_set_centrality_correctors", IPM_MAX_CORRECTORS, mcc_doubles};
-static const RoundsKind REF_KIND{"refinement rounds", "none", "it has no rounds", "ipm_set_refinement", IPM_MAX_REFINE, ref_doubles};
+static const RoundsKind MCC_KIND{"centrality correctors", "no rounds", "ipm_set_centrality_correctors", IPM_FEATURE_CORRECTORS, IPM_MAX_CORRECTORS, mcc_doubles};
+static const RoundsKind REF_KIND{"refinement rounds", "none", "ipm_set_refinement", IPM_FEATURE_REFINEMENT, IPM_MAX_REFINE, ref_doubles};
+
+// A set of columns the caller marks (free columns with curvature, LP free columns): own allocation of np bytes, made on first use and kept.
+struct ColumnSet {
+    bool on = false;                      // the set is not empty: its kernel instantiations run
+    std::vector<int> cols;                // the set, in the caller's order
+    std::vector<char> host;               // host: column j is in the set (empty without a set), what the per-column checks read
+    unsigned char* mark = nullptr;        // 1 on the set's columns, 0 elsewhere and in the padding (written whole); scale-free and
+                                          // constant during a solve, so neither the equilibration nor the roll-back snapshot touch it
+    bool has(int64_t j) const { return on && host[(size_t)j] != 0; }
+};
 
 struct ipm_handle {
     int device = 0;
@@ -168,18 +178,9 @@ struct ipm_handle {
                                           // solve, so the roll-back snapshot carries nothing of it
     std::vector<char> quad_pos;           // host: g_j > 0 (empty without a term), what the free-column checks read
     std::vector<char> bnd_finite;         // host: u_j finite (empty without a finite bound), for the same checks
-    // free columns with curvature (ipm_set_free_columns): own allocation of np bytes, made on first use
-    bool free_on = false;                 // the set is not empty: the Free kernel instantiations run
-    std::vector<int> free_cols;           // the set, in the caller's order
-    std::vector<char> free_host;          // host: column j is free (empty without a set), what ipm_set_bounds reads
-    unsigned char* free_mark = nullptr;   // 1 on the free columns, 0 elsewhere and in the padding (written whole); scale-free and
-                                          // constant during a solve, so neither the equilibration nor the roll-back snapshot touch it
-    // LP free columns (ipm_set_free_lp_columns): own allocation of np bytes, made on first use; never together with
-    // a quadratic term or the set above
-    bool free_lp_on = false;              // the set is not empty: the free_lp kernel instantiations run
-    std::vector<int> free_lp_cols;        // the set, in the caller's order
-    std::vector<char> free_lp_host;       // host: column j is in the set (empty without a set), what ipm_set_bounds reads
-    unsigned char* free_lp_mark = nullptr;   // as free_mark
+    // free columns with curvature (ipm_set_free_columns) and LP free columns (ipm_set_free_lp_columns, DESIGN.md 4-W:
+    // never together with a quadratic term or the first set)
+    ColumnSet free_set, free_lp_set;
     double free_lp_rho = 1e-8;            // the proximal weight, in the handle's units (IPM_FREE_LP_RHO_DEFAULT)
     // centrality correctors (ipm_set_centrality_correctors): up to mcc.k rounds per iteration re-use its factor
     Rounds<MccCtl, MCC_CTL_DOUBLES> mcc{&MCC_KIND};   // mem: q v dx ds r3 r3g | qz dw dz r4 r4g (n-vectors) | dy (m-vector) | partial minima [2][MAXPART] | record | its copy
@@ -442,8 +443,8 @@ static BndArgs bnd_args(ipm_handle* h) {
     return b;
 }
 
-static FreeArgs free_args(const ipm_handle* h) { return FreeArgs{h->free_mark, (int)h->free_cols.size()}; }
-static FreeLpArgs free_lp_args(const ipm_handle* h) { return FreeLpArgs{FreeArgs{h->free_lp_mark, (int)h->free_lp_cols.size()}, h->free_lp_rho}; }
+static FreeArgs free_args(const ipm_handle* h) { return FreeArgs{h->free_set.mark, (int)h->free_set.cols.size()}; }
+static FreeLpArgs free_lp_args(const ipm_handle* h) { return FreeLpArgs{FreeArgs{h->free_lp_set.mark, (int)h->free_lp_set.cols.size()}, h->free_lp_rho}; }
 
 // centrality correctors: views into mcc.mem.  mcc_vec_args / mcc_bnd_args are the handle's views with the candidate's arrays in place.
 static const int MCC_NVECS = 11;
@@ -491,7 +492,7 @@ static DetArgs det_args(const ipm_handle* h) { return DetArgs{h->det_eps_p, h->d
 // variant tables; the legality rule free => quad is variant_legal, which check_ready and the small batch's own check enforce before
 // a launch).  Every other reader of these fields keeps data in step with them: the setters, equilibration, the roll-back copies
 // of (w, z), the refusals.
-static StepVariant step_variant(const ipm_handle* h) { return StepVariant{h->bnd, h->detect, h->quad, h->free_on, h->free_lp_on}; }
+static StepVariant step_variant(const ipm_handle* h) { return StepVariant{h->bnd, h->detect, h->quad, h->free_set.on, h->free_lp_set.on}; }
 // ... and the guard in front of every table look-up (the iteration's and the small path's entries call it before their first launch):
 // a handle whose class is not legal has no row, and an entry point that forgot check_ready gets an error, not a null row.
 static int check_class(ipm_handle* h, const char* who) {

@@ -43,8 +43,7 @@ template <class R> static int rounds_snapshot(ipm_handle* h, const R& r, int res
 template <class R> static int rounds_set(ipm_handle* h, R ipm_handle::*which, const RoundsKind& kind, int32_t k) {
     if (k < 0 || k > kind.kmax) return fail(h, IPM_ERR_INVALID_ARG, "%s: k = %d outside 0 .. %d", kind.setter, (int)k, kind.kmax);
     if (!h) return fail(h, IPM_ERR_INVALID_ARG, "%s: NULL handle", kind.setter);
-    if (k > 0 && h->small) return fail(h, IPM_ERR_INVALID_ARG, "%s: the handle runs the fused small-LP kernel (one workgroup holds the whole loop; %s)", kind.setter, kind.small_why);
-    if (k > 0 && h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "%s: the handle was created with IPM_FLAG_LOCKSTEP (the rounds have no batched twins)", kind.setter);
+    if (k > 0) if (int rc_ = compat_refuse(h, kind.setter, kind.feature)) return rc_;
     (h->*which).k = k;
     return IPM_OK;
 }
@@ -375,8 +374,7 @@ static void fill_stats(ipm_handle* h, ipm_stats* st, double ms) {
 static int check_ready(ipm_handle* h, const char* who) {
     if (!h) return fail(h, IPM_ERR_INVALID_ARG, "%s: NULL handle", who);
     if (!h->haveA || !h->haveBC || !h->haveState) return fail(h, IPM_ERR_STATE, "%s: A, (b,c) and a state must be set first", who);
-    if (h->free_on && !h->quad)          // (a set given before the term is checked against it by ipm_set_quadratic; none ever came)
-        return fail(h, IPM_ERR_INVALID_ARG, "%s: column %d is a free column (ipm_set_free_columns) without a quadratic term: a free column needs g > 0 (ipm_set_quadratic)", who, h->free_cols[0]);
+    if (const int c = free_without_term(h); c >= 0) return fail(h, IPM_ERR_INVALID_ARG, "%s: column %d %s", who, c, FREE_NEEDS_TERM);
     return IPM_OK;
 }
 
@@ -426,10 +424,6 @@ extern "C" int ipm_newton_direction(ipm_handle* h, int corrector, double* dx, do
 
 // ------------------------------------------------------------------------------- centrality correctors
 extern "C" int ipm_set_centrality_correctors(ipm_handle* h, int32_t k) {
-    if (h && h->quad && k > 0 && k <= MCC_KIND.kmax)           // (behind the range check, which reads nothing of the handle)
-        return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_centrality_correctors: the handle holds a quadratic term (ipm_set_quadratic): it takes one step length, and the rounds' accept rule compares step pairs");
-    if (h && h->free_lp_on && k > 0 && k <= MCC_KIND.kmax)
-        return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_centrality_correctors: the handle holds LP free columns (ipm_set_free_lp_columns): the rounds' kernels are not restated for them");
     return rounds_set(h, &ipm_handle::mcc, MCC_KIND, k);
 }
 extern "C" int ipm_get_corrector_info(ipm_handle* h, int64_t out[4]) {
@@ -488,7 +482,7 @@ static SmallItem small_item(ipm_handle* h, int index, int max_steps, int auto_re
     if (h->bnd) it.bd = bnd_args(h);
     it.dt = det_args(h);
     it.g = h->quad ? h->quad_g : nullptr;
-    if (h->free_on) it.fr = free_args(h);
+    if (h->free_set.on) it.fr = free_args(h);
     it.eta = h->opt.eta;
     it.variant = small_variant(h);
     it.index = index;
@@ -545,7 +539,7 @@ extern "C" int ipm_init_state_mehrotra(ipm_handle* h, int32_t* pivots_fixed) {
     if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_init_state_mehrotra: NULL handle");
     if (!h->haveA) return fail(h, IPM_ERR_STATE, "ipm_init_state_mehrotra: A not set");
     if (!h->haveBC) return fail(h, IPM_ERR_STATE, "ipm_init_state_mehrotra: (b, c) not set");
-    if (h->free_on) return fail(h, IPM_ERR_INVALID_ARG, "ipm_init_state_mehrotra: the handle has free columns (ipm_set_free_columns): the least-squares start is not restated for them; use ipm_init_state");
+    if (int rc_ = compat_refuse(h, "ipm_init_state_mehrotra", IPM_FEATURE_MEHROTRA_START)) return rc_;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
     for (int attempt = 0;; ++attempt) {                     // second pass only after a recovered poll time-out

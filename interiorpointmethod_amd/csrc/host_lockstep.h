@@ -16,7 +16,7 @@ static void ls_gemm_hook(void* ctx, int bm, int bn, int bk, int wm, int wn, cons
     if (!ok) h->ls_cut = true;                               // not recordable: ls_record_program reports it
 }
 // (a handle with finite upper bounds only with IPM_FLAG_LOCKSTEP_BOUNDS, the opt-in to the bounded twins)
-static bool ls_bounds_ok(const ipm_handle* h) { return !h->bnd || (h->opt.flags & IPM_FLAG_LOCKSTEP_BOUNDS); }
+static bool ls_bounds_ok(const ipm_handle* h) { return !compat_blocker(h, IPM_FEATURE_LOCKSTEP, nullptr, IPM_FEATURE_BOUNDS); }      // (host_compat.h: lifted by IPM_FLAG_LOCKSTEP_BOUNDS)
 static bool ls_eligible(const ipm_handle* h) {
     return h->lockstep && ls_bounds_ok(h) && h->sparse && !h->small && !h->spf && h->lookahead == 0 && h->stream2 == nullptr && h->B && h->invD &&
            h->haveA && h->haveBC && h->haveState;
@@ -291,8 +291,8 @@ extern "C" int ipm_batch_stats(ipm_batch* b, int32_t index, ipm_stats* stats) {
 extern "C" int ipm_solve_batch(ipm_handle** hs, int32_t n, double tol_p, double tol_d, double tol_gap, int32_t max_iter, ipm_stats* stats) {
     if (!hs || n <= 0 || max_iter < 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_batch: bad arguments");
     for (int i = 0; i < n; ++i) if (!hs[i]) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_batch: NULL handle");
-    for (int i = 0; i < n; ++i)
-        if (!ls_bounds_ok(hs[i])) return fail(hs[i], IPM_ERR_INVALID_ARG, "ipm_solve_batch: handle %d has upper bounds (ipm_set_bounds): no lockstep twin", i);
+    for (int i = 0; i < n; ++i)          // (ls_bounds_ok, in the table's words)
+        if (int rc_ = compat_refuse(hs[i], "ipm_solve_batch", IPM_FEATURE_LOCKSTEP, i, /*to_handle=*/true, IPM_FEATURE_BOUNDS)) return rc_;
     ipm_batch* b = nullptr;
     int rc = ipm_batch_create(hs[0]->device, nullptr, &b);
     if (rc) return rc;

@@ -97,8 +97,8 @@ extern "C" int ipm_solve_small_batch(ipm_handle** hs, int32_t n, double tol_p, d
         ipm_handle* h = hs[i];
         if (!h->haveA || !h->haveBC || !h->haveState) return fail(nullptr, IPM_ERR_STATE, "ipm_solve_small_batch: handle %d: A, (b,c) and a state must be set first", i);
         if (h->profiling) return fail(nullptr, IPM_ERR_STATE, "ipm_solve_small_batch: handle %d has profiling on (ipm_set_profiling)", i);
-        if (h->free_on && !h->quad)          // (check_ready's rule of the single solve: a set whose term never came)
-            return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_small_batch: handle %d: column %d is a free column (ipm_set_free_columns) without a quadratic term: a free column needs g > 0 (ipm_set_quadratic)", i, h->free_cols[0]);
+        if (const int c = free_without_term(h); c >= 0)          // (check_ready's rule of the single solve)
+            return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_solve_small_batch: handle %d: column %d %s", i, c, FREE_NEEDS_TERM);
     }
     ipm_handle* h0 = hs[0];
     HIP_TRY(h0, hipSetDevice(h0->device));
@@ -141,7 +141,7 @@ extern "C" int ipm_init_small_batch_mehrotra(ipm_handle** hs, int32_t n, void* s
     for (int i = 0; i < n; ++i)
         if (!hs[i]->haveA || !hs[i]->haveBC) return fail(nullptr, IPM_ERR_STATE, "ipm_init_small_batch_mehrotra: handle %d: A and (b,c) must be set first", i);
     for (int i = 0; i < n; ++i)              // as ipm_init_state_mehrotra refuses one such handle, before anything is launched
-        if (hs[i]->free_on) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_init_small_batch_mehrotra: handle %d has free columns (ipm_set_free_columns): the least-squares start is not restated for them; use ipm_init_state", i);
+        if (int rc_ = compat_refuse(hs[i], "ipm_init_small_batch_mehrotra", IPM_FEATURE_MEHROTRA_START, i, /*to_handle=*/false)) return rc_;
     ipm_handle* h0 = hs[0];
     HIP_TRY(h0, hipSetDevice(h0->device));
     hipStream_t S = stream ? (hipStream_t)stream : h0->stream;

@@ -292,7 +292,7 @@ extern "C" int ipm_set_dense_columns(ipm_handle* h, int32_t count, const int32_t
     if (count > IPM_MAX_DENSE_COLS) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_dense_columns: %d columns exceed IPM_MAX_DENSE_COLS = %d", (int)count, IPM_MAX_DENSE_COLS);
     if (!h->sparse || !(h->opt.flags & IPM_FLAG_SPARSE_FACTOR)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_dense_columns: the handle has no sparse factor (IPM_FLAG_SPARSE_FACTOR on a sparse handle)");
     if (h->m <= SMALL_MAX_M) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_dense_columns: a handle of m <= %d rows runs the fused small path, which has no split", SMALL_MAX_M);
-    if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_dense_columns: a lockstep handle has no split (its kernels have no batched twins)");
+    if (int rc_ = compat_refuse(h, "ipm_set_dense_columns", IPM_FEATURE_DENSE_SPLIT)) return rc_;
     std::vector<char> seen((size_t)h->n, 0);
     for (int32_t t = 0; t < count; ++t) {
         if (cols[t] < 0 || cols[t] >= h->n) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_dense_columns: column index %d out of range", (int)cols[t]);
@@ -497,10 +497,9 @@ extern "C" int ipm_set_A_csc(ipm_handle* h, const int32_t* colptr, const int32_t
             // its nonzeros one dependent load at a time).
             size_t terms = 0;
             for (int64_t j = 0; j < h->n; ++j) { const size_t c = (size_t)(cp[j + 1] - cp[j]); terms += c * (c + 1) / 2; }
-            // (a handle that holds a quadratic term takes it only with IPM_FLAG_SMALL_QUADRATIC: the Quad variants of the loop,
-            //  ipm_set_quadratic; one that holds free columns only with IPM_FLAG_SMALL_FREE on top: the Free variants, ipm_set_free_columns)
-            const bool want_small = h->fused_small && h->m <= SMALL_MAX_M && terms <= ((size_t)1 << 22) && (!h->quad || (h->opt.flags & IPM_FLAG_SMALL_QUADRATIC)) &&
-                                    (!h->free_on || (h->opt.flags & IPM_FLAG_SMALL_FREE)) && !h->free_lp_on;      // (an LP free set: the multi-kernel path)
+            // (the small path's rows of the compatibility table, host_compat.h: a handle that holds a quadratic term takes the path only with
+            //  IPM_FLAG_SMALL_QUADRATIC, one that holds free columns only with IPM_FLAG_SMALL_FREE on top, one with an LP free set never)
+            const bool want_small = h->fused_small && h->m <= SMALL_MAX_M && terms <= ((size_t)1 << 22) && !compat_blocker(h, IPM_FEATURE_SMALL_PATH);
             // (measured, ms per iteration list / row-owner: SHELL (8 blocks) 0.778 / 0.810, DEGEN3 (12) 1.13 / 1.12, PILOT87 (30)
             //  2.44 / 2.38: the zero fill of B eats the gain from 16 blocks on)
             const bool want_list = h->list_form_opt && h->m > SMALL_MAX_M && h->mp <= 1536 && terms <= ((size_t)1 << 24);

@@ -50,6 +50,7 @@
 using namespace ipm;
 
 #include "host_handle.h"
+#include "host_compat.h"
 #include "host_equilibrate.h"
 #include "host_sparse_setup.h"
 #include "host_residuals.h"
@@ -162,7 +163,7 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     if (opts && (opts->flags & IPM_FLAG_DETECT_QUADRATIC) && !(opts->flags & IPM_FLAG_DETECT_INFEASIBILITY))
         return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_create: IPM_FLAG_DETECT_QUADRATIC without IPM_FLAG_DETECT_INFEASIBILITY (it opts a detecting handle into the tests of a quadratic problem, nothing else)");
     if (opts && (opts->flags & IPM_FLAG_DETECT_QUADRATIC) && (opts->flags & IPM_FLAG_LOCKSTEP))
-        return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_create: IPM_FLAG_DETECT_QUADRATIC with IPM_FLAG_LOCKSTEP (the Quad and Free kernels have no batched twins)");
+        return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_create: IPM_FLAG_DETECT_QUADRATIC with IPM_FLAG_LOCKSTEP %s", compat_row(IPM_FEATURE_DETECT_QP, IPM_FEATURE_LOCKSTEP)->a_on);
     ipm_handle* h = new ipm_handle();
     h->device = device;
     if (opts) h->opt = *opts; else ipm_default_options(&h->opt);
@@ -338,7 +339,7 @@ extern "C" int ipm_destroy(ipm_handle* h) {
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->h_sc) { std::lock_guard<std::mutex> lock(g_hsc_mutex); g_hsc_pool.push_back(h->h_sc); h->h_sc = nullptr; }
-    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->quad_g, (void*)h->free_mark, (void*)h->free_lp_mark, (void*)h->mcc.mem, (void*)h->ref.mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
+    for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->quad_g, (void*)h->free_set.mark, (void*)h->free_lp_set.mark, (void*)h->mcc.mem, (void*)h->ref.mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
         dev_free(h->device, h->stream, p);
     ff_release(h);
     free_sparse_factor(h);
@@ -390,16 +391,14 @@ extern "C" int ipm_set_bc(ipm_handle* h, const double* b, const double* c) {
     return IPM_OK;
 }
 
-// free columns (ipm_set_free_columns) hold no s: every seam that writes a state zeroes it there
+// free columns (of either set) hold no s: every seam that writes a state zeroes it there
 static int enqueue_free_zero_s(ipm_handle* h) {
-    if (!h->free_on && !h->free_lp_on) return IPM_OK;            // (never both: the setters refuse the pair)
-    hipLaunchKernelGGL(free_zero_s_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream,
-                       (const unsigned char*)(h->free_on ? h->free_mark : h->free_lp_mark), h->s, (int)h->n);
+    const ColumnSet& cs = h->free_set.on ? h->free_set : h->free_lp_set;      // (never both: host_compat.h refuses the pair)
+    if (!cs.on) return IPM_OK;
+    hipLaunchKernelGGL(free_zero_s_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, (const unsigned char*)cs.mark, h->s, (int)h->n);
     HIP_TRY(h, hipGetLastError());
     return IPM_OK;
 }
-static bool free_is(const ipm_handle* h, int64_t j) { return h->free_on && h->free_host[(size_t)j] != 0; }
-static bool free_lp_is(const ipm_handle* h, int64_t j) { return h->free_lp_on && h->free_lp_host[(size_t)j] != 0; }
 
 extern "C" int ipm_set_state(ipm_handle* h, const double* x, const double* y, const double* s) {
     if (!h || !x || !y || !s) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_state: bad arguments");
@@ -437,10 +436,7 @@ extern "C" int ipm_set_bounds(ipm_handle* h, const double* u) {
             const double v = u[j];
             if (!(v >= 0.0)) return fail(h, IPM_ERR_INVALID_INPUT, "ipm_set_bounds: u[%lld] = %g (bounds must be >= 0, +inf for none)", (long long)j, v);
             if (v < std::numeric_limits<double>::infinity()) {
-                if (free_is(h, j))
-                    return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_bounds: u[%lld] = %g is finite, but column %lld is a free column (ipm_set_free_columns): it takes no bound", (long long)j, v, (long long)j);
-                if (free_lp_is(h, j))
-                    return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_bounds: u[%lld] = %g is finite, but column %lld is an LP free column (ipm_set_free_lp_columns): it takes no bound", (long long)j, v, (long long)j);
+                if (int rc_ = column_conflict(h, "ipm_set_bounds", IPM_FEATURE_BOUNDS, j, v)) return rc_;
                 ++nU;
             }
         }
@@ -491,18 +487,13 @@ extern "C" int ipm_set_quadratic(ipm_handle* h, const double* g) {
             if (v > 0.0) ++nnz;
         }
     }
-    for (int c : h->free_cols)                                 // a free column keeps its curvature: 1 / g_j is its scaling
-        if (!g || !(g[c] > 0.0))
-            return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: g[%d] = %g, but column %d is a free column (ipm_set_free_columns) and needs g > 0; clear the free set first", c, g ? g[c] : 0.0, c);
+    for (int c : h->free_set.cols)
+        if (int rc_ = column_conflict(h, "ipm_set_quadratic", IPM_FEATURE_QUADRATIC, c, g ? g[c] : 0.0)) return rc_;
     if (nnz == 0) {                                            // NULL or all zeros: the LP code, exactly
         h->quad = false; h->quad_nnz = 0; h->predictor_valid = false; h->quad_pos.clear();
         return IPM_OK;
     }
-    if (h->free_lp_on) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle holds LP free columns (ipm_set_free_lp_columns): they live on a handle without a quadratic term; clear that set first");
-    if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle was created with IPM_FLAG_LOCKSTEP (the Quad kernels have no batched twins)");
-    if (h->detect && !h->detect_qp) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the dual ray of a QP also needs g o x = 0; the tests are not restated)");
-    if (h->mcc.k > 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: %d centrality correctors are set (their accept rule compares step pairs, a quadratic handle takes one step; ipm_set_centrality_correctors(h, 0))", h->mcc.k);
-    if (h->small && !(h->opt.flags & IPM_FLAG_SMALL_QUADRATIC)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_quadratic: the handle runs the fused small-LP kernel, which has no quadratic term; set the term before A (ipm_set_A_csc then takes the multi-kernel path)");
+    if (int rc_ = compat_refuse(h, "ipm_set_quadratic", IPM_FEATURE_QUADRATIC)) return rc_;
     const size_t np = (size_t)h->np;
     std::vector<double> gg(np, 0.0);
     std::copy(g, g + h->n, gg.begin());
@@ -533,99 +524,68 @@ extern "C" int ipm_get_quadratic(ipm_handle* h, double* g, int64_t* nonzeros) {
     return IPM_OK;
 }
 
-// Free columns with curvature.  The marks are the library's own allocation of np bytes, made on first use and kept
-// (clearing only switches the Free kernels off); the whole vector is written, so the padding is zero before any kernel reads it.
-extern "C" int ipm_set_free_columns(ipm_handle* h, const int32_t* idx, int32_t count) {
-    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: NULL handle");
-    if (count < 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: count = %d", (int)count);
-    if (count == 0 || !idx) {                                  // cleared: the Quad (or LP) code, exactly
-        h->free_cols.clear(); h->free_host.clear(); h->free_on = false; h->predictor_valid = false;
+// The two column sets: free columns with curvature and LP free columns (columns without a quadratic
+// term and without a sign constraint, served by proximal-point regularisation of the free block; iteration_rules.h: free_lp_*).  ONE
+// setter body: `feature` names the set and its row of the compatibility table, rho (the LP set's extra; null for the other) is checked
+// and stored with it.  The marks are the library's own allocation of np bytes, made on first use and kept (clearing only switches the
+// set's kernels off); the whole vector is written, so the padding is zero before any kernel reads it.
+static int set_column_set(ipm_handle* h, ColumnSet ipm_handle::*which, int feature, const char* who, const int32_t* idx, int32_t count, const double* rho_in = nullptr) {
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "%s: NULL handle", who);
+    if (count < 0) return fail(h, IPM_ERR_INVALID_ARG, "%s: count = %d", who, (int)count);
+    ColumnSet& cs = h->*which;
+    if (count == 0 || !idx) {                                  // cleared: the code without the set, exactly
+        cs.cols.clear(); cs.host.clear(); cs.on = false; h->predictor_valid = false;
         return IPM_OK;
     }
-    if (h->free_lp_on) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle holds LP free columns (ipm_set_free_lp_columns): the two sets do not share a handle; clear that set first");
-    if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle was created with IPM_FLAG_LOCKSTEP (the Free kernels have no batched twins)");
-    if (h->detect && !h->detect_qp) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the tests are the LP's and are not restated)");
-    if (h->small && !(h->opt.flags & IPM_FLAG_SMALL_FREE)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: the handle runs the fused small kernel, which has no free columns; set them before A (ipm_set_A_csc then takes the multi-kernel path)");
-    std::vector<char> seen((size_t)h->n, 0);
-    for (int32_t t = 0; t < count; ++t) {
-        const int32_t j = idx[t];
-        if (j < 0 || j >= h->n) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: column index %d out of range", (int)j);
-        if (seen[(size_t)j]) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: column index %d is duplicated", (int)j);
-        seen[(size_t)j] = 1;
-        if (h->quad && !h->quad_pos[(size_t)j]) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: column %d has g = 0: a free column needs curvature (ipm_set_quadratic)", (int)j);
-        if (h->bnd && h->bnd_finite[(size_t)j]) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: column %d has a finite upper bound (ipm_set_bounds): a free column takes none", (int)j);
-    }
-    if ((int64_t)count >= h->n) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_columns: all %d columns free leaves no complementarity pair (mu would be 0/0)", (int)count);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t np = (size_t)h->np;
-    if (!h->free_mark && dev_malloc(h->device, h->stream, (void**)&h->free_mark, np) != hipSuccess)
-        return fail(h, IPM_ERR_HIP, "ipm_set_free_columns: %lld bytes could not be allocated", (long long)np);
-    std::vector<unsigned char> mk(np, 0);
-    for (int32_t t = 0; t < count; ++t) mk[(size_t)idx[t]] = 1;
-    HIP_TRY(h, hipMemcpyAsync(h->free_mark, mk.data(), np, hipMemcpyHostToDevice, h->stream));
-    h->free_cols.assign(idx, idx + count); h->free_host.swap(seen); h->free_on = true; h->predictor_valid = false;
-    if (int rc_ = enqueue_free_zero_s(h)) return rc_;              // a state the handle holds loses s on the new free columns
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return IPM_OK;
-}
-
-extern "C" int ipm_get_free_columns(ipm_handle* h, int32_t* idx, int32_t cap, int32_t* count) {
-    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_free_columns: NULL handle");
-    if (cap < 0 || (cap > 0 && !idx)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_free_columns: bad arguments");
-    const int32_t k = (int32_t)h->free_cols.size();
-    if (count) *count = k;
-    for (int32_t t = 0; t < k && t < cap; ++t) idx[t] = h->free_cols[(size_t)t];
-    return IPM_OK;
-}
-
-// LP free columns: columns without a quadratic term and without a sign constraint, served by proximal-point
-// regularisation of the free block (iteration_rules.h: free_lp_*).  The marks are the library's own allocation of np bytes, made on
-// first use and kept (clearing only switches the free_lp kernels off); the whole vector is written.
-extern "C" int ipm_set_free_lp_columns(ipm_handle* h, const int32_t* idx, int32_t count, double rho) {
-    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: NULL handle");
-    if (count < 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: count = %d", (int)count);
-    if (count == 0 || !idx) {                                  // cleared: the LP code, exactly
-        h->free_lp_cols.clear(); h->free_lp_host.clear(); h->free_lp_on = false; h->predictor_valid = false;
-        return IPM_OK;
-    }
-    if (!std::isfinite(rho)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: rho = %g is not finite", rho);
+    double rho = rho_in ? *rho_in : 0.0;
+    if (!std::isfinite(rho)) return fail(h, IPM_ERR_INVALID_ARG, "%s: rho = %g is not finite", who, rho);
     if (!(rho > 0.0)) rho = IPM_FREE_LP_RHO_DEFAULT;
-    if (h->quad) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: the handle holds a quadratic term (ipm_set_quadratic): LP free columns live on a handle without one (a free column with g > 0 is ipm_set_free_columns)");
-    if (h->free_on) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: the handle holds free columns with curvature (ipm_set_free_columns): the two sets do not share a handle");
-    if (h->lockstep) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: the handle was created with IPM_FLAG_LOCKSTEP (the free_lp kernels have no batched twins)");
-    if (h->detect) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: the handle was created with IPM_FLAG_DETECT_INFEASIBILITY (the tests are not restated for LP free columns)");
-    if (h->mcc.k > 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: %d centrality correctors are set (their kernels are not restated for LP free columns; ipm_set_centrality_correctors(h, 0))", h->mcc.k);
-    if (h->small) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: the handle runs the fused small kernel, which has no LP free columns; set them before A (ipm_set_A_csc then takes the multi-kernel path)");
+    if (int rc_ = compat_refuse(h, who, feature)) return rc_;
     std::vector<char> seen((size_t)h->n, 0);
     for (int32_t t = 0; t < count; ++t) {
         const int32_t j = idx[t];
-        if (j < 0 || j >= h->n) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: column index %d out of range", (int)j);
-        if (seen[(size_t)j]) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: column index %d is duplicated", (int)j);
+        if (j < 0 || j >= h->n) return fail(h, IPM_ERR_INVALID_ARG, "%s: column index %d out of range", who, (int)j);
+        if (seen[(size_t)j]) return fail(h, IPM_ERR_INVALID_ARG, "%s: column index %d is duplicated", who, (int)j);
         seen[(size_t)j] = 1;
-        if (h->bnd && h->bnd_finite[(size_t)j]) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: column %d has a finite upper bound (ipm_set_bounds): a free column takes none", (int)j);
+        if (int rc_ = column_conflict(h, who, feature, j)) return rc_;
     }
-    if ((int64_t)count >= h->n) return fail(h, IPM_ERR_INVALID_ARG, "ipm_set_free_lp_columns: all %d columns free leaves no complementarity pair (mu would be 0/0)", (int)count);
+    if ((int64_t)count >= h->n) return fail(h, IPM_ERR_INVALID_ARG, "%s: all %d columns free leaves no complementarity pair (mu would be 0/0)", who, (int)count);
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t np = (size_t)h->np;
-    if (!h->free_lp_mark && dev_malloc(h->device, h->stream, (void**)&h->free_lp_mark, np) != hipSuccess)
-        return fail(h, IPM_ERR_HIP, "ipm_set_free_lp_columns: %lld bytes could not be allocated", (long long)np);
+    if (!cs.mark && dev_malloc(h->device, h->stream, (void**)&cs.mark, np) != hipSuccess)
+        return fail(h, IPM_ERR_HIP, "%s: %lld bytes could not be allocated", who, (long long)np);
     std::vector<unsigned char> mk(np, 0);
     for (int32_t t = 0; t < count; ++t) mk[(size_t)idx[t]] = 1;
-    HIP_TRY(h, hipMemcpyAsync(h->free_lp_mark, mk.data(), np, hipMemcpyHostToDevice, h->stream));
-    h->free_lp_cols.assign(idx, idx + count); h->free_lp_host.swap(seen); h->free_lp_on = true; h->free_lp_rho = rho; h->predictor_valid = false;
+    HIP_TRY(h, hipMemcpyAsync(cs.mark, mk.data(), np, hipMemcpyHostToDevice, h->stream));
+    cs.cols.assign(idx, idx + count); cs.host.swap(seen); cs.on = true; h->predictor_valid = false;
+    if (rho_in) h->free_lp_rho = rho;
     if (int rc_ = enqueue_free_zero_s(h)) return rc_;              // a state the handle holds loses s on the new free columns
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return IPM_OK;
 }
-
-extern "C" int ipm_get_free_lp_columns(ipm_handle* h, int32_t* idx, int32_t cap, int32_t* count, double* rho) {
-    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_free_lp_columns: NULL handle");
-    if (cap < 0 || (cap > 0 && !idx)) return fail(h, IPM_ERR_INVALID_ARG, "ipm_get_free_lp_columns: bad arguments");
-    const int32_t k = (int32_t)h->free_lp_cols.size();
+static int get_column_set(ipm_handle* h, ColumnSet ipm_handle::*which, const char* who, int32_t* idx, int32_t cap, int32_t* count) {
+    if (!h) return fail(h, IPM_ERR_INVALID_ARG, "%s: NULL handle", who);
+    if (cap < 0 || (cap > 0 && !idx)) return fail(h, IPM_ERR_INVALID_ARG, "%s: bad arguments", who);
+    const ColumnSet& cs = h->*which;
+    const int32_t k = (int32_t)cs.cols.size();
     if (count) *count = k;
-    if (rho) *rho = h->free_lp_rho;
-    for (int32_t t = 0; t < k && t < cap; ++t) idx[t] = h->free_lp_cols[(size_t)t];
+    for (int32_t t = 0; t < k && t < cap; ++t) idx[t] = cs.cols[(size_t)t];
     return IPM_OK;
+}
+
+extern "C" int ipm_set_free_columns(ipm_handle* h, const int32_t* idx, int32_t count) {
+    return set_column_set(h, &ipm_handle::free_set, IPM_FEATURE_FREE, "ipm_set_free_columns", idx, count);
+}
+extern "C" int ipm_get_free_columns(ipm_handle* h, int32_t* idx, int32_t cap, int32_t* count) {
+    return get_column_set(h, &ipm_handle::free_set, "ipm_get_free_columns", idx, cap, count);
+}
+extern "C" int ipm_set_free_lp_columns(ipm_handle* h, const int32_t* idx, int32_t count, double rho) {
+    return set_column_set(h, &ipm_handle::free_lp_set, IPM_FEATURE_FREE_LP, "ipm_set_free_lp_columns", idx, count, &rho);
+}
+extern "C" int ipm_get_free_lp_columns(ipm_handle* h, int32_t* idx, int32_t cap, int32_t* count, double* rho) {
+    const int rc = get_column_set(h, &ipm_handle::free_lp_set, "ipm_get_free_lp_columns", idx, cap, count);
+    if (!rc && rho) *rho = h->free_lp_rho;
+    return rc;
 }
 
 // test hook: a column vector of the iteration as the device holds it (the handle's units: no unscaling), n entries
@@ -814,6 +774,14 @@ extern "C" int ipm_debug_step_kernel(int32_t step, int32_t bounded, int32_t dete
 extern "C" int ipm_debug_step_kernel_ex(int32_t step, int32_t bounded, int32_t detect, int32_t quad, int32_t free_cols, int32_t free_lp, char* name_out,
                                         int32_t capacity, int32_t* twin_type_out) {
     return debug_step_kernel("ipm_debug_step_kernel_ex", step, variant_bits(StepVariant{bounded != 0, detect != 0, quad != 0, free_cols != 0, free_lp != 0}), name_out, capacity, twin_type_out);
+}
+// The compatibility table, read back (host only; tests/test_compat_table_host.py, tests/test_gpu_compat_orders.py).
+extern "C" int ipm_debug_compat(int32_t a, int32_t b, int32_t* excluded, int32_t* lifted_by) {
+    if (a < 0 || a >= IPM_FEATURE_COUNT || b < 0 || b >= IPM_FEATURE_COUNT) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_debug_compat: feature id outside 0 .. %d", IPM_FEATURE_COUNT - 1);
+    const CompatRow* r = compat_row(a, b);
+    if (excluded) *excluded = r != nullptr;
+    if (lifted_by) *lifted_by = r ? r->lifted_by : -1;
+    return IPM_OK;
 }
 static int debug_step_kernel(const char* who, int32_t step, unsigned bits, char* name_out, int32_t capacity, int32_t* twin_type_out) {
     static const StepTable* const steps[] = {&STEP_PREPARE, &STEP_STOP_TEST, &STEP_SCALING, &STEP_DIRECTION, &STEP_MU_AFF, &STEP_CORRECTOR_RHS, &STEP_UPDATE};

@@ -7,6 +7,10 @@ import numpy as np
 
 from . import _lib
 from .analysis import _col, _is_sparse, prepare
+# the option checks live in options.py; these names stay importable from here (api.py, batch.py, batches.py, factor_qp.py, the tests)
+from .options import (ROUND_OPTIONS, check_correctors, check_detect_qp, check_free, check_free_lp, check_free_rho, check_options, check_quadratic,  # noqa: F401
+                      check_refine, check_rounds, check_scale, refuse_correctors, refuse_detect_qp, refuse_free, refuse_free_lp, refuse_quadratic,
+                      refuse_refine, refuse_rounds)
 
 STATUS_NAMES = {0: "running", 1: "converged", 2: "max_iter", 3: "nan", 5: "primal_infeasible", 6: "dual_infeasible"}
 
@@ -44,174 +48,6 @@ def mehrotra_started(make, regularize=0.0, auto_regularize=True):
 
 
 SCALE_PASSES = 16          # default cap of the Ruiz passes: the cap, not a tuning knob
-
-
-def check_scale(scale):
-    """THE check of the `scale` keyword, before any device is touched: None (off, the default) or "ruiz"."""
-    if scale not in (None, "ruiz"):
-        raise ValueError('scale must be None or "ruiz", not %r' % (scale,))
-    return scale
-
-
-# THE table of the round options: keyword -> (its maximum, the library's setter, what the batch front ends lack).  One check, one
-# refusal and one setter body (IpmSolver._set_rounds) are built on it.
-ROUND_OPTIONS = {
-    "correctors": (_lib.MAX_CORRECTORS, "ipm_set_centrality_correctors", "centrality-corrector rounds"),
-    "refine": (_lib.MAX_REFINE, "ipm_set_refinement", "refinement rounds"),
-}
-
-
-def check_rounds(name, k):
-    """THE check of a round option's keyword, before any device is touched: an integer 0 .. its maximum."""
-    kmax = ROUND_OPTIONS[name][0]
-    if isinstance(k, bool) or int(k) != k or not 0 <= int(k) <= kmax:
-        raise ValueError("%s must be an integer 0 .. %d, not %r" % (name, kmax, k))
-    return int(k)
-
-
-def refuse_rounds(name, k, who):
-    """THE refusal of the batch front ends, which have no rounds (lockstep twins, the one-workgroup small kernel): the option is
-    checked like anywhere else and k > 0 raises instead of being dropped."""
-    if check_rounds(name, k):
-        raise ValueError("%s=%d: %s runs no %s; solve such LPs one at a time" % (name, k, who, ROUND_OPTIONS[name][2]))
-
-
-# the four names their importers use (api.py, batch.py, batches.py, the tests): one-line wrappers
-def check_correctors(k): return check_rounds("correctors", k)                 # noqa: E704
-def check_refine(k): return check_rounds("refine", k)                         # noqa: E704
-def refuse_correctors(k, who): return refuse_rounds("correctors", k, who)     # noqa: E704
-def refuse_refine(k, who): return refuse_rounds("refine", k, who)             # noqa: E704
-
-
-def check_quadratic(quad, n):
-    """THE check of the `quad` keyword, before any device is touched: None (no term, the default) or n finite entries >= 0, the
-    diagonal g of the objective's quadratic term -> None (also for all zeros: the LP) or a fresh float64 array of length n."""
-    if quad is None:
-        return None
-    g = np.array(quad, dtype=np.float64).reshape(-1)
-    if g.shape[0] != n:
-        raise ValueError("quad has %d entries, the problem has %d columns" % (g.shape[0], n))
-    if not np.all(np.isfinite(g)) or np.any(g < 0):
-        raise ValueError("quad must be finite and >= 0 (the diagonal of a convex quadratic term)")
-    return g if np.any(g > 0) else None
-
-
-def refuse_quadratic(quad, who, why):
-    """THE refusal of what has no quadratic term (the batch front ends' options on IpmSolver: lockstep, detect_infeasibility,
-    correctors): a nonzero term raises instead of being dropped."""
-    if quad is not None and np.any(np.asarray(quad, dtype=np.float64) > 0):
-        raise ValueError("quad: %s takes no quadratic term (%s)" % (who, why))
-
-
-def check_free(free, n, quad=None, ub=None, term_known=True):
-    """THE check of the `free` keyword, before any device is touched: None (no free column, the default), a sequence of distinct
-    column indices 0 .. n-1 or a boolean mask of length n -> None (also for an empty set) or a fresh int32 array, ascending for a
-    mask and in the caller's order otherwise.  A free column carries no sign constraint and no bound and needs curvature: with
-    term_known, quad (the diagonal as check_quadratic returns it, None: no term) must be positive there, and ub (None: no bounds)
-    +inf; and one column at least must keep its complementarity pair.  Every violation is a ValueError naming the column."""
-    if free is None:
-        return None
-    f = np.asarray(free)
-    if f.dtype == np.bool_:
-        if f.reshape(-1).shape[0] != n:
-            raise ValueError("free: the mask has %d entries, the problem has %d columns" % (f.reshape(-1).shape[0], n))
-        idx = np.flatnonzero(f.reshape(-1))
-    else:
-        f = f.reshape(-1)
-        if f.shape[0] and not np.issubdtype(f.dtype, np.integer):
-            if not np.issubdtype(f.dtype, np.floating) or not np.all(np.isfinite(f)) or np.any(f != np.floor(f)):
-                raise ValueError("free must be column indices or a boolean mask, not %r" % (free,))
-        idx = f.astype(np.int64)
-    if not idx.shape[0]:
-        return None
-    seen = set()
-    for j in idx.tolist():
-        if not 0 <= j < n:
-            raise ValueError("free: column index %d out of range (the problem has %d columns)" % (j, n))
-        if j in seen:
-            raise ValueError("free: column index %d is given twice" % j)
-        seen.add(j)
-    if term_known:
-        for j in idx.tolist():
-            if quad is None or not quad[j] > 0:
-                raise ValueError("free: column %d has no quadratic term (quad[%d] = %s): a free column needs curvature, g > 0" % (j, j, "none" if quad is None else repr(float(quad[j]))))
-    if ub is not None:
-        u = np.asarray(ub, dtype=np.float64).reshape(-1)
-        if u.shape[0] != n:
-            raise ValueError("ub has %d entries, the problem has %d columns" % (u.shape[0], n))
-        for j in idx.tolist():
-            if np.isfinite(u[j]):
-                raise ValueError("free: column %d has the finite upper bound %r: a free column takes none" % (j, float(u[j])))
-    if idx.shape[0] >= n:
-        raise ValueError("free: all %d columns free leaves no complementarity pair (mu would be 0/0)" % n)
-    return np.ascontiguousarray(idx, dtype=np.int32)
-
-
-def _free_count(free):
-    """The number of columns a `free` argument names: None 0, a boolean mask its True entries, else its length."""
-    if free is None:
-        return 0
-    f = np.asarray(free)
-    return int(f.sum()) if f.dtype == np.bool_ else int(f.size)
-
-
-def refuse_free(free, who, why):
-    """THE refusal of what has no free columns (the batch front ends, and lockstep / detect_infeasibility / correctors on IpmSolver):
-    a non-empty set raises instead of being dropped."""
-    if _free_count(free):
-        raise ValueError("free: %s takes no free columns (%s)" % (who, why))
-
-
-def check_free_rho(free_rho):
-    """THE check of the `free_rho` keyword: None or a value <= 0 -> 0.0 (the library's default, IPM_FREE_LP_RHO_DEFAULT), a positive
-    finite number -> that float; NaN and Inf are a ValueError."""
-    if free_rho is None:
-        return 0.0
-    rho = float(free_rho)
-    if not np.isfinite(rho):
-        raise ValueError("free_rho = %r is not finite (one positive finite number per solver; None or <= 0: the default %g)" % (free_rho, _lib.FREE_LP_RHO_DEFAULT))
-    return rho if rho > 0 else 0.0
-
-
-def check_free_lp(free_lp, n, ub=None, quad=None, free=None):
-    """THE check of the `free_lp` keyword, before any device is touched: None (no LP free column, the default), a sequence of distinct
-    column indices 0 .. n-1 or a boolean mask of length n -> None (also for an empty set) or a fresh int32 array, as check_free
-    returns it.  An LP free column carries no sign constraint, no bound and no quadratic term: ub (None: no bounds) must be +inf
-    there, the problem must have no quadratic term (quad) and no free columns with curvature (free), and one column at least must
-    keep its complementarity pair.  Every violation is a ValueError naming the column."""
-    try:
-        idx = check_free(free_lp, n, None, ub, term_known=False)
-    except ValueError as e:
-        raise ValueError(str(e).replace("free:", "free_lp:", 1).replace("free must", "free_lp must", 1)) from None
-    if idx is None:
-        return None
-    if quad is not None and np.any(np.asarray(quad, dtype=np.float64) > 0):
-        raise ValueError("free_lp: column %d is an LP free column, but the problem has a quadratic term (quad): a free column with curvature is `free`" % int(idx[0]))
-    if _free_count(free):
-        raise ValueError("free_lp: column %d is an LP free column, but the problem has free columns with curvature (free): the two sets do not share a solver" % int(idx[0]))
-    return idx
-
-
-def refuse_free_lp(free_lp, who, why):
-    """THE refusal of what has no LP free columns (the batch front ends, and lockstep / detect_infeasibility / correctors on
-    IpmSolver): a non-empty set raises instead of being dropped."""
-    if _free_count(free_lp):
-        raise ValueError("free_lp: %s takes no LP free columns (%s)" % (who, why))
-
-
-def check_detect_qp(detect_qp, quad):
-    """THE check of the `detect_qp` keyword, before any device is touched: detect_qp=True asks for the infeasibility tests of a
-    QUADRATIC problem (IPM_FLAG_DETECT_INFEASIBILITY | IPM_FLAG_DETECT_QUADRATIC) and needs a quadratic term (quad as
-    check_quadratic returns it; None: no term) -> bool.  An LP takes detect_infeasibility=True."""
-    if detect_qp and quad is None:
-        raise ValueError("detect_qp=True without a quadratic term (quad): an LP takes detect_infeasibility=True")
-    return bool(detect_qp)
-
-
-def refuse_detect_qp(detect_qp, who, why):
-    """THE refusal of what has no quadratic infeasibility tests (the lockstep front ends): detect_qp=True raises instead of being dropped."""
-    if detect_qp:
-        raise ValueError("detect_qp: %s takes no quadratic infeasibility tests (%s)" % (who, why))
 
 
 RefineInfo = collections.namedtuple("RefineInfo", "k solves applied half_rule reverts first_rel last_rel max_first_rel")
@@ -284,43 +120,14 @@ class IpmSolver:
         column) and set before A, so a small sparse problem takes the multi-kernel path.  quad, free, lockstep,
         detect_infeasibility and correctors > 0 refuse a non-empty set (ValueError).  s is 0 on such a column in every state;
         mehrotra_start / init_state_mehrotra serve the set."""
-        self.scale = check_scale(scale)
-        if lockstep_bounds and not lockstep:
-            raise ValueError("lockstep_bounds=True needs lockstep=True: it opts a lockstep solver into the batch's bounded kernels")
-        correctors = check_correctors(correctors)
-        refine = check_refine(refine)
-        quad = check_quadratic(quad, np.asarray(c).reshape(-1).shape[0] if prepared is None else prepared.n)
         n_cols = np.asarray(c).reshape(-1).shape[0] if prepared is None else prepared.n
-        free = check_free(free, n_cols, quad, ub if prepared is None else getattr(prepared, "ub", None))
-        detect_qp = check_detect_qp(detect_qp, quad)
-        free_lp = check_free_lp(free_lp, n_cols, ub if prepared is None else getattr(prepared, "ub", None), quad, free)
-        free_rho = check_free_rho(free_rho)
-        if lockstep:
-            refuse_free_lp(free_lp, "a lockstep solver", "the batch has no free_lp kernels; solve such problems one at a time")
-        if detect_infeasibility:
-            refuse_free_lp(free_lp, "detect_infeasibility=True", "the infeasibility tests are not restated for LP free columns")
-        if correctors:
-            refuse_free_lp(free_lp, "correctors=%d" % correctors, "the rounds' kernels are not restated for LP free columns")
-        if lockstep:
-            refuse_detect_qp(detect_qp, "a lockstep solver", "the batch has no quadratic kernels; solve such problems one at a time")
-        if lockstep:
-            refuse_free(free, "a lockstep solver", "the batch has no Free kernels; solve such problems one at a time")
-        if detect_infeasibility and not detect_qp:
-            refuse_free(free, "detect_infeasibility=True", "the infeasibility tests are the LP's")
-        if lockstep:
-            refuse_quadratic(quad, "a lockstep solver", "the batch has no quadratic kernels; solve such problems one at a time")
-        if detect_infeasibility and not detect_qp:
-            refuse_quadratic(quad, "detect_infeasibility=True", "the infeasibility tests are the LP's")
-        if correctors:
-            refuse_quadratic(quad, "correctors=%d" % correctors, "a quadratic solver takes one step length, the rounds compare step pairs")
-        if lockstep and dense_cols is not None:
-            raise ValueError("dense_cols=%r: a lockstep solver has no dense-column split; solve such LPs one at a time" % (dense_cols,))
+        v = check_options("IpmSolver", n_cols, scale=scale, lockstep=lockstep, lockstep_bounds=lockstep_bounds, correctors=correctors, refine=refine, quad=quad,
+                          free=free, detect_qp=detect_qp, free_lp=free_lp, free_rho=free_rho, detect_infeasibility=detect_infeasibility,
+                          dense_cols=dense_cols, ub=ub, prepared=prepared)
+        self.scale = scale
+        correctors, refine, quad, free, detect_qp, free_lp, free_rho = (v[k] for k in ("correctors", "refine", "quad", "free", "detect_qp", "free_lp", "free_rho"))
         if prepared is None:
             prepared = prepare(A, b, c, dense=dense, reorder=reorder, factor=factor, ub=ub, dense_cols=dense_cols)
-        elif ub is not None:
-            raise ValueError("pass ub to prepare() when a Prepared is given")
-        elif dense_cols is not None:
-            raise ValueError("pass dense_cols to prepare() when a Prepared is given")
         self.dense_cols = getattr(prepared, "dense_cols", None)          # (an empty array: the handle's set is cleared explicitly, below)
         self._unsplit_info = getattr(prepared, "unsplit_info", None)
         if lockstep and self.dense_cols is not None and len(self.dense_cols):
