@@ -698,6 +698,45 @@ int ipm_debug_ls_merge(int32_t n, const int32_t* off, const int32_t* types_flat,
  * steps (0 before the first step); IPM_ERR_INVALID_ARG, with *count set, when capacity (in words) < 4 * steps
  * (tests/test_gpu_lockstep_wide.py). */
 int ipm_debug_batch_schedule(ipm_batch* b, int32_t* out, int32_t capacity, int32_t* count);
+/* Test hooks of the guard bands (environment IPM_TEST_ALLOC_GUARD=<band bytes>[:<band byte>], read at every allocation and in every
+ * ipm_workspace_bytes* call).  With the knob set every device allocation of the library lies between
+ * two bands of that many bytes filled with the band byte (255 when none is given), and the workspace holds one band before its first
+ * region, one between every two regions and one behind the last.  One record describes one band: of a pool block the band before it
+ * (side 0) and the band behind it (side 1, which begins at the block's first byte past the size asked for); of the workspace the band
+ * behind each region (side 1: it runs from the region's last byte asked for to the next region) and the one before the first (side 0).
+ * tag: the region's name ("ws:nvec") or the allocating call site ("host_fused.h:71#12", #ordinal).  first_bad / bad_count: offset
+ * of the first byte of the band that is not the band byte and the number of such bytes (-1 / 0 where the band is intact or was not
+ * compared). */
+typedef struct ipm_guard_band {
+    char tag[96];
+    uint64_t address;      /* device address of the band's first byte */
+    uint64_t bytes;        /* of the band */
+    uint64_t inner;        /* device address of the allocation or region the band guards */
+    uint64_t inner_bytes;  /* as asked for */
+    int32_t side;          /* 0: before, 1: behind */
+    int32_t device;
+    int32_t byte;          /* the band byte */
+    int32_t ordinal;       /* of the allocation in the process */
+    int64_t first_bad;
+    int64_t bad_count;
+} ipm_guard_band;
+/* The live bands of handle h -- its workspace's and those of the pool blocks allocated on its stream -- or, with h = NULL, of the
+ * process.  *count = their number; out (capacity records, may be NULL) receives the first `capacity`.  Launches and reads nothing. */
+int ipm_debug_guard_list(ipm_handle* h, ipm_guard_band* out, int32_t capacity, int32_t* count);
+/* Compares the same bands now: synchronises the device(s), copies every band to the host and compares there.  *count = the number of
+ * DAMAGED bands; out receives the first `capacity` of them with first_bad / bad_count filled in.  Nothing is repaired. */
+int ipm_debug_guard_check(ipm_handle* h, ipm_guard_band* out, int32_t capacity, int32_t* count);
+/* Reads and clears the process-wide violation log: the damaged bands found when a guarded block was freed or a guarded handle
+ * destroyed (both compare before they release).  *count = records in the log before the call. */
+int ipm_debug_guard_log(ipm_guard_band* out, int32_t capacity, int32_t* count);
+/* Host only: the regions of the workspace of an m x n handle under the knob in effect (opts as for ipm_workspace_bytes_opts, may be
+ * NULL), in address order: tag, address = the region's OFFSET in the workspace, inner = the same, inner_bytes = bytes asked for, bytes =
+ * the band behind it (0 with the knob unset).  *total = what ipm_workspace_bytes_opts reports, *band = the band width (0: unset). */
+int ipm_debug_guard_layout(int64_t m, int64_t n, const ipm_options* opts, ipm_guard_band* out, int32_t capacity, int32_t* count, uint64_t* total,
+                           uint64_t* band);
+/* Host only: the comparison the check and the log use, on a host buffer: *first_bad = offset of the first of the `bytes` bytes at
+ * `band` that differs from `byte` (-1: none), *bad_count = how many differ. */
+int ipm_debug_guard_compare(const unsigned char* band, uint64_t bytes, int32_t byte, int64_t* first_bad, int64_t* bad_count);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@ EXPORTS = [
     "ipm_set_dense_columns", "ipm_get_dense_split_info", "ipm_debug_get_dense_split",
     "ipm_set_profiling", "ipm_get_phase_ms", "ipm_debug_get_stamps", "ipm_debug_ff_schedule", "ipm_debug_ff_trace", "ipm_debug_get_block_inverse", "ipm_debug_get_group_inverse", "ipm_debug_ls_merge",
     "ipm_debug_batch_schedule",
+    "ipm_debug_guard_list", "ipm_debug_guard_check", "ipm_debug_guard_log", "ipm_debug_guard_layout", "ipm_debug_guard_compare",
 ]
 
 IPM_OK = 0
@@ -97,6 +98,18 @@ class IterRecord(C.Structure):
                 ("rd_norm", C.c_double), ("gap", C.c_double), ("mu", C.c_double), ("sigma", C.c_double),
                 ("alpha_aff_p", C.c_double), ("alpha_aff_d", C.c_double), ("alpha_p", C.c_double),
                 ("alpha_d", C.c_double)]
+
+
+class GuardBand(C.Structure):
+    """ipm_guard_band: one guard band of the test knob IPM_TEST_ALLOC_GUARD (include/ipm_hip.h)."""
+    _fields_ = [("tag", C.c_char * 96), ("address", C.c_uint64), ("bytes", C.c_uint64), ("inner", C.c_uint64), ("inner_bytes", C.c_uint64),
+                ("side", C.c_int32), ("device", C.c_int32), ("byte", C.c_int32), ("ordinal", C.c_int32), ("first_bad", C.c_int64),
+                ("bad_count", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["tag"] = self.tag.decode()
+        return d
 
 
 _lib = None
@@ -185,6 +198,12 @@ def load():
     lib.ipm_debug_step_kernel.argtypes = [i32, i32, i32, i32, i32, C.c_char_p, i32, C.POINTER(i32)]
     lib.ipm_debug_step_kernel_ex.argtypes = [i32, i32, i32, i32, i32, i32, C.c_char_p, i32, C.POINTER(i32)]
     lib.ipm_debug_compat.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
+    pg, u64 = C.POINTER(GuardBand), C.c_uint64
+    lib.ipm_debug_guard_list.argtypes = [vp, pg, i32, C.POINTER(i32)]
+    lib.ipm_debug_guard_check.argtypes = [vp, pg, i32, C.POINTER(i32)]
+    lib.ipm_debug_guard_log.argtypes = [pg, i32, C.POINTER(i32)]
+    lib.ipm_debug_guard_layout.argtypes = [i64, i64, C.POINTER(Options), pg, i32, C.POINTER(i32), C.POINTER(u64), C.POINTER(u64)]
+    lib.ipm_debug_guard_compare.argtypes = [C.c_char_p, u64, i32, C.POINTER(i64), C.POINTER(i64)]
     lib.ipm_set_infeasibility_tol.argtypes = [vp, dbl, dbl]
     lib.ipm_get_certificate.argtypes = [vp, pd, pd, pd, pd]
     lib.ipm_order_rows.argtypes = [i64, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), pd]
@@ -225,3 +244,28 @@ def device_count():
     n = C.c_int(0)
     load().ipm_device_count(C.byref(n))
     return n.value
+
+
+
+# ---- the guard bands of the test knob IPM_TEST_ALLOC_GUARD (include/ipm_hip.h: ipm_debug_guard_*), as lists of dicts
+def _guard_records(call, capacity=4096):
+    out, count = (GuardBand * capacity)(), C.c_int32(0)
+    check(None, call(out, capacity, C.byref(count)))
+    if count.value > capacity:
+        return _guard_records(call, count.value)
+    return [out[i].as_dict() for i in range(count.value)]
+
+
+def guard_list(handle=None):
+    """The live bands of a handle (its C pointer), or of the process."""
+    return _guard_records(lambda out, cap, cnt: load().ipm_debug_guard_list(handle, out, cap, cnt))
+
+
+def guard_check(handle=None):
+    """The DAMAGED bands among them, compared now (synchronises the device)."""
+    return _guard_records(lambda out, cap, cnt: load().ipm_debug_guard_check(handle, out, cap, cnt))
+
+
+def guard_log():
+    """Reads and clears the log of the damage found when guarded memory was released."""
+    return _guard_records(lambda out, cap, cnt: load().ipm_debug_guard_log(out, cap, cnt))

@@ -118,6 +118,7 @@ struct ipm_handle {
     void* ws = nullptr;
     size_t ws_bytes = 0;
     bool own_ws = false;
+    bool guarded = false;                 // the workspace carries guard bands (IPM_TEST_ALLOC_GUARD at ipm_create), entered in the registry
     // device arrays (all inside the workspace)
     double *A = nullptr, *B = nullptr, *invD = nullptr;
     double *x = nullptr, *s = nullptr, *c = nullptr, *rc = nullptr, *d = nullptr, *v = nullptr, *q = nullptr;
@@ -332,14 +333,123 @@ static hipError_t alloc_fill(void* p, size_t bytes, hipStream_t stream) {
     const int v = alloc_fill_byte();
     return v < 0 ? hipSuccess : hipMemsetAsync(p, v, bytes, stream);
 }
-static hipError_t dev_malloc(int device, hipStream_t stream, void** p, size_t bytes) {
+// Test knob IPM_TEST_ALLOC_GUARD=<band bytes, a multiple of 256>[:<band byte 0..255, default 255>]: every device allocation of the
+// library gets a band of that many bytes on each side, filled with the band byte, and the workspace one band before its first region,
+// between every two regions and behind the last (make_layout) -- so that a kernel that writes outside the memory it was given shows
+// (tests/test_gpu_alloc_guard.py).  Read at each allocation and by every make_layout, like IPM_TEST_ALLOC_FILL; anything
+// malformed (text, a negative or zero width, no multiple of 256, a byte outside 0..255) is the knob unset.  Unset: band 0 -- no extra
+// byte, no launch, no synchronisation, no registry entry.  Host code only: the comparison is done on the host, there is no kernel.
+struct GuardKnob { size_t band = 0; int byte = 255; };
+static GuardKnob alloc_guard() {
+    GuardKnob g;
+    const char* e = getenv("IPM_TEST_ALLOC_GUARD");
+    if (!e || !*e) return g;
+    char* end = nullptr;
+    const long long w = strtoll(e, &end, 10);
+    if (end == e || w <= 0 || w % 256 || w > (1ll << 30)) return g;
+    long b = 255;
+    if (*end == ':') { const char* t = end + 1; b = strtol(t, &end, 10); if (end == t || b < 0 || b > 255) return g; }
+    if (*end) return g;
+    g.band = (size_t)w; g.byte = (int)b;
+    return g;
+}
+// The process-wide registry of live bands and the log of the damage found when a guarded block was released.  owner: the handle whose
+// workspace the band lies in (null for a pool block, which is told apart by the stream it was allocated on).
+struct GuardRec { ipm_guard_band b; const void* owner; hipStream_t stream; };
+static std::mutex g_guard_mutex;
+static std::vector<GuardRec> g_guard_live;
+static std::vector<ipm_guard_band> g_guard_log;
+static std::atomic<int> g_guard_count{0};       // live records: 0 lets every release return at once
+static int g_guard_ordinal = 0;
+static void guard_compare(const unsigned char* p, size_t bytes, int byte, int64_t* first_bad, int64_t* bad_count) {
+    int64_t first = -1, cnt = 0;
+    for (size_t i = 0; i < bytes; ++i)
+        if (p[i] != (unsigned char)byte) { if (first < 0) first = (int64_t)i; ++cnt; }
+    *first_bad = first; *bad_count = cnt;
+}
+static void guard_register(const void* owner, hipStream_t stream, const char* tag, int side, const void* addr, size_t bytes, const void* inner,
+                           size_t inner_bytes, int device, int byte, int ordinal) {
+    GuardRec r{};
+    snprintf(r.b.tag, sizeof r.b.tag, "%s", tag);
+    r.b.address = (uint64_t)(uintptr_t)addr; r.b.bytes = bytes; r.b.inner = (uint64_t)(uintptr_t)inner; r.b.inner_bytes = inner_bytes;
+    r.b.side = side; r.b.device = device; r.b.byte = byte; r.b.ordinal = ordinal; r.b.first_bad = -1; r.b.bad_count = 0;
+    r.owner = owner; r.stream = stream;
+    g_guard_live.push_back(r);
+    g_guard_count.fetch_add(1, std::memory_order_release);
+}
+// copies the band to the host and compares there (the caller has synchronised whatever may still write); false: a copy failed
+static bool guard_check_band(ipm_guard_band& b) {
+    std::vector<unsigned char> host((size_t)b.bytes);
+    if (hipSetDevice(b.device) != hipSuccess || hipMemcpy(host.data(), (const void*)(uintptr_t)b.address, (size_t)b.bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        b.first_bad = 0; b.bad_count = -1;           // unreadable counts as damaged
+        return false;
+    }
+    guard_compare(host.data(), (size_t)b.bytes, b.byte, &b.first_bad, &b.bad_count);
+    return true;
+}
+// Takes the records `match` selects out of the registry, compares their bands and appends the damaged ones to the log.
+template <class Match> static void guard_release(Match match) {
+    std::vector<GuardRec> mine;
+    {
+        std::lock_guard<std::mutex> lock(g_guard_mutex);
+        for (size_t i = 0; i < g_guard_live.size();)
+            if (match(g_guard_live[i])) { mine.push_back(g_guard_live[i]); g_guard_live[i] = g_guard_live.back(); g_guard_live.pop_back(); g_guard_count.fetch_sub(1, std::memory_order_release); }
+            else ++i;
+    }
+    for (GuardRec& r : mine) {
+        guard_check_band(r.b);
+        if (r.b.bad_count != 0) { std::lock_guard<std::mutex> lock(g_guard_mutex); g_guard_log.push_back(r.b); }
+    }
+}
+// The ONE allocation and the one release behind dev_malloc / dev_free and LuRun (host_lu.h); pool: from the library's stream-ordered
+// pool, else hipMalloc / hipFree.  The pointer handed out stays 256-byte aligned (the band is a multiple of 256).
+static hipError_t guarded_alloc(int device, hipStream_t stream, void** p, size_t bytes, bool pool, const char* file, int line) {
+    const GuardKnob g = alloc_guard();
+    hipError_t e = pool ? hipMallocFromPoolAsync(p, bytes + 2 * g.band, g_pool[device], stream) : hipMalloc(p, bytes + 2 * g.band);
+    if (e != hipSuccess || g.band == 0) return e;
+    char* outer = (char*)*p;
+    char* inner = outer + g.band;
+    *p = inner;
+    if ((e = hipMemsetAsync(outer, g.byte, g.band, stream)) != hipSuccess || (e = hipMemsetAsync(inner + bytes, g.byte, g.band, stream)) != hipSuccess) {
+        if (pool) (void)hipFreeAsync(outer, stream); else (void)hipFree(outer);
+        *p = nullptr;
+        return e;
+    }
+    const char* base = strrchr(file, '/');
+    char tag[96];
+    std::lock_guard<std::mutex> lock(g_guard_mutex);
+    const int ordinal = g_guard_ordinal++;
+    snprintf(tag, sizeof tag, "%s:%d#%d", base ? base + 1 : file, line, ordinal);
+    guard_register(nullptr, stream, tag, 0, outer, g.band, inner, bytes, device, g.byte, ordinal);
+    guard_register(nullptr, stream, tag, 1, inner + bytes, g.band, inner, bytes, device, g.byte, ordinal);
+    return hipSuccess;
+}
+static void guarded_free(hipStream_t stream, void* p, bool pool) {
+    if (!p) return;
+    if (g_guard_count.load(std::memory_order_acquire) > 0) {           // (a block allocated with the knob unset is in no record)
+        void* outer = nullptr;
+        {
+            std::lock_guard<std::mutex> lock(g_guard_mutex);
+            for (const GuardRec& r : g_guard_live)
+                if (!r.owner && r.b.side == 0 && r.b.inner == (uint64_t)(uintptr_t)p) outer = (void*)(uintptr_t)r.b.address;
+        }
+        if (outer) {
+            (void)hipStreamSynchronize(stream);
+            guard_release([p](const GuardRec& r) { return !r.owner && r.b.inner == (uint64_t)(uintptr_t)p; });
+            p = outer;
+        }
+    }
+    if (pool) (void)hipFreeAsync(p, stream); else (void)hipFree(p);
+}
+static hipError_t dev_malloc(int device, hipStream_t stream, void** p, size_t bytes, const char* file = __builtin_FILE(), int line = __builtin_LINE()) {
     if (bytes == 0) bytes = 16;
-    const hipError_t e = async_alloc_ok(device) ? hipMallocFromPoolAsync(p, bytes, g_pool[device], stream) : hipMalloc(p, bytes);
+    const hipError_t e = guarded_alloc(device, stream, p, bytes, async_alloc_ok(device), file, line);
     return e != hipSuccess ? e : alloc_fill(*p, bytes, stream);
 }
 static void dev_free(int device, hipStream_t stream, void* p) {
     if (!p) return;
-    if (async_alloc_ok(device)) (void)hipFreeAsync(p, stream); else (void)hipFree(p);
+    guarded_free(stream, p, async_alloc_ok(device));
 }
 // pinned host mirrors of the scalar record are recycled, never freed (hipHostFree synchronises too)
 static std::mutex g_hsc_mutex;
@@ -358,6 +468,13 @@ struct Layout {
     int nblk, rc_chunks, rows_per_chunk, vblk;
     size_t off_A, off_B, off_inv, off_nvec, off_mvec, off_atp, off_part, off_det, off_sc, off_fixed, off_hist, off_snap, off_slab, total;
     size_t off_rowptr, off_colind, off_rval, off_colptr, off_rowind, off_cval, off_order;
+    // the regions in address order, and the guard band between them (IPM_TEST_ALLOC_GUARD; 0 when unset: the regions lie back to back)
+    struct Region { const char* name; size_t off, bytes; };
+    static const int MAX_REGIONS = 24;
+    Region reg[MAX_REGIONS];
+    int nreg;
+    size_t band;
+    int band_byte;
 };
 static const int N_NVEC = 11;   // x s c rc d v q dxa dsa dx ds
 static const int N_MVEC = 7;    // y b rb t1 t2 dya dy
@@ -366,7 +483,7 @@ static const int N_MVEC = 7;    // y b rb t1 t2 dya dy
 // small-LP size) -- B, inv(L_kk) and the split-K slab are not part of the workspace; ensure_dense_B allocates them if a
 // dense entry point (ipm_form_normal_matrix, ipm_get_factor, ipm_solve_linear) is ever called on such a handle.
 static bool layout_no_dense(int64_t m, int64_t sparse_nnz, unsigned flags) { return sparse_nnz > 0 && (flags & IPM_FLAG_SPARSE_FACTOR) && m > 128; }
-static Layout make_layout(int64_t m, int64_t n, int64_t sparse_nnz = 0, bool no_dense = false) {
+static Layout make_layout(int64_t m, int64_t n, int64_t sparse_nnz = 0, bool no_dense = false, const GuardKnob guard = alloc_guard()) {
     Layout L;
     L.mp = round_up(m, NB);
     {   // the grouped triangular solves (trsv_grouped.h) need whole 1024-row groups: pad a little further when that
@@ -384,29 +501,30 @@ static Layout make_layout(int64_t m, int64_t n, int64_t sparse_nnz = 0, bool no_
     int64_t mx = m > n ? m : n;
     int64_t vb = (mx + VBLK - 1) / VBLK;          // one element per thread until MAXPART blocks
     L.vblk = (int)(vb < 1 ? 1 : (vb > MAXPART ? MAXPART : vb));
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    L.band = guard.band; L.band_byte = guard.byte; L.nreg = 0;
+    size_t off = L.band;                          // a band before the first region, one behind every region
+    auto take = [&](const char* name, size_t bytes) { size_t o = off; L.reg[L.nreg++] = Layout::Region{name, o, bytes}; off += (bytes + 255) / 256 * 256 + L.band; return o; };
     if (sparse_nnz > 0) { L.rc_chunks = 1; L.rows_per_chunk = (int)L.mp; }
-    L.off_A = take(sparse_nnz > 0 ? 0 : sizeof(double) * L.mp * L.np);
-    L.off_B = take(no_dense ? 0 : sizeof(double) * L.mp * L.mp);
-    L.off_inv = take(no_dense ? 0 : sizeof(double) * L.nblk * NB * NB);
-    L.off_nvec = take(sizeof(double) * L.np * N_NVEC);
-    L.off_mvec = take(sizeof(double) * L.mp * N_MVEC);
-    L.off_atp = take(sizeof(double) * L.rc_chunks * L.np);
-    L.off_part = take(sizeof(double) * P_NSLOT_DETECT_QUAD * MAXPART);     // (the slots of the infeasibility tests included, a quadratic handle's two too)
-    L.off_det = take(sizeof(double) * 4);
-    L.off_sc = take(sizeof(Scalars));
-    L.off_fixed = take(256);
-    L.off_hist = take(sizeof(IterRec) * HIST_CAP);
-    L.off_snap = take(sizeof(double) * (2 * L.np + L.mp) + sizeof(Scalars));
-    L.off_slab = take(no_dense ? 0 : sizeof(double) * (size_t)kSlabTiles * 128 * 128);   // split-K partial tiles (64 MB)
-    L.off_order = take(sizeof(int) * ((size_t)L.nblk * (L.nblk + 1) / 2));
-    L.off_rowptr = take(sparse_nnz > 0 ? sizeof(int) * (m + 1) : 0);
-    L.off_colptr = take(sparse_nnz > 0 ? sizeof(int) * (n + 1) : 0);
-    L.off_colind = take(sparse_nnz > 0 ? sizeof(int) * sparse_nnz : 0);
-    L.off_rowind = take(sparse_nnz > 0 ? sizeof(int) * sparse_nnz : 0);
-    L.off_rval = take(sparse_nnz > 0 ? sizeof(double) * sparse_nnz : 0);
-    L.off_cval = take(sparse_nnz > 0 ? sizeof(double) * sparse_nnz : 0);
+    L.off_A = take("ws:A", sparse_nnz > 0 ? 0 : sizeof(double) * L.mp * L.np);
+    L.off_B = take("ws:B", no_dense ? 0 : sizeof(double) * L.mp * L.mp);
+    L.off_inv = take("ws:inv", no_dense ? 0 : sizeof(double) * L.nblk * NB * NB);
+    L.off_nvec = take("ws:nvec", sizeof(double) * L.np * N_NVEC);
+    L.off_mvec = take("ws:mvec", sizeof(double) * L.mp * N_MVEC);
+    L.off_atp = take("ws:atp", sizeof(double) * L.rc_chunks * L.np);
+    L.off_part = take("ws:part", sizeof(double) * P_NSLOT_DETECT_QUAD * MAXPART);     // (the slots of the infeasibility tests included, a quadratic handle's two too)
+    L.off_det = take("ws:det", sizeof(double) * 4);
+    L.off_sc = take("ws:sc", sizeof(Scalars));
+    L.off_fixed = take("ws:fixed", 256);
+    L.off_hist = take("ws:hist", sizeof(IterRec) * HIST_CAP);
+    L.off_snap = take("ws:snap", sizeof(double) * (2 * L.np + L.mp) + sizeof(Scalars));
+    L.off_slab = take("ws:slab", no_dense ? 0 : sizeof(double) * (size_t)kSlabTiles * 128 * 128);   // split-K partial tiles (64 MB)
+    L.off_order = take("ws:order", sizeof(int) * ((size_t)L.nblk * (L.nblk + 1) / 2));
+    L.off_rowptr = take("ws:rowptr", sparse_nnz > 0 ? sizeof(int) * (m + 1) : 0);
+    L.off_colptr = take("ws:colptr", sparse_nnz > 0 ? sizeof(int) * (n + 1) : 0);
+    L.off_colind = take("ws:colind", sparse_nnz > 0 ? sizeof(int) * sparse_nnz : 0);
+    L.off_rowind = take("ws:rowind", sparse_nnz > 0 ? sizeof(int) * sparse_nnz : 0);
+    L.off_rval = take("ws:rval", sparse_nnz > 0 ? sizeof(double) * sparse_nnz : 0);
+    L.off_cval = take("ws:cval", sparse_nnz > 0 ? sizeof(double) * sparse_nnz : 0);
     L.total = off;
     return L;
 }

@@ -9,11 +9,11 @@ struct LuRun {
     std::vector<void*> allocs;
     ~LuRun() {
         if (stream) (void)hipStreamSynchronize(stream);
-        for (void* p : allocs) (void)hipFree(p);
+        for (void* p : allocs) guarded_free(stream, p, /*pool=*/false);
         if (stream) (void)hipStreamDestroy(stream);
     }
-    int alloc(void** p, size_t bytes, const char* what) {
-        hipError_t e = hipMalloc(p, bytes);
+    int alloc(void** p, size_t bytes, const char* what, const char* file = __builtin_FILE(), int line = __builtin_LINE()) {
+        hipError_t e = guarded_alloc(device, stream, p, bytes, /*pool=*/false, file, line);      // test knob IPM_TEST_ALLOC_GUARD (host_handle.h)
         if (e != hipSuccess) {
             (void)hipGetLastError();
             return fail(nullptr, IPM_ERR_WORKSPACE, "lu: cannot allocate %zu bytes of device memory for %s: %s", bytes, what, hipGetErrorString(e));

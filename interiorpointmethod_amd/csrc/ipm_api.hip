@@ -104,9 +104,31 @@ extern "C" int ipm_workspace_bytes_opts(int64_t m, int64_t n, const ipm_options*
 }
 
 // ------------------------------------------------------------------------------- handle
+// Guard bands of the workspace (IPM_TEST_ALLOC_GUARD, host_handle.h): the band behind every region -- from the last byte the region
+// asked for to the next region, so the rounding to 256 is band too -- and the one before the first, filled on the handle's stream and
+// entered in the registry under the handle.
+static hipError_t guard_workspace(ipm_handle* h, const Layout& L) {
+    char* base = (char*)h->ws;
+    hipError_t e = hipMemsetAsync(base, L.band_byte, L.reg[0].off, h->stream);
+    for (int r = 0; r < L.nreg && e == hipSuccess; ++r) {
+        const size_t from = L.reg[r].off + L.reg[r].bytes, to = r + 1 < L.nreg ? L.reg[r + 1].off : L.total;
+        e = hipMemsetAsync(base + from, L.band_byte, to - from, h->stream);
+    }
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lock(g_guard_mutex);
+    const int ordinal = g_guard_ordinal++;
+    guard_register(h, h->stream, L.reg[0].name, 0, base, L.reg[0].off, base + L.reg[0].off, L.reg[0].bytes, h->device, L.band_byte, ordinal);
+    for (int r = 0; r < L.nreg; ++r) {
+        const size_t from = L.reg[r].off + L.reg[r].bytes, to = r + 1 < L.nreg ? L.reg[r + 1].off : L.total;
+        guard_register(h, h->stream, L.reg[r].name, 1, base + from, to - from, base + L.reg[r].off, L.reg[r].bytes, h->device, L.band_byte, ordinal);
+    }
+    h->guarded = true;
+    return hipSuccess;
+}
+
 // Every IPM_* switch ipm_create reads; what follows from them and the option flags (a flag overrides its switch) is decided in
 // ipm_create.  Read at their own stage: IPM_SP_* (build_sparse_factor), IPM_FF_PROF / IPM_FF_TRACE_ITEMS (ff_build), IPM_LU_NB, ff_schedule.h,
-// IPM_TEST_ALLOC_FILL (at every allocation: alloc_fill, host_handle.h).
+// IPM_TEST_ALLOC_FILL, IPM_TEST_ALLOC_GUARD (at every allocation and in every make_layout: alloc_fill, alloc_guard, host_handle.h).
 static void read_env_switches(ipm_handle* h) {
     if (const char* e = getenv("IPM_TEST_SPIN_LIMIT")) h->spin_limit = (unsigned)std::max(1, atoi(e));
     if (const char* e = getenv("IPM_ENVELOPE")) h->envelope = atoi(e);
@@ -246,6 +268,9 @@ extern "C" int ipm_create(int device, int64_t m, int64_t n, const ipm_options* o
     }
     // zero everything except A and B (padding entries of every vector must stay 0)
     CREATE_TRY(hipMemsetAsync(base + L.off_inv, 0, L.off_slab - L.off_inv, h->stream));
+    // test knob IPM_TEST_ALLOC_GUARD (host_handle.h): the bands are filled BEHIND that range memset, which runs across those between
+    // inv and slab, and behind every upload above (none reaches a band: each writes the bytes its region asked for)
+    if (L.band) CREATE_TRY(guard_workspace(h, L));
     {
         std::lock_guard<std::mutex> lock(g_hsc_mutex);
         if (!g_hsc_pool.empty()) { h->h_sc = g_hsc_pool.back(); g_hsc_pool.pop_back(); }
@@ -339,6 +364,10 @@ extern "C" int ipm_destroy(ipm_handle* h) {
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->h_sc) { std::lock_guard<std::mutex> lock(g_hsc_mutex); g_hsc_pool.push_back(h->h_sc); h->h_sc = nullptr; }
+    if (h->guarded) {                                          // every stream is idle: compare the workspace's bands, log the damage
+        const ipm_handle* self = h;
+        guard_release([self](const GuardRec& r) { return r.owner == self; });
+    }
     for (void* p : {(void*)h->stamp_buf, (void*)h->d_flags, (void*)h->d_bulk_done, (void*)h->B_own, (void*)h->invD_own, (void*)h->bnd_mem, (void*)h->quad_g, (void*)h->free_set.mark, (void*)h->free_lp_set.mark, (void*)h->mcc.mem, (void*)h->ref.mem, (void*)h->cert_mem, (void*)h->gXT, (void*)h->gX, (void*)h->gS, (void*)h->gPart})
         dev_free(h->device, h->stream, p);
     ff_release(h);
@@ -781,6 +810,69 @@ extern "C" int ipm_debug_compat(int32_t a, int32_t b, int32_t* excluded, int32_t
     const CompatRow* r = compat_row(a, b);
     if (excluded) *excluded = r != nullptr;
     if (lifted_by) *lifted_by = r ? r->lifted_by : -1;
+    return IPM_OK;
+}
+// The guard bands, read back (IPM_TEST_ALLOC_GUARD, host_handle.h; tests/test_alloc_guard_host.py, tests/test_gpu_alloc_guard.py).
+// A handle's bands: its workspace's and those of the pool blocks allocated on its stream.
+static std::vector<ipm_guard_band> guard_snapshot(const ipm_handle* h) {
+    std::vector<ipm_guard_band> v;
+    std::lock_guard<std::mutex> lock(g_guard_mutex);
+    for (const GuardRec& r : g_guard_live)
+        if (!h || r.owner == h || (!r.owner && r.stream == h->stream && r.b.device == h->device)) v.push_back(r.b);
+    std::sort(v.begin(), v.end(), [](const ipm_guard_band& a, const ipm_guard_band& b) { return a.ordinal != b.ordinal ? a.ordinal < b.ordinal : a.address < b.address; });
+    return v;
+}
+static int guard_copy_out(const std::vector<ipm_guard_band>& v, ipm_guard_band* out, int32_t capacity, int32_t* count) {
+    for (size_t i = 0; out && i < v.size() && (int64_t)i < capacity; ++i) out[i] = v[i];
+    *count = (int32_t)v.size();
+    return IPM_OK;
+}
+extern "C" int ipm_debug_guard_list(ipm_handle* h, ipm_guard_band* out, int32_t capacity, int32_t* count) {
+    if (!count || capacity < 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_debug_guard_list: bad arguments");
+    return guard_copy_out(guard_snapshot(h), out, capacity, count);
+}
+extern "C" int ipm_debug_guard_check(ipm_handle* h, ipm_guard_band* out, int32_t capacity, int32_t* count) {
+    if (!count || capacity < 0) return fail(h, IPM_ERR_INVALID_ARG, "ipm_debug_guard_check: bad arguments");
+    std::vector<ipm_guard_band> v = guard_snapshot(h), bad;
+    bool synced[MAX_DEVICES] = {};
+    for (ipm_guard_band& b : v) {
+        if (b.device >= 0 && b.device < MAX_DEVICES && !synced[b.device]) {      // every stream of the device: nothing is still writing
+            HIP_TRY(h, hipSetDevice(b.device));
+            HIP_TRY(h, hipDeviceSynchronize());
+            synced[b.device] = true;
+        }
+        guard_check_band(b);
+        if (b.bad_count != 0) bad.push_back(b);
+    }
+    return guard_copy_out(bad, out, capacity, count);
+}
+extern "C" int ipm_debug_guard_log(ipm_guard_band* out, int32_t capacity, int32_t* count) {
+    if (!count || capacity < 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_debug_guard_log: bad arguments");
+    std::vector<ipm_guard_band> v;
+    { std::lock_guard<std::mutex> lock(g_guard_mutex); v.swap(g_guard_log); }
+    return guard_copy_out(v, out, capacity, count);
+}
+extern "C" int ipm_debug_guard_layout(int64_t m, int64_t n, const ipm_options* opts, ipm_guard_band* out, int32_t capacity, int32_t* count,
+                                      uint64_t* total, uint64_t* band) {
+    if (!count || capacity < 0 || m <= 0 || n <= 0) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_debug_guard_layout: bad arguments");
+    const int64_t nnz = opts && opts->sparse_nnz > 0 ? opts->sparse_nnz : 0;
+    const Layout L = make_layout(m, n, nnz, layout_no_dense(m, nnz, opts ? opts->flags : 0u));
+    std::vector<ipm_guard_band> v((size_t)L.nreg);
+    for (int r = 0; r < L.nreg; ++r) {
+        ipm_guard_band& b = v[(size_t)r];
+        memset(&b, 0, sizeof b);
+        snprintf(b.tag, sizeof b.tag, "%s", L.reg[r].name);
+        const size_t from = L.reg[r].off + L.reg[r].bytes, to = r + 1 < L.nreg ? L.reg[r + 1].off : L.total;
+        b.address = b.inner = L.reg[r].off; b.inner_bytes = L.reg[r].bytes; b.bytes = L.band ? to - from : 0;
+        b.side = 1; b.device = -1; b.byte = L.band_byte; b.ordinal = r; b.first_bad = -1;
+    }
+    if (total) *total = L.total;
+    if (band) *band = L.band;
+    return guard_copy_out(v, out, capacity, count);
+}
+extern "C" int ipm_debug_guard_compare(const unsigned char* band, uint64_t bytes, int32_t byte, int64_t* first_bad, int64_t* bad_count) {
+    if (!band || !first_bad || !bad_count || byte < 0 || byte > 255) return fail(nullptr, IPM_ERR_INVALID_ARG, "ipm_debug_guard_compare: bad arguments");
+    guard_compare(band, (size_t)bytes, byte, first_bad, bad_count);
     return IPM_OK;
 }
 static int debug_step_kernel(const char* who, int32_t step, unsigned bits, char* name_out, int32_t capacity, int32_t* twin_type_out) {

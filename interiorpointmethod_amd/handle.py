@@ -519,6 +519,14 @@ class IpmSolver:
                 "live_handles", "timeouts_recovered", "fused_small", "fused_factor", "sparse_level_mode", "stream_at", "group_blocks")
         return dict(zip(keys, (int(v) for v in out)))
 
+    def guard_bands(self):
+        """The handle's live guard bands (test knob IPM_TEST_ALLOC_GUARD at construction; ipm_debug_guard_list): list of dicts."""
+        return _lib.guard_list(self._h)
+
+    def guard_check(self):
+        """The damaged ones among them, compared now (ipm_debug_guard_check); [] when every band is intact."""
+        return _lib.guard_check(self._h)
+
     def factor_info(self):
         """Structure of the sparse factor (ipm_get_factor_info) or None for the dense-tile path."""
         if self.factor != "sparse":
